@@ -6,27 +6,36 @@ implicit-GEMM and window-kernel convs with fused Detect tails, SPPF pool, head s
 frames that are already resident in HBM, the [B,4] track slices are all-gathered (N > 1 only), and the ResMLP movement
 vectors of the cycles that became computable are produced (wtracker_amd/pipeline.py).  Prints ONE JSON line on rank 0.
 
-  python bench.py --gpus 1 --steps 20 --warmup 3
+  python bench.py --gpus 1 --steps 20 --warmup 3                      # plain run: the headline alone
+  python bench.py --gpus 1 --steps 20 --warmup 3 --full               # + every other figure and check below
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W
 
+A plain run sets up, warms up, times EXACTLY `--steps` steps of the headline mode (one window; `--repeats R` asks for R windows),
+writes that mode's outputs of its last timed step with `--dump-outputs DIR` (DIR/xywh.npy, conf.npy, anchor.npy, moves.npy,
+move_valid.npy: float32, same seeded inputs in every run) and prints the line.  Everything marked [full] below is measured
+only with `--full`.
+
 What the line carries (everything measured inside this one command):
-  value / ms_per_step   the HEADLINE mode (`dtype`): with the default `--dtype auto` the fastest mode whose survivor indices equal
-                        the fp32 CPU restatement's on EVERY parity frame of this run — "hybrid" (fp16 on every frame + a
-                        full-precision second look at every weak decision, no row cut off: `hybrid_overflow` must be 0), else
-                        "f16x3", else "fp32"; the choice is made from the `parity` object measured in this very command (N = 1).
+  value / ms_per_step   the HEADLINE mode (`dtype`): a plain run with the default `--dtype auto` times the reference-precision mode
+                        "f16x3"; with `--full` it is the fastest reference-precision mode ("f16x3", else "fp32") whose survivor
+                        indices equal the fp32 CPU restatement's on EVERY parity frame of this run; the choice is made from the
+                        `parity` object measured in this very command (N = 1).
                         The reference computes in fp32 and keeps the arg-max anchor (yolo/yolo_train_config.yaml:51,
                         yolo_controller.py:76): a mode that picks another survivor on some frames is not the headline.
                         `--repeats` timed windows of EXACTLY `--steps` steps each, every window bracketed by barrier + device
                         synchronisation, MAX over ranks per window; value = frames of one window / MEDIAN window
-  roofline              dominant kernel of the headline mode, algorithmic FLOPs / live HIP-event launch time
+  headline_exactness_verified, headline_check
+                        [full] the parity gate and the device-side check of the headline mode (null in a plain run)
+  roofline              [full] dominant kernel of the headline mode, algorithmic FLOPs / live HIP-event launch time
   value_fp16 / value_hybrid / value_f16x3 / value_fp32, parity_index_match_<mode>, hybrid_overflow, hybrid_second_look_share
-                        flat copies of the per-mode numbers (N = 1 only)
-  fp16_throughput       the plain fp16 mode: labelled, NOT the headline (survivor index differs on ~2 % of the frames)     (N = 1 only)
-  hybrid / f16x3 / fp32 per-mode objects: value / windows / roofline                                                        (N = 1 only)
-  parity                survivor-index match rate and IoU distribution of ALL modes against the fp32 CPU restatement on
+                        flat copies of the per-mode numbers (a plain run: the headline mode's value only; the others [full], N = 1 only)
+  fp16_throughput       [full] the plain fp16 mode: labelled, NOT the headline (survivor index differs on ~2 % of the frames)  (N = 1 only)
+  hybrid / f16x3 / fp32 per-mode objects: value / windows / roofline; hybrid and fp32 [full]                              (N = 1 only)
+  parity                [full] survivor-index match rate and IoU distribution of ALL modes against the fp32 CPU restatement on
                         the CPU leg's frames, computed outside the timed regions                               (N = 1 only)
-  cpu_baseline          oracle/ (kind "port") timed on the host cores at B = 64, 15 and 1                      (N = 1 only)
+  cpu_baseline          [full] oracle/ (kind "port") timed on the host cores at B = 64, 15 and 1               (N = 1 only)
+  closed_loop, latency  [full] the reference's operating point and its small-batch calls                       (N = 1 only)
   dist                  N > 1: world size and backend as torch.distributed reports them + a checksum of the gathered track
 Fields that cannot be measured from inside the process (HBM bytes and MFMA-busy share come from rocprofv3 PMC passes) are
 read from profiles/*.json ONLY when that file was collected on exactly these kernel sources (`src_sha`), and then carry a
@@ -391,6 +400,19 @@ def latency_leg(weights, scale: str, nc: int, device: int, conf: float) -> dict:
     return {"what": latency_leg.__doc__.split("Per shape:")[0].strip().replace("\n", " "), "rows": rows}
 
 
+def step_outputs(pipe, s: int) -> dict:
+    """What step s of the timed path handed its caller, as float32 host arrays (call after a fence: every row is final).  `xywh`: the track rows
+    of the step's super-batch (NaN = no detection); `conf` / `anchor`: this rank's survivor confidence and anchor index (-1 = none); `moves` /
+    `move_valid`: the raw ResMLP (dx, dy) and validity of the cycles whose prediction frame lies in the super-batch."""
+    lanes = len(pipe.dets)
+    lane = s % lanes
+    k = (s // lanes) % max(int(getattr(pipe.dets[lane], "defer", 1)), 1)  # the lane's ring slot of step s (TrackPipeline._step_on_current_stream)
+    f0, f1 = pipe.plan.super_range(s)
+    lo, hi = pipe.plan.cycles(s)
+    arrays = {"xywh": pipe.track[f0:f1], "conf": pipe.local_conf[lane][k], "anchor": pipe.local_anchor[lane][k], "moves": pipe.moves[lo:hi], "move_valid": pipe.valid[lo:hi]}
+    return {name: a.float().cpu().numpy() for name, a in arrays.items()}
+
+
 class Workload:
     """One precision mode of the benched workload on this rank: `lanes` detector handles, the ResMLP, the pipeline."""
 
@@ -427,7 +449,10 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=10, help="timed windows of --steps steps each (median reported)")
+    ap.add_argument("--repeats", type=int, default=1, help="timed windows of --steps steps each (median reported); the default 1 times exactly --steps steps")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything besides the headline: the other precision modes, the hybrid "
+                    "calibration, the per-kernel roofline, headline_check, the CPU baseline with the parity of every mode, the closed-loop and latency legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the headline mode's last timed step computed to DIR/<name>.npy (float32)")
     ap.add_argument("--batch", type=int, default=64, help="frames per GPU per step (BASELINE config 3: 64)")
     ap.add_argument("--size", type=int, default=640)
     ap.add_argument("--dtype", default="auto", choices=["auto", "fp16", "fp32", "f16x3", "hybrid"],
@@ -545,6 +570,7 @@ def main():
                 s += 1
             fence(pipe)
             win.append(time.perf_counter() - t0)
+        outputs = step_outputs(pipe, s - 1) if args.dump_outputs and rank == 0 else None  # before the profile pass below reuses the buffers
         if world > 1:
             t = torch.tensor(win, dtype=torch.float64, device=dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)  # a window ends when the slowest rank is done
@@ -558,6 +584,8 @@ def main():
                               "peak": PEAK_TFLOPS[dtype], "frac": frames_per_window / world * gflop_frame / med / 1e3 / PEAK_TFLOPS[dtype]},
                "windows": {"n": repeats, "steps_each": args.steps, "median_ms": med * 1e3, "min_ms": min(win) * 1e3, "max_ms": max(win) * 1e3,
                            "first_ms": win[0] * 1e3, "value_best": frames_per_window / min(win), "value_worst": frames_per_window / max(win)}}
+        if outputs is not None:
+            res["outputs"] = outputs
         if profile:
             # per-kernel device time with HIP events on the launch stream: one stream, one event pair around every run of launches
             # of the same kernel (wtk_yolo_get_kernel_profile); lane 0's handle is the profiled one
@@ -644,10 +672,11 @@ def main():
                 "kernels": lines, "class_ms_per_step": {k: v["total_ms"] / prof_steps for k, v in prof.items()},
                 "provenance": prov or None}
 
-    profile = not args.no_profile
+    # A plain run measures the headline mode and nothing else; --full adds every other figure and check of the line
+    profile = args.full and not args.no_profile
     modes: dict = {}
     calibration = None
-    want_hybrid = args.dtype == "hybrid" or (args.dtype == "auto" and world == 1 and not args.no_fp32 and not args.no_hybrid)
+    want_hybrid = args.dtype == "hybrid" or (args.full and args.dtype == "auto" and world == 1 and not args.no_fp32 and not args.no_hybrid)
     if args.hybrid_margin <= 0.0:
         if want_hybrid:
             from wtracker_amd.hybrid import HybridDetector
@@ -683,7 +712,7 @@ def main():
     # the mode measured first, with all windows: the requested one, else the first reference-precision candidate (the SAME mode at every N)
     first_dtype = args.dtype if args.dtype != "auto" else HEADLINE_CANDIDATES[0]
     modes[first_dtype] = measure(first_dtype, args.lanes, args.repeats, profile)
-    if world == 1 and not args.no_fp32:
+    if args.full and world == 1 and not args.no_fp32:
         # every other mode of the same workload, in the same command (fewer windows where a window is long)
         for dt, rep in (("f16x3", max(min(args.repeats, 5), 1)), ("fp16", args.repeats), ("hybrid", max(min(args.repeats, 5), 1)), ("fp32", max(min(args.repeats, 3), 1))):
             if dt not in modes and (dt != "hybrid" or want_hybrid):
@@ -724,7 +753,7 @@ def main():
 
     par = None
     cpu_obj = None
-    if world == 1 and args.cpu_frames > 0:
+    if args.full and world == 1 and args.cpu_frames > 0:
         # ---- CPU baseline (oracle, kind 'port') + parity of every mode against it on the same frames, outside any timed region
         n = max(args.cpu_frames // 64, 1) * 64
         sample = fr.diverse_frames(n, args.size, seed=2000)
@@ -784,21 +813,31 @@ def main():
         head_reason = f"fastest reference-precision mode with parity.index_match_rate == 1.0 and iou_matched.min >= {HEADLINE_IOU_MIN} on this run's parity frames"
         if head_dtype is None:  # no CPU parity leg in this run (N > 1, --cpu-frames 0) or no candidate passed it: the first candidate, and say what was verified
             head_dtype = first_dtype
-            head_reason = ("no CPU parity leg in this run (N > 1 or --cpu-frames 0): the reference-precision mode f16x3; see headline_check for the device-side evidence"
-                           if par is None else "NO candidate passed the parity gate of this run: f16x3 reported, exactness NOT established")
+            if not args.full:
+                head_reason = "plain run: the reference-precision mode f16x3, whose exactness a --full run checks (parity, headline_check)"
+            elif par is None:
+                head_reason = "no CPU parity leg in this run (N > 1 or --cpu-frames 0): the reference-precision mode f16x3; see headline_check for the device-side evidence"
+            else:
+                head_reason = "NO candidate passed the parity gate of this run: f16x3 reported, exactness NOT established"
     head = modes[head_dtype]
-    head_check = device_check(head_dtype) if head_dtype in ("f16x3", "hybrid", "fp16") and not args.no_check else None
+    head_check = device_check(head_dtype) if args.full and head_dtype in ("f16x3", "hybrid", "fp16") and not args.no_check else None
     if par is not None and head_dtype in par:
         verified = exact(head_dtype) and (head_check is None or head_check["verified"])
+    elif not args.full and head_dtype != "fp32":  # plain run: nothing was checked (null, not false)
+        verified = None
     else:  # no CPU leg: the device-side check alone (fp32 IS the reference's arithmetic; --no-check: nothing was verified)
         verified = bool(head_check and head_check["verified"]) if head_dtype != "fp32" else True
+    if head.get("outputs") is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in head["outputs"].items():
+            np.save(os.path.join(args.dump_outputs, f"{name}.npy"), a)
 
     # The two small-batch legs run in THIS process since round 6 (round 5 needed a child process: its replayed captures forked into side streams and ran 2-4 x slower
     # here, where eight hardware queues are requested and a dozen handles have come and gone).  Handles of <= 16 frames now run on the caller's stream alone, eagerly:
     # same device times in either process (0.512 / 0.510 ms single frame, 1.132 / 1.134 ms cycle batch; profiles/r06_notes.md section 4); --legs-subprocess is the A/B.
     closed = lat = None
-    want_closed = world == 1 and not args.no_closed_loop and not args.no_fp32
-    want_lat = world == 1 and not args.no_latency and not args.no_fp32 and args.size == 640
+    want_closed = args.full and world == 1 and not args.no_closed_loop and not args.no_fp32
+    want_lat = args.full and world == 1 and not args.no_latency and not args.no_fp32 and args.size == 640
     if (want_closed or want_lat) and not args.legs_subprocess:
         if want_closed:
             closed = closed_loop(weights, "s", 1, local_rank, args.conf)

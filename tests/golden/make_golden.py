@@ -324,7 +324,7 @@ def main_r2():
 def dropin_check(verbose: bool = True) -> dict:
     """Run the reference's own driver objects (Simulator.run + LoggingController) twice per controller kind — once around the
     reference's controller, once around the product's — on the seeded track, and compare the bboxes.csv files byte for byte.
-    Importable: tests/test_dropin_reference.py calls it when /root/reference is present."""
+    main_r3 (`--r3`) runs it and writes the fixture only when every log is byte-equal."""
     _register_placeholders()
     if REF not in sys.path:
         sys.path.insert(0, REF)

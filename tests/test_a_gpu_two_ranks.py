@@ -39,7 +39,7 @@ def test_bench_n_gt_1_branch_with_two_gloo_ranks(hip_lib):
         env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
         env.pop("GPU_MAX_HW_QUEUES", None)  # the ranks share one device: the runtime default
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--backend", "gloo", "--steps", str(steps), "--warmup", "1", "--repeats", "1",
-               "--no-fp32", "--cpu-frames", "0", "--pool", "64"]
+               "--full", "--no-fp32", "--cpu-frames", "0", "--pool", "64"]
         procs.append(subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = []
     for p in procs:

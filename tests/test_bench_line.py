@@ -96,3 +96,39 @@ def test_line_stays_under_the_limit_when_optional_parts_grow(tmp_path, monkeypat
     assert len(s) < 4096
     line = json.loads(s)
     assert all(k in line for k in CONTRACT) and line["roofline"] and line["cpu_baseline"]
+
+
+@pytest.mark.parametrize("lanes", [1, 2, 3])
+@pytest.mark.parametrize("defer", [1, 2, 5])
+def test_dumped_outputs_are_the_last_steps(lanes, defer):
+    """`bench.py --dump-outputs`: bench.step_outputs hands back the rows, survivors and movement vectors of exactly the step it is asked for, from
+    the lane and ring slot that step ran on (CPU pipeline with the stand-in detectors of test_pipeline_schedule.py, which also write conf / anchor)."""
+    import numpy as np
+    import torch
+
+    import bench
+    from test_pipeline_schedule import CopyPredictor, HoldBackDetector, _Folded, _frames
+    from wtracker_amd.pipeline import TrackPipeline
+
+    class Detector(HoldBackDetector):
+        def predict(self, frames_dev, B, H, W, C, out_xywh, out_conf=None, out_anchor=None, **kw):
+            ids = frames_dev.reshape(B, -1)[:, 0].to(torch.float32) + 256.0 * frames_dev.reshape(B, -1)[:, 1].to(torch.float32)
+            out_conf.copy_(ids)
+            out_anchor.copy_(ids.to(torch.int32))
+            super().predict(frames_dev, B, H, W, C, out_xywh, **kw)
+
+    B, steps = 32, 11
+    pipe = TrackPipeline([Detector(defer) for _ in range(lanes)], CopyPredictor(), _Folded(), B, steps * B, imaging_frame_num=6, pred_frame_num=3,
+                         cycle_frame_num=9, device=torch.device("cpu"))
+    for s in range(steps):
+        pipe.step(s, _frames(s * B, B))
+    pipe.synchronize()
+    out = bench.step_outputs(pipe, steps - 1)
+    ids = np.arange((steps - 1) * B, steps * B, dtype=np.float32)
+    assert sorted(out) == ["anchor", "conf", "move_valid", "moves", "xywh"] and all(a.dtype == np.float32 for a in out.values())
+    np.testing.assert_array_equal(out["conf"], ids)
+    np.testing.assert_array_equal(out["anchor"], ids)
+    np.testing.assert_array_equal(out["xywh"], np.stack([ids, 2 * ids, np.full_like(ids, 3), np.full_like(ids, 4)], axis=1))
+    lo, hi = pipe.plan.cycles(steps - 1)
+    assert hi > lo and out["moves"].shape == (hi - lo, 2) and (out["move_valid"] == 1).all()
+    np.testing.assert_array_equal(out["moves"], pipe.moves[lo:hi].numpy())

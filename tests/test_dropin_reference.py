@@ -8,7 +8,9 @@ and the bboxes.csv files compared byte for byte with the ones the reference's ow
   test_fixture_*           what the fixture records
   test_harness_logs_*      ties the fixture to the code of THIS checkout: the same product controllers, driven by the repo's own
                            harness (wtracker_amd.sim.Simulator + TrackLogger), write a file whose sha256 is the reference log's
-  test_live_*              where /root/reference exists (the build container, never the GPU box) the comparison is run again, live
+
+The live comparison inside the reference's driver needs the reference itself and runs where the fixture is written
+(`make_golden.py --r3` refuses to write it unless every log is byte-equal).
 """
 import hashlib
 import json
@@ -51,16 +53,3 @@ def test_harness_logs_hash_to_the_reference_logs(golden_dir, tmp_path, kind, tim
     got = hashlib.sha256(open(path, "rb").read()).hexdigest()
     assert got == _fixture(golden_dir)["controllers"][f"{kind}_{timing[0]}ms"]["reference_sha256"]
 
-
-@pytest.mark.skipif(not os.path.isdir("/root/reference/wtracker"), reason="the reference only exists in the build container")
-def test_live_product_controllers_inside_the_reference_driver(golden_dir):
-    import importlib.util
-
-    spec = importlib.util.spec_from_file_location("make_golden", os.path.join(golden_dir, "make_golden.py"))
-    mg = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mg)
-    out = mg.dropin_check(verbose=False)
-    fx = _fixture(golden_dir)
-    for name, c in out["controllers"].items():
-        assert c["byte_equal"], name
-        assert c["reference_sha256"] == fx["controllers"][name]["reference_sha256"], name
