@@ -143,9 +143,7 @@ void wtk_yolo_destroy(wtk_yolo *h);
  *                        environment variable WTK_LATENCY_PLAN=0 / 1 overrides AUTO only.
  * The first eager call of a latency-plan handle at a batch size also TIMES its launch choices (every grouped launch's tile / form candidates, inside the real
  * forward pass: ~0.1 s once; WTK_SK_AUTOTUNE=0 keeps the cost model's); the choice changes no result bit.
- * Launches are eager.  Replaying a captured hipGraph of the forward pass is opt-in (environment WTK_GRAPH=1, read when the handle is created): the
- * throughput plan's capture forks into the library's side streams, and the runtime's handling of such graphs is where round 5's two open problems
- * lived (profiles/r06_notes.md section 1).
+ * Launches are eager.
  * The plan never changes per call: within a handle a frame's logits do not depend on the batch it arrives in.  Both plans meet the
  * same tolerances against the fp32 restatement; they are not bit-identical to each other (K is summed in a different order). */
 typedef enum wtk_plan { WTK_PLAN_AUTO = 0, WTK_PLAN_THROUGHPUT = 1, WTK_PLAN_LATENCY = 2 } wtk_plan;

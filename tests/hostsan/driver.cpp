@@ -2,8 +2,8 @@
 // hip_stub.cpp instead of the HIP runtime — over the shape matrix of the GPU suite: model scales n / s / m, network sizes 96 x 160 ... 1280 x 1280,
 // batches 1 ... 64, every dtype, both launch plans, nc 1 / 32 / 80, every entry point a controller or a test calls, handles created and destroyed out of
 // phase.  No kernel runs; what is exercised is planning, weight packing, every launcher's geometry, the allocation sizes against the extents the kernels
-// will address (launch_checks.inc), and the stream / event / graph-capture lifetime protocol (hip_stub.cpp).  Exit code 0 = no sanitizer report and no
-// protocol violation.
+// will address (launch_checks.inc), and the stream / event lifetime protocol (hip_stub.cpp, which also models the captures a caller may open).  Exit
+// code 0 = no sanitizer report and no protocol violation.
 #include "../../include/wtk_hip.h"
 
 #include <cmath>
@@ -132,7 +132,7 @@ static void exercise(wtk_yolo *h, int H, int W, int max_batch, bool small, void 
     for (size_t i = 0; i < host.size(); i += 97) host[i] = (uint8_t)rng.next();
     std::vector<float> xywh((size_t)max_batch * 4), conf(max_batch);
     std::vector<int32_t> anchor(max_batch);
-    // host entry point: first call of the handle (staging allocation, host stream, capture on latency-plan handles), same arguments again (replay), other batches
+    // host entry point: first call of the handle (staging allocation, host stream), same arguments again, other batches
     for (int rep = 0; rep < 2; ++rep)
         for (int B : Bs) {
             CHECK(wtk_yolo_predict_host(h, host.data(), B, H, W, 1, 0.1f, 0.7f, 1, xywh.data(), conf.data(), anchor.data()) == 0, "predict_host gray B%d", B);
@@ -143,13 +143,13 @@ static void exercise(wtk_yolo *h, int H, int W, int max_batch, bool small, void 
         CHECK(wtk_yolo_predict_host(h, host.data(), Bs[1], H - 24, W - 8, 1, 0.25f, 0.7f, 1, xywh.data(), conf.data(), anchor.data()) == 0, "predict_host letterbox");
         CHECK(wtk_yolo_predict_host(h, host.data(), 1, H / 2, W - 8, 3, 0.25f, 0.7f, 1, xywh.data(), conf.data(), anchor.data()) == 0, "predict_host letterbox 2");
     }
-    // a larger frame than the staging buffer was sized for: re-allocation under live graphs
+    // a larger frame than the staging buffer was sized for: re-allocation
     {
         std::vector<uint8_t> big((size_t)(H + 40) * (W + 56) * 3);
         CHECK(wtk_yolo_predict_host(h, big.data(), 1, H + 40, W + 56, 3, 0.1f, 0.7f, 1, xywh.data(), conf.data(), anchor.data()) == 0, "predict_host larger frame");
         CHECK(wtk_yolo_predict_host(h, host.data(), 1, H, W, 1, 0.1f, 0.7f, 1, xywh.data(), conf.data(), anchor.data()) == 0, "predict_host after re-allocation");
     }
-    // caller-owned device buffers on the caller's stream: met once (eager), met again (captured on latency-plan handles), replayed
+    // caller-owned device buffers on the caller's stream, the same argument sets again and again
     DevBufs d;
     const int F = max_batch + 2, FH = H + 32, FW = W + 48; // full frames for the views entry point
     d.alloc((size_t)F * FH * FW, max_batch, 5);
@@ -163,7 +163,7 @@ static void exercise(wtk_yolo *h, int H, int W, int max_batch, bool small, void 
         }
     CHECK(wtk_yolo_predict_views(h, (const uint8_t *)d.frames, F, FH, FW, 1, nullptr, (const int32_t *)d.pos, 1, W, H, 0.1f, 0.7f, 1, (float *)d.xywh, nullptr, nullptr, user_stream) == 0, "predict_views no index");
     CHECK(wtk_yolo_predict_nms(h, (const uint8_t *)d.frames, Bs[1], H, W, 1, 0.1f, 0.7f, 5, (float *)d.xywh, (float *)d.conf, (int32_t *)d.cls, (int32_t *)d.anchor, (int32_t *)d.count, user_stream) == 0, "predict_nms");
-    // stream layout changes drop the captured launches
+    // stream layout changes between calls
     for (int n : {1, 0, 2}) {
         CHECK(wtk_yolo_set_side_streams(h, n) == 0, "set_side_streams %d", n);
         for (int rep = 0; rep < 2; ++rep) CHECK(wtk_yolo_predict(h, (const uint8_t *)d.frames, 1, H, W, 1, 0.1f, 0.7f, 1, (float *)d.xywh, (float *)d.conf, (int32_t *)d.anchor, user_stream) == 0, "predict side %d", n);
@@ -366,7 +366,7 @@ static void schedule_shape() {
     d.release();
 }
 
-// two host threads, a handle each, both capturing through the process-wide pair of side streams (ctypes releases the GIL: TrackPipeline lanes)
+// two host threads, a handle each, both enqueueing at the same time (ctypes releases the GIL: TrackPipeline lanes)
 static void two_threads() {
     std::fprintf(stderr, "[hostsan] two host threads\n");
     const Model m = make_model(kScales[1], 1, 5);
@@ -502,7 +502,7 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "[hostsan] kernels launched: %llu (conv_sk %llu, window %llu, igemm %llu, front %llu, head %llu); peak device memory %.1f GB; violations %d; driver failures %d\n",
                  stub_kernel_launches(nullptr), stub_kernel_launches("conv_sk_kernel"), stub_kernel_launches("conv3x3_halo"), stub_kernel_launches("conv_igemm_kernel"),
                  stub_kernel_launches("front_fused"), stub_kernel_launches("head_"), (double)stub_peak_device_bytes() / 1e9, v, g_fail);
-    // everything the handles took must be back: events and graph execs destroyed, no capture left open, only the process-wide status page and nothing else alive
+    // everything the handles took must be back: events destroyed, no graph exec or capture left behind, only the process-wide status page and nothing else alive
     CHECK(stub_live_events() == 0, "%d events leaked", stub_live_events());
     CHECK(stub_live_execs() == 0, "%d graph execs leaked", stub_live_execs());
     CHECK(stub_open_captures() == 0, "%d captures left open", stub_open_captures());

@@ -44,6 +44,23 @@ def test_binding_argument_counts_match_the_header(hip_lib):
         assert (0 if at is None else len(at)) == n, (name, n, at)
 
 
+def test_every_environment_switch_is_documented():
+    """Every WTK_* variable the library reads has a row in README's "Environment switches" table; the retired ones are gone from both."""
+    csrc = os.path.join(ROOT, "wtracker_amd", "csrc")
+    src = "".join(open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h")))
+    read = set(re.findall(r"\b(?:getenv|env_int)\(\s*\"(WTK_[A-Z0-9_]+)\"", src))
+    assert {"WTK_LATENCY_PLAN", "WTK_NO_SK_MIXED", "WTK_SMALL_NARROW", "WTK_SEGV_BACKTRACE"} <= read, read
+    readme = open(os.path.join(ROOT, "README.md")).read()
+    table = readme.split("## Environment switches", 1)[1].split("\n## ", 1)[0]
+    documented = set(re.findall(r"`(WTK_[A-Z0-9_]+)", table))
+    assert read <= documented, sorted(read - documented)
+    retired = ("GRAPH", "GRAPH_HOST", "GRAPH_VIEWS", "GRAPH_MAX_BATCH", "SK_MIXED_MAX_PX", "SK_PLAN_ATOMS", "SK_SINGLE_MAX", "SK_SLICE_STEPS",
+               "SK_INKERNEL_MAX_KB", "SK_VERBOSE")
+    for name in ("WTK_" + r for r in retired):
+        assert not re.search(r"\b%s\b" % name, src), name
+        assert not re.search(r"\b%s\b" % name, readme), name
+
+
 @pytest.mark.parametrize("scale,nc", [("n", 1), ("s", 1), ("s", 80), ("m", 3)])
 def test_conv_table_matches_python_spec(hip_lib, scale, nc):
     w, d, m = ys.scale_params(scale)

@@ -1,6 +1,5 @@
 #!/usr/bin/env python3
-"""Latency of the controller-style host entry point (wtk_yolo_predict_host) for small batches, with and
-without hipGraph replay (WTK_GRAPH_MAX_BATCH=0 disables)."""
+"""Latency of the controller-style host entry point (wtk_yolo_predict_host) for small batches."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -20,5 +19,5 @@ for dtype in dtypes:
         for _ in range(n):
             det.predict_host(f[:B])
         dt = (time.perf_counter() - t) / n
-        print(f"{dtype} size {size} B={B}: {dt*1e3:.3f} ms/call  ({B/dt:.0f} frames/s)  graph_max={os.environ.get('WTK_GRAPH_MAX_BATCH','16')}", flush=True)
+        print(f"{dtype} size {size} B={B}: {dt*1e3:.3f} ms/call  ({B/dt:.0f} frames/s)", flush=True)
     det.close()

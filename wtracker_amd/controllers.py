@@ -318,7 +318,7 @@ class YoloConfig:
     max_batch: int = 64
     # launch plan of the detector handles (include/wtk_hip.h: wtk_yolo_create_planned).  The reference calls the detector twice per cycle: one single frame
     # (provide_movement_vector, yolo_controller.py:96-98) and one cycle batch of 9 / 15 frames (_cycle_predict_all, :108-109).  "auto": calls of up to
-    # LATENCY_MAX_BATCH frames go to a handle on the latency plan (split-K convs, replayed captures: 0.53 ms instead of 1.0 ms for the single frame), larger
+    # LATENCY_MAX_BATCH frames go to a handle on the latency plan (split-K convs, grouped launches: 0.51 ms instead of 1.0 ms for the single frame), larger
     # ones to a throughput-plan handle (1.2 ms instead of 1.5 ms for 15 frames): each call on the plan that is faster for it; the two handles agree within
     # the tolerance both meet against the fp32 restatement, not bit for bit.  "latency": every call up to 16 frames on ONE latency-plan handle — a frame's
     # result is then bit-identical whichever of the two calls sees it; "throughput": every call on the large-batch kernels.  fp16: always throughput.
@@ -498,9 +498,7 @@ class HipYoloController(SimController):
         det = self._model.detector(net_hw, n)
         dev = fr.device
         # One set of device buffers per (lane, batch size), kept for the controller's life: the view table (frame numbers + positions, one small upload
-        # per call from pinned memory) and the output rows.  The library replays a captured forward pass for a call that comes back with the same
-        # device addresses (wtk_yolo_predict_views: the reference's operating point — one cycle batch and one single-frame call per cycle — is
-        # launch bound), which needs a stream of the controller's own: the legacy default stream cannot be captured.
+        # per call from pinned memory) and the output rows.  Each lane's calls run on a stream of the controller's own.
         stream = self._view_streams.get(lane)
         if stream is None:
             # (a high-priority stream for lane 0 — the call the loop waits for — changes nothing once the handles run on one stream each: deferred log 11.19 k

@@ -42,8 +42,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -455,33 +453,19 @@ template <bool SPLIT, int BM, int BN, int WAVES_P, int WAVES_C, int NS> hipError
 } // namespace
 
 // Default K atoms of a layer with nk steps of 32 channels: a function of the layer alone (see the header: batch invariance; conv_sk_plan_atoms refines it per handle)
-// nk <= sk_single_max(): one block walks the whole K through the ring (no slabs, no hand-off); above it slices of ~sk_slice_steps() steps, at most 8
-// slices (the combining block reads all slabs in ONE round trip).  WTK_SK_SINGLE_MAX / WTK_SK_SLICE_STEPS: tuning switches, read once per process.
-static int sk_env(const char *name, int dflt) {
-    const char *e = std::getenv(name);
-    return e && e[0] ? std::atoi(e) : dflt;
-}
-static int sk_single_max() {
-    static const int v = sk_env("WTK_SK_SINGLE_MAX", 12);
-    return v;
-}
-static int sk_slice_steps() {
-    static const int v = sk_env("WTK_SK_SLICE_STEPS", 8);
-    return v > 0 ? v : 8;
-}
+// nk <= kSkSingleMax: one block walks the whole K through the ring (no slabs, no hand-off); above it slices of ~kSkSliceSteps steps, at most 8
+// slices (the combining block reads all slabs in ONE round trip).
+constexpr int kSkSingleMax = 12, kSkSliceSteps = 8;
 int conv_sk_slices(int nk) {
-    if (nk <= sk_single_max()) return 1;
-    const int s = (nk + sk_slice_steps() - 1) / sk_slice_steps();
+    if (nk <= kSkSingleMax) return 1;
+    const int s = (nk + kSkSliceSteps - 1) / kSkSliceSteps;
     return s < 2 ? 2 : (s > 8 ? 8 : s);
 }
 
 // Form and tile of one launch.  A small cost model in microseconds, calibrated on profiles/r05_notes.md's forced-tile timelines: blocks run one per
 // CU (96-128 KB of LDS) in rounds; a block costs a fixed latency chain, its operand bytes at what a CU's memory path delivers, and — split
 // form — the hand-off (write-through slabs, ticket, slab reads) or the second launch.
-static long long sk_inkernel_max() {
-    static const long long v = (long long)sk_env("WTK_SK_INKERNEL_MAX_KB", 4096) * 1024;
-    return v;
-}
+constexpr long long kSkInKernelMax = 4096LL * 1024; // slab bytes above which the slabs are combined by a second launch
 struct SkShape { // what the cost model needs to know of one conv
     long long M;
     int cout_pad, nk, NA;
@@ -505,7 +489,7 @@ static void sk_member_cost(const SkShape &c, const SkTile &t, int S, int split, 
     if (S > 1) {
         const double slab_bytes = (double)S * c.M * c.cout_pad * 4.0;
         const double tile_kb = t.bm * t.bn * 4.0 / 1024.0;
-        *handoff_us = slab_bytes <= (double)sk_inkernel_max() ? 4.0 + S * tile_kb / 60.0 : 3.0 + slab_bytes / 5.0e6;
+        *handoff_us = slab_bytes <= (double)kSkInKernelMax ? 4.0 + S * tile_kb / 60.0 : 3.0 + slab_bytes / 5.0e6;
     }
 }
 // list scheduling of a grouped launch: member i contributes b[i] blocks of u[i] microseconds each, dispatched in member order, one block per CU at a time
@@ -654,7 +638,7 @@ static hipError_t sk_launch_chosen(SkGroupArgs &g, const SkMember *m, int n, int
     for (int i = 0; i < n; ++i) {
         SkArgs &k = g.p[i];
         k.S = S[i];
-        k.tickets = (k.S > 1 && (long long)k.S * k.M * k.CoutPad * 4 <= sk_inkernel_max()) ? m[i].tickets : nullptr;
+        k.tickets = (k.S > 1 && (long long)k.S * k.M * k.CoutPad * 4 <= kSkInKernelMax) ? m[i].tickets : nullptr;
     }
     for (int i = n; i < kSkGroupMax; ++i) std::memset(&g.p[i], 0, sizeof(SkArgs));
     hipError_t e;
@@ -708,11 +692,6 @@ hipError_t launch_conv_sk_group(const SkMember *m, int n, int split, int num_cus
                 if (shapes[i].M > 16384) ch.separate = 1;
         }
         ch.valid = 1;
-        static const int verbose = sk_env("WTK_SK_VERBOSE", 0);
-        if (verbose)
-            for (int i = 0; i < n; ++i)
-                std::fprintf(stderr, "conv_sk%s: M %lld cout %d nk %d atoms %d -> tile %d form S=%d (launch est %.1f us%s)\n", n > 1 ? " (grouped)" : "", g.p[i].M, g.p[i].CoutPad,
-                             g.p[i].nk, g.p[i].NA, ch.separate ? ch.m_tile[i] : ch.tile, ch.separate ? ch.m_S[i] : ch.S[i], ch.est_us, ch.separate ? ", launched one by one" : "");
     }
     if (n > 1 && ch.separate) {
         for (int i = 0; i < n; ++i) {

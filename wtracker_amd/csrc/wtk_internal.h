@@ -2,7 +2,7 @@
 //   wtk_api.hip     errors, versions, ResMLP / track / recheck / crop entry points
 //   wtk_plan.hip    the detector handle: model table, weight packing, graph planning (channel-slice views), launch schedule of the latency plan,
 //                   stream pool, status page, create / destroy
-//   wtk_run.hip     one forward pass: enqueue, opt-in graph replay, the predict entry points, test hooks
+//   wtk_run.hip     one forward pass: enqueue, the predict entry points, test hooks
 //   wtk_hybrid.hip  the look-twice detector composed from the entry points above
 // Kernel-side declarations live in wtk_kernels.h.
 #pragma once
@@ -198,29 +198,7 @@ struct wtk_yolo {
     hipEvent_t feat_ev[2] = {nullptr, nullptr}, side_done[kSideStreams] = {};
     int use_side = 1;
     int side_streams = 2;
-    // launch-bound regime (small batches): the whole forward is captured once per argument set and replayed
-    struct GraphEntry {
-        const void *frames;
-        int B, H, W, C;
-        float conf;
-        void *o_xywh, *o_conf, *o_anchor;
-        hipGraphExec_t exec;
-        hipEvent_t done = nullptr; // recorded behind every replay: waited for before the exec is destroyed (a replay may still be in flight; the handle's OWN event, because
-                                   // the stream of the last replay is the caller's and may be gone by then)
-        // views form (wtk_yolo_predict_views): the view table's device addresses and the view shape are part of the key
-        const void *idx = nullptr, *pos = nullptr;
-        int vw = 0, vh = 0, nf = 0;
-        bool same_args(const GraphEntry &o) const {
-            return frames == o.frames && B == o.B && H == o.H && W == o.W && C == o.C && conf == o.conf && o_xywh == o.o_xywh && o_conf == o.o_conf &&
-                   o_anchor == o.o_anchor && idx == o.idx && pos == o.pos && vw == o.vw && vh == o.vh && nf == o.nf;
-        }
-    };
-    std::vector<GraphEntry> graphs;
-    std::vector<GraphEntry> seen_once; // caller-buffer argument sets met once (exec == nullptr): captured when they come back
-    int graph_max_batch = 16; // WTK_GRAPH_MAX_BATCH; 0 disables
-    int graph_host = 0;       // WTK_GRAPH=1 / WTK_GRAPH_HOST=1: the *_host entry points replay captures (own staging buffers)
-    int graph_views = 0;      // WTK_GRAPH=1 / WTK_GRAPH_VIEWS=1: caller-buffer argument sets are captured when they come back, then replayed
-    hipStream_t host_stream = nullptr; // stream of the *_host entry points (graph capture needs a non-null stream)
+    hipStream_t host_stream = nullptr; // pooled stream of the *_host entry points (taken at the first host call)
     int ev_created = 0;
     double prof_ms[kProfKernels] = {};
     double prof_flops[kProfKernels] = {};
@@ -228,10 +206,7 @@ struct wtk_yolo {
 };
 
 namespace wtk {
-// stream pool and its protocol checks (wtk_plan.hip)
-int stream_idle(hipStream_t s, const char *what);
+// stream pool (wtk_plan.hip)
 int pooled_stream(int device, hipStream_t *s);
 void unpool_stream(int device, hipStream_t s);
-// captured launches of a handle (wtk_run.hip)
-void drop_graphs(wtk_yolo *h);
 }

@@ -109,17 +109,10 @@ extern "C" int wtk_yolo_conv_info(float width_mult, float depth_mult, int32_t ma
 // queues when the stream is created, and after handles have come and gone the streams of a NEW handle can land on the queue of the
 // caller's stream — the towers then run behind the PAN path instead of next to it (the whole benefit of the side streams, 14 %, was
 // lost for the fourth workload of bench.py).  Reused streams keep the queues they got when the process was young.
-// Lifetime protocol (round 6; tests/hostsan models it): a stream enters the pool only after it has drained (hipStreamSynchronize) and is handed
-// out only when hipStreamIsCapturing says "none" — a stream that was the origin or a fork of a capture can never carry a capture state, or work
-// of a destroyed handle, into the next handle.
+// Lifetime protocol (round 6; tests/hostsan models it): a stream enters the pool only after it has drained (hipStreamSynchronize), so it can never
+// carry work of a destroyed handle into the next handle.  Pooled streams are the library's own: nothing captures them.
 static std::mutex g_stream_mu;
 static std::vector<std::pair<int, hipStream_t>> g_free_streams; // (device, stream)
-int wtk::stream_idle(hipStream_t s, const char *what) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    HIP_TRY(hipStreamIsCapturing(s, &cs));
-    if (cs != hipStreamCaptureStatusNone) return fail(std::string("stream protocol violation: ") + what + " is still part of a stream capture");
-    return 0;
-}
 int wtk::pooled_stream(int device, hipStream_t *s) {
     {
         std::lock_guard<std::mutex> lk(g_stream_mu);
@@ -127,7 +120,7 @@ int wtk::pooled_stream(int device, hipStream_t *s) {
             if (g_free_streams[i].first == device) {
                 *s = g_free_streams[i].second;
                 g_free_streams.erase(g_free_streams.begin() + (long)i);
-                return stream_idle(*s, "a stream handed out by the pool");
+                return 0;
             }
     }
     HIP_TRY(hipStreamCreateWithFlags(s, hipStreamNonBlocking));
@@ -338,6 +331,61 @@ struct Planner {
 };
 } // namespace
 
+// Environment switches (README.md, "Environment switches"): A/B switches and test hooks.  An unset or empty variable keeps the default; a set one
+// is read as a number.
+static int env_int(const char *name, int unset) {
+    const char *e = std::getenv(name);
+    return e && e[0] ? std::atoi(e) : unset;
+}
+
+namespace {
+// The switches that combine with a planning rule of wtk_yolo_create_planned, which applies each one where its rule is decided.
+struct PlanSwitches {
+    int latency_plan;          // WTK_LATENCY_PLAN: -1 unset (the max_batch rule), 1 the latency plan, any other value the throughput plan
+    bool no_side_stream;       // WTK_NO_SIDE_STREAM=1
+    bool materialize_upsample; // WTK_MATERIALIZE_UPSAMPLE=1
+    bool no_igemm_tail;        // WTK_NO_IGEMM_TAIL=1
+    bool no_sk_mixed;          // WTK_NO_SK_MIXED=1
+    bool small_narrow;         // WTK_SMALL_NARROW (0: off)
+    int halo_deep;             // WTK_HALO_DEEP (default 1)
+    bool sk_finish;            // WTK_SK_FINISH=1
+    bool no_fused_front;       // WTK_NO_FUSED_FRONT=1
+    bool no_fused_c2f;         // WTK_NO_FUSED_C2F=1
+};
+
+// Every library-side switch of a handle, read once when it is created: the handle's own fields directly, the rest into PlanSwitches.
+PlanSwitches read_switches(wtk_yolo *h) {
+    h->use_halo = env_int("WTK_NO_HALO", 0) != 1;
+    h->halo_slabs = env_int("WTK_HALO_SLABS", 3) == 2 ? 2 : 3;
+    h->halo_persist = env_int("WTK_HALO_PERSIST", 1) != 0;
+    h->halo_small_blocks = env_int("WTK_HALO_SMALL_BLOCKS", 1) != 0;
+    h->use_tail = env_int("WTK_NO_FUSED_TAIL", 0) != 1;
+    h->use_tail_cls_split = env_int("WTK_NO_SPLIT_CLS_TAIL", 0) != 1;
+    h->use_wide = env_int("WTK_NO_WIDE_1X1", 0) != 1;
+    h->use_ws64 = env_int("WTK_NO_WS64", 0) != 1;
+    h->use_s2win = env_int("WTK_NO_S2WIN", 0) != 1;
+    h->use_c32s = env_int("WTK_NO_C32S", 0) != 1;
+    h->sk_group = env_int("WTK_SK_GROUP", 1) != 0;
+    h->sk_autotune = env_int("WTK_SK_AUTOTUNE", 1) != 0;
+    const int tile = env_int("WTK_SK_TILE", -1), form = env_int("WTK_SK_FORM", -1);
+    h->sk_force_tile = tile >= 0 && tile <= 3 ? tile : -1;
+    h->sk_force_form = form == 0 || form == 1 ? form : -1;
+    h->front_debug = env_int("WTK_FRONT_DEBUG", 0) == 1;
+    PlanSwitches s;
+    s.latency_plan = env_int("WTK_LATENCY_PLAN", -1);
+    s.no_side_stream = env_int("WTK_NO_SIDE_STREAM", 0) == 1;
+    s.materialize_upsample = env_int("WTK_MATERIALIZE_UPSAMPLE", 0) == 1;
+    s.no_igemm_tail = env_int("WTK_NO_IGEMM_TAIL", 0) == 1;
+    s.no_sk_mixed = env_int("WTK_NO_SK_MIXED", 0) == 1;
+    s.small_narrow = env_int("WTK_SMALL_NARROW", 1) != 0;
+    s.halo_deep = env_int("WTK_HALO_DEEP", 1);
+    s.sk_finish = env_int("WTK_SK_FINISH", 0) == 1;
+    s.no_fused_front = env_int("WTK_NO_FUSED_FRONT", 0) == 1;
+    s.no_fused_c2f = env_int("WTK_NO_FUSED_C2F", 0) == 1;
+    return s;
+}
+} // namespace
+
 // WTK_SEGV_BACKTRACE=1 (tests/conftest.py sets it): a SIGSEGV prints the native frames to stderr before the handler that was installed before this
 // library was loaded runs (under pytest: Python's faulthandler, which adds the Python stack and re-raises).  Diagnostic only; off by default.
 namespace {
@@ -356,8 +404,7 @@ void segv_backtrace(int sig, siginfo_t *info, void *ctx) {
     raise(sig);
 }
 __attribute__((constructor)) void install_segv_backtrace() {
-    const char *e = std::getenv("WTK_SEGV_BACKTRACE");
-    if (!e || e[0] != '1') return;
+    if (env_int("WTK_SEGV_BACKTRACE", 0) != 1) return;
     void *warm[4];
     (void)backtrace(warm, 4); // the first call loads libgcc and allocates: done here, not inside the handler
     struct sigaction sa;
@@ -457,14 +504,12 @@ static void sk_schedule(wtk_yolo *h) {
     }
 }
 
-// Order of release (round 6: one protocol, checked by tests/hostsan): (1) the device drains — no kernel, copy or graph replay of this handle is in
-// flight; (2) the graph execs go, BEFORE the events and streams they were captured through; (3) the events; (4) the streams go back to the pool,
-// idle and outside any capture; (5) device memory.
+// Order of release (round 6: one protocol, checked by tests/hostsan): (1) the device drains — no kernel or copy of this handle is in flight;
+// (2) the events; (3) the streams go back to the pool, idle; (4) device memory.
 extern "C" void wtk_yolo_destroy(wtk_yolo *h) {
     if (!h) return;
     DeviceGuard guard(h->device); // the synchronise and the releases below are about the HANDLE's device, whatever the caller's current device is
     (void)hipDeviceSynchronize();
-    drop_graphs(h);
     for (int i = 0; i < h->ev_created; ++i) (void)hipEventDestroy(h->ev[i]);
     for (hipEvent_t e : h->tune_ev) (void)hipEventDestroy(e);
     for (int i = 0; i < 2; ++i)
@@ -526,46 +571,23 @@ extern "C" int wtk_yolo_create_planned(wtk_yolo **out, const wtk_yolo_desc *d, i
     h->S_w = d->imgsz_w;
     h->max_batch = d->max_batch;
     h->dims = dims;
-    if (const char *e = std::getenv("WTK_NO_HALO")) h->use_halo = !(e[0] == '1');
+    const PlanSwitches sw = read_switches(h);
     // Side streams are for LARGE batches.  A handle for the reference's own calls (max_batch <= 16: one frame, one cycle batch) runs on the caller's stream
     // alone: its launches last 5-50 us, and a dependency between two streams costs microseconds when the runtime has put them on different hardware
     // queues, nothing when they share one — so with side streams the same controller loop ran at 7.6 k or 4.4 k frames/s (throughput plan), 9.0 k or
     // 11.2 k (deferred log) depending on GPU_MAX_HW_QUEUES and on which streams the process had created before; on one stream it runs at the same rate
     // in every such environment (profiles/r06_notes.md section 4).  wtk_yolo_set_side_streams(h, 2) turns them on for such a handle explicitly.
     if (d->max_batch <= 16) h->use_side = 0, h->side_streams = 0;
-    if (const char *e = std::getenv("WTK_NO_SIDE_STREAM")) h->use_side = h->use_side && !(e[0] == '1');
-    if (const char *e = std::getenv("WTK_HALO_SLABS")) h->halo_slabs = e[0] == '2' ? 2 : 3;
-    if (const char *e = std::getenv("WTK_HALO_PERSIST")) h->halo_persist = e[0] != '0';
-    if (const char *e = std::getenv("WTK_HALO_SMALL_BLOCKS")) h->halo_small_blocks = e[0] != '0';
-    if (const char *e = std::getenv("WTK_NO_FUSED_TAIL")) h->use_tail = e[0] != '1';
-    if (const char *e = std::getenv("WTK_NO_SPLIT_CLS_TAIL")) h->use_tail_cls_split = e[0] != '1';
-    if (const char *e = std::getenv("WTK_NO_WIDE_1X1")) h->use_wide = e[0] != '1';
-    if (const char *e = std::getenv("WTK_NO_WS64")) h->use_ws64 = e[0] != '1';
-    if (const char *e = std::getenv("WTK_NO_S2WIN")) h->use_s2win = e[0] != '1';
-    if (const char *e = std::getenv("WTK_NO_C32S")) h->use_c32s = e[0] != '1';
+    if (sw.no_side_stream) h->use_side = 0;
     {
         hipDeviceProp_t prop;
         HIP_TRY(hipGetDeviceProperties(&prop, d->device));
         h->num_cus = prop.multiProcessorCount;
     }
     h->latency = d->max_batch <= 4 && !h->is_f16;
-    if (const char *e = std::getenv("WTK_LATENCY_PLAN")) h->latency = e[0] == '1' && !h->is_f16;
+    if (sw.latency_plan >= 0) h->latency = sw.latency_plan == 1 && !h->is_f16;
     if (plan != WTK_PLAN_AUTO) h->latency = plan == WTK_PLAN_LATENCY; // the caller's word beats the rule and the environment
-    // Replayed captures (hipGraph) are OPT-IN since round 6: WTK_GRAPH=1 (every form), or WTK_GRAPH_HOST=1 (the *_host entry points) / WTK_GRAPH_VIEWS=1
-    // (caller buffers, captured the second time an argument set is met), read when the handle is created.  Round 5 replayed by default on latency-plan
-    // handles (0.53 against 0.57 ms per single-frame call); a capture of this forward pass FORKS into the side streams, a graph exec instantiated from
-    // a forked capture runs its branches on streams the runtime creates for it, and that machinery is where the two open problems of round 5 lived (an
-    // intermittent host fault in the first capturing call of a handle after > 100 handles in the process, and replays that ran 2-4 x slower for later
-    // handles of a process with eight hardware queues): profiles/r06_notes.md section 1.  The latency plan of round 6 runs on ONE stream in launches
-    // grouped per dependency level (sk_schedule), so eager launches no longer pay for the fork either.
-    {
-        const char *g = std::getenv("WTK_GRAPH");
-        h->graph_host = h->graph_views = g && g[0] == '1';
-    }
     if (h->latency) h->use_tail = 0;
-    if (const char *e = std::getenv("WTK_GRAPH_MAX_BATCH")) h->graph_max_batch = std::atoi(e);
-    if (const char *e = std::getenv("WTK_GRAPH_HOST")) h->graph_host = e[0] == '1';
-    if (const char *e = std::getenv("WTK_GRAPH_VIEWS")) h->graph_views = e[0] == '1';
 
     Planner P{h, specs, d->convs};
     const int *c = dims.c;
@@ -672,8 +694,7 @@ extern "C" int wtk_yolo_create_planned(wtk_yolo **out, const wtk_yolo_desc *d, i
     // nn.Upsample(2x nearest) + Concat: the consumer's 1x1 conv reads the half-resolution producer directly (two-source
     // loader of the 128x128 tile), so the 4x larger upsampled copy is never written.  Narrow scales whose cv1 does not
     // use that tile (and WTK_MATERIALIZE_UPSAMPLE=1) keep the materialised copy in the concat buffer.
-    bool lazy_up = c[2] % 128 == 0 && c[3] % 128 == 0;
-    if (const char *e = std::getenv("WTK_MATERIALIZE_UPSAMPLE")) lazy_up = lazy_up && e[0] != '1';
+    const bool lazy_up = c[2] % 128 == 0 && c[3] % 128 == 0 && !sw.materialize_upsample;
     if (lazy_up) {
         P.conv({"model.9.cv2"}, sppcat, 0, cat20, c[3]); // t9 -> cat20 slice
         P.c2f("model.12", cat11, 0, c[3], dims.n[3], false, cat17, c[2], -1, 0, cat20, c[3], c[4]); // [up(t9) | t6]; t12 -> cat17 slice
@@ -732,7 +753,7 @@ extern "C" int wtk_yolo_create_planned(wtk_yolo **out, const wtk_yolo_desc *d, i
     }
     // A strided 3x3 conv (128 couts, implicit GEMM, fp16) whose ONLY reader is the 1x1 conv 128 -> 128 right behind it (model.3 ->
     // model.4.cv1 in YOLOv8s): the 1x1 runs in the 3x3's epilogue, its input never reaches HBM.  WTK_NO_IGEMM_TAIL=1 switches it off.
-    if (!P.failed && h->is_f16 && !(std::getenv("WTK_NO_IGEMM_TAIL") && std::getenv("WTK_NO_IGEMM_TAIL")[0] == '1')) {
+    if (!P.failed && h->is_f16 && !sw.no_igemm_tail) {
         for (size_t i = 0; i + 1 < h->ops.size(); ++i) {
             Op &c3 = h->ops[i], &c1 = h->ops[i + 1];
             if (c3.kind != OP_CONV || c1.kind != OP_CONV || c3.halo || c3.k != 3 || c3.stride != 2 || c3.cfg != CFG_128x128 || c3.cout != 128 || c3.cout_pad != 128 ||
@@ -762,14 +783,11 @@ extern "C" int wtk_yolo_create_planned(wtk_yolo **out, const wtk_yolo_desc *d, i
     // the layers whose whole batch is at most 4 096 output pixels — the 12 x 12 maps of imgsz 384 — where the window / implicit-GEMM kernels run ~40-block
     // grids that walk K serially (model.8's bottlenecks 40 us, split over K 24 us: profiles/r05_notes.md section 5); the choice is fixed per handle, so a
     // frame's result still does not depend on its batch.  WTK_NO_SK_MIXED=1 switches the second rule off (A/B).
-    const bool sk_mixed = !h->latency && !h->is_f16 && h->max_batch <= 16 && !(std::getenv("WTK_NO_SK_MIXED") && std::getenv("WTK_NO_SK_MIXED")[0] == '1');
+    const bool sk_mixed = !h->latency && !h->is_f16 && h->max_batch <= 16 && !sw.no_sk_mixed;
     // (f16x3: the 12 x 12 maps of imgsz 384; fp32, whose window kernels are 2.5 x slower per tap, gains on the 24 x 24 maps too — profiles/r05_notes.md section 5)
-    const long long sk_mixed_max_px = std::getenv("WTK_SK_MIXED_MAX_PX") ? std::atoll(std::getenv("WTK_SK_MIXED_MAX_PX")) : (h->split ? 4096 : 10000);
-    h->small_narrow = !h->is_f16 && h->max_batch <= 16 && !(std::getenv("WTK_SMALL_NARROW") && std::getenv("WTK_SMALL_NARROW")[0] == '0');
-    {
-        const int deep = std::getenv("WTK_HALO_DEEP") ? std::atoi(std::getenv("WTK_HALO_DEEP")) : 1;
-        h->halo_deep = h->split && (deep == 2 || (deep == 1 && h->max_batch <= 16));
-    }
+    const long long sk_mixed_max_px = h->split ? 4096 : 10000;
+    h->small_narrow = !h->is_f16 && h->max_batch <= 16 && sw.small_narrow;
+    h->halo_deep = h->split && (sw.halo_deep == 2 || (sw.halo_deep == 1 && h->max_batch <= 16));
     if (h->latency || sk_mixed) {
         for (size_t i = 3; i < h->ops.size(); ++i) { // ops[0..2] stay the fused front's
             Op &op = h->ops[i];
@@ -785,18 +803,15 @@ extern "C" int wtk_yolo_create_planned(wtk_yolo **out, const wtk_yolo_desc *d, i
             // K atoms: the count the launcher's cost model likes best for what this handle is for — a small throughput-plan handle's largest call (a cycle
             // batch's 12 x 12 maps: eight atoms x 34 tiles are 272 blocks = two rounds on 256 CUs, seven are one round), a latency-plan handle's single frame
             // (0.529 -> 0.515 ms at 384 x 384) — and the layer's default where the model sees no difference.  Fixed per handle, so a frame's result does not
-            // depend on its batch.  WTK_SK_PLAN_ATOMS=0: the default count everywhere.
-            const int nk_op = op.k * op.k * op.cin / 32;
-            const bool plan_atoms = !(std::getenv("WTK_SK_PLAN_ATOMS") && std::getenv("WTK_SK_PLAN_ATOMS")[0] == '0');
+            // depend on its batch.
             const long long plan_px = (long long)(h->latency ? 1 : h->max_batch) * ob.h * ob.w;
-            op.sk_atoms = plan_atoms ? conv_sk_plan_atoms(plan_px, op.cout_pad, nk_op, h->num_cus, h->split) : conv_sk_slices(nk_op);
+            op.sk_atoms = conv_sk_plan_atoms(plan_px, op.cout_pad, op.k * op.k * op.cin / 32, h->num_cus, h->split);
             const int S = op.sk_atoms;
             if (S > 1 && dev_alloc(h, (void **)&op.sk_partial, (size_t)S * h->max_batch * ob.h * ob.w * op.cout_pad * sizeof(float))) {
                 wtk_yolo_destroy(h);
                 return 1;
             }
-            const bool two_launches = std::getenv("WTK_SK_FINISH") && std::getenv("WTK_SK_FINISH")[0] == '1'; // A/B switch: slabs combined by a second launch
-            if (S > 1 && !two_launches) {
+            if (S > 1 && !sw.sk_finish) { // (WTK_SK_FINISH=1, A/B switch: slabs combined by a second launch)
                 const size_t nt = conv_sk_ticket_count((long long)h->max_batch * ob.h * ob.w, op.cout_pad) * sizeof(unsigned);
                 if (dev_alloc(h, (void **)&op.sk_tickets, nt)) {
                     wtk_yolo_destroy(h);
@@ -809,33 +824,22 @@ extern "C" int wtk_yolo_create_planned(wtk_yolo **out, const wtk_yolo_desc *d, i
             }
         }
     }
-    if (const char *e = std::getenv("WTK_SK_GROUP")) h->sk_group = e[0] != '0';
-    if (const char *e = std::getenv("WTK_SK_AUTOTUNE")) h->sk_autotune = e[0] != '0';
-    if (const char *e = std::getenv("WTK_SK_TILE")) h->sk_force_tile = std::atoi(e) >= 0 && std::atoi(e) <= 3 ? std::atoi(e) : -1;
-    if (const char *e = std::getenv("WTK_SK_FORM")) h->sk_force_form = std::atoi(e) == 0 || std::atoi(e) == 1 ? std::atoi(e) : -1;
     sk_schedule(h);
     // ops[0..2] are stem, model.1, model.2.cv1 by construction; fuse them when the widths match the kernel
-    {
-        const char *e = std::getenv("WTK_NO_FUSED_FRONT");
-        const bool off = e && e[0] == '1';
-        if (const char *dbg = std::getenv("WTK_FRONT_DEBUG")) h->front_debug = dbg[0] == '1';
-        h->use_front = !off && h->ops.size() > 3 && h->ops[0].kind == OP_STEM && h->ops[1].kind == OP_CONV && h->ops[2].kind == OP_CONV &&
-                       h->ops[1].k == 3 && h->ops[1].stride == 2 && h->ops[2].k == 1 && h->ops[1].act && h->ops[2].act &&
-                       h->ops[2].out2_buf < 0 && h->ops[2].res_buf < 0 &&
-                       (front_fused_eligible(h->is_f16, h->ops[0].cout, h->ops[1].cout, h->ops[2].cout) ||
-                        (h->split && h->ops[1].cin == 32 && front_fused_split_eligible(h->ops[0].cout, h->ops[1].cout, h->ops[2].cout)));
-        // ops[3..5] are the first C2f's bottleneck convs and cv2 (dims.n[0] == 1)
-        const char *e2 = std::getenv("WTK_NO_FUSED_C2F");
-        const bool off2 = e2 && e2[0] == '1';
-        if (!off2 && h->ops.size() > 6 && dims.n[0] == 1) {
-            const Op &m1 = h->ops[3], &m2 = h->ops[4], &cv2 = h->ops[5], &cv1 = h->ops[2];
-            h->use_c2f = m1.kind == OP_CONV && m2.kind == OP_CONV && cv2.kind == OP_CONV && m1.k == 3 && m2.k == 3 && cv2.k == 1 &&
-                         m1.stride == 1 && m2.stride == 1 && m1.act && m2.act && cv2.act && m1.in_buf == cv1.out_buf &&
-                         m2.res_buf == cv1.out_buf && m2.res_coff == m1.in_coff && cv2.in_buf == cv1.out_buf && cv2.in_coff == cv1.out_coff &&
-                         m1.in_coff == cv1.out_coff + 32 && m2.out_coff == cv1.out_coff + 64 && cv2.cin == 96 && m1.Kpad == m2.Kpad &&
-                         cv2.out2_buf < 0 && cv2.res_buf < 0 && m1.cout == 32 && m2.cout == 32 &&
-                         c2f_fused_eligible(h->is_f16, m1.cin, dims.n[0], m2.res_buf >= 0, cv2.cout);
-        }
+    h->use_front = !sw.no_fused_front && h->ops.size() > 3 && h->ops[0].kind == OP_STEM && h->ops[1].kind == OP_CONV && h->ops[2].kind == OP_CONV &&
+                   h->ops[1].k == 3 && h->ops[1].stride == 2 && h->ops[2].k == 1 && h->ops[1].act && h->ops[2].act &&
+                   h->ops[2].out2_buf < 0 && h->ops[2].res_buf < 0 &&
+                   (front_fused_eligible(h->is_f16, h->ops[0].cout, h->ops[1].cout, h->ops[2].cout) ||
+                    (h->split && h->ops[1].cin == 32 && front_fused_split_eligible(h->ops[0].cout, h->ops[1].cout, h->ops[2].cout)));
+    // ops[3..5] are the first C2f's bottleneck convs and cv2 (dims.n[0] == 1)
+    if (!sw.no_fused_c2f && h->ops.size() > 6 && dims.n[0] == 1) {
+        const Op &m1 = h->ops[3], &m2 = h->ops[4], &cv2 = h->ops[5], &cv1 = h->ops[2];
+        h->use_c2f = m1.kind == OP_CONV && m2.kind == OP_CONV && cv2.kind == OP_CONV && m1.k == 3 && m2.k == 3 && cv2.k == 1 &&
+                     m1.stride == 1 && m2.stride == 1 && m1.act && m2.act && cv2.act && m1.in_buf == cv1.out_buf &&
+                     m2.res_buf == cv1.out_buf && m2.res_coff == m1.in_coff && cv2.in_buf == cv1.out_buf && cv2.in_coff == cv1.out_coff &&
+                     m1.in_coff == cv1.out_coff + 32 && m2.out_coff == cv1.out_coff + 64 && cv2.cin == 96 && m1.Kpad == m2.Kpad &&
+                     cv2.out2_buf < 0 && cv2.res_buf < 0 && m1.cout == 32 && m2.cout == 32 &&
+                     c2f_fused_eligible(h->is_f16, m1.cin, dims.n[0], m2.res_buf >= 0, cv2.cout);
     }
 
     // ---- activation workspace: every tensor gets its own allocation (288 GB HBM: no liveness reuse needed)

@@ -1,5 +1,5 @@
 // The detector handle, part 2 (see wtk_internal.h): one forward pass — letterbox / view cut, the fused front, the conv ops (one grouped split-K launch per
-// dependency level on latency-plan handles), pool, head —, the opt-in replay of a captured pass, the predict entry points and the test hooks.
+// dependency level on latency-plan handles), pool, head —, the predict entry points and the test hooks.
 #include "wtk_internal.h"
 
 #include <algorithm>
@@ -87,13 +87,11 @@ static int ensure_nms_scratch(wtk_yolo *h, hipStream_t st) {
 }
 
 // Enqueue one forward pass (letterbox, stem, convs, pool, head) on `st`.  No allocation, no synchronisation
-// (profiling mode excepted): safe inside stream capture.
-// The pair of side streams is shared by every handle of the process on a device (ensure_side_streams).  Handles driven from different host
-// threads (ctypes releases the GIL) must not interleave on it: a stream capture in one thread (the graph path of wtk_yolo_predict pulls the side
-// streams into a hipStreamCaptureModeThreadLocal capture through the event waits) would swallow or reject the other thread's launches.  Every
-// enqueue that touches the shared pair, and the whole capture bracket, holds this lock; a single-threaded caller (the bench, the controllers)
-// never contends on it.
-static std::recursive_mutex g_side_mu;
+// (profiling mode excepted): safe inside a caller's stream capture.
+// The pair of side streams is shared by every handle of the process on a device (ensure_side_streams).  Two host threads (ctypes releases the GIL)
+// that enqueue on it at the same time would interleave their feature-event waits and tower launches on the shared pair.  Every enqueue that touches
+// the pair holds this lock; a single-threaded caller (the bench, the controllers) never contends on it.
+static std::mutex g_side_mu;
 
 // side streams and their events, taken at the first forward pass that uses them
 static int ensure_side_streams(wtk_yolo *h) {
@@ -177,8 +175,8 @@ static int yolo_enqueue_pass(wtk_yolo *h, const uint8_t *frames_dev, int32_t B, 
     const bool grouped = h->latency && h->sk_group && !h->lat_sched.empty();
     if (!grouped && h->use_side && h->side_streams > 0 && !h->profiling && ensure_side_streams(h)) return 1;
     const bool two_lanes = !grouped && h->use_side && h->side_streams > 0 && h->side_stream[1] && !h->profiling;
-    std::unique_lock<std::recursive_mutex> side_lock;
-    if (two_lanes) side_lock = std::unique_lock<std::recursive_mutex>(g_side_mu);
+    std::unique_lock<std::mutex> side_lock;
+    if (two_lanes) side_lock = std::unique_lock<std::mutex>(g_side_mu);
     unsigned side_used = 0; // bit i: side_stream[i] carries work of this pass
     hipStream_t main_st = st;
     size_t first_op = 0;
@@ -608,67 +606,6 @@ static int yolo_enqueue(wtk_yolo *h, const uint8_t *frames_dev, int32_t B, int32
     return yolo_enqueue_pass(h, frames_dev, B, H, W, C, conf, out_xywh, out_conf, out_anchor, st, vs, nms);
 }
 
-// Captured launches carry the stream layout / dynamic-batch pointer they were captured with: drop them all.  Each exec is destroyed only after its last
-// replay has finished (its own event; no device-wide synchronise: other lanes keep running, and a global-mode capture open in another thread stays
-// legal); argument sets met once are forgotten too.
-static void destroy_graph_entry(wtk_yolo::GraphEntry &g) {
-    if (g.done) {
-        (void)hipEventSynchronize(g.done);
-        (void)hipEventDestroy(g.done);
-    }
-    if (g.exec) (void)hipGraphExecDestroy(g.exec);
-    g.exec = nullptr, g.done = nullptr;
-}
-void wtk::drop_graphs(wtk_yolo *h) {
-    for (auto &g : h->graphs) destroy_graph_entry(g);
-    h->graphs.clear();
-    h->seen_once.clear();
-}
-
-// Replay the captured forward pass of this argument set, or capture it now (the whole launch sequence incl. the side streams).
-static int graph_replay_or_capture(wtk_yolo *h, wtk_yolo::GraphEntry key, hipStream_t st, const ViewSrc *vs) {
-    for (auto &g : h->graphs)
-        if (g.same_args(key)) {
-            HIP_TRY(hipGraphLaunch(g.exec, st));
-            HIP_TRY(hipEventRecord(g.done, st));
-            return 0;
-        }
-    hipGraph_t graph = nullptr;
-    const bool forks = !(h->latency && h->sk_group && !h->lat_sched.empty()) && h->use_side && h->side_streams > 0;
-    if (forks && ensure_side_streams(h)) return 1; // streams and events exist before the capture starts
-    std::unique_lock<std::recursive_mutex> capture_lock(g_side_mu); // no other thread may touch the shared side streams while they are captured
-    // protocol: the origin and the streams the capture will fork into are outside any capture when it begins (a stream left inside one by a failed
-    // bracket, here or in the caller's code, must not be captured again: fail loudly instead)
-    if (stream_idle(st, "the stream a capture is about to begin on")) return 1;
-    for (int i = 1; i < wtk_yolo::kSideStreams; ++i)
-        if (h->side_stream[i] && stream_idle(h->side_stream[i], "a side stream")) return 1;
-    HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-    const int rc = yolo_enqueue(h, reinterpret_cast<const uint8_t *>(key.frames), key.B, key.H, key.W, key.C, key.conf, reinterpret_cast<float *>(key.o_xywh),
-                                reinterpret_cast<float *>(key.o_conf), reinterpret_cast<int32_t *>(key.o_anchor), st, vs);
-    const hipError_t ec = hipStreamEndCapture(st, &graph);
-    capture_lock.unlock();
-    if (rc) {
-        if (graph) (void)hipGraphDestroy(graph);
-        return 1;
-    }
-    if (ec != hipSuccess) return fail_hip("hipStreamEndCapture", ec);
-    const hipError_t ei = hipGraphInstantiate(&key.exec, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    if (ei != hipSuccess) return fail_hip("hipGraphInstantiate", ei);
-    if (hipEventCreateWithFlags(&key.done, hipEventDisableTiming) != hipSuccess) {
-        (void)hipGraphExecDestroy(key.exec);
-        return fail("hipEventCreateWithFlags failed");
-    }
-    if (h->graphs.size() >= 16) { // bounded cache: callers that rotate buffers would otherwise grow it without limit
-        destroy_graph_entry(h->graphs.front());
-        h->graphs.erase(h->graphs.begin());
-    }
-    h->graphs.push_back(key);
-    HIP_TRY(hipGraphLaunch(key.exec, st));
-    HIP_TRY(hipEventRecord(key.done, st));
-    return 0;
-}
-
 extern "C" int wtk_yolo_predict(wtk_yolo *h, const uint8_t *frames_dev, int32_t B, int32_t H, int32_t W, int32_t C, float conf, float iou,
                                 int32_t max_det, float *out_xywh, float *out_conf, int32_t *out_anchor, void *stream) {
     (void)iou; // with max_det == 1 the IoU threshold cannot change the survivor
@@ -685,24 +622,7 @@ extern "C" int wtk_yolo_predict(wtk_yolo *h, const uint8_t *frames_dev, int32_t 
         HIP_TRY(hipMalloc(&h->lb_dev, (size_t)h->max_batch * h->S_h * h->S_w * 3));
         h->lb_cap = (size_t)h->max_batch * h->S_h * h->S_w * 3;
     }
-    // Opt-in (WTK_GRAPH / WTK_GRAPH_HOST / WTK_GRAPH_VIEWS, see wtk_yolo_create_planned): replay a captured hipGraph of the forward pass.  The handle's own
-    // staging buffers (the *_host entry points) never change address, so one capture per (B, H, W, C, conf) is replayed forever; a caller's argument set
-    // is captured the second time it is met, so a caller that rotates its buffers never pays for a capture.
-    const bool own_buffers = frames_dev == h->frames_dev && out_xywh == h->o_xywh;
-    const bool use_graph = ((own_buffers && h->graph_host) || (!own_buffers && h->graph_views)) && st != nullptr && !h->profiling && h->graph_max_batch > 0 && B <= h->graph_max_batch;
-    if (!use_graph) return yolo_enqueue(h, frames_dev, B, H, W, C, conf, out_xywh, out_conf, out_anchor, st);
-    wtk_yolo::GraphEntry key{frames_dev, B, H, W, C, conf, out_xywh, out_conf, out_anchor, nullptr};
-    if (!own_buffers) {
-        bool known = false;
-        for (auto &g : h->graphs) known = known || g.same_args(key);
-        for (auto &g : h->seen_once) known = known || g.same_args(key);
-        if (!known) {
-            if (h->seen_once.size() >= 16) h->seen_once.erase(h->seen_once.begin());
-            h->seen_once.push_back(key);
-            return yolo_enqueue(h, frames_dev, B, H, W, C, conf, out_xywh, out_conf, out_anchor, st);
-        }
-    }
-    return graph_replay_or_capture(h, key, st, nullptr);
+    return yolo_enqueue(h, frames_dev, B, H, W, C, conf, out_xywh, out_conf, out_anchor, st);
 }
 
 extern "C" int wtk_yolo_predict_nms(wtk_yolo *h, const uint8_t *frames_dev, int32_t B, int32_t H, int32_t W, int32_t C, float conf, float iou,
@@ -746,23 +666,6 @@ extern "C" int wtk_yolo_predict_views(wtk_yolo *h, const uint8_t *frames_dev, in
         h->lb_cap = (size_t)h->max_batch * h->S_h * h->S_w * 3;
     }
     const ViewSrc vs{pos_xy_dev, frame_index_dev, view_w, view_h, n_frames};
-    // The reference's operating point is this call at B = 1 and B = one cycle (9 / 15 views), once per cycle each (yolo_controller.py:95-109).  With
-    // WTK_GRAPH_VIEWS=1 a caller that comes back with the SAME device addresses (frames, view table, output rows — HipYoloController keeps them per
-    // batch size) gets the captured forward replayed; an argument set is captured the second time it is met (a caller that rotates its buffers never
-    // pays for a capture).  OFF by default: measured in round 4 (bench.py `closed_loop`, 384 x 384 views) the replay changes a B = 1 call from 1.13 to
-    // 1.12 ms and a B = 15 call from 1.38 to 1.35 ms — these calls are bound by the ~60 dependent kernels' own latencies (18 us each on grids of a few
-    // blocks), not by the host's launch rate — while a replay costs its fixed 10-16 us.
-    const bool use_graph = h->graph_views && st != nullptr && !h->profiling && h->graph_max_batch > 0 && B <= h->graph_max_batch;
-    if (use_graph) {
-        wtk_yolo::GraphEntry key{frames_dev, B, H, W, C, conf, out_xywh, out_conf, out_anchor, nullptr};
-        key.idx = frame_index_dev, key.pos = pos_xy_dev, key.vw = view_w, key.vh = view_h, key.nf = n_frames;
-        bool known = false;
-        for (auto &g : h->graphs) known = known || g.same_args(key);
-        for (auto &g : h->seen_once) known = known || g.same_args(key);
-        if (known) return graph_replay_or_capture(h, key, st, &vs);
-        if (h->seen_once.size() >= 16) h->seen_once.erase(h->seen_once.begin());
-        h->seen_once.push_back(key);
-    }
     return yolo_enqueue(h, frames_dev, B, H, W, C, conf, out_xywh, out_conf, out_anchor, st, &vs);
 }
 
@@ -795,8 +698,6 @@ extern "C" int wtk_yolo_predict_host(wtk_yolo *h, const uint8_t *frames_host, in
 
 extern "C" int wtk_yolo_set_side_streams(wtk_yolo *h, int32_t n) {
     if (!h || n < 0 || n > 2) return fail("wtk_yolo_set_side_streams: n must be 0, 1 or 2");
-    DEVICE_GUARD(h);
-    drop_graphs(h); // captured launches (host stream or a caller's) carry the old stream layout
     h->side_streams = n;
     h->use_side = n > 0;
     return 0;
@@ -805,10 +706,6 @@ extern "C" int wtk_yolo_set_side_streams(wtk_yolo *h, int32_t n) {
 extern "C" int wtk_yolo_set_dynamic_batch(wtk_yolo *h, const int32_t *n_dev) {
     if (!h) return fail("wtk_yolo_set_dynamic_batch: null handle");
     h->n_dyn = n_dev;
-    if (!h->graphs.empty() || !h->seen_once.empty()) { // captured launches carry the old pointer
-        DEVICE_GUARD(h);
-        drop_graphs(h);
-    }
     return 0;
 }
 
