@@ -493,6 +493,26 @@ int main(int argc, char **argv) {
         cases.push_back({1, 32, 32, 1, F32, AUTO, 1}); // the smallest legal network: 4 x 4, 2 x 2, 1 x 1 maps
         cases.push_back({0, 32, 64, 5, F16, AUTO, 1});
         cases.push_back({1, 64, 32, 17, X3, AUTO, 1});
+        // the per-layer reference matrix of tests/test_gpu_layer_reference.py: tiny and ragged maps in every dtype and plan, batches that are
+        // not a multiple of 32, a call smaller than its handle, a tall non-square map, class tails of nc = 20 / 80
+        for (int dtype : {F32, F16, X3}) {
+            for (int plan : {THR, LAT}) {
+                if (plan == LAT && dtype == F16) continue;
+                cases.push_back({1, 32, 32, 1, dtype, plan, 1});
+                cases.push_back({1, 64, 32, 3, dtype, plan, 1});
+                cases.push_back({1, 32, 64, 2, dtype, plan, 1});
+            }
+            cases.push_back({1, 352, 224, 2, dtype, THR, 1});
+            cases.push_back({1, 640, 512, 40, dtype, THR, 1});
+            if (dtype != F16) {
+                cases.push_back({1, 128, 128, 4, dtype, AUTO, 1});
+                cases.push_back({1, 640, 640, 8, dtype, AUTO, 1});
+                cases.push_back({1, 1280, 736, 2, dtype, THR, 1});
+                cases.push_back({1, 352, 224, 2, dtype, THR, 20});
+                cases.push_back({1, 352, 224, 2, dtype, THR, 80});
+            }
+        }
+        cases.push_back({1, 384, 384, 8, X3, THR, 1});
     }
     run_matrix("shape matrix", cases, 3);
     hybrid_and_misc();
