@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define WTK_ABI_VERSION 7 /* 7: + wtk_yolo_create_planned / wtk_yolo_plan, wtk_yolo_status (additive); 2: + wtk_yolo_predict_views / _nms, wtk_track_*, wtk_comm_*; 3: + WTK_F16X3, wtk_recheck_*; 4: + wtk_recheck_select_counted; 5: + wtk_recheck_enqueue / _scatter; 6: + wtk_hybrid_* (additive: every earlier entry point is unchanged) */
+#define WTK_ABI_VERSION 7 /* 7: + wtk_yolo_create_planned / wtk_yolo_plan, wtk_yolo_status (additive); 2: + wtk_yolo_predict_views / _nms, wtk_track_*, wtk_comm_*; 3: + WTK_F16X3, wtk_recheck_*; 4: + wtk_recheck_select_counted; 5: + wtk_recheck_enqueue / _scatter; 6: + wtk_hybrid_*; still 7: + wtk_background, wtk_precise_error (additive: every earlier entry point is unchanged) */
 
 typedef enum wtk_dtype {
     WTK_F32 = 0, /* fp32 storage, exact-fp32 MFMA (v_mfma_f32_16x16x4_f32): parity mode   */
@@ -400,6 +400,35 @@ int wtk_comm_unique_id(uint8_t *id_out, size_t cap);
 int wtk_comm_create(wtk_comm **out, int32_t device, int32_t rank, int32_t world, const uint8_t *id);
 void wtk_comm_destroy(wtk_comm *c);
 int wtk_allgather_tracks(wtk_comm *c, const float *local_dev, int32_t n_local, float *all_dev, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Experiment evaluation on the device: the background of an experiment and the precise tracking error of a log, bit-exact to the
+ * reference's numpy code, from frames already resident in device memory (no per-frame host reads, no worm-view image files).
+ * Both enqueue on `stream`; neither synchronises nor allocates.
+ *
+ * wtk_background  replaces BGExtractor.calc_background (its median / mean step)   dataset/bg_extractor.py:18-75
+ *     bg[i] = per-byte median (WTK_BG_MEDIAN: np.median(...).astype(uint8), i.e. floor((a + b) / 2) of the two middle values for even
+ *     n) or mean (WTK_BG_MEAN: floor(sum / n)) of byte i over the probe frames.  frames_dev [n_frames][frame_bytes] (gray or BGR, taken
+ *     as flat bytes); probe_idx_dev [n_probes] frame ids in [0, n_frames) (the caller's to check), or NULL for frames 0 .. n_probes-1.
+ *     n_probes: 1 .. 65535 for the median (uint16 counts), 1 .. 2^24 for the mean (uint32 sums); a larger n is an error, never a
+ *     wrapped result.
+ * wtk_precise_error  replaces ErrorCalculator.calculate_precise per row             eval/error_calculator.py:64-160
+ *     row r: the worm box and the microscope box (xywh; float32, or float64 with boxes_are_f64) discretised as BoxUtils.discretize
+ *     (bbox_utils.py:118-167: floor / ceil, clip to H x W, zero-area boxes illegal), total = pixels of the worm crop of frame
+ *     frame_nums[r] with |frame - bg| > diff_thresh, inside = those in the worm / microscope intersection;
+ *     err[r] = 1 - inside / total (float64), 0 where total = 0, NaN where the worm box is illegal or frame_nums[r] is outside
+ *     [0, n_frames) (those rows are also added to *n_bad_frame_dev, nullable).  counts_dev [n_rows][2] = (total, inside), nullable.
+ *     frames_dev [n_frames][H][W] gray, bg_dev [H][W].  err is PER ROW; the reference's own return value shifts the legal rows'
+ *     errors to the front (see wtracker_amd/evaluation.py, layout="reference").
+ * ------------------------------------------------------------------------------------------ */
+#define WTK_BG_MEDIAN 0
+#define WTK_BG_MEAN 1
+int wtk_background(const uint8_t *frames_dev, int32_t n_frames, int64_t frame_bytes, const int32_t *probe_idx_dev, int32_t n_probes,
+                   int32_t method, uint8_t *bg_dev, void *stream);
+int wtk_precise_error(const uint8_t *frames_dev, int32_t n_frames, int32_t H, int32_t W, const uint8_t *bg_dev,
+                      const void *worm_xywh_dev, const void *mic_xywh_dev, int32_t boxes_are_f64,
+                      const int32_t *frame_nums_dev, int32_t n_rows, double diff_thresh, double *err_dev,
+                      int32_t *counts_dev, int32_t *n_bad_frame_dev, void *stream);
 
 #ifdef __cplusplus
 }

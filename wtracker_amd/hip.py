@@ -61,6 +61,7 @@ SYMBOLS = [
     "wtk_release_cached_memory", "wtk_recheck_select_counted", "wtk_recheck_enqueue", "wtk_recheck_scatter",
     "wtk_hybrid_create", "wtk_hybrid_destroy", "wtk_hybrid_set_margin", "wtk_hybrid_predict", "wtk_hybrid_predict_views", "wtk_hybrid_flush",
     "wtk_hybrid_pending", "wtk_hybrid_counters", "wtk_hybrid_config", "wtk_hybrid_hold",
+    "wtk_background", "wtk_precise_error",
 ]
 
 
@@ -200,6 +201,8 @@ def load() -> C.CDLL:
     lib.wtk_hybrid_hold.argtypes = [vp, i32]
     lib.wtk_hybrid_counters.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.wtk_hybrid_config.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(f32)]
+    lib.wtk_background.argtypes = [vp, i32, C.c_int64, vp, i32, i32, vp, vp]
+    lib.wtk_precise_error.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, vp, i32, C.c_double, vp, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -341,6 +344,26 @@ def track_training_pairs(track_dev, n_frames: int, row0: int, n_rows: int, input
     yi = np.ascontiguousarray(pred_frames, dtype=np.int32)
     _check(load().wtk_track_training_pairs(_ptr(track_dev), _track_is_f64(track_dev), n_frames, row0, n_rows, _ptr(xi), len(xi), _ptr(yi), len(yi),
                                            _ptr(x_dev), _ptr(y_dev), _ptr(keep_dev), C.c_void_p(stream)), "wtk_track_training_pairs")
+
+
+BG_MEDIAN, BG_MEAN = 0, 1  # WTK_BG_MEDIAN / WTK_BG_MEAN
+BG_MEDIAN_MAX_PROBES, BG_MEAN_MAX_PROBES = 65535, 1 << 24
+
+
+def background(frames_dev, n_frames: int, frame_bytes: int, probe_idx_dev, n_probes: int, method: int, bg_dev, stream: int = 0):
+    """bg_dev[frame_bytes] = per-byte median / mean of the probe frames (wtk_background); probe_idx_dev int32 [n_probes] or None (frames 0..n-1)."""
+    _check(load().wtk_background(_ptr(frames_dev), n_frames, frame_bytes, _ptr(probe_idx_dev), n_probes, method, _ptr(bg_dev), C.c_void_p(stream)),
+           "wtk_background")
+
+
+def precise_error(frames_dev, n_frames: int, H: int, W: int, bg_dev, worm_dev, mic_dev, frame_nums_dev, n_rows: int, diff_thresh: float, err_dev,
+                  counts_dev=None, n_bad_frame_dev=None, stream: int = 0):
+    """err_dev float64 [n_rows] = the precise error of every log row (wtk_precise_error); boxes float32 or float64 [n_rows, 4], both of one dtype."""
+    f64 = _track_is_f64(worm_dev)
+    if _track_is_f64(mic_dev) != f64:
+        raise WtkError("worm and microscope boxes must share one dtype")
+    _check(load().wtk_precise_error(_ptr(frames_dev), n_frames, H, W, _ptr(bg_dev), _ptr(worm_dev), _ptr(mic_dev), f64, _ptr(frame_nums_dev), n_rows,
+                                    float(diff_thresh), _ptr(err_dev), _ptr(counts_dev), _ptr(n_bad_frame_dev), C.c_void_p(stream)), "wtk_precise_error")
 
 
 # -------------------------------------------------------------------------------------------------
