@@ -1,9 +1,13 @@
 """TEST INFRASTRUCTURE: builds tests/hostsan/_build/hostsan_driver — the HOST side of every translation unit of libwtk_hip.so (hipcc --cuda-host-only:
 no device code is generated, kernels become launch stubs) with -fsanitize=address,undefined, linked against hip_stub.cpp (the no-op launch layer that
 models device memory and the stream / event / capture protocol) and driver.cpp (the shape matrix).  `python tests/hostsan/build.py [quick|full]` builds
-and runs it; tests/test_host_sanitizer.py does the same inside the CPU suite."""
+and runs it; tests/test_host_sanitizer.py does the same inside the CPU suite.  `python tests/hostsan/build.py trace [--record]` prints (writes to
+tests/golden/launch_trace.json) the launch trace of the quick matrix in each environment of ENVS: launches per kernel and one sha256 over the ordered
+launch lines of the stub (kernel, grid, block, dynamic LDS, stream ordinal, hash of the argument struct)."""
 from __future__ import annotations
 
+import hashlib
+import json
 import os
 import subprocess
 import sys
@@ -16,6 +20,17 @@ OUT = os.path.join(HERE, "_build")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CLANGXX = "/opt/rocm/lib/llvm/bin/clang++"
 SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-g", "-O1"]
+TRACE_FIXTURE = os.path.join(ROOT, "tests", "golden", "launch_trace.json")
+# the environments the quick matrix runs in (tests/test_host_sanitizer.py)
+ENVS = {
+    # a controller user's environment: eager launches, latency plan for small handles, launch choices timed at the first call of a batch size (the stub's
+    # timer returns a constant: every candidate of every launch is still launched and checked)
+    "default": {},
+    # the GPU suite's environment (tests/conftest.py): the throughput kernels on small handles
+    "suite-env": {"WTK_LATENCY_PLAN": "0", "WTK_NO_SK_MIXED": "1", "WTK_SMALL_NARROW": "0", "WTK_SK_AUTOTUNE": "0"},
+    # the latency plan as one launch per conv (the bit-identity reference of the grouped launches)
+    "ungrouped": {"WTK_SK_GROUP": "0", "WTK_SK_AUTOTUNE": "0"},
+}
 HOST_ONLY = ["--cuda-host-only", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function", "-Wno-unused-variable"]
 
 
@@ -86,8 +101,29 @@ def run(mode: str = "quick", env_extra: dict | None = None, timeout: int = 900) 
     return subprocess.run([exe, mode], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env, timeout=timeout)
 
 
+def trace(env_extra: dict) -> dict:
+    """Launch trace of the quick matrix (the two-thread section, whose launch order is the scheduler's, is left out by the driver)."""
+    r = run("quick", dict(env_extra, WTK_STUB_VERBOSE="1"))
+    if r.returncode != 0:
+        raise RuntimeError("\n".join(l for l in r.stdout.splitlines() if not l.startswith("launch "))[-3000:])
+    digest, kernels = hashlib.sha256(), {}
+    for line in r.stdout.splitlines():
+        if line.startswith("launch "):
+            digest.update(line.encode() + b"\n")
+            name = line.split()[1]
+            kernels[name] = kernels.get(name, 0) + 1
+    return {"launches": sum(kernels.values()), "sha256": digest.hexdigest(), "kernels": dict(sorted(kernels.items()))}
+
+
 if __name__ == "__main__":
     mode = sys.argv[1] if len(sys.argv) > 1 else "quick"
+    if mode == "trace":
+        text = json.dumps({name: trace(env) for name, env in ENVS.items()}, indent=1) + "\n"
+        if "--record" in sys.argv:
+            with open(TRACE_FIXTURE, "w") as f:
+                f.write(text)
+        print(text)
+        sys.exit(0)
     extra = dict(a.split("=", 1) for a in sys.argv[2:])
     r = run(mode, extra)
     print(r.stdout)

@@ -517,6 +517,7 @@ int main(int argc, char **argv) {
     run_matrix("shape matrix", cases, 3);
     hybrid_and_misc();
     schedule_shape();
+    stub_set_verbose(0); // the launch trace ends here: two threads interleave their launches in an order that is not the library's to decide
     two_threads();
     const int v = stub_violations();
     std::fprintf(stderr, "[hostsan] kernels launched: %llu (conv_sk %llu, window %llu, igemm %llu, front %llu, head %llu); peak device memory %.1f GB; violations %d; driver failures %d\n",

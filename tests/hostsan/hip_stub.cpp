@@ -102,6 +102,7 @@ struct Capture {
 
 struct StubStream {
     uint32_t magic = kStreamMagic;
+    int ordinal = 0; // order of creation (0: the legacy default stream): how the launch trace names a stream
     int device = 0;
     unsigned flags = 0;
     Capture *cap = nullptr; // open capture this stream belongs to
@@ -134,6 +135,7 @@ std::set<StubEvent *> g_events;
 std::set<StubExec *> g_execs;
 std::map<uint64_t, Capture *> g_captures; // open captures by id
 uint64_t g_next_capture = 1;
+int g_next_stream = 1;
 StubStream g_null_stream; // the legacy default stream
 int g_cur_device = 0;
 thread_local int t_device = 0;
@@ -205,6 +207,29 @@ struct CallConfig {
     hipStream_t stream;
 };
 thread_local std::vector<CallConfig> t_configs;
+
+// Launch trace (WTK_STUB_VERBOSE): FNV-1a over the bytes of a launch's argument struct.  An 8-byte word that points into a live allocation is hashed as
+// (allocation ordinal, offset), so the value does not depend on where the host's allocator put the regions.  The library zero-fills every argument
+// struct before it sets the fields: padding bytes are zeros, not stack garbage.
+uint64_t hash_args(const void *args, size_t bytes) {
+    uint64_t h = 0xcbf29ce484222325ull;
+    auto mix = [&h](uint64_t v, int n) {
+        for (int i = 0; i < n; ++i) h = (h ^ ((v >> (8 * i)) & 0xff)) * 0x100000001b3ull;
+    };
+    const unsigned char *b = static_cast<const unsigned char *>(args);
+    size_t i = 0;
+    for (; i + 8 <= bytes; i += 8) {
+        uint64_t w;
+        std::memcpy(&w, b + i, 8);
+        const auto *r = w ? find_region(reinterpret_cast<const void *>(w)) : nullptr;
+        if (r)
+            mix(r->second.id, 8), mix(w - r->first, 8);
+        else
+            mix(w, 8);
+    }
+    for (; i < bytes; ++i) mix(b[i], 1);
+    return h;
+}
 
 } // namespace
 
@@ -449,6 +474,7 @@ hipError_t hipStreamCreateWithFlags(hipStream_t *out, unsigned flags) {
     StubStream *s = new StubStream();
     s->flags = flags;
     s->device = t_device;
+    s->ordinal = g_next_stream++;
     g_streams.insert(s);
     *out = reinterpret_cast<hipStream_t>(s);
     return hipSuccess;
@@ -750,8 +776,10 @@ hipError_t hipLaunchKernel(const void *func, dim3 grid, dim3 block, void **args,
         return ret(hipErrorInvalidValue);
     }
     ++k.launches;
-    if (g_verbose) std::fprintf(stderr, "launch %s grid %u block %u lds %zu%s\n", k.name.c_str(), grid.x, block.x, shmem, s->cap ? " [captured]" : "");
-    stubchk::check_launch(k.name, grid, block, args);
+    const size_t arg_bytes = stubchk::check_launch(k.name, grid, block, args); // (0: not one of the argument structs launch_checks.inc knows)
+    if (g_verbose)
+        std::fprintf(stderr, "launch %s grid %u %u %u block %u %u %u lds %zu stream %d args %016llx%s\n", k.name.c_str(), grid.x, grid.y, grid.z, block.x, block.y,
+                     block.z, shmem, s->ordinal, (unsigned long long)(arg_bytes ? hash_args(args[0], arg_bytes) : 0), s->cap ? " [captured]" : "");
     enqueue(s, k.name.c_str());
     return hipSuccess;
 }

@@ -95,17 +95,21 @@ static void check_halo_args(const char *kn, const wtk::HaloArgs &a, int es, bool
     if (a.CoutPad < a.Cout) fail(kn, "CoutPad < Cout");
 }
 
-static void check_launch(const std::string &name, dim3 grid, dim3 block, void **args) {
+// returns the size of the kernel's argument struct (args[0]) for the launch trace, 0 for a kernel that is not listed here
+static size_t check_launch(const std::string &name, dim3 grid, dim3 block, void **args) {
     (void)grid, (void)block;
-    if (!args || !args[0]) return;
+    if (!args || !args[0]) return 0;
+    size_t bytes = 0;
     auto has = [&](const char *s) { return name.find(s) != std::string::npos; };
     if (has("conv_igemm_kernel")) {
+        bytes = sizeof(wtk::ConvArgs);
         const TArgs t = parse_targs(name, "conv_igemm_kernel");
         const auto &a = *reinterpret_cast<const wtk::ConvArgs *>(args[0]);
         // <T, BM, BN, WAVES_P, WAVES_C, bools..., SPLIT>: SPLIT is the last bool when there are 9 value arguments
         const bool split = t.ints.size() >= 9 && t.ints.back() == 1;
         check_conv_args("conv_igemm_kernel", a, t.f16 ? 2 : 4, split);
     } else if (has("conv_sk_kernel")) {
+        bytes = sizeof(wtk::SkGroupArgs);
         const TArgs t = parse_targs(name, "conv_sk_kernel"); // <SPLIT, BM, BN, WAVES_P, WAVES_C, NS>
         const bool split = !t.ints.empty() && t.ints[0] == 1;
         const int bm = t.ints.size() > 1 ? (int)t.ints[1] : 64, bn = t.ints.size() > 2 ? (int)t.ints[2] : 32;
@@ -139,26 +143,34 @@ static void check_launch(const std::string &name, dim3 grid, dim3 block, void **
         }
         if (blocks != grid.x) fail("conv_sk_kernel", "grid does not equal the sum of the members' grids");
     } else if (has("sk_finish_kernel")) {
+        bytes = sizeof(wtk::SkArgs);
         const auto &a = *reinterpret_cast<const wtk::SkArgs *>(args[0]);
         dev_ptr_ok(a.partial, (size_t)a.S * a.M * a.CoutPad * 4, "sk_finish_kernel", "partial");
     } else if (has("conv1x1_wide_kernel")) {
+        bytes = sizeof(wtk::ConvArgs);
         check_conv_args("conv1x1_wide_kernel", *reinterpret_cast<const wtk::ConvArgs *>(args[0]), 2, false);
     } else if (has("conv3x3_halo_kernel") || has("conv3x3_halo_pkernel")) {
+        bytes = sizeof(wtk::HaloArgs);
         const bool persistent = has("conv3x3_halo_pkernel");
         const TArgs t = parse_targs(name, persistent ? "conv3x3_halo_pkernel" : "conv3x3_halo_kernel");
         // conv3x3_halo_kernel<T, BN, NHALO, MINW, NWB, HROWS, BMT, TAIL, SPLIT>
         const bool split = !persistent && t.ints.size() >= 8 && t.ints.back() == 1;
         check_halo_args(persistent ? "conv3x3_halo_pkernel" : "conv3x3_halo_kernel", *reinterpret_cast<const wtk::HaloArgs *>(args[0]), t.f16 ? 2 : 4, split, false);
     } else if (has("conv3x3_ws64_kernel")) {
+        bytes = sizeof(wtk::HaloArgs);
         check_halo_args("conv3x3_ws64_kernel", *reinterpret_cast<const wtk::HaloArgs *>(args[0]), 2, false, false);
     } else if (has("conv3x3_s2_kernel")) {
+        bytes = sizeof(wtk::HaloArgs);
         const TArgs t = parse_targs(name, "conv3x3_s2_kernel"); // <BMT, SPLIT>
         check_halo_args("conv3x3_s2_kernel", *reinterpret_cast<const wtk::HaloArgs *>(args[0]), 2, t.ints.size() >= 2 && t.ints[1] == 1, true);
     } else if (has("conv3x3_c32_split_kernel")) {
+        bytes = sizeof(wtk::HaloArgs);
         check_halo_args("conv3x3_c32_split_kernel", *reinterpret_cast<const wtk::HaloArgs *>(args[0]), 2, true, false);
     } else if (has("conv3x3_c32_kernel")) {
+        bytes = sizeof(wtk::HaloArgs);
         check_halo_args("conv3x3_c32_kernel", *reinterpret_cast<const wtk::HaloArgs *>(args[0]), 2, false, false);
     } else if (has("front_fused_split_kernel") || has("front_fused_kernel")) {
+        bytes = sizeof(wtk::FrontArgs);
         const bool split = has("front_fused_split_kernel");
         const char *kn = split ? "front_fused_split_kernel" : "front_fused_kernel";
         const auto &a = *reinterpret_cast<const wtk::FrontArgs *>(args[0]);
@@ -169,6 +181,7 @@ static void check_launch(const std::string &name, dim3 grid, dim3 block, void **
         dev_ptr_ok(a.out, view_bytes((long long)a.N * (a.H / 4) * (a.W / 4), a.out_ld, a.out_coff, split ? 128 : 64, 2), kn, "out");
         if ((a.H % 4) || (a.W % 4)) fail(kn, "frame size not a multiple of 4");
     } else if (has("c2f32_fused_kernel")) {
+        bytes = sizeof(wtk::C2fArgs);
         const auto &a = *reinterpret_cast<const wtk::C2fArgs *>(args[0]);
         const long long px = (long long)a.N * a.H * a.W;
         dev_ptr_ok(a.cat, view_bytes(px, a.cat_ld, std::max(a.a_coff, a.b_coff), 32, 2), "c2f32_fused_kernel", "cat");
@@ -177,6 +190,7 @@ static void check_launch(const std::string &name, dim3 grid, dim3 block, void **
         dev_ptr_ok(a.w_cv2, (size_t)64 * a.Kpad_cv2 * 2, "c2f32_fused_kernel", "w_cv2");
         dev_ptr_ok(a.zeros, 16, "c2f32_fused_kernel", "zeros");
     } else if (has("stem_mfma_kernel")) {
+        bytes = sizeof(wtk::StemArgs);
         const TArgs t = parse_targs(name, "stem_mfma_kernel");
         const auto &a = *reinterpret_cast<const wtk::StemArgs *>(args[0]);
         dev_ptr_ok(a.frames, (size_t)a.N * a.H * a.W * a.C, "stem_mfma_kernel", "frames");
@@ -185,11 +199,13 @@ static void check_launch(const std::string &name, dim3 grid, dim3 block, void **
         dev_ptr_ok(a.bias, (size_t)a.Cout * 4, "stem_mfma_kernel", "bias");
         if (a.Ho * 2 != a.H || a.Wo * 2 != a.W) fail("stem_mfma_kernel", "Ho / Wo are not H / 2, W / 2");
     } else if (has("sppf_pool_kernel")) {
+        bytes = sizeof(wtk::PoolArgs);
         const TArgs t = parse_targs(name, "sppf_pool_kernel");
         const auto &a = *reinterpret_cast<const wtk::PoolArgs *>(args[0]);
         dev_ptr_ok(a.buf, (size_t)a.N * a.H * a.W * 4 * a.c * (t.f16 || a.split ? 2 : 4) * (a.split ? 2 : 1), "sppf_pool_kernel", "buf");
     } else if (has("head_select_kernel") || has("head_nms_kernel")) {
         const bool nms = has("head_nms_kernel");
+        bytes = nms ? sizeof(wtk::NmsArgs) : sizeof(wtk::HeadArgs);
         const char *kn = nms ? "head_nms_kernel" : "head_select_kernel";
         const wtk::HeadArgs &a = nms ? reinterpret_cast<const wtk::NmsArgs *>(args[0])->h : *reinterpret_cast<const wtk::HeadArgs *>(args[0]);
         long long A = 0;
@@ -218,22 +234,26 @@ static void check_launch(const std::string &name, dim3 grid, dim3 block, void **
             if (a.out_anchor) dev_ptr_ok(a.out_anchor, (size_t)a.N * 4, kn, "out_anchor");
         }
     } else if (has("view_letterbox_kernel")) {
+        bytes = sizeof(wtk::ViewLetterboxArgs);
         const auto &a = *reinterpret_cast<const wtk::ViewLetterboxArgs *>(args[0]);
         dev_ptr_ok(a.frames, (size_t)a.F * a.H * a.W * a.C, "view_letterbox_kernel", "frames");
         dev_ptr_ok(a.pos_xy, (size_t)a.N * 8, "view_letterbox_kernel", "pos_xy");
         if (a.frame_index) dev_ptr_ok(a.frame_index, (size_t)a.N * 4, "view_letterbox_kernel", "frame_index");
         dev_ptr_ok(a.dst, (size_t)a.N * a.Sh * a.Sw * a.C, "view_letterbox_kernel", "dst");
     } else if (has("letterbox_kernel")) {
+        bytes = sizeof(wtk::LetterboxArgs);
         const auto &a = *reinterpret_cast<const wtk::LetterboxArgs *>(args[0]);
         dev_ptr_ok(a.src, (size_t)a.N * a.H * a.W * a.C, "letterbox_kernel", "src");
         dev_ptr_ok(a.dst, (size_t)a.N * a.Sh * a.Sw * a.C, "letterbox_kernel", "dst");
     } else if (has("mlp_kernel")) {
+        bytes = sizeof(wtk::MlpArgs);
         const auto &a = *reinterpret_cast<const wtk::MlpArgs *>(args[0]);
         dev_ptr_ok(a.params, (size_t)a.n_params * 4, "mlp_kernel", "params");
         dev_ptr_ok(a.layers, (size_t)a.n_layers * sizeof(wtk::MlpLayerDev), "mlp_kernel", "layers");
         if (a.x) dev_ptr_ok(a.x, (size_t)a.B * a.in_dim * 4, "mlp_kernel", "x");
         dev_ptr_ok(a.y, (size_t)a.B * a.out_dim * 4, "mlp_kernel", "y");
     }
+    return bytes;
 }
 
 } // namespace stubchk

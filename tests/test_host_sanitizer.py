@@ -7,6 +7,7 @@ every launch's argument struct against the live allocations — and tests/hostsa
 destroyed out of phase, two host threads).  What it pins: planning, weight packing, launcher geometry, allocation sizes against kernel extents, and the
 stream / event lifetime protocol of csrc/wtk_plan.hip / wtk_run.hip (the call of yolo_controller.py:64-90, 96-98 that must never die).
 Launches are eager: the library captures nothing, so the stub's capture model is exercised by the selftest (a caller may still capture its own stream)."""
+import json
 import os
 import sys
 
@@ -30,17 +31,33 @@ def test_launch_layer_flags_deliberate_violations():
     assert r.returncode == 0 and "11 of 11 deliberate violations flagged" in r.stdout, r.stdout[-3000:]
 
 
-@pytest.mark.parametrize("env", [
-    {},  # a controller user's environment: eager launches, latency plan for small handles, launch choices timed at the first call of a batch size (the stub's
-    #      timer returns a constant: every candidate of every launch is still launched and checked)
-    # the GPU suite's environment (tests/conftest.py): the throughput kernels on small handles
-    {"WTK_LATENCY_PLAN": "0", "WTK_NO_SK_MIXED": "1", "WTK_SMALL_NARROW": "0", "WTK_SK_AUTOTUNE": "0"},
-    {"WTK_SK_GROUP": "0", "WTK_SK_AUTOTUNE": "0"},  # the latency plan as one launch per conv (the bit-identity reference of the grouped launches)
-], ids=["default", "suite-env", "ungrouped"])
+@pytest.mark.parametrize("env", list(hostsan.ENVS.values()), ids=list(hostsan.ENVS))  # default, suite-env, ungrouped: see tests/hostsan/build.py
 def test_host_side_is_clean_over_the_shape_matrix(env):
     r = hostsan.run("quick", env)
     _ok(r)
     assert "violations 0; driver failures 0" in r.stdout, r.stdout[-3000:]
+
+
+def test_launch_trace_matches_the_recorded_one():
+    """Planning and launching are pinned launch by launch: in every environment of the quick matrix the stub's ordered launch lines (kernel instantiation,
+    grid, block, dynamic LDS, stream ordinal, hash of the argument struct with device pointers as (allocation, offset); the two-thread section left out)
+    hash to the sha256 recorded in tests/golden/launch_trace.json, which was recorded on the commit BEFORE wtk_run.hip was split into resolve / issue steps.
+    A change that leaves behaviour alone reproduces it.  A pull request that changes planning on purpose re-records it on its own tree with
+    `python tests/hostsan/build.py trace --record` and says so."""
+    with open(hostsan.TRACE_FIXTURE) as f:
+        want = json.load(f)
+    assert sorted(want) == sorted(hostsan.ENVS)
+    bad = []
+    for name, env in hostsan.ENVS.items():
+        got = hostsan.trace(env)
+        names = sorted(set(got["kernels"]) | set(want[name]["kernels"]))
+        diff = {k: (want[name]["kernels"].get(k, 0), got["kernels"].get(k, 0)) for k in names if want[name]["kernels"].get(k, 0) != got["kernels"].get(k, 0)}
+        print(f"{name}: {got['launches']} launches (recorded {want[name]['launches']}), sha256 {got['sha256']}")
+        for k, (w, g) in diff.items():
+            print(f"  {k}: recorded {w}, now {g}")
+        if got["sha256"] != want[name]["sha256"] or diff:
+            bad.append(name)
+    assert not bad, f"launch trace differs from tests/golden/launch_trace.json in {bad} (per-kernel count differences are printed above)"
 
 
 def test_host_side_is_clean_over_the_full_matrix():

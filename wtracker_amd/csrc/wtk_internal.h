@@ -115,6 +115,28 @@ struct Op {
     unsigned *sk_tickets = nullptr; // ... and the arrival counters of its tiles (zero between launches; null: one slice, or WTK_SK_FINISH=1)
 };
 
+// Kernel classes of the profile (wtk_yolo_get_kernel_profile; the values are ABI).  The public class 1 ("conv") of wtk_yolo_get_profile is the sum of
+// PROF_IGEMM, PROF_HALO, PROF_FUSED and PROF_C32.
+enum ProfClass {
+    PROF_STEM = 0,
+    PROF_IGEMM = 1, // conv_igemm, conv_sk, conv1x1_wide, the strided window kernel
+    PROF_POOL = 2,
+    PROF_HEAD = 3,
+    PROF_HALO = 4,  // conv3x3_halo (+ fused tails), conv3x3_ws64
+    PROF_FUSED = 5, // fused front / C2f tail
+    PROF_C32 = 6,   // conv3x3_c32
+};
+
+// What one conv op of a forward pass launches at a batch size (wtk_run.hip: resolve_conv decides, issue_conv enqueues): the launcher, the profile class
+// and the filled arguments — `a` for the implicit-GEMM family and split-K, `g` (next to the `a` it was derived from) for the window kernels.
+enum LaunchKind { L_IGEMM, L_IGEMM_SPLIT, L_WIDE_1X1, L_HALO, L_HALO_SPLIT, L_C32, L_C32_SPLIT, L_WS64, L_S2WIN, L_S2WIN_SPLIT, L_SK };
+struct ConvLaunch {
+    LaunchKind kind;
+    ProfClass cls;
+    int cfg; // L_IGEMM, L_IGEMM_SPLIT: the tile configuration (ConvCfg)
+    wtk::ConvArgs a;
+    wtk::HaloArgs g;
+};
 
 struct wtk_yolo {
     int device = 0;
@@ -186,9 +208,7 @@ struct wtk_yolo {
     int *status_dev = nullptr;  // ... and the device's address of the same word
     int status_static = 0;      // flags fixed at create time (none today)
     int profiling = 0;
-    // kernel ids of the profile: 0 stem, 1 conv_igemm, 2 pool, 3 head, 4 conv3x3_halo (+ fused tails), 5 fused front / C2f tail,
-    // 6 conv3x3_c32; the public class 1 ("conv") of wtk_yolo_get_profile is the sum of 1, 4, 5, 6
-    static constexpr int kProfKernels = 7, kProfEvents = 96;
+    static constexpr int kProfKernels = 7, kProfEvents = 96; // (one slot per ProfClass)
     hipEvent_t ev[kProfEvents];
     // concurrency: the P3 / P4 Detect towers run on a side stream next to the PAN path
     // Side streams of one forward pass (op.side = index, 0 = the caller's stream): 1 / 2 = P3 / P4 Detect towers (they only need t15 / t18).  The pair is

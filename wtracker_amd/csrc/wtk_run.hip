@@ -65,6 +65,7 @@ static int run_head(wtk_yolo *h, int B, int H, int W, float conf, float *out_xyw
     a.conf_logit = conf > 0.f && conf < 1.f ? std::log(conf / (1.f - conf)) : (conf <= 0.f ? -INFINITY : INFINITY);
     if (nms) {
         NmsArgs q;
+        std::memset(&q, 0, sizeof(q));
         q.h = a;
         q.iou = nms->iou, q.max_det = nms->max_det;
         q.scratch_score = h->nms_score, q.scratch_cls = h->nms_cls, q.scratch_box = h->nms_box;
@@ -86,8 +87,6 @@ static int ensure_nms_scratch(wtk_yolo *h, hipStream_t st) {
     return 0;
 }
 
-// Enqueue one forward pass (letterbox, stem, convs, pool, head) on `st`.  No allocation, no synchronisation
-// (profiling mode excepted): safe inside a caller's stream capture.
 // The pair of side streams is shared by every handle of the process on a device (ensure_side_streams).  Two host threads (ctypes releases the GIL)
 // that enqueue on it at the same time would interleave their feature-event waits and tower launches on the shared pair.  Every enqueue that touches
 // the pair holds this lock; a single-threaded caller (the bench, the controllers) never contends on it.
@@ -120,426 +119,431 @@ static int ensure_side_streams(wtk_yolo *h) {
     return 0;
 }
 
+// ---- resolve: what a conv op launches at batch B (ConvLaunch, wtk_internal.h).  Nothing here touches a stream or changes the handle. ----
+
+// the conv of `op` as the implicit-GEMM / split-K launchers take it (split handles: pseudo-channel arguments)
+static ConvArgs conv_args(const wtk_yolo *h, const Op &op, int B) {
+    const Buf &ib = h->bufs[op.in_buf], &ob = h->bufs[op.out_buf];
+    ConvArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.in = ib.ptr, a.in_ld = ib.C, a.in_coff = op.in_coff;
+    a.N = B, a.H = ib.h, a.W = ib.w, a.Cin = op.cin;
+    a.Ho = ob.h, a.Wo = ob.w, a.Cout = op.cout, a.CoutPad = op.cout_pad;
+    a.KH = a.KW = op.k, a.stride = op.stride, a.pad = op.k / 2;
+    a.w = op.w, a.bias = op.bias, a.zeros = h->zero_page, a.n_dyn = h->n_dyn;
+    a.out = ob.ptr, a.out_ld = ob.C, a.out_coff = op.out_coff, a.out_f32 = ob.f32;
+    if (op.out2_buf >= 0) a.out2 = h->bufs[op.out2_buf].ptr, a.out2_ld = h->bufs[op.out2_buf].C, a.out2_coff = op.out2_coff;
+    if (op.in2_buf >= 0) a.in2 = h->bufs[op.in2_buf].ptr, a.in2_ld = h->bufs[op.in2_buf].C, a.in2_coff = op.in2_coff, a.in2_split = op.in2_split;
+    if (op.res_buf >= 0) a.res = h->bufs[op.res_buf].ptr, a.res_ld = h->bufs[op.res_buf].C, a.res_coff = op.res_coff;
+    a.act = op.act, a.K = op.K, a.Kpad = op.Kpad;
+    a.M = (long long)B * ob.h * ob.w;
+    a.tile_w = op.tile_w;
+    if (op.tile_w) {
+        const int th = conv_cfg_bm(op.cfg) / op.tile_w;
+        a.tiles_x = (ob.w + op.tile_w - 1) / op.tile_w, a.tiles_y = (ob.h + th - 1) / th;
+    }
+    if (h->split) {
+        // pseudo-channels: every channel count / offset of a split tensor doubles (an fp32 output keeps its real layout)
+        a.in_ld *= 2, a.in_coff *= 2, a.Cin *= 2, a.K *= 2, a.Kpad *= 2;
+        a.in2_ld *= 2, a.in2_coff *= 2, a.in2_split *= 2;
+        a.res_ld *= 2, a.res_coff *= 2, a.out2_ld *= 2, a.out2_coff *= 2;
+        if (!a.out_f32) a.out_ld *= 2, a.out_coff *= 2;
+    }
+    return a;
+}
+
+// ... as conv_sk_kernel takes it (the plan marks only convs that fit: anything else is an internal error)
+static int sk_args(const wtk_yolo *h, const Op &op, int B, ConvArgs &a) {
+    a = conv_args(h, op, B);
+    a.tile_w = 0;
+    if (!conv_sk_eligible(a, h->split)) return fail("internal: conv " + std::to_string(&op - h->ops.data()) + " of the latency plan does not fit conv_sk_kernel");
+    return 0;
+}
+
+// ... and as the window kernels take it on an H x W map, strip geometry apart.  Tensor views, Cin and Kpad come from `a`: a split handle's pseudo-channels
+// are doubled in conv_args alone.  A fused 1x1 tail rides along.
+static HaloArgs halo_args(const wtk_yolo *h, const Op &op, const ConvArgs &a, int H, int W) {
+    HaloArgs g;
+    std::memset(&g, 0, sizeof(g));
+    g.in = a.in, g.in_ld = a.in_ld, g.in_coff = a.in_coff;
+    g.N = a.N, g.H = H, g.W = W, g.Cin = a.Cin;
+    g.Cout = op.cout, g.CoutPad = op.cout_pad;
+    g.w = op.w, g.bias = op.bias;
+    g.out = a.out, g.out_ld = a.out_ld, g.out_coff = a.out_coff;
+    g.out2 = a.out2, g.out2_ld = a.out2_ld, g.out2_coff = a.out2_coff;
+    g.res = a.res, g.res_ld = a.res_ld, g.res_coff = a.res_coff;
+    g.act = op.act, g.Kpad = a.Kpad;
+    g.n_dyn = h->n_dyn, g.zeros = h->zero_page;
+    if (op.tail_op >= 0) {
+        const Op &t = h->ops[op.tail_op];
+        g.tail_w = t.w, g.tail_bias = t.bias, g.tail_kpad = t.Kpad;
+        g.tail_out = h->bufs[t.out_buf].ptr, g.tail_ld = h->bufs[t.out_buf].C, g.tail_coff = t.out_coff;
+        g.tail_cout = t.cout, g.tail_f32 = h->bufs[t.out_buf].f32;
+        if (h->split) { // pseudo-channels for the split weights (and for a split output; the fp32 head logits keep their real layout)
+            g.tail_kpad *= 2;
+            if (!g.tail_f32) g.tail_ld *= 2, g.tail_coff *= 2;
+        }
+    }
+    return g;
+}
+
+// strided 3x3: the parity-plane window kernel; the geometry lives on the OUTPUT map (stacked images, one strip)
+static HaloArgs s2win_args(const wtk_yolo *h, const Op &op, const ConvArgs &a) {
+    HaloArgs g = halo_args(h, op, a, a.Ho, a.Wo);
+    g.S = a.Wo, g.pitch = a.Wo + 1, g.strips = 1, g.bm = 256;
+    g.blocks_per_strip = (int)(((long long)a.N * (a.Ho + 1) * g.pitch + 255) / 256);
+    if (2LL * g.blocks_per_strip * (op.cout_pad / 128) <= h->num_cus) { // small maps: half-size blocks fill the chip
+        g.bm = 128;
+        g.blocks_per_strip = (int)(((long long)a.N * (a.Ho + 1) * g.pitch + 127) / 128);
+    }
+    return g;
+}
+
+// stride-1 3x3 on an LDS-resident window (op.halo 1: conv3x3_halo.hip, 2: conv3x3_c32.hip): the kernel of the family, its strip geometry and tile shape
+static void resolve_window(const wtk_yolo *h, const Op &op, ConvLaunch &r) {
+    const int B = r.a.N, H = r.a.H, W = r.a.W;
+    HaloArgs &g = r.g;
+    g = halo_args(h, op, r.a, H, W);
+    g.slabs = h->split ? 3 : h->halo_slabs, g.persist_cus = h->halo_persist ? h->num_cus : 0;
+    if (op.halo == 1 && h->use_ws64 && h->halo_slabs == 3 &&
+        ws64_eligible(op.k, op.stride, op.cin, op.cout, op.cout_pad, h->is_f16, op.out2_buf >= 0, op.tail_op >= 0)) {
+        halo_geometry_stacked(B, H, W, ws64_rows_max(), &g.S, &g.pitch, &g.strips, &g.blocks_per_strip);
+        // worth it when every group of a persistent block gets at least two tiles (weights are staged once per block)
+        if ((long long)g.strips * g.blocks_per_strip >= 4LL * h->num_cus) {
+            r.kind = L_WS64; // g.bm stays 0 (the weave schedules of round 3 lost: the round-2 schedule)
+            return;
+        }
+    }
+    const int rows_max = (op.halo == 2 && h->split) ? c32_split_rows_max() : (op.halo == 2 || h->split) ? kHaloRowsMax : halo_rows_max(op.cout, h->halo_slabs);
+    if (op.halo == 2) {
+        halo_geometry(H, W, rows_max, &g.S, &g.pitch, &g.strips, &g.blocks_per_strip);
+        r.kind = h->split ? L_C32_SPLIT : L_C32;
+        return;
+    }
+    r.kind = h->split ? L_HALO_SPLIT : L_HALO;
+    halo_geometry_stacked(B, H, W, rows_max, &g.S, &g.pitch, &g.strips, &g.blocks_per_strip);
+    if (h->halo_slabs == 3 || h->split) {
+        // small maps: halve the blocks when 256-pixel blocks leave at least half of the CUs without work
+        const long long tiles = (long long)g.strips * g.blocks_per_strip * (op.cout_pad / (h->split ? split_halo_cout_tile(op.cout) : halo_cout_tile(op.cout)));
+        if (h->halo_small_blocks && 2 * tiles <= h->num_cus) {
+            g.bm = 128;
+            halo_geometry_stacked(B, H, W, rows_max, &g.S, &g.pitch, &g.strips, &g.blocks_per_strip, 128);
+            // still under half of the CUs with 128-pixel blocks (a small handle's cycle batch on the 24 x 24 maps): 64-cout tiles as well —
+            // each block then walks the same taps over half the couts
+            if (h->small_narrow && h->split && op.tail_op < 0 && op.cout_pad % 128 == 0 && 2LL * g.strips * g.blocks_per_strip * (op.cout_pad / 128) <= h->num_cus)
+                g.narrow = 1;
+        }
+    }
+    // fp32 handles: the exact-fp32 matrix instructions make these layers arithmetic bound, so a grid on under three quarters of the CUs (a small
+    // handle's 48 x 48 maps: 141-150 blocks of 128 / 192 couts) is cut into 64-cout tiles (Detect P3 first convs 205 us, class tower 139 us before)
+    if (h->small_narrow && !h->split && op.tail_op < 0 && op.cout_pad % 64 == 0 && halo_cout_tile(op.cout) != 64 &&
+        4LL * g.strips * g.blocks_per_strip * (op.cout_pad / halo_cout_tile(op.cout)) <= 3LL * h->num_cus)
+        g.narrow = 1;
+    // Small f16x3 handles: the 64-cout window tiles on the six-slab ring with fragment prefetch (conv3x3_halo.hip; bit-identical to the
+    // three-slab kernel).  A cycle batch's 24 x 24 layers 19.4 -> 15.9 us each; the 256-pixel tiles and the large handles measure the
+    // same either way (profiles/r05_notes.md section 7), so those keep the three-slab kernel.  WTK_HALO_DEEP: 0 off, 1 small handles
+    // (default), 2 every handle; read when the handle is created.
+    if (h->halo_deep) g.deep = 1;
+}
+
+// The kernel of one conv op at batch B, its profile class and its arguments: every eligibility test and occupancy rule, in the order they apply.
+static int resolve_conv(const wtk_yolo *h, const Op &op, int B, ConvLaunch &r) {
+    const Buf &ib = h->bufs[op.in_buf], &ob = h->bufs[op.out_buf];
+    r.cls = op.sk ? PROF_IGEMM : (op.halo == 2 ? PROF_C32 : (op.halo ? PROF_HALO : PROF_IGEMM));
+    r.cfg = op.cfg, r.kind = L_IGEMM;
+    if (op.sk) {
+        r.kind = L_SK;
+        return sk_args(h, op, B, r.a);
+    }
+    ConvArgs &a = r.a;
+    a = conv_args(h, op, B);
+    const bool plain = op.res_buf < 0 && op.out2_buf < 0 && op.in2_buf < 0, halves = ib.h == 2 * ob.h && ib.w == 2 * ob.w;
+    if (h->split && !op.halo && h->use_s2win && halves && split_s2win_eligible(op.k, op.stride, op.cin, op.cout, op.cout_pad, ob.w, plain && !ob.f32)) {
+        r.kind = L_S2WIN_SPLIT; // split operands: the parity-plane window kernel on pseudo-channels
+        r.g = s2win_args(h, op, a);
+    } else if (h->split && !op.halo) {
+        r.kind = L_IGEMM_SPLIT;
+        // a small handle's 128 x 128-tile layer whose grid leaves a third of the CUs idle: 64-cout tiles, twice the blocks (same K order: same bits)
+        if (h->small_narrow && r.cfg == CFG_128x128 && !a.in2 && !a.tile_w && 3 * ((a.M + 127) / 128) * (a.CoutPad / 128) <= 2LL * h->num_cus) r.cfg = CFG_128x64;
+    } else if (op.halo) {
+        resolve_window(h, op, r);
+    } else if (h->use_s2win && op.tail_op < 0 && s2win_eligible(op.k, op.stride, op.cin, op.cout, op.cout_pad, h->is_f16, ob.w, plain) && halves) {
+        r.kind = L_S2WIN;
+        r.g = s2win_args(h, op, a);
+    } else if (op.tail_op >= 0) { // implicit GEMM with the 1x1 behind it fused into its epilogue
+        const Op &t = h->ops[op.tail_op];
+        a.tail_w = t.w, a.tail_bias = t.bias, a.tail_kpad = t.Kpad, a.tail_act = t.act;
+        a.tail_out = h->bufs[t.out_buf].ptr, a.tail_ld = h->bufs[t.out_buf].C, a.tail_coff = t.out_coff;
+    } else if (h->use_wide && conv1x1_wide_eligible(a, h->is_f16) && a.CoutPad >= 256 && ((a.M + 255) / 256) * (a.CoutPad / 128) >= 384) {
+        r.kind = L_WIDE_1X1;
+    }
+    return 0;
+}
+
+// key of a launch's cached choice (sk_choices, sk_cands, tune_ms, tune_key): a dependency level of lat_sched, or kOpKeyBase + the index of an op launched alone
+constexpr long long kOpKeyBase = 100000;
+static long long choice_key(long long launch, int B) { return (launch << 24) | (long long)B; }
+
+// ---- issue: the resolved launch on stream `st`.  Nothing is decided here. ----
+static int issue_conv(wtk_yolo *h, const Op &op, const ConvLaunch &r, hipStream_t st) {
+    switch (r.kind) {
+    case L_IGEMM: HIP_TRY(launch_conv(r.a, r.cfg, h->is_f16, st)); break;
+    case L_IGEMM_SPLIT: HIP_TRY(launch_conv_split(r.a, r.cfg, st)); break;
+    case L_WIDE_1X1: HIP_TRY(launch_conv1x1_wide(r.a, st)); break;
+    case L_HALO: HIP_TRY(launch_conv3x3_halo(r.g, h->is_f16, st)); break;
+    case L_HALO_SPLIT: HIP_TRY(launch_conv3x3_halo_split(r.g, st)); break;
+    case L_C32: HIP_TRY(launch_conv3x3_c32(r.g, st)); break;
+    case L_C32_SPLIT: HIP_TRY(launch_conv3x3_c32_split(r.g, st)); break;
+    case L_S2WIN: HIP_TRY(launch_conv3x3_s2(r.g, st)); break;
+    case L_S2WIN_SPLIT: HIP_TRY(launch_conv3x3_s2_split(r.g, st)); break;
+    case L_WS64:
+#ifdef WTK_WS64_STAMPS
+        if (std::getenv("WTK_WS64_STAMPS")) {
+            if (!g_dbg_stamps) HIP_TRY(hipMalloc(&g_dbg_stamps, kDbgStampBytes));
+            HaloArgs g = r.g;
+            g.dbg_stamps = g_dbg_stamps;
+            HIP_TRY(launch_conv3x3_ws64(g, h->num_cus, st));
+            break;
+        }
+#endif
+        HIP_TRY(launch_conv3x3_ws64(r.g, h->num_cus, st));
+        break;
+    case L_SK: {
+        const SkMember one{r.a, op.sk_atoms, op.sk_partial, op.sk_tickets};
+        HIP_TRY(launch_conv_sk_group(&one, 1, h->split, h->num_cus, h->sk_force_tile, h->sk_force_form, st, &h->sk_choices[choice_key(kOpKeyBase + (&op - h->ops.data()), r.a.N)]));
+        break;
+    }
+    }
+    return 0;
+}
+
 // `vs` != nullptr: the batch rows are camera views of full frames (wtk_yolo_predict_views) — crop + letterbox in one kernel.
 struct ViewSrc {
     const int32_t *pos_xy, *frame_index;
     int view_w, view_h, n_frames;
 };
-static int yolo_enqueue_pass(wtk_yolo *h, const uint8_t *frames_dev, int32_t B, int32_t H, int32_t W, int32_t C, float conf, float *out_xywh,
-                             float *out_conf, int32_t *out_anchor, hipStream_t st, const ViewSrc *vs, const NmsOut *nms) {
-    const uint8_t *net_in = frames_dev;
+
+// A forward pass while it is enqueued: its lanes and, in profiling mode, the event brackets and counters of the kernel classes.
+// Two lanes: the caller's stream runs backbone + PAN + the P5 tower; the P3 / P4 Detect towers run on the side streams as soon as their feature map is
+// complete and fill the tails of the small PAN kernels.  Profiling keeps everything on one stream so the per-class event brackets stay meaningful.
+struct Pass {
+    wtk_yolo *h;
+    const uint8_t *net_in; // the network-size frames
+    int B, C;
+    hipStream_t main_st;    // the caller's stream
+    bool two_lanes = false;
+    unsigned side_used = 0; // bit i: side_stream[i] carries work of this pass
+    int cur_class = -1, nev = 0;
+    int ev_class[wtk_yolo::kProfEvents];
+    long long launches[wtk_yolo::kProfKernels] = {};
+    double flops[wtk_yolo::kProfKernels] = {};
+    double op_flops(const Op &o) const { return 2.0 * B * o.macs_per_image; } // algorithmic: 2 x output pixels x cout x (cin x k x k)
+    void count(ProfClass cls, double fl = 0.0) { ++launches[cls], flops[cls] += fl; }
+};
+
+// profiling: the launches that follow belong to class `cls` (a new event bracket when the class changes)
+static int mark(Pass &p, ProfClass cls) {
+    if (!p.h->profiling || cls == p.cur_class || p.nev >= wtk_yolo::kProfEvents - 1) return 0;
+    HIP_TRY(hipEventRecord(p.h->ev[p.nev], p.main_st));
+    p.ev_class[p.nev++] = p.cur_class = cls;
+    return 0;
+}
+
+// letterbox (or view crop + letterbox) into the staging image when the frames are not network-size already; H x W becomes the image scale_boxes maps back to
+static int enqueue_input(Pass &p, const uint8_t *frames_dev, int32_t &H, int32_t &W, const ViewSrc *vs) {
+    wtk_yolo *h = p.h;
+    float g, px, py;
     if (vs) {
         ViewLetterboxArgs va;
+        std::memset(&va, 0, sizeof(va));
         va.frames = frames_dev, va.frame_index = vs->frame_index, va.pos_xy = vs->pos_xy, va.dst = h->lb_dev;
-        va.N = B, va.H = H, va.W = W, va.C = C;
-        va.F = vs->n_frames;
-        va.view_w = vs->view_w, va.view_h = vs->view_h;
+        va.N = p.B, va.H = H, va.W = W, va.C = p.C, va.F = vs->n_frames;
+        va.view_w = vs->view_w, va.view_h = vs->view_h, va.Sh = h->S_h, va.Sw = h->S_w;
         va.rows = vs->view_w, va.cols = vs->view_h; // frame[y : y + w, x : x + h], view_controller.py:171
-        va.Sh = h->S_h, va.Sw = h->S_w;
-        float g, px, py;
         letterbox_geom(va.rows, va.cols, h->S_h, h->S_w, va.new_h, va.new_w, va.top, va.left, g, px, py);
-        HIP_TRY(launch_view_letterbox(va, st));
-        net_in = h->lb_dev;
+        HIP_TRY(launch_view_letterbox(va, p.main_st));
+        p.net_in = h->lb_dev;
         H = va.rows, W = va.cols; // from here on the "image" is the view: scale_boxes maps back to view pixels
     } else if (H != h->S_h || W != h->S_w) {
         LetterboxArgs la;
-        la.src = frames_dev;
-        la.dst = h->lb_dev;
-        la.N = B, la.H = H, la.W = W, la.C = C;
-        la.Sh = h->S_h, la.Sw = h->S_w;
-        float g, px, py;
+        std::memset(&la, 0, sizeof(la));
+        la.src = frames_dev, la.dst = h->lb_dev;
+        la.N = p.B, la.H = H, la.W = W, la.C = p.C, la.Sh = h->S_h, la.Sw = h->S_w;
         letterbox_geom(H, W, h->S_h, h->S_w, la.new_h, la.new_w, la.top, la.left, g, px, py);
-        HIP_TRY(launch_letterbox(la, st));
-        net_in = h->lb_dev;
+        HIP_TRY(launch_letterbox(la, p.main_st));
+        p.net_in = h->lb_dev;
     }
+    return 0;
+}
 
-    int cur_class = -1, nev = 0;
-    int ev_class[wtk_yolo::kProfEvents];
-    auto mark = [&](int cls) -> int {
-        if (!h->profiling || cls == cur_class) return 0;
-        if (nev >= wtk_yolo::kProfEvents - 1) return 0;
-        HIP_TRY(hipEventRecord(h->ev[nev], st));
-        ev_class[nev] = cls;
-        ++nev;
-        cur_class = cls;
+// ops[0..2] (stem, model.1, model.2.cv1) as ONE fused kernel
+static int enqueue_front(Pass &p) {
+    wtk_yolo *h = p.h;
+    if (mark(p, PROF_FUSED)) return 1;
+    const Op &o0 = h->ops[0], &o1 = h->ops[1], &o2 = h->ops[2];
+    FrontArgs f;
+    std::memset(&f, 0, sizeof(f));
+    f.frames = p.net_in, f.N = p.B, f.H = h->S_h, f.W = h->S_w, f.C = p.C;
+    f.w0 = o0.w, f.b0 = o0.bias;
+    f.w1 = o1.w, f.b1 = o1.bias, f.Kpad1 = o1.Kpad;
+    f.w2 = o2.w, f.b2 = o2.bias, f.Kpad2 = o2.Kpad;
+    f.out = h->bufs[o2.out_buf].ptr, f.out_ld = h->bufs[o2.out_buf].C, f.out_coff = o2.out_coff;
+    if (h->front_debug) f.dbg_t0 = h->bufs[o0.out_buf].ptr, f.dbg_t1 = h->bufs[o1.out_buf].ptr;
+    if (h->split) { // pseudo-channels (see conv_args)
+        f.Kpad1 *= 2, f.Kpad2 *= 2, f.out_ld *= 2, f.out_coff *= 2;
+        f.n_dyn = h->n_dyn, f.stem_split = 1;
+        HIP_TRY(launch_front_fused_split(f, h->num_cus, p.main_st));
+    } else
+        HIP_TRY(launch_front_fused(f, h->num_cus, p.main_st));
+    p.count(PROF_FUSED, p.op_flops(o0) + p.op_flops(o1) + p.op_flops(o2));
+    return 0;
+}
+
+// ops[3..5] (model.2.m.0.cv1, m.0.cv2, model.2.cv2) as ONE fused kernel, launched at op 5
+static int enqueue_c2f(Pass &p, const Op &op) {
+    wtk_yolo *h = p.h;
+    if (mark(p, PROF_FUSED)) return 1;
+    const Op &m1 = h->ops[3], &m2 = h->ops[4];
+    const Buf &cb = h->bufs[op.in_buf];
+    C2fArgs c;
+    std::memset(&c, 0, sizeof(c));
+    c.cat = cb.ptr, c.cat_ld = cb.C, c.a_coff = op.in_coff, c.b_coff = m1.in_coff;
+    c.N = p.B, c.H = cb.h, c.W = cb.w, c.zeros = h->zero_page;
+    c.w_m1 = m1.w, c.b_m1 = m1.bias, c.w_m2 = m2.w, c.b_m2 = m2.bias, c.Kpad_m = m1.Kpad;
+    c.w_cv2 = op.w, c.b_cv2 = op.bias, c.Kpad_cv2 = op.Kpad;
+    c.out = h->bufs[op.out_buf].ptr, c.out_ld = h->bufs[op.out_buf].C, c.out_coff = op.out_coff;
+    HIP_TRY(launch_c2f_fused(c, h->num_cus, p.main_st));
+    p.count(PROF_FUSED, p.op_flops(m1) + p.op_flops(m2) + p.op_flops(op));
+    return 0;
+}
+
+// one op of the plan in its own launch, on its lane
+static int enqueue_op(Pass &p, size_t oi) {
+    wtk_yolo *h = p.h;
+    const Op &op = h->ops[oi];
+    if (h->use_c2f && (oi == 3 || oi == 4)) return 0; // folded into the fused C2f tail launched at op 5
+    if (op.folded) return 0;                          // runs in the epilogue of the op that names it as tail_op
+    if (h->use_c2f && oi == 5) return enqueue_c2f(p, op);
+    hipStream_t st = p.main_st;
+    if (p.two_lanes && op.side) { // a Detect tower: on its side stream, behind its feature map
+        const int sidx = std::min(op.side, h->side_streams); // wtk_yolo_set_side_streams(1): both towers on side stream 1
+        st = h->side_stream[sidx];
+        if (op.wait_feat >= 0) HIP_TRY(hipStreamWaitEvent(st, h->feat_ev[op.wait_feat], 0));
+        p.side_used |= 1u << sidx;
+    }
+    if (op.kind == OP_STEM) {
+        if (mark(p, PROF_STEM)) return 1;
+        StemArgs a;
+        std::memset(&a, 0, sizeof(a));
+        a.frames = p.net_in, a.N = p.B, a.H = h->S_h, a.W = h->S_w, a.C = p.C;
+        a.w = op.w, a.bias = op.bias, a.out = h->bufs[op.out_buf].ptr;
+        a.Cout = op.cout, a.Ho = h->S_h / 2, a.Wo = h->S_w / 2;
+        a.out_split = a.in_split = h->split; // split store, split operands
+        a.n_dyn = h->n_dyn;
+        HIP_TRY(launch_stem(a, h->is_f16, st));
+        p.count(PROF_STEM, p.op_flops(op));
         return 0;
-    };
-    long long launches[wtk_yolo::kProfKernels] = {};
-    double flops[wtk_yolo::kProfKernels] = {};
-    auto op_flops = [&](const Op &o) { return 2.0 * B * o.macs_per_image; }; // algorithmic: 2 x output pixels x cout x (cin x k x k)
+    }
+    if (op.kind == OP_POOL) {
+        if (mark(p, PROF_POOL)) return 1;
+        const Buf &b = h->bufs[op.in_buf];
+        PoolArgs a;
+        std::memset(&a, 0, sizeof(a));
+        a.buf = b.ptr, a.N = p.B, a.H = b.h, a.W = b.w, a.c = op.cin, a.split = h->split;
+        HIP_TRY(launch_sppf_pool(a, h->is_f16, st));
+        p.count(PROF_POOL);
+        return 0;
+    }
+    ConvLaunch r;
+    if (resolve_conv(h, op, p.B, r) || mark(p, r.cls) || issue_conv(h, op, r, st)) return 1;
+    p.count(r.cls, p.op_flops(op) + (op.tail_op >= 0 ? p.op_flops(h->ops[op.tail_op]) : 0.0));
+    if (p.two_lanes && op.signal_feat >= 0) HIP_TRY(hipEventRecord(h->feat_ev[op.signal_feat], p.main_st));
+    return 0;
+}
 
-    // Two lanes: the caller's stream runs backbone + PAN + the P5 tower; the P3 / P4 Detect towers run on
-    // the side stream as soon as their feature map is complete and fill the tails of the small PAN kernels.
-    // Profiling keeps everything on one stream so the per-class event brackets stay meaningful.
-    // latency-plan handles (round 6): everything on the caller's stream, independent convs grouped per dependency level into one launch each
+// Latency-plan handles (round 6): everything on the caller's stream, the independent convs of a dependency level (sk_schedule) grouped into ONE launch; ops[0 .. 2]
+// (the front, when it did not run fused) first.  In a timing pass of sk_autotune (tune_pass >= 0) a grouped launch runs as its candidate number, between two events.
+static int enqueue_levels(Pass &p, size_t first_op) {
+    wtk_yolo *h = p.h;
+    for (size_t oi = first_op; oi < 3 && oi < h->ops.size(); ++oi)
+        if (enqueue_op(p, oi)) return 1;
+    for (size_t li = 0; li < h->lat_sched.size(); ++li) {
+        const std::vector<int> &L = h->lat_sched[li];
+        if (!(h->ops[L[0]].kind == OP_CONV && h->ops[L[0]].sk)) { // (the pool, or a conv that does not fit the split-K kernel: one op, its own launch)
+            if (enqueue_op(p, (size_t)L[0])) return 1;
+            continue;
+        }
+        if (mark(p, PROF_IGEMM)) return 1;
+        SkMember m[kSkGroupMax];
+        const int n = (int)L.size();
+        for (int k = 0; k < n; ++k) {
+            const Op &op = h->ops[L[k]];
+            m[k] = SkMember{ConvArgs(), op.sk_atoms, op.sk_partial, op.sk_tickets};
+            if (sk_args(h, op, p.B, m[k].a)) return 1;
+            p.flops[PROF_IGEMM] += p.op_flops(op);
+        }
+        const long long key = choice_key((long long)li, p.B);
+        SkChoice *choice = &h->sk_choices[key], cand;
+        hipEvent_t *ev = h->tune_pass >= 0 ? &h->tune_ev[2 * li] : nullptr;
+        if (ev) {
+            std::vector<SkChoice> &cands = h->sk_cands[key];
+            if (cands.empty()) {
+                cands.resize(kSkMaxCandidates);
+                cands.resize((size_t)std::max(conv_sk_enumerate(m, n, h->split, h->num_cus, h->sk_force_tile, h->sk_force_form, cands.data(), kSkMaxCandidates), 0));
+                if (cands.empty()) return fail("internal: no launch candidate for level " + std::to_string(li));
+                h->tune_ms[key].assign(cands.size(), 1e30f);
+            }
+            cand = cands[(size_t)h->tune_pass % cands.size()];
+            choice = &cand;
+            HIP_TRY(hipEventRecord(ev[0], p.main_st));
+        }
+        HIP_TRY(launch_conv_sk_group(m, n, h->split, h->num_cus, h->sk_force_tile, h->sk_force_form, p.main_st, choice));
+        if (ev) {
+            HIP_TRY(hipEventRecord(ev[1], p.main_st));
+            h->tune_key[li] = key;
+        }
+        p.count(PROF_IGEMM);
+    }
+    return 0;
+}
+
+// Enqueue one forward pass on `st`: input (letterbox / view) -> front -> ops or dependency levels -> join the side streams -> head -> profile read-out.
+// No allocation, no synchronisation (profiling mode excepted): safe inside a caller's stream capture.
+static int yolo_enqueue_pass(wtk_yolo *h, const uint8_t *frames_dev, int32_t B, int32_t H, int32_t W, int32_t C, float conf, float *out_xywh,
+                             float *out_conf, int32_t *out_anchor, hipStream_t st, const ViewSrc *vs, const NmsOut *nms) {
+    Pass p{h, frames_dev, B, C, st};
+    if (enqueue_input(p, frames_dev, H, W, vs)) return 1;
     const bool grouped = h->latency && h->sk_group && !h->lat_sched.empty();
     if (!grouped && h->use_side && h->side_streams > 0 && !h->profiling && ensure_side_streams(h)) return 1;
-    const bool two_lanes = !grouped && h->use_side && h->side_streams > 0 && h->side_stream[1] && !h->profiling;
+    p.two_lanes = !grouped && h->use_side && h->side_streams > 0 && h->side_stream[1] && !h->profiling;
     std::unique_lock<std::mutex> side_lock;
-    if (two_lanes) side_lock = std::unique_lock<std::mutex>(g_side_mu);
-    unsigned side_used = 0; // bit i: side_stream[i] carries work of this pass
-    hipStream_t main_st = st;
-    size_t first_op = 0;
-    if (h->use_front && reinterpret_cast<uintptr_t>(net_in) % 4 == 0) {
-        if (mark(5)) return 1;
-        const Op &o0 = h->ops[0], &o1 = h->ops[1], &o2 = h->ops[2];
-        FrontArgs f;
-        std::memset(&f, 0, sizeof(f));
-        f.frames = net_in;
-        f.N = B, f.H = h->S_h, f.W = h->S_w, f.C = C;
-        f.w0 = o0.w, f.b0 = o0.bias;
-        f.w1 = o1.w, f.b1 = o1.bias, f.Kpad1 = o1.Kpad;
-        f.w2 = o2.w, f.b2 = o2.bias, f.Kpad2 = o2.Kpad;
-        f.out = h->bufs[o2.out_buf].ptr;
-        f.out_ld = h->bufs[o2.out_buf].C;
-        f.out_coff = o2.out_coff;
-        if (h->front_debug) f.dbg_t0 = h->bufs[o0.out_buf].ptr, f.dbg_t1 = h->bufs[o1.out_buf].ptr;
-        if (h->split) { // pseudo-channels (see the conv path below)
-            f.Kpad1 *= 2, f.Kpad2 *= 2, f.out_ld *= 2, f.out_coff *= 2;
-            f.n_dyn = h->n_dyn;
-            f.stem_split = 1;
-            HIP_TRY(launch_front_fused_split(f, h->num_cus, st));
-        } else
-            HIP_TRY(launch_front_fused(f, h->num_cus, st));
-        ++launches[5];
-        flops[5] += op_flops(o0) + op_flops(o1) + op_flops(o2);
-        first_op = 3;
-    }
-    // the conv of `op` as the implicit-GEMM / split-K launchers take it (split handles: pseudo-channel arguments)
-    auto conv_args = [&](const Op &op) -> ConvArgs {
-        const Buf &ib = h->bufs[op.in_buf];
-        const Buf &ob = h->bufs[op.out_buf];
-        ConvArgs a;
-        std::memset(&a, 0, sizeof(a));
-        a.in = ib.ptr;
-        a.in_ld = ib.C;
-        a.in_coff = op.in_coff;
-        a.N = B, a.H = ib.h, a.W = ib.w, a.Cin = op.cin;
-        a.Ho = ob.h, a.Wo = ob.w, a.Cout = op.cout;
-        a.CoutPad = op.cout_pad;
-        a.KH = a.KW = op.k;
-        a.stride = op.stride;
-        a.pad = op.k / 2;
-        a.w = op.w;
-        a.bias = op.bias;
-        a.out = ob.ptr;
-        a.out_ld = ob.C;
-        a.out_coff = op.out_coff;
-        a.out_f32 = ob.f32;
-        a.n_dyn = h->n_dyn;
-        if (op.out2_buf >= 0) {
-            a.out2 = h->bufs[op.out2_buf].ptr;
-            a.out2_ld = h->bufs[op.out2_buf].C;
-            a.out2_coff = op.out2_coff;
-        }
-        if (op.in2_buf >= 0) {
-            a.in2 = h->bufs[op.in2_buf].ptr;
-            a.in2_ld = h->bufs[op.in2_buf].C;
-            a.in2_coff = op.in2_coff;
-            a.in2_split = op.in2_split;
-        }
-        if (op.res_buf >= 0) {
-            a.res = h->bufs[op.res_buf].ptr;
-            a.res_ld = h->bufs[op.res_buf].C;
-            a.res_coff = op.res_coff;
-        }
-        a.act = op.act;
-        a.K = op.K;
-        a.Kpad = op.Kpad;
-        a.M = (long long)B * ob.h * ob.w;
-        a.tile_w = op.tile_w;
-        a.zeros = h->zero_page;
-        if (op.tile_w) {
-            const int th = conv_cfg_bm(op.cfg) / op.tile_w;
-            a.tiles_x = (ob.w + op.tile_w - 1) / op.tile_w;
-            a.tiles_y = (ob.h + th - 1) / th;
-        }
-        if (h->split) {
-            // pseudo-channels: every channel count / offset of a split tensor doubles (an fp32 output keeps its real layout)
-            a.in_ld *= 2, a.in_coff *= 2, a.Cin *= 2, a.K *= 2, a.Kpad *= 2;
-            a.in2_ld *= 2, a.in2_coff *= 2, a.in2_split *= 2;
-            a.res_ld *= 2, a.res_coff *= 2, a.out2_ld *= 2, a.out2_coff *= 2;
-            if (!a.out_f32) a.out_ld *= 2, a.out_coff *= 2;
-        }
-        return a;
-    };
-    auto run_op = [&](size_t oi) -> int {
-        const Op &op = h->ops[oi];
-        if (h->use_c2f && (oi == 3 || oi == 4)) return 0; // folded into the fused C2f tail launched at op 5
-        if (op.folded) return 0;                          // runs in the epilogue of the op that names it as tail_op
-        if (h->use_c2f && oi == 5) {
-            if (mark(5)) return 1;
-            const Op &m1 = h->ops[3], &m2 = h->ops[4];
-            const Buf &cb = h->bufs[op.in_buf];
-            C2fArgs c;
-            std::memset(&c, 0, sizeof(c));
-            c.cat = cb.ptr, c.cat_ld = cb.C, c.a_coff = op.in_coff, c.b_coff = m1.in_coff;
-            c.N = B, c.H = cb.h, c.W = cb.w;
-            c.w_m1 = m1.w, c.b_m1 = m1.bias, c.w_m2 = m2.w, c.b_m2 = m2.bias, c.Kpad_m = m1.Kpad;
-            c.w_cv2 = op.w, c.b_cv2 = op.bias, c.Kpad_cv2 = op.Kpad;
-            c.out = h->bufs[op.out_buf].ptr, c.out_ld = h->bufs[op.out_buf].C, c.out_coff = op.out_coff;
-            c.zeros = h->zero_page;
-            HIP_TRY(launch_c2f_fused(c, h->num_cus, main_st));
-            ++launches[5];
-            flops[5] += op_flops(m1) + op_flops(m2) + op_flops(op);
-            return 0;
-        }
-        st = main_st;
-        if (two_lanes && op.side) {
-            const int sidx = std::min(op.side, h->side_streams); // wtk_yolo_set_side_streams(1): both towers on side stream 1
-            st = h->side_stream[sidx];
-            if (op.wait_feat >= 0) HIP_TRY(hipStreamWaitEvent(st, h->feat_ev[op.wait_feat], 0));
-            side_used |= 1u << sidx;
-        }
-        if (op.kind == OP_STEM) {
-            if (mark(0)) return 1;
-            StemArgs a;
-            a.frames = net_in;
-            a.N = B, a.H = h->S_h, a.W = h->S_w, a.C = C;
-            a.w = op.w;
-            a.bias = op.bias;
-            a.out = h->bufs[op.out_buf].ptr;
-            a.Cout = op.cout;
-            a.Ho = h->S_h / 2, a.Wo = h->S_w / 2;
-            a.out_split = h->split; // split store
-            a.in_split = h->split;  // split operands
-            a.n_dyn = h->n_dyn;
-            HIP_TRY(launch_stem(a, h->is_f16, st));
-            ++launches[0];
-            flops[0] += op_flops(op);
-        } else if (op.kind == OP_POOL) {
-            if (mark(2)) return 1;
-            const Buf &b = h->bufs[op.in_buf];
-            PoolArgs a;
-            a.buf = b.ptr;
-            a.N = B, a.H = b.h, a.W = b.w, a.c = op.cin;
-            a.split = h->split;
-            HIP_TRY(launch_sppf_pool(a, h->is_f16, st));
-            ++launches[2];
-        } else {
-            const int kid = op.sk ? 1 : (op.halo == 2 ? 6 : (op.halo ? 4 : 1));
-            if (mark(kid)) return 1;
-            const Buf &ib = h->bufs[op.in_buf];
-            const Buf &ob = h->bufs[op.out_buf];
-            ConvArgs a = conv_args(op);
-            if (op.sk) {
-                a.tile_w = 0;
-                if (!conv_sk_eligible(a, h->split)) return fail("internal: conv " + std::to_string(oi) + " of the latency plan does not fit conv_sk_kernel");
-                const SkMember one{a, op.sk_atoms, op.sk_partial, op.sk_tickets};
-                HIP_TRY(launch_conv_sk_group(&one, 1, h->split, h->num_cus, h->sk_force_tile, h->sk_force_form, st, &h->sk_choices[((long long)(oi + 100000) << 24) | (long long)B]));
-            } else if (h->split && !op.halo && h->use_s2win && ib.h == 2 * ob.h && ib.w == 2 * ob.w &&
-                split_s2win_eligible(op.k, op.stride, op.cin, op.cout, op.cout_pad, ob.w, op.res_buf < 0 && op.out2_buf < 0 && op.in2_buf < 0 && !ob.f32)) {
-                // strided 3x3, split operands: the parity-plane window kernel on pseudo-channels
-                HaloArgs g;
-                std::memset(&g, 0, sizeof(g));
-                g.in = a.in, g.in_ld = a.in_ld, g.in_coff = a.in_coff;
-                g.N = B, g.H = ob.h, g.W = ob.w, g.Cin = a.Cin;
-                g.Cout = op.cout, g.CoutPad = op.cout_pad;
-                g.w = op.w, g.bias = op.bias;
-                g.out = a.out, g.out_ld = a.out_ld, g.out_coff = a.out_coff;
-                g.act = op.act, g.Kpad = a.Kpad;
-                g.n_dyn = h->n_dyn;
-                g.S = ob.w, g.pitch = ob.w + 1, g.strips = 1;
-                g.bm = 256;
-                g.blocks_per_strip = (int)(((long long)B * (ob.h + 1) * g.pitch + 255) / 256);
-                if (2LL * g.blocks_per_strip * (op.cout_pad / 128) <= h->num_cus) {
-                    g.bm = 128;
-                    g.blocks_per_strip = (int)(((long long)B * (ob.h + 1) * g.pitch + 127) / 128);
-                }
-                g.zeros = h->zero_page;
-                HIP_TRY(launch_conv3x3_s2_split(g, st));
-            } else if (h->split && !op.halo) {
-                int cfg = op.cfg;
-                // a small handle's 128 x 128-tile layer whose grid leaves a third of the CUs idle: 64-cout tiles, twice the blocks (same K order: same bits)
-                if (h->small_narrow && h->split && cfg == CFG_128x128 && !a.in2 && !a.tile_w &&
-                    3 * ((a.M + 127) / 128) * (a.CoutPad / 128) <= 2LL * h->num_cus)
-                    cfg = CFG_128x64;
-                HIP_TRY(launch_conv_split(a, cfg, st));
-            } else if (op.halo) {
-                HaloArgs g;
-                std::memset(&g, 0, sizeof(g));
-                g.in = a.in, g.in_ld = a.in_ld, g.in_coff = a.in_coff;
-                g.N = B, g.H = ib.h, g.W = ib.w, g.Cin = op.cin;
-                g.Cout = op.cout, g.CoutPad = op.cout_pad;
-                g.w = op.w, g.bias = op.bias;
-                g.out = a.out, g.out_ld = a.out_ld, g.out_coff = a.out_coff;
-                g.out2 = a.out2, g.out2_ld = a.out2_ld, g.out2_coff = a.out2_coff;
-                g.res = a.res, g.res_ld = a.res_ld, g.res_coff = a.res_coff;
-                g.act = op.act, g.Kpad = op.Kpad;
-                g.n_dyn = h->n_dyn;
-                g.slabs = h->halo_slabs;
-                if (h->split) g.Cin = a.Cin, g.Kpad = a.Kpad, g.slabs = 3; // pseudo-channels
-                if (op.tail_op >= 0) {
-                    const Op &t = h->ops[op.tail_op];
-                    g.tail_w = t.w, g.tail_bias = t.bias, g.tail_kpad = t.Kpad;
-                    g.tail_out = h->bufs[t.out_buf].ptr, g.tail_ld = h->bufs[t.out_buf].C, g.tail_coff = t.out_coff;
-                    g.tail_cout = t.cout;
-                    g.tail_f32 = h->bufs[t.out_buf].f32;
-                    if (h->split) { // pseudo-channels for the split weights (and for a split output; the fp32 head logits keep their real layout)
-                        g.tail_kpad *= 2;
-                        if (!g.tail_f32) g.tail_ld *= 2, g.tail_coff *= 2;
-                    }
-                }
-                g.persist_cus = h->halo_persist ? h->num_cus : 0;
-                const int rows_max = (op.halo == 2 && h->split) ? c32_split_rows_max() : (op.halo == 2 || h->split) ? kHaloRowsMax : halo_rows_max(op.cout, h->halo_slabs);
-                bool ws64 = false;
-                if (op.halo == 1 && h->use_ws64 && h->halo_slabs == 3 &&
-                    ws64_eligible(op.k, op.stride, op.cin, op.cout, op.cout_pad, h->is_f16, op.out2_buf >= 0, op.tail_op >= 0)) {
-                    halo_geometry_stacked(B, ib.h, ib.w, ws64_rows_max(), &g.S, &g.pitch, &g.strips, &g.blocks_per_strip);
-                    // worth it when every group of a persistent block gets at least two tiles (weights are staged once per block)
-                    ws64 = (long long)g.strips * g.blocks_per_strip >= 4LL * h->num_cus;
-                }
-                if (ws64) {
-                    g.zeros = h->zero_page;
-                    g.bm = 0; // (the weave schedules of round 3 lost: the round-2 schedule)
-#ifdef WTK_WS64_STAMPS
-                    if (std::getenv("WTK_WS64_STAMPS")) {
-                        if (!g_dbg_stamps) HIP_TRY(hipMalloc(&g_dbg_stamps, kDbgStampBytes));
-                        g.dbg_stamps = g_dbg_stamps;
-                    }
-#endif
-                    HIP_TRY(launch_conv3x3_ws64(g, h->num_cus, st));
-                } else if (op.halo == 2) {
-                    halo_geometry(ib.h, ib.w, rows_max, &g.S, &g.pitch, &g.strips, &g.blocks_per_strip);
-                } else {
-                    halo_geometry_stacked(B, ib.h, ib.w, rows_max, &g.S, &g.pitch, &g.strips, &g.blocks_per_strip);
-                    if (h->halo_slabs == 3 || h->split) {
-                        // small maps: halve the blocks when 256-pixel blocks leave at least half of the CUs without work
-                        const long long tiles = (long long)g.strips * g.blocks_per_strip * (op.cout_pad / (h->split ? split_halo_cout_tile(op.cout) : halo_cout_tile(op.cout)));
-                        if (h->halo_small_blocks && 2 * tiles <= h->num_cus) {
-                            g.bm = 128;
-                            halo_geometry_stacked(B, ib.h, ib.w, rows_max, &g.S, &g.pitch, &g.strips, &g.blocks_per_strip, 128);
-                            // still under half of the CUs with 128-pixel blocks (a small handle's cycle batch on the 24 x 24 maps): 64-cout tiles as well —
-                            // each block then walks the same taps over half the couts
-                            if (h->small_narrow && h->split && op.tail_op < 0 && op.cout_pad % 128 == 0 &&
-                                2LL * g.strips * g.blocks_per_strip * (op.cout_pad / 128) <= h->num_cus)
-                                g.narrow = 1;
-                        }
-                    }
-                }
-                // fp32 handles: the exact-fp32 matrix instructions make these layers arithmetic bound, so a grid on under three quarters of the CUs (a small
-                // handle's 48 x 48 maps: 141-150 blocks of 128 / 192 couts) is cut into 64-cout tiles (Detect P3 first convs 205 us, class tower 139 us before)
-                if (h->small_narrow && !h->split && !ws64 && op.halo == 1 && op.tail_op < 0 && op.cout_pad % 64 == 0 && halo_cout_tile(op.cout) != 64 &&
-                    4LL * g.strips * g.blocks_per_strip * (op.cout_pad / halo_cout_tile(op.cout)) <= 3LL * h->num_cus)
-                    g.narrow = 1;
-                // Small f16x3 handles: the 64-cout window tiles on the six-slab ring with fragment prefetch (conv3x3_halo.hip; bit-identical to the
-                // three-slab kernel).  A cycle batch's 24 x 24 layers 19.4 -> 15.9 us each; the 256-pixel tiles and the large handles measure the
-                // same either way (profiles/r05_notes.md section 7), so those keep the three-slab kernel.  WTK_HALO_DEEP: 0 off, 1 small handles
-                // (default), 2 every handle; read when the handle is created.
-                if (h->halo_deep && op.halo == 1 && !ws64) g.deep = 1;
-                g.zeros = h->zero_page;
-                if (ws64) {
-                } else if (h->split && op.halo == 2)
-                    HIP_TRY(launch_conv3x3_c32_split(g, st));
-                else if (h->split)
-                    HIP_TRY(launch_conv3x3_halo_split(g, st));
-                else if (op.halo == 2)
-                    HIP_TRY(launch_conv3x3_c32(g, st));
-                else
-                    HIP_TRY(launch_conv3x3_halo(g, h->is_f16, st));
-            } else if (h->use_s2win && op.tail_op < 0 &&
-                       s2win_eligible(op.k, op.stride, op.cin, op.cout, op.cout_pad, h->is_f16, ob.w, op.res_buf < 0 && op.out2_buf < 0 && op.in2_buf < 0) &&
-                       ib.h == 2 * ob.h && ib.w == 2 * ob.w) {
-                // strided 3x3: parity-plane window kernel; the geometry lives on the OUTPUT map (stacked images, one strip)
-                HaloArgs g;
-                std::memset(&g, 0, sizeof(g));
-                g.in = a.in, g.in_ld = a.in_ld, g.in_coff = a.in_coff;
-                g.N = B, g.H = ob.h, g.W = ob.w, g.Cin = op.cin;
-                g.Cout = op.cout, g.CoutPad = op.cout_pad;
-                g.w = op.w, g.bias = op.bias;
-                g.out = a.out, g.out_ld = a.out_ld, g.out_coff = a.out_coff;
-                g.act = op.act, g.Kpad = op.Kpad;
-                g.n_dyn = h->n_dyn;
-                g.S = ob.w, g.pitch = ob.w + 1, g.strips = 1;
-                g.bm = 256;
-                g.blocks_per_strip = (int)(((long long)B * (ob.h + 1) * g.pitch + 255) / 256);
-                if (2LL * g.blocks_per_strip * (op.cout_pad / 128) <= h->num_cus) { // small maps: half-size blocks fill the chip
-                    g.bm = 128;
-                    g.blocks_per_strip = (int)(((long long)B * (ob.h + 1) * g.pitch + 127) / 128);
-                }
-                g.zeros = h->zero_page;
-                HIP_TRY(launch_conv3x3_s2(g, st));
-            } else if (op.tail_op >= 0) { // implicit GEMM with the 1x1 behind it fused into its epilogue
-                const Op &t = h->ops[op.tail_op];
-                a.tail_w = t.w, a.tail_bias = t.bias, a.tail_kpad = t.Kpad, a.tail_act = t.act;
-                a.tail_out = h->bufs[t.out_buf].ptr, a.tail_ld = h->bufs[t.out_buf].C, a.tail_coff = t.out_coff;
-                HIP_TRY(launch_conv(a, op.cfg, h->is_f16, st));
-            } else if (h->use_wide && conv1x1_wide_eligible(a, h->is_f16) && a.CoutPad >= 256 && ((a.M + 255) / 256) * (a.CoutPad / 128) >= 384) {
-                HIP_TRY(launch_conv1x1_wide(a, st));
-            } else {
-                HIP_TRY(launch_conv(a, op.cfg, h->is_f16, st));
-            }
-            ++launches[kid];
-            flops[kid] += op_flops(op) + (op.tail_op >= 0 ? op_flops(h->ops[op.tail_op]) : 0.0);
-            if (two_lanes && op.signal_feat >= 0) HIP_TRY(hipEventRecord(h->feat_ev[op.signal_feat], main_st));
-        }
-            return 0;
-    };
-    if (grouped) {
-        // latency plan: ONE stream, one launch per dependency level (sk_schedule): ops[0 .. 2] (the front, when it did not run fused) first
-        for (size_t oi = first_op; oi < 3 && oi < h->ops.size(); ++oi)
-            if (run_op(oi)) return 1;
-        for (size_t li = 0; li < h->lat_sched.size(); ++li) {
-            const std::vector<int> &L = h->lat_sched[li];
-            if (!(h->ops[L[0]].kind == OP_CONV && h->ops[L[0]].sk)) { // (the pool, or a conv that does not fit the split-K kernel: one op, its own launch)
-                if (run_op((size_t)L[0])) return 1;
-                continue;
-            }
-            if (mark(1)) return 1;
-            SkMember m[kSkGroupMax];
-            for (size_t k = 0; k < L.size(); ++k) {
-                const Op &op = h->ops[L[k]];
-                m[k] = SkMember{conv_args(op), op.sk_atoms, op.sk_partial, op.sk_tickets};
-                m[k].a.tile_w = 0;
-                if (!conv_sk_eligible(m[k].a, h->split)) return fail("internal: conv " + std::to_string(L[k]) + " of the latency plan does not fit conv_sk_kernel");
-                flops[1] += op_flops(op);
-            }
-            const long long key = ((long long)li << 24) | (long long)B;
-            if (h->tune_pass >= 0) { // a timing pass of sk_autotune: this launch as its candidate number (pass mod candidates), between two events
-                std::vector<SkChoice> &cands = h->sk_cands[key];
-                if (cands.empty()) {
-                    cands.resize(kSkMaxCandidates);
-                    cands.resize((size_t)std::max(conv_sk_enumerate(m, (int)L.size(), h->split, h->num_cus, h->sk_force_tile, h->sk_force_form, cands.data(), kSkMaxCandidates), 0));
-                    if (cands.empty()) return fail("internal: no launch candidate for level " + std::to_string(li));
-                    h->tune_ms[key].assign(cands.size(), 1e30f);
-                }
-                SkChoice c = cands[(size_t)h->tune_pass % cands.size()];
-                HIP_TRY(hipEventRecord(h->tune_ev[2 * li], main_st));
-                HIP_TRY(launch_conv_sk_group(m, (int)L.size(), h->split, h->num_cus, h->sk_force_tile, h->sk_force_form, main_st, &c));
-                HIP_TRY(hipEventRecord(h->tune_ev[2 * li + 1], main_st));
-                h->tune_key[li] = key;
-            } else {
-                HIP_TRY(launch_conv_sk_group(m, (int)L.size(), h->split, h->num_cus, h->sk_force_tile, h->sk_force_form, main_st, &h->sk_choices[key]));
-            }
-            ++launches[1];
-        }
-    } else {
-        for (size_t oi = first_op; oi < h->ops.size(); ++oi)
-            if (run_op(oi)) return 1;
-    }
-    st = main_st;
+    if (p.two_lanes) side_lock = std::unique_lock<std::mutex>(g_side_mu);
+    const bool front = h->use_front && reinterpret_cast<uintptr_t>(p.net_in) % 4 == 0;
+    if (front && enqueue_front(p)) return 1;
+    const size_t first_op = front ? 3 : 0;
+    if (grouped && enqueue_levels(p, first_op)) return 1;
+    for (size_t oi = first_op; !grouped && oi < h->ops.size(); ++oi)
+        if (enqueue_op(p, oi)) return 1;
     for (int i = 1; i < wtk_yolo::kSideStreams; ++i)
-        if (side_used & (1u << i)) {
+        if (p.side_used & (1u << i)) {
             HIP_TRY(hipEventRecord(h->side_done[i], h->side_stream[i]));
-            HIP_TRY(hipStreamWaitEvent(main_st, h->side_done[i], 0));
+            HIP_TRY(hipStreamWaitEvent(st, h->side_done[i], 0));
         }
-    if (mark(3)) return 1;
+    if (mark(p, PROF_HEAD)) return 1;
     if (run_head(h, B, H, W, conf, out_xywh, out_conf, out_anchor, st, nms)) return 1;
-    ++launches[3];
-    if (h->profiling) {
-        if (nev < wtk_yolo::kProfEvents) {
-            HIP_TRY(hipEventRecord(h->ev[nev], st));
-            ev_class[nev] = -1;
-            ++nev;
-        }
-        HIP_TRY(hipEventSynchronize(h->ev[nev - 1]));
-        for (int i = 0; i + 1 < nev; ++i) {
-            float ms = 0.f;
-            HIP_TRY(hipEventElapsedTime(&ms, h->ev[i], h->ev[i + 1]));
-            h->prof_ms[ev_class[i]] += ms;
-        }
-        for (int i = 0; i < wtk_yolo::kProfKernels; ++i) h->prof_launches[i] += launches[i], h->prof_flops[i] += flops[i];
+    p.count(PROF_HEAD);
+    if (!h->profiling) return 0;
+    if (p.nev < wtk_yolo::kProfEvents) { // close the last bracket
+        HIP_TRY(hipEventRecord(h->ev[p.nev], st));
+        p.ev_class[p.nev++] = -1;
     }
+    HIP_TRY(hipEventSynchronize(h->ev[p.nev - 1]));
+    for (int i = 0; i + 1 < p.nev; ++i) {
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, h->ev[i], h->ev[i + 1]));
+        h->prof_ms[p.ev_class[i]] += ms;
+    }
+    for (int i = 0; i < wtk_yolo::kProfKernels; ++i) h->prof_launches[i] += p.launches[i], h->prof_flops[i] += p.flops[i];
     return 0;
 }
 
@@ -606,6 +610,15 @@ static int yolo_enqueue(wtk_yolo *h, const uint8_t *frames_dev, int32_t B, int32
     return yolo_enqueue_pass(h, frames_dev, B, H, W, C, conf, out_xywh, out_conf, out_anchor, st, vs, nms);
 }
 
+// staging image of the network input (letterbox / view), allocated once
+static int ensure_staging(wtk_yolo *h, hipStream_t st) {
+    if (h->lb_cap) return 0;
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMalloc(&h->lb_dev, (size_t)h->max_batch * h->S_h * h->S_w * 3));
+    h->lb_cap = (size_t)h->max_batch * h->S_h * h->S_w * 3;
+    return 0;
+}
+
 extern "C" int wtk_yolo_predict(wtk_yolo *h, const uint8_t *frames_dev, int32_t B, int32_t H, int32_t W, int32_t C, float conf, float iou,
                                 int32_t max_det, float *out_xywh, float *out_conf, int32_t *out_anchor, void *stream) {
     (void)iou; // with max_det == 1 the IoU threshold cannot change the survivor
@@ -617,11 +630,7 @@ extern "C" int wtk_yolo_predict(wtk_yolo *h, const uint8_t *frames_dev, int32_t 
     if (H <= 0 || W <= 0) return fail("wtk_yolo_predict: bad frame size");
     DEVICE_GUARD(h);
     hipStream_t st = (hipStream_t)stream;
-    if ((H != h->S_h || W != h->S_w) && h->lb_cap == 0) { // letterbox staging image, allocated once
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipMalloc(&h->lb_dev, (size_t)h->max_batch * h->S_h * h->S_w * 3));
-        h->lb_cap = (size_t)h->max_batch * h->S_h * h->S_w * 3;
-    }
+    if ((H != h->S_h || W != h->S_w) && ensure_staging(h, st)) return 1;
     return yolo_enqueue(h, frames_dev, B, H, W, C, conf, out_xywh, out_conf, out_anchor, st);
 }
 
@@ -637,11 +646,7 @@ extern "C" int wtk_yolo_predict_nms(wtk_yolo *h, const uint8_t *frames_dev, int3
     if (H <= 0 || W <= 0) return fail("wtk_yolo_predict_nms: bad frame size");
     DEVICE_GUARD(h);
     hipStream_t st = (hipStream_t)stream;
-    if ((H != h->S_h || W != h->S_w) && h->lb_cap == 0) {
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipMalloc(&h->lb_dev, (size_t)h->max_batch * h->S_h * h->S_w * 3));
-        h->lb_cap = (size_t)h->max_batch * h->S_h * h->S_w * 3;
-    }
+    if ((H != h->S_h || W != h->S_w) && ensure_staging(h, st)) return 1;
     if (ensure_nms_scratch(h, st)) return 1;
     const NmsOut nms{iou, max_det, out_cls, out_count};
     return yolo_enqueue(h, frames_dev, B, H, W, C, conf, out_xywh, out_conf, out_anchor, st, nullptr, &nms);
@@ -660,11 +665,7 @@ extern "C" int wtk_yolo_predict_views(wtk_yolo *h, const uint8_t *frames_dev, in
     if (!frame_index_dev && B > n_frames) return fail("wtk_yolo_predict_views: without frame_index the batch rows are frames 0..B-1");
     DEVICE_GUARD(h);
     hipStream_t st = (hipStream_t)stream;
-    if (h->lb_cap == 0) { // staging image of the network input, allocated once
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipMalloc(&h->lb_dev, (size_t)h->max_batch * h->S_h * h->S_w * 3));
-        h->lb_cap = (size_t)h->max_batch * h->S_h * h->S_w * 3;
-    }
+    if (ensure_staging(h, st)) return 1;
     const ViewSrc vs{pos_xy_dev, frame_index_dev, view_w, view_h, n_frames};
     return yolo_enqueue(h, frames_dev, B, H, W, C, conf, out_xywh, out_conf, out_anchor, st, &vs);
 }
@@ -830,7 +831,6 @@ extern "C" int wtk_yolo_decode_host(wtk_yolo *h, const float *box_host, const fl
 // scatter concatenated [B][A][.] fp32 logits into the per-level head buffers (storage dtype): the test hook behind the two
 // decode entry points
 static int upload_head_logits(wtk_yolo *h, const float *box_host, const float *cls_host, int32_t B) {
-    // scatter the concatenated [B][A][.] logits into the per-level head buffers (storage dtype)
     const int A = h->anchors;
     size_t a0 = 0;
     for (int l = 0; l < 3; ++l) {
