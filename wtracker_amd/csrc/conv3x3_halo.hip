@@ -225,7 +225,7 @@ __global__ __launch_bounds__(512, MINW) void conv3x3_halo_kernel(const HaloArgs 
     // s_load + s_waitcnt (~0.2 us each) in front of the block's first LDS-DMA request.
     asm volatile("" ::"s"(a.in), "s"(a.w), "s"(a.bias), "s"(a.zeros), "s"(a.in_ld), "s"(a.in_coff), "s"(a.N), "s"(a.H), "s"(a.W), "s"(a.Cin), "s"(a.CoutPad),
                  "s"(a.Kpad), "s"(a.S), "s"(a.pitch), "s"(a.strips), "s"(a.d_strips.mul), "s"(a.d_strips.sh1), "s"(a.d_strips.sh2), "s"(a.d_pitch.mul),
-                 "s"(a.d_pitch.sh1), "s"(a.d_pitch.sh2), "s"(a.d_nct.mul), "s"(a.d_nct.sh1), "s"(a.d_nct.sh2), "s"(a.d_h1.mul), "s"(a.d_h1.sh1), "s"(a.d_h1.sh2), "s"(a.grid));
+                 "s"(a.d_pitch.sh1), "s"(a.d_pitch.sh2), "s"(a.d_nct.mul), "s"(a.d_nct.sh1), "s"(a.d_nct.sh2), "s"(a.d_h1.mul), "s"(a.d_h1.sh1), "s"(a.d_h1.sh2), "s"(a.grid), "s"(a.live_off));
     constexpr int CE = ElemH<T>::CE;
     constexpr int CCH = 8 * CE; // channels per 128-byte chunk
     // BN = 64: 8(P) x 1(C) waves of 32 px x 64 cout; BN = 128 / 192: 4(P) x 2(C) waves of 64 px x 64 / 96 cout
@@ -273,6 +273,14 @@ __global__ __launch_bounds__(512, MINW) void conv3x3_halo_kernel(const HaloArgs 
     const int rb = (int)fdiv(t, a.d_strips); // row blocks major, strips minor: the strips of a row block share input rows (L2)
     const int strip = (int)t - rb * a.strips;
     const int o0 = rb * BMT;
+    const char *zero_page = reinterpret_cast<const char *>(a.zeros);
+    if (a.live_off) { // live mask (sparse Detect box towers): one byte per 128-pixel unit of the strip, read as part of its aligned 32-bit word (a scalar load);
+                      // a block none of whose one (BMT = 128) or two (256: o0 / 128 is even) units is marked exits here, block-uniformly, like the blocks beyond
+                      // n_dyn above: no LDS-DMA issued, no barrier met.  The blocks that stay keep the tile the remap gave them.
+        const unsigned u = (unsigned)strip * (unsigned)a.live_ld + ((unsigned)o0 >> 7);
+        const unsigned wd = *reinterpret_cast<const unsigned *>(zero_page + a.live_off + (u & ~3u));
+        if (((wd >> ((u & 3u) * 8)) & (BMT == 256 ? 0xffffu : 0xffu)) == 0) return;
+    }
     const int xs = strip * a.S;
     const int pitch = a.pitch;
     const int halo_rows = BMT + 2 * pitch + 2;
@@ -282,7 +290,6 @@ __global__ __launch_bounds__(512, MINW) void conv3x3_halo_kernel(const HaloArgs 
 
     const T *in = reinterpret_cast<const T *>(a.in) + (long long)n_base * a.H * a.W * a.in_ld + a.in_coff;
     const T *wgt = reinterpret_cast<const T *>(a.w);
-    const char *zero_page = reinterpret_cast<const char *>(a.zeros);
 
     // ---- loop-invariant per-lane addressing (the inner loop must stay almost VALU-free: a wave64 VALU op
     // costs ~4 issue cycles against 16 per MFMA, so a few dozen address instructions per tap starve the
@@ -1914,6 +1921,8 @@ template <typename T, int BN, int NHALO, int MINW, int NWB, int HROWS, int BMT =
     const long long blocks = (long long)a.strips * a.blocks_per_strip * (a.CoutPad / BN);
     if (blocks <= 0 || blocks > 0x7fffffffLL) return hipErrorInvalidValue;
     if (BMT + 2 * a.pitch + 2 > HROWS || (long long)a.blocks_per_strip * BMT < (long long)a.N * (a.H + 1) * a.pitch) return hipErrorInvalidValue;
+    // live mask: word-aligned, and every unit a block looks at lies inside its strip's row of the mask
+    if (a.live_off && ((a.live_off & 3u) || (a.live_ld & 1) || (long long)a.live_ld * 128 < (long long)a.blocks_per_strip * BMT)) return hipErrorInvalidValue;
     a.d_nct = make_fastdiv((unsigned)(a.CoutPad / BN));
     a.d_bps = make_fastdiv((unsigned)a.blocks_per_strip);
     a.d_strips = make_fastdiv((unsigned)a.strips);

@@ -27,9 +27,10 @@ __device__ __forceinline__ void better(float &s, int &i, float s2, int i2) {
     }
 }
 
+// The scan of one frame's class logits by a 1024-thread block (head_select_kernel, head_select_kernel_sparse).  Returns true in the threads of the
+// first wave, which all hold the frame's result: best score, its anchor (0x7fffffff: none), its logit and the best logit among all OTHER anchors.
 template <typename T>
-__global__ __launch_bounds__(1024) void head_select_kernel(const HeadArgs a) {
-    const int n = blockIdx.x;
+__device__ __forceinline__ bool head_scan(const HeadArgs &a, int n, float &best, int &best_i, float &best_l, float &second) {
     const int A0 = a.lh[0] * a.lw[0], A1 = a.lh[1] * a.lw[1], A2 = a.lh[2] * a.lw[2];
     const int A = A0 + A1 + A2;
 
@@ -38,8 +39,8 @@ __global__ __launch_bounds__(1024) void head_select_kernel(const HeadArgs a) {
     // exactly 1.0f; neighbours a few ulp apart at ordinary logits) resolve to the LOWER anchor index.  So the order here is by score, as in
     // head_nms_kernel; the winner's logit and the best logit among all OTHER anchors are carried along for the decision margin, which stays
     // logit-based (ties with the winner count: margin <= 0).
-    float best = -INFINITY, best_l = -INFINITY, second = -INFINITY;
-    int best_i = 0x7fffffff;
+    best = -INFINITY, best_l = -INFINITY, second = -INFINITY;
+    best_i = 0x7fffffff;
     bool bad = false;
     auto merge = [](float &b, int &bi, float &bl, float &s2nd, float b2, int bi2, float bl2, float s2) __attribute__((always_inline)) {
         if (b2 > b || (b2 == b && bi2 < bi)) {
@@ -91,19 +92,20 @@ __global__ __launch_bounds__(1024) void head_select_kernel(const HeadArgs a) {
         wsec[threadIdx.x >> 6] = second;
     }
     __syncthreads();
-    if (threadIdx.x >= 64) return;
+    if (threadIdx.x >= 64) return false;
     best = ws[0];
     best_i = wi[0];
     best_l = wl[0];
     second = wsec[0];
 #pragma unroll
     for (int w = 1; w < 16; ++w) merge(best, best_i, best_l, second, ws[w], wi[w], wl[w], wsec[w]);
-    if (a.out_margin && threadIdx.x == 0) a.out_margin[n] = fminf(best_l - second, fabsf(best_l - a.conf_logit));
+    return true;
+}
 
-    // candidate iff score > conf (non_max_suppression `xc`)
-    const float score = best;
-    const bool keep = (best_i != 0x7fffffff) && (score > a.conf);
-
+// The row of frame n from its survivor (first wave of the block, lanes 0..63): DFL decode, scale_boxes, clip, xywh; the NaN row when nothing was kept.
+template <typename T>
+__device__ __forceinline__ void head_row(const HeadArgs &a, int n, bool keep, int best_i, float score) {
+    const int A0 = a.lh[0] * a.lw[0], A1 = a.lh[1] * a.lw[1], A2 = a.lh[2] * a.lw[2];
     // ---- DFL decode of the survivor: lanes 0..3 = sides l, t, r, b
     float dist = 0.f;
     int lvl = 0, j = 0;
@@ -174,6 +176,61 @@ __global__ __launch_bounds__(1024) void head_select_kernel(const HeadArgs a) {
     o[3] = by2 - by1;
     if (a.out_conf) a.out_conf[n] = score;
     if (a.out_anchor) a.out_anchor[n] = best_i;
+}
+
+template <typename T>
+__global__ __launch_bounds__(1024) void head_select_kernel(const HeadArgs a) {
+    const int n = blockIdx.x;
+    float best, best_l, second;
+    int best_i;
+    if (!head_scan<T>(a, n, best, best_i, best_l, second)) return;
+    if (a.out_margin && threadIdx.x == 0) a.out_margin[n] = fminf(best_l - second, fabsf(best_l - a.conf_logit));
+
+    // candidate iff score > conf (non_max_suppression `xc`)
+    const float score = best;
+    const bool keep = (best_i != 0x7fffffff) && (score > a.conf);
+    head_row<T>(a, n, keep, best_i, score);
+}
+
+// ---- the head around the sparse Detect box towers (wtk_kernels.h: HeadSparseArgs) ----
+template <typename T>
+__global__ __launch_bounds__(1024) void head_select_kernel_sparse(const HeadSparseArgs q) {
+    const HeadArgs &a = q.h;
+    const int n = blockIdx.x;
+    float best, best_l, second;
+    int best_i;
+    if (!head_scan<T>(a, n, best, best_i, best_l, second)) return;
+    if (threadIdx.x != 0) return;
+    if (a.out_margin) a.out_margin[n] = fminf(best_l - second, fabsf(best_l - a.conf_logit));
+    const bool keep = (best_i != 0x7fffffff) && (best > a.conf);
+    q.sel_anchor[n] = keep ? best_i : -1;
+    q.sel_score[n] = best;
+    if (!keep || (q.n_dyn && n >= *q.n_dyn)) return;
+    // what the box tower of the survivor's level must compute for this frame.  Flat output index of pixel (y, x) of image n in the stacked geometry:
+    // strip s = x / S, o = (n (H + 1) + y) pitch + (x - s S); unit o / 128 of strip s
+    const int A0 = a.lh[0] * a.lw[0], A1 = a.lh[1] * a.lw[1];
+    const int lvl = best_i < A0 ? 0 : (best_i < A0 + A1 ? 1 : 2);
+    const int j = best_i - (lvl == 0 ? 0 : (lvl == 1 ? A0 : A0 + A1));
+    const int H = a.lh[lvl], W = a.lw[lvl], S = q.S[lvl], pitch = q.pitch[lvl], ld = q.ld[lvl];
+    const int y = j / W, x = j % W;
+    unsigned char *live0 = q.live + q.off0[lvl], *live1 = q.live + q.off1[lvl];
+    for (int dy = -1; dy <= 1; ++dy)
+        for (int dx = -1; dx <= 1; ++dx) {
+            const int yy = y + dy, xx = x + dx;
+            if (yy < 0 || yy >= H || xx < 0 || xx >= W) continue; // padding: no pixel of box.0 behind it
+            const int s = xx / S;
+            const int u = s * ld + (((n * (H + 1) + yy) * pitch + (xx - s * S)) >> 7);
+            live0[u] = 1;
+            if (dy == 0 && dx == 0) live1[u] = 1;
+        }
+}
+
+// one wave per frame
+template <typename T>
+__global__ __launch_bounds__(64) void head_decode_kernel(const HeadSparseArgs q) {
+    const int n = blockIdx.x;
+    const int best_i = q.sel_anchor[n];
+    head_row<T>(q.h, n, best_i >= 0, best_i, q.sel_score[n]);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -340,6 +397,18 @@ hipError_t launch_head_nms(const NmsArgs &a, int is_f16, hipStream_t stream) {
         hipLaunchKernelGGL((head_nms_kernel<_Float16>), dim3(a.h.N), dim3(1024), 0, stream, a);
     else
         hipLaunchKernelGGL((head_nms_kernel<float>), dim3(a.h.N), dim3(1024), 0, stream, a);
+    return hipGetLastError();
+}
+
+// the Detect outputs are fp32 tensors in every mode
+hipError_t launch_head_select_sparse(const HeadSparseArgs &a, hipStream_t stream) {
+    if (a.h.N <= 0 || a.h.nc < 1 || a.h.cls_ld < a.h.nc || !a.live || !a.sel_anchor || !a.sel_score) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((head_select_kernel_sparse<float>), dim3(a.h.N), dim3(1024), 0, stream, a);
+    return hipGetLastError();
+}
+hipError_t launch_head_decode(const HeadSparseArgs &a, hipStream_t stream) {
+    if (a.h.N <= 0 || !a.sel_anchor || !a.sel_score || !a.h.out_xywh) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((head_decode_kernel<float>), dim3(a.h.N), dim3(64), 0, stream, a);
     return hipGetLastError();
 }
 

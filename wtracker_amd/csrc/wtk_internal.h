@@ -125,6 +125,7 @@ enum ProfClass {
     PROF_HALO = 4,  // conv3x3_halo (+ fused tails), conv3x3_ws64
     PROF_FUSED = 5, // fused front / C2f tail
     PROF_C32 = 6,   // conv3x3_c32
+    PROF_SPARSE = 7, // conv3x3_halo launches of the sparse Detect box towers: counted with 0 FLOPs (the host does not know how many tiles were live)
 };
 
 // What one conv op of a forward pass launches at a batch size (wtk_run.hip: resolve_conv decides, issue_conv enqueues): the launcher, the profile class
@@ -182,6 +183,20 @@ struct wtk_yolo {
     int use_wide = 1;  // WTK_NO_WIDE_1X1=1: every 1x1 conv through conv_igemm_kernel (A/B switch)
     int use_c2f = 0;   // ops[3..5] (model.2.m.0.cv1, m.0.cv2, model.2.cv2) run as ONE fused kernel (c2f_fused.hip)
     int use_front = 0; // ops[0..2] (stem, model.1, model.2.cv1) run as ONE fused kernel (front_fused.hip)
+    // Sparse Detect box towers (wtk_run.hip: resolve_sparse; DESIGN.md "Sparse box towers").  det[i]: the ops of level i's towers that a sparse call treats
+    // differently — op0 the shared first 3x3 of both towers (run as its class half in place, as its box half behind the head's selection), box1 / box2 the rest
+    // of the box tower.  The live mask, sel_anchor and sel_score belong to the handle (two lanes run two handles concurrently); the mask lies behind the zero
+    // page in the same allocation (HaloArgs::live_off).
+    int use_sparse_box = 1; // WTK_NO_SPARSE_BOX=1: every call dense (A/B and test switch)
+    struct DetLevel {
+        int op0 = -1, box1 = -1, box2 = -1;
+    } det[3];
+    size_t live_bytes = 0; // 0: this handle never runs sparse
+    int *sel_anchor = nullptr;
+    float *sel_score = nullptr;
+    int sparse_B = 0; // > 0: the last forward pass (of this batch size) left the box towers sparse; wtk_yolo_debug_head / _debug_tensor complete them first.
+                      // Host-side state, set when a pass is enqueued: eager passes only (a pass under stream capture stays dense, wtk_run.hip)
+    ConvLaunch sparse_done[6]; // ... by these launches: box.0 and box.1 + box.2 of the three levels as that pass resolved them, mask off
     int num_cus = 0;
     // Latency plan (small batches: the reference's own operating point, one B = cycle_frame_num call and one B = 1 call per cycle,
     // yolo_controller.py:96-98,108-109).  Chosen when the handle is created — max_batch <= 4 and a reference-precision dtype, WTK_LATENCY_PLAN=0/1, or the caller's word (wtk_yolo_create_planned) —
@@ -208,7 +223,7 @@ struct wtk_yolo {
     int *status_dev = nullptr;  // ... and the device's address of the same word
     int status_static = 0;      // flags fixed at create time (none today)
     int profiling = 0;
-    static constexpr int kProfKernels = 7, kProfEvents = 96; // (one slot per ProfClass)
+    static constexpr int kProfKernels = 8, kProfEvents = 96; // (one slot per ProfClass)
     hipEvent_t ev[kProfEvents];
     // concurrency: the P3 / P4 Detect towers run on a side stream next to the PAN path
     // Side streams of one forward pass (op.side = index, 0 = the caller's stream): 1 / 2 = P3 / P4 Detect towers (they only need t15 / t18).  The pair is
@@ -226,6 +241,17 @@ struct wtk_yolo {
 };
 
 namespace wtk {
+// Sparse box towers pay from a call size on.  The six masked launches behind the head each last at least one tile's walk and run one after the other on the
+// caller's stream, where the dense box towers of P3 / P4 ran beside the PAN path; what they save grows with the rounds of blocks the dense launches took.
+// Measured (profiles/r07_notes.md section 6, one caller, sparse against dense per call): -4.1 % where box.1 of P3 is 6.4 rounds of 256-pixel blocks over the CUs
+// (640 x 640, B = 64), +1.2 % at 1.7 rounds (B = 17), +4 .. 5 % at 0.6 .. 1.2 rounds (384 x 384, B = 15 / 32).  A straight line through the two 640 x 640
+// points crosses zero near 2.8 rounds; nothing was measured between them, so the rule keeps a margin: at least FOUR rounds (the line's -1 %).
+// h8 x w8: the P3 map; (h8 + 1) x (w8 + 1) per image is the stacked flat geometry of a one-strip map (halo_geometry_stacked), a few per cent under it for a
+// map cut into strips.  No CU count (a device that reports none): never sparse.
+constexpr int kSparseBlockPx = 256, kSparseMinRounds = 4;
+inline bool sparse_box_pays(int B, int h8, int w8, int num_cus) {
+    return num_cus > 0 && (long long)B * (h8 + 1) * (w8 + 1) >= (long long)kSparseMinRounds * kSparseBlockPx * num_cus;
+}
 // stream pool (wtk_plan.hip)
 int pooled_stream(int device, hipStream_t *s);
 void unpool_stream(int device, hipStream_t s);

@@ -304,9 +304,15 @@ struct HaloArgs {
     int deep;       // split window kernel, 64-cout x 128-pixel tiles without a fused tail: 1 = six-slab weight ring + fragment prefetch (156 KB of LDS)
     int narrow; // split window kernel: 1 = 64-cout tiles for a layer of 128-multiple couts (twice the blocks; for grids that leave most CUs idle)
     int grid; // blocks of the launch (filled by the launchers: reading gridDim.x costs the set-up one more scalar-load round trip)
+    // conv3x3_halo_kernel, nullable (0 = dense): byte offset from `zeros` of a device-side mask of LIVE 128-pixel units of the stacked flat geometry, one byte per
+    // unit, [strip][live_ld] — a block none of whose units is marked exits at once (the sparse Detect box towers, wtk_run.hip).  An offset and not a pointer: it
+    // sits in what used to be padding, so the argument struct of every dense launch keeps its size and its bytes.
+    unsigned live_off;
     const int *n_dyn; // nullable: device-side image count <= N (conv3x3_halo_kernel, conv3x3_s2_kernel): blocks whose tile starts beyond its last image exit at once
     FastDiv d_bps, d_strips, d_pitch, d_nct, d_h1; // filled by the launchers (d_h1: H + 1, conv3x3_halo.hip's stacked rows)
+    int live_ld; // units per strip of the live mask (an even number >= blocks_per_strip * bm / 128)
 };
+static_assert(sizeof(HaloArgs) == 288, "live_off / live_ld fill padding: the struct of a dense launch is what it was before the live mask");
 bool halo_eligible(int k, int stride, int cin, int is_f16);
 bool split_halo_eligible(int k, int stride, int cin, int cout); // split-fp16 operands (real channel counts)
 int split_halo_cout_tile(int cout_stored);
@@ -480,6 +486,23 @@ struct HeadArgs {
     int *status;      // nullable: sticky flags of the handle in pinned HOST memory (bit 0: a non-finite head logit was read; wtk_yolo_status)
 };
 hipError_t launch_head(const HeadArgs &a, int is_f16, hipStream_t stream);
+
+// The same head in two kernels around the SPARSE Detect box towers (max_det = 1 calls of throughput-plan handles, wtk_run.hip): head_select_kernel_sparse scans
+// the class logits as head_select_kernel does (same order, tie rule, margin, range guard), leaves the survivor of every frame in sel_anchor / sel_score and marks
+// the 128-pixel units of the window kernel's stacked flat geometry (halo_geometry_stacked) that the box tower of the survivor's level must compute: live1 = the
+// unit of the survivor's pixel (needed from box.1 + box.2), live0 = the units of its 3 x 3 neighbourhood inside the map (needed from box.0).  A frame without a
+// survivor marks nothing.  head_decode_kernel then reads the survivor's 64 box logits and writes the row exactly as the fused kernel does.
+struct HeadSparseArgs {
+    HeadArgs h;
+    unsigned char *live; // the handle's mask region, zero when head_select_kernel_sparse starts
+    int *sel_anchor;     // [N] survivor (anchor index over the three levels) or -1
+    float *sel_score;    // [N] its score
+    int S[3], pitch[3], ld[3];  // per level: strip width, row pitch, mask units per strip
+    unsigned off0[3], off1[3];  // per level: byte offsets of live0 / live1 in `live`
+    const int *n_dyn;           // nullable: frames beyond *n_dyn mark nothing
+};
+hipError_t launch_head_select_sparse(const HeadSparseArgs &a, hipStream_t stream);
+hipError_t launch_head_decode(const HeadSparseArgs &a, hipStream_t stream);
 
 // General greedy IoU NMS (ultralytics non_max_suppression, class-aware, best class per anchor) for max_det >= 1: HeadArgs plus
 // the per-image scratch and the multi-row outputs.  out_* rows beyond count[n] are NaN / 0 / -1.

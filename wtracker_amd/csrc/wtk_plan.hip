@@ -371,6 +371,7 @@ PlanSwitches read_switches(wtk_yolo *h) {
     h->sk_force_tile = tile >= 0 && tile <= 3 ? tile : -1;
     h->sk_force_form = form == 0 || form == 1 ? form : -1;
     h->front_debug = env_int("WTK_FRONT_DEBUG", 0) == 1;
+    h->use_sparse_box = env_int("WTK_NO_SPARSE_BOX", 0) != 1;
     PlanSwitches s;
     s.latency_plan = env_int("WTK_LATENCY_PLAN", -1);
     s.no_side_stream = env_int("WTK_NO_SIDE_STREAM", 0) == 1;
@@ -746,6 +747,7 @@ extern "C" int wtk_yolo_create_planned(wtk_yolo **out, const wtk_yolo_desc *d, i
                 c2.folded = 1;
             }
         }
+        if (!P.failed) h->det[i].op0 = (int)first_op, h->det[i].box1 = (int)first_op + 1, h->det[i].box2 = (int)first_op + 3;
         if (!P.failed && i < 2) { // P3 and P4 towers only need t15 / t18: independent of the rest of the PAN path
             for (size_t k = first_op; k < h->ops.size(); ++k) h->ops[k].side = i == 1 ? 2 : 1; // P4 tower: side stream 2 (folded onto stream 1 at launch time when the handle runs with one side stream)
             h->ops[first_op].wait_feat = i;
@@ -859,11 +861,29 @@ extern "C" int wtk_yolo_create_planned(wtk_yolo **out, const wtk_yolo_desc *d, i
         wtk_yolo_destroy(h);
         return fail("wtk_yolo_create: no pinned status word (hipHostMalloc failed, or more than 4096 live handles)");
     }
-    if (dev_alloc(h, &h->zero_page, 256)) {
+    // Live mask of the sparse box towers, behind the zero page: per level two arrays (box.0's units, box.1 + box.2's) of strips x ld bytes, ld = the
+    // 128-pixel units of a strip's stacked rows, rounded up to an even count (wtk_run.hip: resolve_sparse lays a call's arrays out the same way).
+    // Split (f16x3) throughput-plan handles only: there the shared first conv of a tower pair runs as three 64-cout tiles, so its box and class halves keep
+    // tile and bits; fp16 / fp32 run it as one 192-cout tile, whose halves would land on other instantiations.
+    // ... and only handles whose largest call reaches the size from which a sparse call pays (sparse_box_pays below; a per-call rule).
+    if (h->split && !h->latency && h->use_sparse_box && wtk::sparse_box_pays(h->max_batch, h->lh[0], h->lw[0], h->num_cus)) {
+        size_t total = 0;
+        for (int i = 0; i < 3; ++i) {
+            int S, pitch, strips, bps;
+            halo_geometry_stacked(h->max_batch, h->lh[i], h->lw[i], kHaloRowsMax, &S, &pitch, &strips, &bps, 256);
+            total += 2 * (((size_t)strips * 2 * bps + 3) & ~(size_t)3);
+        }
+        h->live_bytes = total;
+        if (dev_alloc(h, (void **)&h->sel_anchor, sizeof(int) * h->max_batch) || dev_alloc(h, (void **)&h->sel_score, sizeof(float) * h->max_batch)) {
+            wtk_yolo_destroy(h);
+            return 1;
+        }
+    }
+    if (dev_alloc(h, &h->zero_page, 256 + h->live_bytes)) {
         wtk_yolo_destroy(h);
         return 1;
     }
-    if (hipMemset(h->zero_page, 0, 256) != hipSuccess) {
+    if (hipMemset(h->zero_page, 0, 256 + h->live_bytes) != hipSuccess) {
         wtk_yolo_destroy(h);
         return fail("wtk_yolo_create: hipMemset failed");
     }
@@ -913,7 +933,7 @@ extern "C" int wtk_yolo_get_profile(wtk_yolo *h, int32_t kernel_class, double *t
     double ms = h->prof_ms[kernel_class];
     long long n = h->prof_launches[kernel_class];
     if (kernel_class == 1)
-        for (int k = 4; k < wtk_yolo::kProfKernels; ++k) ms += h->prof_ms[k], n += h->prof_launches[k];
+        for (int k = 4; k < wtk_yolo::kProfKernels; ++k) ms += h->prof_ms[k], n += h->prof_launches[k]; // (the sparse box-tower launches included)
     if (total_ms) *total_ms = ms;
     if (launches) *launches = n;
     return 0;

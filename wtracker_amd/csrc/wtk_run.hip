@@ -39,8 +39,7 @@ struct NmsOut {
     int max_det;
     int *out_cls, *out_count;
 };
-static int run_head(wtk_yolo *h, int B, int H, int W, float conf, float *out_xywh, float *out_conf, int *out_anchor, hipStream_t st,
-                    const NmsOut *nms = nullptr) {
+static HeadArgs head_args(wtk_yolo *h, int B, int H, int W, float conf, float *out_xywh, float *out_conf, int *out_anchor) {
     HeadArgs a;
     std::memset(&a, 0, sizeof(a));
     for (int i = 0; i < 3; ++i) {
@@ -63,6 +62,11 @@ static int run_head(wtk_yolo *h, int B, int H, int W, float conf, float *out_xyw
     a.out_margin = h->o_margin;
     a.status = h->status_dev;
     a.conf_logit = conf > 0.f && conf < 1.f ? std::log(conf / (1.f - conf)) : (conf <= 0.f ? -INFINITY : INFINITY);
+    return a;
+}
+static int run_head(wtk_yolo *h, int B, int H, int W, float conf, float *out_xywh, float *out_conf, int *out_anchor, hipStream_t st,
+                    const NmsOut *nms = nullptr) {
+    const HeadArgs a = head_args(h, B, H, W, conf, out_xywh, out_conf, out_anchor);
     if (nms) {
         NmsArgs q;
         std::memset(&q, 0, sizeof(q));
@@ -280,6 +284,75 @@ static int resolve_conv(const wtk_yolo *h, const Op &op, int B, ConvLaunch &r) {
     return 0;
 }
 
+// ---- sparse Detect box towers (DESIGN.md "Sparse box towers") ----
+// A max_det = 1 call reads the 64 box logits of ONE anchor per frame, so the box towers (model.22.cv2.*) only matter on the 5 x 5 patch under the survivor.
+// What a sparse call launches in place of a level's tower ops: cls0 = the class half (couts hb .. hb + hc) of the shared first conv, in the tower's place on its
+// lane; behind the head's selection box0 = its box half (couts 0 .. hb) and box1 = box.1 with box.2 in its epilogue, both with the live mask.  All three run on
+// the packed weights, the geometry and the 64-cout tile of the dense launches, so every pixel they compute has the dense pass's bits.
+struct SparseBox {
+    ConvLaunch cls0[3], box0[3], box1[3];
+    HeadSparseArgs hs; // geometry and mask layout for the head kernels (hs.h is filled per call)
+    int level_of_op0(const wtk_yolo *h, size_t oi) const {
+        for (int l = 0; l < 3; ++l)
+            if ((int)oi == h->det[l].op0) return l;
+        return -1;
+    }
+    bool skips(const wtk_yolo *h, size_t oi) const {
+        for (int l = 0; l < 3; ++l)
+            if ((int)oi == h->det[l].box1 || (int)oi == h->det[l].box2) return true;
+        return false;
+    }
+};
+
+// The rule, in one place.  A call goes sparse iff it is a max_det = 1 call (the caller checks), the switch WTK_NO_SPARSE_BOX is not set, the call is large
+// enough for the sparse tail to pay (sparse_box_pays, wtk_internal.h: four rounds of P3 blocks, from measurement), the handle is a
+// throughput-plan f16x3 handle (wtk_plan.hip allocates the mask for those alone: fp16 / fp32 run the shared first conv as ONE 192-cout tile, whose halves would
+// be other instantiations; latency-plan handles run the box-tower convs as members of grouped split-K launches shared with the PAN path, and five more
+// dependent levels would cost a single frame more than the skipped tiles save), and EVERY box op of every level resolves, at this batch size, to the window
+// kernel that takes the mask: the shared conv unfused on conv3x3_halo_kernel<split>, box.1 on it with box.2 as its fused tail.  Anything else (a small handle
+// whose 12 x 12 maps run split-K, WTK_NO_FUSED_TAIL, WTK_NO_HALO) keeps the whole handle dense.
+static bool resolve_sparse(const wtk_yolo *h, int B, SparseBox &sp) {
+    if (!h->use_sparse_box || !h->split || h->latency || !h->live_bytes) return false;
+    if (!sparse_box_pays(B, h->lh[0], h->lw[0], h->num_cus)) return false; // a call too small for the sparse tail to pay (wtk_internal.h)
+    std::memset(&sp.hs, 0, sizeof(sp.hs));
+    unsigned off = 0;
+    for (int l = 0; l < 3; ++l) {
+        const wtk_yolo::DetLevel &d = h->det[l];
+        if (d.op0 < 0 || d.box1 < 0 || d.box2 < 0) return false;
+        const Op &o0 = h->ops[d.op0], &b1 = h->ops[d.box1], &b2 = h->ops[d.box2];
+        if (o0.folded || o0.tail_op >= 0 || o0.cout != h->dims.hb + h->dims.hc || h->dims.hb != 64 || h->dims.hc % 64 || b1.tail_op != d.box2 || !b2.folded) return false;
+        ConvLaunch r0, r1;
+        if (resolve_conv(h, o0, B, r0) || resolve_conv(h, b1, B, r1)) return false;
+        if (r0.kind != L_HALO_SPLIT || r1.kind != L_HALO_SPLIT || r0.g.res || r0.g.out2 || r1.g.res || r1.g.out2) return false;
+        if (split_halo_cout_tile(o0.cout) != 64 || r0.g.narrow || r1.g.narrow) return false; // the dense launch must already run on 64-cout tiles
+        if (r0.g.S != r1.g.S || r0.g.pitch != r1.g.pitch || r0.g.strips != r1.g.strips) return false;
+        // mask layout of this call (wtk_plan.hip sized the region for max_batch): per level live0 then live1, strips x ld bytes each
+        const int ld = 2 * (int)(((long long)B * (h->lh[l] + 1) * r0.g.pitch + 255) / 256);
+        const unsigned bytes = ((unsigned)r0.g.strips * (unsigned)ld + 3u) & ~3u;
+        sp.hs.S[l] = r0.g.S, sp.hs.pitch[l] = r0.g.pitch, sp.hs.ld[l] = ld;
+        sp.hs.off0[l] = off, sp.hs.off1[l] = off + bytes;
+        off += 2 * bytes;
+        if (off > h->live_bytes) return false;
+        // the two halves of the shared conv: rows [0, hb) and [hb, hb + hc) of its packed weights and bias, the same slices of d1.  64-cout tiles either way
+        // (narrow: the class half's 128 couts would otherwise pick the 128-cout tile)
+        const int hb = h->dims.hb;
+        sp.box0[l] = r0;
+        sp.box0[l].g.Cout = sp.box0[l].g.CoutPad = hb;
+        sp.box0[l].g.live_off = 256u + sp.hs.off0[l], sp.box0[l].g.live_ld = ld;
+        sp.cls0[l] = r0;
+        HaloArgs &c = sp.cls0[l].g;
+        c.Cout = c.CoutPad = o0.cout - hb, c.narrow = 1;
+        c.w = reinterpret_cast<const char *>(c.w) + (size_t)hb * c.Kpad * 2; // split rows: Kpad pseudo-channels of fp16
+        c.bias = c.bias + hb;
+        c.out_coff += 2 * hb; // pseudo-channels
+        sp.box1[l] = r1;
+        sp.box1[l].g.live_off = 256u + sp.hs.off1[l], sp.box1[l].g.live_ld = ld;
+    }
+    sp.hs.live = reinterpret_cast<unsigned char *>(h->zero_page) + 256;
+    sp.hs.sel_anchor = h->sel_anchor, sp.hs.sel_score = h->sel_score, sp.hs.n_dyn = h->n_dyn;
+    return true;
+}
+
 // key of a launch's cached choice (sk_choices, sk_cands, tune_ms, tune_key): a dependency level of lat_sched, or kOpKeyBase + the index of an op launched alone
 constexpr long long kOpKeyBase = 100000;
 static long long choice_key(long long launch, int B) { return (launch << 24) | (long long)B; }
@@ -333,6 +406,7 @@ struct Pass {
     hipStream_t main_st;    // the caller's stream
     bool two_lanes = false;
     unsigned side_used = 0; // bit i: side_stream[i] carries work of this pass
+    const struct SparseBox *sparse = nullptr; // this pass leaves the box towers to enqueue_sparse_tail
     int cur_class = -1, nev = 0;
     int ev_class[wtk_yolo::kProfEvents];
     long long launches[wtk_yolo::kProfKernels] = {};
@@ -424,6 +498,7 @@ static int enqueue_op(Pass &p, size_t oi) {
     if (h->use_c2f && (oi == 3 || oi == 4)) return 0; // folded into the fused C2f tail launched at op 5
     if (op.folded) return 0;                          // runs in the epilogue of the op that names it as tail_op
     if (h->use_c2f && oi == 5) return enqueue_c2f(p, op);
+    if (p.sparse && p.sparse->skips(h, oi)) return 0; // box.1 / box.2 of a sparse pass: behind the head's selection
     hipStream_t st = p.main_st;
     if (p.two_lanes && op.side) { // a Detect tower: on its side stream, behind its feature map
         const int sidx = std::min(op.side, h->side_streams); // wtk_yolo_set_side_streams(1): both towers on side stream 1
@@ -452,6 +527,12 @@ static int enqueue_op(Pass &p, size_t oi) {
         a.buf = b.ptr, a.N = p.B, a.H = b.h, a.W = b.w, a.c = op.cin, a.split = h->split;
         HIP_TRY(launch_sppf_pool(a, h->is_f16, st));
         p.count(PROF_POOL);
+        return 0;
+    }
+    if (const int l = p.sparse ? p.sparse->level_of_op0(h, oi) : -1; l >= 0) { // the shared first conv of a tower pair: its class half, in its place
+        const ConvLaunch &c = p.sparse->cls0[l];
+        if (mark(p, c.cls) || issue_conv(h, op, c, st)) return 1;
+        p.count(c.cls, p.op_flops(op) * h->dims.hc / (h->dims.hb + h->dims.hc));
         return 0;
     }
     ConvLaunch r;
@@ -507,11 +588,65 @@ static int enqueue_levels(Pass &p, size_t first_op) {
     return 0;
 }
 
+// The end of a sparse pass, on the caller's stream behind the joined side streams: clear the mask, select (which marks), box.0 of the three levels, box.1 + box.2
+// of the three levels, decode.  The six window launches carry a handful of live blocks each and go back to back; in profiling mode they are a class of their own
+// with 0 FLOPs (the host does not know the live tiles), so the roofline does not credit the window kernel with work it skipped.
+static int enqueue_sparse_tail(Pass &p, const SparseBox &sp, int H, int W, float conf, float *out_xywh, float *out_conf, int *out_anchor) {
+    wtk_yolo *h = p.h;
+    hipStream_t st = p.main_st;
+    HeadSparseArgs hs = sp.hs;
+    hs.h = head_args(h, p.B, H, W, conf, out_xywh, out_conf, out_anchor);
+    if (mark(p, PROF_HEAD)) return 1;
+    HIP_TRY(hipMemsetAsync(hs.live, 0, h->live_bytes, st));
+    HIP_TRY(launch_head_select_sparse(hs, st));
+    p.count(PROF_HEAD);
+    if (mark(p, PROF_SPARSE)) return 1;
+    for (int l = 0; l < 3; ++l) {
+        if (issue_conv(h, h->ops[h->det[l].op0], sp.box0[l], st)) return 1;
+        p.count(PROF_SPARSE);
+    }
+    for (int l = 0; l < 3; ++l) {
+        if (issue_conv(h, h->ops[h->det[l].box1], sp.box1[l], st)) return 1;
+        p.count(PROF_SPARSE);
+    }
+    if (mark(p, PROF_HEAD)) return 1;
+    HIP_TRY(launch_head_decode(hs, st));
+    p.count(PROF_HEAD);
+    h->sparse_B = p.B;
+    for (int l = 0; l < 3; ++l) { // what complete_box_towers launches: this pass's own box launches, without the mask
+        h->sparse_done[l] = sp.box0[l], h->sparse_done[3 + l] = sp.box1[l];
+        h->sparse_done[l].g.live_off = h->sparse_done[3 + l].g.live_off = 0;
+        h->sparse_done[l].g.live_ld = h->sparse_done[3 + l].g.live_ld = 0;
+    }
+    return 0;
+}
+
+// Dense on demand: the test hooks that read box-tower tensors (wtk_yolo_debug_head, wtk_yolo_debug_tensor) first run what the last sparse pass skipped — the
+// box ops of its batch size without a mask.  Their inputs (the neck maps, d1's class half) are buffers of their own and still hold that pass's values, and the
+// dense launches compute every pixel with the bits the sparse ones gave the survivors'.  The device is idle when this is called.
+static int complete_box_towers(wtk_yolo *h) {
+    if (!h->sparse_B) return 0;
+    for (int l = 0; l < 3; ++l)
+        if (issue_conv(h, h->ops[h->det[l].op0], h->sparse_done[l], nullptr)) return 1;
+    for (int l = 0; l < 3; ++l)
+        if (issue_conv(h, h->ops[h->det[l].box1], h->sparse_done[3 + l], nullptr)) return 1;
+    HIP_TRY(hipDeviceSynchronize());
+    h->sparse_B = 0;
+    return 0;
+}
+
 // Enqueue one forward pass on `st`: input (letterbox / view) -> front -> ops or dependency levels -> join the side streams -> head -> profile read-out.
-// No allocation, no synchronisation (profiling mode excepted): safe inside a caller's stream capture.
+// No allocation, no synchronisation (profiling mode excepted): safe inside a caller's stream capture.  A pass that is being CAPTURED stays dense: the handle
+// remembers on the host whether its last pass left the box towers sparse (sparse_B, for the debug entry points), and a captured pass runs when its graph is
+// replayed, not when it is enqueued — the host could not know which kind of pass ran last.
 static int yolo_enqueue_pass(wtk_yolo *h, const uint8_t *frames_dev, int32_t B, int32_t H, int32_t W, int32_t C, float conf, float *out_xywh,
                              float *out_conf, int32_t *out_anchor, hipStream_t st, const ViewSrc *vs, const NmsOut *nms) {
     Pass p{h, frames_dev, B, C, st};
+    SparseBox sp;
+    if (!nms && resolve_sparse(h, B, sp)) { // max_det = 1: the box towers only where the survivors need them
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) p.sparse = &sp;
+    }
     if (enqueue_input(p, frames_dev, H, W, vs)) return 1;
     const bool grouped = h->latency && h->sk_group && !h->lat_sched.empty();
     if (!grouped && h->use_side && h->side_streams > 0 && !h->profiling && ensure_side_streams(h)) return 1;
@@ -529,9 +664,14 @@ static int yolo_enqueue_pass(wtk_yolo *h, const uint8_t *frames_dev, int32_t B, 
             HIP_TRY(hipEventRecord(h->side_done[i], h->side_stream[i]));
             HIP_TRY(hipStreamWaitEvent(st, h->side_done[i], 0));
         }
-    if (mark(p, PROF_HEAD)) return 1;
-    if (run_head(h, B, H, W, conf, out_xywh, out_conf, out_anchor, st, nms)) return 1;
-    p.count(PROF_HEAD);
+    if (p.sparse) {
+        if (enqueue_sparse_tail(p, sp, H, W, conf, out_xywh, out_conf, out_anchor)) return 1;
+    } else {
+        h->sparse_B = 0; // a dense pass computes every box logit
+        if (mark(p, PROF_HEAD)) return 1;
+        if (run_head(h, B, H, W, conf, out_xywh, out_conf, out_anchor, st, nms)) return 1;
+        p.count(PROF_HEAD);
+    }
     if (!h->profiling) return 0;
     if (p.nev < wtk_yolo::kProfEvents) { // close the last bracket
         HIP_TRY(hipEventRecord(h->ev[p.nev], st));
@@ -737,6 +877,7 @@ extern "C" int wtk_yolo_debug_head(wtk_yolo *h, int32_t level, int32_t B, float 
     if (!h || level < 0 || level > 2 || B <= 0 || B > h->max_batch) return fail("wtk_yolo_debug_head: bad argument");
     DEVICE_GUARD(h);
     HIP_TRY(hipDeviceSynchronize());
+    if (box_host && complete_box_towers(h)) return 1; // (a sparse pass computed the survivors' box logits only)
     const size_t A = (size_t)h->lh[level] * h->lw[level];
     if (box_host) {
         const size_t n = (size_t)B * A * 64;
@@ -765,6 +906,10 @@ extern "C" int wtk_yolo_debug_tensor(wtk_yolo *h, int32_t conv_index, int32_t B,
     if (out_cap < px * op->cout) return fail("wtk_yolo_debug_tensor: output buffer too small");
     DEVICE_GUARD(h);
     HIP_TRY(hipDeviceSynchronize());
+    for (int l = 0; l < 3; ++l) { // a box-tower conv: a sparse pass computed it on the survivors' tiles only
+        const int oi = (int)(op - h->ops.data());
+        if ((oi == h->det[l].op0 || oi == h->det[l].box1 || oi == h->det[l].box2) && complete_box_towers(h)) return 1;
+    }
     std::vector<char> tmp(px * b.C * (b.f32 ? 4 : h->esize));
     HIP_TRY(hipMemcpy(tmp.data(), b.ptr, tmp.size(), hipMemcpyDeviceToHost));
     std::vector<float> full(px * b.C);
@@ -845,6 +990,7 @@ static int upload_head_logits(wtk_yolo *h, const float *box_host, const float *c
         HIP_TRY(hipMemcpy(h->bufs[h->cls_buf[l]].ptr, cl.data(), cl.size() * 4, hipMemcpyHostToDevice));
         a0 += Al;
     }
+    h->sparse_B = 0; // the head buffers now hold the caller's logits, all of them
     return 0;
 }
 

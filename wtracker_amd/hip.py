@@ -623,7 +623,7 @@ class HipYolo:
         return out
 
     KERNELS = ["stem_mfma_kernel", "conv_igemm_kernel+conv1x1_wide_kernel", "sppf_pool_kernel", "head", "conv3x3_halo_kernel",
-               "front_fused_kernel+c2f32_fused_kernel", "conv3x3_c32_kernel"]
+               "front_fused_kernel+c2f32_fused_kernel", "conv3x3_c32_kernel", "conv3x3_halo_kernel(sparse box towers)"]
 
     def get_kernel_profile(self) -> dict:
         """Per-kernel device time, launches and algorithmic FLOPs of the profiled forwards (wtk_yolo_get_kernel_profile)."""
