@@ -431,6 +431,47 @@ int wtk_precise_error(const uint8_t *frames_dev, int32_t n_frames, int32_t H, in
                       const int32_t *frame_nums_dev, int32_t n_rows, double diff_thresh, double *err_dev,
                       int32_t *counts_dev, int32_t *n_bad_frame_dev, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Weight search for the polynomial-fit controller (csrc/polyfit_opt.hip): the reference's WeightEvaluator and the particle swarm that
+ * polyfit_optimizer.ipynb runs over it, on the device.  Everything enqueues on `stream`; nothing synchronises or allocates.
+ *
+ * wtk_polyfit_dataset  replaces WeightEvaluator._extract_positions                  sim_controllers/polyfit_controller.py:145-188
+ *     One candidate cycle per cycle_start = 0, L, 2L, ... of the track ([n_frames][4] xywh, float32 or float64).  A cycle is kept when
+ *     every input frame cycle_start + input_offsets[i] is >= 0, the target frame cycle_start + pred_time_offset is < n_frames, all
+ *     2 n_times + 2 centre coordinates are finite and sqrt(dx^2 + dy^2) / (pred_time_offset - input_offsets[0]) of target against first
+ *     input lies in [min_speed, max_speed].  input_offsets (host) must be SORTED ascending with input_offsets[n-1] <= pred_time_offset
+ *     (beyond it the reference raises IndexError at the end of the log; here the call is refused) and input_offsets[0] < pred_time_offset.
+ *     Kept cycles are appended IN CYCLE ORDER behind the *count_dev cycles the buffers already hold (several logs: call again with the same
+ *     buffers): y_input_dev [n_times][2 * capacity] with x and y of cycle k in columns 2k, 2k + 1, y_target_dev [2 * capacity] likewise.
+ *     *count_dev += kept; a count above `capacity` (cycles) after the call means the buffers were too small: nothing is written past them.
+ * wtk_polyfit_weight_mae  replaces WeightEvaluator.eval for P weight vectors         polyfit_controller.py:207-221
+ *     mae_dev[p] = mean_m |y_target[m] - polyval(t_pred, polyfit(sample_times, y_input[:, m], degree, w = weights_dev[p]))| over the M series
+ *     (M = 2 x kept cycles; y_input_dev [n_times][ld], ld >= M), numpy's scaling and rcond = n_times * eps cut included.  NaN where the weights
+ *     are not finite, where the solver did not converge, and for M = 0.  Fixed-order reduction: equal inputs give equal bits in every call,
+ *     whatever P.  n_times <= 16, degree <= 7.  scratch_dev: wtk_polyfit_mae_scratch_doubles(P, M) doubles.  stop_dev (nullable): the call
+ *     does nothing once *stop_dev != 0 on the device (the swarm's stop flag).
+ * wtk_polyfit_swarm_step  one epoch of the inertia-weight particle swarm over weight vectors (no counterpart in the reference's code: it calls
+ *     mealpy).  From mae_dev [P] of the current positions: personal bests (strictly lower only), global best (lowest particle among equals),
+ *     history_dev[epoch] = best so far, ctrl_dev = {stop flag, epochs since the last improvement, epochs run, particle of the global best};
+ *     the stop flag rises once max_early_stop epochs brought no improvement, and a raised flag makes this and later calls return at once.
+ *     Otherwise v <- clamp(w v + c1 r1 (pbest - x) + c2 r2 (gbest - x), -vmax, vmax), x <- clip(x + v, lb, ub) with r1 = rand_dev[0][p][n],
+ *     r2 = rand_dev[1][p][n] uniform in [0, 1) (the caller's: one [2][P][N] slice per epoch).  pos / vel / pbest_pos [P][N], pbest_val [P],
+ *     gbest_pos [N], gbest_val [1]; the caller initialises them (pbest_val = gbest_val = +inf, ctrl = 0).
+ * ------------------------------------------------------------------------------------------ */
+int wtk_polyfit_dataset(const void *track_dev, int32_t track_is_f64, int32_t n_frames, int32_t cycle_frame_num,
+                        const int32_t *input_offsets_host, int32_t n_times, int32_t pred_time_offset, double min_speed,
+                        double max_speed, double *y_input_dev, double *y_target_dev, int32_t capacity, int32_t *count_dev,
+                        void *stream);
+int64_t wtk_polyfit_mae_scratch_doubles(int32_t P, int32_t M);
+int wtk_polyfit_weight_mae(const double *y_input_dev, const double *y_target_dev, int64_t ld, int32_t M,
+                           const int32_t *sample_times_host, int32_t n_times, int32_t pred_time_offset, int32_t degree,
+                           const double *weights_dev, int32_t P, double *mae_dev, double *scratch_dev, int64_t scratch_doubles,
+                           const int32_t *stop_dev, void *stream);
+int wtk_polyfit_swarm_step(const double *mae_dev, const double *rand_dev, int32_t P, int32_t N, int32_t epoch,
+                           int32_t max_early_stop, double w, double c1, double c2, double lb, double ub, double vmax,
+                           double *pos_dev, double *vel_dev, double *pbest_pos_dev, double *pbest_val_dev, double *gbest_pos_dev,
+                           double *gbest_val_dev, int32_t *ctrl_dev, double *history_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

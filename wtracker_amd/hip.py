@@ -62,6 +62,7 @@ SYMBOLS = [
     "wtk_hybrid_create", "wtk_hybrid_destroy", "wtk_hybrid_set_margin", "wtk_hybrid_predict", "wtk_hybrid_predict_views", "wtk_hybrid_flush",
     "wtk_hybrid_pending", "wtk_hybrid_counters", "wtk_hybrid_config", "wtk_hybrid_hold",
     "wtk_background", "wtk_precise_error",
+    "wtk_polyfit_dataset", "wtk_polyfit_mae_scratch_doubles", "wtk_polyfit_weight_mae", "wtk_polyfit_swarm_step",
 ]
 
 
@@ -203,6 +204,12 @@ def load() -> C.CDLL:
     lib.wtk_hybrid_config.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(f32)]
     lib.wtk_background.argtypes = [vp, i32, C.c_int64, vp, i32, i32, vp, vp]
     lib.wtk_precise_error.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, vp, i32, C.c_double, vp, vp, vp, vp]
+    f64 = C.c_double
+    lib.wtk_polyfit_dataset.argtypes = [vp, i32, i32, i32, vp, i32, i32, f64, f64, vp, vp, i32, vp, vp]
+    lib.wtk_polyfit_mae_scratch_doubles.argtypes = [i32, i32]
+    lib.wtk_polyfit_mae_scratch_doubles.restype = C.c_int64
+    lib.wtk_polyfit_weight_mae.argtypes = [vp, vp, C.c_int64, i32, vp, i32, i32, i32, vp, i32, vp, vp, C.c_int64, vp, vp]
+    lib.wtk_polyfit_swarm_step.argtypes = [vp, vp, i32, i32, i32, i32, f64, f64, f64, f64, f64, f64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -364,6 +371,36 @@ def precise_error(frames_dev, n_frames: int, H: int, W: int, bg_dev, worm_dev, m
         raise WtkError("worm and microscope boxes must share one dtype")
     _check(load().wtk_precise_error(_ptr(frames_dev), n_frames, H, W, _ptr(bg_dev), _ptr(worm_dev), _ptr(mic_dev), f64, _ptr(frame_nums_dev), n_rows,
                                     float(diff_thresh), _ptr(err_dev), _ptr(counts_dev), _ptr(n_bad_frame_dev), C.c_void_p(stream)), "wtk_precise_error")
+
+
+def polyfit_dataset(track_dev, n_frames: int, cycle_frame_num: int, input_offsets: Sequence[int], pred_time_offset: int, min_speed: float, max_speed: float,
+                    y_input_dev, y_target_dev, capacity: int, count_dev, stream: int = 0):
+    """WeightEvaluator's dataset of one log appended behind the *count_dev cycles already in y_input_dev [N, 2 * capacity] / y_target_dev [2 * capacity]
+    (wtk_polyfit_dataset); input_offsets sorted ascending."""
+    off = np.ascontiguousarray(input_offsets, dtype=np.int32)
+    _check(load().wtk_polyfit_dataset(_ptr(track_dev), _track_is_f64(track_dev), n_frames, cycle_frame_num, _ptr(off), len(off), int(pred_time_offset),
+                                      float(min_speed), float(max_speed), _ptr(y_input_dev), _ptr(y_target_dev), capacity, _ptr(count_dev),
+                                      C.c_void_p(stream)), "wtk_polyfit_dataset")
+
+
+def polyfit_mae_scratch_doubles(P: int, M: int) -> int:
+    return int(load().wtk_polyfit_mae_scratch_doubles(P, M))
+
+
+def polyfit_weight_mae(y_input_dev, y_target_dev, ld: int, M: int, sample_times: Sequence[int], pred_time_offset: int, degree: int, weights_dev, P: int,
+                       mae_dev, scratch_dev, scratch_doubles: int, stop_dev=None, stream: int = 0):
+    """mae_dev[p] = WeightEvaluator.eval(weights_dev[p], degree) for P weight vectors (wtk_polyfit_weight_mae); all float64 device tensors."""
+    st = np.ascontiguousarray(sample_times, dtype=np.int32)
+    _check(load().wtk_polyfit_weight_mae(_ptr(y_input_dev), _ptr(y_target_dev), ld, M, _ptr(st), len(st), int(pred_time_offset), degree, _ptr(weights_dev), P,
+                                         _ptr(mae_dev), _ptr(scratch_dev), scratch_doubles, _ptr(stop_dev), C.c_void_p(stream)), "wtk_polyfit_weight_mae")
+
+
+def polyfit_swarm_step(mae_dev, rand_dev, P: int, N: int, epoch: int, max_early_stop: int, w: float, c1: float, c2: float, lb: float, ub: float, vmax: float,
+                       pos_dev, vel_dev, pbest_pos_dev, pbest_val_dev, gbest_pos_dev, gbest_val_dev, ctrl_dev, history_dev, stream: int = 0):
+    """One epoch of the weight swarm on device-resident state (wtk_polyfit_swarm_step); rand_dev: this epoch's [2, P, N] slice."""
+    _check(load().wtk_polyfit_swarm_step(_ptr(mae_dev), _ptr(rand_dev), P, N, epoch, max_early_stop, float(w), float(c1), float(c2), float(lb), float(ub),
+                                         float(vmax), _ptr(pos_dev), _ptr(vel_dev), _ptr(pbest_pos_dev), _ptr(pbest_val_dev), _ptr(gbest_pos_dev),
+                                         _ptr(gbest_val_dev), _ptr(ctrl_dev), _ptr(history_dev), C.c_void_p(stream)), "wtk_polyfit_swarm_step")
 
 
 # -------------------------------------------------------------------------------------------------
