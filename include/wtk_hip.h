@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define WTK_ABI_VERSION 7 /* 7: + wtk_yolo_create_planned / wtk_yolo_plan, wtk_yolo_status (additive); 2: + wtk_yolo_predict_views / _nms, wtk_track_*, wtk_comm_*; 3: + WTK_F16X3, wtk_recheck_*; 4: + wtk_recheck_select_counted; 5: + wtk_recheck_enqueue / _scatter; 6: + wtk_hybrid_*; still 7: + wtk_background, wtk_precise_error (additive: every earlier entry point is unchanged) */
+#define WTK_ABI_VERSION 7 /* 7: + wtk_yolo_create_planned / wtk_yolo_plan, wtk_yolo_status (additive); 2: + wtk_yolo_predict_views / _nms, wtk_track_*, wtk_comm_*; 3: + WTK_F16X3, wtk_recheck_*; 4: + wtk_recheck_select_counted; 5: + wtk_recheck_enqueue / _scatter; 6: + wtk_hybrid_*; still 7: + wtk_background, wtk_precise_error (additive: every earlier entry point is unchanged); still 7: + wtk_polyfit_*; still 7: + wtk_replay_* (additive) */
 
 typedef enum wtk_dtype {
     WTK_F32 = 0, /* fp32 storage, exact-fp32 MFMA (v_mfma_f32_16x16x4_f32): parity mode   */
@@ -471,6 +471,66 @@ int wtk_polyfit_swarm_step(const double *mae_dev, const double *rand_dev, int32_
                            int32_t max_early_stop, double w, double c1, double c2, double lb, double ub, double vmax,
                            double *pos_dev, double *vel_dev, double *pbest_pos_dev, double *pbest_val_dev, double *gbest_pos_dev,
                            double *gbest_val_dev, int32_t *ctrl_dev, double *history_dev, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Closed-loop replay of track-driven experiments (csrc/replay.hip): the reference's Simulator + SineMotorController + LoggingController
+ * (sim/simulator.py:140-194, sim/motor_controllers.py:58-88, sim_controllers/logging_controller.py:145-185) for E experiments on one
+ * track at once, with ErrorCalculator.calculate_bbox_error / calculate_mse_error (eval/error_calculator.py:164-212) of every logged row.
+ * Everything enqueues on `stream`; nothing synchronises or allocates.  All device arrays of per-cycle values are CYCLE-major: [n_cycles][E].
+ *
+ * Geometry (wtk_replay_config): a cycle has L = imaging_frame_num + moving_frame_num frames; the move of cycle c is decided at frame
+ * c L + imaging_frame_num and taken over the next moving_frame_num frames; the platform position is clamped to [0, frame_w - 1] x
+ * [0, frame_h - 1]; the camera / microscope corner is position - size / 2 (integer division).  Logged are the cycles 0 .. n_log - 1 with
+ * n_log = (num_frames - 1) / L, all L frames of each: R = n_log L rows per experiment, row r = frame r (the last cycle is never logged).
+ * n_cycles: cycles to scan, n_log <= n_cycles, decision frame of the last one < num_frames.
+ *
+ * wtk_replay_scan   one lane per experiment, sequential over cycles.  Move of cycle c per axis, float64, rounded half to even, with
+ *     cam = position - cam_size / 2 (integer) at the cycle's start:
+ *       WTK_REPLAY_CSV      rint(((x - cam) + w / 2) - cam_size / 2)   (x, y, w, h) = track row c L + imaging - pred_frame_num
+ *       WTK_REPLAY_OPTIMAL  rint(a - (cam + cam_size / 2))             a = a_dev[c][e]
+ *       WTK_REPLAY_POLYFIT  rint((a - cam) - cam_size / 2)
+ *       WTK_REPLAY_MLP      rint(a + (b - (cam + cam_size / 2)))       a = clipped model output, b = b_dev[c][e] corner of the first input box
+ *     (0, 0) where valid_dev[c][e] == 0 (CSV: where the row is outside the track or not finite) or the expression is not finite; |move|
+ *     saturates at 2^30.  Then moving_frame_num motor steps: want = share[k] move + carry, took = rint(want), carry = want - took,
+ *     position = clamp(position + took).  share_dev [moving_frame_num] doubles is the caller's half-cosine table
+ *     (cos(k pi / M) - cos((k + 1) pi / M)) / 2, computed on the host.  Out: pos_dev [n_cycles][E][2] position at the cycle's start,
+ *     move_dev [n_cycles][E][2].  a_dev / b_dev [n_cycles][E][2] doubles, valid_dev [n_cycles][E]; CSV needs none of them, b_dev is MLP's.
+ * wtk_replay_rows   one thread per (experiment, logged row) from the scan's pos_dev / move_dev.  Row: platform position, camera box,
+ *     microscope box, logged worm box ((x - cam_x) + cam_x, (y - cam_y) + cam_y, w, h; a non-finite track row as 0, 0, 0, 0), its
+ *     bbox error (0 where the worm box has no area) and MSE error.  bbox_err_dev / mse_err_dev [E][R] (nullable).  rows_dev
+ *     [n_slots][R][WTK_REPLAY_ROW_DOUBLES] (nullable, with row_slot_dev [E]: the slot of experiment e or -1): plt_x, plt_y, cam_x, cam_y,
+ *     cam_w, cam_h, mic_x, mic_y, mic_w, mic_h, wrm_x, wrm_y, wrm_w, wrm_h, cycle, phase (0 imaging, 1 moving).  summary_dev
+ *     [E][WTK_REPLAY_SUMMARY_DOUBLES]: sum and count of the bbox error over all rows, the same over the imaging rows of the cycles
+ *     1 .. n_log - 2 (DataAnalyzer.clean(trim_cycles=True, imaging_only=True)), the count of rows with bbox error > 1e-7, the sum of the
+ *     MSE error.  Sums have a fixed order (per lane in index order, a binary tree per chunk of 4096 rows, chunks in index order): an
+ *     experiment gives the same bits alone and in any population.  scratch_dev: wtk_replay_scratch_doubles(E, R) doubles.
+ * Refused (error code, no memory touched): E < 1, moving_frame_num < 1, imaging_frame_num < 1, pred_frame_num > imaging_frame_num (or < 1
+ * for CSV), a track shorter than R, a camera smaller than the microscope, n_cycles outside the range above, a required pointer that is null.
+ * ------------------------------------------------------------------------------------------ */
+#define WTK_REPLAY_CSV 0
+#define WTK_REPLAY_OPTIMAL 1
+#define WTK_REPLAY_POLYFIT 2
+#define WTK_REPLAY_MLP 3
+#define WTK_REPLAY_ROW_DOUBLES 16
+#define WTK_REPLAY_SUMMARY_DOUBLES 6
+typedef struct wtk_replay_config {
+    int32_t num_frames;        /* frames of the experiment (ExperimentConfig.num_frames) */
+    int32_t imaging_frame_num; /* TimingConfig */
+    int32_t moving_frame_num;
+    int32_t pred_frame_num;
+    int32_t cam_w, cam_h;      /* camera_size_px */
+    int32_t mic_w, mic_h;      /* micro_size_px */
+    int32_t frame_w, frame_h;  /* the frame the position is clamped to (the reader's frame_shape[1], [0]) */
+    int32_t init_x, init_y;    /* ExperimentConfig.init_position */
+} wtk_replay_config;
+int wtk_replay_scan(const wtk_replay_config *cfg, int32_t kind, int32_t E, int32_t n_cycles, const double *track_dev, int32_t n_track,
+                    const double *a_dev, const double *b_dev, const int32_t *valid_dev, const double *share_dev, int32_t *pos_dev,
+                    int32_t *move_dev, void *stream);
+int64_t wtk_replay_scratch_doubles(int32_t E, int64_t R);
+int wtk_replay_rows(const wtk_replay_config *cfg, int32_t E, int32_t n_cycles, const double *track_dev, int32_t n_track,
+                    const double *share_dev, const int32_t *pos_dev, const int32_t *move_dev, const int32_t *row_slot_dev, int32_t n_slots,
+                    double *rows_dev, double *bbox_err_dev, double *mse_err_dev, double *summary_dev, double *scratch_dev,
+                    int64_t scratch_doubles, void *stream);
 
 #ifdef __cplusplus
 }

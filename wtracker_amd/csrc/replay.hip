@@ -1,0 +1,271 @@
+// Closed-loop replay of track-driven experiments on the device: what the reference's Simulator (wtracker/sim/simulator.py:140-194) + SineMotorController
+// (motor_controllers.py:58-88) + LoggingController (logging_controller.py:145-185) do frame by frame for ONE experiment, for a whole population at once,
+// with the bounding-box and MSE tracking error of every logged row (eval/error_calculator.py:164-212).
+//
+// During the imaging phase the platform stands still, so a controller's move is round(f(target_c, platform position)) with a per-cycle target that does
+// not depend on the platform: the loop is a sequential scan over cycles (a few flops each) followed by an embarrassingly parallel expansion to frames.
+//   scan    one lane per experiment, sequential over cycles: move of the cycle from the kind's expression (float64, the reference's operation order),
+//           then the motor's M steps (share * move + carry, rounded half to even, the residual carried, the position clamped to the frame).  Per-cycle
+//           inputs are [C][E] (cycle-major), so a wave's loads coalesce.  Writes the position at cycle start and the move, [C][E] int32 pairs.
+//   rows    one thread per (experiment, logged frame): the frame's platform position from its cycle's start position and move (at most M motor steps, the
+//           scan's arithmetic), camera / microscope / logged worm box, bbox and MSE error of the row; per-experiment sums in a FIXED order: lane-serial
+//           over the chunk, a binary tree in LDS, and a finish launch that adds the chunk partials in index order (the scheme of wtk_polyfit_weight_mae).
+//           The chunking depends on the row count only: an experiment gives the same bits alone and inside any population.  No floating-point atomics.
+// Everything relies on -ffp-contract=off (the library's build flag): share * move + carry is a rounded product and a rounded sum, as in Python.
+#include "wtk_internal.h"
+
+#include <cmath>
+
+using namespace wtk;
+
+namespace {
+
+constexpr int kScanThreads = 64;
+constexpr int kRowThreads = 256;
+constexpr int kRowChunk = 4096; // logged rows per block of the rows kernel: the FIXED chunking of the reductions
+constexpr int kSummary = WTK_REPLAY_SUMMARY_DOUBLES;
+constexpr int kRowDoubles = WTK_REPLAY_ROW_DOUBLES;
+constexpr double kMoveMax = 1073741824.0; // 2^30: moves are kept as int32
+
+struct Geometry {
+    int L, I, M, P;
+    int cam_w, cam_h, mic_w, mic_h;
+    int x_max, y_max; // frame_w - 1, frame_h - 1: the clamp of the platform position
+};
+
+struct ScanArgs {
+    Geometry g;
+    int kind, E, C;
+    int init_x, init_y;
+    const double *track; // [n_track][4] xywh
+    int n_track;
+    const double *a;  // [C][E][2] (CSV: unused)
+    const double *b;  // [C][E][2] (MLP only)
+    const int *valid; // [C][E] (CSV: unused)
+    const double *share; // [M]
+    int *pos;  // [C][E][2]
+    int *move; // [C][E][2]
+};
+
+struct RowsArgs {
+    Geometry g;
+    int E, C, S, n_slots;
+    long long R; // logged rows per experiment
+    int n_log;   // logged cycles
+    const double *track;
+    const double *share;
+    const int *pos, *move; // [C][E][2]
+    const int *row_slot;   // [E] slot of the experiment in `rows`, or -1 (nullable)
+    double *rows;          // [slots][R][kRowDoubles] (nullable)
+    double *bbox_err, *mse_err; // [E][R] (nullable)
+    double *partial;       // [E][S][kSummary]
+    double *summary;       // [E][kSummary]
+};
+
+// one step of SineMotorController.step + ViewController.move_position on one axis
+__device__ __forceinline__ void motor_axis(double share, double mv, double &carry, int &pos, int pos_max) {
+    const double want = share * mv + carry;
+    const double took = rint(want); // round half to even: Python's round on a float
+    carry = want - took;
+    pos = (int)fmin(fmax((double)pos + took, 0.0), (double)pos_max);
+}
+
+// the controller's move on one axis from the camera corner; a non-finite result is no move, a huge one saturates at +-2^30
+__device__ __forceinline__ double finish_move(double v) {
+    if (!isfinite(v)) return 0.0;
+    return fmin(fmax(rint(v), -kMoveMax), kMoveMax);
+}
+
+__global__ __launch_bounds__(kScanThreads) void replay_scan_kernel(const ScanArgs a) {
+    const int e = blockIdx.x * kScanThreads + threadIdx.x;
+    if (e >= a.E) return;
+    const Geometry g = a.g;
+    int px = a.init_x < 0 ? 0 : (a.init_x > g.x_max ? g.x_max : a.init_x), py = a.init_y < 0 ? 0 : (a.init_y > g.y_max ? g.y_max : a.init_y);
+    const double half_w = (double)g.cam_w / 2, half_h = (double)g.cam_h / 2;
+    for (int c = 0; c < a.C; ++c) {
+        const long long ce = (long long)c * a.E + e;
+        a.pos[2 * ce] = px, a.pos[2 * ce + 1] = py;
+        const double cam_x = (double)(px - g.cam_w / 2), cam_y = (double)(py - g.cam_h / 2);
+        double mx = 0.0, my = 0.0;
+        if (a.kind == WTK_REPLAY_CSV) {
+            const long long f = (long long)c * g.L + g.I - g.P; // the frame the controller saw P frames before the decision
+            if (f >= 0 && f < a.n_track) {
+                const double x = a.track[4 * f], y = a.track[4 * f + 1], w = a.track[4 * f + 2], h = a.track[4 * f + 3];
+                if (isfinite(x) && isfinite(y) && isfinite(w) && isfinite(h)) {
+                    mx = finish_move(((x - cam_x) + w / 2) - half_w);
+                    my = finish_move(((y - cam_y) + h / 2) - half_h);
+                }
+            }
+        } else if (a.valid[ce]) {
+            const double ax = a.a[2 * ce], ay = a.a[2 * ce + 1];
+            if (a.kind == WTK_REPLAY_OPTIMAL) {
+                mx = finish_move(ax - (cam_x + half_w));
+                my = finish_move(ay - (cam_y + half_h));
+            } else if (a.kind == WTK_REPLAY_POLYFIT) {
+                mx = finish_move((ax - cam_x) - half_w);
+                my = finish_move((ay - cam_y) - half_h);
+            } else {
+                mx = finish_move(ax + (a.b[2 * ce] - (cam_x + half_w)));
+                my = finish_move(ay + (a.b[2 * ce + 1] - (cam_y + half_h)));
+            }
+        }
+        a.move[2 * ce] = (int)mx, a.move[2 * ce + 1] = (int)my;
+        double cx = 0.0, cy = 0.0;
+        for (int k = 0; k < g.M; ++k) {
+            const double sh = a.share[k];
+            motor_axis(sh, mx, cx, px, g.x_max);
+            motor_axis(sh, my, cy, py, g.y_max);
+        }
+    }
+}
+
+__global__ __launch_bounds__(kRowThreads) void replay_rows_kernel(const RowsArgs a) {
+    __shared__ double red[kSummary][kRowThreads];
+    const Geometry g = a.g;
+    const int e = blockIdx.x / a.S, s = blockIdx.x - e * a.S;
+    int slot = a.row_slot ? a.row_slot[e] : -1;
+    if (slot >= a.n_slots) slot = -1; // never write past `rows`
+    double acc[kSummary];
+    for (int q = 0; q < kSummary; ++q) acc[q] = 0.0;
+    const long long r0 = (long long)s * kRowChunk;
+    for (int i = 0; i < kRowChunk / kRowThreads; ++i) {
+        const long long r = r0 + (long long)i * kRowThreads + threadIdx.x;
+        if (r >= a.R) continue;
+        const int c = (int)(r / g.L), step = (int)(r - (long long)c * g.L);
+        const long long ce = (long long)c * a.E + e;
+        int px = a.pos[2 * ce], py = a.pos[2 * ce + 1];
+        const int done = step <= g.I ? 0 : (step - g.I > g.M ? g.M : step - g.I); // motor steps taken before this frame's camera picture
+        if (done > 0) {
+            const double mx = (double)a.move[2 * ce], my = (double)a.move[2 * ce + 1];
+            double cx = 0.0, cy = 0.0;
+            for (int k = 0; k < done; ++k) {
+                const double sh = a.share[k];
+                motor_axis(sh, mx, cx, px, g.x_max);
+                motor_axis(sh, my, cy, py, g.y_max);
+            }
+        }
+        const double cam_x = (double)(px - g.cam_w / 2), cam_y = (double)(py - g.cam_h / 2);
+        const double mic_x = (double)(px - g.mic_w / 2), mic_y = (double)(py - g.mic_h / 2);
+        const double mic_w = (double)g.mic_w, mic_h = (double)g.mic_h;
+        // the logged worm box: camera-relative (CsvController.predict) and back (LoggingController), a non-finite row as zeros
+        double wx = (a.track[4 * r] - cam_x) + cam_x, wy = (a.track[4 * r + 1] - cam_y) + cam_y, ww = a.track[4 * r + 2], wh = a.track[4 * r + 3];
+        if (!(isfinite(wx) && isfinite(wy) && isfinite(ww) && isfinite(wh))) wx = wy = ww = wh = 0.0;
+        // ErrorCalculator.calculate_bbox_error
+        const double il = fmax(wx, mic_x), it = fmax(wy, mic_y);
+        const double ir = fmin(wx + ww, mic_x + mic_w), ib = fmin(wy + wh, mic_y + mic_h);
+        const double iw = fmax(0.0, ir - il), ih = fmax(0.0, ib - it);
+        const double inter = iw * ih, total = ww * wh;
+        const double err = total == 0.0 ? 0.0 : 1.0 - inter / total;
+        // ErrorCalculator.calculate_mse_error: mean over the two axes of the squared centre distance
+        const double dx = (wx + ww / 2) - (mic_x + mic_w / 2), dy = (wy + wh / 2) - (mic_y + mic_h / 2);
+        const double mse = (dx * dx + dy * dy) / 2;
+        const bool imaging = step < g.I;
+        if (a.bbox_err) a.bbox_err[(long long)e * a.R + r] = err;
+        if (a.mse_err) a.mse_err[(long long)e * a.R + r] = mse;
+        if (slot >= 0 && a.rows) {
+            double *o = a.rows + ((long long)slot * a.R + r) * kRowDoubles;
+            o[0] = (double)px, o[1] = (double)py;
+            o[2] = cam_x, o[3] = cam_y, o[4] = (double)g.cam_w, o[5] = (double)g.cam_h;
+            o[6] = mic_x, o[7] = mic_y, o[8] = mic_w, o[9] = mic_h;
+            o[10] = wx, o[11] = wy, o[12] = ww, o[13] = wh;
+            o[14] = (double)c, o[15] = imaging ? 0.0 : 1.0;
+        }
+        const bool trimmed = imaging && c != 0 && c != a.n_log - 1; // DataAnalyzer.clean(trim_cycles=True, imaging_only=True)
+        acc[0] += err, acc[1] += 1.0;
+        if (trimmed) acc[2] += err, acc[3] += 1.0;
+        if (err > 1e-7) acc[4] += 1.0;
+        acc[5] += mse;
+    }
+    for (int q = 0; q < kSummary; ++q) red[q][threadIdx.x] = acc[q];
+    __syncthreads();
+    for (int half = kRowThreads / 2; half > 0; half >>= 1) {
+        if ((int)threadIdx.x < half)
+            for (int q = 0; q < kSummary; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + half];
+        __syncthreads();
+    }
+    if (threadIdx.x < kSummary) a.partial[((long long)e * a.S + s) * kSummary + threadIdx.x] = red[threadIdx.x][0];
+}
+
+__global__ __launch_bounds__(64) void replay_finish_kernel(const RowsArgs a) {
+    const long long i = (long long)blockIdx.x * 64 + threadIdx.x;
+    if (i >= (long long)a.E * kSummary) return;
+    const long long e = i / kSummary;
+    const int q = (int)(i - e * kSummary);
+    double sum = 0.0;
+    for (int s = 0; s < a.S; ++s) sum += a.partial[(e * a.S + s) * kSummary + q];
+    a.summary[i] = sum;
+}
+
+// the refusals both entry points share; fills the geometry and the counts derived from it
+int check_config(const char *who, const wtk_replay_config *cfg, int32_t kind, int32_t E, int32_t n_cycles, int32_t n_track, Geometry &g, int &n_log) {
+    const std::string w(who);
+    if (!cfg) return fail(w + ": null argument");
+    if (kind < WTK_REPLAY_CSV || kind > WTK_REPLAY_MLP) return fail(w + ": unknown kind");
+    if (E < 1) return fail(w + ": at least one experiment (E >= 1)");
+    if (cfg->moving_frame_num < 1) return fail(w + ": moving_frame_num must be at least 1");
+    if (cfg->imaging_frame_num < 1) return fail(w + ": imaging_frame_num must be at least 1");
+    if (cfg->pred_frame_num > cfg->imaging_frame_num) return fail(w + ": pred_frame_num lies beyond imaging_frame_num");
+    if (cfg->pred_frame_num < (kind == WTK_REPLAY_CSV ? 1 : 0)) return fail(w + ": pred_frame_num must be at least 1 for the CSV kind (the controller has not seen the decision frame yet)");
+    if (cfg->num_frames < 1 || n_track < 0) return fail(w + ": negative size");
+    if (cfg->cam_w < cfg->mic_w || cfg->cam_h < cfg->mic_h) return fail(w + ": the camera is smaller than the microscope");
+    if (cfg->mic_w < 0 || cfg->mic_h < 0) return fail(w + ": negative microscope size");
+    if (cfg->frame_w < 1 || cfg->frame_h < 1) return fail(w + ": empty frame");
+    const long long L = (long long)cfg->imaging_frame_num + cfg->moving_frame_num;
+    if (L > INT32_MAX) return fail(w + ": cycle too long");
+    n_log = (int)((cfg->num_frames - 1) / L); // the last cycle is never logged (its end never arrives)
+    if ((long long)n_log * L > n_track) return fail(w + ": the track is shorter than the logged rows");
+    if (n_cycles < 1 || n_cycles < n_log) return fail(w + ": n_cycles must cover every logged cycle (and be at least 1)");
+    if ((long long)(n_cycles - 1) * L + cfg->imaging_frame_num > (long long)cfg->num_frames - 1)
+        return fail(w + ": the decision frame of cycle n_cycles - 1 lies beyond the experiment's frames");
+    g.L = (int)L, g.I = cfg->imaging_frame_num, g.M = cfg->moving_frame_num, g.P = cfg->pred_frame_num;
+    g.cam_w = cfg->cam_w, g.cam_h = cfg->cam_h, g.mic_w = cfg->mic_w, g.mic_h = cfg->mic_h;
+    g.x_max = cfg->frame_w - 1, g.y_max = cfg->frame_h - 1;
+    return 0;
+}
+
+} // namespace
+
+extern "C" int wtk_replay_scan(const wtk_replay_config *cfg, int32_t kind, int32_t E, int32_t n_cycles, const double *track_dev, int32_t n_track,
+                               const double *a_dev, const double *b_dev, const int32_t *valid_dev, const double *share_dev, int32_t *pos_dev,
+                               int32_t *move_dev, void *stream) {
+    ScanArgs s = {};
+    int n_log = 0;
+    if (check_config("wtk_replay_scan", cfg, kind, E, n_cycles, n_track, s.g, n_log)) return 1;
+    if (!track_dev || !share_dev || !pos_dev || !move_dev) return fail("wtk_replay_scan: null argument");
+    if (kind != WTK_REPLAY_CSV && (!a_dev || !valid_dev)) return fail("wtk_replay_scan: null targets");
+    if (kind == WTK_REPLAY_MLP && !b_dev) return fail("wtk_replay_scan: null origins (b_dev) for the MLP kind");
+    s.kind = kind, s.E = E, s.C = n_cycles, s.init_x = cfg->init_x, s.init_y = cfg->init_y;
+    s.track = track_dev, s.n_track = n_track, s.a = a_dev, s.b = b_dev, s.valid = valid_dev, s.share = share_dev, s.pos = pos_dev, s.move = move_dev;
+    hipLaunchKernelGGL(replay_scan_kernel, dim3((unsigned)((E + kScanThreads - 1) / kScanThreads)), dim3(kScanThreads), 0, (hipStream_t)stream, s);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int64_t wtk_replay_scratch_doubles(int32_t E, int64_t R) {
+    if (E < 0 || R < 0) return -1;
+    return (int64_t)E * ((R + kRowChunk - 1) / kRowChunk) * kSummary;
+}
+
+extern "C" int wtk_replay_rows(const wtk_replay_config *cfg, int32_t E, int32_t n_cycles, const double *track_dev, int32_t n_track,
+                               const double *share_dev, const int32_t *pos_dev, const int32_t *move_dev, const int32_t *row_slot_dev, int32_t n_slots, double *rows_dev,
+                               double *bbox_err_dev, double *mse_err_dev, double *summary_dev, double *scratch_dev, int64_t scratch_doubles,
+                               void *stream) {
+    RowsArgs r = {};
+    int n_log = 0;
+    if (check_config("wtk_replay_rows", cfg, WTK_REPLAY_OPTIMAL, E, n_cycles, n_track, r.g, n_log)) return 1;
+    if (!track_dev || !share_dev || !pos_dev || !move_dev || !summary_dev || !scratch_dev) return fail("wtk_replay_rows: null argument");
+    if ((row_slot_dev == nullptr) != (rows_dev == nullptr) || n_slots < 0 || (rows_dev && n_slots < 1))
+        return fail("wtk_replay_rows: row_slot_dev, rows_dev and n_slots >= 1 go together");
+    r.R = (long long)n_log * r.g.L;
+    const long long S = (r.R + kRowChunk - 1) / kRowChunk;
+    if (S * E > INT32_MAX) return fail("wtk_replay_rows: too many (experiment, chunk) blocks for one launch");
+    if (scratch_doubles < wtk_replay_scratch_doubles(E, r.R)) return fail("wtk_replay_rows: scratch smaller than wtk_replay_scratch_doubles(E, R)");
+    r.E = E, r.C = n_cycles, r.S = (int)S, r.n_log = n_log, r.n_slots = rows_dev ? n_slots : 0;
+    r.track = track_dev, r.share = share_dev, r.pos = pos_dev, r.move = move_dev, r.row_slot = row_slot_dev, r.rows = rows_dev;
+    r.bbox_err = bbox_err_dev, r.mse_err = mse_err_dev, r.partial = scratch_dev, r.summary = summary_dev;
+    hipStream_t st = (hipStream_t)stream;
+    if (S > 0) hipLaunchKernelGGL(replay_rows_kernel, dim3((unsigned)(S * E)), dim3(kRowThreads), 0, st, r);
+    hipLaunchKernelGGL(replay_finish_kernel, dim3((unsigned)(((long long)E * kSummary + 63) / 64)), dim3(64), 0, st, r);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}

@@ -40,6 +40,11 @@ class _ConvBlob(C.Structure):
                 ("reserved", C.c_int32), ("weight", C.POINTER(C.c_float)), ("bias", C.POINTER(C.c_float))]
 
 
+class _ReplayConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("num_frames", "imaging_frame_num", "moving_frame_num", "pred_frame_num", "cam_w", "cam_h", "mic_w", "mic_h",
+                                         "frame_w", "frame_h", "init_x", "init_y")]
+
+
 class _YoloDesc(C.Structure):
     _fields_ = [("device", C.c_int32), ("dtype", C.c_int32), ("imgsz_h", C.c_int32), ("imgsz_w", C.c_int32),
                 ("max_batch", C.c_int32), ("nc", C.c_int32), ("width_mult", C.c_float), ("depth_mult", C.c_float),
@@ -63,6 +68,7 @@ SYMBOLS = [
     "wtk_hybrid_pending", "wtk_hybrid_counters", "wtk_hybrid_config", "wtk_hybrid_hold",
     "wtk_background", "wtk_precise_error",
     "wtk_polyfit_dataset", "wtk_polyfit_mae_scratch_doubles", "wtk_polyfit_weight_mae", "wtk_polyfit_swarm_step",
+    "wtk_replay_scan", "wtk_replay_scratch_doubles", "wtk_replay_rows",
 ]
 
 
@@ -210,6 +216,10 @@ def load() -> C.CDLL:
     lib.wtk_polyfit_mae_scratch_doubles.restype = C.c_int64
     lib.wtk_polyfit_weight_mae.argtypes = [vp, vp, C.c_int64, i32, vp, i32, i32, i32, vp, i32, vp, vp, C.c_int64, vp, vp]
     lib.wtk_polyfit_swarm_step.argtypes = [vp, vp, i32, i32, i32, i32, f64, f64, f64, f64, f64, f64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.wtk_replay_scan.argtypes = [C.POINTER(_ReplayConfig), i32, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.wtk_replay_scratch_doubles.argtypes = [i32, C.c_int64]
+    lib.wtk_replay_scratch_doubles.restype = C.c_int64
+    lib.wtk_replay_rows.argtypes = [C.POINTER(_ReplayConfig), i32, i32, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, C.c_int64, vp]
     _lib = lib
     return lib
 
@@ -401,6 +411,36 @@ def polyfit_swarm_step(mae_dev, rand_dev, P: int, N: int, epoch: int, max_early_
     _check(load().wtk_polyfit_swarm_step(_ptr(mae_dev), _ptr(rand_dev), P, N, epoch, max_early_stop, float(w), float(c1), float(c2), float(lb), float(ub),
                                          float(vmax), _ptr(pos_dev), _ptr(vel_dev), _ptr(pbest_pos_dev), _ptr(pbest_val_dev), _ptr(gbest_pos_dev),
                                          _ptr(gbest_val_dev), _ptr(ctrl_dev), _ptr(history_dev), C.c_void_p(stream)), "wtk_polyfit_swarm_step")
+
+
+REPLAY_CSV, REPLAY_OPTIMAL, REPLAY_POLYFIT, REPLAY_MLP = 0, 1, 2, 3  # WTK_REPLAY_*
+REPLAY_ROW_DOUBLES, REPLAY_SUMMARY_DOUBLES = 16, 6
+
+
+def replay_config(num_frames: int, imaging_frame_num: int, moving_frame_num: int, pred_frame_num: int, camera_size: Sequence[int],
+                  micro_size: Sequence[int], frame_wh: Sequence[int], init_position: Sequence[int]) -> _ReplayConfig:
+    """The wtk_replay_config of an experiment; sizes and positions are (x, y) pairs."""
+    return _ReplayConfig(int(num_frames), int(imaging_frame_num), int(moving_frame_num), int(pred_frame_num), int(camera_size[0]), int(camera_size[1]),
+                         int(micro_size[0]), int(micro_size[1]), int(frame_wh[0]), int(frame_wh[1]), int(init_position[0]), int(init_position[1]))
+
+
+def replay_scan(cfg: _ReplayConfig, kind: int, E: int, n_cycles: int, track_dev, n_track: int, a_dev, b_dev, valid_dev, share_dev, pos_dev, move_dev,
+                stream: int = 0):
+    """Moves and cycle-start positions of E experiments (wtk_replay_scan); per-cycle arrays are [n_cycles, E, ...] device tensors."""
+    _check(load().wtk_replay_scan(C.byref(cfg) if cfg is not None else None, kind, E, n_cycles, _ptr(track_dev), n_track, _ptr(a_dev), _ptr(b_dev),
+                                  _ptr(valid_dev), _ptr(share_dev), _ptr(pos_dev), _ptr(move_dev), C.c_void_p(stream)), "wtk_replay_scan")
+
+
+def replay_scratch_doubles(E: int, R: int) -> int:
+    return int(load().wtk_replay_scratch_doubles(E, R))
+
+
+def replay_rows(cfg: _ReplayConfig, E: int, n_cycles: int, track_dev, n_track: int, share_dev, pos_dev, move_dev, row_slot_dev, n_slots: int, rows_dev,
+                bbox_err_dev, mse_err_dev, summary_dev, scratch_dev, scratch_doubles: int, stream: int = 0):
+    """Log rows, per-row errors and per-experiment summaries from a scan's positions and moves (wtk_replay_rows)."""
+    _check(load().wtk_replay_rows(C.byref(cfg) if cfg is not None else None, E, n_cycles, _ptr(track_dev), n_track, _ptr(share_dev), _ptr(pos_dev),
+                                  _ptr(move_dev), _ptr(row_slot_dev), n_slots, _ptr(rows_dev), _ptr(bbox_err_dev), _ptr(mse_err_dev), _ptr(summary_dev),
+                                  _ptr(scratch_dev), scratch_doubles, C.c_void_p(stream)), "wtk_replay_rows")
 
 
 # -------------------------------------------------------------------------------------------------
