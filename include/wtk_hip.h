@@ -284,7 +284,10 @@ int wtk_track_training_pairs(const void *track_dev, int32_t track_is_f64, int32_
  * reports a decision margin per frame (wtk_yolo_margin_buffer); the K frames of a batch with the smallest margins are
  * detected again by a full-precision handle (WTK_F16X3 / WTK_F32, e.g. through wtk_yolo_predict_views with
  * frame_index = slots) and replace the fast rows where margin < `margin`.  No host synchronisation: K is fixed.
- *   wtk_recheck_select  slots[k] = batch row of the k-th smallest margin (ties: lower row first; NaN = +inf), k < K;
+ * One reading of "weak" holds in every entry point below: a row is weak iff margin < `margin` on the margin AS GIVEN, so a NaN row is
+ * never weak (NaN < x is false for every x) and with `margin` = +inf every row but the NaN and +inf ones is.
+ *   wtk_recheck_select  slots[k] = batch row of the k-th smallest margin (ties: lower row first; for the ORDER a NaN counts as +inf
+ *                       and ties with a real +inf; -0.0 and +0.0 tie), k < K;
  *                       *n_weak (nullable) = min(K, rows with margin < `margin`): the leading slots that will be merged
  *   wtk_recheck_select_counted  the same, and *n_overflow (nullable) += max(rows with margin < `margin` - K, 0): the weak rows
  *                       the ceiling K cut off.  They keep their fast-pass result WITHOUT a second look, so a caller that

@@ -165,16 +165,18 @@ template <typename T> __global__ __launch_bounds__(64) void track_pairs_kernel(c
     a.keep[i] = ok ? 1 : 0;
 }
 
-// rank of every margin among the batch's (ties broken by row): the K smallest go to slots[rank]; NaN counts as +inf.
-// The weak rows (margin < thr) are counted by all 256 threads (wave ballots + one LDS add per wave); what the ceiling K cuts
-// off is ADDED to *n_overflow, so that a caller with K < B can see that rows kept their fast result without a second look.
+// rank of every margin among the batch's (ties broken by row): the K smallest go to slots[rank]; for the ORDER a NaN counts as +inf
+// (it ties with a real +inf, lower row first).  The weak rows are counted on the RAW margin (margin < thr: a NaN row is never weak,
+// whatever thr — +inf included — exactly as recheck_merge_kernel and recheck_enqueue_plan_kernel decide it) by all 256 threads (wave
+// shuffles + one LDS add per wave); what the ceiling K cuts off is ADDED to *n_overflow, so that a caller with K < B can see that rows
+// kept their fast result without a second look.
 __global__ __launch_bounds__(256) void recheck_select_kernel(const RecheckArgs a) {
     __shared__ float m[1024];
     __shared__ int weak;
     if (threadIdx.x == 0) weak = 0;
     for (int i = threadIdx.x; i < a.B; i += 256) {
         const float v = a.margins[i];
-        m[i] = v == v ? v : 3.4e38f;
+        m[i] = v == v ? v : INFINITY;
     }
     __syncthreads();
     int mine = 0;
@@ -183,7 +185,7 @@ __global__ __launch_bounds__(256) void recheck_select_kernel(const RecheckArgs a
         int rank = 0;
         for (int j = 0; j < a.B; ++j) rank += (m[j] < mi || (m[j] == mi && j < i)) ? 1 : 0;
         if (rank < a.K) a.slots[rank] = i;
-        mine += mi < a.thr ? 1 : 0;
+        mine += a.margins[i] < a.thr ? 1 : 0;
     }
     if (a.n_weak || a.n_overflow) {
         for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off, 64);
