@@ -34,11 +34,15 @@ ENVS = {
 HOST_ONLY = ["--cuda-host-only", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function", "-Wno-unused-variable"]
 
 
-def _sources() -> list:
+def _build_lists():
     sys.path.insert(0, ROOT)
     from wtracker_amd import _build
 
-    return list(_build.SOURCES)
+    return _build
+
+
+def _sources() -> list:
+    return list(_build_lists().SOURCES)
 
 
 def _newer(target: str, deps: list) -> bool:
@@ -53,7 +57,7 @@ def _run(cmd: list) -> None:
 
 def build(verbose: bool = False) -> str:
     os.makedirs(OUT, exist_ok=True)
-    headers = [os.path.join(CSRC, "wtk_kernels.h"), os.path.join(CSRC, "wtk_internal.h"), os.path.join(ROOT, "include", "wtk_hip.h")]
+    headers = [os.path.normpath(os.path.join(CSRC, h)) for h in _build_lists().HEADERS]
     jobs, objs = [], []
     for src in _sources():
         obj = os.path.join(OUT, src.replace(".hip", ".o"))

@@ -15,14 +15,11 @@
 // Two barriers per tile (T1 complete; window landed + T1/window reads retired).  Every stage rounds to fp16 where the layer-by-layer
 // kernels store fp16, walks K in the same order (taps 0..8; a, b, m) and uses the same MFMA + SiLU, so the
 // result is bit-identical to conv3x3_c32_kernel x2 + conv_igemm_kernel.
-#include "wtk_kernels.h"
+#include "wtk_device.h"
 
 namespace wtk {
 
 namespace {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 constexpr int kT = 16;             // output tile edge
 constexpr int kP = kT + 4;         // 20: window edge = flat pitch
@@ -33,23 +30,7 @@ constexpr int kWmBytes = 9 * 32 * 64; // [tap][cout] rows of 64 B
 constexpr int kWcBytes = 3 * 64 * 64; // [k slab][cout] rows of 64 B
 static_assert(2 * kBRows * 64 + kT1Rows * 64 + 2 * 256 * 64 + 2 * kWmBytes + kWcBytes <= 160 * 1024, "LDS budget");
 
-__device__ __forceinline__ float pin_f32(float v) {
-    asm("" : "+v"(v));
-    return v;
-}
-// same SiLU as the stand-alone kernels; the product is pinned to fp32 so "(half)(x * r)" is never folded into a
-// single-rounding v_fma_mixlo_f16 (see front_fused.hip)
-__device__ __forceinline__ float silu_cf(float x) {
-    return wtk_silu_scaled(x); // scaled domain, see wtk_kernels.h
-}
-// Raw barriers: s_waitcnt + s_barrier, with compiler-level memory clobbers so no LDS access is moved across them
-// (the s_barrier intrinsic alone is IntrNoMem).  lds_barrier leaves global loads/stores and LDS-DMA in flight.
-__device__ __forceinline__ void lds_barrier() {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_waitcnt(0xc07f); // lgkmcnt(0) only
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
+// lds_barrier (wtk_device.h) leaves global loads/stores and LDS-DMA in flight; this one also waits for them
 __device__ __forceinline__ void vm_lds_barrier() {
     asm volatile("" ::: "memory");
     __builtin_amdgcn_s_waitcnt(0x0070); // vmcnt(0) lgkmcnt(0): this wave's LDS-DMA pieces have landed
@@ -267,7 +248,7 @@ __global__ __launch_bounds__(512, 2) void c2f32_fused_kernel(const C2fArgs a) {
                         for (int r = 0; r < 4; ++r) t[i * 4 + r] = acc[j][i][r];
                     wtk_silu_scaled_run<8>(t);
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) hv[e] = (_Float16)pin_f32(t[e] + (float)res[e]);
+                    for (int e = 0; e < 8; ++e) hv[e] = (_Float16)wtk_pin_f32(t[e] + (float)res[e]);
                 }
                 const int p = (2 * wave + j) * 16 + lr;
                 *reinterpret_cast<half8 *>(mbuf + row64(p, lg)) = hv;

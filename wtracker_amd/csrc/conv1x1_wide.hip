@@ -16,38 +16,15 @@
 //     the SOURCE side of the LDS-DMA (the lane landing on physical chunk p of a row fetches logical chunk p ^ key).
 // Arithmetic is conv_igemm_kernel's: accumulators start at the bias, K is walked upwards in 32-element MFMA steps
 // (v_mfma_f32_16x16x32_f16), SiLU in the log2(e)-scaled domain, one fp16 rounding at the store: bit-identical outputs.
-#include "wtk_kernels.h"
+#include "wtk_device.h"
 
 namespace wtk {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
 constexpr int kBM = 256, kBN = 128, kKS = 32;      // block tile, K elements per step
 constexpr int kStageA = kBM * 64, kStageB = kBN * 64; // bytes
 constexpr int kStage = kStageA + kStageB;            // 24 KB
-
-// one 1-KiB LDS-DMA request in buffer form (SGPR resource + wave-uniform byte offset + per-lane 32-bit offset; a lane offset of
-// 0xffffffff is out of range and lands zeros): 5-10 % less wave time per request than the flat form (tools/lds_dma_rate.hip)
-typedef int rsrc_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ rsrc_t make_rsrc(const void *base) {
-    const unsigned long long b = (unsigned long long)base;
-    rsrc_t r;
-    r.x = (int)(unsigned)(b & 0xffffffffu);
-    r.y = (int)(unsigned)((b >> 32) & 0xffffu);
-    r.z = (int)0xffffff00u;
-    r.w = 0x00020000;
-    return r;
-}
-template <bool NT> __device__ __forceinline__ void dma16(const rsrc_t &rs, unsigned voff, unsigned soff, char *lds_dst) {
-    const unsigned lds = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char *)lds_dst;
-    if constexpr (NT)
-        asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen nt lds" ::"v"(voff), "s"(rs), "s"(soff), "s"(lds) : "memory");
-    else
-        asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds" ::"v"(voff), "s"(rs), "s"(soff), "s"(lds) : "memory");
-}
 
 // NT: the pixel rows are read by exactly one cout tile (CoutPad == 128): non-temporal hint on their requests
 template <bool NT> __global__ __launch_bounds__(256, 2) void conv1x1_wide_kernel(const ConvArgs a) {
@@ -113,9 +90,9 @@ template <bool NT> __global__ __launch_bounds__(256, 2) void conv1x1_wide_kernel
         const bool k_ok = ld_ks * kKS < a.Cin; // steps past Cin (K padding) read zeros
         const unsigned so = (unsigned)(ld_ks * (kKS * 2));
 #pragma unroll
-        for (int q = 0; q < 4; ++q) dma16<NT>(ars, k_ok ? avoff[q] : 0xffffffffu, so, st + (wave + 4 * q) * 1024);
+        for (int q = 0; q < 4; ++q) lds_dma_buf<NT>(ars, k_ok ? avoff[q] : 0xffffffffu, so, st + (wave + 4 * q) * 1024);
 #pragma unroll
-        for (int q = 0; q < 2; ++q) dma16<false>(wrs, wvoff[q], so, st + kStageA + (wave + 4 * q) * 1024);
+        for (int q = 0; q < 2; ++q) lds_dma_buf<false>(wrs, wvoff[q], so, st + kStageA + (wave + 4 * q) * 1024);
         if (++ld_ks == nk) {
             if (++ld_i < my_tiles) setup_loader(ld_i);
         }

@@ -10,7 +10,7 @@
 //   * 64-byte rows need their own XOR swizzles (bank = (addr/4) % 64 covers FOUR rows): pixel rows use
 //     key = (row >> 1) & 3, weight rows key = (((row / NV) & 1) << 1) | ((row >> 1) & 1); both were
 //     checked conflict-free for every ds_read_b128 lane group and every tap offset by enumeration.
-#include "wtk_kernels.h"
+#include "wtk_device.h"
 
 #include <algorithm>
 
@@ -18,15 +18,8 @@ namespace wtk {
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-
 constexpr int kBM = 256;
 constexpr int kRowsMax = kHaloRowsMax; // same strip geometry as the 128-byte-row kernel
-
-__device__ __forceinline__ float silu_c(float x) {
-    return wtk_silu_scaled(x); // x is the log2(e)-scaled pre-activation (wtk_kernels.h)
-}
 
 template <int BN> // BN = CoutPad: 32, 64 or 96; 4 waves, each 64 px x BN cout
 __global__ __launch_bounds__(256) void conv3x3_c32_kernel(const HaloArgs a) {
@@ -127,7 +120,7 @@ __global__ __launch_bounds__(256) void conv3x3_c32_kernel(const HaloArgs a) {
             for (int r = 0; r < 4; ++r) v[i * 4 + r] = acc[i][j][r];
         if (a.act) {
 #pragma unroll
-            for (int i = 0; i < NV; ++i) v[i] = silu_c(v[i]);
+            for (int i = 0; i < NV; ++i) v[i] = wtk_silu_scaled(v[i]);
         }
         const long long pix = ((long long)n * a.H + (int)y) * a.W + xs + x;
         if (res) {

@@ -24,184 +24,30 @@
 //   * 8 waves / block (2 per SIMD); wave tile 64 px x 64 cout (BN = 128) or 32 px x 64 cout (BN = 64);
 //   * all four LDS buffers are distinct objects so hipcc's waitcnt pass does not drain the in-flight
 //     LDS-DMA before each fragment read (see conv_igemm.hip).
-#include "wtk_kernels.h"
+#include "conv3x3_window.h"
 
 #include <cstdlib>
 #include <type_traits>
 
 namespace wtk {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
-template <typename T> struct ElemH;
-template <> struct ElemH<_Float16> {
-    static constexpr int CE = 8;
-};
-template <> struct ElemH<float> {
-    static constexpr int CE = 4;
-};
-
-// SiLU with two transcendentals and three plain VALU ops (v_mul, v_exp, v_add, v_rcp, v_mul).  The obvious
-// x / (1 + __expf(-x)) expands to ~35 instructions (IEEE division + range-checked exp) and made the
-// epilogue, not the MFMA loop, the longest part of every conv.  v_exp/v_rcp are 1-ulp approximations.
-__device__ __forceinline__ float silu_h(float x) {
-    return wtk_silu_scaled(x); // x is the log2(e)-scaled pre-activation (wtk_kernels.h)
-}
-
-__device__ __forceinline__ void mma_h(const uint4 &wf, const uint4 &pf, floatx4 &acc, _Float16 *) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, wf), __builtin_bit_cast(half8, pf), acc, 0, 0, 0);
-}
-__device__ __forceinline__ void mma_h(const uint4 &wf, const uint4 &pf, floatx4 &acc, float *) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__builtin_bit_cast(float, wf.x), __builtin_bit_cast(float, pf.x), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__builtin_bit_cast(float, wf.y), __builtin_bit_cast(float, pf.y), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__builtin_bit_cast(float, wf.z), __builtin_bit_cast(float, pf.z), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__builtin_bit_cast(float, wf.w), __builtin_bit_cast(float, pf.w), acc, 0, 0, 0);
-}
-
-template <int NV> __device__ __forceinline__ void load_run_h(const _Float16 *p, float (&v)[NV]) {
-#pragma unroll
-    for (int i = 0; i < NV; i += 8) {
-        half8 h = *reinterpret_cast<const half8 *>(p + i);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[i + j] = (float)h[j];
-    }
-}
-template <int NV> __device__ __forceinline__ void load_run_h(const float *p, float (&v)[NV]) {
-#pragma unroll
-    for (int i = 0; i < NV; i += 4) {
-        float4 f = *reinterpret_cast<const float4 *>(p + i);
-        v[i] = f.x, v[i + 1] = f.y, v[i + 2] = f.z, v[i + 3] = f.w;
-    }
-}
-template <int NV> __device__ __forceinline__ void store_run_h(_Float16 *p, const float (&v)[NV]) {
-#pragma unroll
-    for (int i = 0; i < NV; i += 8) {
-        half8 h;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) h[j] = (_Float16)v[i + j];
-        *reinterpret_cast<half8 *>(p + i) = h;
-    }
-}
-template <int NV> __device__ __forceinline__ void store_run_h(float *p, const float (&v)[NV]) {
-#pragma unroll
-    for (int i = 0; i < NV; i += 4) *reinterpret_cast<float4 *>(p + i) = make_float4(v[i], v[i + 1], v[i + 2], v[i + 3]);
-}
-
-constexpr int kBM = 256;
-
-// One LDS-DMA piece (64 lanes x 16 B -> 1 KiB at the wave-uniform LDS address).  RAW = true issues it from inline asm:
-// hipcc then does not know an LDS write is pending and inserts no vmcnt wait of its own in front of later ds_reads —
-// the three-slab schedule orders every read behind an explicit counted wait + barrier instead.  (With the builtin, the
-// waitcnt pass tracks pending LDS-DMA per LDS object; once a few are in flight it gives up counting and drains with
-// vmcnt(0) before the first fragment read of a slab, which is exactly the in-flight request the schedule relies on.)
-template <bool RAW> __device__ __forceinline__ void lds_dma16(const char *src, char *lds_dst) {
-    if constexpr (RAW) {
-        const unsigned lds = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char *)lds_dst;
-        asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(lds) : "memory");
-    } else {
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src, (__attribute__((address_space(3))) void *)lds_dst, 16, 0, 0);
-    }
-}
-
-// The same request in buffer form: SGPR resource (base, huge range) + wave-uniform byte offset + per-lane 32-bit offset.  Measured
-// 5-10 % less wave time per request than the flat form (tools/lds_dma_rate.hip: 108 vs 120 cycles), no 64-bit address arithmetic
-// per request, and a lane whose offset is 0xffffffff is out of range and lands ZEROS: no zero-page select for padding rows.
+// LDS-DMA requests of the ring schedules in buffer form (lds_dma_buf, wtk_device.h); 0: the flat form
 #ifndef WTK_HALO_BUFFER_DMA
 #define WTK_HALO_BUFFER_DMA 1
 #endif
-typedef int rsrc_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ rsrc_t make_rsrc(const void *base) {
-    const unsigned long long b = (unsigned long long)base;
-    rsrc_t r;
-    r.x = (int)(unsigned)(b & 0xffffffffu);
-    r.y = (int)(unsigned)((b >> 32) & 0xffffu); // stride 0: raw buffer
-    r.z = (int)0xffffff00u;                     // num_records (bytes): everything a 32-bit offset can reach except the "invalid" marker
-    r.w = 0x00020000;                           // DATA_FORMAT = 32-bit (gfx9 family raw-buffer word 3)
-    return r;
-}
-__device__ __forceinline__ void lds_dma16_buf(const rsrc_t &rs, unsigned voff, unsigned soff, char *lds_dst) {
-    const unsigned lds = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char *)lds_dst;
-    asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds" ::"v"(voff), "s"(rs), "s"(soff), "s"(lds) : "memory");
-}
 
-// s_waitcnt vmcnt(n) for a wave-uniform runtime n (the instruction takes an immediate)
-__device__ __forceinline__ void wait_vmcnt(int n) {
-    switch (n) {
-    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-    case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-    case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-    case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-    case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-    case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-    case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-    case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-    case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-    case 10: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-    case 11: asm volatile("s_waitcnt vmcnt(11)" ::: "memory"); break;
-    case 12: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-    case 13: asm volatile("s_waitcnt vmcnt(13)" ::: "memory"); break;
-    case 14: asm volatile("s_waitcnt vmcnt(14)" ::: "memory"); break;
-    case 15: asm volatile("s_waitcnt vmcnt(15)" ::: "memory"); break;
-    case 16: asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    }
+// ---- steps the four fused-tail epilogues of conv3x3_halo_kernel share (lg = lane >> 4)
+// the tail's accumulators start at its bias: couts c .. c + 3
+__device__ __forceinline__ floatx4 tail_bias4(const HaloArgs &a, int c) { return (floatx4){a.tail_bias[c + 0], a.tail_bias[c + 1], a.tail_bias[c + 2], a.tail_bias[c + 3]}; }
+// NV2 tail couts lg * NV2 .. of pixel `pix`: fp32 (head logits are never rounded; F32: the launcher admits nothing else) or fp16
+template <bool F32, int NV2> __device__ __forceinline__ void tail_store(const HaloArgs &a, long long pix, int lg, const float (&v2)[NV2]) {
+    if (F32 || a.tail_f32)
+        store_run<NV2>(reinterpret_cast<float *>(a.tail_out) + pix * a.tail_ld + a.tail_coff + lg * NV2, v2);
+    else
+        store_run<NV2>(reinterpret_cast<_Float16 *>(a.tail_out) + pix * a.tail_ld + a.tail_coff + lg * NV2, v2);
 }
-
-// Stacked geometry (header comment).  Window row `flat` (relative to the strip) -> input pixel: stacked row rho = flat / pitch
-// holds image n = rho / (H+1), input row iy = rho % (H+1) - 1 (-1: the shared zero row); column ix = xs + flat % pitch - 1.
-__device__ __forceinline__ bool halo_in_coords(const HaloArgs &a, int flat, int xs, int &n, int &iy, int &ix) {
-    const int rho = (int)fdiv((unsigned)flat, a.d_pitch);
-    const int cc = flat - rho * a.pitch;
-    n = (int)fdiv((unsigned)rho, a.d_h1);
-    iy = rho - n * (a.H + 1) - 1;
-    ix = xs + cc - 1;
-    return n < a.N && iy >= 0 && (unsigned)ix < (unsigned)a.W;
-}
-// Flat output index -> (image, row, column inside the strip); false for the junk row / junk columns / past the last image
-__device__ __forceinline__ bool halo_out_coords(const HaloArgs &a, int o, int xs, int &n, int &y, int &x) {
-    const int q = (int)fdiv((unsigned)o, a.d_pitch);
-    x = o - q * a.pitch;
-    n = (int)fdiv((unsigned)q, a.d_h1);
-    y = q - n * (a.H + 1);
-    return n < a.N && y < a.H && x < a.S && xs + x < a.W;
-}
-
-// Per-lane byte offsets of a wave's window pieces (wave w stages pieces w, w+8, ...: 8 rows x 8 chunks of 16 B each).  The 8 x KMAX
-// rows of a wave are evaluated ONCE — lane L works out row L&7 of piece L>>3 — and handed to the lanes that need them with
-// ds_bpermute, instead of every lane redoing the divisions for each of its pieces: the ~250 VALU instructions this took per
-// block sat in front of the block's first LDS-DMA request (stamped: 0.5 us of a 10-18 us block).
-template <typename T, int KMAX>
-__device__ __forceinline__ void halo_piece_offsets(const HaloArgs &a, int o0, int xs, int n_base, int halo_rows, int wave, int lane, unsigned (&hoff)[KMAX],
-                                                   unsigned &hvalid) {
-    static_assert(KMAX <= 8, "one lane per (piece, row)");
-    constexpr int CE = ElemH<T>::CE;
-    const int hr_e = (wave + 8 * (lane >> 3)) * 8 + (lane & 7);
-    int pn, iy, ix;
-    const bool ok_e = halo_in_coords(a, o0 + hr_e, xs, pn, iy, ix) && hr_e < halo_rows;
-    const unsigned row_e = ok_e ? (unsigned)(((((long long)(pn - n_base) * a.H + iy) * a.W + ix) * a.in_ld) * (long long)sizeof(T)) : 0xffffffffu;
-    const unsigned lc_term = (unsigned)((((lane & 7) ^ ((lane >> 3) & 7)) * CE) * (int)sizeof(T)); // logical chunk landing on this lane's slot
-    hvalid = 0;
-#pragma unroll
-    for (int q = 0; q < KMAX; ++q) {
-        const unsigned v = (unsigned)__builtin_amdgcn_ds_bpermute((q * 8 + (lane >> 3)) * 4, (int)row_e);
-        const bool ok = v != 0xffffffffu;
-        hoff[q] = ok ? v + lc_term : 0u;
-        hvalid |= ok ? (1u << q) : 0u;
-    }
-}
-// Output pixel of a wave's flat outputs o_first + L (L < 64), evaluated once per lane: pixel index (n*H + y)*W + xs + x, or -1 for
-// junk rows / columns; `col` = xs + x.  The lanes of pixel tile j fetch theirs with ds_bpermute from lane j*16 + (lane & 15).
-__device__ __forceinline__ void halo_out_pixel(const HaloArgs &a, int o_first, int xs, int lane, int &pix_e, int &col_e) {
-    int n, y, x;
-    const bool ok = halo_out_coords(a, o_first + lane, xs, n, y, x);
-    col_e = xs + x;
-    pix_e = ok ? (n * a.H + y) * a.W + col_e : -1;
-}
-__device__ __forceinline__ int lane_fetch(int src_lane, int v) { return __builtin_amdgcn_ds_bpermute(src_lane * 4, v); }
 
 // HROWS: window rows one LDS buffer holds.  NWB: weight slabs in the ring (2, 3, or 6: the split 64-cout x 128-pixel tile of small handles, see the
 // tap loop).  With NWB == 3 the slab of tap g+2 is
@@ -226,7 +72,7 @@ __global__ __launch_bounds__(512, MINW) void conv3x3_halo_kernel(const HaloArgs 
     asm volatile("" ::"s"(a.in), "s"(a.w), "s"(a.bias), "s"(a.zeros), "s"(a.in_ld), "s"(a.in_coff), "s"(a.N), "s"(a.H), "s"(a.W), "s"(a.Cin), "s"(a.CoutPad),
                  "s"(a.Kpad), "s"(a.S), "s"(a.pitch), "s"(a.strips), "s"(a.d_strips.mul), "s"(a.d_strips.sh1), "s"(a.d_strips.sh2), "s"(a.d_pitch.mul),
                  "s"(a.d_pitch.sh1), "s"(a.d_pitch.sh2), "s"(a.d_nct.mul), "s"(a.d_nct.sh1), "s"(a.d_nct.sh2), "s"(a.d_h1.mul), "s"(a.d_h1.sh1), "s"(a.d_h1.sh2), "s"(a.grid), "s"(a.live_off));
-    constexpr int CE = ElemH<T>::CE;
+    constexpr int CE = Elem<T>::CE;
     constexpr int CCH = 8 * CE; // channels per 128-byte chunk
     // BN = 64: 8(P) x 1(C) waves of 32 px x 64 cout; BN = 128 / 192: 4(P) x 2(C) waves of 64 px x 64 / 96 cout
     constexpr int WAVES_C = BN == 64 ? 1 : 2, WAVES_P = 8 / WAVES_C;
@@ -305,7 +151,7 @@ __global__ __launch_bounds__(512, MINW) void conv3x3_halo_kernel(const HaloArgs 
         const int piece = wave + 8 * q;
         if (piece >= halo_pieces) return; // wave-uniform
         if constexpr (kRing && WTK_HALO_BUFFER_DMA) {
-            lds_dma16_buf(make_rsrc(img), ((hvalid >> q) & 1u) ? hoff[q] : 0xffffffffu, (unsigned)(c * (CCH * (int)sizeof(T))), buf + piece * 1024);
+            lds_dma_buf(make_rsrc(img), ((hvalid >> q) & 1u) ? hoff[q] : 0xffffffffu, (unsigned)(c * (CCH * (int)sizeof(T))), buf + piece * 1024);
         } else {
             const char *src = ((hvalid >> q) & 1u) ? img + (size_t)c * (CCH * sizeof(T)) + hoff[q] : zero_page;
             lds_dma16<kRing>(src, buf + piece * 1024);
@@ -321,7 +167,7 @@ __global__ __launch_bounds__(512, MINW) void conv3x3_halo_kernel(const HaloArgs 
         const unsigned off = back ? hoff[q > 0 ? q - 1 : 0] : hoff[q];
         const bool ok = back ? ((hvalid >> (q > 0 ? q - 1 : 0)) & 1u) : ((hvalid >> q) & 1u);
         if constexpr (kRing && WTK_HALO_BUFFER_DMA) {
-            lds_dma16_buf(make_rsrc(img), ok ? off : 0xffffffffu, (unsigned)(c * (CCH * (int)sizeof(T))), buf + piece * 1024);
+            lds_dma_buf(make_rsrc(img), ok ? off : 0xffffffffu, (unsigned)(c * (CCH * (int)sizeof(T))), buf + piece * 1024);
         } else {
             const char *src = ok ? img + (size_t)c * (CCH * sizeof(T)) + off : zero_page;
             lds_dma16<kRing>(src, buf + piece * 1024);
@@ -343,7 +189,7 @@ __global__ __launch_bounds__(512, MINW) void conv3x3_halo_kernel(const HaloArgs 
             const rsrc_t rs = make_rsrc(wtile);
             const unsigned so = (unsigned)((tap * a.Cin + c * CCH) * (int)sizeof(T)); // wave-uniform
 #pragma unroll
-            for (int i = 0; i < WR; ++i) lds_dma16_buf(rs, wvoff[i], so, buf + (64 * i + 8 * wave) * 128);
+            for (int i = 0; i < WR; ++i) lds_dma_buf(rs, wvoff[i], so, buf + (64 * i + 8 * wave) * 128);
         } else {
             const char *ub = wtile + ((size_t)tap * a.Cin + (size_t)c * CCH) * sizeof(T); // wave-uniform
 #pragma unroll
@@ -385,13 +231,13 @@ __global__ __launch_bounds__(512, MINW) void conv3x3_halo_kernel(const HaloArgs 
             for (int i = 0; i < TC; ++i)
 #pragma unroll
                 for (int j = 0; j < TP; ++j) {
-                    mma_h(wh[i], ph[j], acc[i][j], (T *)nullptr);
-                    mma_h(wl[i], ph[j], acc1[i][j], (T *)nullptr);
+                    mma_frag(wh[i], ph[j], acc[i][j], (T *)nullptr);
+                    mma_frag(wl[i], ph[j], acc1[i][j], (T *)nullptr);
                 }
 #pragma unroll
             for (int i = 0; i < TC; ++i)
 #pragma unroll
-                for (int j = 0; j < TP; ++j) mma_h(wh[i], pl[j], acc1[i][j], (T *)nullptr);
+                for (int j = 0; j < TP; ++j) mma_frag(wh[i], pl[j], acc1[i][j], (T *)nullptr);
             return;
         }
 #pragma unroll
@@ -406,7 +252,7 @@ __global__ __launch_bounds__(512, MINW) void conv3x3_halo_kernel(const HaloArgs 
 #pragma unroll
             for (int i = 0; i < TC; ++i)
 #pragma unroll
-                for (int j = 0; j < TP; ++j) mma_h(wf[i], pf[j], acc[i][j], (T *)nullptr);
+                for (int j = 0; j < TP; ++j) mma_frag(wf[i], pf[j], acc[i][j], (T *)nullptr);
         }
     };
 
@@ -435,13 +281,13 @@ __global__ __launch_bounds__(512, MINW) void conv3x3_halo_kernel(const HaloArgs 
             for (int i = 0; i < TC; ++i)
 #pragma unroll
                 for (int j = 0; j < TP; ++j) {
-                    mma_h(f[2 * TP + i], f[j], acc[i][j], (T *)nullptr);
-                    mma_h(f[2 * TP + TC + i], f[j], acc1[i][j], (T *)nullptr);
+                    mma_frag(f[2 * TP + i], f[j], acc[i][j], (T *)nullptr);
+                    mma_frag(f[2 * TP + TC + i], f[j], acc1[i][j], (T *)nullptr);
                 }
 #pragma unroll
             for (int i = 0; i < TC; ++i)
 #pragma unroll
-                for (int j = 0; j < TP; ++j) mma_h(f[2 * TP + i], f[TP + j], acc1[i][j], (T *)nullptr);
+                for (int j = 0; j < TP; ++j) mma_frag(f[2 * TP + i], f[TP + j], acc1[i][j], (T *)nullptr);
         }
     };
 
@@ -671,13 +517,7 @@ __global__ __launch_bounds__(512, MINW) void conv3x3_halo_kernel(const HaloArgs 
 #pragma unroll
                 for (int c2 = 0; c2 < 2; ++c2) {
                     half8 hv, lv;
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        const float x = v[c2 * 8 + e];
-                        const _Float16 hh = (_Float16)x;
-                        hv[e] = hh;
-                        lv[e] = (_Float16)((x - (float)hh) * kSplitScale);
-                    }
+                    split_pack8(v + c2 * 8, hv, lv);
                     const int c = 2 * (lg & 1) + c2; // chunk of the hi halves; the lo halves: + 4
                     *reinterpret_cast<half8 *>(mine + p * 128 + ((c ^ (p & 7)) << 4)) = hv;
                     *reinterpret_cast<half8 *>(mine + p * 128 + (((c + 4) ^ (p & 7)) << 4)) = lv;
@@ -691,7 +531,7 @@ __global__ __launch_bounds__(512, MINW) void conv3x3_halo_kernel(const HaloArgs 
         floatx4 acc2[2][TPH], acc2l[2][TPH];
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            const floatx4 b4 = (floatx4){a.tail_bias[lg * 8 + i * 4 + 0], a.tail_bias[lg * 8 + i * 4 + 1], a.tail_bias[lg * 8 + i * 4 + 2], a.tail_bias[lg * 8 + i * 4 + 3]};
+            const floatx4 b4 = tail_bias4(a, lg * 8 + i * 4);
 #pragma unroll
             for (int j = 0; j < TPH; ++j) acc2[i][j] = b4, acc2l[i][j] = (floatx4){0.f, 0.f, 0.f, 0.f};
         }
@@ -721,8 +561,7 @@ __global__ __launch_bounds__(512, MINW) void conv3x3_halo_kernel(const HaloArgs 
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v2[i * 4 + r] = wtk_split_value(acc2[i][j][r], acc2l[i][j][r]);
-            if (lg * 8 < a.tail_cout) // padded couts are never stored; the class logits are an fp32 tensor (launch check)
-                store_run_h<8>(reinterpret_cast<float *>(a.tail_out) + pix * a.tail_ld + a.tail_coff + lg * 8, v2);
+            if (lg * 8 < a.tail_cout) tail_store<true>(a, pix, lg, v2); // padded couts are never stored; the class logits are an fp32 tensor (launch check)
         }
         return;
     } else if constexpr (TAIL && SPLIT) {
@@ -757,13 +596,7 @@ __global__ __launch_bounds__(512, MINW) void conv3x3_halo_kernel(const HaloArgs 
 #pragma unroll
                 for (int c2 = 0; c2 < 2; ++c2) {
                     half8 hv, lv;
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        const float x = v[c2 * 8 + e];
-                        const _Float16 hh = (_Float16)x;
-                        hv[e] = hh;
-                        lv[e] = (_Float16)((x - (float)hh) * kSplitScale);
-                    }
+                    split_pack8(v + c2 * 8, hv, lv);
                     const int c = 2 * (lg & 1) + c2; // chunk of the hi halves; the lo halves: + 4
                     *reinterpret_cast<half8 *>(mine + p * 128 + ((c ^ (p & 7)) << 4)) = hv;
                     *reinterpret_cast<half8 *>(mine + p * 128 + (((c + 4) ^ (p & 7)) << 4)) = lv;
@@ -774,8 +607,7 @@ __global__ __launch_bounds__(512, MINW) void conv3x3_halo_kernel(const HaloArgs 
         floatx4 acc2[4][TP], acc2l[4][TP];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const floatx4 b4 = (floatx4){a.tail_bias[lg * 16 + i * 4 + 0], a.tail_bias[lg * 16 + i * 4 + 1], a.tail_bias[lg * 16 + i * 4 + 2],
-                                         a.tail_bias[lg * 16 + i * 4 + 3]};
+            const floatx4 b4 = tail_bias4(a, lg * 16 + i * 4);
 #pragma unroll
             for (int j = 0; j < TP; ++j) acc2[i][j] = b4, acc2l[i][j] = (floatx4){0.f, 0.f, 0.f, 0.f};
         }
@@ -805,8 +637,8 @@ __global__ __launch_bounds__(512, MINW) void conv3x3_halo_kernel(const HaloArgs 
             for (int i = 0; i < 4; ++i)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v2[i * 4 + r] = wtk_split_value(acc2[i][j][r], acc2l[i][j][r]);
-            if (a.tail_f32)
-                store_run_h<16>(reinterpret_cast<float *>(a.tail_out) + pix * a.tail_ld + a.tail_coff + lg * 16, v2); // head logits stay fp32
+            if (a.tail_f32) // tail_store typed out: calling it here changes the code hipcc generates for this branch's two kernels
+                store_run<16>(reinterpret_cast<float *>(a.tail_out) + pix * a.tail_ld + a.tail_coff + lg * 16, v2); // head logits stay fp32
             else
                 wtk_split_store<16>(reinterpret_cast<_Float16 *>(a.tail_out) + pix * a.tail_ld + a.tail_coff, lg * 16, v2);
         }
@@ -837,7 +669,7 @@ __global__ __launch_bounds__(512, MINW) void conv3x3_halo_kernel(const HaloArgs 
                 for (int e = 0; e < 8; ++e) {
                     const int idx = c2 * 8 + e;
                     const float x = acc[idx >> 2][j][idx & 3];
-                    hv[e] = (_Float16)(a.act ? silu_h(x) : x);
+                    hv[e] = (_Float16)(a.act ? wtk_silu_scaled(x) : x);
                 }
                 const int c = 2 * lg + c2;
                 *reinterpret_cast<half8 *>(mine + p * 128 + ((c ^ (p & 7)) << 4)) = hv;
@@ -850,7 +682,7 @@ __global__ __launch_bounds__(512, MINW) void conv3x3_halo_kernel(const HaloArgs 
         floatx4 acc2[2][TPH];
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            const floatx4 b4 = (floatx4){a.tail_bias[lg * 8 + i * 4 + 0], a.tail_bias[lg * 8 + i * 4 + 1], a.tail_bias[lg * 8 + i * 4 + 2], a.tail_bias[lg * 8 + i * 4 + 3]};
+            const floatx4 b4 = tail_bias4(a, lg * 8 + i * 4);
 #pragma unroll
             for (int j = 0; j < TPH; ++j) acc2[i][j] = b4;
         }
@@ -865,7 +697,6 @@ __global__ __launch_bounds__(512, MINW) void conv3x3_halo_kernel(const HaloArgs 
                 for (int i = 0; i < 2; ++i) acc2[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf2[ks][i], pf, acc2[i][j], 0, 0, 0);
             }
         }
-        _Float16 *tout = reinterpret_cast<_Float16 *>(a.tail_out);
 #pragma unroll
         for (int j = 0; j < TPH; ++j) {
             const long long pix = lane_fetch((wave_c * TPH + j) * 16 + lr, pix_e);
@@ -875,12 +706,7 @@ __global__ __launch_bounds__(512, MINW) void conv3x3_halo_kernel(const HaloArgs 
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v2[i * 4 + r] = acc2[i][j][r];
-            if (lg * 8 < a.tail_cout) { // padded couts are never stored
-                if (a.tail_f32)
-                    store_run_h<8>(reinterpret_cast<float *>(a.tail_out) + pix * a.tail_ld + a.tail_coff + lg * 8, v2); // head logits stay fp32
-                else
-                    store_run_h<8>(tout + pix * a.tail_ld + a.tail_coff + lg * 8, v2);
-            }
+            if (lg * 8 < a.tail_cout) tail_store<false>(a, pix, lg, v2); // padded couts are never stored
         }
         return;
     } else if constexpr (TAIL) {
@@ -905,7 +731,7 @@ __global__ __launch_bounds__(512, MINW) void conv3x3_halo_kernel(const HaloArgs 
                     for (int e = 0; e < 8; ++e) {
                         const int idx = c2 * 8 + e;
                         const float x = acc[idx >> 2][j][idx & 3];
-                        hv[e] = (_Float16)(a.act ? silu_h(x) : x);
+                        hv[e] = (_Float16)(a.act ? wtk_silu_scaled(x) : x);
                     }
                     const int c = 2 * lg + c2;
                     *reinterpret_cast<half8 *>(tile + p * 128 + ((c ^ (p & 7)) << 4)) = hv;
@@ -915,8 +741,7 @@ __global__ __launch_bounds__(512, MINW) void conv3x3_halo_kernel(const HaloArgs 
             floatx4 acc2[4][TP];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const floatx4 b4 = (floatx4){a.tail_bias[lg * 16 + i * 4 + 0], a.tail_bias[lg * 16 + i * 4 + 1], a.tail_bias[lg * 16 + i * 4 + 2],
-                                             a.tail_bias[lg * 16 + i * 4 + 3]};
+                const floatx4 b4 = tail_bias4(a, lg * 16 + i * 4);
 #pragma unroll
                 for (int j = 0; j < TP; ++j) acc2[i][j] = b4;
             }
@@ -930,7 +755,6 @@ __global__ __launch_bounds__(512, MINW) void conv3x3_halo_kernel(const HaloArgs 
 #pragma unroll
                     for (int i = 0; i < 4; ++i) acc2[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf2[ks][i], pf, acc2[i][j], 0, 0, 0);
                 }
-            _Float16 *tout = reinterpret_cast<_Float16 *>(a.tail_out);
 #pragma unroll
             for (int j = 0; j < TP; ++j) {
                 const long long pix = lane_fetch(j * 16 + lr, pix_e);
@@ -940,10 +764,7 @@ __global__ __launch_bounds__(512, MINW) void conv3x3_halo_kernel(const HaloArgs 
                 for (int i = 0; i < 4; ++i)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) v2[i * 4 + r] = acc2[i][j][r];
-                if (a.tail_f32)
-                    store_run_h<16>(reinterpret_cast<float *>(a.tail_out) + pix * a.tail_ld + a.tail_coff + lg * 16, v2); // head logits stay fp32
-                else
-                    store_run_h<16>(tout + pix * a.tail_ld + a.tail_coff + lg * 16, v2);
+                tail_store<false>(a, pix, lg, v2);
             }
             return;
         }
@@ -993,7 +814,7 @@ __global__ __launch_bounds__(512, MINW) void conv3x3_halo_kernel(const HaloArgs 
                 if constexpr (SPLIT)
                     wtk_split_load<NV>(reinterpret_cast<const _Float16 *>(a.res) + pix * a.res_ld + a.res_coff, cb, rv);
                 else
-                    load_run_h<NV>(res + pix * a.res_ld + a.res_coff + cb, rv);
+                    load_run<NV>(res + pix * a.res_ld + a.res_coff + cb, rv);
 #pragma unroll
                 for (int i = 0; i < NV; ++i) v[i] += rv[i];
             }
@@ -1001,7 +822,7 @@ __global__ __launch_bounds__(512, MINW) void conv3x3_halo_kernel(const HaloArgs 
         if constexpr (SPLIT)
             wtk_split_store<NV>(reinterpret_cast<_Float16 *>(a.out) + pix * a.out_ld + a.out_coff, cb, v);
         else
-            store_run_h<NV>(out + pix * a.out_ld + a.out_coff + cb, v);
+            store_run<NV>(out + pix * a.out_ld + a.out_coff + cb, v);
         if (out2) { // 2x nearest upsample: pixel (n, 2y+dy, 2X+dx) of the [2H][2W] map = 4*pix - 2X + 2W*dy + dx
             const int W2 = a.W * 2;
 #pragma unroll
@@ -1012,7 +833,7 @@ __global__ __launch_bounds__(512, MINW) void conv3x3_halo_kernel(const HaloArgs 
                     if constexpr (SPLIT)
                         wtk_split_store<NV>(reinterpret_cast<_Float16 *>(a.out2) + pix2 * a.out2_ld + a.out2_coff, cb, v);
                     else
-                        store_run_h<NV>(out2 + pix2 * a.out2_ld + a.out2_coff + cb, v);
+                        store_run<NV>(out2 + pix2 * a.out2_ld + a.out2_coff + cb, v);
                 }
         }
     }
@@ -1033,7 +854,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_pkernel(const HaloArgs a)
                  "s"(a.Kpad), "s"(a.S), "s"(a.pitch), "s"(a.strips), "s"(a.d_strips.mul), "s"(a.d_strips.sh1), "s"(a.d_strips.sh2), "s"(a.d_pitch.mul),
                  "s"(a.d_pitch.sh1), "s"(a.d_pitch.sh2), "s"(a.d_nct.mul), "s"(a.d_nct.sh1), "s"(a.d_nct.sh2), "s"(a.d_h1.mul), "s"(a.d_h1.sh1), "s"(a.d_h1.sh2), "s"(a.grid),
                  "s"(a.blocks_per_strip)); // one batch of scalar loads (see conv3x3_halo_kernel)
-    constexpr int CE = ElemH<T>::CE;
+    constexpr int CE = Elem<T>::CE;
     constexpr int CCH = 8 * CE;
     constexpr int WAVES_C = 2, WAVES_P = 4;
     constexpr int WC = BN / WAVES_C;
@@ -1099,7 +920,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_pkernel(const HaloArgs a)
         const unsigned off = back ? tc.hoff[q > 0 ? q - 1 : 0] : tc.hoff[q];
         const bool ok = back ? ((tc.hvalid >> (q > 0 ? q - 1 : 0)) & 1u) : ((tc.hvalid >> q) & 1u);
         if constexpr (WTK_HALO_BUFFER_DMA) {
-            lds_dma16_buf(make_rsrc(tc.img), ok ? off : 0xffffffffu, (unsigned)(c * (CCH * (int)sizeof(T))), buf + piece * 1024);
+            lds_dma_buf(make_rsrc(tc.img), ok ? off : 0xffffffffu, (unsigned)(c * (CCH * (int)sizeof(T))), buf + piece * 1024);
         } else {
             const char *src = ok ? tc.img + (size_t)c * (CCH * sizeof(T)) + off : zero_page;
             lds_dma16<true>(src, buf + piece * 1024);
@@ -1118,7 +939,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_pkernel(const HaloArgs a)
             const rsrc_t rs = make_rsrc(wtile);
             const unsigned so = (unsigned)((tap * a.Cin + c * CCH) * (int)sizeof(T));
 #pragma unroll
-            for (int i = 0; i < WR; ++i) lds_dma16_buf(rs, wvoff[i], so, buf + (64 * i + 8 * wave) * 128);
+            for (int i = 0; i < WR; ++i) lds_dma_buf(rs, wvoff[i], so, buf + (64 * i + 8 * wave) * 128);
         } else {
             const char *ub = wtile + ((size_t)tap * a.Cin + (size_t)c * CCH) * sizeof(T);
 #pragma unroll
@@ -1151,7 +972,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_pkernel(const HaloArgs a)
 #pragma unroll
             for (int i = 0; i < TC; ++i)
 #pragma unroll
-                for (int j = 0; j < TP; ++j) mma_h(wf[i], pf[j], acc[i][j], (T *)nullptr);
+                for (int j = 0; j < TP; ++j) mma_frag(wf[i], pf[j], acc[i][j], (T *)nullptr);
         }
     };
 
@@ -1261,12 +1082,12 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_pkernel(const HaloArgs a)
                         for (int i = 0; i < NV; ++i) vv[i] += (float)rres[j][i >> 3][i & 7];
                     } else {
                         float rv[NV];
-                        load_run_h<NV>(res + pix * a.res_ld + a.res_coff + cb, rv);
+                        load_run<NV>(res + pix * a.res_ld + a.res_coff + cb, rv);
 #pragma unroll
                         for (int i = 0; i < NV; ++i) vv[i] += rv[i];
                     }
                 }
-                store_run_h<NV>(out + pix * a.out_ld + a.out_coff + cb, vv);
+                store_run<NV>(out + pix * a.out_ld + a.out_coff + cb, vv);
                 if (out2) {
                     const int W2 = a.W * 2;
 #pragma unroll
@@ -1274,7 +1095,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_pkernel(const HaloArgs a)
 #pragma unroll
                         for (int dx = 0; dx < 2; ++dx) {
                             const long long pix2 = 4 * pix - 2 * colj[j] + W2 * dy + dx;
-                            store_run_h<NV>(out2 + pix2 * a.out2_ld + a.out2_coff + cb, vv);
+                            store_run<NV>(out2 + pix2 * a.out2_ld + a.out2_coff + cb, vv);
                         }
                 }
             }
@@ -1287,624 +1108,10 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_pkernel(const HaloArgs a)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the final tile's duplicate requests must not outlive the block's LDS
 }
 
-
-// ---------------------------------------------------------------------------------------------------------------
-// Weight-stationary window kernel for the 64 -> 64 channel 3x3 layers (fp16: the c = 64 bottlenecks on the 80x80 maps).
-//
-// All nine tap slabs of such a layer are 9 x 64 x 64 x 2 B = 72 KiB: they fit LDS next to two window buffers, so they are
-// staged ONCE per persistent block and the main loop has no weight LDS-DMA and no per-tap barrier at all (the one change the
-// ablation of conv3x3_halo_kernel showed to shorten a tap, profiles/r01_notes.md).  The block is two GROUPS of four waves (one
-// wave of each group per SIMD).  A group owns a window buffer and walks its own tiles of 256 flat output pixels; per tile it
-//   P: multiplies — 18 (tap, k-half) steps of 16 MFMAs per wave (64 px x 64 cout wave tile, 0.5 ds_read_b128 per MFMA), fragment
-//      reads of step s+1 issued before the MFMAs of step s, no barrier, no vector-memory instruction in the stream;
-//   Q: requests the next tile's window (LDS-DMA, buffer form), runs the SiLU / residual epilogue of the tile just finished while
-//      those requests land, waits for them.
-// The groups alternate: while one multiplies the other is in Q, one s_barrier per interval (= per 288 MFMAs of a wave instead of
-// per 32).  The matrix pipe of a SIMD is fed by one wave at a time and never waits for an epilogue or a window.
-// Geometry, fragment layouts, K order (tap-major, two 32-deep halves), bias-initialised accumulators and SiLU are those of
-// conv3x3_halo_kernel<_Float16, 64, ...>: results are bit-identical (WTK_NO_WS64=1 switches back; tests compare).
-// LDS: 73 728 (weights) + 2 x 44 032 (344-row windows: strips of <= 41 columns) = 161 792 B of 163 840.
-// ---------------------------------------------------------------------------------------------------------------
-constexpr int kWsRows = 344;                 // window rows per group buffer (43 pieces of 8 rows)
-constexpr int kWsPiecesPerWave = 11;         // 43 pieces over the 4 waves of a group
-
-// NWV (round 3): pixel tiles (of the four of a wave's 64 x 64 tile) whose epilogue is DEFERRED — their sums move to a second accumulator set
-// when the group leaves its multiply phase and the SiLU / residual / store of those values is woven, one floatx4 at a time, between the
-// MFMAs of the group's NEXT multiply phase (sched_group_barrier pins the interleave; stores go out as raw buffer stores whose junk lanes
-// carry an out-of-range offset, so the phase has no branch in it).  Stamps of the round-2 kernel had Q (stage + epilogue, ~8 400 cycles)
-// as the long pole of every interval against ~5 100 for the multiply: the partner's matrix time was wasted for a third of each interval,
-// and with two waves per SIMD no amount of overlap BETWEEN waves gets under (P + Q) / 2 — only work moved INTO the multiplying wave's
-// own instruction stream does.  NWV = 0 is the round-2 kernel (WTK_WS64_WEAVE=0), results are bit-identical for every NWV.
-template <int NWV>
-__global__ __launch_bounds__(512) void conv3x3_ws64_kernel(const HaloArgs a) {
-    static_assert(NWV >= 0 && NWV <= 4, "woven pixel tiles");
-    asm volatile("" ::"s"(a.in), "s"(a.w), "s"(a.bias), "s"(a.in_ld), "s"(a.in_coff), "s"(a.N), "s"(a.H), "s"(a.W), "s"(a.Kpad), "s"(a.S), "s"(a.pitch),
-                 "s"(a.strips), "s"(a.d_strips.mul), "s"(a.d_strips.sh1), "s"(a.d_strips.sh2), "s"(a.d_pitch.mul), "s"(a.d_pitch.sh1), "s"(a.d_pitch.sh2),
-                 "s"(a.d_h1.mul), "s"(a.d_h1.sh1), "s"(a.d_h1.sh2), "s"(a.grid), "s"(a.blocks_per_strip));
-    using T = _Float16;
-    constexpr int TP = 4, TC = 4, NV = 16, WP = 64;
-    __shared__ __attribute__((aligned(16))) char wts[9 * 8192];
-    __shared__ __attribute__((aligned(16))) char win0[kWsRows * 128];
-    __shared__ __attribute__((aligned(16))) char win1[kWsRows * 128];
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int grp = wave >> 2, gw = wave & 3; // group, wave inside the group (= pixel quarter of the group's tile)
-    const int lr = lane & 15, lg = lane >> 4;
-    const int pitch = a.pitch;
-    const int halo_rows = 256 + 2 * pitch + 2;
-    const int total = a.strips * a.blocks_per_strip; // one cout tile
-    const int NG = 2 * a.grid;                      // groups in the launch
-    const int g0 = 2 * (int)blockIdx.x;             // this block's first group id
-    // tiles of a group: v = g, g + NG, ... < total
-    const int nA = g0 < total ? (total - g0 + NG - 1) / NG : 0;
-    const int nB = g0 + 1 < total ? (total - g0 - 1 + NG - 1) / NG : 0;
-    const int n_mine = grp ? nB : nA;
-    const int intervals = 2 * nA > 2 * nB + 1 ? 2 * nA : 2 * nB + 1;
-    char *win = grp ? win1 : win0;
-
-    // ---- per-tile geometry (flat origin, strip, image base, window piece offsets)
-    struct Tile {
-        int o0, xs;
-        const char *img;
-        unsigned hoff[kWsPiecesPerWave];
-        unsigned hvalid;
-    };
-    auto setup_tile = [&](int k, Tile &tc) __attribute__((always_inline)) {
-        const int v = g0 + grp + k * NG;
-        const int xcd = v & 7, q8 = total >> 3, r8 = total & 7; // XCD-aware bijective remap (as conv3x3_halo_kernel)
-        const int L = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (v >> 3);
-        const int rb = (int)fdiv((unsigned)L, a.d_strips);
-        const int strip = L - rb * a.strips;
-        tc.o0 = rb * 256;
-        tc.xs = strip * a.S;
-        const int n_base = (int)fdiv(fdiv((unsigned)tc.o0, a.d_pitch), a.d_h1);
-        tc.img = reinterpret_cast<const char *>(reinterpret_cast<const T *>(a.in) + (long long)n_base * a.H * a.W * a.in_ld + a.in_coff);
-        // window rows of this wave's pieces gw, gw + 4, ...: lane L evaluates row L & 7 of piece slot L >> 3 in two rounds (slots 0..7, 8..10)
-        unsigned row_e[2];
-#pragma unroll
-        for (int rr = 0; rr < 2; ++rr) {
-            const int q = rr * 8 + (lane >> 3);
-            const int hr = (gw + 4 * q) * 8 + (lane & 7);
-            int pn = 0, iy = 0, ix = 0;
-            const bool ok = q < kWsPiecesPerWave && hr < halo_rows && halo_in_coords(a, tc.o0 + hr, tc.xs, pn, iy, ix);
-            // 32-bit offsets relative to the window's first image: pixel index < 2^24, bytes per pixel < 2^24 -> full-rate 24-bit multiplies
-            const unsigned pixel = __umul24(__umul24((unsigned)(pn - n_base), (unsigned)a.H) + (unsigned)iy, (unsigned)a.W) + (unsigned)ix;
-            row_e[rr] = ok ? __umul24(pixel, (unsigned)(a.in_ld * (int)sizeof(T))) : 0xffffffffu;
-        }
-        const unsigned lc_term = (unsigned)((((lane & 7) ^ ((lane >> 3) & 7)) * 8) * (int)sizeof(T));
-        tc.hvalid = 0;
-#pragma unroll
-        for (int q = 0; q < kWsPiecesPerWave; ++q) {
-            const unsigned v2 = (unsigned)__builtin_amdgcn_ds_bpermute(((q & 7) * 8 + (lane >> 3)) * 4, (int)row_e[q >> 3]);
-            const bool ok = v2 != 0xffffffffu;
-            tc.hoff[q] = ok ? v2 + lc_term : 0u;
-            tc.hvalid |= ok ? (1u << q) : 0u;
-        }
-    };
-    auto stage_window = [&](const Tile &tc) __attribute__((always_inline)) {
-        const rsrc_t rs = make_rsrc(tc.img);
-#pragma unroll
-        for (int q = 0; q < kWsPiecesPerWave; ++q) {
-            const int piece = gw + 4 * q;
-            if (piece * 8 >= kWsRows) continue; // static after unrolling for q < 10; q == 10: waves 0..2 only (wave-uniform)
-            lds_dma16_buf(rs, ((tc.hvalid >> q) & 1u) ? tc.hoff[q] : 0xffffffffu, 0u, win + piece * 1024);
-        }
-    };
-
-    // ---- prologue: all nine weight slabs (every thread one 16-byte piece per tap) + group 0's first window
-    {
-        const int row = tid >> 3, wp = tid & 7;
-        const int key = ((row >> 1) & 1) | (((row / NV) & 3) << 1);
-        const unsigned wvoff = (unsigned)(((long long)row * a.Kpad + (wp ^ key) * 8) * (long long)sizeof(T));
-        const rsrc_t rs = make_rsrc(a.w);
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) lds_dma16_buf(rs, wvoff, (unsigned)(tap * 64 * (int)sizeof(T)), wts + tap * 8192 + (8 * wave) * 128);
-    }
-    Tile cur;
-    cur.o0 = cur.xs = 0, cur.img = nullptr, cur.hvalid = 0;
-    if (grp == 0 && n_mine > 0) {
-        setup_tile(0, cur);
-        stage_window(cur);
-    }
-    // accumulators start at the bias
-    floatx4 acc[TC][TP];
-    auto arm_acc = [&]() __attribute__((always_inline)) { // the bias is re-read per tile (64 B per lane, cache resident): 16 registers that need not live through the multiply phase
-#pragma unroll
-        for (int i = 0; i < TC; ++i) {
-            const float4 b = *reinterpret_cast<const float4 *>(a.bias + lg * NV + i * 4);
-#pragma unroll
-            for (int j = 0; j < TP; ++j) acc[i][j] = (floatx4){b.x, b.y, b.z, b.w};
-        }
-    };
-    arm_acc();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-
-    // fragment addressing (conv3x3_halo_kernel, BN = 64)
-    const int wrow_l = (lr >> 2) * NV + (lr & 3);
-    const int wkey_l = ((wrow_l >> 1) & 1) | (((wrow_l / NV) & 3) << 1);
-    const unsigned wfrag0 = wrow_l * 128 + ((lg ^ wkey_l) << 4);
-    const int prow0 = gw * WP + lr;
-    T *out = reinterpret_cast<T *>(a.out);
-    const T *res = reinterpret_cast<const T *>(a.res);
-    const int cb = lg * NV;
-
-    auto load_frags = [&](int step, uint4 (&pf)[TP], uint4 (&wf)[TC]) __attribute__((always_inline)) { // step static after unrolling
-        const int tap = step >> 1, kh = step & 1;
-        const int base = prow0 + (tap / 3) * pitch + (tap % 3);
-        unsigned pa = base * 128 + ((lg ^ (base & 7)) << 4);
-        unsigned wa = tap * 8192 + wfrag0;
-        if (kh) pa ^= 64u, wa ^= 64u;
-#pragma unroll
-        for (int j = 0; j < TP; ++j) pf[j] = *reinterpret_cast<const uint4 *>(win + pa + j * 2048);
-#pragma unroll
-        for (int i = 0; i < TC; ++i) wf[i] = *reinterpret_cast<const uint4 *>(wts + wa + i * 512);
-    };
-    // ---- deferred (woven) part of the previous tile's epilogue: sums, residual values and store offsets of its last NWV pixel tiles
-    constexpr int NB = NWV > 0 ? NWV : 1;
-    constexpr int kPieces = 4 * NWV; // one floatx4 (4 couts of one pixel) per piece
-    floatx4 accB[TC][NB];
-    half8 rresB[NB][2];
-    unsigned ooffB[NB]; // byte offset of the lane's 16 couts of that pixel in `out`; kJunkOff for junk pixels: beyond the descriptor's range, also after the
-                        // + 16 of a pixel's second store (0xffffffff would wrap to 15 and land inside the tensor), so the hardware drops the store
-    constexpr unsigned kJunkOff = 0xf0000000u, kOutRange = 0xe0000000u;
-#pragma unroll
-    for (int jw = 0; jw < NB; ++jw) {
-        ooffB[jw] = kJunkOff;
-#pragma unroll
-        for (int i = 0; i < TC; ++i) accB[i][jw] = (floatx4){0.f, 0.f, 0.f, 0.f};
-        rresB[jw][0] = rresB[jw][1] = (half8){0, 0, 0, 0, 0, 0, 0, 0};
-    }
-    const __amdgpu_buffer_rsrc_t out_rs = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char *>(a.out) + (long long)a.out_coff * (long long)sizeof(T), 0,
-                                                                            (int)kOutRange, 0x00020000);
-    // step of the multiply phase that hosts piece p: the pieces are spread evenly over steps 0 .. 15
-    auto compute_tile = [&]() __attribute__((always_inline)) {
-        constexpr bool WV = NWV > 0; // the woven pieces run in EVERY multiply phase: a group's first tile has nothing pending and weaves zeros whose stores are
-                                     // dropped (out-of-range offsets) — one instruction stream, no branch, no second copy of the 288-MFMA body
-        // Two fragment register sets: the eight ds_read_b128 of step s+1 are issued BETWEEN the MFMAs of step s (one read per two
-        // MFMAs), so a wave that has the SIMD's matrix pipe to itself never waits for LDS.  hipcc's scheduler otherwise sinks every
-        // read to just before its first use (one register set, the LDS latency exposed 18 times per tile): the sched_barrier /
-        // sched_group_barrier calls pin the order.
-        uint4 pf[2][TP], wf[2][TC];
-        uint2 packed[2]; // a pixel's 8 finished couts (two pieces) on their way to one 16-byte store
-        if (a.slabs & 8) __builtin_amdgcn_s_setprio(3); // the multiplying wave wins the SIMD's issue arbitration; its partner (stage + epilogue) takes the gaps
-        load_frags(0, pf[0], wf[0]);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int s = 0; s < 18; ++s) {
-            if (s + 1 < 18) load_frags(s + 1, pf[(s + 1) & 1], wf[(s + 1) & 1]);
-#pragma unroll
-            for (int i = 0; i < TC; ++i)
-#pragma unroll
-                for (int j = 0; j < TP; ++j) mma_h(wf[s & 1][i], pf[s & 1][j], acc[i][j], (T *)nullptr);
-            // piece p = (pixel tile jw, cout quad i) of the deferred tile rides on this step when p * 16 / kPieces == s
-            bool hosts = false;
-            if constexpr (WV) {
-#pragma unroll
-                for (int p = 0; p < kPieces; ++p) {
-                    if (p * 16 / kPieces != s) continue;
-                    hosts = true;
-                    const int jw = p >> 2, i = p & 3;
-                    float v[4];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = accB[i][jw][r];
-                    wtk_silu_scaled_run<4, true>(v); // scalar add / multiply: a packed fp32 instruction costs 27-32 issue cycles beside MFMAs
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = wtk_pin_f32(v[r] + (float)rresB[jw][i >> 1][(i & 1) * 4 + r]); // zeros when the layer has no residual
-                    typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-                    const half4 h4 = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
-                    packed[i & 1] = __builtin_bit_cast(uint2, h4);
-                    if (i & 1) {
-                        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-                        const u32x4 d = {packed[0].x, packed[0].y, packed[1].x, packed[1].y};
-                        __builtin_amdgcn_raw_buffer_store_b128(d, out_rs, (int)(ooffB[jw] + (unsigned)((i >> 1) * 16)), 0, 0);
-                    }
-                }
-            }
-            if (s + 1 < 18) {
-#pragma unroll
-                for (int g = 0; g < 8; ++g) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 2, 0); // 2 MFMA
-                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); // 1 DS read
-                    if (WV && hosts) __builtin_amdgcn_sched_group_barrier(0x002, 4, 0); // 4 VALU of the woven piece
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        if (a.slabs & 8) __builtin_amdgcn_s_setprio(0);
-    };
-    // `defer_tail`: the last NWV pixel tiles are not finished here — their sums, residual values and store offsets go to the deferred set and
-    // ride on the group's next multiply phase (only when the group HAS a next tile; the last tile of a group is finished whole)
-    auto epilogue = [&](const Tile &tc, bool defer_tail) __attribute__((always_inline)) {
-        int pix_e, col_e;
-        halo_out_pixel(a, tc.o0 + gw * WP, tc.xs, lane, pix_e, col_e);
-        long long pixj[TP];
-#pragma unroll
-        for (int j = 0; j < TP; ++j) pixj[j] = lane_fetch(j * 16 + lr, pix_e);
-        // the residual of ALL four pixel tiles is requested before any arithmetic (junk pixels read pixel 0): one exposed memory
-        // latency per tile instead of four — this phase is the long pole of an interval (stamped), every cycle it waits counts
-        half8 rraw[TP][2];
-        if (res) {
-#pragma unroll
-            for (int j = 0; j < TP; ++j) {
-                const T *rp = res + (pixj[j] < 0 ? 0 : pixj[j]) * a.res_ld + a.res_coff + cb;
-                rraw[j][0] = *reinterpret_cast<const half8 *>(rp);
-                rraw[j][1] = *reinterpret_cast<const half8 *>(rp + 8);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < TP; ++j) {
-            if (NWV > 0 && j >= TP - NWV && defer_tail) { // wave-uniform
-                const int jw = j - (TP - NWV);
-#pragma unroll
-                for (int i = 0; i < TC; ++i) accB[i][jw] = acc[i][j];
-                if (res) rresB[jw][0] = rraw[j][0], rresB[jw][1] = rraw[j][1]; // (no residual: they stay the zeros they were initialised to)
-                ooffB[jw] = pixj[j] >= 0 ? (unsigned)((pixj[j] * a.out_ld + cb) * (long long)sizeof(T)) : kJunkOff;
-                continue;
-            }
-            float v[NV];
-#pragma unroll
-            for (int i = 0; i < TC; ++i)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[i * 4 + r] = acc[i][j][r];
-            if (a.act) {
-                wtk_silu_scaled_run<NV, (WTK_SILU_SCALAR_MASK & 1) != 0>(v);
-            }
-            if (res) {
-#pragma unroll
-                for (int i = 0; i < NV; ++i) {
-                    v[i] += (float)rraw[j][i >> 3][i & 7];
-                    if constexpr ((WTK_SILU_SCALAR_MASK & 1) != 0) v[i] = wtk_pin_f32(v[i]);
-                }
-            }
-            if (pixj[j] >= 0) store_run_h<NV>(out + pixj[j] * a.out_ld + a.out_coff + cb, v);
-        }
-    };
-
-    // ---- interval schedule: group g multiplies in intervals i with (i & 1) == g, the other group is in Q; one barrier per interval
-    Tile done; // tile whose accumulators are waiting for their epilogue
-    done = cur;
-#ifdef WTK_WS64_STAMPS
-    const bool stamp_on = a.dbg_stamps != nullptr && blockIdx.x < 2 && lane == 0;
-    unsigned long long *stamp = a.dbg_stamps + ((long long)blockIdx.x * 8 + wave) * 16 * 4;
-    if (stamp_on) stamp[16 * 4 - 1] = __builtin_amdgcn_s_memtime(); // slot 15.3: loop entry
-#endif
-    for (int i = 0; i < intervals; ++i) {
-#ifdef WTK_WS64_STAMPS
-        if (stamp_on && i < 15) stamp[i * 4 + 0] = __builtin_amdgcn_s_memtime();
-#endif
-        if ((i & 1) == grp) {
-            const int k = (i - grp) >> 1;
-            if (k < n_mine) {
-                compute_tile();
-                done = cur;
-            }
-        } else {
-            const int kprev = (i - 1 - grp) >> 1, knext = (i + 1 - grp) >> 1;
-            const bool has_prev = i - 1 - grp >= 0 && kprev < n_mine, has_next = knext < n_mine;
-            if (has_next) {
-                setup_tile(knext, cur);
-                stage_window(cur); // the group finished reading its window before the last barrier
-            }
-            if (has_prev) {
-                epilogue(done, has_next);
-                arm_acc();
-            }
-#ifdef WTK_WS64_STAMPS
-            if (stamp_on && i < 15) stamp[i * 4 + 1] = __builtin_amdgcn_s_memtime();
-#endif
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#ifdef WTK_WS64_STAMPS
-        if (stamp_on && i < 15) stamp[i * 4 + 2] = __builtin_amdgcn_s_memtime();
-#endif
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-#ifdef WTK_WS64_STAMPS
-        if (stamp_on && i < 15) stamp[i * 4 + 3] = __builtin_amdgcn_s_memtime();
-#endif
-    }
-}
-
-hipError_t launch_ws64(HaloArgs a, int num_cus, hipStream_t stream) {
-    const long long tiles = (long long)a.strips * a.blocks_per_strip;
-    if (tiles <= 0 || tiles > 0x3fffffffLL || num_cus < 8) return hipErrorInvalidValue;
-    if (256 + 2 * a.pitch + 2 > kWsRows) return hipErrorInvalidValue;
-    a.d_nct = make_fastdiv(1u);
-    a.d_bps = make_fastdiv((unsigned)a.blocks_per_strip);
-    a.d_strips = make_fastdiv((unsigned)a.strips);
-    a.d_pitch = make_fastdiv((unsigned)a.pitch);
-    a.d_h1 = make_fastdiv((unsigned)(a.H + 1));
-    const long long cap = num_cus / 8 * 8; // one block per CU (158 KiB of LDS)
-    const long long want = (tiles + 1) / 2;
-    const unsigned grid = (unsigned)(want < cap ? want : cap);
-    a.grid = (int)grid;
-    // (the woven-epilogue schedules of round 3 — NWV = 1 .. 3 pixel tiles of a wave's four riding on the next multiply phase — measured no gain and are no
-    // longer instantiated: NWV = 0 is round 2's schedule)
-    hipLaunchKernelGGL(conv3x3_ws64_kernel<0>, dim3(grid), dim3(512), 0, stream, a);
-    return hipGetLastError();
-}
-
-
-// ---------------------------------------------------------------------------------------------------------------
-// 3x3 / STRIDE-2 convolution with an LDS-resident window (fp16, 128-cout tile): model.5 / 7 / 16 / 19 of YOLOv8s.
-//
-// The implicit-GEMM kernel re-stages the pixel operand for each of the nine taps (one LDS-DMA request per 4 MFMAs and wave).
-// Here the input is read as its four PARITY PLANES: plane (py, px) holds input pixels (2Y + py, 2X + px), i.e. one pixel per
-// output pixel, and in plane coordinates the stride-2 conv is a stride-1 conv whose taps are 1-D shifts of the flat window —
-// exactly the geometry of conv3x3_halo_kernel on the OUTPUT map (stacked images, one shared zero row, pitch = Wo + 1).
-// Output (y, x) needs input rows 2y-1, 2y, 2y+1 = plane rows (y-1, py=1), (y, py=0), (y, py=1), columns alike, so
-//   plane (1,1) serves 4 taps (kh, kw in {0, 2}), planes (0,1) and (1,0) two each, plane (0,0) one (kh = kw = 1): 9 in all.
-// A 64-channel chunk of one plane is staged ONCE (its per-lane request addresses gather the plane out of the NHWC tensor:
-// the plane's offset is a wave-uniform constant on top of plane (0,0)'s per-row offsets) and multiplied by 1 / 2 / 2 / 4 taps:
-// 2.25 taps per staged window instead of 1.  Weight slabs: the three-slab ring of conv3x3_halo_kernel (slab of step g+2
-// requested in step g, counted vmcnt).  Window pieces are requested ahead of the slab pieces of a step, so "all but the slab
-// requests of this step" (vmcnt(WR)) at the last tap of a plane means the next plane's window has landed.
-// K is walked chunk-major / plane-major (the implicit-GEMM kernel: tap-major), so results equal that kernel's up to fp32
-// summation order, not bit for bit (WTK_NO_S2WIN=1 switches back; tests compare within one fp16 ulp of the activations' scale).
-// ---------------------------------------------------------------------------------------------------------------
-constexpr int kS2Rows = 344; // window rows per buffer (43 pieces): BMT + (Wo + 1) + 2 <= 344  ->  Wo <= 85 at BMT = 256
-
-// SPLIT: split-fp16 operands (see conv3x3_halo_kernel): pseudo-channel a.Cin / in_ld / out_ld, three MFMAs per tile pair and K step.
-template <int BMT, bool SPLIT = false>
-__global__ __launch_bounds__(512, 2) void conv3x3_s2_kernel(const HaloArgs a) {
-    asm volatile("" ::"s"(a.in), "s"(a.w), "s"(a.bias), "s"(a.in_ld), "s"(a.in_coff), "s"(a.N), "s"(a.H), "s"(a.W), "s"(a.Cin), "s"(a.CoutPad), "s"(a.Kpad),
-                 "s"(a.S), "s"(a.pitch), "s"(a.d_pitch.mul), "s"(a.d_pitch.sh1), "s"(a.d_pitch.sh2), "s"(a.d_nct.mul), "s"(a.d_nct.sh1), "s"(a.d_nct.sh2),
-                 "s"(a.d_h1.mul), "s"(a.d_h1.sh1), "s"(a.d_h1.sh2), "s"(a.grid));
-    using T = _Float16;
-    constexpr int BN = 128, WAVES_C = 2, WAVES_P = 4, WC = 64, WP = BMT / WAVES_P, TP = WP / 16, TC = 4, NV = 16, WR = 2;
-    constexpr int kPieces = kS2Rows / 8;              // 43
-    constexpr int KW = (kPieces + 7) / 8;             // window pieces per wave (6)
-    __shared__ __attribute__((aligned(16))) char win0[kS2Rows * 128];
-    __shared__ __attribute__((aligned(16))) char win1[kS2Rows * 128];
-    __shared__ __attribute__((aligned(16))) char wbuf0[BN * 128];
-    __shared__ __attribute__((aligned(16))) char wbuf1[BN * 128];
-    __shared__ __attribute__((aligned(16))) char wbuf2[BN * 128];
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wave_p = wave / WAVES_C, wave_c = wave % WAVES_C;
-    const int lr = lane & 15, lg = lane >> 4;
-    const int nct = a.CoutPad / BN;
-    int nwg = a.grid;
-    if (a.n_dyn) { // dynamic batch (see conv3x3_halo_kernel)
-        const int lim = min(max(*a.n_dyn, 0), a.N) * (a.H + 1) * a.pitch;
-        const int live = ((lim + BMT - 1) / BMT) * nct;
-        if ((int)blockIdx.x >= live) return;
-        nwg = min(nwg, live);
-    }
-    int L;
-    {
-        const int bid = blockIdx.x;
-        const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-        L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
-    const unsigned t = fdiv((unsigned)L, a.d_nct);
-    const int n0 = (L - (int)t * nct) * BN;
-    const int o0 = (int)t * BMT; // one strip: row blocks only
-    const int pitch = a.pitch;   // Wo + 1
-    const int halo_rows = BMT + pitch + 2;
-    const int Hin = 2 * a.H, Win = 2 * a.W; // a.H, a.W: OUTPUT map (the geometry lives there)
-    const int n_base = (int)fdiv(fdiv((unsigned)o0, a.d_pitch), a.d_h1);
-    const char *img = reinterpret_cast<const char *>(reinterpret_cast<const T *>(a.in) + (long long)n_base * Hin * Win * a.in_ld + a.in_coff);
-    const T *wgt = reinterpret_cast<const T *>(a.w);
-
-    // ---- window rows of this wave's pieces (wave, wave + 8, ...): byte offset of plane (0,0)'s pixel (2Y, 2X), evaluated once
-    unsigned hoff[KW];
-    unsigned hvalid = 0;
-    {
-        const int hr_e = (wave + 8 * (lane >> 3)) * 8 + (lane & 7);
-        int pn = 0, Y = 0, X = 0;
-        const bool ok_e = (lane >> 3) < KW && hr_e < halo_rows && halo_in_coords(a, o0 + hr_e, 0, pn, Y, X);
-        const unsigned pixel = __umul24(__umul24((unsigned)(pn - n_base), (unsigned)Hin) + (unsigned)(2 * Y), (unsigned)Win) + (unsigned)(2 * X);
-        const unsigned row_e = ok_e ? __umul24(pixel, (unsigned)(a.in_ld * (int)sizeof(T))) : 0xffffffffu;
-        const unsigned lc_term = (unsigned)((((lane & 7) ^ ((lane >> 3) & 7)) * 8) * (int)sizeof(T));
-#pragma unroll
-        for (int q = 0; q < KW; ++q) {
-            const unsigned v = (unsigned)__builtin_amdgcn_ds_bpermute((q * 8 + (lane >> 3)) * 4, (int)row_e);
-            const bool ok = v != 0xffffffffu;
-            hoff[q] = ok ? v + lc_term : 0u;
-            hvalid |= ok ? (1u << q) : 0u;
-        }
-    }
-    const rsrc_t irs = make_rsrc(img);
-    // window piece q of this wave for plane (py, px), channel chunk c (never skipped: constant request count per step)
-    auto issue_piece = [&](char *buf, int q, int py, int px, int c) __attribute__((always_inline)) { // q static after unrolling
-        const bool back = q > 0 && wave + 8 * q >= kPieces; // wave-uniform: the last slot of the highest waves re-requests their previous piece
-        const int piece = __builtin_amdgcn_readfirstlane(back ? wave + 8 * (q - 1) : wave + 8 * q);
-        const unsigned off = back ? hoff[q > 0 ? q - 1 : 0] : hoff[q];
-        const bool ok = back ? ((hvalid >> (q > 0 ? q - 1 : 0)) & 1u) : ((hvalid >> q) & 1u);
-        const unsigned so = (unsigned)__builtin_amdgcn_readfirstlane((((py * Win + px) * a.in_ld) + c * 64) * (int)sizeof(T)); // wave-uniform
-        lds_dma16_buf(irs, ok ? off : 0xffffffffu, so, buf + piece * 1024);
-    };
-    const int wrow0 = tid >> 3, wp = tid & 7;
-    unsigned wvoff[WR];
-#pragma unroll
-    for (int i = 0; i < WR; ++i) {
-        const int row = wrow0 + 64 * i;
-        const int key = ((row >> 1) & 1) | (((row / NV) & 3) << 1);
-        wvoff[i] = (unsigned)(((long long)row * a.Kpad + (wp ^ key) * 8) * (long long)sizeof(T));
-    }
-    const rsrc_t wrs = make_rsrc(wgt + (long long)n0 * a.Kpad);
-    auto issue_weights = [&](char *buf, int tap, int c) __attribute__((always_inline)) {
-        const unsigned so = (unsigned)((tap * a.Cin + c * 64) * (int)sizeof(T));
-#pragma unroll
-        for (int i = 0; i < WR; ++i) lds_dma16_buf(wrs, wvoff[i], so, buf + (64 * i + 8 * wave) * 128);
-    };
-
-    const int cb = n0 + wave_c * WC + lg * NV;
-    floatx4 acc[TC][TP];
-    floatx4 acc1[SPLIT ? TC : 1][SPLIT ? TP : 1];
-#pragma unroll
-    for (int i = 0; i < TC; ++i) {
-        const floatx4 b4 = (floatx4){a.bias[cb + i * 4 + 0], a.bias[cb + i * 4 + 1], a.bias[cb + i * 4 + 2], a.bias[cb + i * 4 + 3]};
-#pragma unroll
-        for (int j = 0; j < TP; ++j) {
-            acc[i][j] = b4;
-            if constexpr (SPLIT) acc1[i][j] = (floatx4){0.f, 0.f, 0.f, 0.f};
-        }
-    }
-    const int wrow_l = wave_c * WC + (lr >> 2) * NV + (lr & 3);
-    const int wkey_l = ((wrow_l >> 1) & 1) | (((wrow_l / NV) & 3) << 1);
-    const unsigned wfrag0 = wrow_l * 128 + ((lg ^ wkey_l) << 4);
-    const int prow0 = wave_p * WP + lr;
-    auto compute_tap = [&](const char *win, const char *wb, int tapoff) __attribute__((always_inline)) {
-        const int base = prow0 + tapoff;
-        const unsigned pfrag0 = base * 128 + ((lg ^ (base & 7)) << 4);
-        if constexpr (SPLIT) {
-            uint4 ph[TP], wh[TC], wl[TC], pl[TP];
-#pragma unroll
-            for (int j = 0; j < TP; ++j) ph[j] = *reinterpret_cast<const uint4 *>(win + pfrag0 + j * 2048);
-#pragma unroll
-            for (int i = 0; i < TC; ++i) wh[i] = *reinterpret_cast<const uint4 *>(wb + wfrag0 + i * 512);
-#pragma unroll
-            for (int i = 0; i < TC; ++i) wl[i] = *reinterpret_cast<const uint4 *>(wb + (wfrag0 ^ 64u) + i * 512);
-#pragma unroll
-            for (int j = 0; j < TP; ++j) pl[j] = *reinterpret_cast<const uint4 *>(win + (pfrag0 ^ 64u) + j * 2048);
-#pragma unroll
-            for (int i = 0; i < TC; ++i)
-#pragma unroll
-                for (int j = 0; j < TP; ++j) {
-                    mma_h(wh[i], ph[j], acc[i][j], (T *)nullptr);
-                    mma_h(wl[i], ph[j], acc1[i][j], (T *)nullptr);
-                }
-#pragma unroll
-            for (int i = 0; i < TC; ++i)
-#pragma unroll
-                for (int j = 0; j < TP; ++j) mma_h(wh[i], pl[j], acc1[i][j], (T *)nullptr);
-            return;
-        }
-#pragma unroll
-        for (int kh2 = 0; kh2 < 2; ++kh2) {
-            const unsigned pa = kh2 ? (pfrag0 ^ 64u) : pfrag0;
-            const unsigned wa = kh2 ? (wfrag0 ^ 64u) : wfrag0;
-            uint4 pf[TP], wf[TC];
-#pragma unroll
-            for (int j = 0; j < TP; ++j) pf[j] = *reinterpret_cast<const uint4 *>(win + pa + j * 2048);
-#pragma unroll
-            for (int i = 0; i < TC; ++i) wf[i] = *reinterpret_cast<const uint4 *>(wb + wa + i * 512);
-#pragma unroll
-            for (int i = 0; i < TC; ++i)
-#pragma unroll
-                for (int j = 0; j < TP; ++j) mma_h(wf[i], pf[j], acc[i][j], (T *)nullptr);
-        }
-    };
-
-    // ---- the nine steps of a channel chunk.  Plane order (1,1) [4 taps], (0,1) [2], (1,0) [2], (0,0) [1]; window buffers alternate per
-    // plane (even number of planes per chunk: the parity is static).  kStep*: static tables, indexed by the unrolled step.
-    //                         step:   0  1  2  3   4  5   6  7   8
-    constexpr int kStepTap[9] =      { 0, 2, 6, 8,  3, 5,  1, 7,  4};              // kh * 3 + kw of the packed weights
-    constexpr int kStepDY[9] =       {-1,-1, 0, 0,  0, 0, -1, 0,  0};
-    constexpr int kStepDX[9] =       {-1, 0,-1, 0, -1, 0,  0, 0,  0};
-    constexpr int kStepBuf[9] =      { 0, 0, 0, 0,  1, 1,  0, 0,  1};              // window buffer of the step's plane
-    constexpr int kStepReq[9] =      { 2, 2, 2, 0,  KW,0,  KW,0,  KW};             // next plane's window pieces requested in this step
-    constexpr int kStepReqFrom[9] =  { 0, 2, 4, 0,  0, 0,  0, 0,  0};              // first piece slot of that request
-    constexpr int kNextPy[9] =       { 0, 0, 0, 0,  1, 1,  0, 0,  1};              // plane whose window the step requests:
-    constexpr int kNextPx[9] =       { 1, 1, 1, 1,  0, 0,  0, 0,  1};              //   (0,1) (0,1) (0,1) - (1,0) - (0,0) - next chunk's (1,1)
-    static_assert(KW == 6, "request schedule written for six window pieces per wave");
-    const int nchunks = a.Cin / 64;
-
-    // ---- prologue: window of chunk 0 / plane (1,1) + slabs of steps 0 and 1
-#pragma unroll
-    for (int q = 0; q < KW; ++q) issue_piece(win0, q, 1, 1, 0);
-    issue_weights(wbuf0, kStepTap[0], 0);
-    issue_weights(wbuf1, kStepTap[1], 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-
-    // one step; S is a compile-time constant so that every table entry, buffer choice and request count folds
-    auto step = [&](auto s_tag, int c, bool more) __attribute__((always_inline)) {
-        constexpr int S = decltype(s_tag)::value;
-        const char *wcur = S % 3 == 0 ? wbuf0 : (S % 3 == 1 ? wbuf1 : wbuf2);
-        char *wnext2 = (S + 2) % 3 == 0 ? wbuf0 : ((S + 2) % 3 == 1 ? wbuf1 : wbuf2);
-        const char *wcur_win = kStepBuf[S] ? win1 : win0;
-        char *wnext_win = kStepBuf[S] ? win0 : win1;
-        compute_tap(wcur_win, wcur, (kStepDY[S] + 1) * pitch + (kStepDX[S] + 1));
-        // requests after the step's reads and MFMAs; window pieces BEFORE slab pieces (they are the older ones for the counted wait)
-        const int cn = S == 8 ? (more ? c + 1 : c) : c;
-        if constexpr (kStepReq[S] > 0) {
-#pragma unroll
-            for (int q = 0; q < kStepReq[S]; ++q) issue_piece(wnext_win, kStepReqFrom[S] + q, kNextPy[S], kNextPx[S], cn);
-        }
-        if constexpr (S < 7)
-            issue_weights(wnext2, kStepTap[S + 2], c);
-        else
-            issue_weights(wnext2, kStepTap[S - 7], more ? c + 1 : c);
-        // last step of a plane (3, 5, 7, 8): everything but this step's slab requests has landed -> the next plane's window is complete
-        constexpr bool plane_end = S == 3 || S == 5 || S == 7 || S == 8;
-        wait_vmcnt(plane_end ? WR : WR + kStepReq[S]);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-    };
-    for (int c = 0; c < nchunks; ++c) {
-        const bool more = c + 1 < nchunks;
-        step(std::integral_constant<int, 0>{}, c, more);
-        step(std::integral_constant<int, 1>{}, c, more);
-        step(std::integral_constant<int, 2>{}, c, more);
-        step(std::integral_constant<int, 3>{}, c, more);
-        step(std::integral_constant<int, 4>{}, c, more);
-        step(std::integral_constant<int, 5>{}, c, more);
-        step(std::integral_constant<int, 6>{}, c, more);
-        step(std::integral_constant<int, 7>{}, c, more);
-        step(std::integral_constant<int, 8>{}, c, more);
-    }
-
-    // ---- epilogue (bias already in the accumulators)
-    int pix_e, col_e;
-    halo_out_pixel(a, o0 + wave_p * WP, 0, lane, pix_e, col_e);
-    long long pixj[TP];
-#pragma unroll
-    for (int j = 0; j < TP; ++j) pixj[j] = lane_fetch(j * 16 + lr, pix_e);
-    T *out = reinterpret_cast<T *>(a.out);
-    if (cb + NV <= a.Cout) {
-#pragma unroll
-        for (int j = 0; j < TP; ++j) {
-            if (pixj[j] < 0) continue;
-            float v[NV];
-#pragma unroll
-            for (int i = 0; i < TC; ++i)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    if constexpr (SPLIT)
-                        v[i * 4 + r] = wtk_split_value(acc[i][j][r], acc1[i][j][r]);
-                    else
-                        v[i * 4 + r] = acc[i][j][r];
-                }
-            if (a.act) {
-                wtk_silu_scaled_run<NV>(v);
-            }
-            if constexpr (SPLIT)
-                wtk_split_store<NV>(reinterpret_cast<_Float16 *>(a.out) + pixj[j] * a.out_ld + a.out_coff, cb, v);
-            else
-                store_run_h<NV>(out + pixj[j] * a.out_ld + a.out_coff + cb, v);
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the last chunk's duplicate requests must not outlive the block's LDS
-}
-
-template <int BMT, bool SPLIT = false> hipError_t launch_s2(HaloArgs a, hipStream_t stream) {
-    const long long blocks = (long long)a.blocks_per_strip * (a.CoutPad / 128);
-    if (blocks <= 0 || blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-    a.d_nct = make_fastdiv((unsigned)(a.CoutPad / 128));
-    a.d_bps = make_fastdiv((unsigned)a.blocks_per_strip);
-    a.d_strips = make_fastdiv(1u);
-    a.d_pitch = make_fastdiv((unsigned)a.pitch);
-    a.d_h1 = make_fastdiv((unsigned)(a.H + 1));
-    a.grid = (int)blocks;
-    hipLaunchKernelGGL((conv3x3_s2_kernel<BMT, SPLIT>), dim3((unsigned)blocks), dim3(512), 0, stream, a);
-    return hipGetLastError();
-}
-
 template <typename T, int BN, int HROWS> hipError_t launch_hp(HaloArgs a, int num_cus, hipStream_t stream) {
     const long long tiles = (long long)a.strips * a.blocks_per_strip * (a.CoutPad / BN);
     if (tiles <= 0 || tiles > 0x3fffffffLL || num_cus < 8) return hipErrorInvalidValue;
-    if (kBM + 2 * a.pitch + 2 > HROWS || (a.Cin / (8 * ElemH<T>::CE)) % 2 != 0) return hipErrorInvalidValue;
+    if (kBM + 2 * a.pitch + 2 > HROWS || (a.Cin / (8 * Elem<T>::CE)) % 2 != 0) return hipErrorInvalidValue;
     a.d_nct = make_fastdiv((unsigned)(a.CoutPad / BN));
     a.d_bps = make_fastdiv((unsigned)a.blocks_per_strip);
     a.d_strips = make_fastdiv((unsigned)a.strips);
@@ -1931,6 +1138,30 @@ template <typename T, int BN, int NHALO, int MINW, int NWB, int HROWS, int BMT =
     a.grid = (int)blocks;
     hipLaunchKernelGGL((conv3x3_halo_kernel<T, BN, NHALO, MINW, NWB, HROWS, BMT, TAIL, SPLIT>), dim3((unsigned)blocks), dim3(512), 0, stream, a);
     return hipGetLastError();
+}
+
+// The variant of one tile shape (T, BN, NHALO, MINW): weight ring (nwb = 3, or 2 = the two-slab / vmcnt(0) schedule, 256-pixel blocks only), pixels per
+// block and fused tail.  A 192-cout tile with three slabs only leaves room for 352-row windows (the planner then cuts wide maps into strips of <= 45 columns).
+template <typename T, int BN, int NHALO, int MINW, bool SPLIT = false> hipError_t launch_h_tile(const HaloArgs &a, int nwb, int bm, hipStream_t stream) {
+    constexpr int HR3 = BN == 192 ? kHaloRowsSmall : kHaloRowsMax;
+    if (a.tail_w) { // validated by the caller: fp16, 64- or 128-cout tile, three slabs
+        if constexpr (sizeof(T) == 2 && BN != 192)
+            return bm == 128 ? launch_h<T, BN, NHALO, MINW, 3, kHaloRowsMax, 128, true, SPLIT>(a, stream) : launch_h<T, BN, NHALO, MINW, 3, kHaloRowsMax, 256, true, SPLIT>(a, stream);
+        return hipErrorInvalidValue;
+    }
+    if (nwb != 2) return bm == 128 ? launch_h<T, BN, NHALO, MINW, 3, HR3, 128, false, SPLIT>(a, stream) : launch_h<T, BN, NHALO, MINW, 3, HR3, 256, false, SPLIT>(a, stream);
+    if constexpr (!SPLIT) {
+        if (bm == kBM) return launch_h<T, BN, NHALO, MINW, 2, kHaloRowsMax>(a, stream);
+    }
+    return hipErrorInvalidValue;
+}
+// ... and the tile shape of a layer: 128 / 192 couts on two window buffers; 64 couts on one buffer and four blocks' worth of registers when the layer is a
+// single channel chunk, on two otherwise
+template <typename T> hipError_t launch_h_any(const HaloArgs &a, int bn, int nchunks, int nwb, int bm, hipStream_t stream) {
+    if (bn == 128) return launch_h_tile<T, 128, 2, 2>(a, nwb, bm, stream);
+    if (bn == 192) return launch_h_tile<T, 192, 2, 2>(a, nwb, bm, stream);
+    if (nchunks == 1) return launch_h_tile<T, 64, 1, 4>(a, nwb, bm, stream);
+    return launch_h_tile<T, 64, 2, 2>(a, nwb, bm, stream);
 }
 
 } // namespace
@@ -1961,12 +1192,9 @@ hipError_t launch_conv3x3_halo_split(const HaloArgs &a, hipStream_t stream) {
     if ((long long)a.blocks_per_strip * bm < (long long)a.N * (a.H + 1) * a.pitch) return hipErrorInvalidValue;
     if (a.res && (a.res_ld % 64 || a.res_coff % 64)) return hipErrorInvalidValue;
     if (a.out2 && (a.out2_ld % 64 || a.out2_coff % 64)) return hipErrorInvalidValue;
-    if (bn == 128 && a.tail_w) return bm == 128 ? launch_h<_Float16, 128, 2, 2, 3, kHaloRowsMax, 128, true, true>(a, stream) : launch_h<_Float16, 128, 2, 2, 3, kHaloRowsMax, 256, true, true>(a, stream);
-    if (bn == 128) return bm == 128 ? launch_h<_Float16, 128, 2, 2, 3, kHaloRowsMax, 128, false, true>(a, stream) : launch_h<_Float16, 128, 2, 2, 3, kHaloRowsMax, 256, false, true>(a, stream);
-    if (a.tail_w) return bm == 128 ? launch_h<_Float16, 64, 2, 2, 3, kHaloRowsMax, 128, true, true>(a, stream) : launch_h<_Float16, 64, 2, 2, 3, kHaloRowsMax, 256, true, true>(a, stream);
-    // six-slab ring: the 128-pixel tile only (the 256-pixel tile, 24 MFMAs per wave and tap, measured the same with either ring)
-    if (a.deep && bm == 128) return launch_h<_Float16, 64, 2, 1, 6, kHaloRowsMax, 128, false, true>(a, stream);
-    return bm == 128 ? launch_h<_Float16, 64, 2, 2, 3, kHaloRowsMax, 128, false, true>(a, stream) : launch_h<_Float16, 64, 2, 2, 3, kHaloRowsMax, 256, false, true>(a, stream);
+    // six-slab ring: the 64-cout x 128-pixel tile only (the 256-pixel tile, 24 MFMAs per wave and tap, measured the same with either ring)
+    if (bn == 64 && !a.tail_w && a.deep && bm == 128) return launch_h<_Float16, 64, 2, 1, 6, kHaloRowsMax, 128, false, true>(a, stream);
+    return bn == 128 ? launch_h_tile<_Float16, 128, 2, 2, true>(a, 3, bm, stream) : launch_h_tile<_Float16, 64, 2, 2, true>(a, 3, bm, stream);
 }
 
 int halo_rows_max(int cout_stored, int slabs) { return (slabs == 3 && halo_cout_tile(cout_stored) == 192) ? kHaloRowsSmall : kHaloRowsMax; }
@@ -1987,51 +1215,6 @@ void halo_geometry_stacked(int N, int H, int W, int rows_max, int *S, int *pitch
     *blocks_per_strip = (int)(((long long)N * (H + 1) * *pitch + bm - 1) / bm);
 }
 
-// stride-2 window kernel: a.H / a.W are the OUTPUT map; one strip (pitch = W + 1); a.bm = 128 selects the half-size block
-bool s2win_eligible(int k, int stride, int cin, int cout, int cout_pad, int is_f16, int wo, bool plain) {
-    // cin >= 128: the 64-channel strided conv (model.3) keeps the implicit-GEMM kernel, whose fused-tail form (model.3 + model.4.cv1) must stay
-    // bit-identical to its stand-alone form (test_fused_kernels_equal_layer_by_layer switches the fusion off and on)
-    return is_f16 && k == 3 && stride == 2 && cin % 64 == 0 && cin >= 128 && cout_pad % 128 == 0 && cout % 16 == 0 && plain && 256 + (wo + 1) + 2 <= kS2Rows;
-}
-
-hipError_t launch_conv3x3_s2(const HaloArgs &a, hipStream_t stream) {
-    if (a.Cin % 64 || a.CoutPad % 128 || a.Cout > a.CoutPad || a.Cout % 16 || a.out2 || a.tail_w || a.res || a.Kpad < 9 * a.Cin || a.Kpad % 64) return hipErrorInvalidValue;
-    if (a.in_ld % 8 || a.in_coff % 8 || a.out_ld % 8 || a.out_coff % 8) return hipErrorInvalidValue;
-    const int bm = a.bm == 128 ? 128 : 256;
-    if (a.strips != 1 || a.S != a.W || a.pitch != a.W + 1 || bm + a.pitch + 2 > kS2Rows) return hipErrorInvalidValue;
-    if ((long long)a.blocks_per_strip * bm < (long long)a.N * (a.H + 1) * a.pitch) return hipErrorInvalidValue;
-    return bm == 128 ? launch_s2<128>(a, stream) : launch_s2<256>(a, stream);
-}
-
-// split-fp16 operands: real channel counts here
-bool split_s2win_eligible(int k, int stride, int cin, int cout, int cout_pad, int wo, bool plain) {
-    return k == 3 && stride == 2 && cin % 32 == 0 && cout_pad % 128 == 0 && cout == cout_pad && plain && 256 + (wo + 1) + 2 <= kS2Rows;
-}
-// a.Cin / Kpad / in_ld / in_coff / out_ld / out_coff in pseudo-channels (2 x real), a.Cout real
-hipError_t launch_conv3x3_s2_split(const HaloArgs &a, hipStream_t stream) {
-    if (a.Cin % 64 || a.CoutPad % 128 || a.Cout != a.CoutPad || a.out2 || a.tail_w || a.res || a.Kpad != 9 * a.Cin) return hipErrorInvalidValue;
-    if (a.in_ld % 64 || a.in_coff % 64 || a.out_ld % 64 || a.out_coff % 64) return hipErrorInvalidValue;
-    const int bm = a.bm == 128 ? 128 : 256;
-    if (a.strips != 1 || a.S != a.W || a.pitch != a.W + 1 || bm + a.pitch + 2 > kS2Rows) return hipErrorInvalidValue;
-    if ((long long)a.blocks_per_strip * bm < (long long)a.N * (a.H + 1) * a.pitch) return hipErrorInvalidValue;
-    return bm == 128 ? launch_s2<128, true>(a, stream) : launch_s2<256, true>(a, stream);
-}
-
-int ws64_rows_max() { return kWsRows; }
-
-bool ws64_eligible(int k, int stride, int cin, int cout, int cout_pad, int is_f16, bool has_out2, bool has_tail) {
-    return is_f16 && k == 3 && stride == 1 && cin == 64 && cout == 64 && cout_pad == 64 && !has_out2 && !has_tail;
-}
-
-hipError_t launch_conv3x3_ws64(const HaloArgs &a, int num_cus, hipStream_t stream) {
-    if (a.Cin != 64 || a.Cout != 64 || a.CoutPad != 64 || a.out2 || a.tail_w || a.Kpad < 576 || a.Kpad % 64) return hipErrorInvalidValue;
-    if (a.in_ld % 8 || a.in_coff % 8 || a.out_ld % 8 || a.out_coff % 8) return hipErrorInvalidValue;
-    if (a.res && (a.res_ld % 8 || a.res_coff % 8)) return hipErrorInvalidValue;
-    if (a.pitch != (a.strips == 1 ? a.S + 1 : a.S + 2) || a.strips * a.S < a.W || (a.strips == 1 && a.S != a.W)) return hipErrorInvalidValue;
-    if ((long long)a.blocks_per_strip * 256 < (long long)a.N * (a.H + 1) * a.pitch) return hipErrorInvalidValue;
-    return launch_ws64(a, num_cus, stream);
-}
-
 int halo_cout_tile(int cout_stored) { return cout_stored % 128 == 0 ? 128 : (cout_stored % 192 == 0 ? 192 : 64); }
 
 hipError_t launch_conv3x3_halo(const HaloArgs &a, int is_f16, hipStream_t stream) {
@@ -2050,8 +1233,6 @@ hipError_t launch_conv3x3_halo(const HaloArgs &a, int is_f16, hipStream_t stream
     if (a.res && (a.res_ld % ce || a.res_coff % ce)) return hipErrorInvalidValue;
     if (a.out2 && (a.out2_ld % ce || a.out2_coff % ce)) return hipErrorInvalidValue;
     const int nchunks = a.Cin / cch;
-    // three weight slabs + counted vmcnt (default) or the two-slab / vmcnt(0) schedule (slabs == 2).  A 192-cout tile with three
-    // slabs only leaves room for 352-row windows: the planner then cuts wide maps into strips of <= 45 columns.
     // persistent form only where a block gets to walk several tiles (measured: -5..-8 % at 6-7 tiles per CU, -1..2 % at 1.75, but
     // +4 % when every block has exactly one tile: its per-tile bookkeeping then buys nothing)
     const long long tiles = (long long)a.strips * a.blocks_per_strip * (a.CoutPad / bn);
@@ -2059,49 +1240,9 @@ hipError_t launch_conv3x3_halo(const HaloArgs &a, int is_f16, hipStream_t stream
         if (is_f16) return bn == 128 ? launch_hp<_Float16, 128, kHaloRowsMax>(a, a.persist_cus, stream) : launch_hp<_Float16, 192, kHaloRowsSmall>(a, a.persist_cus, stream);
         return bn == 128 ? launch_hp<float, 128, kHaloRowsMax>(a, a.persist_cus, stream) : launch_hp<float, 192, kHaloRowsSmall>(a, a.persist_cus, stream);
     }
-    if (a.tail_w && bn == 128) { // class tower: one tile per block (both window buffers hold the exchange tiles afterwards)
-        if (bm == 128) return launch_h<_Float16, 128, 2, 2, 3, kHaloRowsMax, 128, true>(a, stream);
-        return launch_h<_Float16, 128, 2, 2, 3, kHaloRowsMax, 256, true>(a, stream);
-    }
-    if (a.tail_w) { // validated above: fp16, 64-cout tile, three slabs
-        if (bm == 128) return nchunks == 1 ? launch_h<_Float16, 64, 1, 4, 3, kHaloRowsMax, 128, true>(a, stream) : launch_h<_Float16, 64, 2, 2, 3, kHaloRowsMax, 128, true>(a, stream);
-        return nchunks == 1 ? launch_h<_Float16, 64, 1, 4, 3, kHaloRowsMax, 256, true>(a, stream) : launch_h<_Float16, 64, 2, 2, 3, kHaloRowsMax, 256, true>(a, stream);
-    }
-    if (a.slabs != 2 && bm == 128) { // half-size blocks: small maps that would otherwise leave CUs without a block
-        if (is_f16) {
-            if (bn == 128) return launch_h<_Float16, 128, 2, 2, 3, kHaloRowsMax, 128>(a, stream);
-            if (bn == 192) return launch_h<_Float16, 192, 2, 2, 3, kHaloRowsSmall, 128>(a, stream);
-            if (nchunks == 1) return launch_h<_Float16, 64, 1, 4, 3, kHaloRowsMax, 128>(a, stream);
-            return launch_h<_Float16, 64, 2, 2, 3, kHaloRowsMax, 128>(a, stream);
-        }
-        if (bn == 128) return launch_h<float, 128, 2, 2, 3, kHaloRowsMax, 128>(a, stream);
-        if (bn == 192) return launch_h<float, 192, 2, 2, 3, kHaloRowsSmall, 128>(a, stream);
-        if (nchunks == 1) return launch_h<float, 64, 1, 4, 3, kHaloRowsMax, 128>(a, stream);
-        return launch_h<float, 64, 2, 2, 3, kHaloRowsMax, 128>(a, stream);
-    }
-    if (bm != kBM) return hipErrorInvalidValue;
-    if (a.slabs != 2) {
-        if (is_f16) {
-            if (bn == 128) return launch_h<_Float16, 128, 2, 2, 3, kHaloRowsMax>(a, stream);
-            if (bn == 192) return launch_h<_Float16, 192, 2, 2, 3, kHaloRowsSmall>(a, stream);
-            if (nchunks == 1) return launch_h<_Float16, 64, 1, 4, 3, kHaloRowsMax>(a, stream);
-            return launch_h<_Float16, 64, 2, 2, 3, kHaloRowsMax>(a, stream);
-        }
-        if (bn == 128) return launch_h<float, 128, 2, 2, 3, kHaloRowsMax>(a, stream);
-        if (bn == 192) return launch_h<float, 192, 2, 2, 3, kHaloRowsSmall>(a, stream);
-        if (nchunks == 1) return launch_h<float, 64, 1, 4, 3, kHaloRowsMax>(a, stream);
-        return launch_h<float, 64, 2, 2, 3, kHaloRowsMax>(a, stream);
-    }
-    if (is_f16) {
-        if (bn == 128) return launch_h<_Float16, 128, 2, 2, 2, kHaloRowsMax>(a, stream);
-        if (bn == 192) return launch_h<_Float16, 192, 2, 2, 2, kHaloRowsMax>(a, stream);
-        if (nchunks == 1) return launch_h<_Float16, 64, 1, 4, 2, kHaloRowsMax>(a, stream);
-        return launch_h<_Float16, 64, 2, 2, 2, kHaloRowsMax>(a, stream);
-    }
-    if (bn == 128) return launch_h<float, 128, 2, 2, 2, kHaloRowsMax>(a, stream);
-    if (bn == 192) return launch_h<float, 192, 2, 2, 2, kHaloRowsMax>(a, stream);
-    if (nchunks == 1) return launch_h<float, 64, 1, 4, 2, kHaloRowsMax>(a, stream);
-    return launch_h<float, 64, 2, 2, 2, kHaloRowsMax>(a, stream);
+    // one tile per block: three weight slabs + counted vmcnt (default), or the two-slab / vmcnt(0) schedule (slabs == 2)
+    const int nwb = a.slabs == 2 ? 2 : 3;
+    return is_f16 ? launch_h_any<_Float16>(a, bn, nchunks, nwb, bm, stream) : launch_h_any<float>(a, bn, nchunks, nwb, bm, stream);
 }
 
 } // namespace wtk

@@ -19,7 +19,7 @@
 //   * zero padding / ragged tiles are handled by predicated 16-byte loads (no im2col buffer).
 //   * pixel tiles are 2-D patches (tile_w x BM/tile_w) on large maps so the 3x3 halo is re-read from
 //     L1/L2 rather than HBM, and block ids are remapped so neighbouring tiles share an XCD's L2.
-#include "wtk_kernels.h"
+#include "wtk_device.h"
 
 #ifndef WTK_IGEMM_ORDER
 #define WTK_IGEMM_ORDER 0 // 1: issue the next stage's LDS-DMA between the two k-halves (measured 2 % slower: less time to land before the barrier)
@@ -27,92 +27,10 @@
 
 namespace wtk {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-
-template <typename T> struct Elem;
-template <> struct Elem<_Float16> {
-    static constexpr int CE = 8; // elements per 16-byte chunk
-};
-template <> struct Elem<float> {
-    static constexpr int CE = 4;
-};
-
-// SiLU with two transcendentals and three plain VALU ops (v_mul, v_exp, v_add, v_rcp, v_mul).  The obvious
-// x / (1 + __expf(-x)) expands to ~35 instructions (IEEE division + range-checked exp) and made the
-// epilogue, not the MFMA loop, the longest part of every conv.  v_exp/v_rcp are 1-ulp approximations.
-__device__ __forceinline__ float silu_f(float x) {
-    return wtk_silu_scaled(x); // x is the log2(e)-scaled pre-activation (wtk_kernels.h)
-}
-
-// one 16-byte operand fragment pair -> MFMA(s)
-__device__ __forceinline__ void mma_frag(const uint4 &wf, const uint4 &pf, floatx4 &acc, _Float16 *) {
-    half8 a = __builtin_bit_cast(half8, wf);
-    half8 b = __builtin_bit_cast(half8, pf);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, acc, 0, 0, 0);
-}
-__device__ __forceinline__ void mma_frag(const uint4 &wf, const uint4 &pf, floatx4 &acc, float *) {
-    // lane (r, g) holds k = 4*(g + 4*khalf) + i, i = 0..3; MFMA #i contracts the i-th element of every
-    // lane group: k set {i, 4+i, 8+i, 12+i} (+16*khalf) — same k on both operands.
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__builtin_bit_cast(float, wf.x), __builtin_bit_cast(float, pf.x), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__builtin_bit_cast(float, wf.y), __builtin_bit_cast(float, pf.y), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__builtin_bit_cast(float, wf.z), __builtin_bit_cast(float, pf.z), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__builtin_bit_cast(float, wf.w), __builtin_bit_cast(float, pf.w), acc, 0, 0, 0);
-}
-
-template <int NV> __device__ __forceinline__ void load_run(const _Float16 *p, float (&v)[NV]) {
-#pragma unroll
-    for (int i = 0; i < NV; i += 8) {
-        half8 h = *reinterpret_cast<const half8 *>(p + i);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[i + j] = (float)h[j];
-    }
-}
-template <int NV> __device__ __forceinline__ void load_run(const float *p, float (&v)[NV]) {
-#pragma unroll
-    for (int i = 0; i < NV; i += 4) {
-        float4 f = *reinterpret_cast<const float4 *>(p + i);
-        v[i] = f.x, v[i + 1] = f.y, v[i + 2] = f.z, v[i + 3] = f.w;
-    }
-}
-template <int NV> __device__ __forceinline__ void store_run(_Float16 *p, const float (&v)[NV]) {
-#pragma unroll
-    for (int i = 0; i < NV; i += 8) {
-        half8 h;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) h[j] = (_Float16)v[i + j];
-        *reinterpret_cast<half8 *>(p + i) = h;
-    }
-}
-template <int NV> __device__ __forceinline__ void store_run(float *p, const float (&v)[NV]) {
-#pragma unroll
-    for (int i = 0; i < NV; i += 4) *reinterpret_cast<float4 *>(p + i) = make_float4(v[i], v[i + 1], v[i + 2], v[i + 3]);
-}
-
-// LDS-DMA requests in buffer form (SGPR resource + wave-uniform byte offset + per-lane 32-bit offset) from inline asm: 5-10 % less
-// wave time per request than the flat form (tools/lds_dma_rate.hip), no 64-bit address arithmetic and no zero-page select per row
-// (a lane offset of 0xffffffff is out of range and lands zeros).  hipcc does not see these requests: every barrier that publishes a
-// stage is preceded by an explicit s_waitcnt vmcnt(0).  The two-source (UP) loader keeps the builtin form.
+// LDS-DMA requests in buffer form (lds_dma_buf, wtk_device.h) for the single-source loaders; the two-source (UP) loader keeps the builtin form.
 #ifndef WTK_IGEMM_BUFFER_DMA
 #define WTK_IGEMM_BUFFER_DMA 1
 #endif
-typedef int rsrc_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ rsrc_t make_rsrc(const void *base) {
-    const unsigned long long b = (unsigned long long)base;
-    rsrc_t r;
-    r.x = (int)(unsigned)(b & 0xffffffffu);
-    r.y = (int)(unsigned)((b >> 32) & 0xffffu);
-    r.z = (int)0xffffff00u;
-    r.w = 0x00020000;
-    return r;
-}
-template <bool NTL> __device__ __forceinline__ void dma_buf(const rsrc_t &rs, unsigned voff, unsigned soff, char *lds_dst) {
-    const unsigned lds = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char *)lds_dst;
-    if constexpr (NTL)
-        asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen nt lds" ::"v"(voff), "s"(rs), "s"(soff), "s"(lds) : "memory");
-    else
-        asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds" ::"v"(voff), "s"(rs), "s"(soff), "s"(lds) : "memory");
-}
 
 // K1: 1x1 stride-1 conv (no tap walk).  NT: the pixel operand is read by exactly one cout tile, so its
 // LDS-DMA loads carry the non-temporal hint (measured: +8..17 % on the HBM-bound 1x1 layers, -15..25 % when a
@@ -317,10 +235,10 @@ __global__ __launch_bounds__(64 * WAVES_P * WAVES_C, (2 * (BM + BN) * 128 <= 52 
                 const bool k_ok = kc < a.Cin; // K tail of the last step is zero
                 if (UP && ld_ks * BKE < a.in2_split) { // block-uniform: in2_split is a multiple of the K step; low-resolution rows are shared by 4 pixels: no nt
 #pragma unroll
-                    for (int r = 0; r < PR; ++r) dma_buf<false>(in2_rs, poff2[r], so, pt + (RPP * r + 8 * wave) * 128);
+                    for (int r = 0; r < PR; ++r) lds_dma_buf<false>(in2_rs, poff2[r], so, pt + (RPP * r + 8 * wave) * 128);
                 } else {
 #pragma unroll
-                    for (int r = 0; r < PR; ++r) dma_buf<NT>(in_rs, k_ok ? poff[r] : 0xffffffffu, so, pt + (RPP * r + 8 * wave) * 128);
+                    for (int r = 0; r < PR; ++r) lds_dma_buf<NT>(in_rs, k_ok ? poff[r] : 0xffffffffu, so, pt + (RPP * r + 8 * wave) * 128);
                 }
             } else {
                 const int kh = a.KW == 3 ? (tap * 11) >> 5 : tap / a.KW, kw = tap - kh * a.KW; // tap/3 for tap < 32
@@ -330,11 +248,11 @@ __global__ __launch_bounds__(64 * WAVES_P * WAVES_C, (2 * (BM + BN) * 128 <= 52 
                 for (int r = 0; r < PR; ++r) {
                     const int hi = phi0[r] + kh, wi = pwi0[r] + kw;
                     const bool ok = tap_ok && (unsigned)hi < (unsigned)a.H && (unsigned)wi < (unsigned)a.W;
-                    dma_buf<false>(in_rs, ok ? poff[r] + delta : 0xffffffffu, 0u, pt + (RPP * r + 8 * wave) * 128);
+                    lds_dma_buf<false>(in_rs, ok ? poff[r] + delta : 0xffffffffu, 0u, pt + (RPP * r + 8 * wave) * 128);
                 }
             }
 #pragma unroll
-            for (int i = 0; i < WR; ++i) dma_buf<false>(w_rs, wvoff[i], so, wt + (RPP * i + 8 * wave) * 128);
+            for (int i = 0; i < WR; ++i) lds_dma_buf<false>(w_rs, wvoff[i], so, wt + (RPP * i + 8 * wave) * 128);
         } else if (K1) {
             const bool k_ok = kc < a.Cin; // K tail of the last step is zero
             if (UP && ld_ks * BKE < a.in2_split) { // block-uniform: in2_split is a multiple of the K step

@@ -38,7 +38,7 @@
 // conflict-free ds_read_b128 MFMA fragments.  Two storage modes share all of it because both spend 4 bytes per value:
 //   SPLIT  split-fp16 pairs [hi32 | lo32] per 32 channels, three v_mfma_f32_16x16x32_f16 per product (wtk_kernels.h, kSplitScale)
 //   fp32   32 floats per row, exact v_mfma_f32_16x16x4_f32
-#include "wtk_kernels.h"
+#include "wtk_device.h"
 
 #include <algorithm>
 #include <cmath>
@@ -48,23 +48,7 @@
 namespace wtk {
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef int rsrc_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ rsrc_t sk_rsrc(const void *base) {
-    const unsigned long long b = (unsigned long long)base;
-    rsrc_t r;
-    r.x = (int)(unsigned)(b & 0xffffffffu);
-    r.y = (int)(unsigned)((b >> 32) & 0xffffu);
-    r.z = (int)0xffffff00u; // num_records: a lane offset of 0xffffffff is out of range and lands zeros
-    r.w = 0x00020000;
-    return r;
-}
-__device__ __forceinline__ void sk_dma(const rsrc_t &rs, unsigned voff, unsigned soff, char *lds_dst) {
-    const unsigned lds = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char *)lds_dst;
-    asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds" ::"v"(voff), "s"(rs), "s"(soff), "s"(lds) : "memory");
-}
+// (wait_vmcnt of wtk_device.h takes a runtime count; the immediates here are compile-time multiples of PER)
 // wait until all but the youngest n * PER vector-memory operations of this wave are done (n stages of PER requests each still in flight)
 template <int PER> __device__ __forceinline__ void sk_wait_stages(int n) {
     static_assert(PER * 6 <= 63, "vmcnt is a 6-bit counter");
@@ -169,9 +153,9 @@ __device__ __forceinline__ void sk_body(const SkArgs &a, const unsigned bid, cha
     const int ch = tid & 7, r0 = tid >> 3;
     const int lchunk = ch ^ (r0 & 7);
     const int nb = (int)fdiv((unsigned)m0, a.d_howo); // image of the tile's first pixel: lane offsets are relative to it (32-bit)
-    const rsrc_t in_rs = sk_rsrc(a.in + (long long)nb * a.H * a.W * a.in_ldb + a.in_offb);
-    const rsrc_t in2_rs = sk_rsrc(a.in2 ? a.in2 + (long long)nb * (a.H >> 1) * (a.W >> 1) * a.in2_ldb + a.in2_offb : a.in);
-    const rsrc_t w_rs = sk_rsrc(a.w + (long long)n0 * a.w_rowb);
+    const rsrc_t in_rs = make_rsrc(a.in + (long long)nb * a.H * a.W * a.in_ldb + a.in_offb);
+    const rsrc_t in2_rs = make_rsrc(a.in2 ? a.in2 + (long long)nb * (a.H >> 1) * (a.W >> 1) * a.in2_ldb + a.in2_offb : a.in);
+    const rsrc_t w_rs = make_rsrc(a.w + (long long)n0 * a.w_rowb);
     unsigned poff[PR], poff2[PR];
     int hi0[PR], wi0[PR];
 #pragma unroll
@@ -204,18 +188,18 @@ __device__ __forceinline__ void sk_body(const SkArgs &a, const unsigned bid, cha
         char *pt = buf + 8 * wave * 128, *wt = buf + (BM + 8 * wave) * 128;
         if (cb < a.in2_blocks) { // 1x1 over [up2x(low) | high]: these channels live in the half-resolution tensor
 #pragma unroll
-            for (int i = 0; i < PR; ++i) sk_dma(in2_rs, poff2[i], (unsigned)cb * 128u, pt + RPP * i * 128);
+            for (int i = 0; i < PR; ++i) lds_dma_buf(in2_rs, poff2[i], (unsigned)cb * 128u, pt + RPP * i * 128);
         } else {
             const int kh = a.KW == 3 ? (tap * 11) >> 5 : 0, kw = tap - kh * a.KW; // tap / 3 for tap < 32; a 1x1 has the one tap
             const unsigned delta = (unsigned)((kh * a.W + kw) * (int)a.in_ldb + cb * 128);
 #pragma unroll
             for (int i = 0; i < PR; ++i) {
                 const bool ok = (unsigned)(hi0[i] + kh) < (unsigned)a.H && (unsigned)(wi0[i] + kw) < (unsigned)a.W;
-                sk_dma(in_rs, ok ? poff[i] + delta : 0xffffffffu, 0u, pt + RPP * i * 128);
+                lds_dma_buf(in_rs, ok ? poff[i] + delta : 0xffffffffu, 0u, pt + RPP * i * 128);
             }
         }
 #pragma unroll
-        for (int i = 0; i < WR; ++i) sk_dma(w_rs, wvoff[i], (unsigned)ks * 128u, wt + RPP * i * 128);
+        for (int i = 0; i < WR; ++i) lds_dma_buf(w_rs, wvoff[i], (unsigned)ks * 128u, wt + RPP * i * 128);
     };
 
     // the bias of this lane's couts: requested before the first operand so that its round trip is over long before the epilogue (a small layer is

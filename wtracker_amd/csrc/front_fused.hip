@@ -18,15 +18,13 @@
 //   same order and uses the same MFMA, so the result equals the unfused kernels' bit for bit.
 // Barriers are raw s_barrier + lgkmcnt(0) so the next tile's patch loads and the previous tile's output
 // stores stay in flight across them (a __syncthreads would drain vmcnt at every stage).
-#include "wtk_kernels.h"
+#include "wtk_device.h"
 
 namespace wtk {
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 constexpr int kT = 16;                 // output tile edge (1/4-resolution pixels)
 constexpr int kSE = 2 * kT + 1;        // 33: stem-output tile edge
@@ -51,28 +49,7 @@ static_assert(kW1Bytes + kW2Bytes + kSBytes + kPOBytes <= 160 * 1024, "LDS budge
 // ~10-instruction IEEE division of the stand-alone stem without changing a single fp16 result.
 constexpr float kInv255 = 1.0f / 255.0f;
 
-// Pins an fp32 value in a VGPR.  Without it hipcc folds "(half)(a * b)" into v_fma_mixlo_f16, which rounds the
-// exact product ONCE to fp16; the stand-alone kernels round the product to fp32 first (v_mul_f32 +
-// v_cvt_pk_f16_f32), and this kernel promises their bits.
-__device__ __forceinline__ float pin_f32(float v) {
-    asm("" : "+v"(v));
-    return v;
-}
-
-__device__ __forceinline__ float silu_ff(float x) {
-    return wtk_silu_scaled(x); // scaled domain, see wtk_kernels.h
-}
-
-__device__ __forceinline__ _Float16 norm_byte(uint32_t b) { return (_Float16)pin_f32((float)b * kInv255); }
-
-// LDS-only barrier: waits for this wave's LDS traffic (lgkmcnt(0)), not for global loads/stores in flight.
-// The asm clobbers keep the compiler from moving LDS accesses across it (the s_barrier intrinsic alone is IntrNoMem).
-__device__ __forceinline__ void lds_barrier() {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_waitcnt(0xc07f); // vmcnt = 63 (no wait), expcnt = 7, lgkmcnt = 0
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
+__device__ __forceinline__ _Float16 norm_byte(uint32_t b) { return (_Float16)wtk_pin_f32((float)b * kInv255); }
 
 template <bool DBG>
 __global__ __launch_bounds__(512, 2) void front_fused_kernel(const FrontArgs a) {
@@ -278,7 +255,7 @@ __global__ __launch_bounds__(512, 2) void front_fused_kernel(const FrontArgs a) 
                 }
                 const int gy = 2 * oy0 - 1 + sy, gx = 2 * ox0 - 1 + sx;
                 const bool inside = (unsigned)gy < (unsigned)Hs && (unsigned)gx < (unsigned)Ws;
-                // silu_ff pins its fp32 product, so rounding is product -> fp32 -> fp16 as in the stand-alone kernels;
+                // wtk_silu_scaled pins its fp32 product, so rounding is product -> fp32 -> fp16 as in the stand-alone kernels;
                 // pixels outside the stem map are model.1's zero padding: mask the packed halves (4 selects, not 8)
                 half8 hv;
                 {

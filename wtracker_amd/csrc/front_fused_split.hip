@@ -19,14 +19,11 @@
 // conv_igemm_kernel's split form: per K step hi.hi into `acc`, lo.hi then hi.lo into `acc1`; v = acc + acc1 * 2^-11; SiLU; split),
 // so the result equals the unfused kernels' bit for bit (tests/test_gpu_f16x3.py switches the fusion off and on).
 // Barriers are raw s_barrier + lgkmcnt(0) so the next tile's patch loads and the previous tile's output stores stay in flight.
-#include "wtk_kernels.h"
+#include "wtk_device.h"
 
 namespace wtk {
 
 namespace {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 constexpr int kTW = 16, kTH = 4;          // output tile (1/4-resolution pixels)
 constexpr int kSW = 2 * kTW + 1;          // 33 stem-output columns
@@ -50,14 +47,6 @@ constexpr int kPOBytes = ((kPBytes > kO1Bytes ? kPBytes : kO1Bytes) + 63) / 64 *
 static_assert(kW1Bytes + kW2Bytes + kSBytes + kPOBytes + 1024 <= 160 * 1024, "LDS budget");
 static_assert(kUnits <= 512, "one patch unit per thread");
 
-// LDS-only barrier: waits for this wave's LDS traffic (lgkmcnt(0)), not for global loads/stores in flight.
-__device__ __forceinline__ void lds_barrier_s() {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_waitcnt(0xc07f); // vmcnt = 63 (no wait), expcnt = 7, lgkmcnt = 0
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-
 // Packed fp32 forms (v_pk_add_f32 / v_pk_mul_f32) in the epilogues: measured 574 us against 610 us for the scalar forms on the
 // BASELINE shape (-DWTK_FFS_PACKED=0 builds the scalar, pinned forms; same IEEE operations, bit-identical results) — unlike the
 // window kernels, whose epilogues run beside a wave issuing fp16 matrix instructions back to back, the stages here are VALU bound.
@@ -71,7 +60,7 @@ __device__ __forceinline__ float ffs_pin(float v) {
     return wtk_pin_f32(v);
 #endif
 }
-// eight fp32 values -> their split halves (wtk_split_store's arithmetic)
+// split_pack8 (wtk_device.h) with the difference and the product pinned in the -DWTK_FFS_PACKED=0 build
 __device__ __forceinline__ void split8(const float (&v)[8], half8 &hv, half8 &lv) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
@@ -288,7 +277,7 @@ __global__ __launch_bounds__(512, 2) void front_fused_split_kernel(const FrontAr
         }
         STAMP(0);
         flush_pending(); // previous tile's output -> global
-        lds_barrier_s();
+        lds_barrier();
         STAMP(1);
 
         // ======== B: prefetch the next tile's patch; stem: P -> S (fp32 matrix instructions, one per tap and cout tile)
@@ -383,7 +372,7 @@ __global__ __launch_bounds__(512, 2) void front_fused_split_kernel(const FrontAr
             }
         }
         STAMP(2);
-        lds_barrier_s();
+        lds_barrier();
         STAMP(3);
 
         // ======== C: model.1 (3x3 / stride 2 over S) -> O1.  Wave = output row `orow` of the tile x 32 couts
@@ -434,7 +423,7 @@ __global__ __launch_bounds__(512, 2) void front_fused_split_kernel(const FrontAr
             }
         }
         STAMP(4);
-        lds_barrier_s(); // a pixel's 64 channels come from two waves
+        lds_barrier(); // a pixel's 64 channels come from two waves
         STAMP(5);
 
         // ======== D: cv1 (1x1, 64 -> 64) over O1 -> registers (stored one stage later)
@@ -477,7 +466,7 @@ __global__ __launch_bounds__(512, 2) void front_fused_split_kernel(const FrontAr
                                                 : nullptr;
         }
         STAMP(6);
-        lds_barrier_s(); // O1 fully consumed before the next tile's P overwrites it
+        lds_barrier(); // O1 fully consumed before the next tile's P overwrites it
         STAMP(7);
     }
     flush_pending();

@@ -1,10 +1,8 @@
 // Stem (preprocess + model.0), letterbox and SPPF pooling kernels.  HBM-bound byte/elementwise
 // work: coalesced 16-byte accesses, LDS-resident maps for the chained pools.
-#include "wtk_kernels.h"
+#include "wtk_device.h"
 
 namespace wtk {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 
 // ---------------------------------------------------------------------------------------------
 // Stem: fuses ultralytics' predictor preprocess (BGR->RGB, HWC uint8 -> float /255)

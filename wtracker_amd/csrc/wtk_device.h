@@ -1,0 +1,172 @@
+// Device primitives shared by the convolution kernels of libwtk_hip.so: vector types, the raw buffer resource, LDS-DMA requests,
+// counted waits, fragment MMAs, 16-byte runs and split-fp16 packing.  One definition and one comment each; a kernel file that
+// needs a variant of its own says in one line what differs.
+#pragma once
+#include "wtk_kernels.h"
+
+namespace wtk {
+
+typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+typedef float floatx4 __attribute__((ext_vector_type(4)));
+typedef int rsrc_t __attribute__((ext_vector_type(4)));
+
+template <typename T> struct Elem;
+template <> struct Elem<_Float16> {
+    static constexpr int CE = 8; // elements per 16-byte chunk
+};
+template <> struct Elem<float> {
+    static constexpr int CE = 4;
+};
+
+// Raw buffer resource over everything a 32-bit offset can reach from `base`
+__device__ __forceinline__ rsrc_t make_rsrc(const void *base) {
+    const unsigned long long b = (unsigned long long)base;
+    rsrc_t r;
+    r.x = (int)(unsigned)(b & 0xffffffffu);
+    r.y = (int)(unsigned)((b >> 32) & 0xffffu); // stride 0: raw buffer
+    r.z = (int)0xffffff00u;                     // num_records (bytes): everything a 32-bit offset can reach except the "invalid" marker
+    r.w = 0x00020000;                           // DATA_FORMAT = 32-bit (gfx9 family raw-buffer word 3)
+    return r;
+}
+
+// One LDS-DMA piece (64 lanes x 16 B -> 1 KiB at the wave-uniform LDS address) in buffer form: SGPR resource (base, huge range) +
+// wave-uniform byte offset + per-lane 32-bit offset.  Measured 5-10 % less wave time per request than the flat form
+// (tools/lds_dma_rate.hip: 108 vs 120 cycles), no 64-bit address arithmetic per request, and a lane whose offset is 0xffffffff is out
+// of range and lands ZEROS: no zero-page select for padding rows.  Issued from inline asm, so hipcc does not see the request: every
+// barrier that publishes its data is preceded by an explicit s_waitcnt vmcnt.  NT: non-temporal hint (rows read exactly once).
+template <bool NT = false> __device__ __forceinline__ void lds_dma_buf(const rsrc_t &rs, unsigned voff, unsigned soff, char *lds_dst) {
+    const unsigned lds = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char *)lds_dst;
+    if constexpr (NT)
+        asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen nt lds" ::"v"(voff), "s"(rs), "s"(soff), "s"(lds) : "memory");
+    else
+        asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds" ::"v"(voff), "s"(rs), "s"(soff), "s"(lds) : "memory");
+}
+
+// The same piece in flat form.  RAW = true issues it from inline asm: hipcc then does not know an LDS write is pending and inserts no
+// vmcnt wait of its own in front of later ds_reads — the three-slab schedule of conv3x3_halo_kernel orders every read behind an
+// explicit counted wait + barrier instead.  (With the builtin, the waitcnt pass tracks pending LDS-DMA per LDS object; once a few are
+// in flight it gives up counting and drains with vmcnt(0) before the first fragment read of a slab, which is exactly the in-flight
+// request the schedule relies on.)
+template <bool RAW> __device__ __forceinline__ void lds_dma16(const char *src, char *lds_dst) {
+    if constexpr (RAW) {
+        const unsigned lds = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char *)lds_dst;
+        asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(lds) : "memory");
+    } else {
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src, (__attribute__((address_space(3))) void *)lds_dst, 16, 0, 0);
+    }
+}
+
+// s_waitcnt vmcnt(n) for a wave-uniform runtime n (the instruction takes an immediate)
+__device__ __forceinline__ void wait_vmcnt(int n) {
+    switch (n) {
+    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+    case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
+    case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
+    case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
+    case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
+    case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
+    case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
+    case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
+    case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
+    case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
+    case 10: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
+    case 11: asm volatile("s_waitcnt vmcnt(11)" ::: "memory"); break;
+    case 12: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
+    case 13: asm volatile("s_waitcnt vmcnt(13)" ::: "memory"); break;
+    case 14: asm volatile("s_waitcnt vmcnt(14)" ::: "memory"); break;
+    case 15: asm volatile("s_waitcnt vmcnt(15)" ::: "memory"); break;
+    case 16: asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); break;
+    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+    }
+}
+
+// LDS-only barrier: waits for this wave's LDS traffic (lgkmcnt(0)), not for global loads/stores or LDS-DMA in flight.
+// The asm clobbers keep the compiler from moving LDS accesses across it (the s_barrier intrinsic alone is IntrNoMem).
+__device__ __forceinline__ void lds_barrier() {
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_waitcnt(0xc07f); // vmcnt = 63 (no wait), expcnt = 7, lgkmcnt = 0
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+}
+
+// one 16-byte operand fragment pair -> MFMA(s)
+__device__ __forceinline__ void mma_frag(const uint4 &wf, const uint4 &pf, floatx4 &acc, _Float16 *) {
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, wf), __builtin_bit_cast(half8, pf), acc, 0, 0, 0);
+}
+__device__ __forceinline__ void mma_frag(const uint4 &wf, const uint4 &pf, floatx4 &acc, float *) {
+    // lane (r, g) holds k = 4*(g + 4*khalf) + i, i = 0..3; MFMA #i contracts the i-th element of every
+    // lane group: k set {i, 4+i, 8+i, 12+i} (+16*khalf) — same k on both operands.
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__builtin_bit_cast(float, wf.x), __builtin_bit_cast(float, pf.x), acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__builtin_bit_cast(float, wf.y), __builtin_bit_cast(float, pf.y), acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__builtin_bit_cast(float, wf.z), __builtin_bit_cast(float, pf.z), acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__builtin_bit_cast(float, wf.w), __builtin_bit_cast(float, pf.w), acc, 0, 0, 0);
+}
+
+// NV consecutive channels of one pixel <-> fp32 registers, 16 bytes per access
+template <int NV> __device__ __forceinline__ void load_run(const _Float16 *p, float (&v)[NV]) {
+#pragma unroll
+    for (int i = 0; i < NV; i += 8) {
+        half8 h = *reinterpret_cast<const half8 *>(p + i);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[i + j] = (float)h[j];
+    }
+}
+template <int NV> __device__ __forceinline__ void load_run(const float *p, float (&v)[NV]) {
+#pragma unroll
+    for (int i = 0; i < NV; i += 4) {
+        float4 f = *reinterpret_cast<const float4 *>(p + i);
+        v[i] = f.x, v[i + 1] = f.y, v[i + 2] = f.z, v[i + 3] = f.w;
+    }
+}
+template <int NV> __device__ __forceinline__ void store_run(_Float16 *p, const float (&v)[NV]) {
+#pragma unroll
+    for (int i = 0; i < NV; i += 8) {
+        half8 h;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) h[j] = (_Float16)v[i + j];
+        *reinterpret_cast<half8 *>(p + i) = h;
+    }
+}
+template <int NV> __device__ __forceinline__ void store_run(float *p, const float (&v)[NV]) {
+#pragma unroll
+    for (int i = 0; i < NV; i += 4) *reinterpret_cast<float4 *>(p + i) = make_float4(v[i], v[i + 1], v[i + 2], v[i + 3]);
+}
+
+// eight fp32 values -> their split-fp16 halves (wtk_kernels.h, kSplitScale): hi = fp16(x), lo = fp16((x - hi) * 2^11)
+__device__ __forceinline__ void split_pack8(const float *v, half8 &hv, half8 &lv) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const _Float16 h = (_Float16)v[e];
+        hv[e] = h;
+        lv[e] = (_Float16)((v[e] - (float)h) * kSplitScale);
+    }
+}
+// store NV (8 or 16) consecutive channels starting at real channel c (multiple of NV) of one pixel; `pix` = the pixel's pseudo-channel 0
+template <int NV> __device__ __forceinline__ void wtk_split_store(_Float16 *pix, int c, const float (&v)[NV]) {
+    static_assert(NV % 8 == 0 && NV <= 32, "runs of 8 channels inside one 32-channel block");
+    _Float16 *p = pix + 64 * (c >> 5) + (c & 31);
+#pragma unroll
+    for (int i = 0; i < NV; i += 8) {
+        half8 hv, lv;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { // split_pack8 typed out: calling it here changes the code hipcc generates for 11 kernels (conv_sk, c32 split, stem, split igemm)
+            const _Float16 h = (_Float16)v[i + j];
+            hv[j] = h;
+            lv[j] = (_Float16)((v[i + j] - (float)h) * kSplitScale);
+        }
+        *reinterpret_cast<half8 *>(p + i) = hv;
+        *reinterpret_cast<half8 *>(p + 32 + i) = lv;
+    }
+}
+template <int NV> __device__ __forceinline__ void wtk_split_load(const _Float16 *pix, int c, float (&v)[NV]) {
+    static_assert(NV % 8 == 0 && NV <= 32, "runs of 8 channels inside one 32-channel block");
+    const _Float16 *p = pix + 64 * (c >> 5) + (c & 31);
+#pragma unroll
+    for (int i = 0; i < NV; i += 8) {
+        const half8 hv = *reinterpret_cast<const half8 *>(p + i), lv = *reinterpret_cast<const half8 *>(p + 32 + i);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[i + j] = wtk_split_value((float)hv[j], (float)lv[j]);
+    }
+}
+
+} // namespace wtk

@@ -113,34 +113,7 @@ constexpr float kSplitScale = 2048.0f, kSplitInv = 1.0f / 2048.0f;
 // two), so the single rounding of the fma is the rounding of the separate multiply + add this replaces — the same bits, one VALU op less per value
 // in epilogues that are VALU bound (-ffp-contract=off keeps the compiler from fusing on its own, hence the explicit builtin)
 __device__ __forceinline__ float wtk_split_value(float hi, float lo) { return __builtin_fmaf(lo, kSplitInv, hi); }
-typedef _Float16 wtk_h8 __attribute__((ext_vector_type(8)));
-// store NV (8 or 16) consecutive channels starting at real channel c (multiple of NV) of one pixel; `pix` = the pixel's pseudo-channel 0
-template <int NV> __device__ __forceinline__ void wtk_split_store(_Float16 *pix, int c, const float (&v)[NV]) {
-    static_assert(NV % 8 == 0 && NV <= 32, "runs of 8 channels inside one 32-channel block");
-    _Float16 *p = pix + 64 * (c >> 5) + (c & 31);
-#pragma unroll
-    for (int i = 0; i < NV; i += 8) {
-        wtk_h8 hv, lv;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const _Float16 h = (_Float16)v[i + j];
-            hv[j] = h;
-            lv[j] = (_Float16)((v[i + j] - (float)h) * kSplitScale);
-        }
-        *reinterpret_cast<wtk_h8 *>(p + i) = hv;
-        *reinterpret_cast<wtk_h8 *>(p + 32 + i) = lv;
-    }
-}
-template <int NV> __device__ __forceinline__ void wtk_split_load(const _Float16 *pix, int c, float (&v)[NV]) {
-    static_assert(NV % 8 == 0 && NV <= 32, "runs of 8 channels inside one 32-channel block");
-    const _Float16 *p = pix + 64 * (c >> 5) + (c & 31);
-#pragma unroll
-    for (int i = 0; i < NV; i += 8) {
-        const wtk_h8 hv = *reinterpret_cast<const wtk_h8 *>(p + i), lv = *reinterpret_cast<const wtk_h8 *>(p + 32 + i);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[i + j] = wtk_split_value((float)hv[j], (float)lv[j]);
-    }
-}
+// split_pack8 / wtk_split_store / wtk_split_load: wtk_device.h
 
 // ---------------------------------------------------------------------------------------------
 // Implicit-GEMM convolution (conv_igemm.hip).  Activations are NHWC; a tensor argument is a
