@@ -175,6 +175,14 @@ int wtk_yolo_debug_head(wtk_yolo *h, int32_t level, int32_t B, float *box_host, 
  * front is active) hold stale data. */
 int wtk_yolo_debug_tensor(wtk_yolo *h, int32_t conv_index, int32_t B, float *out_host, size_t out_cap,
                           int32_t *shape_hwc);
+/* ... and one index that names no conv: the live-tile counts of the last sparse forward pass (list form of the
+ * sparse Detect box towers), shape {1, 1, 4}: tiles listed for box.0, tiles listed for box.1 + box.2, and the
+ * grids of the two launches (the host's upper bounds of the counts).  Zeros where the handle never ran one. */
+#define WTK_DEBUG_SPARSE_COUNTS (-1)
+/* ... and conv_index = WTK_DEBUG_RAW(i): conv i as the last pass LEFT it.  Reading a Detect box-tower conv by its
+ * plain index first completes what a sparse pass skipped (dense launches over every pixel); the raw read does not,
+ * so after a sparse pass only the tiles under the survivors hold that pass's values.  (An involution: i <-> -2 - i.) */
+#define WTK_DEBUG_RAW(i) (-2 - (i))
 /* Run ONLY decode + selection on caller-provided head logits (HOST fp32, same layout as
  * wtk_yolo_debug_head, levels concatenated in anchor order) — isolates the NMS/argmax logic
  * from conv rounding for bit-exact index tests. */

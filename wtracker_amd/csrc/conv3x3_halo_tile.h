@@ -1,0 +1,744 @@
+// The body of one tile of the 3x3 window kernels of conv3x3_halo.hip, as text: included (twice, WTK_HALO_TILE_PART 1 then 2) into the body of
+// conv3x3_halo_kernel, whose block finds its tile from blockIdx.x, and of halo_list_kernel, whose block reads it from a device-side list.  Text and not a
+// __device__ function on purpose: with the body behind a call, even a force-inlined one, hipcc schedules and allocates every instantiation of
+// conv3x3_halo_kernel differently (tools/asm_kernel_diff.py); included, the kernel is token for token what it was.
+// The including body provides: T, BN, NHALO, MINW, NWB, HROWS, BMT, TAIL, SPLIT (template parameters or constants) and `a` (HaloArgs) before part 1 — the
+// compile-time constants, the LDS buffers and the thread indices; n0, o0, strip (first cout, first flat output, column strip of the tile; block-uniform ints)
+// and, in WTK_HALO_STAMPS builds, st_t0 before part 2 — everything else.
+#if WTK_HALO_TILE_PART == 1
+    constexpr int CE = Elem<T>::CE;
+    constexpr int CCH = 8 * CE; // channels per 128-byte chunk
+    // BN = 64: 8(P) x 1(C) waves of 32 px x 64 cout; BN = 128 / 192: 4(P) x 2(C) waves of 64 px x 64 / 96 cout
+    constexpr int WAVES_C = BN == 64 ? 1 : 2, WAVES_P = 8 / WAVES_C;
+    constexpr int WC = BN / WAVES_C;
+    constexpr int WP = BMT / WAVES_P, TP = WP / 16, TC = WC / 16, NV = 4 * TC;
+    constexpr int WR = BN / 64; // weight rows staged per thread per tap
+
+    constexpr int kHaloBytesT = HROWS * 128;
+    __shared__ __attribute__((aligned(16))) char halo0[kHaloBytesT];
+    __shared__ __attribute__((aligned(16))) char halo1[NHALO == 2 ? kHaloBytesT : 16];
+    static_assert(NWB == 2 || NWB == 3 || (NWB == 6 && NHALO == 2 && !TAIL && SPLIT), "slab ring: 2, 3 or 6 (split tiles, two window buffers, no fused tail)");
+    constexpr bool kRing = NWB >= 3; // counted waits, raw LDS-DMA requests
+    __shared__ __attribute__((aligned(16))) char wbuf0[NWB > 3 ? 16 : BN * 128];
+    __shared__ __attribute__((aligned(16))) char wbuf1[NWB > 3 ? 16 : BN * 128];
+    __shared__ __attribute__((aligned(16))) char wbuf2[NWB == 3 ? BN * 128 : 16];
+    __shared__ __attribute__((aligned(16))) char wring[NWB > 3 ? NWB * BN * 128 : 16]; // the six-slab ring: slot = global tap index % 6
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wave_p = wave / WAVES_C, wave_c = wave % WAVES_C;
+    const int lr = lane & 15, lg = lane >> 4;
+#elif WTK_HALO_TILE_PART == 2
+    const int xs = strip * a.S;
+    const int pitch = a.pitch;
+    const int halo_rows = BMT + 2 * pitch + 2;
+    const int halo_pieces = (halo_rows + 7) >> 3;
+    // piece offsets are 32-bit and relative to the first image the window touches
+    const int n_base = (int)fdiv(fdiv((unsigned)o0, a.d_pitch), a.d_h1);
+
+    const T *in = reinterpret_cast<const T *>(a.in) + (long long)n_base * a.H * a.W * a.in_ld + a.in_coff;
+    const T *wgt = reinterpret_cast<const T *>(a.w);
+
+    // ---- loop-invariant per-lane addressing (the inner loop must stay almost VALU-free: a wave64 VALU op
+    // costs ~4 issue cycles against 16 per MFMA, so a few dozen address instructions per tap starve the
+    // matrix pipe).
+    // Window pieces: wave w stages pieces w, w+8, ... (<= kMaxPiecesPerWave); the window geometry does not
+    // depend on the channel chunk, so each piece's per-lane byte offset inside the image is computed once.
+    constexpr int kMaxPiecesPerWave = (HROWS / 8 + 7) / 8;
+    unsigned hoff[kMaxPiecesPerWave];
+    unsigned hvalid;
+    halo_piece_offsets<T, kMaxPiecesPerWave>(a, o0, xs, n_base, halo_rows, wave, lane, hoff, hvalid);
+    const char *img = reinterpret_cast<const char *>(in);
+    auto issue_halo_piece = [&](char *buf, int q, int c) { // q static after unrolling
+        const int piece = wave + 8 * q;
+        if (piece >= halo_pieces) return; // wave-uniform
+        if constexpr (kRing && WTK_HALO_BUFFER_DMA) {
+            lds_dma_buf(make_rsrc(img), ((hvalid >> q) & 1u) ? hoff[q] : 0xffffffffu, (unsigned)(c * (CCH * (int)sizeof(T))), buf + piece * 1024);
+        } else {
+            const char *src = ((hvalid >> q) & 1u) ? img + (size_t)c * (CCH * sizeof(T)) + hoff[q] : zero_page;
+            lds_dma16<kRing>(src, buf + piece * 1024);
+        }
+    };
+    // Same, but never skipped (see the three-slab schedule below).  Pieces past the window rows carry zeros into unused
+    // rows; a piece index past the BUFFER (only the last q of the highest waves) re-requests the wave's previous piece.
+    auto issue_halo_piece_always = [&](char *buf, int q, int c) __attribute__((always_inline)) { // q static after unrolling
+        constexpr int kPieces = HROWS / 8;
+        static_assert(kPieces >= 16, "window buffer too small");
+        const bool back = q > 0 && wave + 8 * q >= kPieces; // wave-uniform
+        const int piece = back ? wave + 8 * (q - 1) : wave + 8 * q;
+        const unsigned off = back ? hoff[q > 0 ? q - 1 : 0] : hoff[q];
+        const bool ok = back ? ((hvalid >> (q > 0 ? q - 1 : 0)) & 1u) : ((hvalid >> q) & 1u);
+        if constexpr (kRing && WTK_HALO_BUFFER_DMA) {
+            lds_dma_buf(make_rsrc(img), ok ? off : 0xffffffffu, (unsigned)(c * (CCH * (int)sizeof(T))), buf + piece * 1024);
+        } else {
+            const char *src = ok ? img + (size_t)c * (CCH * sizeof(T)) + off : zero_page;
+            lds_dma16<kRing>(src, buf + piece * 1024);
+        }
+    };
+    // Weight slab of (tap, chunk c): rows = couts n0 .. n0+BN, 128 bytes each.  Uniform base + invariant
+    // per-lane 32-bit offset (lets the compiler use the SGPR-base form of global_load_lds).
+    const int wrow0 = tid >> 3, wp = tid & 7;
+    unsigned wvoff[WR];
+#pragma unroll
+    for (int i = 0; i < WR; ++i) {
+        const int row = wrow0 + 64 * i;
+        const int key = ((row >> 1) & 1) | (((row / NV) & 3) << 1);
+        wvoff[i] = (unsigned)(((long long)row * a.Kpad + (wp ^ key) * CE) * (long long)sizeof(T));
+    }
+    const char *wtile = reinterpret_cast<const char *>(wgt + (long long)n0 * a.Kpad);
+    auto issue_weights = [&](char *buf, int tap, int c) {
+        if constexpr (kRing && WTK_HALO_BUFFER_DMA) {
+            const rsrc_t rs = make_rsrc(wtile);
+            const unsigned so = (unsigned)((tap * a.Cin + c * CCH) * (int)sizeof(T)); // wave-uniform
+#pragma unroll
+            for (int i = 0; i < WR; ++i) lds_dma_buf(rs, wvoff[i], so, buf + (64 * i + 8 * wave) * 128);
+        } else {
+            const char *ub = wtile + ((size_t)tap * a.Cin + (size_t)c * CCH) * sizeof(T); // wave-uniform
+#pragma unroll
+            for (int i = 0; i < WR; ++i) lds_dma16<kRing>(ub + wvoff[i], buf + (64 * i + 8 * wave) * 128);
+        }
+    };
+
+    floatx4 acc[TC][TP];
+    floatx4 acc1[SPLIT ? TC : 1][SPLIT ? TP : 1]; // split mode: the 2^-11 cross terms
+#pragma unroll
+    for (int i = 0; i < TC; ++i)
+#pragma unroll
+        for (int j = 0; j < TP; ++j) {
+            acc[i][j] = (floatx4){0.f, 0.f, 0.f, 0.f};
+            if constexpr (SPLIT) acc1[i][j] = (floatx4){0.f, 0.f, 0.f, 0.f};
+        }
+
+    // weight fragments: row(i) = wave_c*64 + (lr>>2)*16 + 4*i + (lr&3); the swizzle key does not depend on
+    // i, so the four tiles are one base + immediates (i*512), and the second k-half is base ^ 64.
+    const int wrow_l = wave_c * WC + (lr >> 2) * NV + (lr & 3);
+    const int wkey_l = ((wrow_l >> 1) & 1) | (((wrow_l / NV) & 3) << 1);
+    const unsigned wfrag0 = wrow_l * 128 + ((lg ^ wkey_l) << 4);
+    const int prow0 = wave_p * WP + lr; // window row of this lane's pixel in tile 0 at tap (0,0)
+
+    auto compute_tap = [&](const char *halo, const char *wb, int tapoff) {
+        const int base = prow0 + tapoff;
+        const unsigned pfrag0 = base * 128 + ((lg ^ (base & 7)) << 4); // tiles j: + j*2048 (key unchanged)
+        if constexpr (SPLIT) { // k-half 0 = the hi halves of the row's 32 channels, k-half 1 = their lo halves
+            uint4 ph[TP], wh[TC], wl[TC], pl[TP];
+#pragma unroll
+            for (int j = 0; j < TP; ++j) ph[j] = *reinterpret_cast<const uint4 *>(halo + pfrag0 + j * 2048);
+#pragma unroll
+            for (int i = 0; i < TC; ++i) wh[i] = *reinterpret_cast<const uint4 *>(wb + wfrag0 + i * 512);
+#pragma unroll
+            for (int i = 0; i < TC; ++i) wl[i] = *reinterpret_cast<const uint4 *>(wb + (wfrag0 ^ 64u) + i * 512);
+#pragma unroll
+            for (int j = 0; j < TP; ++j) pl[j] = *reinterpret_cast<const uint4 *>(halo + (pfrag0 ^ 64u) + j * 2048);
+#pragma unroll
+            for (int i = 0; i < TC; ++i)
+#pragma unroll
+                for (int j = 0; j < TP; ++j) {
+                    mma_frag(wh[i], ph[j], acc[i][j], (T *)nullptr);
+                    mma_frag(wl[i], ph[j], acc1[i][j], (T *)nullptr);
+                }
+#pragma unroll
+            for (int i = 0; i < TC; ++i)
+#pragma unroll
+                for (int j = 0; j < TP; ++j) mma_frag(wh[i], pl[j], acc1[i][j], (T *)nullptr);
+            return;
+        }
+#pragma unroll
+        for (int kh2 = 0; kh2 < 2; ++kh2) {
+            const unsigned pa = kh2 ? (pfrag0 ^ 64u) : pfrag0;
+            const unsigned wa = kh2 ? (wfrag0 ^ 64u) : wfrag0;
+            uint4 pf[TP], wf[TC];
+#pragma unroll
+            for (int j = 0; j < TP; ++j) pf[j] = *reinterpret_cast<const uint4 *>(halo + pa + j * 2048);
+#pragma unroll
+            for (int i = 0; i < TC; ++i) wf[i] = *reinterpret_cast<const uint4 *>(wb + wa + i * 512);
+#pragma unroll
+            for (int i = 0; i < TC; ++i)
+#pragma unroll
+                for (int j = 0; j < TP; ++j) mma_frag(wf[i], pf[j], acc[i][j], (T *)nullptr);
+        }
+    };
+
+    // Six-slab ring (split tiles): the fragments of tap g + 1 are read from LDS BEFORE the MFMAs of tap g are issued, into the second of two register
+    // sets (g & 1): with one barrier per tap and all eight waves in step, the ds_read phase (8 waves x 10-12 b128 reads = 80-96 KB per tap through a
+    // 128 B/clk port) and the MFMA phase (two waves per SIMD) otherwise run one after the other.  Same MFMAs in the same order per accumulator.
+    constexpr int kFr = (NWB > 3 && SPLIT) ? 2 * TP + 2 * TC : 1;
+    uint4 fr[NWB > 3 ? 2 : 1][kFr];
+    auto load_frags = [&](uint4(&f)[kFr], const char *halo, const char *wb, int tapoff) __attribute__((always_inline)) {
+        if constexpr (NWB > 3 && SPLIT) {
+            const int base = prow0 + tapoff;
+            const unsigned pfrag0 = base * 128 + ((lg ^ (base & 7)) << 4);
+#pragma unroll
+            for (int j = 0; j < TP; ++j) f[j] = *reinterpret_cast<const uint4 *>(halo + pfrag0 + j * 2048);
+#pragma unroll
+            for (int i = 0; i < TC; ++i) f[2 * TP + i] = *reinterpret_cast<const uint4 *>(wb + wfrag0 + i * 512);
+#pragma unroll
+            for (int i = 0; i < TC; ++i) f[2 * TP + TC + i] = *reinterpret_cast<const uint4 *>(wb + (wfrag0 ^ 64u) + i * 512);
+#pragma unroll
+            for (int j = 0; j < TP; ++j) f[TP + j] = *reinterpret_cast<const uint4 *>(halo + (pfrag0 ^ 64u) + j * 2048);
+        }
+    };
+    auto mma_frags = [&](const uint4(&f)[kFr]) __attribute__((always_inline)) { // the order of compute_tap's split branch
+        if constexpr (NWB > 3 && SPLIT) {
+#pragma unroll
+            for (int i = 0; i < TC; ++i)
+#pragma unroll
+                for (int j = 0; j < TP; ++j) {
+                    mma_frag(f[2 * TP + i], f[j], acc[i][j], (T *)nullptr);
+                    mma_frag(f[2 * TP + TC + i], f[j], acc1[i][j], (T *)nullptr);
+                }
+#pragma unroll
+            for (int i = 0; i < TC; ++i)
+#pragma unroll
+                for (int j = 0; j < TP; ++j) mma_frag(f[2 * TP + i], f[TP + j], acc1[i][j], (T *)nullptr);
+        }
+    };
+
+    const int nchunks = a.Cin / CCH;
+    const int cb = n0 + wave_c * WC + lg * NV; // first of the NV consecutive couts this lane owns
+    // the accumulators start at the bias (rows exist up to CoutPad): no v_add per output value in the epilogue
+#pragma unroll
+    for (int i = 0; i < TC; ++i) {
+        const floatx4 b4 = (floatx4){a.bias[cb + i * 4 + 0], a.bias[cb + i * 4 + 1], a.bias[cb + i * 4 + 2], a.bias[cb + i * 4 + 3]};
+#pragma unroll
+        for (int j = 0; j < TP; ++j) acc[i][j] = b4;
+    }
+
+#ifdef WTK_HALO_STAMPS
+    const unsigned long long st_t1 = __builtin_amdgcn_s_memrealtime();
+#endif
+    // ---- prologue: whole window of chunk 0 + weights of tap 0 (and tap 1 with the three-slab ring)
+#pragma unroll
+    for (int q = 0; q < kMaxPiecesPerWave; ++q) issue_halo_piece(halo0, q, 0);
+    if constexpr (NWB > 3) { // six-slab ring: the slabs of taps 0..4 (a layer has at least 9 taps)
+#pragma unroll
+        for (int t0 = 0; t0 < NWB - 1; ++t0) issue_weights(wring + t0 * (BN * 128), t0, 0);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    } else {
+        issue_weights(wbuf0, 0, 0);
+        if (NWB == 3) {
+            issue_weights(wbuf1, 1, 0);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the raw requests are invisible to the compiler's own wait insertion
+        }
+    }
+    __syncthreads();
+    // The bias values above come from ordinary loads: without a use in front of the loop hipcc waits for them at their first use INSIDE it, and —
+    // not knowing how many raw LDS-DMA requests are younger — does so with a vmcnt(0) on every trip (found in the 64-cout x 128-pixel variants:
+    // one full drain per two chunks; tools/asm_loop_waits.py lists such waits).  Here the queue is empty anyway.
+#pragma unroll
+    for (int i = 0; i < TC; ++i)
+#pragma unroll
+        for (int j = 0; j < TP; ++j) asm volatile("" : "+v"(acc[i][j]));
+    if constexpr (NWB > 3) load_frags(fr[0], halo0, wring, 0);
+
+#ifdef WTK_HALO_TAP_STAMPS // diagnostic builds: per-wave cycle totals of (issue + ds_read + MFMA), vmcnt wait, barrier wait
+    unsigned long long tap_sum[3] = {0, 0, 0};
+    unsigned long long tap_prev = __builtin_amdgcn_s_memtime();
+    const unsigned long long clk_c0 = tap_prev, clk_r0 = __builtin_amdgcn_s_memrealtime(); // in-kernel clock = d(memtime) / d(memrealtime) x 100 MHz
+#endif
+    // one channel chunk = 9 taps.  CP = parity of the chunk: window in halo[CP].
+    // NWB == 2: tap t's weights in wbuf[(CP+t)&1], next tap's slab requested at the top of the tap, vmcnt(0) at its end.
+    // NWB == 3: tap t's weights in wbuf[t % 3] (9 taps per chunk keep the ring aligned), slab of tap t+2 requested at the
+    //           top of tap t, counted wait at its end: only the requests of THIS tap stay in flight across the barrier.
+    auto chunk_body = [&](auto cp_tag, int c) {
+        constexpr int CP = decltype(cp_tag)::value;
+        const char *hcur = (NHALO == 2 && CP == 1) ? halo1 : halo0;
+        char *hnext = (NHALO == 2 && CP == 0) ? halo1 : halo0;
+        const bool more = c + 1 < nchunks;
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+            if constexpr (NWB == 2) {
+                char *wnext = ((CP + tap) & 1) ? wbuf0 : wbuf1;
+                const char *wcur = ((CP + tap) & 1) ? wbuf1 : wbuf0;
+                if (tap < 8)
+                    issue_weights(wnext, tap + 1, c);
+                else if (more)
+                    issue_weights(wnext, 0, c + 1);
+                if (NHALO == 2 && more && tap < kMaxPiecesPerWave) // next chunk's window, one piece per wave per
+                    issue_halo_piece(hnext, tap, c + 1);           // tap, underneath the MFMAs
+                compute_tap(hcur, wcur, (tap / 3) * pitch + (tap % 3));
+                __syncthreads(); // vmcnt(0): everything issued above has landed; everyone is done reading wcur
+            } else if constexpr (NWB > 3) {
+                // Six-slab ring (64-cout split tiles: 2 x 54 + 6 x 8 = 156 KB).  The slab of global tap g = 9 c + tap lives in slot g % 6 = (3 CP + tap) % 6;
+                // tap g requests the slab of tap g + 5 into the slot tap g - 1 was read from, so a slab has four taps to arrive (the three-slab ring:
+                // one) and is there one tap BEFORE its tap: tap g reads the fragments of tap g + 1 first and multiplies its own — read during tap g - 1 —
+                // underneath.  The next chunk's window goes out two pieces per tap at taps 0..3: it has landed by the wait of tap 7, in front of the
+                // fragment reads of the next chunk's tap 0.  Write-after-read: the slot of tap g - 1 and the window of chunk c - 1 were last read one tap
+                // before their last tap, a barrier earlier than the first request into them.  Same taps in the same order: bit-identical.
+                constexpr int kSlab = BN * 128;
+                static_assert(kMaxPiecesPerWave <= 8, "window pieces are requested at taps 0..3, two per tap");
+                auto pcs = [](int t) constexpr { t = (t + 9) % 9; const int left = kMaxPiecesPerWave - 2 * t; return left < 0 ? 0 : (left > 2 ? 2 : left); };
+                const int par = (CP + tap) & 1; // parity of the global tap index (a constant once the tap loop is unrolled)
+                const char *wnext1 = wring + ((3 * CP + tap + 1) % NWB) * kSlab;
+                char *wnext5 = wring + ((3 * CP + tap + 5) % NWB) * kSlab;
+                if (tap < 8)
+                    load_frags(fr[par ^ 1], hcur, wnext1, ((tap + 1) / 3) * pitch + ((tap + 1) % 3));
+                else
+                    load_frags(fr[par ^ 1], hnext, wnext1, 0); // (last chunk: values nobody uses)
+                mma_frags(fr[par]);
+                if (tap < 4)
+                    issue_weights(wnext5, tap + 5, c);
+                else
+                    issue_weights(wnext5, tap - 4, more ? c + 1 : c); // last chunk: a slab nobody reads again (constant request count per tap)
+                if (2 * tap < kMaxPiecesPerWave) issue_halo_piece_always(hnext, 2 * tap, more ? c + 1 : c);
+                if (2 * tap + 1 < kMaxPiecesPerWave) issue_halo_piece_always(hnext, 2 * tap + 1, more ? c + 1 : c);
+                // landed after this wait: the slab of tap g + 2 (requested at tap g - 3) and everything older; in flight: the window pieces of tap g - 3
+                // and all requests of taps g - 2 .. g
+                constexpr int WRc = BN / 64;
+                const int in_flight = pcs(tap - 3) + (WRc + pcs(tap - 2)) + (WRc + pcs(tap - 1)) + (WRc + pcs(tap));
+                wait_vmcnt(in_flight);
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+                asm volatile("" ::: "memory");
+            } else {
+                const char *wcur = tap % 3 == 0 ? wbuf0 : (tap % 3 == 1 ? wbuf1 : wbuf2);
+                char *wnext2 = (tap + 2) % 3 == 0 ? wbuf0 : ((tap + 2) % 3 == 1 ? wbuf1 : wbuf2);
+                // The number of LDS-DMA instructions per tap is a compile-time constant (no branch around any of them):
+                // hipcc tracks pending LDS-DMA per LDS object and, when it cannot count the younger requests, puts a
+                // vmcnt(0) in front of the first fragment read of a slab — draining exactly what this schedule keeps
+                // in flight.  Where nothing is needed (last chunk: no next slab / no next window) a harmless duplicate
+                // is requested instead: a slab nobody reads again, or a window piece of the dead buffer.
+                const int issued = WR + ((NHALO == 2 && tap < kMaxPiecesPerWave) ? 1 : 0); // constant after unrolling
+                compute_tap(hcur, wcur, (tap / 3) * pitch + (tap % 3));
+                // The requests go out AFTER the tap's fragment reads and MFMAs have been issued: an LDS-DMA instruction costs
+                // 100-185 issue cycles next to ds_reads but far less in the quiet stretch before the barrier, where this wave
+                // would otherwise only wait for its SIMD neighbour (stamped: ~290 of ~1530 cycles per tap)
+                if (tap < 7)
+                    issue_weights(wnext2, tap + 2, c);
+                else
+                    issue_weights(wnext2, tap - 7, more ? c + 1 : c);
+                if (NHALO == 2 && tap < kMaxPiecesPerWave) issue_halo_piece_always(hnext, tap, more ? c + 1 : c); // tap is unrolled
+                // everything requested in EARLIER taps (next tap's slab, older window pieces) has landed; this tap's
+                // requests keep flying.  lgkmcnt(0): this wave's fragment reads of wcur / hcur are done.
+#ifdef WTK_HALO_TAP_STAMPS
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                const unsigned long long ts0 = __builtin_amdgcn_s_memtime();
+                wait_vmcnt(issued);
+                const unsigned long long ts1 = __builtin_amdgcn_s_memtime();
+                __builtin_amdgcn_s_barrier();
+                asm volatile("" ::: "memory");
+                const unsigned long long ts2 = __builtin_amdgcn_s_memtime();
+                tap_sum[0] += ts0 - tap_prev, tap_sum[1] += ts1 - ts0, tap_sum[2] += ts2 - ts1, tap_prev = ts2;
+#else
+                wait_vmcnt(issued);
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+                asm volatile("" ::: "memory");
+#endif
+                if constexpr (NHALO == 1) {
+                    // ONE window buffer and more than one chunk (the two-blocks-per-CU form of the split kernel): the next chunk's window is requested when
+                    // everybody is done with this one, and waited for on the spot — the OTHER block of the CU is what runs meanwhile
+                    if (tap == 8 && more) {
+#pragma unroll
+                        for (int q = 0; q < kMaxPiecesPerWave; ++q) issue_halo_piece(halo0, q, c + 1);
+                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                        __builtin_amdgcn_s_barrier();
+                        asm volatile("" ::: "memory");
+                    }
+                }
+            }
+        }
+    };
+    for (int c = 0; c < nchunks; c += 2) {
+        chunk_body(std::integral_constant<int, 0>{}, c);
+        if (c + 1 < nchunks) chunk_body(std::integral_constant<int, 1>{}, c + 1);
+    }
+
+#ifdef WTK_HALO_TAP_STAMPS
+    if (lane == 0 && a.dbg_stamps)
+    {
+        for (int i = 0; i < 3; ++i) a.dbg_stamps[((long long)blockIdx.x * 8 + wave) * 4 + i] = tap_sum[i];
+        const unsigned long long dc = __builtin_amdgcn_s_memtime() - clk_c0, dr = __builtin_amdgcn_s_memrealtime() - clk_r0;
+        a.dbg_stamps[((long long)blockIdx.x * 8 + wave) * 4 + 3] = (dc << 24) | (dr & 0xffffff);
+    }
+#endif
+#ifdef WTK_HALO_STAMPS
+    const unsigned long long st_t2 = __builtin_amdgcn_s_memrealtime();
+    struct StampOnExit {
+        unsigned long long *p, t0, t1, t2;
+        bool on;
+        __device__ ~StampOnExit() {
+            if (on) p[0] = t0, p[1] = t1, p[2] = t2, p[3] = __builtin_amdgcn_s_memrealtime();
+        }
+    } stamp_on_exit{a.dbg_stamps + ((long long)blockIdx.x * 8 + wave) * 4, st_t0, st_t1, st_t2, a.dbg_stamps != nullptr && lane == 0};
+#endif
+    // ---- epilogue (the bias is already inside the accumulators).  Output pixels: one evaluation per lane, fetched per pixel tile
+    // (before any lane leaves: ds_bpermute reads from active lanes only)
+    int pix_e, col_e;
+    halo_out_pixel(a, o0 + wave_p * WP, xs, lane, pix_e, col_e);
+    int pixj[TAIL ? 1 : TP], colj[TAIL ? 1 : TP]; // the fused-tail variants have no padded couts: they fetch inside their loops
+    if constexpr (!TAIL) {
+#pragma unroll
+        for (int j = 0; j < TP; ++j) pixj[j] = lane_fetch(j * 16 + lr, pix_e), colj[j] = lane_fetch(j * 16 + lr, col_e);
+    }
+    if (cb + NV > a.Cout) return;
+    // ---- fused 1x1 tail (fp16, 64-cout tile: the wave owns ALL 64 output channels of its pixels).  The Detect box tower's
+    // last conv (1x1, 64 -> 64, no activation) consumes this conv's output and nothing else does: instead of writing the
+    // 64-channel tensor and launching a second kernel that reads it back, the SiLU'd fp16 values go to a wave-local LDS tile
+    // (the window buffer is free after the last tap's barrier) and are multiplied by the 1x1 weights right here.  Same fp16
+    // rounding of the intermediate, same K order (two 32-deep steps), same MFMA: bit-identical to the two-kernel path.
+    if constexpr (TAIL && SPLIT && BN == 128) {
+        // ---- split-fp16 form of the 128-cout tail (f16x3 handles, Detect class towers: 3x3 128 -> 128, then 1x1 128 -> nc stored as 32 padded
+        // couts, fp32 logits).  A wave holds 64 pixels x ONE HALF of the channels; every wave writes its SiLU'd values as split rows — per pixel and
+        // block of 32 channels one 128-byte row [hi32 | lo32], 2 x WP rows = 16 KB per wave — into a tile of its own, the two cout-waves of a pixel
+        // group meet at one block barrier, and each then multiplies HALF of the group's pixels over all four channel blocks (blocks 0, 1 from the
+        // low-channel wave's tile, 2, 3 from the high-channel one: the K order of the stand-alone split 1x1, per block hi.hi into acc2, lo.hi then
+        // hi.lo into acc2l, value = acc2 + 2^-11 acc2l: bit-identical to the two-kernel path).  The eight tiles (128 KB) take both window buffers
+        // (three each) and two of the three slab buffers — all free once the last tap's requests have landed (the last taps re-request a slab nobody
+        // reads: it must not land on a tile, hence the drain in front of the first store).
+        static_assert(WAVES_C == 2 && TC == 4 && TP % 2 == 0 && NHALO == 2 && NWB == 3 && kHaloBytesT >= 3 * 2 * WP * 128 && BN * 128 >= 2 * WP * 128,
+                      "split class-tower tail: 4 x 2 waves, three tiles per window buffer, one per slab buffer");
+        constexpr int kTile = 2 * WP * 128; // bytes of one wave's tile: rows blk * WP + p
+        auto tile_of = [&](int w) __attribute__((always_inline)) -> char * {
+            return w < 3 ? halo0 + w * kTile : (w < 6 ? halo1 + (w - 3) * kTile : (w == 6 ? wbuf0 : wbuf1));
+        };
+        const _Float16 *w2 = reinterpret_cast<const _Float16 *>(a.tail_w);
+        const int arow = (lr >> 2) * 8 + (lr & 3); // + 4i: the lane ends up owning couts lg*8 .. lg*8+7 of the 32 stored ones
+        half8 wh2[4][2], wl2[4][2];                // A fragments straight from global memory (16 KB of weights, L2 resident); requested first, used last
+#pragma unroll
+        for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const _Float16 *wr = w2 + (long long)(arow + 4 * i) * a.tail_kpad + kb * 64 + lg * 8;
+                wh2[kb][i] = *reinterpret_cast<const half8 *>(wr);
+                wl2[kb][i] = *reinterpret_cast<const half8 *>(wr + 32);
+            }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // (also the weight fragments above: a few hundred cycles, once per block)
+        __builtin_amdgcn_s_barrier();                     // every wave's requests have landed, every wave is past its last fragment read
+        asm volatile("" ::: "memory");
+        {
+            char *mine = tile_of(wave) + (lg >> 1) * (WP * 128); // this lane's 16 couts lie in block lg / 2 of the wave's two, channels 16 (lg & 1) .. + 15 of it
+#pragma unroll
+            for (int j = 0; j < TP; ++j) {
+                const int p = j * 16 + lr;
+                float v[NV];
+#pragma unroll
+                for (int i = 0; i < TC; ++i)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v[i * 4 + r] = wtk_split_value(acc[i][j][r], acc1[i][j][r]);
+                if (a.act) wtk_silu_scaled_run<NV>(v);
+#pragma unroll
+                for (int c2 = 0; c2 < 2; ++c2) {
+                    half8 hv, lv;
+                    split_pack8(v + c2 * 8, hv, lv);
+                    const int c = 2 * (lg & 1) + c2; // chunk of the hi halves; the lo halves: + 4
+                    *reinterpret_cast<half8 *>(mine + p * 128 + ((c ^ (p & 7)) << 4)) = hv;
+                    *reinterpret_cast<half8 *>(mine + p * 128 + (((c + 4) ^ (p & 7)) << 4)) = lv;
+                }
+            }
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        constexpr int TPH = TP / 2; // pixel tiles of the group this wave finishes
+        floatx4 acc2[2][TPH], acc2l[2][TPH];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const floatx4 b4 = tail_bias4(a, lg * 8 + i * 4);
+#pragma unroll
+            for (int j = 0; j < TPH; ++j) acc2[i][j] = b4, acc2l[i][j] = (floatx4){0.f, 0.f, 0.f, 0.f};
+        }
+#pragma unroll
+        for (int kb = 0; kb < 4; ++kb) {
+            const char *src = tile_of(wave_p * 2 + (kb >> 1)) + (kb & 1) * (WP * 128); // channels 0..63 of the group from the low-channel wave, 64..127 from the other
+#pragma unroll
+            for (int j = 0; j < TPH; ++j) {
+                const int p = (wave_c * TPH + j) * 16 + lr;
+                const half8 ph = *reinterpret_cast<const half8 *>(src + p * 128 + ((lg ^ (p & 7)) << 4));
+                const half8 pl = *reinterpret_cast<const half8 *>(src + p * 128 + (((lg + 4) ^ (p & 7)) << 4));
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    acc2[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh2[kb][i], ph, acc2[i][j], 0, 0, 0);
+                    acc2l[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl2[kb][i], ph, acc2l[i][j], 0, 0, 0);
+                }
+#pragma unroll
+                for (int i = 0; i < 2; ++i) acc2l[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh2[kb][i], pl, acc2l[i][j], 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < TPH; ++j) {
+            const long long pix = lane_fetch((wave_c * TPH + j) * 16 + lr, pix_e);
+            if (pix < 0) continue;
+            float v2[8];
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v2[i * 4 + r] = wtk_split_value(acc2[i][j][r], acc2l[i][j][r]);
+            if (lg * 8 < a.tail_cout) tail_store<true>(a, pix, lg, v2); // padded couts are never stored; the class logits are an fp32 tensor (launch check)
+        }
+        return;
+    } else if constexpr (TAIL && SPLIT) {
+        // ---- split-fp16 form of the 64-cout tail (f16x3 handles, Detect box towers): the wave's SiLU'd values go to LDS as split rows — one 128-byte
+        // row [hi32 | lo32] per pixel and block of 32 channels, block 0 in the first window buffer, block 1 in the second (both free after the last tap's
+        // barrier), wave-local — and are multiplied by the split 1x1 weights as conv_igemm_kernel's split form does: two K steps (the blocks), per step
+        // hi.hi into acc2, lo.hi then hi.lo into acc2l, value = acc2 + 2^-11 acc2l: bit-identical to the two-kernel path.
+        static_assert(BN == 64 && TC == 4 && NHALO == 2, "split fused tail: 64 couts per wave, two window buffers");
+        char *tile0 = halo0 + wave * (WP * 128), *tile1 = halo1 + wave * (WP * 128);
+        const _Float16 *w2 = reinterpret_cast<const _Float16 *>(a.tail_w);
+        const int arow = (lr >> 2) * 16 + (lr & 3); // + 4i: cout row of A fragment tile i (the lane ends up owning couts lg*16 .. lg*16+15)
+        half8 wh2[2][4], wl2[2][4]; // A fragments straight from global memory (16 KB of weights, L2 resident); requested first, used last
+#pragma unroll
+        for (int blk = 0; blk < 2; ++blk)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const _Float16 *wr = w2 + (long long)(arow + 4 * i) * a.tail_kpad + blk * 64 + lg * 8;
+                wh2[blk][i] = *reinterpret_cast<const half8 *>(wr);
+                wl2[blk][i] = *reinterpret_cast<const half8 *>(wr + 32);
+            }
+        {
+            char *mine = (lg >> 1) ? tile1 : tile0; // this lane's 16 couts lie in block lg / 2, channels 16 (lg & 1) .. + 15 of it
+#pragma unroll
+            for (int j = 0; j < TP; ++j) {
+                const int p = j * 16 + lr;
+                float v[NV];
+#pragma unroll
+                for (int i = 0; i < TC; ++i)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v[i * 4 + r] = wtk_split_value(acc[i][j][r], acc1[i][j][r]);
+                if (a.act) wtk_silu_scaled_run<NV>(v);
+#pragma unroll
+                for (int c2 = 0; c2 < 2; ++c2) {
+                    half8 hv, lv;
+                    split_pack8(v + c2 * 8, hv, lv);
+                    const int c = 2 * (lg & 1) + c2; // chunk of the hi halves; the lo halves: + 4
+                    *reinterpret_cast<half8 *>(mine + p * 128 + ((c ^ (p & 7)) << 4)) = hv;
+                    *reinterpret_cast<half8 *>(mine + p * 128 + (((c + 4) ^ (p & 7)) << 4)) = lv;
+                }
+            }
+        }
+        // the rows of a pixel come from all four lane groups of this wave: its LDS operations execute in order, no barrier
+        floatx4 acc2[4][TP], acc2l[4][TP];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const floatx4 b4 = tail_bias4(a, lg * 16 + i * 4);
+#pragma unroll
+            for (int j = 0; j < TP; ++j) acc2[i][j] = b4, acc2l[i][j] = (floatx4){0.f, 0.f, 0.f, 0.f};
+        }
+#pragma unroll
+        for (int blk = 0; blk < 2; ++blk) {
+            const char *tile = blk ? tile1 : tile0;
+#pragma unroll
+            for (int j = 0; j < TP; ++j) {
+                const int p = j * 16 + lr;
+                const half8 ph = *reinterpret_cast<const half8 *>(tile + p * 128 + ((lg ^ (p & 7)) << 4));
+                const half8 pl = *reinterpret_cast<const half8 *>(tile + p * 128 + (((lg + 4) ^ (p & 7)) << 4));
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    acc2[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh2[blk][i], ph, acc2[i][j], 0, 0, 0);
+                    acc2l[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl2[blk][i], ph, acc2l[i][j], 0, 0, 0);
+                }
+#pragma unroll
+                for (int i = 0; i < 4; ++i) acc2l[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh2[blk][i], pl, acc2l[i][j], 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < TP; ++j) {
+            const long long pix = lane_fetch(j * 16 + lr, pix_e);
+            if (pix < 0) continue;
+            float v2[16];
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v2[i * 4 + r] = wtk_split_value(acc2[i][j][r], acc2l[i][j][r]);
+            if (a.tail_f32) // tail_store typed out: calling it here changes the code hipcc generates for this branch's two kernels
+                store_run<16>(reinterpret_cast<float *>(a.tail_out) + pix * a.tail_ld + a.tail_coff + lg * 16, v2); // head logits stay fp32
+            else
+                wtk_split_store<16>(reinterpret_cast<_Float16 *>(a.tail_out) + pix * a.tail_ld + a.tail_coff, lg * 16, v2);
+        }
+        return;
+    } else if constexpr (TAIL && BN == 128) {
+        // ---- 128-cout tile (the Detect class tower: 3x3 128 -> 128, then 1x1 128 -> nc stored as 32 padded channels).  A wave
+        // holds 64 pixels x ONE HALF of the channels, so the two cout-waves of a pixel group exchange through LDS: both write
+        // their SiLU'd fp16 tile (64 px x 64 ch), one block barrier, then each of them multiplies HALF of the group's pixels over
+        // all 128 channels — k-steps 0,1 from the low-channel tile, 2,3 from the high-channel tile: the K order of the stand-alone
+        // 1x1 kernel, so the result is bit-identical.  Both window buffers are free after the last tap's barrier.
+        static_assert(sizeof(T) == 2 && WAVES_C == 2 && TC == 4 && TP % 2 == 0, "fused class-tower tail: fp16, 4 x 2 waves");
+        const _Float16 *w2 = reinterpret_cast<const _Float16 *>(a.tail_w);
+        const int arow = (lr >> 2) * 8 + (lr & 3); // + 4i: the lane ends up owning couts lg*8 .. lg*8+7 of the 32 stored ones
+        half8 wf2[4][2];                           // A fragments straight from global memory (8 KB of weights); requested first, used last
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+            for (int i = 0; i < 2; ++i) wf2[ks][i] = *reinterpret_cast<const half8 *>(w2 + (long long)(arow + 4 * i) * a.tail_kpad + ks * 32 + lg * 8);
+        auto tile_of = [&](int w) __attribute__((always_inline)) -> char * { return (w < 4 ? halo0 : halo1) + (w & 3) * (WP * 128); };
+        char *mine = tile_of(wave);
+#pragma unroll
+        for (int j = 0; j < TP; ++j) {
+            const int p = j * 16 + lr;
+#pragma unroll
+            for (int c2 = 0; c2 < 2; ++c2) {
+                half8 hv;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const int idx = c2 * 8 + e;
+                    const float x = acc[idx >> 2][j][idx & 3];
+                    hv[e] = (_Float16)(a.act ? wtk_silu_scaled(x) : x);
+                }
+                const int c = 2 * lg + c2;
+                *reinterpret_cast<half8 *>(mine + p * 128 + ((c ^ (p & 7)) << 4)) = hv;
+            }
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        constexpr int TPH = TP / 2; // pixel tiles of the group this wave finishes
+        floatx4 acc2[2][TPH];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const floatx4 b4 = tail_bias4(a, lg * 8 + i * 4);
+#pragma unroll
+            for (int j = 0; j < TPH; ++j) acc2[i][j] = b4;
+        }
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+            const char *src = tile_of(wave_p * 2 + (ks >> 1)); // channels 0..63 of the group, then 64..127
+#pragma unroll
+            for (int j = 0; j < TPH; ++j) {
+                const int p = (wave_c * TPH + j) * 16 + lr;
+                const half8 pf = *reinterpret_cast<const half8 *>(src + p * 128 + ((((ks & 1) * 4 + lg) ^ (p & 7)) << 4));
+#pragma unroll
+                for (int i = 0; i < 2; ++i) acc2[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf2[ks][i], pf, acc2[i][j], 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < TPH; ++j) {
+            const long long pix = lane_fetch((wave_c * TPH + j) * 16 + lr, pix_e);
+            if (pix < 0) continue;
+            float v2[8];
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v2[i * 4 + r] = acc2[i][j][r];
+            if (lg * 8 < a.tail_cout) tail_store<false>(a, pix, lg, v2); // padded couts are never stored
+        }
+        return;
+    } else if constexpr (TAIL) {
+        static_assert(!TAIL || (BN == 64 && sizeof(T) == 2), "fused tail: fp16, 64- or 128-cout tile");
+        {
+            static_assert(BN != 64 || TC == 4, "64 couts per wave");
+            char *tile = halo0 + wave * (WP * 128); // WP rows of 128 B: 64 channels of the wave's pixels
+            const _Float16 *w2 = reinterpret_cast<const _Float16 *>(a.tail_w);
+            const int arow = (lr >> 2) * 16 + (lr & 3); // + 4i: cout row of A fragment tile i (same permutation as above)
+            half8 wf2[2][4]; // A fragments straight from global memory (8 KB of weights, L2 resident); requested first, used last
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) wf2[ks][i] = *reinterpret_cast<const half8 *>(w2 + (long long)(arow + 4 * i) * a.tail_kpad + ks * 32 + lg * 8);
+#pragma unroll
+            for (int j = 0; j < TP; ++j) {
+                const int p = j * 16 + lr; // row of the wave's tile
+#pragma unroll
+                for (int c2 = 0; c2 < 2; ++c2) {
+                    half8 hv;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        const int idx = c2 * 8 + e;
+                        const float x = acc[idx >> 2][j][idx & 3];
+                        hv[e] = (_Float16)(a.act ? wtk_silu_scaled(x) : x);
+                    }
+                    const int c = 2 * lg + c2;
+                    *reinterpret_cast<half8 *>(tile + p * 128 + ((c ^ (p & 7)) << 4)) = hv;
+                }
+            }
+            // the first conv's accumulators are dead now: the second set starts at the tail's bias
+            floatx4 acc2[4][TP];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const floatx4 b4 = tail_bias4(a, lg * 16 + i * 4);
+#pragma unroll
+                for (int j = 0; j < TP; ++j) acc2[i][j] = b4;
+            }
+            // wave-local tile: a wave's LDS operations execute in order, no barrier
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+                for (int j = 0; j < TP; ++j) {
+                    const int p = j * 16 + lr;
+                    const half8 pf = *reinterpret_cast<const half8 *>(tile + p * 128 + (((ks * 4 + lg) ^ (p & 7)) << 4));
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) acc2[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf2[ks][i], pf, acc2[i][j], 0, 0, 0);
+                }
+#pragma unroll
+            for (int j = 0; j < TP; ++j) {
+                const long long pix = lane_fetch(j * 16 + lr, pix_e);
+                if (pix < 0) continue;
+                float v2[16];
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v2[i * 4 + r] = acc2[i][j][r];
+                tail_store<false>(a, pix, lg, v2);
+            }
+            return;
+        }
+    }
+    T *out = reinterpret_cast<T *>(a.out);
+    T *out2 = reinterpret_cast<T *>(a.out2);
+    const T *res = reinterpret_cast<const T *>(a.res);
+    // the residual of all pixel tiles is requested before any arithmetic (junk pixels read pixel 0): one exposed memory latency
+    // per block instead of TP (variants with a 256-register budget only)
+    constexpr bool kHoistRes = MINW <= 2 && sizeof(T) == 2 && BN != 192 && !TAIL && !SPLIT; // raw fp16 values: 8 VGPRs per pixel tile
+    half8 rres[kHoistRes ? TP : 1][kHoistRes ? NV / 8 : 1];
+    if constexpr (kHoistRes) {
+        if (res) {
+#pragma unroll
+            for (int j = 0; j < TP; ++j) {
+                const long long pr = pixj[j];
+                const T *rp = res + (pr < 0 ? 0 : pr) * a.res_ld + a.res_coff + cb;
+#pragma unroll
+                for (int q = 0; q < NV / 8; ++q) rres[j][q] = *reinterpret_cast<const half8 *>(rp + 8 * q);
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < TP; ++j) {
+        const long long pix = pixj[TAIL ? 0 : j];
+        const int col = colj[TAIL ? 0 : j];
+        if (pix < 0) continue;
+        float v[NV];
+#pragma unroll
+        for (int i = 0; i < TC; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                if constexpr (SPLIT)
+                    v[i * 4 + r] = wtk_split_value(acc[i][j][r], acc1[i][j][r]);
+                else
+                    v[i * 4 + r] = acc[i][j][r];
+            }
+        if (a.act) {
+            wtk_silu_scaled_run<NV>(v);
+        }
+        if (res) {
+            if constexpr (kHoistRes) {
+#pragma unroll
+                for (int i = 0; i < NV; ++i) v[i] += (float)rres[j][i >> 3][i & 7];
+            } else {
+                float rv[NV];
+                if constexpr (SPLIT)
+                    wtk_split_load<NV>(reinterpret_cast<const _Float16 *>(a.res) + pix * a.res_ld + a.res_coff, cb, rv);
+                else
+                    load_run<NV>(res + pix * a.res_ld + a.res_coff + cb, rv);
+#pragma unroll
+                for (int i = 0; i < NV; ++i) v[i] += rv[i];
+            }
+        }
+        if constexpr (SPLIT)
+            wtk_split_store<NV>(reinterpret_cast<_Float16 *>(a.out) + pix * a.out_ld + a.out_coff, cb, v);
+        else
+            store_run<NV>(out + pix * a.out_ld + a.out_coff + cb, v);
+        if (out2) { // 2x nearest upsample: pixel (n, 2y+dy, 2X+dx) of the [2H][2W] map = 4*pix - 2X + 2W*dy + dx
+            const int W2 = a.W * 2;
+#pragma unroll
+            for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+                for (int dx = 0; dx < 2; ++dx) {
+                    const long long pix2 = 4 * pix - 2 * col + W2 * dy + dx;
+                    if constexpr (SPLIT)
+                        wtk_split_store<NV>(reinterpret_cast<_Float16 *>(a.out2) + pix2 * a.out2_ld + a.out2_coff, cb, v);
+                    else
+                        store_run<NV>(out2 + pix2 * a.out2_ld + a.out2_coff + cb, v);
+                }
+        }
+    }
+#endif
+#undef WTK_HALO_TILE_PART

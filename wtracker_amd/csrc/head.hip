@@ -200,11 +200,14 @@ __global__ __launch_bounds__(1024) void head_select_kernel_sparse(const HeadSpar
     float best, best_l, second;
     int best_i;
     if (!head_scan<T>(a, n, best, best_i, best_l, second)) return;
-    if (threadIdx.x != 0) return;
-    if (a.out_margin) a.out_margin[n] = fminf(best_l - second, fabsf(best_l - a.conf_logit));
+    const int lane = threadIdx.x; // the first wave, every lane with the frame's result: lane 0 writes it, lanes 0 .. 8 mark one pixel of the 3 x 3 neighbourhood each
+    if (lane >= 9) return;
     const bool keep = (best_i != 0x7fffffff) && (best > a.conf);
-    q.sel_anchor[n] = keep ? best_i : -1;
-    q.sel_score[n] = best;
+    if (lane == 0) {
+        if (a.out_margin) a.out_margin[n] = fminf(best_l - second, fabsf(best_l - a.conf_logit));
+        q.sel_anchor[n] = keep ? best_i : -1;
+        q.sel_score[n] = best;
+    }
     if (!keep || (q.n_dyn && n >= *q.n_dyn)) return;
     // what the box tower of the survivor's level must compute for this frame.  Flat output index of pixel (y, x) of image n in the stacked geometry:
     // strip s = x / S, o = (n (H + 1) + y) pitch + (x - s S); unit o / 128 of strip s
@@ -214,15 +217,25 @@ __global__ __launch_bounds__(1024) void head_select_kernel_sparse(const HeadSpar
     const int H = a.lh[lvl], W = a.lw[lvl], S = q.S[lvl], pitch = q.pitch[lvl], ld = q.ld[lvl];
     const int y = j / W, x = j % W;
     unsigned char *live0 = q.live + q.off0[lvl], *live1 = q.live + q.off1[lvl];
-    for (int dy = -1; dy <= 1; ++dy)
-        for (int dx = -1; dx <= 1; ++dx) {
-            const int yy = y + dy, xx = x + dx;
-            if (yy < 0 || yy >= H || xx < 0 || xx >= W) continue; // padding: no pixel of box.0 behind it
-            const int s = xx / S;
-            const int u = s * ld + (((n * (H + 1) + yy) * pitch + (xx - s * S)) >> 7);
-            live0[u] = 1;
-            if (dy == 0 && dx == 0) live1[u] = 1;
+    // list form: whoever turns a unit's byte from 0 to 1 lists its tile (each unit once; the ORDER of a list depends on the blocks' arrival, the set of tiles
+    // and what they compute do not)
+    auto mark = [&](unsigned char *live, int stage, int s, int r) __attribute__((always_inline)) {
+        const unsigned u = (unsigned)(s * ld + r);
+        if (!q.list[0]) {
+            live[u] = 1;
+            return;
         }
+        const unsigned bit = 1u << ((u & 3u) * 8);
+        if (atomicOr(reinterpret_cast<unsigned *>(live + (u & ~3u)), bit) & bit) return;
+        const unsigned i = atomicAdd(q.count + stage, 1u);
+        if (i < q.cap[stage]) q.list[stage][i] = (unsigned)lvl << 30 | (unsigned)s << kHaloListUnitBits | (unsigned)r;
+    };
+    const int yy = y + lane / 3 - 1, xx = x + lane % 3 - 1;
+    if (yy < 0 || yy >= H || xx < 0 || xx >= W) return; // padding: no pixel of box.0 behind it
+    const int s = xx / S;
+    const int r = ((n * (H + 1) + yy) * pitch + (xx - s * S)) >> 7;
+    mark(live0, 0, s, r);
+    if (lane == 4) mark(live1, 1, s, r);
 }
 
 // one wave per frame
@@ -230,6 +243,24 @@ template <typename T>
 __global__ __launch_bounds__(64) void head_decode_kernel(const HeadSparseArgs q) {
     const int n = blockIdx.x;
     const int best_i = q.sel_anchor[n];
+    if (q.list[0]) { // list form: the mask and the counters go back to zero for the next call (this kernel runs behind both tower stages)
+        const HeadArgs &a = q.h;
+        const int lane = threadIdx.x;
+        if (best_i >= 0 && lane < 9) { // the units head_select_kernel_sparse marked for this frame (a frame beyond *n_dyn marked none: it clears clear bytes)
+            const int A0 = a.lh[0] * a.lw[0], A1 = a.lh[1] * a.lw[1];
+            const int lvl = best_i < A0 ? 0 : (best_i < A0 + A1 ? 1 : 2);
+            const int j = best_i - (lvl == 0 ? 0 : (lvl == 1 ? A0 : A0 + A1));
+            const int H = a.lh[lvl], W = a.lw[lvl], S = q.S[lvl], pitch = q.pitch[lvl], ld = q.ld[lvl];
+            const int yy = j / W + lane / 3 - 1, xx = j % W + lane % 3 - 1;
+            if (yy >= 0 && yy < H && xx >= 0 && xx < W) {
+                const int s = xx / S;
+                const int u = s * ld + (((n * (H + 1) + yy) * pitch + (xx - s * S)) >> 7);
+                q.live[q.off0[lvl] + u] = 0;
+                if (lane == 4) q.live[q.off1[lvl] + u] = 0;
+            }
+        }
+        if (n == 0 && lane < 2) q.count[2 + lane] = q.count[lane], q.count[lane] = 0;
+    }
     head_row<T>(q.h, n, best_i >= 0, best_i, q.sel_score[n]);
 }
 
@@ -403,6 +434,9 @@ hipError_t launch_head_nms(const NmsArgs &a, int is_f16, hipStream_t stream) {
 // the Detect outputs are fp32 tensors in every mode
 hipError_t launch_head_select_sparse(const HeadSparseArgs &a, hipStream_t stream) {
     if (a.h.N <= 0 || a.h.nc < 1 || a.h.cls_ld < a.h.nc || !a.live || !a.sel_anchor || !a.sel_score) return hipErrorInvalidValue;
+    if ((reinterpret_cast<uintptr_t>(a.live) & 3u) || (a.list[0] && (!a.list[1] || !a.count))) return hipErrorInvalidValue;
+    for (int l = 0; l < 3; ++l)
+        if (a.list[0] && ((a.off0[l] | a.off1[l]) & 3u)) return hipErrorInvalidValue;
     hipLaunchKernelGGL((head_select_kernel_sparse<float>), dim3(a.h.N), dim3(1024), 0, stream, a);
     return hipGetLastError();
 }

@@ -192,6 +192,13 @@ struct wtk_yolo {
         int op0 = -1, box1 = -1, box2 = -1;
     } det[3];
     size_t live_bytes = 0; // 0: this handle never runs sparse
+    // List form (the default; WTK_SPARSE_LIST=0: the masked form, one full-grid launch per level and stage behind a cleared mask).  Behind the mask's live_mask_bytes
+    // in the same region: four counters (HeadSparseArgs::count), then the two stages' tile lists of live_list_cap[] entries, sized like the mask for max_batch.
+    int use_sparse_list = 1;
+    int sparse_min_tenths = 0; // threshold of sparse_box_pays (below) for this handle's calls, in tenths of a round
+    size_t live_mask_bytes = 0;
+    unsigned live_list_cap[2] = {0, 0};
+    unsigned sparse_grid[2] = {0, 0}; // grids of the two list launches of the last list-form sparse pass (wtk_yolo_debug_tensor: WTK_DEBUG_SPARSE_COUNTS)
     int *sel_anchor = nullptr;
     float *sel_score = nullptr;
     int sparse_B = 0; // > 0: the last forward pass (of this batch size) left the box towers sparse; wtk_yolo_debug_head / _debug_tensor complete them first.
@@ -241,17 +248,25 @@ struct wtk_yolo {
 };
 
 namespace wtk {
-// Sparse box towers pay from a call size on.  The six masked launches behind the head each last at least one tile's walk and run one after the other on the
-// caller's stream, where the dense box towers of P3 / P4 ran beside the PAN path; what they save grows with the rounds of blocks the dense launches took.
-// Measured (profiles/r07_notes.md section 6, one caller, sparse against dense per call): -4.1 % where box.1 of P3 is 6.4 rounds of 256-pixel blocks over the CUs
-// (640 x 640, B = 64), +1.2 % at 1.7 rounds (B = 17), +4 .. 5 % at 0.6 .. 1.2 rounds (384 x 384, B = 15 / 32).  A straight line through the two 640 x 640
-// points crosses zero near 2.8 rounds; nothing was measured between them, so the rule keeps a margin: at least FOUR rounds (the line's -1 %).
+// Sparse box towers pay from a call size on.  The tail behind the head — select, box.0 of the three levels from the live-tile list, box.1 + box.2 likewise, decode
+// — is four dependent launches on the caller's stream, each at least one tile's walk (box.0 of P5: 144 taps), where the dense box towers of P3 / P4 ran beside the
+// PAN path; what it saves grows with the rounds of blocks the dense launches took.  Measured (profiles/r08_notes.md part 2, one caller, sparse against dense per
+// call, "rounds" = 256-pixel blocks of the dense P3 box.1 launch over the CUs): -5.7 % at 6.4 rounds (640 x 640, B = 64), -3.0 % at 4.0, -3.5 % at 3.2 (B = 32),
+// -2.1 % at 2.4 (B = 24), -0.1 % at 1.7 (B = 17), +1.0 % at 1.2 and +2.3 % at 0.55 (384 x 384, B = 32 / 15 on a 32-frame handle).  The smallest measured size
+// at which sparse is at least 1 % faster is 2.4 rounds; tests/test_gpu_sparse_box.py pins a call of 2.65 rounds (640 x 512, B = 33) as dense, so the threshold
+// is the next measured point, 3.2 rounds, in tenths of a round.
 // h8 x w8: the P3 map; (h8 + 1) x (w8 + 1) per image is the stacked flat geometry of a one-strip map (halo_geometry_stacked), a few per cent under it for a
 // map cut into strips.  No CU count (a device that reports none): never sparse.
-constexpr int kSparseBlockPx = 256, kSparseMinRounds = 4;
-inline bool sparse_box_pays(int B, int h8, int w8, int num_cus) {
-    return num_cus > 0 && (long long)B * (h8 + 1) * (w8 + 1) >= (long long)kSparseMinRounds * kSparseBlockPx * num_cus;
+constexpr int kSparseBlockPx = 256, kSparseMinTenths = 32;
+// kSparseMaxDenseBatch is not measured but fixed: a handle of at most 16 frames (a controller's) stays dense and allocates nothing, whatever the threshold.
+// min_tenths: the handle's threshold (kSparseMinTenths; WTK_SPARSE_MIN_TENTHS, a measurement switch read at create, moves it).
+constexpr int kSparseMaxDenseBatch = 16;
+inline bool sparse_box_pays(int B, int h8, int w8, int num_cus, int min_tenths = kSparseMinTenths) {
+    return num_cus > 0 && 10ll * B * (h8 + 1) * (w8 + 1) >= (long long)min_tenths * kSparseBlockPx * num_cus;
 }
+// Upper bound of the 128-pixel units ONE survivor marks for box.0: its 3 x 3 neighbourhood is three runs of <= 3 flat outputs, 2 * pitch + 3 outputs from the
+// first to the last, in one column strip or in two neighbours (a strip is >= 3 columns wide whenever there are two).  box.1 + box.2: one unit per survivor.
+inline int sparse_units_per_frame(int pitch, int strips) { return ((2 * pitch + 2) / 128 + 2) * (strips > 1 ? 2 : 1); }
 // stream pool (wtk_plan.hip)
 int pooled_stream(int device, hipStream_t *s);
 void unpool_stream(int device, hipStream_t s);

@@ -290,6 +290,17 @@ bool halo_eligible(int k, int stride, int cin, int is_f16);
 bool split_halo_eligible(int k, int stride, int cin, int cout); // split-fp16 operands (real channel counts)
 int split_halo_cout_tile(int cout_stored);
 hipError_t launch_conv3x3_halo_split(const HaloArgs &a, hipStream_t stream); // channel counts / offsets but Cout in pseudo-channels
+// One stage of the sparse Detect box towers over all three levels in ONE launch (halo_list_kernel): block b < *count runs the tile list[b] names, with the split
+// 64-cout x 128-pixel instantiation (plain, or with the fused 64 -> 64 tail when the members carry one); a block beyond the count exits at once.  A list entry
+// (written by head_select_kernel_sparse): level << 30 | column strip << 22 | 128-pixel unit of the strip's stacked flat outputs.  The members are a call's
+// launches of the levels as launch_conv3x3_halo_split takes them (64 couts, one cout tile; their mask, bm and n_dyn are not read).
+constexpr int kHaloListStripBits = 8, kHaloListUnitBits = 22;
+struct HaloListArgs {
+    HaloArgs m[3];
+    const unsigned *list;
+    const unsigned *count;
+};
+hipError_t launch_conv3x3_halo_list(const HaloListArgs &g, unsigned grid, hipStream_t stream); // grid: the host's upper bound of *count
 bool split_s2win_eligible(int k, int stride, int cin, int cout, int cout_pad, int wo, bool plain); // real channel counts
 hipError_t launch_conv3x3_s2_split(const HaloArgs &a, hipStream_t stream);
 int halo_rows_max(int cout_stored, int slabs); // window rows the kernel variant for this Cout can hold
@@ -467,12 +478,20 @@ hipError_t launch_head(const HeadArgs &a, int is_f16, hipStream_t stream);
 // survivor marks nothing.  head_decode_kernel then reads the survivor's 64 box logits and writes the row exactly as the fused kernel does.
 struct HeadSparseArgs {
     HeadArgs h;
-    unsigned char *live; // the handle's mask region, zero when head_select_kernel_sparse starts
+    unsigned char *live; // the handle's mask region, zero when head_select_kernel_sparse starts (4-byte aligned, as are off0 / off1)
     int *sel_anchor;     // [N] survivor (anchor index over the three levels) or -1
     float *sel_score;    // [N] its score
     int S[3], pitch[3], ld[3];  // per level: strip width, row pitch, mask units per strip
     unsigned off0[3], off1[3];  // per level: byte offsets of live0 / live1 in `live`
     const int *n_dyn;           // nullable: frames beyond *n_dyn mark nothing
+    // List form (nullable: the masked form, whose caller clears `live` before every call).  The frame that marks a unit FIRST (an atomic OR on the unit's mask
+    // word) also appends its tile to list[stage] (stage 0: box.0, 1: box.1 + box.2; HaloListArgs) under counter count[stage]: every marked unit is listed once,
+    // whatever the order in which the frames' blocks arrive.  An entry beyond cap[stage] is not written (the counter still counts it).  head_decode_kernel, the
+    // last kernel of a call, leaves the region as it found it: every frame clears the units it marked, and the counters move to count[2 + stage] (what the debug
+    // read returns) and back to zero.
+    unsigned *list[2];
+    unsigned *count; // [4]
+    unsigned cap[2];
 };
 hipError_t launch_head_select_sparse(const HeadSparseArgs &a, hipStream_t stream);
 hipError_t launch_head_decode(const HeadSparseArgs &a, hipStream_t stream);

@@ -372,6 +372,8 @@ PlanSwitches read_switches(wtk_yolo *h) {
     h->sk_force_form = form == 0 || form == 1 ? form : -1;
     h->front_debug = env_int("WTK_FRONT_DEBUG", 0) == 1;
     h->use_sparse_box = env_int("WTK_NO_SPARSE_BOX", 0) != 1;
+    h->use_sparse_list = env_int("WTK_SPARSE_LIST", 1) != 0;
+    h->sparse_min_tenths = std::max(env_int("WTK_SPARSE_MIN_TENTHS", wtk::kSparseMinTenths), 0);
     PlanSwitches s;
     s.latency_plan = env_int("WTK_LATENCY_PLAN", -1);
     s.no_side_stream = env_int("WTK_NO_SIDE_STREAM", 0) == 1;
@@ -866,14 +868,21 @@ extern "C" int wtk_yolo_create_planned(wtk_yolo **out, const wtk_yolo_desc *d, i
     // Split (f16x3) throughput-plan handles only: there the shared first conv of a tower pair runs as three 64-cout tiles, so its box and class halves keep
     // tile and bits; fp16 / fp32 run it as one 192-cout tile, whose halves would land on other instantiations.
     // ... and only handles whose largest call reaches the size from which a sparse call pays (sparse_box_pays below; a per-call rule).
-    if (h->split && !h->latency && h->use_sparse_box && wtk::sparse_box_pays(h->max_batch, h->lh[0], h->lw[0], h->num_cus)) {
+    if (h->split && !h->latency && h->use_sparse_box && h->max_batch > wtk::kSparseMaxDenseBatch &&
+        wtk::sparse_box_pays(h->max_batch, h->lh[0], h->lw[0], h->num_cus, h->sparse_min_tenths)) {
         size_t total = 0;
+        int per_frame = 0;
         for (int i = 0; i < 3; ++i) {
             int S, pitch, strips, bps;
             halo_geometry_stacked(h->max_batch, h->lh[i], h->lw[i], kHaloRowsMax, &S, &pitch, &strips, &bps, 256);
             total += 2 * (((size_t)strips * 2 * bps + 3) & ~(size_t)3);
+            per_frame = std::max(per_frame, wtk::sparse_units_per_frame(pitch, strips));
         }
-        h->live_bytes = total;
+        h->live_mask_bytes = h->live_bytes = total;
+        if (h->use_sparse_list) { // counters and the two tile lists (wtk_internal.h): a frame lists at most per_frame tiles for box.0 and one for box.1 + box.2
+            h->live_list_cap[0] = (unsigned)h->max_batch * (unsigned)per_frame, h->live_list_cap[1] = (unsigned)h->max_batch;
+            h->live_bytes = total + 16 + 4 * ((size_t)h->live_list_cap[0] + h->live_list_cap[1]);
+        }
         if (dev_alloc(h, (void **)&h->sel_anchor, sizeof(int) * h->max_batch) || dev_alloc(h, (void **)&h->sel_score, sizeof(float) * h->max_batch)) {
             wtk_yolo_destroy(h);
             return 1;

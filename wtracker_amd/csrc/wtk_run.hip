@@ -292,6 +292,7 @@ static int resolve_conv(const wtk_yolo *h, const Op &op, int B, ConvLaunch &r) {
 struct SparseBox {
     ConvLaunch cls0[3], box0[3], box1[3];
     HeadSparseArgs hs; // geometry and mask layout for the head kernels (hs.h is filled per call)
+    unsigned list_grid[2]; // list form: the host's bound of the live tiles of this call per stage = the grid of its launch
     int level_of_op0(const wtk_yolo *h, size_t oi) const {
         for (int l = 0; l < 3; ++l)
             if ((int)oi == h->det[l].op0) return l;
@@ -305,7 +306,7 @@ struct SparseBox {
 };
 
 // The rule, in one place.  A call goes sparse iff it is a max_det = 1 call (the caller checks), the switch WTK_NO_SPARSE_BOX is not set, the call is large
-// enough for the sparse tail to pay (sparse_box_pays, wtk_internal.h: four rounds of P3 blocks, from measurement), the handle is a
+// enough for the sparse tail to pay (sparse_box_pays, wtk_internal.h: 3.2 rounds of P3 blocks, from measurement), the handle is a
 // throughput-plan f16x3 handle (wtk_plan.hip allocates the mask for those alone: fp16 / fp32 run the shared first conv as ONE 192-cout tile, whose halves would
 // be other instantiations; latency-plan handles run the box-tower convs as members of grouped split-K launches shared with the PAN path, and five more
 // dependent levels would cost a single frame more than the skipped tiles save), and EVERY box op of every level resolves, at this batch size, to the window
@@ -313,9 +314,10 @@ struct SparseBox {
 // whose 12 x 12 maps run split-K, WTK_NO_FUSED_TAIL, WTK_NO_HALO) keeps the whole handle dense.
 static bool resolve_sparse(const wtk_yolo *h, int B, SparseBox &sp) {
     if (!h->use_sparse_box || !h->split || h->latency || !h->live_bytes) return false;
-    if (!sparse_box_pays(B, h->lh[0], h->lw[0], h->num_cus)) return false; // a call too small for the sparse tail to pay (wtk_internal.h)
+    if (!sparse_box_pays(B, h->lh[0], h->lw[0], h->num_cus, h->sparse_min_tenths)) return false; // a call too small for the sparse tail to pay (wtk_internal.h)
     std::memset(&sp.hs, 0, sizeof(sp.hs));
     unsigned off = 0;
+    int per_frame = 0;
     for (int l = 0; l < 3; ++l) {
         const wtk_yolo::DetLevel &d = h->det[l];
         if (d.op0 < 0 || d.box1 < 0 || d.box2 < 0) return false;
@@ -332,7 +334,8 @@ static bool resolve_sparse(const wtk_yolo *h, int B, SparseBox &sp) {
         sp.hs.S[l] = r0.g.S, sp.hs.pitch[l] = r0.g.pitch, sp.hs.ld[l] = ld;
         sp.hs.off0[l] = off, sp.hs.off1[l] = off + bytes;
         off += 2 * bytes;
-        if (off > h->live_bytes) return false;
+        if (off > h->live_mask_bytes) return false;
+        per_frame = std::max(per_frame, sparse_units_per_frame(r0.g.pitch, r0.g.strips));
         // the two halves of the shared conv: rows [0, hb) and [hb, hb + hc) of its packed weights and bias, the same slices of d1.  64-cout tiles either way
         // (narrow: the class half's 128 couts would otherwise pick the 128-cout tile)
         const int hb = h->dims.hb;
@@ -350,6 +353,14 @@ static bool resolve_sparse(const wtk_yolo *h, int B, SparseBox &sp) {
     }
     sp.hs.live = reinterpret_cast<unsigned char *>(h->zero_page) + 256;
     sp.hs.sel_anchor = h->sel_anchor, sp.hs.sel_score = h->sel_score, sp.hs.n_dyn = h->n_dyn;
+    sp.list_grid[0] = sp.list_grid[1] = 0;
+    if (h->use_sparse_list) { // counters and lists behind the mask (wtk_plan.hip); a call lists at most B * per_frame tiles for box.0 and B for box.1 + box.2
+        sp.list_grid[0] = (unsigned)B * (unsigned)per_frame, sp.list_grid[1] = (unsigned)B;
+        if (sp.list_grid[0] > h->live_list_cap[0] || sp.list_grid[1] > h->live_list_cap[1]) return false;
+        sp.hs.count = reinterpret_cast<unsigned *>(sp.hs.live + h->live_mask_bytes);
+        sp.hs.list[0] = sp.hs.count + 4, sp.hs.list[1] = sp.hs.list[0] + h->live_list_cap[0];
+        sp.hs.cap[0] = sp.list_grid[0], sp.hs.cap[1] = sp.list_grid[1];
+    }
     return true;
 }
 
@@ -588,31 +599,44 @@ static int enqueue_levels(Pass &p, size_t first_op) {
     return 0;
 }
 
-// The end of a sparse pass, on the caller's stream behind the joined side streams: clear the mask, select (which marks), box.0 of the three levels, box.1 + box.2
-// of the three levels, decode.  The six window launches carry a handful of live blocks each and go back to back; in profiling mode they are a class of their own
-// with 0 FLOPs (the host does not know the live tiles), so the roofline does not credit the window kernel with work it skipped.
+// The end of a sparse pass, on the caller's stream behind the joined side streams: select (which marks the live units and lists their tiles), box.0 of the three
+// levels in one launch from the list, box.1 + box.2 likewise, decode (which also leaves mask and counters zero for the next call): four dependent launches whose
+// window grids are the host's bound of the live tiles.  The masked form (WTK_SPARSE_LIST=0) clears the mask, selects, and runs the six window launches of the
+// levels as full grids whose blocks look their units up in the mask.  In profiling mode the window launches are a class of their own with 0 FLOPs (the host does
+// not know the live tiles), so the roofline does not credit the window kernel with work it skipped.
 static int enqueue_sparse_tail(Pass &p, const SparseBox &sp, int H, int W, float conf, float *out_xywh, float *out_conf, int *out_anchor) {
     wtk_yolo *h = p.h;
     hipStream_t st = p.main_st;
     HeadSparseArgs hs = sp.hs;
     hs.h = head_args(h, p.B, H, W, conf, out_xywh, out_conf, out_anchor);
     if (mark(p, PROF_HEAD)) return 1;
-    HIP_TRY(hipMemsetAsync(hs.live, 0, h->live_bytes, st));
+    if (!hs.list[0]) HIP_TRY(hipMemsetAsync(hs.live, 0, h->live_mask_bytes, st));
     HIP_TRY(launch_head_select_sparse(hs, st));
     p.count(PROF_HEAD);
     if (mark(p, PROF_SPARSE)) return 1;
-    for (int l = 0; l < 3; ++l) {
-        if (issue_conv(h, h->ops[h->det[l].op0], sp.box0[l], st)) return 1;
-        p.count(PROF_SPARSE);
-    }
-    for (int l = 0; l < 3; ++l) {
-        if (issue_conv(h, h->ops[h->det[l].box1], sp.box1[l], st)) return 1;
-        p.count(PROF_SPARSE);
+    if (hs.list[0]) {
+        for (int stage = 0; stage < 2; ++stage) {
+            HaloListArgs g;
+            for (int l = 0; l < 3; ++l) g.m[l] = (stage ? sp.box1 : sp.box0)[l].g;
+            g.list = hs.list[stage], g.count = hs.count + stage;
+            HIP_TRY(launch_conv3x3_halo_list(g, sp.list_grid[stage], st));
+            for (int l = 0; l < 3; ++l) p.count(PROF_SPARSE); // the class counts box-tower convs run sparse, as the masked form's six launches do: one launch, three convs
+        }
+    } else {
+        for (int l = 0; l < 3; ++l) {
+            if (issue_conv(h, h->ops[h->det[l].op0], sp.box0[l], st)) return 1;
+            p.count(PROF_SPARSE);
+        }
+        for (int l = 0; l < 3; ++l) {
+            if (issue_conv(h, h->ops[h->det[l].box1], sp.box1[l], st)) return 1;
+            p.count(PROF_SPARSE);
+        }
     }
     if (mark(p, PROF_HEAD)) return 1;
     HIP_TRY(launch_head_decode(hs, st));
     p.count(PROF_HEAD);
     h->sparse_B = p.B;
+    h->sparse_grid[0] = sp.list_grid[0], h->sparse_grid[1] = sp.list_grid[1];
     for (int l = 0; l < 3; ++l) { // what complete_box_towers launches: this pass's own box launches, without the mask
         h->sparse_done[l] = sp.box0[l], h->sparse_done[3 + l] = sp.box1[l];
         h->sparse_done[l].g.live_off = h->sparse_done[3 + l].g.live_off = 0;
@@ -895,6 +919,21 @@ extern "C" int wtk_yolo_debug_head(wtk_yolo *h, int32_t level, int32_t B, float 
 
 extern "C" int wtk_yolo_debug_tensor(wtk_yolo *h, int32_t conv_index, int32_t B, float *out_host, size_t out_cap, int32_t *shape_hwc) {
     if (!h || B <= 0 || B > h->max_batch) return fail("wtk_yolo_debug_tensor: bad argument");
+    if (conv_index == WTK_DEBUG_SPARSE_COUNTS) { // no conv: [1][1][4] = tiles the last list-form sparse pass listed for box.0 and box.1 + box.2, and the grids it launched
+        if (shape_hwc) shape_hwc[0] = 1, shape_hwc[1] = 1, shape_hwc[2] = 4;
+        if (!out_host) return 0;
+        if (out_cap < 4) return fail("wtk_yolo_debug_tensor: output buffer too small");
+        unsigned cnt[2] = {0, 0};
+        if (h->live_list_cap[0]) {
+            DEVICE_GUARD(h);
+            HIP_TRY(hipDeviceSynchronize());
+            HIP_TRY(hipMemcpy(cnt, reinterpret_cast<const char *>(h->zero_page) + 256 + h->live_mask_bytes + 8, sizeof(cnt), hipMemcpyDeviceToHost));
+        }
+        out_host[0] = (float)cnt[0], out_host[1] = (float)cnt[1], out_host[2] = (float)h->sparse_grid[0], out_host[3] = (float)h->sparse_grid[1];
+        return 0;
+    }
+    const bool raw = conv_index <= WTK_DEBUG_RAW(0); // the tensor as the last pass left it: no dense completion of a sparse pass
+    if (raw) conv_index = WTK_DEBUG_RAW(conv_index);
     const Op *op = nullptr;
     for (const Op &o : h->ops)
         if (o.spec == conv_index && o.out_buf >= 0) op = &o;
@@ -908,7 +947,7 @@ extern "C" int wtk_yolo_debug_tensor(wtk_yolo *h, int32_t conv_index, int32_t B,
     HIP_TRY(hipDeviceSynchronize());
     for (int l = 0; l < 3; ++l) { // a box-tower conv: a sparse pass computed it on the survivors' tiles only
         const int oi = (int)(op - h->ops.data());
-        if ((oi == h->det[l].op0 || oi == h->det[l].box1 || oi == h->det[l].box2) && complete_box_towers(h)) return 1;
+        if (!raw && (oi == h->det[l].op0 || oi == h->det[l].box1 || oi == h->det[l].box2) && complete_box_towers(h)) return 1;
     }
     std::vector<char> tmp(px * b.C * (b.f32 ? 4 : h->esize));
     HIP_TRY(hipMemcpy(tmp.data(), b.ptr, tmp.size(), hipMemcpyDeviceToHost));

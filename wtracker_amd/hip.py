@@ -666,14 +666,21 @@ class HipYolo:
             clss.append(cl)
         return np.concatenate(boxes, 1), np.concatenate(clss, 1)
 
-    def debug_tensor(self, conv_index: int, B: int) -> np.ndarray:
-        """Output of conv blob `conv_index` (yolo_conv_table order) of the last forward: fp32 [B,h,w,cout]."""
+    def debug_tensor(self, conv_index: int, B: int, raw: bool = False) -> np.ndarray:
+        """Output of conv blob `conv_index` (yolo_conv_table order) of the last forward: fp32 [B,h,w,cout].  raw: as the pass left it — a Detect
+        box-tower conv is not completed densely after a sparse pass (WTK_DEBUG_RAW), so only the tiles under the survivors hold that pass's values."""
         lib = load()
+        if raw:
+            conv_index = -2 - conv_index
         shp = (C.c_int32 * 3)()
         _check(lib.wtk_yolo_debug_tensor(self._h, conv_index, B, None, 0, shp), "wtk_yolo_debug_tensor")
         out = np.empty((B, shp[0], shp[1], shp[2]), dtype=np.float32)
         _check(lib.wtk_yolo_debug_tensor(self._h, conv_index, B, _ptr(out), out.size, shp), "wtk_yolo_debug_tensor")
         return out
+
+    def sparse_counts(self):
+        """(tiles listed for box.0, for box.1 + box.2, grid of the box.0 launch, of the box.1 + box.2 launch) of the last list-form sparse pass."""
+        return tuple(int(v) for v in self.debug_tensor(-1, 1).ravel())  # WTK_DEBUG_SPARSE_COUNTS
 
     def decode_host(self, box: np.ndarray, cls: np.ndarray, H: int, W: int, conf: float = 0.1):
         box = np.ascontiguousarray(box, dtype=np.float32)
