@@ -1,9 +1,9 @@
 """TEST INFRASTRUCTURE: builds tests/hostsan/_build/hostsan_driver — the HOST side of every translation unit of libwtk_hip.so (hipcc --cuda-host-only:
 no device code is generated, kernels become launch stubs) with -fsanitize=address,undefined, linked against hip_stub.cpp (the no-op launch layer that
-models device memory and the stream / event / capture protocol) and driver.cpp (the shape matrix).  `python tests/hostsan/build.py [quick|full]` builds
-and runs it; tests/test_host_sanitizer.py does the same inside the CPU suite.  `python tests/hostsan/build.py trace [--record]` prints (writes to
-tests/golden/launch_trace.json) the launch trace of the quick matrix in each environment of ENVS: launches per kernel and one sha256 over the ordered
-launch lines of the stub (kernel, grid, block, dynamic LDS, stream ordinal, hash of the argument struct)."""
+models device memory and the stream / event / capture protocol) and driver.cpp (the shape matrix).  `python tests/hostsan/build.py [quick|full|failures]` builds
+and runs it; tests/test_host_sanitizer.py does the same inside the CPU suite.  `python tests/hostsan/build.py trace [quick|full] [--record]` prints
+(writes to tests/golden/launch_trace.json, launch_trace_full.json) the launch trace of that matrix in each environment of ENVS (FULL_ENVS): launches per
+kernel and one sha256 over the ordered launch lines of the stub (kernel, grid, block, dynamic LDS, stream ordinal, hash of the argument struct)."""
 from __future__ import annotations
 
 import hashlib
@@ -31,6 +31,10 @@ ENVS = {
     # the latency plan as one launch per conv (the bit-identity reference of the grouped launches)
     "ungrouped": {"WTK_SK_GROUP": "0", "WTK_SK_AUTOTUNE": "0"},
 }
+# the `full` matrix (handles above 16 frames: the sparse region, the list grids, ws64, the persistent window form, the 1280 geometry) runs in one
+FULL_ENVS = {"full": {"WTK_SK_AUTOTUNE": "0"}}
+TRACE_FIXTURE_FULL = os.path.join(ROOT, "tests", "golden", "launch_trace_full.json")
+TRACES = {"quick": (ENVS, TRACE_FIXTURE, 900), "full": (FULL_ENVS, TRACE_FIXTURE_FULL, 1500)}
 HOST_ONLY = ["--cuda-host-only", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function", "-Wno-unused-variable"]
 
 
@@ -105,9 +109,9 @@ def run(mode: str = "quick", env_extra: dict | None = None, timeout: int = 900) 
     return subprocess.run([exe, mode], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env, timeout=timeout)
 
 
-def trace(env_extra: dict) -> dict:
-    """Launch trace of the quick matrix (the two-thread section, whose launch order is the scheduler's, is left out by the driver)."""
-    r = run("quick", dict(env_extra, WTK_STUB_VERBOSE="1"))
+def trace(env_extra: dict, mode: str = "quick") -> dict:
+    """Launch trace of the quick / full matrix (the two-thread section, whose launch order is the scheduler's, is left out by the driver)."""
+    r = run(mode, dict(env_extra, WTK_STUB_VERBOSE="1"), timeout=TRACES[mode][2])
     if r.returncode != 0:
         raise RuntimeError("\n".join(l for l in r.stdout.splitlines() if not l.startswith("launch "))[-3000:])
     digest, kernels = hashlib.sha256(), {}
@@ -122,9 +126,11 @@ def trace(env_extra: dict) -> dict:
 if __name__ == "__main__":
     mode = sys.argv[1] if len(sys.argv) > 1 else "quick"
     if mode == "trace":
-        text = json.dumps({name: trace(env) for name, env in ENVS.items()}, indent=1) + "\n"
+        matrix = "full" if "full" in sys.argv[2:] else "quick"
+        envs, fixture, _ = TRACES[matrix]
+        text = json.dumps({name: trace(env, matrix) for name, env in envs.items()}, indent=1) + "\n"
         if "--record" in sys.argv:
-            with open(TRACE_FIXTURE, "w") as f:
+            with open(fixture, "w") as f:
                 f.write(text)
         print(text)
         sys.exit(0)

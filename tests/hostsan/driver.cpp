@@ -25,6 +25,7 @@ int stub_live_execs(void);
 int stub_open_captures(void);
 unsigned long long stub_kernel_launches(const char *substr);
 void stub_set_verbose(int);
+long long stub_fail_malloc(long long n);
 // the slice of the HIP API the driver itself needs (device buffers of a caller)
 int hipMalloc(void **, size_t);
 int hipFree(void *);
@@ -387,6 +388,60 @@ static void two_threads() {
     a.join(), b.join();
 }
 
+// A create that fails leaves nothing behind, whichever of its allocations is the one that fails; so do the fp16 range guards of the two weight packers.
+// Mode `failures`, a run of its own behind stub_set_verbose(0): some seven hundred creates would triple the time of every matrix run, and no trace sees them.
+static void creation_failures() {
+    std::fprintf(stderr, "[hostsan] creation failures\n");
+    struct {
+        int H, W, B, dtype, plan;
+    } const handles[3] = {{128, 128, 3, WTK_F16, WTK_PLAN_THROUGHPUT}, {384, 384, 4, WTK_F16X3, WTK_PLAN_LATENCY} /* scratch and tickets */, {640, 640, 64, WTK_F16X3, WTK_PLAN_THROUGHPUT} /* sparse region */};
+    const Model m = make_model(kScales[1], 1, 13);
+    // (process-wide state that a first create sets up — kernel attributes, the status page — exists when the first failing create runs: a create has succeeded)
+    const auto failed_clean = [](const Model &mm, int H, int W, int B, int dtype, int plan, const char *what, long long n) {
+        const size_t bytes = stub_live_device_bytes();
+        const int events = stub_live_events();
+        wtk_yolo_desc d;
+        std::memset(&d, 0, sizeof(d));
+        d.device = 0, d.dtype = (wtk_dtype)dtype, d.imgsz_h = H, d.imgsz_w = W, d.max_batch = B, d.nc = mm.nc;
+        d.width_mult = mm.sc.width, d.depth_mult = mm.sc.depth, d.max_channels = mm.sc.maxch, d.n_convs = (int)mm.blobs.size(), d.convs = mm.blobs.data();
+        wtk_yolo *h = nullptr;
+        const int rc = wtk_yolo_create_planned(&h, &d, plan);
+        CHECK(rc != 0, "%s %lld: create %dx%d B%d dtype %d succeeded", what, n, H, W, B, dtype);
+        CHECK(h == nullptr, "%s %lld: *out written by a failed create", what, n);
+        CHECK(wtk_last_error()[0] != 0, "%s %lld: no error text", what, n);
+        CHECK(stub_live_device_bytes() == bytes, "%s %lld: %zu device bytes live after a failed create, %zu before", what, n, stub_live_device_bytes(), bytes);
+        CHECK(stub_live_events() == events, "%s %lld: %d events live after a failed create, %d before", what, n, stub_live_events(), events);
+        if (rc == 0) wtk_yolo_destroy(h);
+    };
+    for (const auto &c : handles) {
+        stub_fail_malloc(-1);
+        wtk_yolo *h = create(m, c.H, c.W, c.B, c.dtype, c.plan);
+        const long long count = stub_fail_malloc(-1);
+        wtk_yolo_destroy(h);
+        CHECK(count > 100, "a create of %lld allocations", count);
+        for (long long n = 0; n < count; ++n) {
+            stub_fail_malloc(n);
+            failed_clean(m, c.H, c.W, c.B, c.dtype, c.plan, "failed allocation", n);
+        }
+        stub_fail_malloc(-1);
+        h = create(m, c.H, c.W, c.B, c.dtype, c.plan);
+        CHECK(stub_fail_malloc(-1) == count, "a create after the failures allocates as the first did");
+        wtk_yolo_destroy(h);
+    }
+    // fp16 range guards: a weight of 1e6 in model.0 (pack_stem) and in the last class conv (pack_conv), in both fp16-storage dtypes
+    for (int last : {0, 1}) {
+        Model big = make_model(kScales[1], 1, 13);
+        big.w[last ? big.w.size() - 1 : 0][0] = 1e6f;
+        for (int dtype : {(int)WTK_F16, (int)WTK_F16X3}) {
+            failed_clean(big, 128, 128, 3, dtype, WTK_PLAN_THROUGHPUT, "range guard", last);
+            const std::string want = "wtk_yolo_create: a folded weight of conv blob " + std::to_string(last ? big.w.size() - 1 : 0);
+            CHECK(std::strstr(wtk_last_error(), want.c_str()) && std::strstr(wtk_last_error(), "is outside the fp16 range: this model needs dtype WTK_F32"), "range guard message");
+        }
+        wtk_yolo *h = create(big, 128, 128, 3, WTK_F32, WTK_PLAN_THROUGHPUT); // ... which fp32 takes
+        wtk_yolo_destroy(h);
+    }
+}
+
 // The launch layer must SEE what it claims to see: each of these is a protocol violation committed on purpose; the mode passes when every one is flagged.
 static int selftest() {
     int flagged = 0, expected = 0;
@@ -455,6 +510,21 @@ static int selftest() {
     return flagged == expected ? 0 : 1;
 }
 
+// the closing report and checks of every mode but the selftest
+static int finish() {
+    const int v = stub_violations();
+    std::fprintf(stderr, "[hostsan] kernels launched: %llu (conv_sk %llu, window %llu, igemm %llu, front %llu, head %llu); peak device memory %.1f GB; violations %d; driver failures %d\n",
+                 stub_kernel_launches(nullptr), stub_kernel_launches("conv_sk_kernel"), stub_kernel_launches("conv3x3_halo"), stub_kernel_launches("conv_igemm_kernel"),
+                 stub_kernel_launches("front_fused"), stub_kernel_launches("head_"), (double)stub_peak_device_bytes() / 1e9, v, g_fail);
+    // everything the handles took must be back: events destroyed, no graph exec or capture left behind, only the process-wide status page and nothing else alive
+    CHECK(stub_live_events() == 0, "%d events leaked", stub_live_events());
+    CHECK(stub_live_execs() == 0, "%d graph execs leaked", stub_live_execs());
+    CHECK(stub_open_captures() == 0, "%d captures left open", stub_open_captures());
+    CHECK(stub_live_device_bytes() == 0, "%zu bytes of device memory leaked", stub_live_device_bytes());
+    std::fprintf(stderr, "[hostsan] live streams at exit (pooled, by design): %d\n", stub_live_streams());
+    return (v || g_fail) ? 1 : 0;
+}
+
 int main(int argc, char **argv) {
     const std::string mode = argc > 1 ? argv[1] : "quick";
     if (mode == "selftest") return selftest();
@@ -463,6 +533,11 @@ int main(int argc, char **argv) {
     CHECK(wtk_device_count() == 1, "device count");
     const int F32 = WTK_F32, F16 = WTK_F16, X3 = WTK_F16X3, AUTO = WTK_PLAN_AUTO, THR = WTK_PLAN_THROUGHPUT, LAT = WTK_PLAN_LATENCY;
     std::vector<Case> cases;
+    if (mode == "failures") {
+        stub_set_verbose(0);
+        creation_failures();
+        return finish();
+    }
     // the two configurations of the round-5 crashes first (scale n, B = 3, tiny maps; a latency-plan fp32 handle of capacity 16 and a throughput-plan fp16 handle)
     cases.push_back({0, 160, 160, 16, F32, LAT, 1});
     cases.push_back({0, 96, 160, 3, F16, THR, 1});
@@ -519,15 +594,5 @@ int main(int argc, char **argv) {
     schedule_shape();
     stub_set_verbose(0); // the launch trace ends here: two threads interleave their launches in an order that is not the library's to decide
     two_threads();
-    const int v = stub_violations();
-    std::fprintf(stderr, "[hostsan] kernels launched: %llu (conv_sk %llu, window %llu, igemm %llu, front %llu, head %llu); peak device memory %.1f GB; violations %d; driver failures %d\n",
-                 stub_kernel_launches(nullptr), stub_kernel_launches("conv_sk_kernel"), stub_kernel_launches("conv3x3_halo"), stub_kernel_launches("conv_igemm_kernel"),
-                 stub_kernel_launches("front_fused"), stub_kernel_launches("head_"), (double)stub_peak_device_bytes() / 1e9, v, g_fail);
-    // everything the handles took must be back: events destroyed, no graph exec or capture left behind, only the process-wide status page and nothing else alive
-    CHECK(stub_live_events() == 0, "%d events leaked", stub_live_events());
-    CHECK(stub_live_execs() == 0, "%d graph execs leaked", stub_live_execs());
-    CHECK(stub_open_captures() == 0, "%d captures left open", stub_open_captures());
-    CHECK(stub_live_device_bytes() == 0, "%zu bytes of device memory leaked", stub_live_device_bytes());
-    std::fprintf(stderr, "[hostsan] live streams at exit (pooled, by design): %d\n", stub_live_streams());
-    return (v || g_fail) ? 1 : 0;
+    return finish();
 }

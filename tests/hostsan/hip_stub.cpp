@@ -60,6 +60,8 @@ std::set<uint64_t> g_live_region_ids;
 std::map<uintptr_t, Region> g_regions;
 constexpr size_t kReserveAbove = 8u << 20; // regions above 8 MiB are address-space reservations
 size_t g_live_bytes = 0, g_peak_bytes = 0;
+long long g_fail_malloc = -1; // stub_fail_malloc: the hipMalloc that many calls from now fails (-1: none)
+long long g_mallocs = 0;      // hipMalloc calls since the last stub_fail_malloc
 
 const std::pair<const uintptr_t, Region> *find_region(const void *p) {
     const uintptr_t a = reinterpret_cast<uintptr_t>(p);
@@ -275,6 +277,14 @@ uint64_t stub_kernel_launches(const char *substr) {
     return n;
 }
 void stub_set_verbose(int v) { g_verbose = v != 0; }
+// Fault injection: the n-th next hipMalloc (0 = the very next) returns hipErrorOutOfMemory, once; n < 0 switches it off.  Returns the number of hipMalloc
+// calls since the previous call of this function (how a driver counts the allocations of an operation).
+long long stub_fail_malloc(long long n) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    const long long calls = g_mallocs;
+    g_fail_malloc = n, g_mallocs = 0;
+    return calls;
+}
 
 // ---- registration (what hipcc's host stubs call at load time) ---------------------------------------------------------------
 void **__hipRegisterFatBinary(const void *) {
@@ -351,6 +361,8 @@ hipError_t hipMalloc(void **p, size_t bytes) {
     std::lock_guard<std::mutex> lk(g_mu);
     unsafe_call("hipMalloc");
     if (!p) return ret(hipErrorInvalidValue);
+    ++g_mallocs;
+    if (g_fail_malloc >= 0 && g_fail_malloc-- == 0) return ret(hipErrorOutOfMemory);
     if (bytes == 0) {
         *p = nullptr;
         return hipSuccess;

@@ -38,18 +38,14 @@ def test_host_side_is_clean_over_the_shape_matrix(env):
     assert "violations 0; driver failures 0" in r.stdout, r.stdout[-3000:]
 
 
-def test_launch_trace_matches_the_recorded_one():
-    """Planning and launching are pinned launch by launch: in every environment of the quick matrix the stub's ordered launch lines (kernel instantiation,
-    grid, block, dynamic LDS, stream ordinal, hash of the argument struct with device pointers as (allocation, offset); the two-thread section left out)
-    hash to the sha256 recorded in tests/golden/launch_trace.json, which was recorded on the commit BEFORE wtk_run.hip was split into resolve / issue steps.
-    A change that leaves behaviour alone reproduces it.  A pull request that changes planning on purpose re-records it on its own tree with
-    `python tests/hostsan/build.py trace --record` and says so."""
-    with open(hostsan.TRACE_FIXTURE) as f:
+def _trace_matches(matrix):
+    envs, fixture, _ = hostsan.TRACES[matrix]
+    with open(fixture) as f:
         want = json.load(f)
-    assert sorted(want) == sorted(hostsan.ENVS)
+    assert sorted(want) == sorted(envs)
     bad = []
-    for name, env in hostsan.ENVS.items():
-        got = hostsan.trace(env)
+    for name, env in envs.items():
+        got = hostsan.trace(env, matrix)
         names = sorted(set(got["kernels"]) | set(want[name]["kernels"]))
         diff = {k: (want[name]["kernels"].get(k, 0), got["kernels"].get(k, 0)) for k in names if want[name]["kernels"].get(k, 0) != got["kernels"].get(k, 0)}
         print(f"{name}: {got['launches']} launches (recorded {want[name]['launches']}), sha256 {got['sha256']}")
@@ -57,7 +53,25 @@ def test_launch_trace_matches_the_recorded_one():
             print(f"  {k}: recorded {w}, now {g}")
         if got["sha256"] != want[name]["sha256"] or diff:
             bad.append(name)
-    assert not bad, f"launch trace differs from tests/golden/launch_trace.json in {bad} (per-kernel count differences are printed above)"
+    assert not bad, f"launch trace differs from {os.path.relpath(fixture, hostsan.ROOT)} in {bad} (per-kernel count differences are printed above)"
+
+
+def test_launch_trace_matches_the_recorded_one():
+    """Planning and launching are pinned launch by launch: in every environment of the quick matrix the stub's ordered launch lines (kernel instantiation,
+    grid, block, dynamic LDS, stream ordinal, hash of the argument struct with device pointers as (allocation, offset); the two-thread section left out)
+    hash to the sha256 recorded in tests/golden/launch_trace.json, which was recorded on the commit BEFORE wtk_run.hip was split into resolve / issue steps.
+    A change that leaves behaviour alone reproduces it.  A pull request that changes planning on purpose re-records it on its own tree with
+    `python tests/hostsan/build.py trace --record` and says so."""
+    _trace_matches("quick")
+
+
+def test_failed_creates_leave_nothing_behind():
+    """Mode `failures`: three handles (fp16 128 x 128, latency f16x3 384 x 384 with scratch and tickets, f16x3 640 x 640 B = 64 with the sparse region), each created
+    once per allocation it makes with that allocation failing: the call returns non-zero, leaves *out null and an error text, and the device bytes and events
+    that are live afterwards are those from before; then the create succeeds again.  The same for the fp16 range guards of pack_stem and pack_conv."""
+    r = hostsan.run("failures", timeout=1500)
+    _ok(r)
+    assert "[hostsan] creation failures" in r.stdout and "violations 0; driver failures 0" in r.stdout, r.stdout[-3000:]
 
 
 def test_host_side_is_clean_over_the_full_matrix():
@@ -65,3 +79,10 @@ def test_host_side_is_clean_over_the_full_matrix():
     r = hostsan.run("full", {"WTK_SK_AUTOTUNE": "0"}, timeout=1500)
     _ok(r)
     assert "violations 0; driver failures 0" in r.stdout, r.stdout[-3000:]
+
+
+def test_full_matrix_launch_trace_matches_the_recorded_one():
+    """The same pin over the `full` matrix (tests/golden/launch_trace_full.json, recorded on the commit BEFORE wtk_yolo_create_planned was split into passes): the
+    handles above 16 frames, which the quick matrix never creates — the sparse region and the list grids, ws64, the persistent window form, the 1280 geometry.
+    Re-recorded with `python tests/hostsan/build.py trace full --record`."""
+    _trace_matches("full")

@@ -192,8 +192,8 @@ struct wtk_yolo {
         int op0 = -1, box1 = -1, box2 = -1;
     } det[3];
     size_t live_bytes = 0; // 0: this handle never runs sparse
-    // List form (the default; WTK_SPARSE_LIST=0: the masked form, one full-grid launch per level and stage behind a cleared mask).  Behind the mask's live_mask_bytes
-    // in the same region: four counters (HeadSparseArgs::count), then the two stages' tile lists of live_list_cap[] entries, sized like the mask for max_batch.
+    // List form (the default; WTK_SPARSE_LIST=0: the masked form, one full-grid launch per level and stage behind a cleared mask): counters and the two stages'
+    // tile lists of live_list_cap[] entries behind the mask's live_mask_bytes, sized like the mask for max_batch (the layout: SparseMask below).
     int use_sparse_list = 1;
     int sparse_min_tenths = 0; // threshold of sparse_box_pays (below) for this handle's calls, in tenths of a round
     size_t live_mask_bytes = 0;
@@ -267,6 +267,33 @@ inline bool sparse_box_pays(int B, int h8, int w8, int num_cus, int min_tenths =
 // Upper bound of the 128-pixel units ONE survivor marks for box.0: its 3 x 3 neighbourhood is three runs of <= 3 flat outputs, 2 * pitch + 3 outputs from the
 // first to the last, in one column strip or in two neighbours (a strip is >= 3 columns wide whenever there are two).  box.1 + box.2: one unit per survivor.
 inline int sparse_units_per_frame(int pitch, int strips) { return ((2 * pitch + 2) / 128 + 2) * (strips > 1 ? 2 : 1); }
+// The sparse region: what lies behind the zero page in the handle's zero_page allocation, and the only place that knows its layout.
+//   [kZeroPageBytes of zeros][mask: per level live0 then live1][kSparseCounters counters (HeadSparseArgs::count)][tile list of stage 0][tile list of stage 1]
+// A mask array (live0: box.0's units, live1: box.1 + box.2's) is strips x ld bytes, rounded up to 4; ld = the 128-pixel units of a strip's stacked rows, rounded
+// up to an even count.  The mask depends on the batch: wtk_plan.hip sizes it, and the lists, for max_batch from halo_geometry_stacked; resolve_sparse
+// (wtk_run.hip) lays a call's arrays out for its B from the resolved launch's geometry, inside that size.  Counters and lists sit behind the HANDLE's mask size.
+constexpr unsigned kZeroPageBytes = 256, kSparseCounters = 4;
+struct SparseMask {
+    int ld[3] = {0, 0, 0};
+    unsigned off0[3] = {0, 0, 0}, off1[3] = {0, 0, 0}; // byte offsets of live0 / live1 of a level from the start of the region
+    unsigned bytes = 0;                                // of the levels added so far
+    int units_per_frame = 0;                           // most tiles one frame lists for box.0 (box.1 + box.2: one)
+};
+// level l (lh rows; pitch, strips: the stacked flat geometry of its window launch) of a batch of B frames, behind the levels before it
+inline void sparse_mask_add_level(SparseMask &m, int l, int B, int lh, int pitch, int strips) {
+    m.ld[l] = 2 * (int)(((long long)B * (lh + 1) * pitch + 255) / 256);
+    const unsigned bytes = ((unsigned)strips * (unsigned)m.ld[l] + 3u) & ~3u;
+    m.off0[l] = m.bytes, m.off1[l] = m.bytes + bytes;
+    m.bytes += 2 * bytes;
+    const int units = sparse_units_per_frame(pitch, strips);
+    if (units > m.units_per_frame) m.units_per_frame = units;
+}
+// entries of the tile list of a stage (0: box.0, 1: box.1 + box.2) that B frames can fill
+inline unsigned sparse_list_cap(const SparseMask &m, int stage, int B) { return stage ? (unsigned)B : (unsigned)B * (unsigned)m.units_per_frame; }
+// byte offsets from the start of the region, for a handle whose mask takes mask_bytes and whose lists hold cap[] entries
+inline size_t sparse_count_off(size_t mask_bytes) { return mask_bytes; }
+inline size_t sparse_list_off(size_t mask_bytes, const unsigned cap[2], int stage) { return mask_bytes + 4 * (size_t)kSparseCounters + (stage ? 4 * (size_t)cap[0] : 0); }
+inline size_t sparse_region_bytes(size_t mask_bytes, const unsigned cap[2]) { return sparse_list_off(mask_bytes, cap, 1) + 4 * (size_t)cap[1]; }
 // stream pool (wtk_plan.hip)
 int pooled_stream(int device, hipStream_t *s);
 void unpool_stream(int device, hipStream_t s);

@@ -10,6 +10,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <memory>
 
 using namespace wtk;
 
@@ -221,12 +222,88 @@ static int pack_conv(wtk_yolo *h, Op &op, const std::vector<const float *> &w_pa
     return 0;
 }
 
+// Stem (model.0) weights next to pack_conv's: repack [cout][3][3][3(RGB)] -> K = tap*4 + channel (see stem_mfma_kernel).  The stem reads unscaled pixels and
+// produces scaled activations.  Split mode: split-fp16 operands like every other conv of the handle (pixels / 255 and the weights as hi + lo pairs).
+static int pack_stem(wtk_yolo *h, Op &op, const wtk_conv_blob &blob) {
+    const int c0 = op.cout;
+    const float *w0 = blob.weight;
+    const bool stem_split = h->split;
+    const int taps = (h->is_f16 || stem_split) ? 16 : 9;
+    std::vector<float> wp((size_t)c0 * taps * 4, 0.f);
+    for (int co = 0; co < c0; ++co)
+        for (int tap = 0; tap < 9; ++tap)
+            for (int ch = 0; ch < 3; ++ch)
+                wp[((size_t)co * taps + tap) * 4 + ch] = (float)((double)w0[((size_t)co * 9 + tap) * 3 + ch] * (double)kActScale);
+    if (h->is_f16 || stem_split)
+        for (float x : wp) {
+            if (!(std::fabs(x) <= 65504.0f))
+                return fail("wtk_yolo_create: a folded weight of conv blob " + std::to_string(op.spec) + " (model.0) is outside the fp16 range: this model needs dtype WTK_F32");
+        }
+    std::vector<float> stem_bias(c0);
+    for (int co = 0; co < c0; ++co) stem_bias[co] = (float)((double)blob.bias[co] * (double)kActScale);
+    std::vector<uint16_t> wh;
+    const void *src = wp.data();
+    size_t bytes = wp.size() * 4;
+    if (h->is_f16) {
+        wh.resize(wp.size());
+        for (size_t i = 0; i < wp.size(); ++i) wh[i] = f32_to_f16_bits(wp[i]);
+        src = wh.data();
+        bytes = wh.size() * 2;
+    } else if (stem_split) { // [cout][16][4] hi halves, then [cout][16][4] lo halves
+        wh.resize(2 * wp.size());
+        for (size_t i = 0; i < wp.size(); ++i) {
+            const uint16_t hb = f32_to_f16_bits(wp[i]);
+            wh[i] = hb;
+            wh[wp.size() + i] = f32_to_f16_bits((wp[i] - f16_bits_to_f32(hb)) * kSplitScale);
+        }
+        src = wh.data();
+        bytes = wh.size() * 2;
+    }
+    if (dev_alloc(h, &op.w, bytes) || dev_alloc(h, (void **)&op.bias, sizeof(float) * c0)) return 1;
+    if (hipMemcpy(op.w, src, bytes, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(op.bias, stem_bias.data(), sizeof(float) * c0, hipMemcpyHostToDevice) != hipSuccess)
+        return fail("wtk_yolo_create: stem weight upload failed");
+    return 0;
+}
+
 namespace {
+// A tensor as the planner sees it: the channels of buffer `buf` from `coff` on (channel-slice views instead of concat / upsample tensors).  buf < 0: none.
+struct View {
+    int buf = -1, coff = 0;
+};
+// What a conv does besides in -> out.  Every member defaults to "none"; a call names the one it uses (with_out2 ... below).
+struct ConvExtra {
+    View out2;              // second destination of the output (ConvArgs::out2: the 2x-upsampled copy of the materialised-upsample variant)
+    View res;               // residual added to the output (a C2f bottleneck's shortcut)
+    View in2;               // half-resolution source of the first in2_split input channels (ConvArgs::in2: the lazy upsample)
+    int in2_split = 0;
+    int cout_store_pad = 0; // channels actually stored when that is more than the blobs' (zero rows beyond)
+};
+ConvExtra with_out2(View v) {
+    ConvExtra x;
+    x.out2 = v;
+    return x;
+}
+ConvExtra with_res(View v) {
+    ConvExtra x;
+    x.res = v;
+    return x;
+}
+ConvExtra with_in2(View v, int split) {
+    ConvExtra x;
+    x.in2 = v, x.in2_split = split;
+    return x;
+}
+ConvExtra with_store_pad(int cout) {
+    ConvExtra x;
+    x.cout_store_pad = cout;
+    return x;
+}
+
 struct Planner {
     wtk_yolo *h;
     const std::vector<ConvSpec> &specs;
     const wtk_conv_blob *blobs;
-    bool failed = false;
 
     int new_buf(int hh, int ww, int C) {
         Buf b;
@@ -238,10 +315,7 @@ struct Planner {
         return (int)h->bufs.size() - 1;
     }
     // generic conv op from one or more blobs (concatenated along cout)
-    void conv(const std::vector<std::string> &names, int in_buf, int in_coff, int out_buf, int out_coff, int out2_buf = -1,
-              int out2_coff = 0, int res_buf = -1, int res_coff = 0, int cout_store_pad = 0, int in2_buf = -1, int in2_coff = 0,
-              int in2_split = 0) {
-        if (failed) return;
+    int conv(const std::vector<std::string> &names, View in, View out, const ConvExtra &x = ConvExtra()) {
         Op op;
         op.kind = OP_CONV;
         std::vector<const float *> wp, bp;
@@ -249,11 +323,7 @@ struct Planner {
         int cout = 0;
         for (auto &nm : names) {
             const int i = find_spec(specs, nm);
-            if (i < 0) {
-                failed = true;
-                fail("internal: unknown conv " + nm);
-                return;
-            }
+            if (i < 0) return fail("internal: unknown conv " + nm);
             const ConvSpec &s = specs[i];
             if (op.spec < 0) op.spec = i;
             op.cin = s.cin;
@@ -265,68 +335,50 @@ struct Planner {
             couts.push_back(s.cout);
             cout += s.cout;
         }
-        op.cout = std::max(cout, cout_store_pad); // channels actually stored (>= real cout, zero rows beyond)
+        op.cout = std::max(cout, x.cout_store_pad); // channels actually stored (>= real cout, zero rows beyond)
         op.cfg = pick_cfg(op.cout, op.k == 1 && op.stride == 1);
         if (h->split && op.cfg == CFG_256x64) op.cfg = CFG_128x64; // the split 256x64 instantiation spills (two accumulator sets)
-        op.in_buf = in_buf;
-        op.in_coff = in_coff;
-        op.out_buf = out_buf;
-        op.out_coff = out_coff;
-        op.out2_buf = out2_buf;
-        op.out2_coff = out2_coff;
-        op.res_buf = res_buf;
-        op.res_coff = res_coff;
-        op.in2_buf = in2_buf;
-        op.in2_coff = in2_coff;
-        op.in2_split = in2_split;
-        if (in2_buf >= 0) {
-            const Buf &lb = h->bufs[in2_buf];
-            const Buf &hb = h->bufs[in_buf];
-            if (op.cfg != CFG_128x128 || op.k != 1 || lb.h * 2 != hb.h || lb.w * 2 != hb.w || in2_coff + in2_split > lb.C || in2_split > op.cin) {
-                failed = true;
-                fail("internal: two-source conv " + names[0] + " does not fit the 128x128 loader");
-                return;
-            }
+        op.in_buf = in.buf, op.in_coff = in.coff;
+        op.out_buf = out.buf, op.out_coff = out.coff;
+        op.out2_buf = x.out2.buf, op.out2_coff = x.out2.coff;
+        op.res_buf = x.res.buf, op.res_coff = x.res.coff;
+        op.in2_buf = x.in2.buf, op.in2_coff = x.in2.coff, op.in2_split = x.in2_split;
+        if (op.in2_buf >= 0) {
+            const Buf &lb = h->bufs[op.in2_buf];
+            const Buf &hb = h->bufs[op.in_buf];
+            if (op.cfg != CFG_128x128 || op.k != 1 || lb.h * 2 != hb.h || lb.w * 2 != hb.w || op.in2_coff + op.in2_split > lb.C || op.in2_split > op.cin)
+                return fail("internal: two-source conv " + names[0] + " does not fit the 128x128 loader");
         }
-        const Buf &ib = h->bufs[in_buf];
-        const Buf &ob = h->bufs[out_buf];
+        const Buf &ib = h->bufs[op.in_buf];
+        const Buf &ob = h->bufs[op.out_buf];
         const int pad = op.k / 2;
         const int ho = (ib.h + 2 * pad - op.k) / op.stride + 1, wo = (ib.w + 2 * pad - op.k) / op.stride + 1;
-        if (ho != ob.h || wo != ob.w || in_coff + op.cin > ib.C || out_coff + op.cout > ob.C) {
-            failed = true;
-            fail("internal: shape mismatch planning conv " + names[0]);
-            return;
-        }
+        if (ho != ob.h || wo != ob.w || op.in_coff + op.cin > ib.C || op.out_coff + op.cout > ob.C) return fail("internal: shape mismatch planning conv " + names[0]);
         // 2-D pixel tiles where the map is large enough that a linear tile would be a thin strip
         const int bm = conv_cfg_bm(op.cfg);
         op.tile_w = 0;
         if (op.k == 3 && wo >= 64 && wo % 16 == 0 && ho % (bm / 16) == 0) op.tile_w = 16;
         op.halo = halo_eligible(op.k, op.stride, op.cin, h->is_f16) && h->use_halo ? 1 : 0;
         if (h->split) op.halo = split_halo_eligible(op.k, op.stride, op.cin, op.cout) && h->use_halo ? 1 : 0;
-        if (!h->split && h->use_halo && c32_eligible(op.k, op.stride, op.cin, op.cout, h->is_f16, out2_buf >= 0)) op.halo = 2;
-        if (h->split && h->use_halo && h->use_c32s && c32_split_eligible(op.k, op.stride, op.cin, op.cout, out2_buf < 0 && in2_buf < 0 && !ob.f32)) op.halo = 2;
+        if (!h->split && h->use_halo && c32_eligible(op.k, op.stride, op.cin, op.cout, h->is_f16, op.out2_buf >= 0)) op.halo = 2;
+        if (h->split && h->use_halo && h->use_c32s && c32_split_eligible(op.k, op.stride, op.cin, op.cout, op.out2_buf < 0 && op.in2_buf < 0 && !ob.f32)) op.halo = 2;
         op.macs_per_image = (double)ho * wo * cout * op.k * op.k * op.cin;
-        if (pack_conv(h, op, wp, bp, couts)) {
-            failed = true;
-            return;
-        }
+        if (pack_conv(h, op, wp, bp, couts)) return 1;
         h->ops.push_back(op);
+        return 0;
     }
-    // C2f block: input view -> output view.  Returns nothing; allocates its concat + temp buffers.
-    void c2f(const std::string &p, int in_buf, int in_coff, int c2, int n, bool shortcut, int out_buf, int out_coff, int out2_buf = -1,
-             int out2_coff = 0, int in2_buf = -1, int in2_coff = 0, int in2_split = 0) {
-        if (failed) return;
-        const Buf ib = h->bufs[in_buf];
+    // C2f block: input view -> output view; allocates its concat + temp buffers.  x.in2 feeds cv1, x.out2 is cv2's second destination.
+    int c2f(const std::string &p, View in, int c2, int n, bool shortcut, View out, const ConvExtra &x = ConvExtra()) {
+        const Buf ib = h->bufs[in.buf];
         const int c = c2 / 2;
         const int cat = new_buf(ib.h, ib.w, (2 + n) * c);
         const int tmp = new_buf(ib.h, ib.w, c);
-        conv({p + ".cv1"}, in_buf, in_coff, cat, 0, -1, 0, -1, 0, 0, in2_buf, in2_coff, in2_split);
+        if (conv({p + ".cv1"}, in, {cat}, with_in2(x.in2, x.in2_split))) return 1;
         for (int i = 0; i < n; ++i) {
             const std::string m = p + ".m." + std::to_string(i);
-            conv({m + ".cv1"}, cat, (1 + i) * c, tmp, 0);
-            conv({m + ".cv2"}, tmp, 0, cat, (2 + i) * c, -1, 0, shortcut ? cat : -1, (1 + i) * c);
+            if (conv({m + ".cv1"}, {cat, (1 + i) * c}, {tmp}) || conv({m + ".cv2"}, {tmp}, {cat, (2 + i) * c}, with_res({shortcut ? cat : -1, (1 + i) * c}))) return 1;
         }
-        conv({p + ".cv2"}, cat, 0, out_buf, out_coff, out2_buf, out2_coff);
+        return conv({p + ".cv2"}, {cat}, out, with_out2(x.out2));
     }
 };
 } // namespace
@@ -339,7 +391,7 @@ static int env_int(const char *name, int unset) {
 }
 
 namespace {
-// The switches that combine with a planning rule of wtk_yolo_create_planned, which applies each one where its rule is decided.
+// The switches that combine with a planning rule of wtk_yolo_create_planned: the pass that decides the rule applies the switch.
 struct PlanSwitches {
     int latency_plan;          // WTK_LATENCY_PLAN: -1 unset (the max_batch rule), 1 the latency plan, any other value the throughput plan
     bool no_side_stream;       // WTK_NO_SIDE_STREAM=1
@@ -534,7 +586,11 @@ extern "C" void wtk_yolo_destroy(wtk_yolo *h) {
 extern "C" int wtk_yolo_create(wtk_yolo **out, const wtk_yolo_desc *d) { return wtk_yolo_create_planned(out, d, WTK_PLAN_AUTO); }
 extern "C" int wtk_yolo_plan(wtk_yolo *h) { return h ? (h->latency ? WTK_PLAN_LATENCY : WTK_PLAN_THROUGHPUT) : -1; }
 
-extern "C" int wtk_yolo_create_planned(wtk_yolo **out, const wtk_yolo_desc *d, int32_t plan) {
+// ---- The passes of wtk_yolo_create_planned, in the order the driver below calls them.  Each returns non-zero on failure (wtk_last_error says why); the
+// driver owns the half-built handle and releases everything a failed create has allocated. ----
+
+// The descriptor against the model table of its scale (ModelDims / conv_specs), which it fills in.
+static int validate_desc(wtk_yolo **out, const wtk_yolo_desc *d, int32_t plan, ModelDims &dims, std::vector<ConvSpec> &specs) {
     if (!out || !d || !d->convs) return fail("wtk_yolo_create: null argument");
     if (plan != WTK_PLAN_AUTO && plan != WTK_PLAN_THROUGHPUT && plan != WTK_PLAN_LATENCY) return fail("wtk_yolo_create_planned: plan must be WTK_PLAN_AUTO, _THROUGHPUT or _LATENCY");
     if (plan == WTK_PLAN_LATENCY && d->dtype == WTK_F16) return fail("wtk_yolo_create_planned: the latency plan is built for WTK_F32 and WTK_F16X3 handles");
@@ -545,8 +601,8 @@ extern "C" int wtk_yolo_create_planned(wtk_yolo **out, const wtk_yolo_desc *d, i
     // launch of its own (implicit GEMM over cls_ld = nc rounded up to 8 couts).  The reference trains single_cls (yolo/yolo_train_config.yaml:27).
     if (d->nc < 1 || d->nc > 80) return fail("wtk_yolo_create: nc must be in [1, 80]");
     if (wtk_device_count() <= d->device) return fail("wtk_yolo_create: no such HIP device (is a GPU visible?)");
-    const ModelDims dims = model_dims(d->width_mult, d->depth_mult, d->max_channels, d->nc);
-    const std::vector<ConvSpec> specs = conv_specs(dims);
+    dims = model_dims(d->width_mult, d->depth_mult, d->max_channels, d->nc);
+    specs = conv_specs(dims);
     if ((int)specs.size() != d->n_convs) return fail("wtk_yolo_create: n_convs does not match the model scale");
     for (size_t i = 0; i < specs.size(); ++i) {
         const wtk_conv_blob &b = d->convs[i];
@@ -562,10 +618,11 @@ extern "C" int wtk_yolo_create_planned(wtk_yolo **out, const wtk_yolo_desc *d, i
             if (dims.c[i] % 64 != 0 && !(i == 0 && dims.c[0] == 32)) return fail("wtk_yolo_create: WTK_F16X3 needs channel widths in multiples of 64 (stem: 32)");
         if (dims.hb % 32 || dims.hc % 32) return fail("wtk_yolo_create: WTK_F16X3 needs head widths in multiples of 32");
     }
-    DEVICE_GUARD(d);
-    if (ensure_attributes(d->device)) return 1;
+    return 0;
+}
 
-    wtk_yolo *h = new wtk_yolo();
+// The handle's fixed facts: dtype, the environment switches, the side-stream rule, the CU count and the plan.
+static int init_handle(wtk_yolo *h, const wtk_yolo_desc *d, const ModelDims &dims, int32_t plan, PlanSwitches &sw) {
     h->device = d->device;
     h->is_f16 = d->dtype == WTK_F16;
     h->split = d->dtype == WTK_F16X3;
@@ -574,7 +631,7 @@ extern "C" int wtk_yolo_create_planned(wtk_yolo **out, const wtk_yolo_desc *d, i
     h->S_w = d->imgsz_w;
     h->max_batch = d->max_batch;
     h->dims = dims;
-    const PlanSwitches sw = read_switches(h);
+    sw = read_switches(h);
     // Side streams are for LARGE batches.  A handle for the reference's own calls (max_batch <= 16: one frame, one cycle batch) runs on the caller's stream
     // alone: its launches last 5-50 us, and a dependency between two streams costs microseconds when the runtime has put them on different hardware
     // queues, nothing when they share one — so with side streams the same controller loop ran at 7.6 k or 4.4 k frames/s (throughput plan), 9.0 k or
@@ -582,22 +639,74 @@ extern "C" int wtk_yolo_create_planned(wtk_yolo **out, const wtk_yolo_desc *d, i
     // in every such environment (profiles/r06_notes.md section 4).  wtk_yolo_set_side_streams(h, 2) turns them on for such a handle explicitly.
     if (d->max_batch <= 16) h->use_side = 0, h->side_streams = 0;
     if (sw.no_side_stream) h->use_side = 0;
-    {
-        hipDeviceProp_t prop;
-        HIP_TRY(hipGetDeviceProperties(&prop, d->device));
-        h->num_cus = prop.multiProcessorCount;
-    }
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, d->device));
+    h->num_cus = prop.multiProcessorCount;
     h->latency = d->max_batch <= 4 && !h->is_f16;
     if (sw.latency_plan >= 0) h->latency = sw.latency_plan == 1 && !h->is_f16;
     if (plan != WTK_PLAN_AUTO) h->latency = plan == WTK_PLAN_LATENCY; // the caller's word beats the rule and the environment
     if (h->latency) h->use_tail = 0;
+    return 0;
+}
 
+// Detect tails of the level whose tower ops start at first_op (shared first conv, box.1, cls.1, box.2, cls.2): a tower's last 1x1 runs in the epilogue of the
+// 3x3 before it.
+static void fuse_detect_tails(wtk_yolo *h, size_t first_op) {
+    if (!h->use_tail) return;
+    // box tower: the last 1x1 runs in the epilogue of the 3x3 before it (fp16, 64 channels)
+    Op &b1 = h->ops[first_op + 1], &b2 = h->ops[first_op + 3];
+    if ((h->is_f16 || h->split) && b1.halo == 1 && b1.cout == 64 && b1.cout_pad == 64 && b2.k == 1 && b2.cin == 64 && b2.cout == 64 && !b2.act &&
+        b2.in_buf == b1.out_buf && b2.res_buf < 0 && b2.out2_buf < 0 && b1.res_buf < 0 && b1.out2_buf < 0 && h->halo_slabs == 3) {
+        b1.tail_op = (int)first_op + 3;
+        b2.folded = 1;
+    }
+    // class tower: 3x3 (128 -> 128) then 1x1 (128 -> nc, stored as cls_ld = 8, 16, 24 or 32 channels)
+    Op &c1 = h->ops[first_op + 2], &c2 = h->ops[first_op + 4];
+    if ((h->is_f16 || (h->split && h->use_tail_cls_split)) && c1.halo == 1 && c1.cout == 128 && c1.cout_pad == 128 && c2.k == 1 && c2.cin == 128 && c2.cout <= 32 && c2.cout_pad == 32 &&
+        !c2.act && c2.in_buf == c1.out_buf && c2.res_buf < 0 && c2.out2_buf < 0 && c1.res_buf < 0 && c1.out2_buf < 0 && h->halo_slabs == 3 &&
+        c2.cout == h->cls_ld) {
+        c1.tail_op = (int)first_op + 4;
+        c2.folded = 1;
+    }
+}
+
+// Detect level i on feature map `feat`: both towers' first 3x3 share one conv (weights concatenated along cout).
+static int plan_detect_level(Planner &P, int i, int feat) {
+    wtk_yolo *h = P.h;
+    const ModelDims &dims = h->dims;
+    const std::string b = "model.22.cv2." + std::to_string(i), cl = "model.22.cv3." + std::to_string(i);
+    const int fh = h->bufs[feat].h, fw = h->bufs[feat].w;
+    const int d1 = P.new_buf(fh, fw, dims.hb + dims.hc);
+    const int d2b = P.new_buf(fh, fw, dims.hb);
+    const int d2c = P.new_buf(fh, fw, dims.hc);
+    h->box_buf[i] = P.new_buf(fh, fw, 64);
+    h->cls_buf[i] = P.new_buf(fh, fw, h->cls_ld);
+    h->bufs[h->box_buf[i]].f32 = h->bufs[h->cls_buf[i]].f32 = 1;
+    h->lh[i] = fh;
+    h->lw[i] = fw;
+    const size_t first_op = h->ops.size();
+    if (P.conv({b + ".0", cl + ".0"}, {feat}, {d1}) ||
+        P.conv({b + ".1"}, {d1}, {d2b}) ||
+        P.conv({cl + ".1"}, {d1, dims.hb}, {d2c}) ||
+        P.conv({b + ".2"}, {d2b}, {h->box_buf[i]}) ||
+        P.conv({cl + ".2"}, {d2c}, {h->cls_buf[i]}, with_store_pad(h->cls_ld)))
+        return 1;
+    fuse_detect_tails(h, first_op);
+    h->det[i].op0 = (int)first_op, h->det[i].box1 = (int)first_op + 1, h->det[i].box2 = (int)first_op + 3;
+    if (i < 2) { // P3 and P4 towers only need t15 / t18: independent of the rest of the PAN path
+        for (size_t k = first_op; k < h->ops.size(); ++k) h->ops[k].side = i == 1 ? 2 : 1; // P4 tower: side stream 2 (folded onto stream 1 at launch time when the handle runs with one side stream)
+        h->ops[first_op].wait_feat = i;
+    }
+    return 0;
+}
+
+// The op graph: buffers, stem, backbone, SPPF, neck, Detect.
+static int build_graph(wtk_yolo *h, const wtk_yolo_desc *d, const std::vector<ConvSpec> &specs, const PlanSwitches &sw) {
     Planner P{h, specs, d->convs};
+    const ModelDims &dims = h->dims;
     const int *c = dims.c;
     const int H = h->S_h, W = h->S_w;
-    auto hw = [&](int s, int &hh, int &ww) { hh = H / s, ww = W / s; };
-    int h2, w2, h4, w4, h8, w8, h16, w16, h32, w32;
-    hw(2, h2, w2), hw(4, h4, w4), hw(8, h8, w8), hw(16, h16, w16), hw(32, h32, w32);
+    const int h2 = H / 2, w2 = W / 2, h4 = H / 4, w4 = W / 4, h8 = H / 8, w8 = W / 8, h16 = H / 16, w16 = W / 16, h32 = H / 32, w32 = W / 32;
 
     // ---- buffers that hold more than one logical tensor (concat-free FPN/PAN)
     const int t0 = P.new_buf(h2, w2, c[0]);
@@ -617,218 +726,119 @@ extern "C" int wtk_yolo_create_planned(wtk_yolo **out, const wtk_yolo_desc *d, i
     const int t21 = P.new_buf(h32, w32, c[4]);
 
     // ---- backbone
-    {
-        Op op;
-        op.kind = OP_STEM;
-        op.out_buf = t0;
-        op.cout = c[0];
-        op.macs_per_image = (double)h2 * w2 * c[0] * 27;
-        const int i0 = find_spec(specs, "model.0");
-        op.spec = i0;
-        // repack [cout][3][3][3(RGB)] -> K = tap*4 + channel (see stem_mfma_kernel)
-        const float *w0 = d->convs[i0].weight;
-        // split mode: split-fp16 operands like every other conv of the handle (pixels / 255 and the weights as hi + lo pairs)
-        const bool stem_split = h->split;
-        const int taps = (h->is_f16 || stem_split) ? 16 : 9;
-        std::vector<float> wp((size_t)c[0] * taps * 4, 0.f);
-        for (int co = 0; co < c[0]; ++co)
-            for (int tap = 0; tap < 9; ++tap)
-                for (int ch = 0; ch < 3; ++ch) // the stem reads unscaled pixels and produces scaled activations
-                    wp[((size_t)co * taps + tap) * 4 + ch] = (float)((double)w0[((size_t)co * 9 + tap) * 3 + ch] * (double)kActScale);
-        if (h->is_f16 || stem_split)
-            for (float x : wp) {
-                if (!(std::fabs(x) <= 65504.0f)) {
-                    wtk_yolo_destroy(h);
-                    return fail("wtk_yolo_create: a folded weight of conv blob " + std::to_string(i0) + " (model.0) is outside the fp16 range: this model needs dtype WTK_F32");
-                }
-            }
-        std::vector<float> stem_bias(c[0]);
-        for (int co = 0; co < c[0]; ++co) stem_bias[co] = (float)((double)d->convs[i0].bias[co] * (double)kActScale);
-        void *wdev;
-        float *bdev;
-        std::vector<uint16_t> wh;
-        const void *src = wp.data();
-        size_t bytes = wp.size() * 4;
-        if (h->is_f16) {
-            wh.resize(wp.size());
-            for (size_t i = 0; i < wp.size(); ++i) wh[i] = f32_to_f16_bits(wp[i]);
-            src = wh.data();
-            bytes = wh.size() * 2;
-        } else if (stem_split) { // [cout][16][4] hi halves, then [cout][16][4] lo halves
-            wh.resize(2 * wp.size());
-            for (size_t i = 0; i < wp.size(); ++i) {
-                const uint16_t hb = f32_to_f16_bits(wp[i]);
-                wh[i] = hb;
-                wh[wp.size() + i] = f32_to_f16_bits((wp[i] - f16_bits_to_f32(hb)) * kSplitScale);
-            }
-            src = wh.data();
-            bytes = wh.size() * 2;
-        }
-        if (dev_alloc(h, &wdev, bytes) || dev_alloc(h, (void **)&bdev, sizeof(float) * c[0])) {
-            wtk_yolo_destroy(h);
-            return 1;
-        }
-        if (hipMemcpy(wdev, src, bytes, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(bdev, stem_bias.data(), sizeof(float) * c[0], hipMemcpyHostToDevice) != hipSuccess) {
-            wtk_yolo_destroy(h);
-            return fail("wtk_yolo_create: stem weight upload failed");
-        }
-        op.w = wdev;
-        op.bias = bdev;
-        h->ops.push_back(op);
-    }
-    P.conv({"model.1"}, t0, 0, t1, 0);
-    P.c2f("model.2", t1, 0, c[1], dims.n[0], true, t2, 0);
-    P.conv({"model.3"}, t2, 0, t3, 0);
-    P.c2f("model.4", t3, 0, c[2], dims.n[1], true, cat14, c[3]);
-    P.conv({"model.5"}, cat14, c[3], t5, 0);
-    P.c2f("model.6", t5, 0, c[3], dims.n[2], true, cat11, c[4]);
-    P.conv({"model.7"}, cat11, c[4], t7, 0);
-    P.c2f("model.8", t7, 0, c[4], dims.n[3], true, t8, 0);
-    // SPPF
-    P.conv({"model.9.cv1"}, t8, 0, sppcat, 0);
-    if (!P.failed) {
-        Op op;
-        op.kind = OP_POOL;
-        op.in_buf = sppcat;
-        op.cin = c[4] / 2;
-        h->ops.push_back(op);
-    }
+    Op stem;
+    stem.kind = OP_STEM;
+    stem.out_buf = t0;
+    stem.cout = c[0];
+    stem.macs_per_image = (double)h2 * w2 * c[0] * 27;
+    stem.spec = find_spec(specs, "model.0");
+    if (pack_stem(h, stem, d->convs[stem.spec])) return 1;
+    h->ops.push_back(stem);
+    if (P.conv({"model.1"}, {t0}, {t1}) ||
+        P.c2f("model.2", {t1}, c[1], dims.n[0], true, {t2}) ||
+        P.conv({"model.3"}, {t2}, {t3}) ||
+        P.c2f("model.4", {t3}, c[2], dims.n[1], true, {cat14, c[3]}) ||
+        P.conv({"model.5"}, {cat14, c[3]}, {t5}) ||
+        P.c2f("model.6", {t5}, c[3], dims.n[2], true, {cat11, c[4]}) ||
+        P.conv({"model.7"}, {cat11, c[4]}, {t7}) ||
+        P.c2f("model.8", {t7}, c[4], dims.n[3], true, {t8}) ||
+        P.conv({"model.9.cv1"}, {t8}, {sppcat})) // SPPF
+        return 1;
+    Op pool;
+    pool.kind = OP_POOL;
+    pool.in_buf = sppcat;
+    pool.cin = c[4] / 2;
+    h->ops.push_back(pool);
     // nn.Upsample(2x nearest) + Concat: the consumer's 1x1 conv reads the half-resolution producer directly (two-source
     // loader of the 128x128 tile), so the 4x larger upsampled copy is never written.  Narrow scales whose cv1 does not
     // use that tile (and WTK_MATERIALIZE_UPSAMPLE=1) keep the materialised copy in the concat buffer.
     const bool lazy_up = c[2] % 128 == 0 && c[3] % 128 == 0 && !sw.materialize_upsample;
     if (lazy_up) {
-        P.conv({"model.9.cv2"}, sppcat, 0, cat20, c[3]); // t9 -> cat20 slice
-        P.c2f("model.12", cat11, 0, c[3], dims.n[3], false, cat17, c[2], -1, 0, cat20, c[3], c[4]); // [up(t9) | t6]; t12 -> cat17 slice
-        P.c2f("model.15", cat14, 0, c[2], dims.n[3], false, t15, 0, -1, 0, cat17, c[2], c[3]);      // [up(t12) | t4]
+        if (P.conv({"model.9.cv2"}, {sppcat}, {cat20, c[3]}) ||                                                          // t9 -> cat20 slice
+            P.c2f("model.12", {cat11}, c[3], dims.n[3], false, {cat17, c[2]}, with_in2({cat20, c[3]}, c[4])) ||           // [up(t9) | t6]; t12 -> cat17 slice
+            P.c2f("model.15", {cat14}, c[2], dims.n[3], false, {t15}, with_in2({cat17, c[2]}, c[3])))                     // [up(t12) | t4]
+            return 1;
     } else {
-        P.conv({"model.9.cv2"}, sppcat, 0, cat20, c[3], cat11, 0); // t9 -> cat20 slice, upsampled copy -> cat11
-        P.c2f("model.12", cat11, 0, c[3], dims.n[3], false, cat17, c[2], cat14, 0); // t12 -> cat17 slice, up -> cat14
-        P.c2f("model.15", cat14, 0, c[2], dims.n[3], false, t15, 0);
+        if (P.conv({"model.9.cv2"}, {sppcat}, {cat20, c[3]}, with_out2({cat11})) ||                                      // t9 -> cat20 slice, upsampled copy -> cat11
+            P.c2f("model.12", {cat11}, c[3], dims.n[3], false, {cat17, c[2]}, with_out2({cat14})) ||                      // t12 -> cat17 slice, up -> cat14
+            P.c2f("model.15", {cat14}, c[2], dims.n[3], false, {t15}))
+            return 1;
     }
-    if (!P.failed) h->ops.back().signal_feat = 0; // P3 feature map complete
-    P.conv({"model.16"}, t15, 0, cat17, 0);
-    P.c2f("model.18", cat17, 0, c[3], dims.n[3], false, t18, 0);
-    if (!P.failed) h->ops.back().signal_feat = 1; // P4 feature map complete
-    P.conv({"model.19"}, t18, 0, cat20, 0);
-    P.c2f("model.21", cat20, 0, c[4], dims.n[3], false, t21, 0);
-    // ---- Detect: both towers' first 3x3 share one conv (weights concatenated along cout)
-    const int feat[3] = {t15, t18, t21};
-    const int fh[3] = {h8, h16, h32}, fw[3] = {w8, w16, w32};
+    h->ops.back().signal_feat = 0; // P3 feature map complete
+    if (P.conv({"model.16"}, {t15}, {cat17}) || P.c2f("model.18", {cat17}, c[3], dims.n[3], false, {t18})) return 1;
+    h->ops.back().signal_feat = 1; // P4 feature map complete
+    if (P.conv({"model.19"}, {t18}, {cat20}) || P.c2f("model.21", {cat20}, c[4], dims.n[3], false, {t21})) return 1;
+    // ---- Detect
     h->cls_ld = (d->nc + 7) / 8 * 8; // class logits are stored in 16-byte groups: nc = 1 costs 16 B per anchor, not 64
-    for (int i = 0; i < 3 && !P.failed; ++i) {
-        const std::string b = "model.22.cv2." + std::to_string(i), cl = "model.22.cv3." + std::to_string(i);
-        const int d1 = P.new_buf(fh[i], fw[i], dims.hb + dims.hc);
-        const int d2b = P.new_buf(fh[i], fw[i], dims.hb);
-        const int d2c = P.new_buf(fh[i], fw[i], dims.hc);
-        h->box_buf[i] = P.new_buf(fh[i], fw[i], 64);
-        h->cls_buf[i] = P.new_buf(fh[i], fw[i], h->cls_ld);
-        h->bufs[h->box_buf[i]].f32 = h->bufs[h->cls_buf[i]].f32 = 1;
-        h->lh[i] = fh[i];
-        h->lw[i] = fw[i];
-        const size_t first_op = h->ops.size();
-        P.conv({b + ".0", cl + ".0"}, feat[i], 0, d1, 0);
-        P.conv({b + ".1"}, d1, 0, d2b, 0);
-        P.conv({cl + ".1"}, d1, dims.hb, d2c, 0);
-        P.conv({b + ".2"}, d2b, 0, h->box_buf[i], 0);
-        P.conv({cl + ".2"}, d2c, 0, h->cls_buf[i], 0, -1, 0, -1, 0, h->cls_ld);
-        if (!P.failed && h->use_tail) { // box tower: the last 1x1 runs in the epilogue of the 3x3 before it (fp16, 64 channels)
-            Op &b1 = h->ops[first_op + 1], &b2 = h->ops[first_op + 3];
-            if ((h->is_f16 || h->split) && b1.halo == 1 && b1.cout == 64 && b1.cout_pad == 64 && b2.k == 1 && b2.cin == 64 && b2.cout == 64 && !b2.act &&
-                b2.in_buf == b1.out_buf && b2.res_buf < 0 && b2.out2_buf < 0 && b1.res_buf < 0 && b1.out2_buf < 0 && h->halo_slabs == 3) {
-                b1.tail_op = (int)first_op + 3;
-                b2.folded = 1;
-            }
-            // class tower: 3x3 (128 -> 128) then 1x1 (128 -> nc, stored as cls_ld = 8, 16, 24 or 32 channels)
-            Op &c1 = h->ops[first_op + 2], &c2 = h->ops[first_op + 4];
-            if ((h->is_f16 || (h->split && h->use_tail_cls_split)) && c1.halo == 1 && c1.cout == 128 && c1.cout_pad == 128 && c2.k == 1 && c2.cin == 128 && c2.cout <= 32 && c2.cout_pad == 32 &&
-                !c2.act && c2.in_buf == c1.out_buf && c2.res_buf < 0 && c2.out2_buf < 0 && c1.res_buf < 0 && c1.out2_buf < 0 && h->halo_slabs == 3 &&
-                c2.cout == h->cls_ld) {
-                c1.tail_op = (int)first_op + 4;
-                c2.folded = 1;
-            }
-        }
-        if (!P.failed) h->det[i].op0 = (int)first_op, h->det[i].box1 = (int)first_op + 1, h->det[i].box2 = (int)first_op + 3;
-        if (!P.failed && i < 2) { // P3 and P4 towers only need t15 / t18: independent of the rest of the PAN path
-            for (size_t k = first_op; k < h->ops.size(); ++k) h->ops[k].side = i == 1 ? 2 : 1; // P4 tower: side stream 2 (folded onto stream 1 at launch time when the handle runs with one side stream)
-            h->ops[first_op].wait_feat = i;
-        }
-    }
-    // A strided 3x3 conv (128 couts, implicit GEMM, fp16) whose ONLY reader is the 1x1 conv 128 -> 128 right behind it (model.3 ->
-    // model.4.cv1 in YOLOv8s): the 1x1 runs in the 3x3's epilogue, its input never reaches HBM.  WTK_NO_IGEMM_TAIL=1 switches it off.
-    if (!P.failed && h->is_f16 && !sw.no_igemm_tail) {
-        for (size_t i = 0; i + 1 < h->ops.size(); ++i) {
-            Op &c3 = h->ops[i], &c1 = h->ops[i + 1];
-            if (c3.kind != OP_CONV || c1.kind != OP_CONV || c3.halo || c3.k != 3 || c3.stride != 2 || c3.cfg != CFG_128x128 || c3.cout != 128 || c3.cout_pad != 128 ||
-                !c3.act || c3.res_buf >= 0 || c3.out2_buf >= 0 || c3.in2_buf >= 0 || c3.tail_op >= 0 || c3.folded)
-                continue;
-            if (c1.k != 1 || c1.stride != 1 || c1.cin != 128 || c1.cout != 128 || c1.cout_pad != 128 || c1.in_buf != c3.out_buf || c1.in_coff != c3.out_coff ||
-                c1.res_buf >= 0 || c1.out2_buf >= 0 || c1.in2_buf >= 0 || c1.folded || c1.tail_op >= 0 || h->bufs[c3.out_buf].C != 128)
-                continue;
-            bool other_reader = false;
-            for (size_t j = 0; j < h->ops.size(); ++j) {
-                const Op &o = h->ops[j];
-                if (j != i + 1 && (o.in_buf == c3.out_buf || o.res_buf == c3.out_buf || o.in2_buf == c3.out_buf)) other_reader = true;
-            }
-            if (other_reader) continue;
-            c3.tail_op = (int)i + 1;
-            c1.folded = 1;
-        }
-    }
-    if (P.failed) {
-        wtk_yolo_destroy(h);
-        return 1;
-    }
+    const int feat[3] = {t15, t18, t21};
+    for (int i = 0; i < 3; ++i)
+        if (plan_detect_level(P, i, feat[i])) return 1;
     h->anchors = h8 * w8 + h16 * w16 + h32 * w32;
-    for (const Op &op : h->ops) h->macs_per_frame += op.macs_per_image;
-    // Which convs the split-K kernel (conv_sk.hip) takes, and their slab scratch.  Latency plan: everything with rows of 32 input channels.
-    // Throughput plan of a SMALL handle (max_batch <= 16, fp32 / f16x3: what a controller's cycle batch of 9 / 15 frames runs on, yolo_controller.py:108-109):
-    // the layers whose whole batch is at most 4 096 output pixels — the 12 x 12 maps of imgsz 384 — where the window / implicit-GEMM kernels run ~40-block
-    // grids that walk K serially (model.8's bottlenecks 40 us, split over K 24 us: profiles/r05_notes.md section 5); the choice is fixed per handle, so a
-    // frame's result still does not depend on its batch.  WTK_NO_SK_MIXED=1 switches the second rule off (A/B).
+    return 0;
+}
+
+// A strided 3x3 conv (128 couts, implicit GEMM, fp16) whose ONLY reader is the 1x1 conv 128 -> 128 right behind it (model.3 ->
+// model.4.cv1 in YOLOv8s): the 1x1 runs in the 3x3's epilogue, its input never reaches HBM.  WTK_NO_IGEMM_TAIL=1 switches it off.
+static void fuse_strided_tails(wtk_yolo *h, const PlanSwitches &sw) {
+    if (!h->is_f16 || sw.no_igemm_tail) return;
+    for (size_t i = 0; i + 1 < h->ops.size(); ++i) {
+        Op &c3 = h->ops[i], &c1 = h->ops[i + 1];
+        if (c3.kind != OP_CONV || c1.kind != OP_CONV || c3.halo || c3.k != 3 || c3.stride != 2 || c3.cfg != CFG_128x128 || c3.cout != 128 || c3.cout_pad != 128 ||
+            !c3.act || c3.res_buf >= 0 || c3.out2_buf >= 0 || c3.in2_buf >= 0 || c3.tail_op >= 0 || c3.folded)
+            continue;
+        if (c1.k != 1 || c1.stride != 1 || c1.cin != 128 || c1.cout != 128 || c1.cout_pad != 128 || c1.in_buf != c3.out_buf || c1.in_coff != c3.out_coff ||
+            c1.res_buf >= 0 || c1.out2_buf >= 0 || c1.in2_buf >= 0 || c1.folded || c1.tail_op >= 0 || h->bufs[c3.out_buf].C != 128)
+            continue;
+        bool other_reader = false;
+        for (size_t j = 0; j < h->ops.size(); ++j) {
+            const Op &o = h->ops[j];
+            if (j != i + 1 && (o.in_buf == c3.out_buf || o.res_buf == c3.out_buf || o.in2_buf == c3.out_buf)) other_reader = true;
+        }
+        if (other_reader) continue;
+        c3.tail_op = (int)i + 1;
+        c1.folded = 1;
+    }
+}
+
+// Which convs the split-K kernel (conv_sk.hip) takes, and their slab scratch.  Latency plan: everything with rows of 32 input channels.
+// Throughput plan of a SMALL handle (max_batch <= 16, fp32 / f16x3: what a controller's cycle batch of 9 / 15 frames runs on, yolo_controller.py:108-109):
+// the layers whose whole batch is at most 4 096 output pixels — the 12 x 12 maps of imgsz 384 — where the window / implicit-GEMM kernels run ~40-block
+// grids that walk K serially (model.8's bottlenecks 40 us, split over K 24 us: profiles/r05_notes.md section 5); the choice is fixed per handle, so a
+// frame's result still does not depend on its batch.  WTK_NO_SK_MIXED=1 switches the second rule off (A/B).  The other small-handle rules are set here too.
+static int mark_split_k(wtk_yolo *h, const PlanSwitches &sw) {
     const bool sk_mixed = !h->latency && !h->is_f16 && h->max_batch <= 16 && !sw.no_sk_mixed;
     // (f16x3: the 12 x 12 maps of imgsz 384; fp32, whose window kernels are 2.5 x slower per tap, gains on the 24 x 24 maps too — profiles/r05_notes.md section 5)
     const long long sk_mixed_max_px = h->split ? 4096 : 10000;
     h->small_narrow = !h->is_f16 && h->max_batch <= 16 && sw.small_narrow;
     h->halo_deep = h->split && (sw.halo_deep == 2 || (sw.halo_deep == 1 && h->max_batch <= 16));
-    if (h->latency || sk_mixed) {
-        for (size_t i = 3; i < h->ops.size(); ++i) { // ops[0..2] stay the fused front's
-            Op &op = h->ops[i];
-            if (op.kind != OP_CONV || op.folded || op.tail_op >= 0 || op.out2_buf >= 0 || op.cin % 32 || (op.k != 1 && op.k != 3) || op.cout_pad % 32 || op.cout % 8) continue;
-            if (op.in2_buf >= 0 && (op.k != 1 || op.in2_split % 32)) continue;
-            {
-                const Buf &ibx = h->bufs[op.in_buf]; // conv_sk_kernel addresses a tile's pixels by 32-bit lane offsets from its first image: two images inside 31 bits
-                if (2LL * ibx.h * ibx.w * ibx.C * 4 > 0x7fffffffLL) continue;
-            }
-            if (sk_mixed && (long long)h->max_batch * h->bufs[op.out_buf].h * h->bufs[op.out_buf].w > sk_mixed_max_px) continue;
-            op.sk = 1;
-            const Buf &ob = h->bufs[op.out_buf];
-            // K atoms: the count the launcher's cost model likes best for what this handle is for — a small throughput-plan handle's largest call (a cycle
-            // batch's 12 x 12 maps: eight atoms x 34 tiles are 272 blocks = two rounds on 256 CUs, seven are one round), a latency-plan handle's single frame
-            // (0.529 -> 0.515 ms at 384 x 384) — and the layer's default where the model sees no difference.  Fixed per handle, so a frame's result does not
-            // depend on its batch.
-            const long long plan_px = (long long)(h->latency ? 1 : h->max_batch) * ob.h * ob.w;
-            op.sk_atoms = conv_sk_plan_atoms(plan_px, op.cout_pad, op.k * op.k * op.cin / 32, h->num_cus, h->split);
-            const int S = op.sk_atoms;
-            if (S > 1 && dev_alloc(h, (void **)&op.sk_partial, (size_t)S * h->max_batch * ob.h * ob.w * op.cout_pad * sizeof(float))) {
-                wtk_yolo_destroy(h);
-                return 1;
-            }
-            if (S > 1 && !sw.sk_finish) { // (WTK_SK_FINISH=1, A/B switch: slabs combined by a second launch)
-                const size_t nt = conv_sk_ticket_count((long long)h->max_batch * ob.h * ob.w, op.cout_pad) * sizeof(unsigned);
-                if (dev_alloc(h, (void **)&op.sk_tickets, nt)) {
-                    wtk_yolo_destroy(h);
-                    return 1;
-                }
-                if (hipMemset(op.sk_tickets, 0, nt) != hipSuccess) {
-                    wtk_yolo_destroy(h);
-                    return fail("wtk_yolo_create: hipMemset failed");
-                }
-            }
+    if (!h->latency && !sk_mixed) return 0;
+    for (size_t i = 3; i < h->ops.size(); ++i) { // ops[0..2] stay the fused front's
+        Op &op = h->ops[i];
+        if (op.kind != OP_CONV || op.folded || op.tail_op >= 0 || op.out2_buf >= 0 || op.cin % 32 || (op.k != 1 && op.k != 3) || op.cout_pad % 32 || op.cout % 8) continue;
+        if (op.in2_buf >= 0 && (op.k != 1 || op.in2_split % 32)) continue;
+        const Buf &ib = h->bufs[op.in_buf], &ob = h->bufs[op.out_buf];
+        if (2LL * ib.h * ib.w * ib.C * 4 > 0x7fffffffLL) continue; // conv_sk_kernel addresses a tile's pixels by 32-bit lane offsets from its first image: two images inside 31 bits
+        if (sk_mixed && (long long)h->max_batch * ob.h * ob.w > sk_mixed_max_px) continue;
+        op.sk = 1;
+        // K atoms: the count the launcher's cost model likes best for what this handle is for — a small throughput-plan handle's largest call (a cycle
+        // batch's 12 x 12 maps: eight atoms x 34 tiles are 272 blocks = two rounds on 256 CUs, seven are one round), a latency-plan handle's single frame
+        // (0.529 -> 0.515 ms at 384 x 384) — and the layer's default where the model sees no difference.  Fixed per handle, so a frame's result does not
+        // depend on its batch.
+        const long long plan_px = (long long)(h->latency ? 1 : h->max_batch) * ob.h * ob.w;
+        op.sk_atoms = conv_sk_plan_atoms(plan_px, op.cout_pad, op.k * op.k * op.cin / 32, h->num_cus, h->split);
+        const int S = op.sk_atoms;
+        if (S > 1 && dev_alloc(h, (void **)&op.sk_partial, (size_t)S * h->max_batch * ob.h * ob.w * op.cout_pad * sizeof(float))) return 1;
+        if (S > 1 && !sw.sk_finish) { // (WTK_SK_FINISH=1, A/B switch: slabs combined by a second launch)
+            const size_t nt = conv_sk_ticket_count((long long)h->max_batch * ob.h * ob.w, op.cout_pad) * sizeof(unsigned);
+            if (dev_alloc(h, (void **)&op.sk_tickets, nt)) return 1;
+            if (hipMemset(op.sk_tickets, 0, nt) != hipSuccess) return fail("wtk_yolo_create: hipMemset failed");
         }
     }
-    sk_schedule(h);
+    return 0;
+}
+
+// Whether the front and the first C2f run as the fused kernels.
+static void choose_fused_front(wtk_yolo *h, const PlanSwitches &sw) {
     // ops[0..2] are stem, model.1, model.2.cv1 by construction; fuse them when the widths match the kernel
     h->use_front = !sw.no_fused_front && h->ops.size() > 3 && h->ops[0].kind == OP_STEM && h->ops[1].kind == OP_CONV && h->ops[2].kind == OP_CONV &&
                    h->ops[1].k == 3 && h->ops[1].stride == 2 && h->ops[2].k == 1 && h->ops[1].act && h->ops[2].act &&
@@ -836,69 +846,76 @@ extern "C" int wtk_yolo_create_planned(wtk_yolo **out, const wtk_yolo_desc *d, i
                    (front_fused_eligible(h->is_f16, h->ops[0].cout, h->ops[1].cout, h->ops[2].cout) ||
                     (h->split && h->ops[1].cin == 32 && front_fused_split_eligible(h->ops[0].cout, h->ops[1].cout, h->ops[2].cout)));
     // ops[3..5] are the first C2f's bottleneck convs and cv2 (dims.n[0] == 1)
-    if (!sw.no_fused_c2f && h->ops.size() > 6 && dims.n[0] == 1) {
+    if (!sw.no_fused_c2f && h->ops.size() > 6 && h->dims.n[0] == 1) {
         const Op &m1 = h->ops[3], &m2 = h->ops[4], &cv2 = h->ops[5], &cv1 = h->ops[2];
         h->use_c2f = m1.kind == OP_CONV && m2.kind == OP_CONV && cv2.kind == OP_CONV && m1.k == 3 && m2.k == 3 && cv2.k == 1 &&
                      m1.stride == 1 && m2.stride == 1 && m1.act && m2.act && cv2.act && m1.in_buf == cv1.out_buf &&
                      m2.res_buf == cv1.out_buf && m2.res_coff == m1.in_coff && cv2.in_buf == cv1.out_buf && cv2.in_coff == cv1.out_coff &&
                      m1.in_coff == cv1.out_coff + 32 && m2.out_coff == cv1.out_coff + 64 && cv2.cin == 96 && m1.Kpad == m2.Kpad &&
                      cv2.out2_buf < 0 && cv2.res_buf < 0 && m1.cout == 32 && m2.cout == 32 &&
-                     c2f_fused_eligible(h->is_f16, m1.cin, dims.n[0], m2.res_buf >= 0, cv2.cout);
+                     c2f_fused_eligible(h->is_f16, m1.cin, h->dims.n[0], m2.res_buf >= 0, cv2.cout);
     }
+}
 
-    // ---- activation workspace: every tensor gets its own allocation (288 GB HBM: no liveness reuse needed)
-    for (Buf &b : h->bufs) {
-        if (dev_alloc(h, &b.ptr, b.elems_per_image * (size_t)h->max_batch * (b.f32 ? 4 : h->esize))) {
-            wtk_yolo_destroy(h);
-            return 1;
-        }
-    }
+// Activation workspace — every tensor gets its own allocation (288 GB HBM: no liveness reuse needed) —, the output rows and the status word.
+static int alloc_workspace(wtk_yolo *h) {
+    for (Buf &b : h->bufs)
+        if (dev_alloc(h, &b.ptr, b.elems_per_image * (size_t)h->max_batch * (b.f32 ? 4 : h->esize))) return 1;
     if (dev_alloc(h, (void **)&h->o_xywh, sizeof(float) * 4 * h->max_batch) || dev_alloc(h, (void **)&h->o_conf, sizeof(float) * h->max_batch) ||
-        dev_alloc(h, (void **)&h->o_anchor, sizeof(int) * h->max_batch) || dev_alloc(h, (void **)&h->o_margin, sizeof(float) * h->max_batch)) {
-        wtk_yolo_destroy(h);
+        dev_alloc(h, (void **)&h->o_anchor, sizeof(int) * h->max_batch) || dev_alloc(h, (void **)&h->o_margin, sizeof(float) * h->max_batch))
         return 1;
-    }
     if (acquire_status_word(&h->status_host, &h->status_dev)) {
         h->status_host = nullptr;
-        wtk_yolo_destroy(h);
         return fail("wtk_yolo_create: no pinned status word (hipHostMalloc failed, or more than 4096 live handles)");
     }
-    // Live mask of the sparse box towers, behind the zero page: per level two arrays (box.0's units, box.1 + box.2's) of strips x ld bytes, ld = the
-    // 128-pixel units of a strip's stacked rows, rounded up to an even count (wtk_run.hip: resolve_sparse lays a call's arrays out the same way).
-    // Split (f16x3) throughput-plan handles only: there the shared first conv of a tower pair runs as three 64-cout tiles, so its box and class halves keep
-    // tile and bits; fp16 / fp32 run it as one 192-cout tile, whose halves would land on other instantiations.
-    // ... and only handles whose largest call reaches the size from which a sparse call pays (sparse_box_pays below; a per-call rule).
+    return 0;
+}
+
+// The zero page and, behind it in the same allocation, the sparse region of the Detect box towers (wtk_internal.h: SparseMask lays it out, here for max_batch,
+// in wtk_run.hip: resolve_sparse for a call's batch).
+// Split (f16x3) throughput-plan handles only: there the shared first conv of a tower pair runs as three 64-cout tiles, so its box and class halves keep
+// tile and bits; fp16 / fp32 run it as one 192-cout tile, whose halves would land on other instantiations.
+// ... and only handles whose largest call reaches the size from which a sparse call pays (sparse_box_pays; a per-call rule).
+static int alloc_sparse_region(wtk_yolo *h) {
     if (h->split && !h->latency && h->use_sparse_box && h->max_batch > wtk::kSparseMaxDenseBatch &&
         wtk::sparse_box_pays(h->max_batch, h->lh[0], h->lw[0], h->num_cus, h->sparse_min_tenths)) {
-        size_t total = 0;
-        int per_frame = 0;
+        wtk::SparseMask m;
         for (int i = 0; i < 3; ++i) {
             int S, pitch, strips, bps;
             halo_geometry_stacked(h->max_batch, h->lh[i], h->lw[i], kHaloRowsMax, &S, &pitch, &strips, &bps, 256);
-            total += 2 * (((size_t)strips * 2 * bps + 3) & ~(size_t)3);
-            per_frame = std::max(per_frame, wtk::sparse_units_per_frame(pitch, strips));
+            wtk::sparse_mask_add_level(m, i, h->max_batch, h->lh[i], pitch, strips);
         }
-        h->live_mask_bytes = h->live_bytes = total;
-        if (h->use_sparse_list) { // counters and the two tile lists (wtk_internal.h): a frame lists at most per_frame tiles for box.0 and one for box.1 + box.2
-            h->live_list_cap[0] = (unsigned)h->max_batch * (unsigned)per_frame, h->live_list_cap[1] = (unsigned)h->max_batch;
-            h->live_bytes = total + 16 + 4 * ((size_t)h->live_list_cap[0] + h->live_list_cap[1]);
+        h->live_mask_bytes = h->live_bytes = m.bytes;
+        if (h->use_sparse_list) { // counters and the two tile lists: a frame lists at most units_per_frame tiles for box.0 and one for box.1 + box.2
+            for (int s = 0; s < 2; ++s) h->live_list_cap[s] = wtk::sparse_list_cap(m, s, h->max_batch);
+            h->live_bytes = wtk::sparse_region_bytes(m.bytes, h->live_list_cap);
         }
-        if (dev_alloc(h, (void **)&h->sel_anchor, sizeof(int) * h->max_batch) || dev_alloc(h, (void **)&h->sel_score, sizeof(float) * h->max_batch)) {
-            wtk_yolo_destroy(h);
-            return 1;
-        }
+        if (dev_alloc(h, (void **)&h->sel_anchor, sizeof(int) * h->max_batch) || dev_alloc(h, (void **)&h->sel_score, sizeof(float) * h->max_batch)) return 1;
     }
-    if (dev_alloc(h, &h->zero_page, 256 + h->live_bytes)) {
-        wtk_yolo_destroy(h);
-        return 1;
-    }
-    if (hipMemset(h->zero_page, 0, 256 + h->live_bytes) != hipSuccess) {
-        wtk_yolo_destroy(h);
-        return fail("wtk_yolo_create: hipMemset failed");
-    }
+    if (dev_alloc(h, &h->zero_page, wtk::kZeroPageBytes + h->live_bytes)) return 1;
+    if (hipMemset(h->zero_page, 0, wtk::kZeroPageBytes + h->live_bytes) != hipSuccess) return fail("wtk_yolo_create: hipMemset failed");
+    return 0;
+}
+
+extern "C" int wtk_yolo_create_planned(wtk_yolo **out, const wtk_yolo_desc *d, int32_t plan) {
+    ModelDims dims;
+    std::vector<ConvSpec> specs;
+    if (validate_desc(out, d, plan, dims, specs)) return 1;
+    DEVICE_GUARD(d);
+    if (ensure_attributes(d->device)) return 1;
+    std::unique_ptr<wtk_yolo, void (*)(wtk_yolo *)> owner(new wtk_yolo(), wtk_yolo_destroy); // a failed create releases whatever the passes allocated
+    wtk_yolo *h = owner.get();
+    PlanSwitches sw;
+    if (init_handle(h, d, dims, plan, sw) || build_graph(h, d, specs, sw)) return 1;
+    fuse_strided_tails(h, sw);
+    for (const Op &op : h->ops) h->macs_per_frame += op.macs_per_image;
+    if (mark_split_k(h, sw)) return 1;
+    sk_schedule(h);
+    choose_fused_front(h, sw);
+    if (alloc_workspace(h) || alloc_sparse_region(h)) return 1;
     // streams (side streams, the host entry points' stream) are taken from the process pool at first use: a handle that never runs
     // with side streams (the hybrid's second look) or never sees a host call does not occupy a hardware queue slot
-    *out = h;
+    *out = owner.release();
     return 0;
 }
 

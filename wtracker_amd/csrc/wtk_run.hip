@@ -316,8 +316,7 @@ static bool resolve_sparse(const wtk_yolo *h, int B, SparseBox &sp) {
     if (!h->use_sparse_box || !h->split || h->latency || !h->live_bytes) return false;
     if (!sparse_box_pays(B, h->lh[0], h->lw[0], h->num_cus, h->sparse_min_tenths)) return false; // a call too small for the sparse tail to pay (wtk_internal.h)
     std::memset(&sp.hs, 0, sizeof(sp.hs));
-    unsigned off = 0;
-    int per_frame = 0;
+    SparseMask m; // this call's mask arrays inside the region that wtk_plan.hip sized for max_batch (wtk_internal.h)
     for (int l = 0; l < 3; ++l) {
         const wtk_yolo::DetLevel &d = h->det[l];
         if (d.op0 < 0 || d.box1 < 0 || d.box2 < 0) return false;
@@ -328,20 +327,16 @@ static bool resolve_sparse(const wtk_yolo *h, int B, SparseBox &sp) {
         if (r0.kind != L_HALO_SPLIT || r1.kind != L_HALO_SPLIT || r0.g.res || r0.g.out2 || r1.g.res || r1.g.out2) return false;
         if (split_halo_cout_tile(o0.cout) != 64 || r0.g.narrow || r1.g.narrow) return false; // the dense launch must already run on 64-cout tiles
         if (r0.g.S != r1.g.S || r0.g.pitch != r1.g.pitch || r0.g.strips != r1.g.strips) return false;
-        // mask layout of this call (wtk_plan.hip sized the region for max_batch): per level live0 then live1, strips x ld bytes each
-        const int ld = 2 * (int)(((long long)B * (h->lh[l] + 1) * r0.g.pitch + 255) / 256);
-        const unsigned bytes = ((unsigned)r0.g.strips * (unsigned)ld + 3u) & ~3u;
-        sp.hs.S[l] = r0.g.S, sp.hs.pitch[l] = r0.g.pitch, sp.hs.ld[l] = ld;
-        sp.hs.off0[l] = off, sp.hs.off1[l] = off + bytes;
-        off += 2 * bytes;
-        if (off > h->live_mask_bytes) return false;
-        per_frame = std::max(per_frame, sparse_units_per_frame(r0.g.pitch, r0.g.strips));
+        sparse_mask_add_level(m, l, B, h->lh[l], r0.g.pitch, r0.g.strips);
+        if (m.bytes > h->live_mask_bytes) return false;
+        sp.hs.S[l] = r0.g.S, sp.hs.pitch[l] = r0.g.pitch, sp.hs.ld[l] = m.ld[l];
+        sp.hs.off0[l] = m.off0[l], sp.hs.off1[l] = m.off1[l];
         // the two halves of the shared conv: rows [0, hb) and [hb, hb + hc) of its packed weights and bias, the same slices of d1.  64-cout tiles either way
         // (narrow: the class half's 128 couts would otherwise pick the 128-cout tile)
         const int hb = h->dims.hb;
         sp.box0[l] = r0;
         sp.box0[l].g.Cout = sp.box0[l].g.CoutPad = hb;
-        sp.box0[l].g.live_off = 256u + sp.hs.off0[l], sp.box0[l].g.live_ld = ld;
+        sp.box0[l].g.live_off = kZeroPageBytes + m.off0[l], sp.box0[l].g.live_ld = m.ld[l];
         sp.cls0[l] = r0;
         HaloArgs &c = sp.cls0[l].g;
         c.Cout = c.CoutPad = o0.cout - hb, c.narrow = 1;
@@ -349,16 +344,16 @@ static bool resolve_sparse(const wtk_yolo *h, int B, SparseBox &sp) {
         c.bias = c.bias + hb;
         c.out_coff += 2 * hb; // pseudo-channels
         sp.box1[l] = r1;
-        sp.box1[l].g.live_off = 256u + sp.hs.off1[l], sp.box1[l].g.live_ld = ld;
+        sp.box1[l].g.live_off = kZeroPageBytes + m.off1[l], sp.box1[l].g.live_ld = m.ld[l];
     }
-    sp.hs.live = reinterpret_cast<unsigned char *>(h->zero_page) + 256;
+    sp.hs.live = reinterpret_cast<unsigned char *>(h->zero_page) + kZeroPageBytes;
     sp.hs.sel_anchor = h->sel_anchor, sp.hs.sel_score = h->sel_score, sp.hs.n_dyn = h->n_dyn;
     sp.list_grid[0] = sp.list_grid[1] = 0;
-    if (h->use_sparse_list) { // counters and lists behind the mask (wtk_plan.hip); a call lists at most B * per_frame tiles for box.0 and B for box.1 + box.2
-        sp.list_grid[0] = (unsigned)B * (unsigned)per_frame, sp.list_grid[1] = (unsigned)B;
+    if (h->use_sparse_list) { // counters and lists behind the handle's mask; a call lists at most B * units_per_frame tiles for box.0 and B for box.1 + box.2
+        for (int s = 0; s < 2; ++s) sp.list_grid[s] = sparse_list_cap(m, s, B);
         if (sp.list_grid[0] > h->live_list_cap[0] || sp.list_grid[1] > h->live_list_cap[1]) return false;
-        sp.hs.count = reinterpret_cast<unsigned *>(sp.hs.live + h->live_mask_bytes);
-        sp.hs.list[0] = sp.hs.count + 4, sp.hs.list[1] = sp.hs.list[0] + h->live_list_cap[0];
+        sp.hs.count = reinterpret_cast<unsigned *>(sp.hs.live + sparse_count_off(h->live_mask_bytes));
+        for (int s = 0; s < 2; ++s) sp.hs.list[s] = reinterpret_cast<unsigned *>(sp.hs.live + sparse_list_off(h->live_mask_bytes, h->live_list_cap, s));
         sp.hs.cap[0] = sp.list_grid[0], sp.hs.cap[1] = sp.list_grid[1];
     }
     return true;
@@ -927,7 +922,8 @@ extern "C" int wtk_yolo_debug_tensor(wtk_yolo *h, int32_t conv_index, int32_t B,
         if (h->live_list_cap[0]) {
             DEVICE_GUARD(h);
             HIP_TRY(hipDeviceSynchronize());
-            HIP_TRY(hipMemcpy(cnt, reinterpret_cast<const char *>(h->zero_page) + 256 + h->live_mask_bytes + 8, sizeof(cnt), hipMemcpyDeviceToHost));
+            // count[2], count[3]: where head_decode_kernel leaves the two stages' counts (HeadSparseArgs)
+            HIP_TRY(hipMemcpy(cnt, reinterpret_cast<const char *>(h->zero_page) + kZeroPageBytes + sparse_count_off(h->live_mask_bytes) + 2 * sizeof(unsigned), sizeof(cnt), hipMemcpyDeviceToHost));
         }
         out_host[0] = (float)cnt[0], out_host[1] = (float)cnt[1], out_host[2] = (float)h->sparse_grid[0], out_host[3] = (float)h->sparse_grid[1];
         return 0;
