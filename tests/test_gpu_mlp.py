@@ -11,6 +11,7 @@ from oracle import resmlp_oracle
 from wtracker_amd import hip, resmlp
 from wtracker_amd.controllers import HipMLPController
 from wtracker_amd.sim import ExperimentConfig, TimingConfig, TrackLogger
+from harness import mlp_ref
 from harness.sim_harness import Simulator
 
 pytestmark = pytest.mark.gpu
@@ -39,10 +40,19 @@ def test_forward_matches_reference_golden(hip_lib, golden_dir, tag):
 @pytest.mark.parametrize("tag", ["100ms", "200ms"])
 def test_forward_matches_oracle_on_large_batch(hip_lib, golden_dir, tag):
     st = resmlp_oracle.load_state(os.path.join(golden_dir, f"resmlp_{tag}.npz"))
-    _, g = _mlp(golden_dir, tag)
+    m, g = _mlp(golden_dir, tag)
     rng = np.random.default_rng(5)
     x = rng.normal(0, 6, size=(5556, 28)).astype(np.float32)  # BASELINE C4: 50 000 / 9 cycles
-    np.testing.assert_allclose(g.forward_host(x), resmlp_oracle.forward(st, x), rtol=1e-4, atol=5e-4)
+    y = g.forward_host(x)
+    np.testing.assert_allclose(y, resmlp_oracle.forward(st, x), rtol=1e-4, atol=5e-4)
+    # ... and against the UNFOLDED float64 network, within 8 x what a sequential fp32 forward deviates from it (harness/mlp_ref.py): the bound
+    # above admits errors dozens of times larger than any honest fp32 result at |y| ~ 16-50
+    sd, acts = mlp_ref.fixture_network(os.path.join(golden_dir, f"resmlp_{tag}.npz"))
+    y64, tol = mlp_ref.forward64(sd, acts, x), mlp_ref.tolerance(sd, acts, x)
+    row = mlp_ref.Row(f"shipped {tag}", mlp_ref.param_path(m.layers), len(m.layers), mlp_ref.blob_floats(m.layers), float(np.abs(y - y64).max()), tol,
+                      float(np.abs(y64).max()))
+    print("\n" + mlp_ref.table("shipped predictor, 5556 samples", [row]))
+    assert row.dev <= tol, row
 
 
 @pytest.mark.parametrize("tag,timing,name", [("100ms", (100, 40, 50), "sim_mlp_bboxes.csv"), ("200ms", (200, 40, 50), "sim_mlp200_bboxes.csv")])
@@ -151,7 +161,7 @@ def test_device_polyfit_and_median_against_numpy_on_ragged_tracks(hip_lib):
     track[100:140] = np.nan
     centers = np.stack([track[:, 0] + track[:, 2] / 2, track[:, 1] + track[:, 3] / 2], axis=1)
     n_cycles = n // cyc + 2
-    times, weights, deg = np.array([-9, -6, -3, 0, 2, 4]), np.array([1, 1, 2, 3, 4, 5.0]), 3
+    times, weights = np.array([-9, -6, -3, 0, 2, 4]), np.array([1, 1, 2, 3, 4, 5.0])
     for dtype in (torch.float64, torch.float32):
         tr = torch.from_numpy(track).to(dtype).cuda()
         trn = tr.double().cpu().numpy()
@@ -171,25 +181,26 @@ def test_device_polyfit_and_median_against_numpy_on_ragged_tracks(hip_lib):
             if len(w):
                 np.testing.assert_array_equal(p[c], np.median(w, axis=0))  # bit-exact: sort + mean of the middle pair
         assert seen == {0, 1, 2}
-        hip.track_polyfit(tr, n, cycles, n_cycles, cyc, times, weights, deg, cyc + img // 2, pred, valid)
-        torch.cuda.synchronize()
-        p, v = pred.cpu().numpy(), valid.cpu().numpy()
-        ranks = set()
-        for c in range(n_cycles):
-            f = c * cyc + times
-            ok = (f >= 0) & (f < n)
-            ok[ok] &= np.isfinite(cen[f[ok]]).all(axis=1)
-            assert bool(v[c]) == bool(ok.any())
-            if ok.any():
-                import warnings
+        for deg in range(4):
+            hip.track_polyfit(tr, n, cycles, n_cycles, cyc, times, weights, deg, cyc + img // 2, pred, valid)
+            torch.cuda.synchronize()
+            p, v = pred.cpu().numpy(), valid.cpu().numpy()
+            ranks = set()
+            for c in range(n_cycles):
+                f = c * cyc + times
+                ok = (f >= 0) & (f < n)
+                ok[ok] &= np.isfinite(cen[f[ok]]).all(axis=1)
+                assert bool(v[c]) == bool(ok.any())
+                if ok.any():
+                    import warnings
 
-                with warnings.catch_warnings():
-                    warnings.simplefilter("ignore")  # RankWarning on under-determined cycles: numpy returns the minimum-norm fit
-                    coef = poly.polyfit(times[ok], cen[f[ok]], deg=deg, w=weights[ok])
-                want = poly.polyval(cyc + img // 2, coef)
-                ranks.add(min(int(ok.sum()), deg + 1))
-                np.testing.assert_allclose(p[c], want, rtol=0, atol=1e-6)
-        assert ranks == {1, 2, 3, 4}  # under-determined cycles are exercised
+                    with warnings.catch_warnings():
+                        warnings.simplefilter("ignore")  # RankWarning on under-determined cycles: numpy returns the minimum-norm fit
+                        coef = poly.polyfit(times[ok], cen[f[ok]], deg=deg, w=weights[ok])
+                    want = poly.polyval(cyc + img // 2, coef)
+                    ranks.add(min(int(ok.sum()), deg + 1))
+                    np.testing.assert_allclose(p[c], want, rtol=0, atol=1e-6, err_msg=f"degree {deg}, cycle {c}")
+            assert ranks == set(range(1, deg + 2))  # under-determined cycles are exercised (degree 3: 1, 2, 3 samples for 4 coefficients)
 
 
 def test_device_training_pairs_match_reference_dataset(hip_lib, golden_dir):

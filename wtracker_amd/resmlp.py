@@ -77,7 +77,11 @@ def fold_state_dict(sd: Mapping[str, np.ndarray], input_frames: Sequence[int], p
     per_block = 0
     if n_blocks:
         per_block = len({int(m.group(1)) for k in sd for m in [re.match(r"model\.blocks\.0\.sequence\.(\d+)\.", k)] if m})
-    prefixes = ["model.input.mlp_layer"] + [f"model.blocks.{b}.sequence.{l}.mlp_layer" for b in range(n_blocks) for l in range(per_block)]
+    if "model.input.mlp_layer.0.weight" not in sd:
+        # RMLP(in_dim=None) has an nn.Identity input and no `model.input.*` keys; the device kernel always starts with an input layer
+        raise WtkError("ResMLP: the state dict has no input layer (model.input.mlp_layer.0.weight is missing): "
+                       "a predictor built with in_dim=None (identity input) is not supported by mlp_kernel")
+    prefixes = ["model.input.mlp_layer"] +[f"model.blocks.{b}.sequence.{l}.mlp_layer" for b in range(n_blocks) for l in range(per_block)]
     if activations is not None and len(activations) != len(prefixes):
         raise WtkError(f"ResMLP: {len(activations)} activations given for {len(prefixes)} layers")
     layers = [_fold(p, sd, None if activations is None else activations[i]) for i, p in enumerate(prefixes)]
