@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define WTK_ABI_VERSION 7 /* 7: + wtk_yolo_create_planned / wtk_yolo_plan, wtk_yolo_status (additive); 2: + wtk_yolo_predict_views / _nms, wtk_track_*, wtk_comm_*; 3: + WTK_F16X3, wtk_recheck_*; 4: + wtk_recheck_select_counted; 5: + wtk_recheck_enqueue / _scatter; 6: + wtk_hybrid_*; still 7: + wtk_background, wtk_precise_error (additive: every earlier entry point is unchanged); still 7: + wtk_polyfit_*; still 7: + wtk_replay_* (additive) */
+#define WTK_ABI_VERSION 7 /* 7: + wtk_yolo_create_planned / wtk_yolo_plan, wtk_yolo_status (additive); 2: + wtk_yolo_predict_views / _nms, wtk_track_*, wtk_comm_*; 3: + WTK_F16X3, wtk_recheck_*; 4: + wtk_recheck_select_counted; 5: + wtk_recheck_enqueue / _scatter; 6: + wtk_hybrid_*; still 7: + wtk_background, wtk_precise_error (additive: every earlier entry point is unchanged); still 7: + wtk_polyfit_*; still 7: + wtk_replay_* (additive); still 7: + wtk_replay_polyfit_targets / _scratch_doubles, wtk_replay_objective (additive) */
 
 typedef enum wtk_dtype {
     WTK_F32 = 0, /* fp32 storage, exact-fp32 MFMA (v_mfma_f32_16x16x4_f32): parity mode   */
@@ -542,6 +542,42 @@ int wtk_replay_rows(const wtk_replay_config *cfg, int32_t E, int32_t n_cycles, c
                     const double *share_dev, const int32_t *pos_dev, const int32_t *move_dev, const int32_t *row_slot_dev, int32_t n_slots,
                     double *rows_dev, double *bbox_err_dev, double *mse_err_dev, double *summary_dev, double *scratch_dev,
                     int64_t scratch_doubles, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The closed-loop error as the objective of the Polyfit weight search (csrc/replay.hip).
+ *
+ * wtk_replay_polyfit_targets   the per-cycle Polyfit targets of P weight vectors in one call: a_dev [n_cycles][P][2], valid_dev
+ *     [n_cycles][P], what wtk_replay_scan reads.  weights_dev [P][n_times] doubles on the device (the swarm's position buffer); one degree,
+ *     one set of sample_times_host (frame offsets from the cycle's start, weight j belongs to time j) and one t_eval for all of them.  For
+ *     every (cycle, particle) the result has the bits wtk_track_polyfit (float64 track) gives for that cycle with that particle's weights.
+ *     The SVD of a fit depends on the weights and on which samples are finite only, so the caller groups the cycles: class_mask_dev
+ *     [n_classes] (bit j set: sample j of the cycle lies inside the track and its centre x + w / 2, y + h / 2 is finite), cycle_class_dev
+ *     [n_cycles] the class of each cycle.  One SVD per (class, particle), then one thread per (cycle, particle).  A cycle whose samples
+ *     are not the ones its class names (or whose class index is out of range) gets valid = 0; so do a class without samples and a solve
+ *     that did not converge.  scratch_dev: wtk_replay_polyfit_targets_scratch_doubles(n_classes, P, n_times, degree) doubles (-1: bad sizes).
+ * wtk_replay_objective   wtk_replay_scan, then the reduction of wtk_replay_rows without row, per-row or slot output, then
+ *     objective_dev[e] = one float64 division of experiment e's summary: WTK_REPLAY_OBJ_TRIMMED_BBOX summary[2] / summary[3] (the rows
+ *     DataAnalyzer.clean(trim_cycles=True, imaging_only=True) keeps), _MEAN_BBOX [0] / [1], _MEAN_MSE [5] / [1], _NON_PERFECT [4] / [1];
+ *     0 / 0 is NaN.  pos_dev / move_dev / summary_dev / scratch_dev are the work buffers of the two steps, sized as for them.
+ * stop_dev (nullable): when *stop_dev != 0 at run time every launch of the call returns at once and no memory is touched (the ctrl
+ *     word of wtk_polyfit_swarm_step: all epochs of a search are enqueued back to back).
+ * Refused (error code, no memory touched): n_times outside 1..16, degree outside 0..7, P outside 1..65535, n_classes outside
+ *     1..n_cycles, scratch too small, a required pointer that is null; wtk_replay_objective: what wtk_replay_scan / _rows refuse, an unknown
+ *     objective, the trimmed objective with fewer than 3 logged cycles.
+ * ------------------------------------------------------------------------------------------ */
+#define WTK_REPLAY_OBJ_TRIMMED_BBOX 0
+#define WTK_REPLAY_OBJ_MEAN_BBOX 1
+#define WTK_REPLAY_OBJ_MEAN_MSE 2
+#define WTK_REPLAY_OBJ_NON_PERFECT 3
+int64_t wtk_replay_polyfit_targets_scratch_doubles(int32_t n_classes, int32_t P, int32_t n_times, int32_t degree);
+int wtk_replay_polyfit_targets(const double *track_dev, int32_t n_track, int32_t n_cycles, int32_t cycle_frame_num, const double *weights_dev,
+                               int32_t P, const int32_t *sample_times_host, int32_t n_times, int32_t degree, double t_eval,
+                               const int32_t *cycle_class_dev, const int32_t *class_mask_dev, int32_t n_classes, double *a_dev,
+                               int32_t *valid_dev, double *scratch_dev, int64_t scratch_doubles, const int32_t *stop_dev, void *stream);
+int wtk_replay_objective(const wtk_replay_config *cfg, int32_t kind, int32_t E, int32_t n_cycles, const double *track_dev, int32_t n_track,
+                         const double *a_dev, const double *b_dev, const int32_t *valid_dev, const double *share_dev, int32_t *pos_dev,
+                         int32_t *move_dev, double *summary_dev, double *scratch_dev, int64_t scratch_doubles, int32_t objective,
+                         double *objective_dev, const int32_t *stop_dev, void *stream);
 
 #ifdef __cplusplus
 }

@@ -11,8 +11,17 @@
 //           scan's arithmetic), camera / microscope / logged worm box, bbox and MSE error of the row; per-experiment sums in a FIXED order: lane-serial
 //           over the chunk, a binary tree in LDS, and a finish launch that adds the chunk partials in index order (the scheme of wtk_polyfit_weight_mae).
 //           The chunking depends on the row count only: an experiment gives the same bits alone and inside any population.  No floating-point atomics.
+//   targets one call for the per-cycle Polyfit targets of a whole POPULATION of weight vectors (the weight search's position buffer, on the device), in the
+//           layout the scan reads.  The <= 16 x 8 SVD of a fit depends on the weights and on WHICH samples of the cycle are finite only, so the cycles are
+//           grouped by that set (a <= 16-bit mask; the caller derives the classes from the track once): pass A solves one SVD per (class, particle) and
+//           keeps the rotated matrix, V, s^2, scl and the compacted weights particle-minor in scratch; pass B, one thread per (cycle, particle), reads its
+//           class's record and the cycle's centres (LDS: one cycle per block) and does track_polyfit_kernel<double>'s dot products and Horner evaluation.
+//           Every operation and its order are that kernel's: the targets have its bits.
+//   objective  scan + rows (no row, per-row or slot output) + one division per experiment: the swarm's objective without a host round trip.
+//   A nullable stop flag (the swarm's ctrl word) turns the targets, the objective and, through them only, the scan and the rows reduction into no-ops.
 // Everything relies on -ffp-contract=off (the library's build flag): share * move + carry is a rounded product and a rounded sum, as in Python.
 #include "wtk_internal.h"
+#include "jacobi_svd.h"
 
 #include <cmath>
 
@@ -45,6 +54,7 @@ struct ScanArgs {
     const double *share; // [M]
     int *pos;  // [C][E][2]
     int *move; // [C][E][2]
+    const int *stop; // nullable: *stop != 0 -> the launch touches nothing (wtk_replay_objective only)
 };
 
 struct RowsArgs {
@@ -60,7 +70,38 @@ struct RowsArgs {
     double *bbox_err, *mse_err; // [E][R] (nullable)
     double *partial;       // [E][S][kSummary]
     double *summary;       // [E][kSummary]
+    const int *stop;       // nullable, as ScanArgs::stop
 };
+
+struct PopArgs {
+    const double *track; // [n_track][4] xywh
+    int n_track, L;
+    const double *weights; // [P][n_times]
+    int P, C, n_times, degree, n_classes;
+    int times[kTrackMaxTimes];
+    double t_eval;
+    const int *cycle_class; // [C]
+    const int *class_mask;  // [n_classes]: bit j = sample j of the cycle is inside the track and has a finite centre
+    double *rec;            // [n_classes][pop_record(n_times, K)][P]
+    double *a;              // [C][P][2]
+    int *valid;             // [C][P]
+    const int *stop;
+};
+
+struct ObjectiveArgs {
+    const double *summary; // [E][kSummary]
+    double *objective;     // [E]
+    int E, num, den;       // objective = summary[num] / summary[den]
+    const int *stop;
+};
+
+// fields of a (class, particle) record, each P doubles apart: L_rot [n_times][K], V [K][K], s2 [K], scl [K], compacted weights [n_times], converged
+__host__ __device__ inline int pop_off_V(int n_times, int K) { return n_times * K; }
+__host__ __device__ inline int pop_off_s2(int n_times, int K) { return n_times * K + K * K; }
+__host__ __device__ inline int pop_off_scl(int n_times, int K) { return n_times * K + K * K + K; }
+__host__ __device__ inline int pop_off_w(int n_times, int K) { return n_times * K + K * K + 2 * K; }
+__host__ __device__ inline int pop_off_ok(int n_times, int K) { return n_times * K + K * K + 2 * K + n_times; }
+__host__ __device__ inline int pop_record(int n_times, int K) { return n_times * K + K * K + 2 * K + n_times + 1; }
 
 // one step of SineMotorController.step + ViewController.move_position on one axis
 __device__ __forceinline__ void motor_axis(double share, double mv, double &carry, int &pos, int pos_max) {
@@ -77,6 +118,7 @@ __device__ __forceinline__ double finish_move(double v) {
 }
 
 __global__ __launch_bounds__(kScanThreads) void replay_scan_kernel(const ScanArgs a) {
+    if (a.stop && *a.stop) return;
     const int e = blockIdx.x * kScanThreads + threadIdx.x;
     if (e >= a.E) return;
     const Geometry g = a.g;
@@ -121,6 +163,7 @@ __global__ __launch_bounds__(kScanThreads) void replay_scan_kernel(const ScanArg
 
 __global__ __launch_bounds__(kRowThreads) void replay_rows_kernel(const RowsArgs a) {
     __shared__ double red[kSummary][kRowThreads];
+    if (a.stop && *a.stop) return; // block-uniform
     const Geometry g = a.g;
     const int e = blockIdx.x / a.S, s = blockIdx.x - e * a.S;
     int slot = a.row_slot ? a.row_slot[e] : -1;
@@ -187,6 +230,7 @@ __global__ __launch_bounds__(kRowThreads) void replay_rows_kernel(const RowsArgs
 }
 
 __global__ __launch_bounds__(64) void replay_finish_kernel(const RowsArgs a) {
+    if (a.stop && *a.stop) return;
     const long long i = (long long)blockIdx.x * 64 + threadIdx.x;
     if (i >= (long long)a.E * kSummary) return;
     const long long e = i / kSummary;
@@ -194,6 +238,146 @@ __global__ __launch_bounds__(64) void replay_finish_kernel(const RowsArgs a) {
     double sum = 0.0;
     for (int s = 0; s < a.S; ++s) sum += a.partial[(e * a.S + s) * kSummary + q];
     a.summary[i] = sum;
+}
+
+__global__ __launch_bounds__(64) void replay_objective_kernel(const ObjectiveArgs a) {
+    if (a.stop && *a.stop) return;
+    const int e = blockIdx.x * 64 + threadIdx.x;
+    if (e >= a.E) return;
+    // the float64 division Summary's properties perform on the host (counts are exact doubles); 0 / 0 = NaN, which the swarm never lets win
+    a.objective[e] = a.summary[(long long)e * kSummary + a.num] / a.summary[(long long)e * kSummary + a.den];
+}
+
+// Pass A of the population targets: one thread per (class, particle).  track_polyfit_kernel's compaction, scl, scaled Vandermonde matrix and SVD for the
+// samples the class keeps; the record is written particle-minor (a wave of consecutive particles writes consecutive addresses).
+__global__ __launch_bounds__(64) void replay_polyfit_solve_kernel(const PopArgs a) {
+    if (a.stop && *a.stop) return;
+    const int PB = (a.P + 63) / 64;
+    const int k = blockIdx.x / PB, p = (blockIdx.x - k * PB) * 64 + threadIdx.x;
+    if (p >= a.P) return;
+    const int K = a.degree + 1;
+    const unsigned mask = (unsigned)a.class_mask[k] & ((1u << a.n_times) - 1u);
+    double tt[kTrackMaxTimes], ww[kTrackMaxTimes];
+    int n = 0;
+    for (int j = 0; j < a.n_times; ++j)
+        if ((mask >> j) & 1u) tt[n] = (double)a.times[j], ww[n] = a.weights[(long long)p * a.n_times + j], ++n;
+    if (n == 0) return; // no sample: pass B writes valid = 0 without looking at the record
+    // scaled weighted Vandermonde: L[j][q] = w_j t_j^q / scl_q
+    double scl[kTrackMaxCoef];
+    for (int q = 0; q < K; ++q) scl[q] = 0.0;
+    for (int j = 0; j < n; ++j) {
+        double tp = 1.0; // t^q by repeated multiplication, as numpy's vander
+        for (int q = 0; q < K; ++q) {
+            const double v = ww[j] * tp;
+            scl[q] += v * v;
+            tp *= tt[j];
+        }
+    }
+    for (int q = 0; q < K; ++q) scl[q] = scl[q] > 0.0 ? sqrt(scl[q]) : 1.0;
+    double L[kTrackMaxTimes][kTrackMaxCoef], V[kTrackMaxCoef][kTrackMaxCoef];
+    for (int j = 0; j < n; ++j) {
+        double tp = 1.0;
+        for (int q = 0; q < K; ++q) L[j][q] = ww[j] * tp / scl[q], tp *= tt[j];
+    }
+    double *r = a.rec + (long long)k * pop_record(a.n_times, K) * a.P + p; // field f of this record: r[f * P]
+    const long long P = a.P;
+    const bool ok = jacobi_svd_columns(L, V, n, K);
+    r[pop_off_ok(a.n_times, K) * P] = ok ? 1.0 : 0.0;
+    if (!ok) return; // every cycle of this class and particle: valid = 0
+    for (int e = 0; e < K; ++e) {
+        double q = 0.0;
+        for (int j = 0; j < n; ++j) q += L[j][e] * L[j][e];
+        r[(pop_off_s2(a.n_times, K) + e) * P] = q;
+        r[(pop_off_scl(a.n_times, K) + e) * P] = scl[e];
+    }
+    for (int j = 0; j < n; ++j) {
+        r[(pop_off_w(a.n_times, K) + j) * P] = ww[j];
+        for (int e = 0; e < K; ++e) r[(j * K + e) * P] = L[j][e];
+    }
+    for (int q = 0; q < K; ++q)
+        for (int e = 0; e < K; ++e) r[(pop_off_V(a.n_times, K) + q * K + e) * P] = V[q][e];
+}
+
+// Pass B: one thread per (cycle, particle), one cycle per block, so the cycle's centres are read once into LDS.  The samples found in the track are
+// compared with the class's mask: a cycle whose class does not describe it (a class table of another track) gets valid = 0, never a fit of the wrong samples.
+__global__ __launch_bounds__(64) void replay_polyfit_eval_kernel(const PopArgs a) {
+    __shared__ double px[kTrackMaxTimes], py[kTrackMaxTimes];
+    __shared__ int stale;
+    if (a.stop && *a.stop) return; // block-uniform
+    const int PB = (a.P + 63) / 64;
+    const int c = blockIdx.x / PB, p = (blockIdx.x - c * PB) * 64 + threadIdx.x;
+    const int K = a.degree + 1;
+    const int k = a.cycle_class[c];
+    const bool known = k >= 0 && k < a.n_classes;
+    const unsigned mask = known ? (unsigned)a.class_mask[k] & ((1u << a.n_times) - 1u) : 0u;
+    if (threadIdx.x == 0) stale = known ? 0 : 1;
+    __syncthreads();
+    if ((int)threadIdx.x < a.n_times) {
+        const int j = threadIdx.x;
+        const long long f = (long long)c * a.L + a.times[j];
+        double cx = 0.0, cy = 0.0;
+        bool finite = f >= 0 && f < a.n_track;
+        if (finite) {
+            const double x = a.track[4 * f + 0], y = a.track[4 * f + 1], w = a.track[4 * f + 2], h = a.track[4 * f + 3];
+            cx = x + w / 2; // BoxUtils.center
+            cy = y + h / 2;
+            finite = isfinite(cx) && isfinite(cy);
+        }
+        if (finite != (((mask >> j) & 1u) != 0u)) {
+            stale = 1; // every writer writes the same value
+        } else if (finite) {
+            const int slot = __popc(mask & ((1u << j) - 1u)); // the compaction: samples in time order
+            px[slot] = cx, py[slot] = cy;
+        }
+    }
+    __syncthreads();
+    if (p >= a.P) return;
+    const long long P = a.P, cp = (long long)c * P + p;
+    const int n = __popc(mask);
+    const double *r = a.rec + (long long)(known ? k : 0) * pop_record(a.n_times, K) * P + p;
+    if (stale || n == 0 || r[pop_off_ok(a.n_times, K) * P] == 0.0) {
+        a.a[2 * cp] = a.a[2 * cp + 1] = 0.0;
+        a.valid[cp] = 0;
+        return;
+    }
+    const double *s2 = r + pop_off_s2(a.n_times, K) * P, *scl = r + pop_off_scl(a.n_times, K) * P, *ww = r + pop_off_w(a.n_times, K) * P;
+    const double *V = r + pop_off_V(a.n_times, K) * P;
+    double s2max = 0.0;
+    for (int e = 0; e < K; ++e) s2max = fmax(s2max, s2[e * P]);
+    const double rcond = (double)n * 2.220446049250313e-16; // numpy: len(x) * finfo(float64).eps
+    double cx[kTrackMaxCoef], cy[kTrackMaxCoef];
+#pragma unroll
+    for (int q = 0; q < kTrackMaxCoef; ++q) cx[q] = cy[q] = 0.0;
+    for (int e = 0; e < K; ++e) {
+        const double s2e = s2[e * P];
+        if (!(s2e > rcond * rcond * s2max)) continue; // s_e <= rcond * s_max: the minimum-norm solution leaves the direction at zero
+        double dx = 0.0, dy = 0.0;
+        for (int j = 0; j < n; ++j) {
+            const double l = r[(j * K + e) * P], w = ww[j * P];
+            dx += l * (w * px[j]), dy += l * (w * py[j]);
+        }
+        dx /= s2e, dy /= s2e;
+#pragma unroll
+        for (int q = 0; q < kTrackMaxCoef; ++q)
+            if (q < K) {
+                const double v = V[(q * K + e) * P];
+                cx[q] += v * dx, cy[q] += v * dy;
+            }
+    }
+    // polyval (Horner, highest power first) of c / scl at t_eval
+    double x = 0.0, y = 0.0;
+#pragma unroll
+    for (int q = kTrackMaxCoef - 1; q >= 0; --q)
+        if (q < K) {
+            const double s = scl[q * P];
+            if (q == K - 1)
+                x = cx[q] / s, y = cy[q] / s;
+            else
+                x = cx[q] / s + x * a.t_eval, y = cy[q] / s + y * a.t_eval;
+        }
+    a.a[2 * cp] = x;
+    a.a[2 * cp + 1] = y;
+    a.valid[cp] = 1;
 }
 
 // the refusals both entry points share; fills the geometry and the counts derived from it
@@ -223,20 +407,56 @@ int check_config(const char *who, const wtk_replay_config *cfg, int32_t kind, in
     return 0;
 }
 
+// checks and argument structs of the two steps, apart from their launches: wtk_replay_objective refuses before anything is enqueued
+int prepare_scan(const char *who, const wtk_replay_config *cfg, int32_t kind, int32_t E, int32_t n_cycles, const double *track_dev, int32_t n_track,
+                 const double *a_dev, const double *b_dev, const int32_t *valid_dev, const double *share_dev, int32_t *pos_dev, int32_t *move_dev, ScanArgs &s) {
+    const std::string w(who);
+    int n_log = 0;
+    if (check_config(who, cfg, kind, E, n_cycles, n_track, s.g, n_log)) return 1;
+    if (!track_dev || !share_dev || !pos_dev || !move_dev) return fail(w + ": null argument");
+    if (kind != WTK_REPLAY_CSV && (!a_dev || !valid_dev)) return fail(w + ": null targets");
+    if (kind == WTK_REPLAY_MLP && !b_dev) return fail(w + ": null origins (b_dev) for the MLP kind");
+    s.kind = kind, s.E = E, s.C = n_cycles, s.init_x = cfg->init_x, s.init_y = cfg->init_y;
+    s.track = track_dev, s.n_track = n_track, s.a = a_dev, s.b = b_dev, s.valid = valid_dev, s.share = share_dev, s.pos = pos_dev, s.move = move_dev;
+    return 0;
+}
+
+void launch_scan(const ScanArgs &s, hipStream_t st) {
+    hipLaunchKernelGGL(replay_scan_kernel, dim3((unsigned)((s.E + kScanThreads - 1) / kScanThreads)), dim3(kScanThreads), 0, st, s);
+}
+
+int prepare_rows(const char *who, const wtk_replay_config *cfg, int32_t E, int32_t n_cycles, const double *track_dev, int32_t n_track, const double *share_dev,
+                 const int32_t *pos_dev, const int32_t *move_dev, const int32_t *row_slot_dev, int32_t n_slots, double *rows_dev, double *bbox_err_dev,
+                 double *mse_err_dev, double *summary_dev, double *scratch_dev, int64_t scratch_doubles, RowsArgs &r) {
+    const std::string w(who);
+    int n_log = 0;
+    if (check_config(who, cfg, WTK_REPLAY_OPTIMAL, E, n_cycles, n_track, r.g, n_log)) return 1;
+    if (!track_dev || !share_dev || !pos_dev || !move_dev || !summary_dev || !scratch_dev) return fail(w + ": null argument");
+    if ((row_slot_dev == nullptr) != (rows_dev == nullptr) || n_slots < 0 || (rows_dev && n_slots < 1))
+        return fail(w + ": row_slot_dev, rows_dev and n_slots >= 1 go together");
+    r.R = (long long)n_log * r.g.L;
+    const long long S = (r.R + kRowChunk - 1) / kRowChunk;
+    if (S * E > INT32_MAX) return fail(w + ": too many (experiment, chunk) blocks for one launch");
+    if (scratch_doubles < wtk_replay_scratch_doubles(E, r.R)) return fail(w + ": scratch smaller than wtk_replay_scratch_doubles(E, R)");
+    r.E = E, r.C = n_cycles, r.S = (int)S, r.n_log = n_log, r.n_slots = rows_dev ? n_slots : 0;
+    r.track = track_dev, r.share = share_dev, r.pos = pos_dev, r.move = move_dev, r.row_slot = row_slot_dev, r.rows = rows_dev;
+    r.bbox_err = bbox_err_dev, r.mse_err = mse_err_dev, r.partial = scratch_dev, r.summary = summary_dev;
+    return 0;
+}
+
+void launch_rows(const RowsArgs &r, hipStream_t st) {
+    if (r.S > 0) hipLaunchKernelGGL(replay_rows_kernel, dim3((unsigned)((long long)r.S * r.E)), dim3(kRowThreads), 0, st, r);
+    hipLaunchKernelGGL(replay_finish_kernel, dim3((unsigned)(((long long)r.E * kSummary + 63) / 64)), dim3(64), 0, st, r);
+}
+
 } // namespace
 
 extern "C" int wtk_replay_scan(const wtk_replay_config *cfg, int32_t kind, int32_t E, int32_t n_cycles, const double *track_dev, int32_t n_track,
                                const double *a_dev, const double *b_dev, const int32_t *valid_dev, const double *share_dev, int32_t *pos_dev,
                                int32_t *move_dev, void *stream) {
     ScanArgs s = {};
-    int n_log = 0;
-    if (check_config("wtk_replay_scan", cfg, kind, E, n_cycles, n_track, s.g, n_log)) return 1;
-    if (!track_dev || !share_dev || !pos_dev || !move_dev) return fail("wtk_replay_scan: null argument");
-    if (kind != WTK_REPLAY_CSV && (!a_dev || !valid_dev)) return fail("wtk_replay_scan: null targets");
-    if (kind == WTK_REPLAY_MLP && !b_dev) return fail("wtk_replay_scan: null origins (b_dev) for the MLP kind");
-    s.kind = kind, s.E = E, s.C = n_cycles, s.init_x = cfg->init_x, s.init_y = cfg->init_y;
-    s.track = track_dev, s.n_track = n_track, s.a = a_dev, s.b = b_dev, s.valid = valid_dev, s.share = share_dev, s.pos = pos_dev, s.move = move_dev;
-    hipLaunchKernelGGL(replay_scan_kernel, dim3((unsigned)((E + kScanThreads - 1) / kScanThreads)), dim3(kScanThreads), 0, (hipStream_t)stream, s);
+    if (prepare_scan("wtk_replay_scan", cfg, kind, E, n_cycles, track_dev, n_track, a_dev, b_dev, valid_dev, share_dev, pos_dev, move_dev, s)) return 1;
+    launch_scan(s, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -251,21 +471,73 @@ extern "C" int wtk_replay_rows(const wtk_replay_config *cfg, int32_t E, int32_t 
                                double *bbox_err_dev, double *mse_err_dev, double *summary_dev, double *scratch_dev, int64_t scratch_doubles,
                                void *stream) {
     RowsArgs r = {};
-    int n_log = 0;
-    if (check_config("wtk_replay_rows", cfg, WTK_REPLAY_OPTIMAL, E, n_cycles, n_track, r.g, n_log)) return 1;
-    if (!track_dev || !share_dev || !pos_dev || !move_dev || !summary_dev || !scratch_dev) return fail("wtk_replay_rows: null argument");
-    if ((row_slot_dev == nullptr) != (rows_dev == nullptr) || n_slots < 0 || (rows_dev && n_slots < 1))
-        return fail("wtk_replay_rows: row_slot_dev, rows_dev and n_slots >= 1 go together");
-    r.R = (long long)n_log * r.g.L;
-    const long long S = (r.R + kRowChunk - 1) / kRowChunk;
-    if (S * E > INT32_MAX) return fail("wtk_replay_rows: too many (experiment, chunk) blocks for one launch");
-    if (scratch_doubles < wtk_replay_scratch_doubles(E, r.R)) return fail("wtk_replay_rows: scratch smaller than wtk_replay_scratch_doubles(E, R)");
-    r.E = E, r.C = n_cycles, r.S = (int)S, r.n_log = n_log, r.n_slots = rows_dev ? n_slots : 0;
-    r.track = track_dev, r.share = share_dev, r.pos = pos_dev, r.move = move_dev, r.row_slot = row_slot_dev, r.rows = rows_dev;
-    r.bbox_err = bbox_err_dev, r.mse_err = mse_err_dev, r.partial = scratch_dev, r.summary = summary_dev;
+    if (prepare_rows("wtk_replay_rows", cfg, E, n_cycles, track_dev, n_track, share_dev, pos_dev, move_dev, row_slot_dev, n_slots, rows_dev, bbox_err_dev,
+                     mse_err_dev, summary_dev, scratch_dev, scratch_doubles, r))
+        return 1;
+    launch_rows(r, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int wtk_replay_objective(const wtk_replay_config *cfg, int32_t kind, int32_t E, int32_t n_cycles, const double *track_dev, int32_t n_track,
+                                    const double *a_dev, const double *b_dev, const int32_t *valid_dev, const double *share_dev, int32_t *pos_dev,
+                                    int32_t *move_dev, double *summary_dev, double *scratch_dev, int64_t scratch_doubles, int32_t objective,
+                                    double *objective_dev, const int32_t *stop_dev, void *stream) {
+    ScanArgs s = {};
+    RowsArgs r = {};
+    if (prepare_scan("wtk_replay_objective", cfg, kind, E, n_cycles, track_dev, n_track, a_dev, b_dev, valid_dev, share_dev, pos_dev, move_dev, s)) return 1;
+    if (prepare_rows("wtk_replay_objective", cfg, E, n_cycles, track_dev, n_track, share_dev, pos_dev, move_dev, nullptr, 0, nullptr, nullptr, nullptr,
+                     summary_dev, scratch_dev, scratch_doubles, r))
+        return 1;
+    if (!objective_dev) return fail("wtk_replay_objective: null argument");
+    ObjectiveArgs o = {};
+    switch (objective) {
+    case WTK_REPLAY_OBJ_TRIMMED_BBOX: o.num = 2, o.den = 3; break;
+    case WTK_REPLAY_OBJ_MEAN_BBOX: o.num = 0, o.den = 1; break;
+    case WTK_REPLAY_OBJ_MEAN_MSE: o.num = 5, o.den = 1; break;
+    case WTK_REPLAY_OBJ_NON_PERFECT: o.num = 4, o.den = 1; break;
+    default: return fail("wtk_replay_objective: unknown objective");
+    }
+    if (objective == WTK_REPLAY_OBJ_TRIMMED_BBOX && r.n_log < 3)
+        return fail("wtk_replay_objective: the trimmed objective needs at least 3 logged cycles (the first and the last are dropped)");
+    s.stop = r.stop = o.stop = stop_dev;
+    o.summary = summary_dev, o.objective = objective_dev, o.E = E;
     hipStream_t st = (hipStream_t)stream;
-    if (S > 0) hipLaunchKernelGGL(replay_rows_kernel, dim3((unsigned)(S * E)), dim3(kRowThreads), 0, st, r);
-    hipLaunchKernelGGL(replay_finish_kernel, dim3((unsigned)(((long long)E * kSummary + 63) / 64)), dim3(64), 0, st, r);
+    launch_scan(s, st);
+    launch_rows(r, st);
+    hipLaunchKernelGGL(replay_objective_kernel, dim3((unsigned)((E + 63) / 64)), dim3(64), 0, st, o);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int64_t wtk_replay_polyfit_targets_scratch_doubles(int32_t n_classes, int32_t P, int32_t n_times, int32_t degree) {
+    if (n_classes < 0 || P < 0 || n_times < 1 || n_times > kTrackMaxTimes || degree < 0 || degree + 1 > kTrackMaxCoef) return -1;
+    return (int64_t)n_classes * pop_record(n_times, degree + 1) * P;
+}
+
+extern "C" int wtk_replay_polyfit_targets(const double *track_dev, int32_t n_track, int32_t n_cycles, int32_t cycle_frame_num, const double *weights_dev,
+                                          int32_t P, const int32_t *sample_times_host, int32_t n_times, int32_t degree, double t_eval,
+                                          const int32_t *cycle_class_dev, const int32_t *class_mask_dev, int32_t n_classes, double *a_dev,
+                                          int32_t *valid_dev, double *scratch_dev, int64_t scratch_doubles, const int32_t *stop_dev, void *stream) {
+    if (!track_dev || !weights_dev || !sample_times_host || !cycle_class_dev || !class_mask_dev || !a_dev || !valid_dev || !scratch_dev)
+        return fail("wtk_replay_polyfit_targets: null argument");
+    if (n_times <= 0 || n_times > kTrackMaxTimes) return fail("wtk_replay_polyfit_targets: 1..16 sample times");
+    if (degree < 0 || degree + 1 > kTrackMaxCoef) return fail("wtk_replay_polyfit_targets: degree must be in [0, 7]");
+    if (P < 1 || P > 65535) return fail("wtk_replay_polyfit_targets: need 1 <= P <= 65535 weight vectors");
+    if (n_track < 0 || n_cycles < 1 || cycle_frame_num <= 0) return fail("wtk_replay_polyfit_targets: need n_track >= 0, n_cycles >= 1 and a positive cycle_frame_num");
+    if (n_classes < 1 || n_classes > n_cycles) return fail("wtk_replay_polyfit_targets: need 1 <= n_classes <= n_cycles");
+    if (scratch_doubles < wtk_replay_polyfit_targets_scratch_doubles(n_classes, P, n_times, degree))
+        return fail("wtk_replay_polyfit_targets: scratch smaller than wtk_replay_polyfit_targets_scratch_doubles(n_classes, P, n_times, degree)");
+    const long long PB = (P + 63) / 64;
+    if (PB * n_cycles > INT32_MAX) return fail("wtk_replay_polyfit_targets: too many (cycle, particle) blocks for one launch");
+    PopArgs a = {};
+    a.track = track_dev, a.n_track = n_track, a.L = cycle_frame_num, a.weights = weights_dev, a.P = P, a.C = n_cycles, a.n_times = n_times, a.degree = degree;
+    a.n_classes = n_classes, a.t_eval = t_eval, a.cycle_class = cycle_class_dev, a.class_mask = class_mask_dev, a.rec = scratch_dev, a.a = a_dev;
+    a.valid = valid_dev, a.stop = stop_dev;
+    for (int i = 0; i < kTrackMaxTimes; ++i) a.times[i] = i < n_times ? sample_times_host[i] : 0;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(replay_polyfit_solve_kernel, dim3((unsigned)(PB * n_classes)), dim3(64), 0, st, a);
+    hipLaunchKernelGGL(replay_polyfit_eval_kernel, dim3((unsigned)(PB * n_cycles)), dim3(64), 0, st, a);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -69,6 +69,7 @@ SYMBOLS = [
     "wtk_background", "wtk_precise_error",
     "wtk_polyfit_dataset", "wtk_polyfit_mae_scratch_doubles", "wtk_polyfit_weight_mae", "wtk_polyfit_swarm_step",
     "wtk_replay_scan", "wtk_replay_scratch_doubles", "wtk_replay_rows",
+    "wtk_replay_polyfit_targets_scratch_doubles", "wtk_replay_polyfit_targets", "wtk_replay_objective",
 ]
 
 
@@ -220,6 +221,10 @@ def load() -> C.CDLL:
     lib.wtk_replay_scratch_doubles.argtypes = [i32, C.c_int64]
     lib.wtk_replay_scratch_doubles.restype = C.c_int64
     lib.wtk_replay_rows.argtypes = [C.POINTER(_ReplayConfig), i32, i32, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, C.c_int64, vp]
+    lib.wtk_replay_polyfit_targets_scratch_doubles.argtypes = [i32, i32, i32, i32]
+    lib.wtk_replay_polyfit_targets_scratch_doubles.restype = C.c_int64
+    lib.wtk_replay_polyfit_targets.argtypes = [vp, i32, i32, i32, vp, i32, vp, i32, i32, f64, vp, vp, i32, vp, vp, vp, C.c_int64, vp, vp]
+    lib.wtk_replay_objective.argtypes = [C.POINTER(_ReplayConfig), i32, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int64, i32, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -441,6 +446,33 @@ def replay_rows(cfg: _ReplayConfig, E: int, n_cycles: int, track_dev, n_track: i
     _check(load().wtk_replay_rows(C.byref(cfg) if cfg is not None else None, E, n_cycles, _ptr(track_dev), n_track, _ptr(share_dev), _ptr(pos_dev),
                                   _ptr(move_dev), _ptr(row_slot_dev), n_slots, _ptr(rows_dev), _ptr(bbox_err_dev), _ptr(mse_err_dev), _ptr(summary_dev),
                                   _ptr(scratch_dev), scratch_doubles, C.c_void_p(stream)), "wtk_replay_rows")
+
+
+REPLAY_OBJECTIVES = {"trimmed_bbox_error": 0, "bbox_error": 1, "mse_error": 2, "non_perfect": 3}  # WTK_REPLAY_OBJ_*
+
+
+def replay_polyfit_targets_scratch_doubles(n_classes: int, P: int, n_times: int, degree: int) -> int:
+    return int(load().wtk_replay_polyfit_targets_scratch_doubles(n_classes, P, n_times, degree))
+
+
+def replay_polyfit_targets(track_dev, n_track: int, n_cycles: int, cycle_frame_num: int, weights_dev, P: int, sample_times: Sequence[int], degree: int,
+                           t_eval: float, cycle_class_dev, class_mask_dev, n_classes: int, a_dev, valid_dev, scratch_dev, scratch_doubles: int, stop_dev=None,
+                           stream: int = 0):
+    """Polyfit targets of P device-resident weight vectors in one call (wtk_replay_polyfit_targets): a_dev [n_cycles, P, 2], valid_dev [n_cycles, P]."""
+    if _track_is_f64(track_dev) != 1:
+        raise WtkError("wtk_replay_polyfit_targets takes a float64 track")
+    st = np.ascontiguousarray(sample_times, dtype=np.int32)
+    _check(load().wtk_replay_polyfit_targets(_ptr(track_dev), n_track, n_cycles, cycle_frame_num, _ptr(weights_dev), P, _ptr(st), len(st), degree, float(t_eval),
+                                             _ptr(cycle_class_dev), _ptr(class_mask_dev), n_classes, _ptr(a_dev), _ptr(valid_dev), _ptr(scratch_dev),
+                                             scratch_doubles, _ptr(stop_dev), C.c_void_p(stream)), "wtk_replay_polyfit_targets")
+
+
+def replay_objective(cfg: _ReplayConfig, kind: int, E: int, n_cycles: int, track_dev, n_track: int, a_dev, b_dev, valid_dev, share_dev, pos_dev, move_dev,
+                     summary_dev, scratch_dev, scratch_doubles: int, objective: int, objective_dev, stop_dev=None, stream: int = 0):
+    """objective_dev[e] = the chosen closed-loop error of experiment e (wtk_replay_objective): scan, rows reduction and one division, no host round trip."""
+    _check(load().wtk_replay_objective(C.byref(cfg) if cfg is not None else None, kind, E, n_cycles, _ptr(track_dev), n_track, _ptr(a_dev), _ptr(b_dev),
+                                       _ptr(valid_dev), _ptr(share_dev), _ptr(pos_dev), _ptr(move_dev), _ptr(summary_dev), _ptr(scratch_dev), scratch_doubles,
+                                       objective, _ptr(objective_dev), _ptr(stop_dev), C.c_void_p(stream)), "wtk_replay_objective")
 
 
 # -------------------------------------------------------------------------------------------------

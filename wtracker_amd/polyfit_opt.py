@@ -27,8 +27,8 @@ MAX_POP = 65535
 @dataclass
 class SwarmResult:
     weights: np.ndarray  # [N] best weight vector (weight i belongs to the i-th smallest offset)
-    mae: float           # its MAE: bit-equal to WeightEvaluator.eval(weights, deg)
-    history: np.ndarray  # [epochs] best MAE after every epoch run
+    mae: float           # its MAE: bit-equal to WeightEvaluator.eval(weights, deg)  (Replay.optimize_polyfit: the closed-loop objective value instead)
+    history: np.ndarray  # [epochs] best MAE (objective value) after every epoch run
     epochs: int          # epochs run (< max_epoch when the search stopped early)
     degree: int
 

@@ -12,6 +12,12 @@ During the imaging phase the platform stands still, so a controller's move is ro
 depend on the platform.  The builders (`csv`, `optimal`, `polyfit`, `mlp`) compute the targets of all cycles with the existing device calls; `run` scans
 the cycles (one lane per experiment) and expands to frames.  Everything is enqueued on the current torch stream; `run` synchronises once.
 
+The closed-loop error is also the objective of a weight search:
+
+    t = rp.polyfit_population(weights_dev, 2, [-9, -6, -3, 0, 2, 4])   # [P, N] device weights, one call
+    rp.objective(t)                                                     # device float64 [P], no synchronisation
+    best = rp.optimize_polyfit(2, [-9, -6, -3, 0, 2, 4], start=[open_loop.weights])
+
 There is no CPU fallback: without a visible GPU the constructor raises.  Not covered: the YOLO controller (its targets depend on the camera view),
 `StepMotorController`, DataAnalyzer's speed and unit columns.
 """
@@ -26,10 +32,26 @@ import numpy as np
 
 from . import hip
 from .controllers import PolyfitConfig, _read_track_csv
+from .polyfit_opt import MAX_POP, MAX_TIMES, SwarmResult, WeightEvaluator, _check_degree
 from .resmlp import FoldedResMLP, from_torch_module
 from .sim import LOG_COLUMNS, ExperimentConfig, TimingConfig
 
 KINDS = {"csv": hip.REPLAY_CSV, "optimal": hip.REPLAY_OPTIMAL, "polyfit": hip.REPLAY_POLYFIT, "mlp": hip.REPLAY_MLP}
+OBJECTIVES = hip.REPLAY_OBJECTIVES  # name -> WTK_REPLAY_OBJ_*; each is the Summary property of the same name prefixed with `mean_` / `trimmed_mean_`
+
+
+def polyfit_classes(track: np.ndarray, cycle_frame_num: int, n_cycles: int, sample_times) -> tuple:
+    """The cycles of a track grouped by WHICH samples of the fit exist: -> (cycle_class int32 [n_cycles], class_mask int32 [K]).  Bit j of a mask:
+    frame c L + sample_times[j] lies inside the track and its centre (x + w / 2, y + h / 2) is finite.  Classes are numbered by ascending mask."""
+    st = np.asarray(sample_times, dtype=np.int64)
+    frames = np.arange(n_cycles, dtype=np.int64)[:, None] * int(cycle_frame_num) + st[None, :]
+    inside = (frames >= 0) & (frames < len(track))
+    rows = track[np.where(inside, frames, 0)]
+    with np.errstate(invalid="ignore", over="ignore"):
+        finite = inside & np.isfinite(rows[..., 0] + rows[..., 2] / 2) & np.isfinite(rows[..., 1] + rows[..., 3] / 2)
+    masks = (finite.astype(np.int64) << np.arange(len(st), dtype=np.int64)[None, :]).sum(axis=1)
+    class_mask, cycle_class = np.unique(masks, return_inverse=True)
+    return cycle_class.reshape(-1).astype(np.int32), class_mask.astype(np.int32)
 
 
 @dataclass
@@ -150,6 +172,8 @@ class Replay:
         self._share = torch.from_numpy(share).to(self._dev)
         self._cycles = torch.arange(self.n_cycles, dtype=torch.int32, device=self._dev)
         self._track_f32 = None
+        self._classes = {}  # sorted sample times -> (cycle_class, class_mask) on the device
+        self._last_times = None  # of the last polyfit_population / optimize_polyfit call (to_config's default)
 
     # ------------------------------------------------------------------ targets
     def _stream(self) -> int:
@@ -222,6 +246,178 @@ class Replay:
             b[:, 0] = self.track[first, :2]
             valid[:, 0] = ok
         return Targets("mlp", 1, a, b, valid, keep=net)  # nothing is waited for: the handle lives as long as its targets
+
+    # ------------------------------------------------------------------ populations of weight vectors
+    def _sample_times(self, sample_times) -> tuple:
+        st = np.asarray(sample_times)
+        if st.ndim != 1 or not 1 <= st.size <= MAX_TIMES:
+            raise ValueError(f"sample_times must be 1..{MAX_TIMES} frame offsets (the device solver's limit)")
+        if not np.all(st == np.round(st)):
+            raise ValueError("sample_times must be whole frame numbers")
+        return tuple(int(t) for t in np.sort(st.astype(np.int64)))  # the reference sorts the times and not the weights
+
+    def polyfit_class_table(self, sample_times) -> tuple:
+        """(cycle_class int32 [n_cycles], class_mask int32 [K]) device tensors for the sorted `sample_times`: derived from the track once (the first
+        call copies the track to the host and waits for it) and cached, so nothing inside an epoch loop ever asks for it."""
+        import torch
+
+        st = self._sample_times(sample_times)
+        if st not in self._classes:
+            cycle_class, class_mask = polyfit_classes(self.track.cpu().numpy(), self.L, self.n_cycles, st)
+            self._classes[st] = (torch.from_numpy(cycle_class).to(self._dev), torch.from_numpy(class_mask).to(self._dev))
+        return self._classes[st]
+
+    def _weights_dev(self, weights, N: int):
+        import torch
+
+        if not isinstance(weights, torch.Tensor):
+            weights = torch.from_numpy(np.ascontiguousarray(weights, dtype=np.float64))
+        if weights.dim() != 2 or weights.shape[1] != N:
+            raise ValueError(f"weights must have shape [P, {N}] (one weight per sample time), got {tuple(weights.shape)}")
+        if not 1 <= weights.shape[0] <= MAX_POP:
+            raise ValueError(f"1..{MAX_POP} weight vectors per call")
+        return weights.to(device=self._dev, dtype=torch.float64).contiguous()
+
+    def _enqueue_population(self, w_dev, degree: int, st: tuple, classes, a, valid, scratch, stop_dev=None):
+        cycle_class, class_mask = classes
+        hip.replay_polyfit_targets(self.track, self.n_track, self.n_cycles, self.L, w_dev, int(w_dev.shape[0]), st, degree, self.L + self.I // 2, cycle_class,
+                                   class_mask, int(class_mask.numel()), a, valid, scratch, scratch.numel(), stop_dev, stream=self._stream())
+
+    def polyfit_population(self, weights, degree: int, sample_times) -> Targets:
+        """`polyfit([PolyfitConfig(degree, sample_times, w) for w in weights])` in one call and with the same bits: `weights` [P, N] is a device float64
+        tensor (used in place) or an array (uploaded); row p's weight j belongs to the j-th smallest sample time.  Two launches whatever P is; nothing
+        is waited for (but the first call for a set of sample times derives the class table from the track, see polyfit_class_table)."""
+        import torch
+
+        degree, st = _check_degree(degree), self._sample_times(sample_times)
+        w = self._weights_dev(weights, len(st))
+        P = int(w.shape[0])
+        classes = self.polyfit_class_table(st)
+        self._last_times = st
+        with torch.cuda.device(self._dev):
+            a = torch.empty((self.n_cycles, P, 2), dtype=torch.float64, device=self._dev)
+            valid = torch.empty((self.n_cycles, P), dtype=torch.int32, device=self._dev)
+            scratch = torch.empty((max(1, hip.replay_polyfit_targets_scratch_doubles(int(classes[1].numel()), P, len(st), degree)),), dtype=torch.float64,
+                                  device=self._dev)
+            self._enqueue_population(w, degree, st, classes, a, valid, scratch)
+        return Targets("polyfit", P, a, None, valid)
+
+    def _objective_kind(self, kind: str) -> int:
+        if kind not in OBJECTIVES:
+            raise ValueError(f"unknown objective {kind!r}: one of {sorted(OBJECTIVES)}")
+        if kind == "trimmed_bbox_error" and self.n_log < 3:
+            raise ValueError(f"the trimmed objective drops the first and the last logged cycle: the experiment logs {self.n_log}, at least 3 are needed")
+        return OBJECTIVES[kind]
+
+    def _objective_buffers(self, E: int) -> dict:
+        import torch
+
+        dev, C = self._dev, self.n_cycles
+        return dict(pos=torch.empty((C, E, 2), dtype=torch.int32, device=dev), move=torch.empty((C, E, 2), dtype=torch.int32, device=dev),
+                    summary=torch.empty((E, hip.REPLAY_SUMMARY_DOUBLES), dtype=torch.float64, device=dev),
+                    scratch=torch.empty((max(1, hip.replay_scratch_doubles(E, self.n_rows)),), dtype=torch.float64, device=dev))
+
+    def _enqueue_objective(self, targets: Targets, kind: int, buf: dict, out, stop_dev=None):
+        hip.replay_objective(self._cfg, KINDS[targets.kind], int(targets.E), self.n_cycles, self.track, self.n_track, targets.a, targets.b, targets.valid,
+                             self._share, buf["pos"], buf["move"], buf["summary"], buf["scratch"], buf["scratch"].numel(), kind, out, stop_dev,
+                             stream=self._stream())
+
+    def objective(self, targets: Targets, kind: str = "trimmed_bbox_error"):
+        """The closed-loop error of every experiment of `targets` as a device float64 [E] tensor, enqueued on the current torch stream (no synchronisation):
+        "trimmed_bbox_error" = Summary.trimmed_mean_bbox_error, "bbox_error" = mean_bbox_error, "mse_error" = mean_mse_error, "non_perfect" = non_perfect
+        of `run(targets)`, bit for bit (the same sums, the same float64 division; 0 / 0 is NaN)."""
+        import torch
+
+        if targets.kind not in KINDS:
+            raise ValueError(f"unknown kind {targets.kind!r}")
+        k, E = self._objective_kind(kind), int(targets.E)
+        for t in (targets.a, targets.b, targets.valid):
+            if t is not None and (t.shape[0] != self.n_cycles or t.shape[1] != E or not t.is_contiguous()):
+                raise ValueError("targets must be contiguous [n_cycles, E, ...] tensors of this Replay")
+        with torch.cuda.device(self._dev):
+            out = torch.empty((E,), dtype=torch.float64, device=self._dev)
+            self._enqueue_objective(targets, k, self._objective_buffers(E), out)
+        return out
+
+    def optimize_polyfit(self, degree: int, sample_times, objective: str = "trimmed_bbox_error", pop_size: int = 100, c1: float = 2.05, c2: float = 2.05,
+                         max_epoch: int = 300, max_early_stop: int = 100, seed: int = 0, lb: float = 0.0, ub: float = 1.0, start=None,
+                         _trace: Optional[list] = None) -> SwarmResult:
+        """Particle-swarm search for the Polyfit weights of lowest CLOSED-LOOP error of this experiment: WeightEvaluator.optimize's rule and random-number
+        protocol exactly (the same wtk_polyfit_swarm_step; see that docstring), with `objective` (see `objective`) of the replayed population in the place
+        of the open-loop MAE.  Per epoch: targets of the positions, objective, step; every epoch is enqueued at once and the host waits once.
+
+        `start` [K, N] (K < pop_size) replaces the random start of particles 1 .. K; particle 0 stays at `ub`.  With the open-loop winner in `start` the
+        result is never worse than it (nor than uniform weights).  In the returned SwarmResult `mae` holds the objective value of `weights` and `history`
+        the best value after every epoch; `run(polyfit([to_config(degree, result.weights)]))` reproduces `mae` bit for bit.
+
+        The objective is piecewise constant in the weights (a move is an integer number of pixels), so many particles tie and small steps change nothing.
+        With `lb = 0` a particle can zero so many weights that fits become rank deficient, where the device's fit of absolute centres differs from the
+        reference's (Limits); a positive `lb` avoids that."""
+        import torch
+
+        degree, st = _check_degree(degree), self._sample_times(sample_times)
+        kind = self._objective_kind(objective)
+        N = len(st)
+        if int(pop_size) != pop_size or not 1 <= pop_size <= MAX_POP:
+            raise ValueError(f"pop_size must be in [1, {MAX_POP}]")
+        if int(max_epoch) != max_epoch or max_epoch < 1 or int(max_early_stop) != max_early_stop or max_early_stop < 1:
+            raise ValueError("max_epoch and max_early_stop must be positive integers")
+        if not (np.isfinite(lb) and np.isfinite(ub) and lb < ub):
+            raise ValueError(f"need finite bounds lb < ub, got [{lb}, {ub}]")
+        P, E = int(pop_size), int(max_epoch)
+        rng = np.random.default_rng(seed)
+        x0 = lb + (ub - lb) * rng.random((P, N))
+        x0[0, :] = ub
+        if start is not None:
+            start = np.asarray(start, dtype=np.float64)
+            if start.ndim != 2 or start.shape[1] != N or start.shape[0] > P - 1:
+                raise ValueError(f"start must have shape [K, {N}] with K <= pop_size - 1, got {start.shape}")
+            if not (np.isfinite(start).all() and (start >= lb).all() and (start <= ub).all()):
+                raise ValueError(f"start must lie inside [{lb}, {ub}]")
+            x0[1 : 1 + len(start)] = start
+        rand = rng.random((E, 2, P, N))
+        vmax = 0.5 * (ub - lb)
+        classes = self.polyfit_class_table(st)  # from the track, before any epoch is enqueued
+        self._last_times = st
+        W_MAX, W_MIN = WeightEvaluator.W_MAX, WeightEvaluator.W_MIN
+        with torch.cuda.device(self._dev):
+            dev, f64 = self._dev, torch.float64
+            stream = self._stream()
+            pos = torch.from_numpy(x0).to(dev)
+            rand_dev = torch.from_numpy(rand).to(dev)
+            vel = torch.zeros((P, N), dtype=f64, device=dev)
+            pbest_pos = pos.clone()
+            pbest_val = torch.full((P,), float("inf"), dtype=f64, device=dev)
+            gbest_pos = pos[0].clone()
+            gbest_val = torch.full((1,), float("inf"), dtype=f64, device=dev)
+            ctrl = torch.zeros((4,), dtype=torch.int32, device=dev)
+            history = torch.full((E,), float("nan"), dtype=f64, device=dev)
+            value = torch.empty((P,), dtype=f64, device=dev)
+            tg = Targets("polyfit", P, torch.zeros((self.n_cycles, P, 2), dtype=f64, device=dev), None,
+                         torch.zeros((self.n_cycles, P), dtype=torch.int32, device=dev))
+            fit_scratch = torch.empty((max(1, hip.replay_polyfit_targets_scratch_doubles(int(classes[1].numel()), P, N, degree)),), dtype=f64, device=dev)
+            buf = self._objective_buffers(P)
+            for e in range(E):
+                self._enqueue_population(pos, degree, st, classes, tg.a, tg.valid, fit_scratch, stop_dev=ctrl)
+                self._enqueue_objective(tg, kind, buf, value, stop_dev=ctrl)
+                if _trace is not None:  # tests: the state every epoch starts from and the objective values it saw (stream-ordered copies)
+                    _trace.append((pos.clone(), vel.clone(), value.clone()))
+                hip.polyfit_swarm_step(value, rand_dev[e], P, N, e, int(max_early_stop), W_MAX - (W_MAX - W_MIN) * e / E, c1, c2, lb, ub, vmax, pos, vel,
+                                       pbest_pos, pbest_val, gbest_pos, gbest_val, ctrl, history, stream=stream)
+            torch.cuda.current_stream(dev).synchronize()  # the one host synchronisation
+            epochs = int(ctrl[2].item())
+            return SwarmResult(weights=gbest_pos.cpu().numpy(), mae=float(gbest_val.item()), history=history[:epochs].cpu().numpy(), epochs=epochs,
+                               degree=degree)
+
+    def to_config(self, degree: int, weights, sample_times=None) -> PolyfitConfig:
+        """The PolyfitConfig of a search result.  `sample_times` default to those of the last `optimize_polyfit` / `polyfit_population` call."""
+        st = self._last_times if sample_times is None else self._sample_times(sample_times)
+        if st is None:
+            raise ValueError("no sample times yet: pass sample_times, or call optimize_polyfit / polyfit_population first")
+        w = [float(v) for v in np.asarray(weights, dtype=np.float64).reshape(-1)]
+        if len(w) != len(st):
+            raise ValueError(f"{len(st)} weights expected, got {len(w)}")
+        return PolyfitConfig(degree=_check_degree(degree), sample_times=list(st), weights=w)
 
     # ------------------------------------------------------------------ the loop
     def run(self, targets: Targets, rows: Sequence[int] = (0,), per_row_errors: bool = False) -> ReplayResult:
