@@ -100,6 +100,20 @@ def test_population_targets_have_the_bits_of_one_launch_per_config(pop, hard, de
     assert class_mask[cycle_class[40]] == 0 and class_mask[cycle_class[60]] == 0b100000
 
 
+@pytest.mark.parametrize("degree,times", [(0, [0]), (7, list(range(-14, 2)))])
+def test_population_targets_at_the_solver_limits(pop, degree, times):
+    """The two ends of the admitted range (1 x 1 and 16 x 8) with a population that crosses the wave boundary.  The first cycles lack the samples
+    before the track, so at degree 7 there are classes with fewer samples than coefficients."""
+    rp = pop["rp"]
+    weights = np.random.default_rng(13).uniform(0.05, 1.0, size=(66, len(times)))
+    a, v = assert_targets_equal(rp, weights, degree, times)
+    cycle_class, class_mask = (t.cpu().numpy() for t in rp.polyfit_class_table(times))
+    kept = np.array([bin(int(m)).count("1") for m in class_mask])[cycle_class]
+    assert v.any() and not v[kept == 0].any()
+    if degree == 7:
+        assert ((kept > 0) & (kept < degree + 1)).any() and (kept == 16).any()
+
+
 def test_class_table_of_the_fixture(pop):
     """At least 4 classes: the first cycles lack the samples before the track (cycle 0 keeps t = 0 and t = 1 only; cycle 1 loses t = 1 to NaN row 6
     as well), the NaN rows cost single samples."""

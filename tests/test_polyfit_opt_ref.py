@@ -77,7 +77,7 @@ def test_new_module_symbols_and_script_exist(hip_lib):
         assert os.path.exists(os.path.join(ROOT, "tools", tool)), tool
     from wtracker_amd import _build
 
-    assert "polyfit_opt.hip" in _build.SOURCES and "jacobi_svd.h" in _build.HEADERS
+    assert "polyfit_opt.hip" in _build.SOURCES and "polyfit_solve.h" in _build.HEADERS
 
 
 def test_entry_points_refuse_bad_arguments_before_any_launch(hip_lib):

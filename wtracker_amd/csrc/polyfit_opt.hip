@@ -6,7 +6,7 @@
 //           block scan -> scatter, so the kept cycles land in cycle order behind the *count_dev series that are already there.
 // MAE       all series share one time axis, so fit-then-extrapolate is ONE linear functional per weight vector w and degree d:
 //           y_pred[m] = sum_n g_n y_input[n][m],  g = v(t_pred)^T pinv(diag(w) V / scl) diag(w) / scl  (V the Vandermonde matrix of the sample
-//           times, scl its weighted column norms), from an N x (d + 1) SVD with numpy's cut (singular values <= N eps s_max dropped).
+//           times, scl its weighted column norms), from polyfit_solve.h's N x (d + 1) factor with numpy's cut (singular values <= N eps s_max dropped).
 //             rows kernel    one thread per candidate: g[16] (all NaN when the weights are not finite or the solver did not converge)
 //             mae kernel     block (chunk s, candidate p): sum over the chunk's kMaeChunk series of |y_target - sum_n g_n y_input[n]|, g from LDS,
 //                            reads coalesced along the series axis, lane-serial partial sums, then a fixed tree
@@ -16,7 +16,7 @@
 //           the stop flag, then the inertia-weight velocity / position update from host-supplied random numbers.  Once the stop flag is up the
 //           evaluation kernels and the step return at once, so all epochs can be enqueued back to back without a host round trip.
 #include "wtk_internal.h"
-#include "jacobi_svd.h"
+#include "polyfit_solve.h"
 
 #include <climits>
 #include <cmath>
@@ -29,7 +29,6 @@ constexpr int kDsThreads = 1024;  // candidate cycles per pass of the dataset bl
 constexpr int kMaeThreads = 256;
 constexpr int kMaeChunk = 4096;   // series per block of the mae kernel: the FIXED chunking of the reduction
 constexpr int kSwarmThreads = 256;
-constexpr double kEps = 2.220446049250313e-16;
 
 struct DatasetArgs {
     const void *track; // [n_frames][4] xywh, float or double
@@ -134,58 +133,35 @@ template <typename T> __global__ __launch_bounds__(kDsThreads) void polyfit_data
     if (threadIdx.x == 0) *a.count = base;
 }
 
-// numpy.polynomial.polynomial.polyfit(x, ., deg, w) followed by polyval at t_pred, as the row g the data are multiplied with
+// numpy.polynomial.polynomial.polyfit(x, ., deg, w) followed by polyval at t_pred, as the row g the data are multiplied with: polyfit_solve.h's factor,
+// then the functional instead of a right-hand side
 __global__ __launch_bounds__(64) void polyfit_rows_kernel(const RowsArgs a) {
     if (a.stop && *a.stop) return;
     const int p = blockIdx.x * 64 + threadIdx.x;
     if (p >= a.P) return;
     const int n = a.n_times, K = a.degree + 1;
     double *g = a.g + (long long)p * kTrackMaxTimes;
-    double ww[kTrackMaxTimes];
+    double tt[kTrackMaxTimes], ww[kTrackMaxTimes];
     bool finite = true;
-    for (int j = 0; j < n; ++j) ww[j] = a.weights[(long long)p * n + j], finite = finite && isfinite(ww[j]);
-    // scaled weighted Vandermonde: L[j][q] = w_j t_j^q / scl_q (t^q by repeated multiplication, as numpy's vander)
-    double scl[kTrackMaxCoef];
-    for (int q = 0; q < K; ++q) scl[q] = 0.0;
-    for (int j = 0; j < n; ++j) {
-        double tp = 1.0;
-        for (int q = 0; q < K; ++q) {
-            const double v = ww[j] * tp;
-            scl[q] += v * v;
-            tp *= (double)a.times[j];
-        }
-    }
-    for (int q = 0; q < K; ++q) scl[q] = scl[q] > 0.0 ? sqrt(scl[q]) : 1.0;
-    double L[kTrackMaxTimes][kTrackMaxCoef], V[kTrackMaxCoef][kTrackMaxCoef];
-    for (int j = 0; j < n; ++j) {
-        double tp = 1.0;
-        for (int q = 0; q < K; ++q) L[j][q] = ww[j] * tp / scl[q], tp *= (double)a.times[j];
-    }
-    if (!finite || !jacobi_svd_columns(L, V, n, K)) { // no silent number: the candidate's MAE becomes NaN
+    for (int j = 0; j < n; ++j) tt[j] = (double)a.times[j], ww[j] = a.weights[(long long)p * n + j], finite = finite && isfinite(ww[j]);
+    PolyfitFactor fit;
+    if (!finite || !polyfit_factor(fit, tt, ww, n, K)) { // no silent number: the candidate's MAE becomes NaN
         for (int j = 0; j < kTrackMaxTimes; ++j) g[j] = nan("");
         return;
     }
-    double s2[kTrackMaxCoef], s2max = 0.0;
-    for (int e = 0; e < K; ++e) {
-        double q = 0.0;
-        for (int j = 0; j < n; ++j) q += L[j][e] * L[j][e];
-        s2[e] = q;
-        s2max = fmax(s2max, q);
-    }
-    const double rcond = (double)n * kEps; // numpy: len(x) * finfo(float64).eps
     // z_e = (v(t_pred) / scl) . V[:, e] / s_e^2 for the directions numpy keeps; g_j = w_j sum_e L_rot[j][e] z_e
     double z[kTrackMaxCoef];
     for (int e = 0; e < K; ++e) {
         z[e] = 0.0;
-        if (!(s2[e] > rcond * rcond * s2max)) continue; // s_e <= rcond * s_max: the minimum-norm solution leaves the direction at zero
+        if (!polyfit_keeps(fit.s2[e], fit.s2max, n)) continue;
         double tp = 1.0, acc = 0.0;
-        for (int q = 0; q < K; ++q) acc += V[q][e] * (tp / scl[q]), tp *= a.t_pred;
-        z[e] = acc / s2[e];
+        for (int q = 0; q < K; ++q) acc += fit.V[q][e] * (tp / fit.scl[q]), tp *= a.t_pred;
+        z[e] = acc / fit.s2[e];
     }
     for (int j = 0; j < kTrackMaxTimes; ++j) {
         double acc = 0.0;
         if (j < n)
-            for (int e = 0; e < K; ++e) acc += L[j][e] * z[e];
+            for (int e = 0; e < K; ++e) acc += fit.L[j][e] * z[e];
         g[j] = j < n ? ww[j] * acc : 0.0;
     }
 }
@@ -284,7 +260,7 @@ __global__ __launch_bounds__(kSwarmThreads) void polyfit_swarm_step_kernel(const
 
 int check_axis(const char *who, const int32_t *times_host, int32_t n_times) {
     if (!times_host) return fail(std::string(who) + ": null argument");
-    if (n_times <= 0 || n_times > kTrackMaxTimes) return fail(std::string(who) + ": 1..16 sample times");
+    if (check_fit_shape(who, n_times, 0)) return 1; // the axis alone: the dataset has no degree, wtk_polyfit_weight_mae checks its own next
     for (int i = 1; i < n_times; ++i)
         if (times_host[i] < times_host[i - 1]) return fail(std::string(who) + ": the sample times must be sorted");
     return 0;
@@ -325,7 +301,7 @@ extern "C" int wtk_polyfit_weight_mae(const double *y_input_dev, const double *y
                                       double *scratch_dev, int64_t scratch_doubles, const int32_t *stop_dev, void *stream) {
     if (!weights_dev || !mae_dev || !scratch_dev) return fail("wtk_polyfit_weight_mae: null argument");
     if (check_axis("wtk_polyfit_weight_mae", sample_times_host, n_times)) return 1;
-    if (degree < 0 || degree + 1 > kTrackMaxCoef) return fail("wtk_polyfit_weight_mae: degree must be in [0, 7]");
+    if (check_fit_shape("wtk_polyfit_weight_mae", n_times, degree)) return 1;
     if (P < 0 || M < 0 || ld < M) return fail("wtk_polyfit_weight_mae: need P >= 0, M >= 0 and a row stride ld >= M");
     if (M > 0 && (!y_input_dev || !y_target_dev)) return fail("wtk_polyfit_weight_mae: null dataset");
     if (P > 65535) return fail("wtk_polyfit_weight_mae: at most 65535 weight vectors per call");

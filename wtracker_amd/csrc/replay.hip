@@ -15,13 +15,13 @@
 //           layout the scan reads.  The <= 16 x 8 SVD of a fit depends on the weights and on WHICH samples of the cycle are finite only, so the cycles are
 //           grouped by that set (a <= 16-bit mask; the caller derives the classes from the track once): pass A solves one SVD per (class, particle) and
 //           keeps the rotated matrix, V, s^2, scl and the compacted weights particle-minor in scratch; pass B, one thread per (cycle, particle), reads its
-//           class's record and the cycle's centres (LDS: one cycle per block) and does track_polyfit_kernel<double>'s dot products and Horner evaluation.
-//           Every operation and its order are that kernel's: the targets have its bits.
+//           class's record and the cycle's centres (LDS: one cycle per block) and solves and evaluates.  Both passes call the functions
+//           track_polyfit_kernel calls (polyfit_solve.h: polyfit_factor, polyfit_eval_axes), so the targets have that kernel's bits.
 //   objective  scan + rows (no row, per-row or slot output) + one division per experiment: the swarm's objective without a host round trip.
 //   A nullable stop flag (the swarm's ctrl word) turns the targets, the objective and, through them only, the scan and the rows reduction into no-ops.
 // Everything relies on -ffp-contract=off (the library's build flag): share * move + carry is a rounded product and a rounded sum, as in Python.
 #include "wtk_internal.h"
-#include "jacobi_svd.h"
+#include "polyfit_solve.h"
 
 #include <cmath>
 
@@ -102,6 +102,18 @@ __host__ __device__ inline int pop_off_scl(int n_times, int K) { return n_times 
 __host__ __device__ inline int pop_off_w(int n_times, int K) { return n_times * K + K * K + 2 * K; }
 __host__ __device__ inline int pop_off_ok(int n_times, int K) { return n_times * K + K * K + 2 * K + n_times; }
 __host__ __device__ inline int pop_record(int n_times, int K) { return n_times * K + K * K + 2 * K + n_times + 1; }
+
+// a (class, particle) record as polyfit_eval_axes reads it; r points at the particle's first field
+struct PopRecordView {
+    const double *r;
+    long long P;
+    int n_times, K;
+    __device__ __forceinline__ double L(int j, int e) const { return r[(j * K + e) * P]; }
+    __device__ __forceinline__ double V(int q, int e) const { return r[(pop_off_V(n_times, K) + q * K + e) * P]; }
+    __device__ __forceinline__ double s2(int e) const { return r[(pop_off_s2(n_times, K) + e) * P]; }
+    __device__ __forceinline__ double scl(int q) const { return r[(pop_off_scl(n_times, K) + q) * P]; }
+    __device__ __forceinline__ double w(int j) const { return r[(pop_off_w(n_times, K) + j) * P]; }
+};
 
 // one step of SineMotorController.step + ViewController.move_position on one axis
 __device__ __forceinline__ void motor_axis(double share, double mv, double &carry, int &pos, int pos_max) {
@@ -248,8 +260,8 @@ __global__ __launch_bounds__(64) void replay_objective_kernel(const ObjectiveArg
     a.objective[e] = a.summary[(long long)e * kSummary + a.num] / a.summary[(long long)e * kSummary + a.den];
 }
 
-// Pass A of the population targets: one thread per (class, particle).  track_polyfit_kernel's compaction, scl, scaled Vandermonde matrix and SVD for the
-// samples the class keeps; the record is written particle-minor (a wave of consecutive particles writes consecutive addresses).
+// Pass A of the population targets: one thread per (class, particle).  The factor of the samples the class keeps; the record is written particle-minor
+// (a wave of consecutive particles writes consecutive addresses).
 __global__ __launch_bounds__(64) void replay_polyfit_solve_kernel(const PopArgs a) {
     if (a.stop && *a.stop) return;
     const int PB = (a.P + 63) / 64;
@@ -262,40 +274,22 @@ __global__ __launch_bounds__(64) void replay_polyfit_solve_kernel(const PopArgs 
     for (int j = 0; j < a.n_times; ++j)
         if ((mask >> j) & 1u) tt[n] = (double)a.times[j], ww[n] = a.weights[(long long)p * a.n_times + j], ++n;
     if (n == 0) return; // no sample: pass B writes valid = 0 without looking at the record
-    // scaled weighted Vandermonde: L[j][q] = w_j t_j^q / scl_q
-    double scl[kTrackMaxCoef];
-    for (int q = 0; q < K; ++q) scl[q] = 0.0;
-    for (int j = 0; j < n; ++j) {
-        double tp = 1.0; // t^q by repeated multiplication, as numpy's vander
-        for (int q = 0; q < K; ++q) {
-            const double v = ww[j] * tp;
-            scl[q] += v * v;
-            tp *= tt[j];
-        }
-    }
-    for (int q = 0; q < K; ++q) scl[q] = scl[q] > 0.0 ? sqrt(scl[q]) : 1.0;
-    double L[kTrackMaxTimes][kTrackMaxCoef], V[kTrackMaxCoef][kTrackMaxCoef];
-    for (int j = 0; j < n; ++j) {
-        double tp = 1.0;
-        for (int q = 0; q < K; ++q) L[j][q] = ww[j] * tp / scl[q], tp *= tt[j];
-    }
     double *r = a.rec + (long long)k * pop_record(a.n_times, K) * a.P + p; // field f of this record: r[f * P]
     const long long P = a.P;
-    const bool ok = jacobi_svd_columns(L, V, n, K);
+    PolyfitFactor fit;
+    const bool ok = polyfit_factor(fit, tt, ww, n, K);
     r[pop_off_ok(a.n_times, K) * P] = ok ? 1.0 : 0.0;
     if (!ok) return; // every cycle of this class and particle: valid = 0
     for (int e = 0; e < K; ++e) {
-        double q = 0.0;
-        for (int j = 0; j < n; ++j) q += L[j][e] * L[j][e];
-        r[(pop_off_s2(a.n_times, K) + e) * P] = q;
-        r[(pop_off_scl(a.n_times, K) + e) * P] = scl[e];
+        r[(pop_off_s2(a.n_times, K) + e) * P] = fit.s2[e];
+        r[(pop_off_scl(a.n_times, K) + e) * P] = fit.scl[e];
     }
     for (int j = 0; j < n; ++j) {
         r[(pop_off_w(a.n_times, K) + j) * P] = ww[j];
-        for (int e = 0; e < K; ++e) r[(j * K + e) * P] = L[j][e];
+        for (int e = 0; e < K; ++e) r[(j * K + e) * P] = fit.L[j][e];
     }
     for (int q = 0; q < K; ++q)
-        for (int e = 0; e < K; ++e) r[(pop_off_V(a.n_times, K) + q * K + e) * P] = V[q][e];
+        for (int e = 0; e < K; ++e) r[(pop_off_V(a.n_times, K) + q * K + e) * P] = fit.V[q][e];
 }
 
 // Pass B: one thread per (cycle, particle), one cycle per block, so the cycle's centres are read once into LDS.  The samples found in the track are
@@ -340,41 +334,8 @@ __global__ __launch_bounds__(64) void replay_polyfit_eval_kernel(const PopArgs a
         a.valid[cp] = 0;
         return;
     }
-    const double *s2 = r + pop_off_s2(a.n_times, K) * P, *scl = r + pop_off_scl(a.n_times, K) * P, *ww = r + pop_off_w(a.n_times, K) * P;
-    const double *V = r + pop_off_V(a.n_times, K) * P;
-    double s2max = 0.0;
-    for (int e = 0; e < K; ++e) s2max = fmax(s2max, s2[e * P]);
-    const double rcond = (double)n * 2.220446049250313e-16; // numpy: len(x) * finfo(float64).eps
-    double cx[kTrackMaxCoef], cy[kTrackMaxCoef];
-#pragma unroll
-    for (int q = 0; q < kTrackMaxCoef; ++q) cx[q] = cy[q] = 0.0;
-    for (int e = 0; e < K; ++e) {
-        const double s2e = s2[e * P];
-        if (!(s2e > rcond * rcond * s2max)) continue; // s_e <= rcond * s_max: the minimum-norm solution leaves the direction at zero
-        double dx = 0.0, dy = 0.0;
-        for (int j = 0; j < n; ++j) {
-            const double l = r[(j * K + e) * P], w = ww[j * P];
-            dx += l * (w * px[j]), dy += l * (w * py[j]);
-        }
-        dx /= s2e, dy /= s2e;
-#pragma unroll
-        for (int q = 0; q < kTrackMaxCoef; ++q)
-            if (q < K) {
-                const double v = V[(q * K + e) * P];
-                cx[q] += v * dx, cy[q] += v * dy;
-            }
-    }
-    // polyval (Horner, highest power first) of c / scl at t_eval
-    double x = 0.0, y = 0.0;
-#pragma unroll
-    for (int q = kTrackMaxCoef - 1; q >= 0; --q)
-        if (q < K) {
-            const double s = scl[q * P];
-            if (q == K - 1)
-                x = cx[q] / s, y = cy[q] / s;
-            else
-                x = cx[q] / s + x * a.t_eval, y = cy[q] / s + y * a.t_eval;
-        }
+    double x, y;
+    polyfit_eval_axes(PopRecordView{r, P, a.n_times, K}, px, py, n, K, a.t_eval, x, y);
     a.a[2 * cp] = x;
     a.a[2 * cp + 1] = y;
     a.valid[cp] = 1;
@@ -521,8 +482,7 @@ extern "C" int wtk_replay_polyfit_targets(const double *track_dev, int32_t n_tra
                                           int32_t *valid_dev, double *scratch_dev, int64_t scratch_doubles, const int32_t *stop_dev, void *stream) {
     if (!track_dev || !weights_dev || !sample_times_host || !cycle_class_dev || !class_mask_dev || !a_dev || !valid_dev || !scratch_dev)
         return fail("wtk_replay_polyfit_targets: null argument");
-    if (n_times <= 0 || n_times > kTrackMaxTimes) return fail("wtk_replay_polyfit_targets: 1..16 sample times");
-    if (degree < 0 || degree + 1 > kTrackMaxCoef) return fail("wtk_replay_polyfit_targets: degree must be in [0, 7]");
+    if (check_fit_shape("wtk_replay_polyfit_targets", n_times, degree)) return 1;
     if (P < 1 || P > 65535) return fail("wtk_replay_polyfit_targets: need 1 <= P <= 65535 weight vectors");
     if (n_track < 0 || n_cycles < 1 || cycle_frame_num <= 0) return fail("wtk_replay_polyfit_targets: need n_track >= 0, n_cycles >= 1 and a positive cycle_frame_num");
     if (n_classes < 1 || n_classes > n_cycles) return fail("wtk_replay_polyfit_targets: need 1 <= n_classes <= n_cycles");

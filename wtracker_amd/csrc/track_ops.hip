@@ -4,7 +4,7 @@
 // rows of a track in one launch each.  These are a few dozen flops per cycle: latency-bound gathers, one thread per sample,
 // fp64 like the reference's numpy code.  No MFMA, no LDS tiling — there is nothing to tile.
 #include "wtk_kernels.h"
-#include "jacobi_svd.h"
+#include "polyfit_solve.h"
 
 #include <cmath>
 
@@ -58,12 +58,8 @@ template <typename T> __global__ __launch_bounds__(64) void track_median_kernel(
 }
 
 // PolyfitController.provide_movement_vector (polyfit_controller.py:54-84) up to the camera offsets (the fit commutes with the
-// translation by the camera corner): numpy.polynomial.polynomial.polyfit(t, centres, deg, w=weights) restated — weighted
-// Vandermonde with columns scaled to unit norm, minimum-norm least squares (numpy.linalg.lstsq = LAPACK gelsd: singular values
-// <= rcond * s_max are treated as zero, rcond = len(t) * eps with len(t) = the finite samples) — then polyval at `t_eval`.
-// The (<= 16 x 8) problem is solved through a one-sided Jacobi SVD of the scaled matrix itself, so the cut-off is numpy's at
-// every admitted degree (an eigen-decomposition of the Gram matrix, which round 2 used, only resolves singular-value ratios
-// down to ~3e-7 and truncated directions numpy keeps at degree >= 4-5 over tens of frames).
+// translation by the camera corner): numpy's weighted polyfit through the finite samples of the cycle (len(t) = their count), then
+// polyval at `t_eval`.  The fit itself is polyfit_solve.h's.
 template <typename T> __global__ __launch_bounds__(64) void track_polyfit_kernel(const TrackPolyfitArgs a) {
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i >= a.n_samples) return;
@@ -77,53 +73,14 @@ template <typename T> __global__ __launch_bounds__(64) void track_polyfit_kernel
         double cx, cy;
         if (f >= 0 && f < a.n_frames && load_center(track, a.n_frames, (int)f, cx, cy)) tt[n] = (double)a.times[j], ww[n] = a.weights[j], px[n] = cx, py[n] = cy, ++n;
     }
-    if (n == 0) {
+    PolyfitFactor fit;
+    if (n == 0 || !polyfit_factor(fit, tt, ww, n, K)) { // no sample, or no converged SVD (never seen): "no prediction" rather than a silently wrong fit
         a.pred[2 * i] = a.pred[2 * i + 1] = 0.0;
         a.valid[i] = 0;
         return;
     }
-    // scaled weighted Vandermonde: L[j][p] = w_j t_j^p / scl_p
-    double scl[kTrackMaxCoef];
-    for (int p = 0; p < K; ++p) scl[p] = 0.0;
-    for (int j = 0; j < n; ++j) {
-        double tp = 1.0; // t^p by repeated multiplication, as numpy's vander
-        for (int p = 0; p < K; ++p) {
-            const double v = ww[j] * tp;
-            scl[p] += v * v;
-            tp *= tt[j];
-        }
-    }
-    for (int p = 0; p < K; ++p) scl[p] = scl[p] > 0.0 ? sqrt(scl[p]) : 1.0;
-    double L[kTrackMaxTimes][kTrackMaxCoef], V[kTrackMaxCoef][kTrackMaxCoef];
-    for (int j = 0; j < n; ++j) {
-        double tp = 1.0;
-        for (int p = 0; p < K; ++p) L[j][p] = ww[j] * tp / scl[p], tp *= tt[j];
-    }
-    if (!jacobi_svd_columns(L, V, n, K)) { // columns still visibly non-orthogonal after 30 sweeps (never seen): "no prediction" rather than a silently wrong fit
-        a.pred[2 * i] = a.pred[2 * i + 1] = 0.0;
-        a.valid[i] = 0;
-        return;
-    }
-    double s2[kTrackMaxCoef], s2max = 0.0;
-    for (int e = 0; e < K; ++e) {
-        double q = 0.0;
-        for (int j = 0; j < n; ++j) q += L[j][e] * L[j][e];
-        s2[e] = q;
-        s2max = fmax(s2max, q);
-    }
-    const double rcond = (double)n * 2.220446049250313e-16; // numpy: len(x) * finfo(float64).eps
-    double cx[kTrackMaxCoef], cy[kTrackMaxCoef];
-    for (int p = 0; p < K; ++p) cx[p] = cy[p] = 0.0;
-    for (int e = 0; e < K; ++e) {
-        if (!(s2[e] > rcond * rcond * s2max)) continue; // s_e <= rcond * s_max: null-space direction, the minimum-norm solution leaves it at zero
-        double dx = 0.0, dy = 0.0; // (u_e . rhs) / s_e = (L_rot[:,e] . rhs) / s_e^2
-        for (int j = 0; j < n; ++j) dx += L[j][e] * (ww[j] * px[j]), dy += L[j][e] * (ww[j] * py[j]);
-        dx /= s2[e], dy /= s2[e];
-        for (int p = 0; p < K; ++p) cx[p] += V[p][e] * dx, cy[p] += V[p][e] * dy;
-    }
-    // polyval (Horner, highest power first) of c / scl at t_eval
-    double x = cx[K - 1] / scl[K - 1], y = cy[K - 1] / scl[K - 1];
-    for (int p = K - 2; p >= 0; --p) x = cx[p] / scl[p] + x * a.t_eval, y = cy[p] / scl[p] + y * a.t_eval;
+    double x, y;
+    polyfit_eval_axes(PolyfitLocal{fit, ww}, px, py, n, K, a.t_eval, x, y);
     a.pred[2 * i] = x;
     a.pred[2 * i + 1] = y;
     a.valid[i] = 1;

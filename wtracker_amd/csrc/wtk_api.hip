@@ -224,8 +224,7 @@ extern "C" int wtk_track_polyfit(const void *track_dev, int32_t track_is_f64, in
                                  double t_eval, double *pred_dev, int32_t *valid_dev, void *stream) {
     if (!track_dev || !cycles_dev || !sample_times_host || !weights_host || !pred_dev || !valid_dev) return fail("wtk_track_polyfit: null argument");
     if (n_samples < 0 || n_frames < 0) return fail("wtk_track_polyfit: negative size");
-    if (n_times <= 0 || n_times > kTrackMaxTimes) return fail("wtk_track_polyfit: 1..16 sample times");
-    if (degree < 0 || degree + 1 > kTrackMaxCoef) return fail("wtk_track_polyfit: degree must be in [0, 7]");
+    if (check_fit_shape("wtk_track_polyfit", n_times, degree)) return 1;
     if (cycle_frame_num <= 0) return fail("wtk_track_polyfit: cycle_frame_num must be positive");
     if (n_samples == 0) return 0;
     TrackPolyfitArgs a;

@@ -21,6 +21,12 @@ namespace wtk {
 int fail(const std::string &msg);
 int fail_hip(const char *what, hipError_t e);
 int ensure_attributes(int device); // kernel attributes, once per device
+// the shapes the device's polynomial fit (polyfit_solve.h) admits, refused under the entry point's name
+inline int check_fit_shape(const char *who, int32_t n_times, int32_t degree) {
+    if (n_times <= 0 || n_times > kTrackMaxTimes) return fail(std::string(who) + ": 1..16 sample times");
+    if (degree < 0 || degree + 1 > kTrackMaxCoef) return fail(std::string(who) + ": degree must be in [0, 7]");
+    return 0;
+}
 }
 #define HIP_TRY(expr)                                                                                                          \
     do {                                                                                                                       \

@@ -58,6 +58,83 @@ def _check_degree(deg) -> int:
     return int(deg)
 
 
+def weights_to_device(owner, weights, N: int, per: str, min_rows: int = 0):
+    """`weights` [P, N] (array: uploaded; tensor: used in place when it already is float64, contiguous and there) as a float64 tensor on the device
+    of `owner` (a WeightEvaluator or a Replay; its `_dev` is read after the shape is checked).  `per` names what a weight belongs to in the error
+    message; P must lie in [min_rows, MAX_POP]."""
+    import torch
+
+    if not isinstance(weights, torch.Tensor):
+        weights = torch.from_numpy(np.ascontiguousarray(weights, dtype=np.float64))
+    if weights.dim() != 2 or weights.shape[1] != N:
+        raise ValueError(f"weights must have shape [P, {N}] (one weight per {per}), got {tuple(weights.shape)}")
+    if not min_rows <= weights.shape[0] <= MAX_POP:
+        raise ValueError(f"{min_rows}..{MAX_POP} weight vectors per call" if min_rows else f"at most {MAX_POP} weight vectors per call")
+    return weights.to(device=owner._dev, dtype=torch.float64).contiguous()
+
+
+def polyfit_config(degree, sample_times, weights) -> PolyfitConfig:
+    """The PolyfitConfig of one weight vector over the (sorted) `sample_times`."""
+    w = [float(v) for v in np.asarray(weights, dtype=np.float64).reshape(-1)]
+    if len(w) != len(sample_times):
+        raise ValueError(f"{len(sample_times)} weights expected, got {len(w)}")
+    return PolyfitConfig(degree=_check_degree(degree), sample_times=[int(t) for t in sample_times], weights=w)
+
+
+W_MAX, W_MIN = 0.9, 0.4  # inertia weight of the swarm at the first / after the last epoch
+
+
+def check_swarm_args(pop_size, max_epoch, max_early_stop, lb, ub) -> tuple:
+    """(P, E) as ints.  swarm_search calls it; a caller that sizes buffers by P calls it first, so that every refusal comes before the device is touched."""
+    if int(pop_size) != pop_size or not 1 <= pop_size <= MAX_POP:
+        raise ValueError(f"pop_size must be in [1, {MAX_POP}]")
+    if int(max_epoch) != max_epoch or max_epoch < 1 or int(max_early_stop) != max_early_stop or max_early_stop < 1:
+        raise ValueError("max_epoch and max_early_stop must be positive integers")
+    if not (np.isfinite(lb) and np.isfinite(ub) and lb < ub):
+        raise ValueError(f"need finite bounds lb < ub, got [{lb}, {ub}]")
+    return int(pop_size), int(max_epoch)
+
+
+def swarm_search(device, N: int, enqueue_value, degree: int, pop_size, c1, c2, max_epoch, max_early_stop, seed, lb, ub, start=None,
+                 _trace: Optional[list] = None) -> SwarmResult:
+    """The particle swarm of `WeightEvaluator.optimize` (its docstring states the rule) over any objective of N weights: `enqueue_value(pos, value,
+    ctrl)` enqueues, on the current stream of `device`, the evaluation of the positions `pos` [P, N] into `value` [P] as a no-op once the stop flag
+    `ctrl` is up.  `start` [K, N], K < P, already checked by the caller, replaces the random start of particles 1 .. K (drawn all the same, so the
+    random numbers of the epochs do not depend on it).  Every epoch is enqueued at once; the host waits once, for the current stream."""
+    import torch
+
+    P, E = check_swarm_args(pop_size, max_epoch, max_early_stop, lb, ub)
+    rng = np.random.default_rng(seed)
+    x0 = lb + (ub - lb) * rng.random((P, N))
+    x0[0, :] = ub
+    if start is not None:
+        x0[1 : 1 + len(start)] = start
+    rand = rng.random((E, 2, P, N))
+    vmax = 0.5 * (ub - lb)
+    with torch.cuda.device(device):
+        f64 = torch.float64
+        stream = torch.cuda.current_stream(device)
+        pos = torch.from_numpy(x0).to(device)
+        rand_dev = torch.from_numpy(rand).to(device)
+        vel = torch.zeros((P, N), dtype=f64, device=device)
+        pbest_pos = pos.clone()
+        pbest_val = torch.full((P,), float("inf"), dtype=f64, device=device)
+        gbest_pos = pos[0].clone()
+        gbest_val = torch.full((1,), float("inf"), dtype=f64, device=device)
+        ctrl = torch.zeros((4,), dtype=torch.int32, device=device)
+        history = torch.full((E,), float("nan"), dtype=f64, device=device)
+        value = torch.empty((P,), dtype=f64, device=device)
+        for e in range(E):
+            enqueue_value(pos, value, ctrl)
+            if _trace is not None:  # tests: the state every epoch starts from and the values it saw (stream-ordered copies)
+                _trace.append((pos.clone(), vel.clone(), value.clone()))
+            hip.polyfit_swarm_step(value, rand_dev[e], P, N, e, int(max_early_stop), W_MAX - (W_MAX - W_MIN) * e / E, c1, c2, lb, ub, vmax, pos, vel,
+                                   pbest_pos, pbest_val, gbest_pos, gbest_val, ctrl, history, stream=stream.cuda_stream)
+        stream.synchronize()  # the one host synchronisation
+        epochs = int(ctrl[2].item())
+        return SwarmResult(weights=gbest_pos.cpu().numpy(), mae=float(gbest_val.item()), history=history[:epochs].cpu().numpy(), epochs=epochs, degree=degree)
+
+
 class WeightEvaluator:
     """Mean absolute error of the weighted polynomial fit over the cycles of one or more experiment logs, for one weight vector (`eval`, the
     reference's method) or a whole population (`eval_many`), and the swarm search over it (`optimize`).
@@ -138,16 +215,7 @@ class WeightEvaluator:
 
     # ------------------------------------------------------------------ evaluation
     def _weights_dev(self, weights):
-        import torch
-
-        if not isinstance(weights, torch.Tensor):
-            weights = torch.from_numpy(np.ascontiguousarray(weights, dtype=np.float64))
-        N = len(self.input_time_offsets)
-        if weights.dim() != 2 or weights.shape[1] != N:
-            raise ValueError(f"weights must have shape [P, {N}] (one weight per input time offset), got {tuple(weights.shape)}")
-        if weights.shape[0] > MAX_POP:
-            raise ValueError(f"at most {MAX_POP} weight vectors per call")
-        return weights.to(device=self._dev, dtype=torch.float64).contiguous()
+        return weights_to_device(self, weights, len(self.input_time_offsets), "input time offset")
 
     def _enqueue_mae(self, w_dev, deg: int, mae_dev, scratch, stop_dev=None):
         import torch
@@ -176,7 +244,7 @@ class WeightEvaluator:
         return float(self.eval_many(w[None, :], deg).cpu().numpy()[0])
 
     # ------------------------------------------------------------------ search
-    W_MAX, W_MIN = 0.9, 0.4  # inertia weight at the first / after the last epoch
+    W_MAX, W_MIN = W_MAX, W_MIN  # the module's, under the names the rule below uses
 
     def optimize(self, deg: int = 2, pop_size: int = 100, c1: float = 2.05, c2: float = 2.05, max_epoch: int = 300, max_early_stop: int = 100, seed: int = 0,
                  lb: float = 0.0, ub: float = 1.0, _trace: Optional[list] = None) -> SwarmResult:
@@ -195,46 +263,14 @@ class WeightEvaluator:
         import torch
 
         deg = _check_degree(deg)
-        N = len(self.input_time_offsets)
-        if int(pop_size) != pop_size or not 1 <= pop_size <= MAX_POP:
-            raise ValueError(f"pop_size must be in [1, {MAX_POP}]")
-        if int(max_epoch) != max_epoch or max_epoch < 1 or int(max_early_stop) != max_early_stop or max_early_stop < 1:
-            raise ValueError("max_epoch and max_early_stop must be positive integers")
-        if not (np.isfinite(lb) and np.isfinite(ub) and lb < ub):
-            raise ValueError(f"need finite bounds lb < ub, got [{lb}, {ub}]")
-        P, E = int(pop_size), int(max_epoch)
-        rng = np.random.default_rng(seed)
-        x0 = lb + (ub - lb) * rng.random((P, N))
-        x0[0, :] = ub
-        rand = rng.random((E, 2, P, N))
-        vmax = 0.5 * (ub - lb)
-        with torch.cuda.device(self._dev):
-            dev, f64 = self._dev, torch.float64
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            pos = torch.from_numpy(x0).to(dev)
-            rand_dev = torch.from_numpy(rand).to(dev)
-            vel = torch.zeros((P, N), dtype=f64, device=dev)
-            pbest_pos = pos.clone()
-            pbest_val = torch.full((P,), float("inf"), dtype=f64, device=dev)
-            gbest_pos = pos[0].clone()
-            gbest_val = torch.full((1,), float("inf"), dtype=f64, device=dev)
-            ctrl = torch.zeros((4,), dtype=torch.int32, device=dev)
-            history = torch.full((E,), float("nan"), dtype=f64, device=dev)
-            mae = torch.empty((P,), dtype=f64, device=dev)
-            scratch = torch.empty((max(1, hip.polyfit_mae_scratch_doubles(P, self.n_series)),), dtype=f64, device=dev)
-            for e in range(E):
-                self._enqueue_mae(pos, deg, mae, scratch, stop_dev=ctrl)
-                if _trace is not None:  # tests: the state every epoch starts from and the MAE values it saw (stream-ordered copies)
-                    _trace.append((pos.clone(), vel.clone(), mae.clone()))
-                hip.polyfit_swarm_step(mae, rand_dev[e], P, N, e, int(max_early_stop), self.W_MAX - (self.W_MAX - self.W_MIN) * e / E, c1, c2, lb, ub, vmax,
-                                       pos, vel, pbest_pos, pbest_val, gbest_pos, gbest_val, ctrl, history, stream=stream)
-            torch.cuda.synchronize(dev)
-            epochs = int(ctrl[2].item())
-            return SwarmResult(weights=gbest_pos.cpu().numpy(), mae=float(gbest_val.item()), history=history[:epochs].cpu().numpy(), epochs=epochs, degree=deg)
+        P, _ = check_swarm_args(pop_size, max_epoch, max_early_stop, lb, ub)
+        scratch = torch.empty((max(1, hip.polyfit_mae_scratch_doubles(P, self.n_series)),), dtype=torch.float64, device=self._dev)
+
+        def enqueue_mae(pos, mae, ctrl):
+            self._enqueue_mae(pos, deg, mae, scratch, stop_dev=ctrl)
+
+        return swarm_search(self._dev, len(self.input_time_offsets), enqueue_mae, deg, pop_size, c1, c2, max_epoch, max_early_stop, seed, lb, ub, _trace=_trace)
 
     def to_config(self, deg: int, weights) -> PolyfitConfig:
         """The PolyfitConfig (sample times = the sorted offsets) that PolyfitController / HipPolyfitController take."""
-        w = [float(v) for v in np.asarray(weights, dtype=np.float64).reshape(-1)]
-        if len(w) != len(self.input_time_offsets):
-            raise ValueError(f"{len(self.input_time_offsets)} weights expected, got {len(w)}")
-        return PolyfitConfig(degree=_check_degree(deg), sample_times=[int(t) for t in self.input_time_offsets], weights=w)
+        return polyfit_config(deg, self.input_time_offsets, weights)

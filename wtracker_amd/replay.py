@@ -32,7 +32,7 @@ import numpy as np
 
 from . import hip
 from .controllers import PolyfitConfig, _read_track_csv
-from .polyfit_opt import MAX_POP, MAX_TIMES, SwarmResult, WeightEvaluator, _check_degree
+from .polyfit_opt import MAX_TIMES, SwarmResult, _check_degree, check_swarm_args, polyfit_config, swarm_search, weights_to_device
 from .resmlp import FoldedResMLP, from_torch_module
 from .sim import LOG_COLUMNS, ExperimentConfig, TimingConfig
 
@@ -268,15 +268,7 @@ class Replay:
         return self._classes[st]
 
     def _weights_dev(self, weights, N: int):
-        import torch
-
-        if not isinstance(weights, torch.Tensor):
-            weights = torch.from_numpy(np.ascontiguousarray(weights, dtype=np.float64))
-        if weights.dim() != 2 or weights.shape[1] != N:
-            raise ValueError(f"weights must have shape [P, {N}] (one weight per sample time), got {tuple(weights.shape)}")
-        if not 1 <= weights.shape[0] <= MAX_POP:
-            raise ValueError(f"1..{MAX_POP} weight vectors per call")
-        return weights.to(device=self._dev, dtype=torch.float64).contiguous()
+        return weights_to_device(self, weights, N, "sample time", min_rows=1)
 
     def _enqueue_population(self, w_dev, degree: int, st: tuple, classes, a, valid, scratch, stop_dev=None):
         cycle_class, class_mask = classes
@@ -342,9 +334,9 @@ class Replay:
     def optimize_polyfit(self, degree: int, sample_times, objective: str = "trimmed_bbox_error", pop_size: int = 100, c1: float = 2.05, c2: float = 2.05,
                          max_epoch: int = 300, max_early_stop: int = 100, seed: int = 0, lb: float = 0.0, ub: float = 1.0, start=None,
                          _trace: Optional[list] = None) -> SwarmResult:
-        """Particle-swarm search for the Polyfit weights of lowest CLOSED-LOOP error of this experiment: WeightEvaluator.optimize's rule and random-number
-        protocol exactly (the same wtk_polyfit_swarm_step; see that docstring), with `objective` (see `objective`) of the replayed population in the place
-        of the open-loop MAE.  Per epoch: targets of the positions, objective, step; every epoch is enqueued at once and the host waits once.
+        """Particle-swarm search for the Polyfit weights of lowest CLOSED-LOOP error of this experiment: WeightEvaluator.optimize's search
+        (polyfit_opt.swarm_search; see that docstring for the rule) with `objective` (see `objective`) of the replayed population in the place of the
+        open-loop MAE.  Per epoch: targets of the positions, objective, step; every epoch is enqueued at once and the host waits once.
 
         `start` [K, N] (K < pop_size) replaces the random start of particles 1 .. K; particle 0 stays at `ub`.  With the open-loop winner in `start` the
         result is never worse than it (nor than uniform weights).  In the returned SwarmResult `mae` holds the objective value of `weights` and `history`
@@ -357,67 +349,34 @@ class Replay:
 
         degree, st = _check_degree(degree), self._sample_times(sample_times)
         kind = self._objective_kind(objective)
-        N = len(st)
-        if int(pop_size) != pop_size or not 1 <= pop_size <= MAX_POP:
-            raise ValueError(f"pop_size must be in [1, {MAX_POP}]")
-        if int(max_epoch) != max_epoch or max_epoch < 1 or int(max_early_stop) != max_early_stop or max_early_stop < 1:
-            raise ValueError("max_epoch and max_early_stop must be positive integers")
-        if not (np.isfinite(lb) and np.isfinite(ub) and lb < ub):
-            raise ValueError(f"need finite bounds lb < ub, got [{lb}, {ub}]")
-        P, E = int(pop_size), int(max_epoch)
-        rng = np.random.default_rng(seed)
-        x0 = lb + (ub - lb) * rng.random((P, N))
-        x0[0, :] = ub
+        N, (P, _) = len(st), check_swarm_args(pop_size, max_epoch, max_early_stop, lb, ub)
         if start is not None:
             start = np.asarray(start, dtype=np.float64)
             if start.ndim != 2 or start.shape[1] != N or start.shape[0] > P - 1:
                 raise ValueError(f"start must have shape [K, {N}] with K <= pop_size - 1, got {start.shape}")
             if not (np.isfinite(start).all() and (start >= lb).all() and (start <= ub).all()):
                 raise ValueError(f"start must lie inside [{lb}, {ub}]")
-            x0[1 : 1 + len(start)] = start
-        rand = rng.random((E, 2, P, N))
-        vmax = 0.5 * (ub - lb)
         classes = self.polyfit_class_table(st)  # from the track, before any epoch is enqueued
         self._last_times = st
-        W_MAX, W_MIN = WeightEvaluator.W_MAX, WeightEvaluator.W_MIN
         with torch.cuda.device(self._dev):
             dev, f64 = self._dev, torch.float64
-            stream = self._stream()
-            pos = torch.from_numpy(x0).to(dev)
-            rand_dev = torch.from_numpy(rand).to(dev)
-            vel = torch.zeros((P, N), dtype=f64, device=dev)
-            pbest_pos = pos.clone()
-            pbest_val = torch.full((P,), float("inf"), dtype=f64, device=dev)
-            gbest_pos = pos[0].clone()
-            gbest_val = torch.full((1,), float("inf"), dtype=f64, device=dev)
-            ctrl = torch.zeros((4,), dtype=torch.int32, device=dev)
-            history = torch.full((E,), float("nan"), dtype=f64, device=dev)
-            value = torch.empty((P,), dtype=f64, device=dev)
             tg = Targets("polyfit", P, torch.zeros((self.n_cycles, P, 2), dtype=f64, device=dev), None,
                          torch.zeros((self.n_cycles, P), dtype=torch.int32, device=dev))
             fit_scratch = torch.empty((max(1, hip.replay_polyfit_targets_scratch_doubles(int(classes[1].numel()), P, N, degree)),), dtype=f64, device=dev)
             buf = self._objective_buffers(P)
-            for e in range(E):
-                self._enqueue_population(pos, degree, st, classes, tg.a, tg.valid, fit_scratch, stop_dev=ctrl)
-                self._enqueue_objective(tg, kind, buf, value, stop_dev=ctrl)
-                if _trace is not None:  # tests: the state every epoch starts from and the objective values it saw (stream-ordered copies)
-                    _trace.append((pos.clone(), vel.clone(), value.clone()))
-                hip.polyfit_swarm_step(value, rand_dev[e], P, N, e, int(max_early_stop), W_MAX - (W_MAX - W_MIN) * e / E, c1, c2, lb, ub, vmax, pos, vel,
-                                       pbest_pos, pbest_val, gbest_pos, gbest_val, ctrl, history, stream=stream)
-            torch.cuda.current_stream(dev).synchronize()  # the one host synchronisation
-            epochs = int(ctrl[2].item())
-            return SwarmResult(weights=gbest_pos.cpu().numpy(), mae=float(gbest_val.item()), history=history[:epochs].cpu().numpy(), epochs=epochs,
-                               degree=degree)
+
+        def enqueue_error(pos, value, ctrl):
+            self._enqueue_population(pos, degree, st, classes, tg.a, tg.valid, fit_scratch, stop_dev=ctrl)
+            self._enqueue_objective(tg, kind, buf, value, stop_dev=ctrl)
+
+        return swarm_search(self._dev, N, enqueue_error, degree, pop_size, c1, c2, max_epoch, max_early_stop, seed, lb, ub, start=start, _trace=_trace)
 
     def to_config(self, degree: int, weights, sample_times=None) -> PolyfitConfig:
         """The PolyfitConfig of a search result.  `sample_times` default to those of the last `optimize_polyfit` / `polyfit_population` call."""
         st = self._last_times if sample_times is None else self._sample_times(sample_times)
         if st is None:
             raise ValueError("no sample times yet: pass sample_times, or call optimize_polyfit / polyfit_population first")
-        w = [float(v) for v in np.asarray(weights, dtype=np.float64).reshape(-1)]
-        if len(w) != len(st):
-            raise ValueError(f"{len(st)} weights expected, got {len(w)}")
-        return PolyfitConfig(degree=_check_degree(degree), sample_times=list(st), weights=w)
+        return polyfit_config(degree, st, weights)
 
     # ------------------------------------------------------------------ the loop
     def run(self, targets: Targets, rows: Sequence[int] = (0,), per_row_errors: bool = False) -> ReplayResult:
