@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define WTK_ABI_VERSION 7 /* 7: + wtk_yolo_create_planned / wtk_yolo_plan, wtk_yolo_status (additive); 2: + wtk_yolo_predict_views / _nms, wtk_track_*, wtk_comm_*; 3: + WTK_F16X3, wtk_recheck_*; 4: + wtk_recheck_select_counted; 5: + wtk_recheck_enqueue / _scatter; 6: + wtk_hybrid_*; still 7: + wtk_background, wtk_precise_error (additive: every earlier entry point is unchanged); still 7: + wtk_polyfit_*; still 7: + wtk_replay_* (additive); still 7: + wtk_replay_polyfit_targets / _scratch_doubles, wtk_replay_objective (additive) */
+#define WTK_ABI_VERSION 7 /* 7: + wtk_yolo_create_planned / wtk_yolo_plan, wtk_yolo_status (additive); 2: + wtk_yolo_predict_views / _nms, wtk_track_*, wtk_comm_*; 3: + WTK_F16X3, wtk_recheck_*; 4: + wtk_recheck_select_counted; 5: + wtk_recheck_enqueue / _scatter; 6: + wtk_hybrid_*; still 7: + wtk_background, wtk_precise_error (additive: every earlier entry point is unchanged); still 7: + wtk_polyfit_*; still 7: + wtk_replay_* (additive); still 7: + wtk_replay_polyfit_targets / _scratch_doubles, wtk_replay_objective (additive); still 7: + wtk_replay_yolo_step / _positions / _track (additive) */
 
 typedef enum wtk_dtype {
     WTK_F32 = 0, /* fp32 storage, exact-fp32 MFMA (v_mfma_f32_16x16x4_f32): parity mode   */
@@ -578,6 +578,31 @@ int wtk_replay_objective(const wtk_replay_config *cfg, int32_t kind, int32_t E, 
                          const double *a_dev, const double *b_dev, const int32_t *valid_dev, const double *share_dev, int32_t *pos_dev,
                          int32_t *move_dev, double *summary_dev, double *scratch_dev, int64_t scratch_doubles, int32_t objective,
                          double *objective_dev, const int32_t *stop_dev, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The YOLO controller's closed loop from device-resident state (csrc/replay.hip): the one experiment kind whose
+ * targets depend on the camera view.  E = 1; pos_dev / move_dev are the scan's [n_cycles][1][2] arrays, filled cycle by cycle.  The caller
+ * writes pos_dev[0] (the clamped init position) and then enqueues, per cycle c on ONE stream: wtk_yolo_predict_views (B = 1,
+ * pos_xy_dev = pos_dev + 2 c, the controller's decision view) and wtk_replay_yolo_step.  Nothing goes to the host in between.
+ *
+ * wtk_replay_yolo_step   HipYoloController.provide_movement_vector on xywh_dev (float32 [4], view pixels, NaN x 4 = no detection) as numpy 2
+ *     evaluates it on a float32 row: (0, 0) unless all four are finite; else per axis mid = x + w / 2 and mid - cam_size / 2 in float32,
+ *     rounded half to even.  Then the scan's moving_frame_num motor steps (the same device function).  Writes move_dev[c] and, where
+ *     c + 1 < n_cycles, pos_dev[c + 1].  One thread, plain stores.
+ * wtk_replay_yolo_positions   one thread per logged frame: frame_pos_dev [R][2], the platform position at that frame's camera picture
+ *     (wtk_replay_rows' position of the row): what wtk_yolo_predict_views takes as pos_xy_dev for the log's detections.
+ * wtk_replay_yolo_track   one thread per logged frame: xywh_dev [R][4] float32 view-pixel detections -> track_dev [R][4] float64 absolute
+ *     boxes, what wtk_replay_rows reads.  TrackLogger._write_rows' dtype rule, per cycle: all L rows finite -> x + cam_x in float32, then
+ *     widened; any row NaN -> the whole cycle in float64.  NaN rows stay NaN (wtk_replay_rows logs them as 0, 0, 0, 0).
+ * Refused (error code, no memory touched): what wtk_replay_scan refuses of the geometry, c outside [0, n_cycles), a camera or frame side
+ * above 8192, a null pointer.
+ * ------------------------------------------------------------------------------------------ */
+int wtk_replay_yolo_step(const wtk_replay_config *cfg, int32_t n_cycles, int32_t c, const float *xywh_dev, const double *share_dev,
+                         int32_t *pos_dev, int32_t *move_dev, void *stream);
+int wtk_replay_yolo_positions(const wtk_replay_config *cfg, int32_t n_cycles, const double *share_dev, const int32_t *pos_dev,
+                              const int32_t *move_dev, int32_t *frame_pos_dev, void *stream);
+int wtk_replay_yolo_track(const wtk_replay_config *cfg, int32_t n_cycles, const float *xywh_dev, const int32_t *frame_pos_dev, double *track_dev,
+                          void *stream);
 
 #ifdef __cplusplus
 }

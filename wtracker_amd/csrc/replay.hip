@@ -18,6 +18,11 @@
 //           class's record and the cycle's centres (LDS: one cycle per block) and solves and evaluates.  Both passes call the functions
 //           track_polyfit_kernel calls (polyfit_solve.h: polyfit_factor, polyfit_eval_axes), so the targets have that kernel's bits.
 //   objective  scan + rows (no row, per-row or slot output) + one division per experiment: the swarm's objective without a host round trip.
+//   yolo    the YOLO controller's loop, whose targets depend on the camera view: between two single-frame detector calls ONE thread
+//           turns the detector's float32 row into the move (numpy's float32 arithmetic of HipYoloController.provide_movement_vector) and the next cycle's
+//           position, where wtk_yolo_predict_views reads it; after the loop one thread per logged frame gives the frame's platform position (the
+//           detector's pos_xy for the log pass) and one thread per logged frame turns view-pixel detections into the absolute float64 track the rows
+//           kernel reads (TrackLogger's per-cycle float32 / float64 rule).  The motor is motor_steps() / frame_position(), shared with scan and rows.
 //   A nullable stop flag (the swarm's ctrl word) turns the targets, the objective and, through them only, the scan and the rows reduction into no-ops.
 // Everything relies on -ffp-contract=off (the library's build flag): share * move + carry is a rounded product and a rounded sum, as in Python.
 #include "wtk_internal.h"
@@ -95,6 +100,26 @@ struct ObjectiveArgs {
     const int *stop;
 };
 
+struct YoloStepArgs {
+    Geometry g;
+    int c, C;
+    const float *xywh;   // [4] the single-frame call's row, view pixels; NaN x 4 = no detection
+    const double *share; // [M]
+    int *pos;            // [C][1][2]: reads pos[c], writes pos[c + 1] (where c + 1 < C)
+    int *move;           // [C][1][2]: writes move[c]
+};
+
+struct YoloFramesArgs {
+    Geometry g;
+    long long R; // logged rows
+    const double *share;
+    const int *pos, *move; // [C][1][2]
+    int *frame_pos;        // [R][2] platform position at every logged frame's camera picture (the positions kernel writes it)
+    const int *frame_pos_in; // the same array as the track kernel reads it
+    const float *xywh;     // [R][4] detections in view pixels
+    double *track;         // [R][4] absolute xywh
+};
+
 // fields of a (class, particle) record, each P doubles apart: L_rot [n_times][K], V [K][K], s2 [K], scl [K], compacted weights [n_times], converged
 __host__ __device__ inline int pop_off_V(int n_times, int K) { return n_times * K; }
 __host__ __device__ inline int pop_off_s2(int n_times, int K) { return n_times * K + K * K; }
@@ -121,6 +146,24 @@ __device__ __forceinline__ void motor_axis(double share, double mv, double &carr
     const double took = rint(want); // round half to even: Python's round on a float
     carry = want - took;
     pos = (int)fmin(fmax((double)pos + took, 0.0), (double)pos_max);
+}
+
+// `steps` motor steps of the move (mx, my) from (px, py), the carry starting at zero: what a cycle's moving phase does to the platform (steps = M) and what
+// has happened to it before a frame of that phase (steps < M).  The ONE statement of the motor: the scan, the rows and the YOLO loop's kernels all call it.
+__device__ __forceinline__ void motor_steps(const Geometry &g, const double *share, int steps, double mx, double my, int &px, int &py) {
+    double cx = 0.0, cy = 0.0;
+    for (int k = 0; k < steps; ++k) {
+        const double sh = share[k];
+        motor_axis(sh, mx, cx, px, g.x_max);
+        motor_axis(sh, my, cy, py, g.y_max);
+    }
+}
+
+// the platform position at the camera picture of step `step` of a cycle, from the cycle's start position and move ([C][E][2] entry ce)
+__device__ __forceinline__ void frame_position(const Geometry &g, const double *share, const int *pos, const int *move, long long ce, int step, int &px, int &py) {
+    px = pos[2 * ce], py = pos[2 * ce + 1];
+    const int done = step <= g.I ? 0 : (step - g.I > g.M ? g.M : step - g.I); // motor steps taken before this frame's camera picture
+    if (done > 0) motor_steps(g, share, done, (double)move[2 * ce], (double)move[2 * ce + 1], px, py);
 }
 
 // the controller's move on one axis from the camera corner; a non-finite result is no move, a huge one saturates at +-2^30
@@ -164,12 +207,7 @@ __global__ __launch_bounds__(kScanThreads) void replay_scan_kernel(const ScanArg
             }
         }
         a.move[2 * ce] = (int)mx, a.move[2 * ce + 1] = (int)my;
-        double cx = 0.0, cy = 0.0;
-        for (int k = 0; k < g.M; ++k) {
-            const double sh = a.share[k];
-            motor_axis(sh, mx, cx, px, g.x_max);
-            motor_axis(sh, my, cy, py, g.y_max);
-        }
+        motor_steps(g, a.share, g.M, mx, my, px, py);
     }
 }
 
@@ -188,17 +226,8 @@ __global__ __launch_bounds__(kRowThreads) void replay_rows_kernel(const RowsArgs
         if (r >= a.R) continue;
         const int c = (int)(r / g.L), step = (int)(r - (long long)c * g.L);
         const long long ce = (long long)c * a.E + e;
-        int px = a.pos[2 * ce], py = a.pos[2 * ce + 1];
-        const int done = step <= g.I ? 0 : (step - g.I > g.M ? g.M : step - g.I); // motor steps taken before this frame's camera picture
-        if (done > 0) {
-            const double mx = (double)a.move[2 * ce], my = (double)a.move[2 * ce + 1];
-            double cx = 0.0, cy = 0.0;
-            for (int k = 0; k < done; ++k) {
-                const double sh = a.share[k];
-                motor_axis(sh, mx, cx, px, g.x_max);
-                motor_axis(sh, my, cy, py, g.y_max);
-            }
-        }
+        int px, py;
+        frame_position(g, a.share, a.pos, a.move, ce, step, px, py);
         const double cam_x = (double)(px - g.cam_w / 2), cam_y = (double)(py - g.cam_h / 2);
         const double mic_x = (double)(px - g.mic_w / 2), mic_y = (double)(py - g.mic_h / 2);
         const double mic_w = (double)g.mic_w, mic_h = (double)g.mic_h;
@@ -258,6 +287,64 @@ __global__ __launch_bounds__(64) void replay_objective_kernel(const ObjectiveArg
     if (e >= a.E) return;
     // the float64 division Summary's properties perform on the host (counts are exact doubles); 0 / 0 = NaN, which the swarm never lets win
     a.objective[e] = a.summary[(long long)e * kSummary + a.num] / a.summary[(long long)e * kSummary + a.den];
+}
+
+// The YOLO controller between two single-frame detector calls: HipYoloController.provide_movement_vector on the row where the detector left it, then the
+// cycle's motor steps.  The row is float32 and numpy keeps it so: mid = x + w / 2 and mid - cam_size / 2 are float32 operations (the Python float is weak),
+// round() is half to even on that float32 value.  One thread: a cycle is a few dozen flops.
+__global__ __launch_bounds__(64) void replay_yolo_step_kernel(const YoloStepArgs a) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const Geometry g = a.g;
+    int px = a.pos[2 * a.c], py = a.pos[2 * a.c + 1];
+    const float x = a.xywh[0], y = a.xywh[1], w = a.xywh[2], h = a.xywh[3];
+    double mx = 0.0, my = 0.0;
+    if (isfinite(x) && isfinite(y) && isfinite(w) && isfinite(h)) {
+        const float mid_x = x + w / 2.f, mid_y = y + h / 2.f;
+        const float half_w = (float)((double)g.cam_w / 2), half_h = (float)((double)g.cam_h / 2);
+        mx = finish_move((double)(mid_x - half_w)); // rint of a float32 value is the same number in float64
+        my = finish_move((double)(mid_y - half_h));
+    }
+    a.move[2 * a.c] = (int)mx, a.move[2 * a.c + 1] = (int)my;
+    motor_steps(g, a.share, g.M, mx, my, px, py);
+    if (a.c + 1 < a.C) a.pos[2 * (a.c + 1)] = px, a.pos[2 * (a.c + 1) + 1] = py;
+}
+
+// one thread per logged frame: the position wtk_yolo_predict_views cuts the frame's camera view at (the rows kernel's position of that row)
+__global__ __launch_bounds__(kRowThreads) void replay_yolo_positions_kernel(const YoloFramesArgs a) {
+    const long long r = (long long)blockIdx.x * kRowThreads + threadIdx.x;
+    if (r >= a.R) return;
+    const Geometry g = a.g;
+    const int c = (int)(r / g.L), step = (int)(r - (long long)c * g.L);
+    int px, py;
+    frame_position(g, a.share, a.pos, a.move, c, step, px, py);
+    a.frame_pos[2 * r] = px, a.frame_pos[2 * r + 1] = py;
+}
+
+__device__ __forceinline__ bool finite_row(const float *v) { return isfinite(v[0]) && isfinite(v[1]) && isfinite(v[2]) && isfinite(v[3]); }
+
+// one thread per logged frame: TrackLogger._write_rows' `boxes[:, 0] += cams[:, 0]` with the dtype the cycle's batch has there.  A cycle without a miss
+// is a float32 array (the sum is rounded to float32, then widened); one NaN row makes the whole cycle float64.  Misses stay NaN.
+__global__ __launch_bounds__(kRowThreads) void replay_yolo_track_kernel(const YoloFramesArgs a) {
+    const long long r = (long long)blockIdx.x * kRowThreads + threadIdx.x;
+    if (r >= a.R) return;
+    const Geometry g = a.g;
+    const long long first = r / g.L * g.L;
+    bool any_miss = false;
+    for (int i = 0; i < g.L; ++i) any_miss |= !finite_row(a.xywh + 4 * (first + i));
+    const float *v = a.xywh + 4 * r;
+    double *o = a.track + 4 * r;
+    if (!finite_row(v)) {
+        const double nanv = __builtin_nan("");
+        o[0] = o[1] = o[2] = o[3] = nanv;
+        return;
+    }
+    const int cam_x = a.frame_pos_in[2 * r] - g.cam_w / 2, cam_y = a.frame_pos_in[2 * r + 1] - g.cam_h / 2;
+    if (any_miss) {
+        o[0] = (double)v[0] + (double)cam_x, o[1] = (double)v[1] + (double)cam_y;
+    } else {
+        o[0] = (double)(v[0] + (float)cam_x), o[1] = (double)(v[1] + (float)cam_y);
+    }
+    o[2] = (double)v[2], o[3] = (double)v[3];
 }
 
 // Pass A of the population targets: one thread per (class, particle).  The factor of the samples the class keeps; the record is written particle-minor
@@ -498,6 +585,56 @@ extern "C" int wtk_replay_polyfit_targets(const double *track_dev, int32_t n_tra
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(replay_polyfit_solve_kernel, dim3((unsigned)(PB * n_classes)), dim3(64), 0, st, a);
     hipLaunchKernelGGL(replay_polyfit_eval_kernel, dim3((unsigned)(PB * n_cycles)), dim3(64), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- the YOLO controller's loop: E = 1, every per-cycle array is [n_cycles][1][2]
+namespace {
+
+int check_yolo(const char *who, const wtk_replay_config *cfg, int32_t n_cycles, Geometry &g, long long &R) {
+    int n_log = 0;
+    // (the track these calls stand for is the detector's own output: it always has the R logged rows; pred_frame_num = 0 is the controller's oldest frame)
+    if (check_config(who, cfg, WTK_REPLAY_OPTIMAL, 1, n_cycles, INT32_MAX, g, n_log)) return 1;
+    if (g.cam_w > 8192 || g.cam_h > 8192 || cfg->frame_w > 8192 || cfg->frame_h > 8192)
+        return fail(std::string(who) + ": camera and frame sizes up to 8192 (the float32 sums of the log are exact in the rows' float64 round trip below 2^13)");
+    R = (long long)n_log * g.L;
+    return 0;
+}
+
+} // namespace
+
+extern "C" int wtk_replay_yolo_step(const wtk_replay_config *cfg, int32_t n_cycles, int32_t c, const float *xywh_dev, const double *share_dev,
+                                    int32_t *pos_dev, int32_t *move_dev, void *stream) {
+    YoloStepArgs a = {};
+    long long R = 0;
+    if (check_yolo("wtk_replay_yolo_step", cfg, n_cycles, a.g, R)) return 1;
+    if (!xywh_dev || !share_dev || !pos_dev || !move_dev) return fail("wtk_replay_yolo_step: null argument");
+    if (c < 0 || c >= n_cycles) return fail("wtk_replay_yolo_step: cycle outside [0, n_cycles)");
+    a.c = c, a.C = n_cycles, a.xywh = xywh_dev, a.share = share_dev, a.pos = pos_dev, a.move = move_dev;
+    hipLaunchKernelGGL(replay_yolo_step_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int wtk_replay_yolo_positions(const wtk_replay_config *cfg, int32_t n_cycles, const double *share_dev, const int32_t *pos_dev,
+                                         const int32_t *move_dev, int32_t *frame_pos_dev, void *stream) {
+    YoloFramesArgs a = {};
+    if (check_yolo("wtk_replay_yolo_positions", cfg, n_cycles, a.g, a.R)) return 1;
+    if (!share_dev || !pos_dev || !move_dev || !frame_pos_dev) return fail("wtk_replay_yolo_positions: null argument");
+    a.share = share_dev, a.pos = pos_dev, a.move = move_dev, a.frame_pos = frame_pos_dev;
+    if (a.R > 0) hipLaunchKernelGGL(replay_yolo_positions_kernel, dim3((unsigned)((a.R + kRowThreads - 1) / kRowThreads)), dim3(kRowThreads), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int wtk_replay_yolo_track(const wtk_replay_config *cfg, int32_t n_cycles, const float *xywh_dev, const int32_t *frame_pos_dev, double *track_dev,
+                                     void *stream) {
+    YoloFramesArgs a = {};
+    if (check_yolo("wtk_replay_yolo_track", cfg, n_cycles, a.g, a.R)) return 1;
+    if (!xywh_dev || !frame_pos_dev || !track_dev) return fail("wtk_replay_yolo_track: null argument");
+    a.xywh = xywh_dev, a.frame_pos_in = frame_pos_dev, a.track = track_dev;
+    if (a.R > 0) hipLaunchKernelGGL(replay_yolo_track_kernel, dim3((unsigned)((a.R + kRowThreads - 1) / kRowThreads)), dim3(kRowThreads), 0, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     return 0;
 }

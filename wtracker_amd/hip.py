@@ -70,6 +70,7 @@ SYMBOLS = [
     "wtk_polyfit_dataset", "wtk_polyfit_mae_scratch_doubles", "wtk_polyfit_weight_mae", "wtk_polyfit_swarm_step",
     "wtk_replay_scan", "wtk_replay_scratch_doubles", "wtk_replay_rows",
     "wtk_replay_polyfit_targets_scratch_doubles", "wtk_replay_polyfit_targets", "wtk_replay_objective",
+    "wtk_replay_yolo_step", "wtk_replay_yolo_positions", "wtk_replay_yolo_track",
 ]
 
 
@@ -225,6 +226,10 @@ def load() -> C.CDLL:
     lib.wtk_replay_polyfit_targets_scratch_doubles.restype = C.c_int64
     lib.wtk_replay_polyfit_targets.argtypes = [vp, i32, i32, i32, vp, i32, vp, i32, i32, f64, vp, vp, i32, vp, vp, vp, C.c_int64, vp, vp]
     lib.wtk_replay_objective.argtypes = [C.POINTER(_ReplayConfig), i32, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int64, i32, vp, vp, vp]
+    if hasattr(lib, "wtk_replay_yolo_step") or not os.environ.get("WTK_HIP_LIB"):  # (an older build named by WTK_HIP_LIB for an A/B timing may lack them)
+        lib.wtk_replay_yolo_step.argtypes = [C.POINTER(_ReplayConfig), i32, i32, vp, vp, vp, vp, vp]
+        lib.wtk_replay_yolo_positions.argtypes = [C.POINTER(_ReplayConfig), i32, vp, vp, vp, vp, vp]
+        lib.wtk_replay_yolo_track.argtypes = [C.POINTER(_ReplayConfig), i32, vp, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -473,6 +478,25 @@ def replay_objective(cfg: _ReplayConfig, kind: int, E: int, n_cycles: int, track
     _check(load().wtk_replay_objective(C.byref(cfg) if cfg is not None else None, kind, E, n_cycles, _ptr(track_dev), n_track, _ptr(a_dev), _ptr(b_dev),
                                        _ptr(valid_dev), _ptr(share_dev), _ptr(pos_dev), _ptr(move_dev), _ptr(summary_dev), _ptr(scratch_dev), scratch_doubles,
                                        objective, _ptr(objective_dev), _ptr(stop_dev), C.c_void_p(stream)), "wtk_replay_objective")
+
+
+def replay_yolo_step(cfg: _ReplayConfig, n_cycles: int, c: int, xywh_dev, share_dev, pos_dev, move_dev, stream: int = 0):
+    """The YOLO controller between two single-frame detector calls (wtk_replay_yolo_step): move_dev[c] from the float32 row xywh_dev, pos_dev[c + 1] after
+    the cycle's motor steps.  pos_dev / move_dev: int32 [n_cycles, 1, 2] device tensors."""
+    _check(load().wtk_replay_yolo_step(C.byref(cfg) if cfg is not None else None, n_cycles, c, _ptr(xywh_dev), _ptr(share_dev), _ptr(pos_dev), _ptr(move_dev),
+                                       C.c_void_p(stream)), "wtk_replay_yolo_step")
+
+
+def replay_yolo_positions(cfg: _ReplayConfig, n_cycles: int, share_dev, pos_dev, move_dev, frame_pos_dev, stream: int = 0):
+    """frame_pos_dev int32 [R, 2]: the platform position at every logged frame's camera picture (wtk_replay_yolo_positions)."""
+    _check(load().wtk_replay_yolo_positions(C.byref(cfg) if cfg is not None else None, n_cycles, _ptr(share_dev), _ptr(pos_dev), _ptr(move_dev),
+                                            _ptr(frame_pos_dev), C.c_void_p(stream)), "wtk_replay_yolo_positions")
+
+
+def replay_yolo_track(cfg: _ReplayConfig, n_cycles: int, xywh_dev, frame_pos_dev, track_dev, stream: int = 0):
+    """View-pixel detections float32 [R, 4] -> the absolute float64 track [R, 4] wtk_replay_rows reads (wtk_replay_yolo_track)."""
+    _check(load().wtk_replay_yolo_track(C.byref(cfg) if cfg is not None else None, n_cycles, _ptr(xywh_dev), _ptr(frame_pos_dev), _ptr(track_dev),
+                                        C.c_void_p(stream)), "wtk_replay_yolo_track")
 
 
 # -------------------------------------------------------------------------------------------------

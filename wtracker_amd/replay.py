@@ -18,8 +18,15 @@ The closed-loop error is also the objective of a weight search (DESIGN.md sectio
     rp.objective(t)                                                     # device float64 [P], no synchronisation
     best = rp.optimize_polyfit(2, [-9, -6, -3, 0, 2, 4], start=[open_loop.weights])
 
-There is no CPU fallback: without a visible GPU the constructor raises.  Not covered: the YOLO controller (its targets depend on the camera view),
-`StepMotorController`, DataAnalyzer's speed and unit columns.
+The YOLO controller's targets depend on the camera view, so its loop cannot be a scan over precomputed targets: `YoloReplay` enqueues the detector's
+single-frame call and a small control kernel per cycle, all on one stream, and the log's detections afterwards in batches:
+
+    yr = YoloReplay(device_frames, timing_config, experiment_config, yolo_config)   # what HipYoloController(tc, cfg, device_frames=...) takes
+    res = yr.run()                    # a ReplayResult with E = 1, bit for bit the host loop's moves and log; one host synchronisation
+    res.detections                    # device float32 [R, 4], view pixels
+
+There is no CPU fallback: without a visible GPU the constructors raise.  Not covered: `StepMotorController`, DataAnalyzer's speed and unit columns, the
+YOLO controller's second look (YoloConfig.recheck_margin).
 """
 from __future__ import annotations
 
@@ -30,8 +37,8 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from . import hip
-from .controllers import PolyfitConfig, _read_track_csv
+from . import hip, yolo_spec
+from .controllers import PolyfitConfig, YoloConfig, _raise_on_overflow, _read_track_csv
 from .polyfit_opt import MAX_TIMES, SwarmResult, _check_degree, check_swarm_args, polyfit_config, swarm_search, weights_to_device
 from .resmlp import FoldedResMLP, from_torch_module
 from .sim import LOG_COLUMNS, ExperimentConfig, TimingConfig
@@ -97,11 +104,11 @@ class Summary:
 
 class ReplayResult:
     """moves, positions [E, C, 2] int32 (the move of cycle c and the platform position at its start); summary; bbox_error / mse_error [E, R] float64 when
-    requested; the full log rows of the experiments named in `rows`."""
+    requested; the full log rows of the experiments named in `rows`; `detections` (YoloReplay only): device float32 [R, 4] xywh in view pixels."""
 
-    def __init__(self, moves, positions, summary, decision_frames, row_ids, row_data, bbox_error, mse_error):
+    def __init__(self, moves, positions, summary, decision_frames, row_ids, row_data, bbox_error, mse_error, detections=None):
         self.moves, self.positions, self.summary, self.decision_frames = moves, positions, summary, decision_frames
-        self.bbox_error, self.mse_error = bbox_error, mse_error
+        self.bbox_error, self.mse_error, self.detections = bbox_error, mse_error, detections
         self._slot = {int(e): k for k, e in enumerate(row_ids)}
         self._rows = row_data  # [slots, R, 16]
 
@@ -414,8 +421,169 @@ class Replay:
             s = summary.cpu().numpy()
             res = ReplayResult(
                 moves=move.permute(1, 0, 2).contiguous().cpu().numpy(), positions=pos.permute(1, 0, 2).contiguous().cpu().numpy(),
-                summary=Summary(s[:, 0].copy(), s[:, 1].astype(np.int64), s[:, 2].copy(), s[:, 3].astype(np.int64), s[:, 4].astype(np.int64), s[:, 5].copy()),
+                summary=_summary_of(s),
                 decision_frames=np.arange(C, dtype=np.int64) * self.L + self.I, row_ids=row_ids,
                 row_data=row_data.cpu().numpy() if row_ids else np.zeros((0, R, hip.REPLAY_ROW_DOUBLES)),
                 bbox_error=bbox.cpu().numpy() if per_row_errors else None, mse_error=mse.cpu().numpy() if per_row_errors else None)
         return res
+
+
+def _summary_of(s: np.ndarray) -> Summary:
+    return Summary(s[:, 0].copy(), s[:, 1].astype(np.int64), s[:, 2].copy(), s[:, 3].astype(np.int64), s[:, 4].astype(np.int64), s[:, 5].copy())
+
+
+class YoloReplay:
+    """The closed loop of HipYoloController on device-resident frames, without a host wait per cycle: what `Simulator` + `SineMotorController` +
+    `TrackLogger(HipYoloController(timing_config, yolo_config, device_frames=device_frames))` produce, bit for bit (same handles, same kernels, same inputs).
+
+    Phase 1, per scanned cycle on one stream: the single-frame detector call on the controller's decision view (`yolo_config.load_model().detector(net_hw, 1)`,
+    frame and platform position read from device memory) and wtk_replay_yolo_step, which turns the row into the move and the next cycle's position where the
+    next call reads it.  Phase 2: the platform position of every logged frame, the detector over the R logged frames in chunks of `log_batch`, the absolute
+    track with TrackLogger's dtype rule, and wtk_replay_rows.  `run` is ordered behind the caller's current stream once and synchronises once, at the end;
+    then the handles' range-guard words are checked.
+
+    `log_batch`: None = cycle_frame_num on the handle `detector(net_hw, cycle_frame_num)` returns (the host loop's cycle batch: its bits).  Any other size
+    takes a throughput-plan handle of that size owned by this object (large-batch kernels, the sparse box tail); the last chunk may be partial.  Handles on
+    different plans agree within the tolerance both meet against the fp32 restatement, not bit for bit.
+
+    The constructor makes one warm-up call per batch size it will use (a latency-plan handle times its launch candidates inside its first eager call at a
+    batch size, which waits for the device) and waits for it, so `run` never does.  The model's handles are shared with every controller of the same
+    YoloConfig: do not run one of those while a `run` is enqueued.
+
+    Refused: `recheck_margin > 0` (the second look reads the margins on the host), frames that are not a contiguous CUDA uint8 [F, H, W] / [F, H, W, 3] tensor
+    or fewer than `num_frames`, and every geometry wtk_replay_rows refuses."""
+
+    def __init__(self, device_frames, timing_config: TimingConfig, experiment_config: ExperimentConfig, yolo_config: YoloConfig, log_batch: Optional[int] = None):
+        if hip.device_count() < 1:
+            raise hip.WtkError("YoloReplay needs a GPU: no HIP device visible (there is no CPU fallback)")
+        import torch
+
+        tc, ec, fr = timing_config, experiment_config, device_frames
+        if yolo_config.recheck_margin > 0:
+            raise ValueError("YoloReplay does not take recheck_margin > 0: the second look reads the first call's margins on the host, once per call")
+        if not getattr(fr, "is_cuda", False) or str(fr.dtype) != "torch.uint8" or fr.dim() not in (3, 4) or (fr.dim() == 4 and fr.shape[3] != 3):
+            raise hip.WtkError("device_frames must be a CUDA uint8 tensor [F,H,W] or [F,H,W,3]")
+        if not fr.is_contiguous():
+            raise hip.WtkError("device_frames must be contiguous")
+        F = int(ec.num_frames)
+        if int(fr.shape[0]) < F:
+            raise ValueError(f"device_frames holds {int(fr.shape[0])} frames, the experiment needs num_frames = {F}")
+        self.timing_config, self.experiment_config, self.yolo_config = tc, ec, yolo_config
+        self._frames, self._dev = fr, fr.device
+        cam, mic = tuple(int(v) for v in tc.camera_size_px), tuple(int(v) for v in tc.micro_size_px)
+        self.L, self.I, self.M, self.P = int(tc.cycle_frame_num), int(tc.imaging_frame_num), int(tc.moving_frame_num), int(tc.pred_frame_num)
+        # what wtk_replay_rows refuses, before anything is enqueued (the entry points refuse it again)
+        if self.I < 1 or self.M < 1 or F - 1 < self.I:
+            raise ValueError("the experiment needs imaging_frame_num >= 1, moving_frame_num >= 1 and at least one decision frame")
+        if not 0 <= self.P <= self.I:
+            raise ValueError(f"pred_frame_num = {self.P} lies outside [0, imaging_frame_num = {self.I}]")
+        if cam[0] < mic[0] or cam[1] < mic[1] or min(mic) < 0:
+            raise ValueError(f"the camera {cam} is smaller than the microscope {mic}")
+        H, W = int(fr.shape[1]), int(fr.shape[2])
+        if max(cam + (H, W)) > 8192:
+            raise ValueError("camera and frame sides up to 8192 pixels (wtk_replay_yolo_track)")
+        self.frame_shape = (H, W)
+        self.n_cycles = (F - 1 - self.I) // self.L + 1
+        self.n_log = (F - 1) // self.L
+        self.n_rows = R = self.n_log * self.L
+        self.log_batch = self.L if log_batch is None else int(log_batch)
+        if self.log_batch < 1:
+            raise ValueError("log_batch must be at least 1")
+        self._cfg = hip.replay_config(F, self.I, self.M, self.P, cam, mic, (W, H), ec.init_position)
+        kw = dict(yolo_config.pred_kwargs)
+        self._imgsz, self._conf, self._iou = int(kw.pop("imgsz", 640)), float(kw.pop("conf", 0.25)), float(kw.pop("iou", 0.7))
+        if "max_det" in kw:
+            raise TypeError("predict() got multiple values for keyword argument 'max_det'")  # as HipYoloController.launch_views
+        self._view = cam
+        net_hw = yolo_spec.letterbox_shape(cam[0], cam[1], self._imgsz)  # the view's shape is (rows = w, cols = h)
+        model = self._model = yolo_config.load_model()
+        # the cycle batch's handle first: where both calls share one handle (plan "latency") and it was too small for L, the model replaces it here
+        self.log_detector = model.detector(net_hw, self.L) if self.log_batch == self.L else None
+        self.step_detector = model.detector(net_hw, 1)
+        self._own = None
+        if self.log_detector is None:
+            width, depth, maxch = yolo_spec.scale_params(yolo_config.scale)
+            self.log_detector = self._own = hip.HipYolo(model.weights, net_hw, self.log_batch, dtype=self.step_detector.dtype, nc=model.nc, width=width, depth=depth,
+                                                        max_channels=maxch, device=yolo_config.device_index(), plan="throughput")
+        C, dev, i32, f32 = self.n_cycles, self._dev, torch.int32, torch.float32
+        # the controller's deque holds the cycle's frames 0 .. I at the decision and it reads entry [-pred_frame_num] (entry 0 when that is 0)
+        decision = list(range(self.I + 1))[-self.P]
+        share = np.array([(np.cos((k * np.pi) / self.M) - np.cos(((k + 1) * np.pi) / self.M)) / 2 for k in range(self.M)], dtype=np.float64)
+        x0, y0 = (int(min(max(int(v), 0), m - 1)) for v, m in zip(ec.init_position, (W, H)))
+        with torch.cuda.device(dev):
+            self._stream = torch.cuda.Stream(device=dev)
+            self._share = torch.from_numpy(share).to(dev)
+            self._pos0 = torch.tensor([x0, y0], dtype=i32, device=dev)
+            self._decision_idx = (torch.arange(C, dtype=i32, device=dev) * self.L + decision).contiguous()
+            self._log_idx = torch.arange(max(R, 1), dtype=i32, device=dev)
+            self._pos, self._move = torch.zeros((C, 1, 2), dtype=i32, device=dev), torch.zeros((C, 1, 2), dtype=i32, device=dev)
+            self._step_rows = torch.zeros((C, 4), dtype=f32, device=dev)  # the single-frame call's row of every cycle
+            self._step_conf, self._step_anchor = torch.zeros((C,), dtype=f32, device=dev), torch.zeros((C,), dtype=i32, device=dev)
+            self._frame_pos = self._pos0.repeat(max(R, 1), 1).contiguous()
+            self._det = torch.zeros((max(R, 1), 4), dtype=f32, device=dev)
+            self._det_conf, self._det_anchor = torch.zeros((max(R, 1),), dtype=f32, device=dev), torch.zeros((max(R, 1),), dtype=i32, device=dev)
+            self._track = torch.zeros((max(R, 1), 4), dtype=torch.float64, device=dev)
+            self._slots = torch.zeros((1,), dtype=i32, device=dev)
+            self._rows = torch.empty((1, R, hip.REPLAY_ROW_DOUBLES), dtype=torch.float64, device=dev)
+            self._summary = torch.empty((1, hip.REPLAY_SUMMARY_DOUBLES), dtype=torch.float64, device=dev)
+            self._scratch = torch.empty((max(1, hip.replay_scratch_doubles(1, R)),), dtype=torch.float64, device=dev)
+            # the warm-up calls: every batch size `run` will use, on the frames and at the position the run starts from
+            self._pos[0, 0].copy_(self._pos0)
+            self._stream.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(self._stream):
+                self._step_call(0)
+                for n in sorted({min(self.log_batch, R), R % self.log_batch} - {0}):
+                    self._log_call(0, n)
+            self._finish()
+
+    def close(self):
+        """Destroy the log handle this object owns (a `log_batch` other than the cycle length); the model's handles stay with the model."""
+        if self._own is not None:
+            self._stream.synchronize()
+            self._own.close()
+            self._own = None
+
+    def _detectors(self) -> list:
+        return [self.step_detector] if self.log_detector is self.step_detector else [self.step_detector, self.log_detector]
+
+    def _finish(self):
+        self._stream.synchronize()  # the one host synchronisation
+        for det in self._detectors():
+            _raise_on_overflow(det)
+
+    def _step_call(self, c: int):
+        fr, (vw, vh) = self._frames, self._view
+        self.step_detector.predict_views(fr, fr.shape[0], fr.shape[1], fr.shape[2], fr.shape[3] if fr.dim() == 4 else 1, self._decision_idx[c:c + 1], self._pos[c],
+                                         1, vw, vh, self._step_rows[c], self._step_conf[c:c + 1], self._step_anchor[c:c + 1], conf=self._conf, iou=self._iou,
+                                         max_det=1, stream=self._stream.cuda_stream)
+
+    def _log_call(self, r0: int, n: int):
+        fr, (vw, vh) = self._frames, self._view
+        self.log_detector.predict_views(fr, fr.shape[0], fr.shape[1], fr.shape[2], fr.shape[3] if fr.dim() == 4 else 1, self._log_idx[r0:r0 + n],
+                                        self._frame_pos[r0:r0 + n], n, vw, vh, self._det[r0:r0 + n], self._det_conf[r0:r0 + n], self._det_anchor[r0:r0 + n],
+                                        conf=self._conf, iou=self._iou, max_det=1, stream=self._stream.cuda_stream)
+
+    def run(self) -> ReplayResult:
+        """Enqueue the whole experiment and wait for it once.  Two runs give the same bits."""
+        import torch
+
+        C, R, dev = self.n_cycles, self.n_rows, self._dev
+        with torch.cuda.device(dev):
+            st = self._stream.cuda_stream
+            self._stream.wait_stream(torch.cuda.current_stream(dev))  # a caller that refills device_frames in place has its writes on that stream
+            with torch.cuda.stream(self._stream):
+                self._pos[0, 0].copy_(self._pos0)
+                for c in range(C):  # phase 1: nothing in this loop goes to the host
+                    self._step_call(c)
+                    hip.replay_yolo_step(self._cfg, C, c, self._step_rows[c], self._share, self._pos, self._move, stream=st)
+                hip.replay_yolo_positions(self._cfg, C, self._share, self._pos, self._move, self._frame_pos, stream=st)
+                for r0 in range(0, R, self.log_batch):
+                    self._log_call(r0, min(self.log_batch, R - r0))
+                hip.replay_yolo_track(self._cfg, C, self._det, self._frame_pos, self._track, stream=st)
+                hip.replay_rows(self._cfg, 1, C, self._track, R, self._share, self._pos, self._move, self._slots, 1, self._rows, None, None, self._summary,
+                                self._scratch, self._scratch.numel(), stream=st)
+                detections = self._det[:R].clone()
+            self._finish()
+            return ReplayResult(moves=self._move.permute(1, 0, 2).contiguous().cpu().numpy(), positions=self._pos.permute(1, 0, 2).contiguous().cpu().numpy(),
+                                summary=_summary_of(self._summary.cpu().numpy()), decision_frames=np.arange(C, dtype=np.int64) * self.L + self.I, row_ids=[0],
+                                row_data=self._rows.cpu().numpy(), bbox_error=None, mse_error=None, detections=detections)
