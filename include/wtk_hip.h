@@ -604,6 +604,30 @@ int wtk_replay_yolo_positions(const wtk_replay_config *cfg, int32_t n_cycles, co
 int wtk_replay_yolo_track(const wtk_replay_config *cfg, int32_t n_cycles, const float *xywh_dev, const int32_t *frame_pos_dev, double *track_dev,
                           void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Background-subtraction worm boxes (csrc/box_ops.hip): BoxCalculator._calc_bounding_box (dataset/box_calculator.py:75-101) for gray
+ * frames, on frames resident in device memory.  Everything enqueues on `stream`; nothing synchronises or allocates.
+ *
+ * Per selected frame f (frame_idx_dev[i], or i where frame_idx_dev is NULL), in exact integer arithmetic:
+ *   m0 = |f - bg| > diff_thresh;  erode 5 x 5 and dilate 15 x 15 (= the reference's 5 x 5 opening followed by its 11 x 11 dilation), both
+ *   over the in-image pixels of the window only;  for every 8-connected component A2 = twice the area of the polygon through the pixel
+ *   centres of its outer border (cv.contourArea of the RETR_EXTERNAL / CHAIN_APPROX_NONE contour);  the winner has the largest A2, among
+ *   equal A2 the one whose raster-first pixel comes last;  boxes_dev[i] = (min x, min y, width, height) of the winner in pixels,
+ *   (0, 0, 0, 0) where nothing is foreground.
+ * area2_dev [n_sel] int64 (nullable): the winner's A2, 0 without foreground.  mask_dev [n_sel][H][W] uint8 (nullable): the mask after
+ * the morphology, 0 / 255.  boxes_dev may be NULL when area2_dev is: only the mask stage runs (its bit-packed result stays in scratch).
+ * Faults: a frame index outside [0, n_frames) reads nothing and gives box (-1, -1, -1, -1), area -1 and a zero mask; so does a frame
+ * whose border trace exceeds its bound of 8 H W steps (a defect, never seen).  *fault_count_dev += the number of such frames.
+ * scratch: wtk_boxes_scratch_bytes(H, W, n_sel) bytes, 8-byte aligned: [n_sel] uint64 winner keys, then [n_sel][H][ceil(W / 32)] uint32
+ * mask words (bit b of word c of a row = pixel 32 c + b).  wtk_boxes_scratch_bytes returns -1 for sizes wtk_boxes refuses.
+ * Refused (error code, nothing launched): a null pointer, n_frames / H / W / n_sel <= 0, H * W > 2^30, diff_thresh outside 1 .. 255,
+ * scratch too small or misaligned, more than 2^31 - 1 blocks in one call (split the selection).
+ * ------------------------------------------------------------------------------------------ */
+int64_t wtk_boxes_scratch_bytes(int32_t H, int32_t W, int32_t n_sel);
+int wtk_boxes(const uint8_t *frames_dev, int32_t n_frames, int32_t H, int32_t W, const uint8_t *bg_dev, const int32_t *frame_idx_dev,
+              int32_t n_sel, int32_t diff_thresh, int32_t *boxes_dev, int64_t *area2_dev, uint8_t *mask_dev, int32_t *fault_count_dev,
+              void *scratch, int64_t scratch_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,6 +2,7 @@
   * BGExtractor.calc_background               wtracker/dataset/bg_extractor.py:18-75        -> background(), BGExtractor
   * ErrorCalculator.calculate_precise          wtracker/eval/error_calculator.py:64-160       -> precise_error()
   * DataAnalyzer.calc_precise_error            wtracker/eval/data_analyzer.py:289-324         -> precise_error_from_log()
+  * BoxCalculator._calc_bounding_box           wtracker/dataset/box_calculator.py:75-101      -> boxes(), BoxCalculator (csrc/box_ops.hip)
 Both steps run on frames already in device memory (csrc/eval_ops.hip): the background streams the probe frames once (mean) or twice (median) and
 never stacks them on the host; the error is computed per log row from the full frames, so the worm-view images the reference's LoggingController
 saves for it (logging_controller.py:157-170, save_wrm_view) are not needed.  Results are bit-exact to the reference's numpy code.
@@ -83,6 +84,139 @@ class BGExtractor:
 
     def calc_background(self, num_probes: int, sampling: str = "uniform", method: str = "median") -> np.ndarray:
         return background(self.reader, num_probes, sampling, method).cpu().numpy()
+
+
+BOXES_SCRATCH_BYTES = 256 << 20  # boxes() works through a selection in chunks whose scratch stays within this (one frame's, if that alone is larger)
+
+
+def _boxes_threshold(diff_thresh) -> int:
+    assert diff_thresh > 0, "Difference threshold must be greater than 0."
+    thr = min(int(math.floor(diff_thresh)), 255)  # |frame - bg| is an integer of at most 255: > t is > floor(t), and nothing exceeds 255
+    if thr < 1:
+        raise ValueError("diff_thresh below 1 marks every differing pixel: not a threshold boxes() takes")
+    return thr
+
+
+def boxes(frames, background, diff_thresh=20, frame_indices=None, return_area: bool = False, return_mask: bool = False, fault_count=None):
+    """BoxCalculator's box of every selected frame as a CUDA int32 [n, 4] tensor (x, y, w, h), enqueued on the current torch stream with no host
+    synchronisation: threshold |frame - background| > diff_thresh, 5 x 5 opening, 11 x 11 dilation, the bounding box of the contour with the largest
+    cv.contourArea; (0, 0, 0, 0) without foreground (DESIGN.md section 18 states the semantics and what is left unpinned).
+    frames         a contiguous CUDA uint8 [F,H,W] tensor (read in place), or a host array / reader as background() takes them (only the selected frames
+                   are read and uploaded).  [F,H,W,3] is refused: the colour branch goes through cv.cvtColor and is out of scope.
+    background     uint8 [H,W], CUDA or host
+    frame_indices  None (every frame), a sequence, or a CUDA int32 tensor.  On device frames an index outside [0, F) gives the row (-1, -1, -1, -1)
+                   (and area -1, a zero mask) instead of an error, since raising would need a synchronisation; fault_count, a CUDA int32 [1] tensor of the
+                   caller's, has the number of such rows added to it.
+    return_area    also the int64 [n] A2 = twice the winning contour's area;  return_mask  also the uint8 [n,H,W] mask after the morphology (0 / 255).
+    Scratch is 8 + 4 H ceil(W / 32) bytes per frame.  A selection is processed in chunks of max(1, BOXES_SCRATCH_BYTES // that) frames (256 MiB: 951 frames
+    of 1500 x 1500), so 60 000 frames of 1500 x 1500 take 64 calls on one 256 MiB buffer; frame offsets are 64-bit throughout."""
+    import torch
+
+    thr = _boxes_threshold(diff_thresh)
+    on_device = _is_cuda(frames)
+    shape = tuple(frames.shape[1:]) if on_device else (tuple(frames.frame_shape) if hasattr(frames, "frame_shape") else tuple(np.shape(frames)[1:]))
+    if len(shape) == 3:
+        raise ValueError("boxes takes gray frames [F,H,W] only: the reference's colour branch goes through cv.cvtColor and is out of scope")
+    if len(shape) != 2:
+        raise ValueError(f"frames must be uint8 [F,H,W], not frames of shape {shape}")
+    if on_device and (frames.dtype != torch.uint8 or not frames.is_contiguous()):
+        raise ValueError("device frames must be a contiguous CUDA uint8 tensor [F,H,W]")
+    H, W = (int(v) for v in shape)
+    F = len(frames)
+    bg = background if _is_cuda(background) else torch.from_numpy(np.ascontiguousarray(background))
+    if bg.dtype != torch.uint8 or tuple(bg.shape) != (H, W):
+        raise ValueError(f"background must be uint8 [{H},{W}] (gray)")
+    dev = frames.device if on_device else (bg.device if bg.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+    bg = bg.to(dev).contiguous()
+    idx_dev = idx_host = None
+    if frame_indices is None:
+        n = F
+    elif _is_cuda(frame_indices):
+        if not on_device:
+            raise ValueError("device frame indices need device frames")
+        idx_dev = frame_indices.to(dtype=torch.int32).contiguous()
+        n = int(idx_dev.shape[0])
+    else:
+        idx_host = np.asarray(list(frame_indices) if not isinstance(frame_indices, np.ndarray) else frame_indices).astype(np.int64).reshape(-1)
+        n = len(idx_host)
+        if on_device:
+            idx_dev = torch.from_numpy(np.clip(idx_host, -1, 2 ** 31 - 1).astype(np.int32)).to(dev)  # (any index outside [0, F) stays outside)
+    out = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    area = torch.empty(n, dtype=torch.int64, device=dev) if return_area else None
+    mask = torch.empty((n, H, W), dtype=torch.uint8, device=dev) if return_mask else None
+    if n:
+        if fault_count is None:
+            fault_count = torch.zeros(1, dtype=torch.int32, device=dev)
+        per_frame = hip.boxes_scratch_bytes(H, W, 1)
+        wpr = (W + 31) // 32
+        blocks = max(((H + 63) // 64) * ((wpr + 61) // 62), ((H + 31) // 32) * ((wpr + 63) // 64))  # an upper bound of either launch's blocks per frame
+        chunk = max(1, min(BOXES_SCRATCH_BYTES // per_frame, (2 ** 31 - 1) // blocks))
+        scratch = torch.empty(hip.boxes_scratch_bytes(H, W, min(chunk, n)), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream().cuda_stream
+            for lo in range(0, n, chunk):
+                k = min(chunk, n - lo)
+                if on_device:
+                    src, n_src, idx = (frames, F, idx_dev[lo:lo + k]) if idx_dev is not None else (frames[lo:lo + k], k, None)
+                else:
+                    stack = np.empty((k, H, W), dtype=np.uint8)
+                    for j in range(k):
+                        i = int(idx_host[lo + j]) if idx_host is not None else lo + j
+                        f = np.asarray(frames[i])
+                        if f.dtype != np.uint8 or f.shape != (H, W):
+                            raise ValueError(f"frame {i} is {f.dtype} {f.shape}, expected uint8 {(H, W)}")
+                        stack[j] = f
+                    src, n_src, idx = torch.from_numpy(stack).to(dev), k, None
+                hip.boxes(src, n_src, H, W, bg, idx, k, thr, out[lo:lo + k], None if area is None else area[lo:lo + k],
+                          None if mask is None else mask[lo:lo + k], fault_count, scratch, scratch.numel(), stream)
+    res = (out,) + ((area,) if return_area else ()) + ((mask,) if return_mask else ())
+    return res if len(res) > 1 else out
+
+
+class BoxCalculator:
+    """BoxCalculator (box_calculator.py:11-161) with the per-frame image step on the device.  `frames_or_reader`: what boxes() accepts; gray frames only.
+    Boxes are host int64 rows (x, y, w, h), (-1, -1, -1, -1) until computed; num_workers and chunk_size are accepted and ignored."""
+
+    def __init__(self, frames_or_reader, background, diff_thresh: int = 20) -> None:
+        assert diff_thresh > 0, "Difference threshold must be greater than 0."
+        fr = frames_or_reader
+        shape = tuple(fr.frame_shape) if hasattr(fr, "frame_shape") else tuple(fr.shape[1:])
+        assert shape == tuple(background.shape), "Background shape must match frame shape."
+        if len(shape) == 3 and shape[2] == 3:
+            raise ValueError("BoxCalculator takes gray frames only: the reference's colour branch goes through cv.cvtColor and is out of scope")
+        if len(shape) != 2:
+            raise ValueError("background must be either a gray or a color image.")
+        self._frame_reader = fr
+        self._background = background
+        self._diff_thresh = diff_thresh
+        self._all_bboxes = np.full((len(fr), 4), -1, dtype=int)
+
+    def all_bboxes(self) -> np.ndarray:
+        return self._all_bboxes
+
+    def get_bbox(self, frame_idx: int) -> np.ndarray:
+        if self._all_bboxes[frame_idx][0] == -1:
+            self.calc_specified_boxes([frame_idx])
+        return self._all_bboxes[frame_idx]
+
+    def calc_specified_boxes(self, frame_indices, num_workers=None, chunk_size: int = 50) -> np.ndarray:
+        import torch
+
+        idx = np.asarray(list(frame_indices), dtype=np.int64).reshape(-1)
+        if idx.size and (idx.min() < -len(self._frame_reader) or idx.max() >= len(self._frame_reader)):
+            raise IndexError(f"frame index outside the {len(self._frame_reader)} frames")
+        idx = np.where(idx < 0, idx + len(self._frame_reader), idx)
+        todo = np.unique(idx[self._all_bboxes[idx, 0] == -1])
+        if todo.size:
+            faults = torch.zeros(1, dtype=torch.int32, device="cuda" if not _is_cuda(self._frame_reader) else self._frame_reader.device)
+            got = boxes(self._frame_reader, self._background, self._diff_thresh, todo, fault_count=faults).cpu().numpy()
+            if int(faults.item()):
+                raise RuntimeError(f"{int(faults.item())} frame(s) exceeded the border trace's step bound")
+            self._all_bboxes[todo] = got
+        return self._all_bboxes[idx, :]
+
+    def calc_all_boxes(self, num_workers=None, chunk_size: int = 50) -> np.ndarray:
+        return self.calc_specified_boxes(range(len(self._frame_reader)), num_workers, chunk_size)
 
 
 def reference_layout(per_row):

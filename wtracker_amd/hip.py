@@ -71,6 +71,7 @@ SYMBOLS = [
     "wtk_replay_scan", "wtk_replay_scratch_doubles", "wtk_replay_rows",
     "wtk_replay_polyfit_targets_scratch_doubles", "wtk_replay_polyfit_targets", "wtk_replay_objective",
     "wtk_replay_yolo_step", "wtk_replay_yolo_positions", "wtk_replay_yolo_track",
+    "wtk_boxes_scratch_bytes", "wtk_boxes",
 ]
 
 
@@ -230,6 +231,10 @@ def load() -> C.CDLL:
         lib.wtk_replay_yolo_step.argtypes = [C.POINTER(_ReplayConfig), i32, i32, vp, vp, vp, vp, vp]
         lib.wtk_replay_yolo_positions.argtypes = [C.POINTER(_ReplayConfig), i32, vp, vp, vp, vp, vp]
         lib.wtk_replay_yolo_track.argtypes = [C.POINTER(_ReplayConfig), i32, vp, vp, vp, vp]
+    if hasattr(lib, "wtk_boxes") or not os.environ.get("WTK_HIP_LIB"):
+        lib.wtk_boxes_scratch_bytes.argtypes = [i32, i32, i32]
+        lib.wtk_boxes_scratch_bytes.restype = C.c_int64
+        lib.wtk_boxes.argtypes = [vp, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, C.c_int64, vp]
     _lib = lib
     return lib
 
@@ -381,6 +386,23 @@ def background(frames_dev, n_frames: int, frame_bytes: int, probe_idx_dev, n_pro
     """bg_dev[frame_bytes] = per-byte median / mean of the probe frames (wtk_background); probe_idx_dev int32 [n_probes] or None (frames 0..n-1)."""
     _check(load().wtk_background(_ptr(frames_dev), n_frames, frame_bytes, _ptr(probe_idx_dev), n_probes, method, _ptr(bg_dev), C.c_void_p(stream)),
            "wtk_background")
+
+
+def boxes_scratch_bytes(H: int, W: int, n_sel: int) -> int:
+    """Bytes of scratch wtk_boxes needs for n_sel frames of H x W: 8 + 4 H ceil(W / 32) per frame (the winner key and the bit mask)."""
+    n = int(load().wtk_boxes_scratch_bytes(H, W, n_sel))
+    if n < 0:
+        raise WtkError(f"wtk_boxes_scratch_bytes: H = {H}, W = {W}, n_sel = {n_sel} is not a shape wtk_boxes takes (all positive, H * W <= 2^30)")
+    return n
+
+
+def boxes(frames_dev, n_frames: int, H: int, W: int, bg_dev, frame_idx_dev, n_sel: int, diff_thresh: int, boxes_dev, area2_dev, mask_dev, fault_count_dev,
+          scratch_dev, scratch_bytes: int, stream: int = 0):
+    """boxes_dev int32 [n_sel, 4] = the box of the largest foreground contour of every selected frame (wtk_boxes); frame_idx_dev int32 [n_sel] or None
+    (frames 0..n_sel-1), area2_dev int64 [n_sel] or None, mask_dev uint8 [n_sel, H, W] or None, fault_count_dev int32 [1] (added to), scratch_dev of
+    boxes_scratch_bytes(H, W, n_sel) bytes.  boxes_dev None (with area2_dev None): the mask stage alone."""
+    _check(load().wtk_boxes(_ptr(frames_dev), n_frames, H, W, _ptr(bg_dev), _ptr(frame_idx_dev), n_sel, int(diff_thresh), _ptr(boxes_dev), _ptr(area2_dev),
+                            _ptr(mask_dev), _ptr(fault_count_dev), _ptr(scratch_dev), int(scratch_bytes), C.c_void_p(stream)), "wtk_boxes")
 
 
 def precise_error(frames_dev, n_frames: int, H: int, W: int, bg_dev, worm_dev, mic_dev, frame_nums_dev, n_rows: int, diff_thresh: float, err_dev,
