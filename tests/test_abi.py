@@ -30,18 +30,42 @@ def test_library_exports_every_declared_symbol(hip_lib):
     assert hip_lib.wtk_device_count() >= 0
 
 
+C_KINDS = {"int": "i32", "int32_t": "i32", "int64_t": "i64", "size_t": "size", "float": "f32", "double": "f64", "void": "void"}
+CTYPES_KINDS = {ctypes.c_int32: "i32", ctypes.c_int64: "i64", ctypes.c_size_t: "size", ctypes.c_float: "f32", ctypes.c_double: "f64", None: "void"}
+
+
+def header_kind(decl: str, is_param: bool) -> str:
+    """The kind of one C declaration ("const float *x_dev", "int64_t ld", the return type "const char *"): "ptr" or the scalar's own."""
+    if "*" in decl:
+        return "ptr"
+    words = [w for w in decl.split() if w != "const"]
+    return C_KINDS[words[0]] if len(words) == 1 + is_param else "?" + decl  # (one type word, then the parameter's name)
+
+
+def ctypes_kind(t) -> str:
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or (isinstance(t, type) and issubclass(t, ctypes._Pointer)):
+        return "ptr"
+    return CTYPES_KINDS.get(t, "?" + repr(t))
+
+
 def test_binding_argument_counts_match_the_header(hip_lib):
-    """Every prototype of include/wtk_hip.h against the ctypes `argtypes` wtracker_amd.hip.load() declares: a parameter added to one side only
-    would otherwise surface as a corrupted call on the GPU box."""
+    """Every prototype of include/wtk_hip.h against the ctypes `restype` / `argtypes` wtracker_amd.hip.load() declares, kind by kind (pointer,
+    int32, int64, size_t, float, double): a parameter added to one side only, or an int32 where the header has int64_t, would otherwise surface
+    as a corrupted call on the GPU box."""
     text = open(os.path.join(ROOT, "include", "wtk_hip.h")).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    protos = re.findall(r"\b(wtk_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S)
-    assert sorted({n for n, _ in protos}) == header_symbols()
-    for name, params in protos:
+    protos = re.findall(r"^([A-Za-z_][\w \t]*?[\s*])(wtk_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S | re.M)
+    assert [n for _, n, _ in protos] == hip.SYMBOLS  # (the table keeps the header's order)
+    assert sorted(n for _, n, _ in protos) == header_symbols()
+    for ret, name, params in protos:
         p = params.strip()
-        n = 0 if p in ("", "void") else p.count(",") + 1
-        at = getattr(hip_lib, name).argtypes
-        assert (0 if at is None else len(at)) == n, (name, n, at)
+        want = [] if p in ("", "void") else [header_kind(d, True) for d in p.split(",")]
+        fn = getattr(hip_lib, name)
+        assert fn.argtypes is not None, name
+        assert [ctypes_kind(t) for t in fn.argtypes] == want, (name, want, fn.argtypes)
+        assert ctypes_kind(fn.restype) == header_kind(ret, False), (name, ret, fn.restype)
+    restype, argtypes = hip.SIGNATURES["wtk_replay_scratch_doubles"]
+    assert (restype, list(argtypes)) == (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int64])  # (the table itself is what load() applied)
 
 
 def test_every_environment_switch_is_documented():

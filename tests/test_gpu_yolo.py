@@ -1,7 +1,9 @@
 """GPU parity: YOLOv8 detector path (stem, implicit-GEMM convs, SPPF, head select) vs the CPU
 restatement (oracle/yolo_oracle.py; parity unpinned — no ultralytics, no trained weights) on the
 same seeded weights and frames.  Everything goes through the C ABI."""
+import gc
 import os
+import weakref
 
 import numpy as np
 import pytest
@@ -646,8 +648,8 @@ def test_views_call_is_ordered_behind_writes_pending_on_the_callers_stream(hip_l
 
 def test_a_handle_replaced_by_a_larger_one_stays_valid_for_the_call_still_in_flight(hip_lib, tmp_path):
     """a call launched on lane 1 (the deferred cycle batch) names its detector handle in its token.  When a later, larger call makes the
-    controller replace that handle (capacity 16 -> 64), the device drains first and the old handle stays readable until its tokens are collected:
-    the token's rows are the rows an undisturbed call returns."""
+    controller replace that handle (capacity 16 -> 64), the device drains first and the old handle stays open for as long as the token names it:
+    the token's rows are the rows an undisturbed call returns, and the handle goes with its last name."""
     from wtracker_amd.controllers import HipYoloController, YoloConfig
     from wtracker_amd.sim import ExperimentConfig, TimingConfig
 
@@ -664,11 +666,18 @@ def test_a_handle_replaced_by_a_larger_one_stays_valid_for_the_call_still_in_fli
     cfg.model = None
     ctrl = HipYoloController(tc, cfg, device_frames=dev)
     token = ctrl.launch_views(ent(15), lane=1)  # throughput-plan handle of 16 frames
-    small = token["det"]
+    small = token.det
     got40 = ctrl.predict_views(ent(40))  # same key, larger batch: the 16-frame handle is replaced by one of 64
-    assert ctrl._model.detector((128, 128), 15) is not small and small in ctrl._model._retired
-    np.testing.assert_array_equal(ctrl.collect_views(token), want15)
+    assert ctrl._model.detector((128, 128), 15) is not small and small not in ctrl._model._dets.values()
+    assert small._h  # the model let go of it, the token did not: still open
+    got15 = ctrl.collect_views(token)
+    assert small._h  # ... until collect_views has returned the rows
+    np.testing.assert_array_equal(got15, want15)
     np.testing.assert_array_equal(got40[:15], want15)  # (batch invariance across the two handles of one plan: same kernels, same K order)
+    gone = weakref.ref(small)
+    del token, small
+    gc.collect()
+    assert gone() is None and not ctrl._inflight  # nothing else kept the replaced handle: it was closed with its last name (HipYolo.__del__)
 
 
 def test_converted_unfused_checkpoint_runs_on_device(hip_lib, tmp_path):

@@ -149,3 +149,112 @@ def test_hard_fixture_has_the_properties_it_exists_for(golden_dir):
             gone = plt[g.L :: g.L] - plt[: -g.L : g.L]
             assert (gone[:, 0] != mv[: len(gone), 1]).any() and (gone[:, 1] != mv[: len(gone), 2]).any()  # the clamp binds on both axes
         assert ties > 0  # exact .5 ties: round-half-to-even decides
+
+
+# ------------------------------------------------------------------------------------------------- the Python layer's shared rules (no GPU)
+# (num_frames, (imaging, pred, moving) ms at 60 frames/s, hand-counted (n_cycles, n_log) or None)
+GEOMETRY_CASES = [(7, (100, 40, 50), (1, 0)),      # I, M, P = 6, 3, 3: the decision frame 6 exists, no cycle ends: nothing is logged
+                  (10, (100, 40, 50), (1, 1)),     # one logged cycle
+                  (16, (100, 40, 50), (2, 1)),     # a second decision (frame 15) in a cycle that never ends
+                  (200, (100, 40, 50), (22, 22)),
+                  (10, (100, 0, 50), (1, 1)), (200, (100, 0, 50), None),     # P = 0
+                  (4, (50, 40, 100), (1, 0)), (200, (50, 40, 100), None),    # I, M, P = 3, 6, 3
+                  (13, (200, 200, 16), (1, 0)), (14, (200, 200, 16), (1, 1)), (200, (200, 200, 16), None)]  # I, M, P = 12, 1, 12
+
+
+@pytest.mark.parametrize("num_frames,timing,counts", GEOMETRY_CASES)
+def test_loop_geometry_equals_the_restatements(num_frames, timing, counts):
+    from wtracker_amd.replay import LoopGeometry
+
+    ec = ExperimentConfig(**{**EXP0, "num_frames": num_frames})
+    tc = TimingConfig(ec, *timing, (4, 4), (0.32, 0.32))
+    for frame_shape in (None, (300, 500)):
+        g, ref = LoopGeometry.of(tc, ec, frame_shape), rr.Geometry.of(tc, ec, frame_shape)
+        assert (g.L, g.I, g.M, g.P, g.n_cycles, g.n_log, g.n_rows) == (ref.L, ref.I, ref.M, ref.P, ref.n_cycles, ref.n_log, ref.n_log * ref.L)
+        assert counts is None or (g.n_cycles, g.n_log) == counts
+        assert (g.cam, g.mic, g.frame_shape) == (ref.cam, ref.mic, ref.frame_wh[::-1])
+        assert g.decision_frames.tolist() == [c * ref.L + ref.I for c in range(ref.n_cycles)]
+        want = dict(num_frames=ref.num_frames, imaging_frame_num=ref.I, moving_frame_num=ref.M, pred_frame_num=ref.P, cam_w=ref.cam[0], cam_h=ref.cam[1],
+                    mic_w=ref.mic[0], mic_h=ref.mic[1], frame_w=ref.frame_wh[0], frame_h=ref.frame_wh[1], init_x=ref.init[0], init_y=ref.init[1])
+        assert {name: getattr(g.config, name) for name, _ in g.config._fields_} == want
+        with pytest.raises(AttributeError):  # (dataclasses.FrozenInstanceError is one)
+            g.L = 1
+
+
+def test_loop_geometry_refusals():
+    from wtracker_amd.replay import LoopGeometry
+
+    ec = ExperimentConfig(**EXP0)
+    of = lambda *timing, cam=(4, 4), mic=(0.32, 0.32), ec=ec: LoopGeometry.of(TimingConfig(ec, *timing, cam, mic), ec)  # noqa: E731
+    of(100, 40, 50)
+    with pytest.raises(ValueError, match="moving_frame_num"):
+        of(100, 40, 0)
+    with pytest.raises(ValueError, match="imaging_frame_num"):
+        of(0, 0, 50)
+    with pytest.raises(ValueError, match="decision frame"):
+        of(100, 40, 50, ec=ExperimentConfig(**{**EXP0, "num_frames": 6}))
+    with pytest.raises(ValueError, match="pred_frame_num"):
+        of(100, 140, 50)
+    with pytest.raises(ValueError, match="smaller than the microscope"):
+        of(100, 40, 50, cam=(0.2, 4))
+    with pytest.raises(ValueError, match="smaller than the microscope"):
+        of(100, 40, 50, cam=(4, 0.2))
+
+
+@pytest.mark.parametrize("M", [1, 2, 9])
+def test_sine_shares_are_the_restatements(M):
+    from wtracker_amd.replay import sine_shares
+
+    assert np.array_equal(sine_shares(M), rr.share_table(M)) and sine_shares(M).dtype == np.float64
+
+
+def test_call_params_reads_pred_kwargs_once_and_refuses_max_det():
+    from wtracker_amd.controllers import YoloConfig
+
+    assert YoloConfig("m.wtk").call_params() == (384, 0.1, 0.7)  # the dataclass's own pred_kwargs
+    assert YoloConfig("m.wtk", pred_kwargs={}).call_params() == (640, 0.25, 0.7)  # the reference's (ultralytics') defaults
+    got = YoloConfig("m.wtk", pred_kwargs={"imgsz": 128.0, "conf": 1, "iou": 0.5, "half": False}).call_params()
+    assert got == (128, 1.0, 0.5) and [type(v) for v in got] == [int, float, float]
+    with pytest.raises(TypeError, match="max_det"):
+        YoloConfig("m.wtk", pred_kwargs={"imgsz": 128, "max_det": 3}).call_params()
+
+
+class _Frames:
+    """A stand-in with a tensor's attributes: `check_device_frames` must refuse on each of them, and no GPU is needed to say so."""
+
+    def __init__(self, shape, is_cuda=True, dtype="torch.uint8", contiguous=True):
+        self.shape, self.is_cuda, self.dtype, self._contiguous = shape, is_cuda, dtype, contiguous
+
+    def dim(self):
+        return len(self.shape)
+
+    def is_contiguous(self):
+        return self._contiguous
+
+
+def test_check_device_frames_refuses_what_the_library_cannot_read():
+    import torch
+
+    from wtracker_amd import hip
+    from wtracker_amd.controllers import check_device_frames
+
+    check_device_frames(_Frames((5, 8, 9)))
+    check_device_frames(_Frames((5, 8, 9, 3)))
+    bad = [torch.zeros((5, 8, 9), dtype=torch.uint8), np.zeros((5, 8, 9), np.uint8), _Frames((5, 8, 9), is_cuda=False),  # on the host
+           torch.zeros((5, 8, 9), dtype=torch.float32), _Frames((5, 8, 9), dtype="torch.float32"),                        # not uint8
+           _Frames((5, 8, 9, 4)), _Frames((5, 8, 9, 1)), _Frames((8, 9)), _Frames((5, 8, 9, 3, 1)),                        # [F,H,W,4] and other layouts
+           _Frames((5, 8, 9), contiguous=False)]
+    for fr in bad:
+        with pytest.raises(hip.WtkError, match="device_frames"):
+            check_device_frames(fr)
+
+
+def test_nan_rows_keeps_float32_unless_a_frame_has_no_detection():
+    from wtracker_amd.controllers import nan_rows
+
+    xywh = np.arange(12, dtype=np.float32).reshape(3, 4)
+    found = nan_rows(xywh, np.array([5, 0, 7], dtype=np.int32))
+    assert found is xywh and found.dtype == np.float32
+    got = nan_rows(xywh, np.array([5, -1, 7], dtype=np.int32))
+    assert got.dtype == np.float64 and np.isnan(got[1]).all() and np.array_equal(got[[0, 2]], xywh[[0, 2]].astype(np.float64))
+    assert np.array_equal(xywh, np.arange(12, dtype=np.float32).reshape(3, 4))  # the input is left alone

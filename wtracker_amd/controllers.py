@@ -184,22 +184,23 @@ class _DeviceTrackMixin:
     ALL cycles of the experiment in one launch (libwtk_hip.so, track_ops.hip).  The predictors' targets do not depend on the
     platform position — only the final `round(target - camera centre)` does, and that stays on the host in float64."""
 
-    def _upload_track(self, device: int):
+    def _evaluate_cycles(self, device: int, launch) -> None:
+        """`launch(track, cycles, n_cycles, pred, valid, stream)` enqueues the predictor of every cycle; the host keeps the targets it wrote."""
         import torch
 
-        self._dev = torch.device("cuda", device)
-        self._track_dev = torch.from_numpy(np.ascontiguousarray(self.track, dtype=np.float64)).to(self._dev)
-        n_cycles = self.n_frames // self.timing_config.cycle_frame_num + 2
-        self._cycles_dev = torch.arange(n_cycles, dtype=torch.int32, device=self._dev)
-        self._pred_dev = torch.zeros((n_cycles, 2), dtype=torch.float64, device=self._dev)
-        self._valid_dev = torch.zeros((n_cycles,), dtype=torch.int32, device=self._dev)
-        return n_cycles
+        dev = torch.device("cuda", device)
+        track = torch.from_numpy(np.ascontiguousarray(self.track, dtype=np.float64)).to(dev)
+        n = self.n_frames // self.timing_config.cycle_frame_num + 2
+        pred, valid = torch.zeros((n, 2), dtype=torch.float64, device=dev), torch.zeros((n,), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            launch(track, torch.arange(n, dtype=torch.int32, device=dev), n, pred, valid, torch.cuda.current_stream(dev).cuda_stream)
+        torch.cuda.synchronize(dev)
+        self._targets, self._has_target = pred.cpu().numpy(), valid.cpu().numpy().astype(bool)
 
-    def _download(self):
-        import torch
-
-        torch.cuda.synchronize(self._dev)
-        return self._pred_dev.cpu().numpy(), self._valid_dev.cpu().numpy().astype(bool)
+    def _target(self, sim):
+        """The current cycle's target (x, y); None when the cycle has none."""
+        c = sim.cycle_number
+        return self._targets[c] if c < len(self._targets) and self._has_target[c] else None
 
 
 class HipOptimalController(_DeviceTrackMixin, CsvController):
@@ -208,22 +209,15 @@ class HipOptimalController(_DeviceTrackMixin, CsvController):
 
     def __init__(self, timing_config: TimingConfig, csv_path: str, device: int = 0):
         CsvController.__init__(self, timing_config, csv_path)
-        import torch
-
-        n = self._upload_track(device)
-        with torch.cuda.device(self._dev):
-            hip.track_median_centers(self._track_dev, self.n_frames, self._cycles_dev, n, timing_config.cycle_frame_num,
-                                     timing_config.imaging_frame_num, self._pred_dev, self._valid_dev,
-                                     stream=torch.cuda.current_stream(self._dev).cuda_stream)
-        self._targets, self._has_target = self._download()
+        self._evaluate_cycles(device, lambda track, cycles, n, pred, valid, stream: hip.track_median_centers(
+            track, self.n_frames, cycles, n, timing_config.cycle_frame_num, timing_config.imaging_frame_num, pred, valid, stream=stream))
 
     def provide_movement_vector(self, sim) -> tuple:
-        c = sim.cycle_number
-        if c >= len(self._targets) or not self._has_target[c]:
+        target = self._target(sim)
+        if target is None:
             return 0, 0
-        x_next, y_next = self._targets[c]
         cx, cy, cw, ch = sim.view.camera_position
-        return round(x_next - (cx + cw / 2)), round(y_next - (cy + ch / 2))
+        return round(target[0] - (cx + cw / 2)), round(target[1] - (cy + ch / 2))
 
 
 class HipPolyfitController(_DeviceTrackMixin, CsvController):
@@ -234,25 +228,18 @@ class HipPolyfitController(_DeviceTrackMixin, CsvController):
 
     def __init__(self, timing_config: TimingConfig, polyfit_config: PolyfitConfig, csv_path: str, device: int = 0):
         CsvController.__init__(self, timing_config, csv_path)
-        import torch
-
-        self.polyfit_config = polyfit_config
-        n = self._upload_track(device)
-        t_eval = timing_config.cycle_frame_num + timing_config.imaging_frame_num // 2
-        with torch.cuda.device(self._dev):
-            hip.track_polyfit(self._track_dev, self.n_frames, self._cycles_dev, n, timing_config.cycle_frame_num,
-                              polyfit_config.sample_times, polyfit_config.weights, polyfit_config.degree, t_eval, self._pred_dev,
-                              self._valid_dev, stream=torch.cuda.current_stream(self._dev).cuda_stream)
-        self._targets, self._has_target = self._download()
+        self.polyfit_config, tc, pc = polyfit_config, timing_config, polyfit_config
+        self._evaluate_cycles(device, lambda track, cycles, n, pred, valid, stream: hip.track_polyfit(
+            track, self.n_frames, cycles, n, tc.cycle_frame_num, pc.sample_times, pc.weights, pc.degree, tc.cycle_frame_num + tc.imaging_frame_num // 2,
+            pred, valid, stream=stream))
 
     def provide_movement_vector(self, sim) -> tuple:
-        c = sim.cycle_number
-        if c >= len(self._targets) or not self._has_target[c]:
+        target = self._target(sim)
+        if target is None:
             return 0, 0
-        x_pred, y_pred = self._targets[c]
-        cx, cy, cw, ch = sim.view.camera_position
+        cx, cy = sim.view.camera_position[:2]
         # reference: (x_pred - cam_x) - cam_w / 2 on camera-relative fits
-        return round((x_pred - cx) - sim.view.camera_size[0] / 2), round((y_pred - cy) - sim.view.camera_size[1] / 2)
+        return round((target[0] - cx) - sim.view.camera_size[0] / 2), round((target[1] - cy) - sim.view.camera_size[1] / 2)
 
 
 class HipMLPController(CsvController):
@@ -340,10 +327,64 @@ class YoloConfig:
             return self.recheck_dtype
         return "f16x3" if yolo_spec.split_capable(self.scale, nc) else "fp32"
 
+    def call_params(self) -> tuple:
+        """(imgsz, conf, iou) of a detector call, the reference's defaults; naming `max_det` is the TypeError its `predict(max_det=1, **kw)` raises."""
+        kw = self.pred_kwargs
+        if "max_det" in kw:
+            raise TypeError("predict() got multiple values for keyword argument 'max_det'")
+        return int(kw.get("imgsz", 640)), float(kw.get("conf", 0.25)), float(kw.get("iou", 0.7))
+
     def load_model(self) -> "_YoloModel":
         if self.model is None:
             self.model = _YoloModel(self)
         return self.model
+
+
+def check_device_frames(fr) -> None:
+    """The full frames of the device-resident path (HipYoloController, replay.YoloReplay): what wtk_yolo_predict_views reads in place."""
+    if (not getattr(fr, "is_cuda", False) or str(fr.dtype) != "torch.uint8" or fr.dim() not in (3, 4) or (fr.dim() == 4 and fr.shape[3] != 3)
+            or not fr.is_contiguous()):
+        raise hip.WtkError("device_frames must be a contiguous CUDA uint8 tensor [F,H,W] or [F,H,W,3]")
+
+
+def nan_rows(xywh: np.ndarray, anchor: np.ndarray) -> np.ndarray:
+    """Rows without a detection (anchor < 0) become NaN; float64 if there is one (np.stack of float32 and float64 rows, yolo_controller.py:85-90)."""
+    if (anchor < 0).any():
+        out = xywh.astype(np.float64)
+        out[anchor < 0] = np.nan
+        return out
+    return xywh
+
+
+@dataclass(slots=True)
+class _ViewBuffers:
+    """Buffers of one (lane, batch size n), kept for the controller's life: the view table `meta` (int32 [3 n]: frame numbers, then positions) and its
+    pinned source `host` / `host_np`; the rows `out`, `cf`, `an`; `out_h`, `an_h`: they come back through pinned memory with ONE synchronisation."""
+
+    meta: Any
+    host: Any
+    host_np: Any
+    out: Any
+    cf: Any
+    an: Any
+    out_h: Any
+    an_h: Any
+
+
+@dataclass(slots=True, eq=False)
+class _ViewToken:
+    """What launch_views hands to collect_views.  It names its detector handle: a handle the model has replaced lives until its last token is gone."""
+
+    lane: int
+    stream: Any
+    det: hip.HipYolo
+    bufs: _ViewBuffers
+    n: int
+    view: tuple
+    net_hw: tuple
+    conf: float
+    iou: float
+    flags: Optional[int] = None  # the handle's status word, where another lane had to read it before this call was collected
 
 
 def _raise_on_overflow(det: hip.HipYolo, flags: Optional[int] = None) -> None:
@@ -365,18 +406,22 @@ class _YoloModel:
         self.cfg = cfg
         self.weights, self.nc = yolo_spec.load_weights(cfg.model_path)
         self._dets: dict = {}
-        self._retired: list = []
 
     LATENCY_MAX_BATCH = 4  # measured cross-over between the plans near B = 6 at imgsz 384 (profiles/r05_notes.md)
 
     def _retire(self, det: hip.HipYolo) -> None:
-        """A handle that is replaced by a larger one: a call launched on it (HipYoloController.launch_views, lane 1) may still be running and its token
-        still names the handle — the device drains before the handle goes, and the handle stays readable (status) until its tokens are collected."""
+        """A handle that is replaced by a larger one: a call launched on it (launch_views, lane 1) may still be running, so the device drains before the
+        model lets go of it.  It lives on while a token (collect_views reads its status word) or a YoloReplay names it; HipYolo.__del__ closes it."""
         import torch
 
         if torch.cuda.is_available():
             torch.cuda.synchronize(self.cfg.device_index())
-        self._retired.append(det)  # closed when the model goes: collect_views may still ask it for its status word
+
+    def close(self) -> None:
+        """Close every handle the model holds."""
+        for det in self._dets.values():
+            det.close()
+        self._dets.clear()
 
     def detector(self, net_hw: tuple, batch: int, dtype: Optional[str] = None) -> hip.HipYolo:
         dtype = dtype or self.cfg.dtype
@@ -425,10 +470,7 @@ class HipYoloController(SimController):
         self._view_bufs: dict = {}
         self._inflight: dict = {}  # id(detector handle) -> token of the call that may still run on it
         if device_frames is not None:
-            if not getattr(device_frames, "is_cuda", False) or str(device_frames.dtype) != "torch.uint8" or device_frames.dim() not in (3, 4):
-                raise hip.WtkError("device_frames must be a CUDA uint8 tensor [F,H,W] or [F,H,W,3]")
-            if not device_frames.is_contiguous():
-                raise hip.WtkError("device_frames must be contiguous")
+            check_device_frames(device_frames)
 
     def on_sim_start(self, sim):
         self._camera_frames.clear()
@@ -450,14 +492,8 @@ class HipYoloController(SimController):
         batch = np.stack([np.asarray(f) for f in frames], axis=0)
         if batch.dtype != np.uint8:
             raise hip.WtkError("frames must be uint8")
-        kw = dict(self.yolo_config.pred_kwargs)
-        imgsz = int(kw.pop("imgsz", 640))
-        conf = float(kw.pop("conf", 0.25))
-        iou = float(kw.pop("iou", 0.7))
-        if "max_det" in kw:
-            raise TypeError("predict() got multiple values for keyword argument 'max_det'")  # as the reference would
-        H, W = batch.shape[1], batch.shape[2]
-        net_hw = yolo_spec.letterbox_shape(H, W, imgsz)
+        imgsz, conf, iou = self.yolo_config.call_params()
+        net_hw = yolo_spec.letterbox_shape(batch.shape[1], batch.shape[2], imgsz)
         det = self._model.detector(net_hw, batch.shape[0])
         xywh, _, anchor = det.predict_host(batch, conf=conf, iou=iou, max_det=1)
         _raise_on_overflow(det)
@@ -469,18 +505,14 @@ class HipYoloController(SimController):
                     batch[weak], conf=conf, iou=iou, max_det=1)
                 xywh[weak], anchor[weak] = x32, a32
                 self.last_rechecked = len(weak)
-        if (anchor < 0).any():
-            out = xywh.astype(np.float64)
-            out[anchor < 0] = np.nan
-            return out
-        return xywh
+        return nan_rows(xywh, anchor)
 
     def predict_views(self, entries) -> np.ndarray:
         """`entries`: (frame number, position x, position y, (view_w, view_h)) tuples recorded by on_camera_frame.  Same return
         convention as predict(): [N,4] xywh in VIEW pixels, NaN rows for frames without a detection."""
         return self.collect_views(self.launch_views(entries))
 
-    def launch_views(self, entries, lane: int = 0) -> dict:
+    def launch_views(self, entries, lane: int = 0) -> _ViewToken:
         """First half of predict_views: enqueue the view cut + letterbox + detector for `entries` on the controller's stream of `lane` and return a
         token for collect_views().  Nothing is waited for.  Lane 1 is what the deferred track log uses for the cycle batch: it runs beside the next
         cycle's single-frame call (lane 0) instead of in front of it.  Tokens of one lane must be collected before that lane launches again."""
@@ -488,17 +520,12 @@ class HipYoloController(SimController):
 
         assert len(entries) > 0
         fr = self._device_frames
-        kw = dict(self.yolo_config.pred_kwargs)
-        imgsz, conf, iou = int(kw.pop("imgsz", 640)), float(kw.pop("conf", 0.25)), float(kw.pop("iou", 0.7))
-        if "max_det" in kw:
-            raise TypeError("predict() got multiple values for keyword argument 'max_det'")
+        imgsz, conf, iou = self.yolo_config.call_params()
         vw, vh = entries[0][3]
         n = len(entries)
         net_hw = yolo_spec.letterbox_shape(vw, vh, imgsz)  # the view's shape is (rows = w, cols = h)
         det = self._model.detector(net_hw, n)
         dev = fr.device
-        # One set of device buffers per (lane, batch size), kept for the controller's life: the view table (frame numbers + positions, one small upload
-        # per call from pinned memory) and the output rows.  Each lane's calls run on a stream of the controller's own.
         stream = self._view_streams.get(lane)
         if stream is None:
             # (a high-priority stream for lane 0 — the call the loop waits for — changes nothing once the handles run on one stream each: deferred log 11.19 k
@@ -507,11 +534,11 @@ class HipYoloController(SimController):
         # A detector handle has ONE set of activation buffers: a call on another lane that still runs on the same handle (plan "latency" / "throughput":
         # both calls of a cycle share a handle) is waited for first; with plan "auto" the two calls have a handle each and overlap.
         busy = self._inflight.get(id(det))
-        if busy is not None and busy["lane"] != lane:
-            busy["stream"].synchronize()
+        if busy is not None and busy.lane != lane:
+            busy.stream.synchronize()
             # the handle's sticky status word now holds THAT call's flags: they go into its token before this call can raise its own (a flag is
             # reported by the call that caused it, whichever lane collects first)
-            busy["flags"] = det.status(clear=True)
+            busy.flags = det.status(clear=True)
         # EVERY call is ordered behind the caller's current stream: a caller that refills or extends `device_frames` in place between cycles has its
         # writes on that stream, and the crop / letterbox kernel must not read frames that are still being written.  The order costs an event record +
         # wait (~90 us of host time in front of the first launch when the current stream is the legacy default stream: cProfile, round 6) only when
@@ -521,61 +548,51 @@ class HipYoloController(SimController):
             stream.wait_stream(cur)
         bufs = self._view_bufs.get((lane, n))
         if bufs is None:
-            bufs = self._view_bufs[(lane, n)] = dict(meta=torch.empty((3 * n,), dtype=torch.int32, device=dev), host=torch.empty((3 * n,), dtype=torch.int32).pin_memory(),
-                                                     out=torch.empty((n, 4), dtype=torch.float32, device=dev), cf=torch.empty((n,), dtype=torch.float32, device=dev),
-                                                     an=torch.empty((n,), dtype=torch.int32, device=dev),
-                                                     # the rows come back through pinned memory: two asynchronous copies behind the forward pass on the same stream and
-                                                     # ONE synchronisation (two blocking `.cpu()` calls cost ~40 us of a 0.5 ms call)
-                                                     out_h=torch.empty((n, 4), dtype=torch.float32).pin_memory(), an_h=torch.empty((n,), dtype=torch.int32).pin_memory())
-            bufs["host_np"] = bufs["host"].numpy()
-        hn = bufs["host_np"]
-        hn[:n] = [e[0] for e in entries]
-        hn[n:] = [v for e in entries for v in (e[1], e[2])]
-        host = bufs["host"]
-        meta, out, cf, an = bufs["meta"], bufs["out"], bufs["cf"], bufs["an"]
+            host = torch.empty((3 * n,), dtype=torch.int32).pin_memory()
+            bufs = self._view_bufs[(lane, n)] = _ViewBuffers(
+                meta=torch.empty((3 * n,), dtype=torch.int32, device=dev), host=host, host_np=host.numpy(), out=torch.empty((n, 4), dtype=torch.float32, device=dev),
+                cf=torch.empty((n,), dtype=torch.float32, device=dev), an=torch.empty((n,), dtype=torch.int32, device=dev),
+                out_h=torch.empty((n, 4), dtype=torch.float32).pin_memory(), an_h=torch.empty((n,), dtype=torch.int32).pin_memory())
+        bufs.host_np[:n] = [e[0] for e in entries]
+        bufs.host_np[n:] = [v for e in entries for v in (e[1], e[2])]
+        meta, out, cf, an = bufs.meta, bufs.out, bufs.cf, bufs.an
         idx, pos = meta[:n], meta[n:].view(n, 2)
         C = fr.shape[3] if fr.dim() == 4 else 1
         with torch.cuda.device(dev), torch.cuda.stream(stream):
-            meta.copy_(host, non_blocking=True)
+            meta.copy_(bufs.host, non_blocking=True)
             det.predict_views(fr, fr.shape[0], fr.shape[1], fr.shape[2], C, idx, pos, n, vw, vh, out, cf, an, conf=conf, iou=iou, max_det=1, stream=stream.cuda_stream)
-            bufs["out_h"].copy_(out, non_blocking=True)
-            bufs["an_h"].copy_(an, non_blocking=True)
-        token = dict(lane=lane, stream=stream, det=det, bufs=bufs, n=n, view=(vw, vh), net_hw=net_hw, conf=conf, iou=iou, C=C)
+            bufs.out_h.copy_(out, non_blocking=True)
+            bufs.an_h.copy_(an, non_blocking=True)
+        token = _ViewToken(lane, stream, det, bufs, n, (vw, vh), net_hw, conf, iou)
         self._inflight[id(det)] = token
         return token
 
-    def collect_views(self, token: dict) -> np.ndarray:
+    def collect_views(self, token: _ViewToken) -> np.ndarray:
         """Second half of predict_views: wait for the token's call and return its rows."""
         import torch
 
-        stream, det, bufs, n = token["stream"], token["det"], token["bufs"], token["n"]
+        stream, det, bufs, n = token.stream, token.det, token.bufs, token.n
         fr = self._device_frames
-        dev = fr.device
         stream.synchronize()
         if self._inflight.get(id(det)) is token:
             del self._inflight[id(det)]
-        xywh, anchor = bufs["out_h"].numpy().copy(), bufs["an_h"].numpy().copy()
-        _raise_on_overflow(det, token.get("flags"))
+        xywh, anchor = bufs.out_h.numpy().copy(), bufs.an_h.numpy().copy()
+        _raise_on_overflow(det, token.flags)
         self.last_rechecked = 0
         if self.yolo_config.recheck_margin > 0 and det.dtype in ("fp16", "f16", "float16"):
             weak = np.nonzero(det.last_margins(n) < self.yolo_config.recheck_margin)[0]
             if len(weak):
-                vw, vh = token["view"]
-                out, cf, an = bufs["out"], bufs["cf"], bufs["an"]
-                idx, pos = bufs["meta"][:n], bufs["meta"][n:].view(n, 2)
-                wsel = torch.from_numpy(weak).to(dev)
-                det32 = self._model.detector(token["net_hw"], len(weak), dtype=self.yolo_config.recheck_mode(self._model.nc))
+                out, cf, an = bufs.out, bufs.cf, bufs.an
+                idx, pos = bufs.meta[:n], bufs.meta[n:].view(n, 2)
+                wsel = torch.from_numpy(weak).to(fr.device)
+                det32 = self._model.detector(token.net_hw, len(weak), dtype=self.yolo_config.recheck_mode(self._model.nc))
                 k = len(weak)
-                with torch.cuda.device(dev), torch.cuda.stream(stream):
-                    det32.predict_views(fr, fr.shape[0], fr.shape[1], fr.shape[2], token["C"], idx[wsel].contiguous(), pos[wsel].contiguous(), k, vw, vh,
-                                        out[:k], cf[:k], an[:k], conf=token["conf"], iou=token["iou"], max_det=1, stream=stream.cuda_stream)
+                with torch.cuda.device(fr.device), torch.cuda.stream(stream):
+                    det32.predict_views(fr, fr.shape[0], fr.shape[1], fr.shape[2], fr.shape[3] if fr.dim() == 4 else 1, idx[wsel].contiguous(), pos[wsel].contiguous(), k, *token.view,
+                                        out[:k], cf[:k], an[:k], conf=token.conf, iou=token.iou, max_det=1, stream=stream.cuda_stream)
                     xywh[weak], anchor[weak] = out[:k].cpu().numpy(), an[:k].cpu().numpy()
                 self.last_rechecked = k
-        if (anchor < 0).any():
-            res = xywh.astype(np.float64)
-            res[anchor < 0] = np.nan
-            return res
-        return xywh
+        return nan_rows(xywh, anchor)
 
     def begin_movement_prediction(self, sim) -> None:
         pass

@@ -43,6 +43,35 @@ def _is_cuda(x) -> bool:
     return bool(getattr(x, "is_cuda", False))
 
 
+def _frame_shape(frames) -> tuple:
+    """The shape of one frame of a tensor, an array or a reader (its frame_shape)."""
+    return tuple(frames.frame_shape) if hasattr(frames, "frame_shape") else tuple(np.shape(frames)[1:])
+
+
+def _host_stack(frames, ids, shape: tuple) -> np.ndarray:
+    """The frames `ids` of a host array or reader as one uint8 array [len(ids), *shape]; only those frames are read."""
+    stack = np.empty((len(ids),) + shape, dtype=np.uint8)
+    for k, i in enumerate(ids):
+        f = np.asarray(frames[int(i)])
+        if f.dtype != np.uint8 or f.shape != shape:
+            raise ValueError(f"frame {int(i)} is {f.dtype} {f.shape}, expected uint8 {shape}")
+        stack[k] = f
+    return stack
+
+
+def _device_background(background, H: int, W: int, device=None, channel_axis: bool = False):
+    """`background` as a contiguous uint8 [H, W] tensor on `device` (None: where it is, a host array on the current GPU); channel_axis: [H, W, 1] too."""
+    import torch
+
+    bg = background if _is_cuda(background) else torch.from_numpy(np.ascontiguousarray(background))
+    gray = tuple(bg.shape[:2]) == (H, W) and bg.numel() == H * W if channel_axis else tuple(bg.shape) == (H, W)
+    if bg.dtype != torch.uint8 or not gray:
+        raise ValueError(f"background must be uint8 [{H},{W}] (gray)")
+    if device is None:
+        device = bg.device if bg.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    return bg.reshape(H, W).to(device).contiguous()
+
+
 def background(frames, num_probes: int, sampling: str = "uniform", method: str = "median"):
     """Per-pixel median / mean of `num_probes` sampled frames as a CUDA uint8 tensor of one frame's shape, enqueued on the current torch stream.
     `frames`: a CUDA uint8 tensor [F,H,W] or [F,H,W,3] (the probes are read in place), a host array of that shape, or a reader with __len__,
@@ -55,21 +84,13 @@ def background(frames, num_probes: int, sampling: str = "uniform", method: str =
     ids = probe_indices(length, num_probes, sampling)
     if len(ids) == 0:
         raise ValueError("no frames to sample the background from")
+    shape = _frame_shape(frames)
     if _is_cuda(frames):
         if frames.dtype != torch.uint8 or frames.dim() not in (3, 4) or not frames.is_contiguous():
             raise ValueError("device frames must be a contiguous CUDA uint8 tensor [F,H,W] or [F,H,W,3]")
-        shape = tuple(frames.shape[1:])
-        src, n_frames = frames, length
-        idx = torch.from_numpy(ids.astype(np.int32)).to(frames.device)
+        src, n_frames, idx = frames, length, torch.from_numpy(ids.astype(np.int32)).to(frames.device)
     else:
-        shape = tuple(frames.frame_shape) if hasattr(frames, "frame_shape") else tuple(np.shape(frames)[1:])
-        stack = np.empty((len(ids),) + shape, dtype=np.uint8)
-        for k, i in enumerate(ids):
-            f = np.asarray(frames[int(i)])
-            if f.dtype != np.uint8 or f.shape != shape:
-                raise ValueError(f"frame {int(i)} is {f.dtype} {f.shape}, expected uint8 {shape}")
-            stack[k] = f
-        src, n_frames, idx = torch.from_numpy(stack).cuda(), len(ids), None
+        src, n_frames, idx = torch.from_numpy(_host_stack(frames, ids, shape)).cuda(), len(ids), None
     bg = torch.empty(shape, dtype=torch.uint8, device=src.device)
     with torch.cuda.device(src.device):
         hip.background(src, n_frames, math.prod(shape), idx, len(ids), _METHODS[method], bg, torch.cuda.current_stream().cuda_stream)
@@ -113,8 +134,7 @@ def boxes(frames, background, diff_thresh=20, frame_indices=None, return_area: b
     import torch
 
     thr = _boxes_threshold(diff_thresh)
-    on_device = _is_cuda(frames)
-    shape = tuple(frames.shape[1:]) if on_device else (tuple(frames.frame_shape) if hasattr(frames, "frame_shape") else tuple(np.shape(frames)[1:]))
+    on_device, shape = _is_cuda(frames), _frame_shape(frames)
     if len(shape) == 3:
         raise ValueError("boxes takes gray frames [F,H,W] only: the reference's colour branch goes through cv.cvtColor and is out of scope")
     if len(shape) != 2:
@@ -123,11 +143,8 @@ def boxes(frames, background, diff_thresh=20, frame_indices=None, return_area: b
         raise ValueError("device frames must be a contiguous CUDA uint8 tensor [F,H,W]")
     H, W = (int(v) for v in shape)
     F = len(frames)
-    bg = background if _is_cuda(background) else torch.from_numpy(np.ascontiguousarray(background))
-    if bg.dtype != torch.uint8 or tuple(bg.shape) != (H, W):
-        raise ValueError(f"background must be uint8 [{H},{W}] (gray)")
-    dev = frames.device if on_device else (bg.device if bg.is_cuda else torch.device("cuda", torch.cuda.current_device()))
-    bg = bg.to(dev).contiguous()
+    bg = _device_background(background, H, W, frames.device if on_device else None)
+    dev = bg.device
     idx_dev = idx_host = None
     if frame_indices is None:
         n = F
@@ -159,14 +176,8 @@ def boxes(frames, background, diff_thresh=20, frame_indices=None, return_area: b
                 if on_device:
                     src, n_src, idx = (frames, F, idx_dev[lo:lo + k]) if idx_dev is not None else (frames[lo:lo + k], k, None)
                 else:
-                    stack = np.empty((k, H, W), dtype=np.uint8)
-                    for j in range(k):
-                        i = int(idx_host[lo + j]) if idx_host is not None else lo + j
-                        f = np.asarray(frames[i])
-                        if f.dtype != np.uint8 or f.shape != (H, W):
-                            raise ValueError(f"frame {i} is {f.dtype} {f.shape}, expected uint8 {(H, W)}")
-                        stack[j] = f
-                    src, n_src, idx = torch.from_numpy(stack).to(dev), k, None
+                    ids = range(lo, lo + k) if idx_host is None else idx_host[lo:lo + k]
+                    src, n_src, idx = torch.from_numpy(_host_stack(frames, ids, (H, W))).to(dev), k, None
                 hip.boxes(src, n_src, H, W, bg, idx, k, thr, out[lo:lo + k], None if area is None else area[lo:lo + k],
                           None if mask is None else mask[lo:lo + k], fault_count, scratch, scratch.numel(), stream)
     res = (out,) + ((area,) if return_area else ()) + ((mask,) if return_mask else ())
@@ -179,8 +190,7 @@ class BoxCalculator:
 
     def __init__(self, frames_or_reader, background, diff_thresh: int = 20) -> None:
         assert diff_thresh > 0, "Difference threshold must be greater than 0."
-        fr = frames_or_reader
-        shape = tuple(fr.frame_shape) if hasattr(fr, "frame_shape") else tuple(fr.shape[1:])
+        fr, shape = frames_or_reader, _frame_shape(frames_or_reader)
         assert shape == tuple(background.shape), "Background shape must match frame shape."
         if len(shape) == 3 and shape[2] == 3:
             raise ValueError("BoxCalculator takes gray frames only: the reference's colour branch goes through cv.cvtColor and is out of scope")
@@ -280,11 +290,7 @@ def precise_error(frames, background, worm_xywh, mic_xywh, frame_nums, diff_thre
     frames = frames.reshape(frames.shape[:3]).contiguous()
     F, H, W = (int(s) for s in frames.shape)
     dev = frames.device
-    bg = background if _is_cuda(background) else torch.from_numpy(np.ascontiguousarray(background))
-    bg = bg.to(dev)
-    if bg.dtype != torch.uint8 or tuple(bg.shape[:2]) != (H, W) or bg.numel() != H * W:
-        raise ValueError(f"background must be uint8 [{H},{W}] (gray)")
-    bg = bg.reshape(H, W).contiguous()
+    bg = _device_background(background, H, W, dev, channel_axis=True)
     f32 = all(str(getattr(b, "dtype", "")).endswith("float32") for b in (worm_xywh, mic_xywh))  # float32 boxes keep the reference's float32 x + w
     dtype = torch.float32 if f32 else torch.float64
     worm, mic = _boxes(worm_xywh, dtype, dev), _boxes(mic_xywh, dtype, dev)

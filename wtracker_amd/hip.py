@@ -51,28 +51,86 @@ class _YoloDesc(C.Structure):
                 ("max_channels", C.c_int32), ("n_convs", C.c_int32), ("convs", C.POINTER(_ConvBlob))]
 
 
-# every symbol include/wtk_hip.h declares (tests/test_abi.py checks the header against this list)
-SYMBOLS = [
-    "wtk_last_error", "wtk_abi_version", "wtk_device_count",
-    "wtk_mlp_create", "wtk_mlp_destroy", "wtk_mlp_forward", "wtk_mlp_forward_host", "wtk_mlp_predict_track",
-    "wtk_yolo_conv_count", "wtk_yolo_conv_info", "wtk_yolo_create", "wtk_yolo_create_planned", "wtk_yolo_plan", "wtk_yolo_status", "wtk_yolo_destroy", "wtk_yolo_predict",
-    "wtk_yolo_predict_host", "wtk_yolo_debug_head", "wtk_yolo_decode_host", "wtk_yolo_workload",
-    "wtk_yolo_set_profiling", "wtk_yolo_get_profile", "wtk_yolo_get_kernel_profile", "wtk_crop_views", "wtk_yolo_debug_tensor",
-    "wtk_yolo_predict_views", "wtk_track_median_centers", "wtk_track_polyfit", "wtk_track_training_pairs",
-    "wtk_yolo_predict_nms", "wtk_yolo_decode_nms_host",
-    "wtk_comm_unique_id", "wtk_comm_create", "wtk_comm_destroy", "wtk_allgather_tracks",
-    "wtk_yolo_margin_buffer", "wtk_yolo_last_margins_host",
-    "wtk_recheck_select", "wtk_recheck_merge", "wtk_yolo_set_dynamic_batch", "wtk_yolo_set_side_streams",
-    "wtk_release_cached_memory", "wtk_recheck_select_counted", "wtk_recheck_enqueue", "wtk_recheck_scatter",
-    "wtk_hybrid_create", "wtk_hybrid_destroy", "wtk_hybrid_set_margin", "wtk_hybrid_predict", "wtk_hybrid_predict_views", "wtk_hybrid_flush",
-    "wtk_hybrid_pending", "wtk_hybrid_counters", "wtk_hybrid_config", "wtk_hybrid_hold",
-    "wtk_background", "wtk_precise_error",
-    "wtk_polyfit_dataset", "wtk_polyfit_mae_scratch_doubles", "wtk_polyfit_weight_mae", "wtk_polyfit_swarm_step",
-    "wtk_replay_scan", "wtk_replay_scratch_doubles", "wtk_replay_rows",
-    "wtk_replay_polyfit_targets_scratch_doubles", "wtk_replay_polyfit_targets", "wtk_replay_objective",
-    "wtk_replay_yolo_step", "wtk_replay_yolo_positions", "wtk_replay_yolo_track",
-    "wtk_boxes_scratch_bytes", "wtk_boxes",
-]
+_vp, _i32, _i64, _f32, _f64, _size = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_size_t
+_pvp, _pi32, _pi64, _pf32, _pf64, _pcfg = C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_f32), C.POINTER(_f64), C.POINTER(_ReplayConfig)
+
+# The C ABI, one row per symbol of include/wtk_hip.h and in its order: name -> (restype, argtypes).  load() applies it and nothing else declares a
+# signature; tests/test_abi.py compares every row with the header's prototype, kind by kind (pointer, int32, int64, size_t, float, double).
+SIGNATURES = {
+    "wtk_last_error": (C.c_char_p, []),
+    "wtk_abi_version": (_i32, []),
+    "wtk_device_count": (_i32, []),
+    "wtk_mlp_create": (_i32, [_pvp, C.POINTER(_MlpDesc)]),
+    "wtk_mlp_destroy": (None, [_vp]),
+    "wtk_mlp_forward": (_i32, [_vp, _vp, _i32, _vp, _vp]),
+    "wtk_mlp_forward_host": (_i32, [_vp, _vp, _i32, _vp]),
+    "wtk_mlp_predict_track": (_i32, [_vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
+    "wtk_yolo_conv_count": (_i32, [_f32, _f32, _i32, _i32]),
+    "wtk_yolo_conv_info": (_i32, [_f32, _f32, _i32, _i32, _i32, _pi32, _pi32, _pi32, _pi32, _pi32, C.c_char_p, _size]),
+    "wtk_yolo_create": (_i32, [_pvp, C.POINTER(_YoloDesc)]),
+    "wtk_yolo_destroy": (None, [_vp]),
+    "wtk_yolo_create_planned": (_i32, [_pvp, C.POINTER(_YoloDesc), _i32]),
+    "wtk_yolo_plan": (_i32, [_vp]),
+    "wtk_yolo_predict": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _f32, _f32, _i32, _vp, _vp, _vp, _vp]),
+    "wtk_yolo_predict_host": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _f32, _f32, _i32, _vp, _vp, _vp]),
+    "wtk_yolo_debug_head": (_i32, [_vp, _i32, _i32, _vp, _vp]),
+    "wtk_yolo_debug_tensor": (_i32, [_vp, _i32, _i32, _vp, _size, _vp]),
+    "wtk_yolo_decode_host": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp]),
+    "wtk_yolo_status": (_i32, [_vp, _pi32, _i32]),
+    "wtk_yolo_workload": (_i32, [_vp, _pf64, _pi32]),
+    "wtk_yolo_set_profiling": (_i32, [_vp, _i32]),
+    "wtk_yolo_get_profile": (_i32, [_vp, _i32, _pf64, _pi64]),
+    "wtk_yolo_get_kernel_profile": (_i32, [_vp, _i32, _pf64, _pi64, _pf64]),
+    "wtk_crop_views": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp]),
+    "wtk_yolo_margin_buffer": (_i32, [_vp, _pvp]),
+    "wtk_yolo_last_margins_host": (_i32, [_vp, _i32, _vp]),
+    "wtk_yolo_predict_nms": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "wtk_yolo_decode_nms_host": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "wtk_track_median_centers": (_i32, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "wtk_track_polyfit": (_i32, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _f64, _vp, _vp, _vp]),
+    "wtk_track_training_pairs": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "wtk_recheck_select": (_i32, [_vp, _i32, _i32, _f32, _vp, _vp, _vp]),
+    "wtk_recheck_select_counted": (_i32, [_vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp]),
+    "wtk_yolo_set_dynamic_batch": (_i32, [_vp, _vp]),
+    "wtk_yolo_set_side_streams": (_i32, [_vp, _i32]),
+    "wtk_release_cached_memory": (_i32, []),
+    "wtk_recheck_merge": (_i32, [_vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "wtk_recheck_enqueue": (_i32, [_vp, _i32, _f32, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "wtk_recheck_scatter": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "wtk_hybrid_create": (_i32, [_pvp, _vp, _vp, _f32, _i32, _i32]),
+    "wtk_hybrid_destroy": (None, [_vp]),
+    "wtk_hybrid_set_margin": (_i32, [_vp, _f32]),
+    "wtk_hybrid_predict": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp]),
+    "wtk_hybrid_predict_views": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp]),
+    "wtk_hybrid_flush": (_i32, [_vp, _vp]),
+    "wtk_hybrid_pending": (_i32, [_vp]),
+    "wtk_hybrid_counters": (_i32, [_vp, _pi64, _pi64]),
+    "wtk_hybrid_hold": (_i32, [_vp, _i32]),
+    "wtk_hybrid_config": (_i32, [_vp, _pi32, _pi32, _pf32]),
+    "wtk_yolo_predict_views": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _f32, _f32, _i32, _vp, _vp, _vp, _vp]),
+    "wtk_comm_unique_id": (_i32, [_vp, _size]),
+    "wtk_comm_create": (_i32, [_pvp, _i32, _i32, _i32, _vp]),
+    "wtk_comm_destroy": (None, [_vp]),
+    "wtk_allgather_tracks": (_i32, [_vp, _vp, _i32, _vp, _vp]),
+    "wtk_background": (_i32, [_vp, _i32, _i64, _vp, _i32, _i32, _vp, _vp]),
+    "wtk_precise_error": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _f64, _vp, _vp, _vp, _vp]),
+    "wtk_polyfit_dataset": (_i32, [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _f64, _f64, _vp, _vp, _i32, _vp, _vp]),
+    "wtk_polyfit_mae_scratch_doubles": (_i64, [_i32, _i32]),
+    "wtk_polyfit_weight_mae": (_i32, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i64, _vp, _vp]),
+    "wtk_polyfit_swarm_step": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _f64, _f64, _f64, _f64, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "wtk_replay_scan": (_i32, [_pcfg, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "wtk_replay_scratch_doubles": (_i64, [_i32, _i64]),
+    "wtk_replay_rows": (_i32, [_pcfg, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "wtk_replay_polyfit_targets_scratch_doubles": (_i64, [_i32, _i32, _i32, _i32]),
+    "wtk_replay_polyfit_targets": (_i32, [_vp, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _f64, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "wtk_replay_objective": (_i32, [_pcfg, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "wtk_replay_yolo_step": (_i32, [_pcfg, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "wtk_replay_yolo_positions": (_i32, [_pcfg, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "wtk_replay_yolo_track": (_i32, [_pcfg, _i32, _vp, _vp, _vp, _vp]),
+    "wtk_boxes_scratch_bytes": (_i64, [_i32, _i32, _i32]),
+    "wtk_boxes": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+}
+SYMBOLS = list(SIGNATURES)  # every symbol include/wtk_hip.h declares
 
 
 def lib_path() -> str:
@@ -150,91 +208,13 @@ def load() -> C.CDLL:
                        "there is no CPU fallback")
     _preload_torch_hip_runtime()
     lib = C.CDLL(_LIB_PATH)
-    vp, i32, f32 = C.c_void_p, C.c_int32, C.c_float
-    lib.wtk_last_error.restype = C.c_char_p
-    lib.wtk_abi_version.restype = C.c_int
-    lib.wtk_device_count.restype = C.c_int
-    lib.wtk_mlp_create.argtypes = [C.POINTER(vp), C.POINTER(_MlpDesc)]
-    lib.wtk_mlp_destroy.argtypes = [vp]
-    lib.wtk_mlp_destroy.restype = None
-    lib.wtk_mlp_forward.argtypes = [vp, vp, i32, vp, vp]
-    lib.wtk_mlp_forward_host.argtypes = [vp, vp, i32, vp]
-    lib.wtk_mlp_predict_track.argtypes = [vp, vp, i32, vp, i32, vp, i32, vp, vp, vp]
-    lib.wtk_yolo_conv_count.argtypes = [f32, f32, i32, i32]
-    lib.wtk_yolo_conv_info.argtypes = [f32, f32, i32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32),
-                                       C.POINTER(i32), C.POINTER(i32), C.c_char_p, C.c_size_t]
-    lib.wtk_yolo_create.argtypes = [C.POINTER(vp), C.POINTER(_YoloDesc)]
-    lib.wtk_yolo_create_planned.argtypes = [C.POINTER(vp), C.POINTER(_YoloDesc), i32]
-    lib.wtk_yolo_plan.argtypes = [vp]
-    if hasattr(lib, "wtk_yolo_status") or not os.environ.get("WTK_HIP_LIB"):  # (an older build named by WTK_HIP_LIB for an A/B timing may lack it)
-        lib.wtk_yolo_status.argtypes = [vp, C.POINTER(i32), i32]
-    lib.wtk_yolo_destroy.argtypes = [vp]
-    lib.wtk_yolo_destroy.restype = None
-    lib.wtk_yolo_predict.argtypes = [vp, vp, i32, i32, i32, i32, f32, f32, i32, vp, vp, vp, vp]
-    lib.wtk_yolo_predict_host.argtypes = [vp, vp, i32, i32, i32, i32, f32, f32, i32, vp, vp, vp]
-    lib.wtk_yolo_debug_head.argtypes = [vp, i32, i32, vp, vp]
-    lib.wtk_yolo_decode_host.argtypes = [vp, vp, vp, i32, i32, i32, f32, vp, vp, vp]
-    lib.wtk_yolo_workload.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(i32)]
-    lib.wtk_yolo_set_profiling.argtypes = [vp, i32]
-    lib.wtk_yolo_debug_tensor.argtypes = [vp, i32, i32, vp, C.c_size_t, vp]
-    lib.wtk_yolo_get_profile.argtypes = [vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
-    lib.wtk_yolo_get_kernel_profile.argtypes = [vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
-    lib.wtk_crop_views.argtypes = [vp, i32, i32, i32, i32, vp, i32, i32, vp, vp]
-    lib.wtk_track_median_centers.argtypes = [vp, i32, i32, vp, i32, i32, i32, vp, vp, vp]
-    lib.wtk_track_polyfit.argtypes = [vp, i32, i32, vp, i32, i32, vp, vp, i32, i32, C.c_double, vp, vp, vp]
-    lib.wtk_track_training_pairs.argtypes = [vp, i32, i32, i32, i32, vp, i32, vp, i32, vp, vp, vp, vp]
-    lib.wtk_yolo_predict_nms.argtypes = [vp, vp, i32, i32, i32, i32, f32, f32, i32, vp, vp, vp, vp, vp, vp]
-    lib.wtk_yolo_decode_nms_host.argtypes = [vp, vp, vp, i32, i32, i32, f32, f32, i32, vp, vp, vp, vp, vp]
-    lib.wtk_yolo_margin_buffer.argtypes = [vp, C.POINTER(vp)]
-    lib.wtk_yolo_last_margins_host.argtypes = [vp, i32, vp]
-    lib.wtk_recheck_select.argtypes = [vp, i32, i32, f32, vp, vp, vp]
-    lib.wtk_recheck_select_counted.argtypes = [vp, i32, i32, f32, vp, vp, vp, vp]
-    lib.wtk_recheck_enqueue.argtypes = [vp, i32, f32, vp, C.c_int64, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.wtk_recheck_scatter.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.wtk_yolo_set_dynamic_batch.argtypes = [vp, vp]
-    lib.wtk_yolo_set_side_streams.argtypes = [vp, i32]
-    lib.wtk_recheck_merge.argtypes = [vp, vp, i32, i32, f32, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.wtk_comm_unique_id.argtypes = [vp, C.c_size_t]
-    lib.wtk_comm_create.argtypes = [C.POINTER(vp), i32, i32, i32, vp]
-    lib.wtk_comm_destroy.argtypes = [vp]
-    lib.wtk_comm_destroy.restype = None
-    lib.wtk_allgather_tracks.argtypes = [vp, vp, i32, vp, vp]
-    lib.wtk_yolo_predict_views.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, f32, f32, i32, vp, vp, vp, vp]
-    lib.wtk_hybrid_create.argtypes = [C.POINTER(vp), vp, vp, f32, i32, i32]
-    lib.wtk_hybrid_destroy.argtypes = [vp]
-    lib.wtk_hybrid_destroy.restype = None
-    lib.wtk_hybrid_set_margin.argtypes = [vp, f32]
-    lib.wtk_hybrid_predict.argtypes = [vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp]
-    lib.wtk_hybrid_predict_views.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, f32, vp, vp, vp, vp]
-    lib.wtk_hybrid_flush.argtypes = [vp, vp]
-    lib.wtk_hybrid_pending.argtypes = [vp]
-    lib.wtk_hybrid_hold.argtypes = [vp, i32]
-    lib.wtk_hybrid_counters.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    lib.wtk_hybrid_config.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(f32)]
-    lib.wtk_background.argtypes = [vp, i32, C.c_int64, vp, i32, i32, vp, vp]
-    lib.wtk_precise_error.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, vp, i32, C.c_double, vp, vp, vp, vp]
-    f64 = C.c_double
-    lib.wtk_polyfit_dataset.argtypes = [vp, i32, i32, i32, vp, i32, i32, f64, f64, vp, vp, i32, vp, vp]
-    lib.wtk_polyfit_mae_scratch_doubles.argtypes = [i32, i32]
-    lib.wtk_polyfit_mae_scratch_doubles.restype = C.c_int64
-    lib.wtk_polyfit_weight_mae.argtypes = [vp, vp, C.c_int64, i32, vp, i32, i32, i32, vp, i32, vp, vp, C.c_int64, vp, vp]
-    lib.wtk_polyfit_swarm_step.argtypes = [vp, vp, i32, i32, i32, i32, f64, f64, f64, f64, f64, f64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.wtk_replay_scan.argtypes = [C.POINTER(_ReplayConfig), i32, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp]
-    lib.wtk_replay_scratch_doubles.argtypes = [i32, C.c_int64]
-    lib.wtk_replay_scratch_doubles.restype = C.c_int64
-    lib.wtk_replay_rows.argtypes = [C.POINTER(_ReplayConfig), i32, i32, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, C.c_int64, vp]
-    lib.wtk_replay_polyfit_targets_scratch_doubles.argtypes = [i32, i32, i32, i32]
-    lib.wtk_replay_polyfit_targets_scratch_doubles.restype = C.c_int64
-    lib.wtk_replay_polyfit_targets.argtypes = [vp, i32, i32, i32, vp, i32, vp, i32, i32, f64, vp, vp, i32, vp, vp, vp, C.c_int64, vp, vp]
-    lib.wtk_replay_objective.argtypes = [C.POINTER(_ReplayConfig), i32, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int64, i32, vp, vp, vp]
-    if hasattr(lib, "wtk_replay_yolo_step") or not os.environ.get("WTK_HIP_LIB"):  # (an older build named by WTK_HIP_LIB for an A/B timing may lack them)
-        lib.wtk_replay_yolo_step.argtypes = [C.POINTER(_ReplayConfig), i32, i32, vp, vp, vp, vp, vp]
-        lib.wtk_replay_yolo_positions.argtypes = [C.POINTER(_ReplayConfig), i32, vp, vp, vp, vp, vp]
-        lib.wtk_replay_yolo_track.argtypes = [C.POINTER(_ReplayConfig), i32, vp, vp, vp, vp]
-    if hasattr(lib, "wtk_boxes") or not os.environ.get("WTK_HIP_LIB"):
-        lib.wtk_boxes_scratch_bytes.argtypes = [i32, i32, i32]
-        lib.wtk_boxes_scratch_bytes.restype = C.c_int64
-        lib.wtk_boxes.argtypes = [vp, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, C.c_int64, vp]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(lib, name, None)
+        if fn is None:
+            if os.environ.get("WTK_HIP_LIB"):  # (an older build named for an A/B timing may lack the newer entry points)
+                continue
+            raise WtkError(f"{_LIB_PATH} does not export {name}: the library is older than this binding (rebuild it)")
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 

@@ -33,15 +33,20 @@ class SwarmResult:
     degree: int
 
 
+def check_times(times, name: str) -> np.ndarray:
+    """`times` (`name` to its caller): 1-D, 1 .. MAX_TIMES whole frame offsets -> int64, sorted as the reference sorts them (and not the weights)."""
+    t = np.asarray(times)
+    if t.ndim != 1 or t.size == 0:
+        raise ValueError(f"{name} must be a non-empty 1-D sequence of frame offsets")
+    if t.size > MAX_TIMES:
+        raise ValueError(f"at most {MAX_TIMES} {name} (the device solver's limit), got {t.size}")
+    if not np.all(t == np.round(t)):
+        raise ValueError(f"{name} must be whole frame numbers")
+    return np.sort(t.astype(np.int64))
+
+
 def _check_offsets(input_time_offsets, pred_time_offset) -> np.ndarray:
-    off = np.asarray(input_time_offsets)
-    if off.ndim != 1 or off.size == 0:
-        raise ValueError("input_time_offsets must be a non-empty 1-D sequence of frame offsets")
-    if off.size > MAX_TIMES:
-        raise ValueError(f"at most {MAX_TIMES} input time offsets (the device solver's limit), got {off.size}")
-    if not np.all(off == np.round(off)):
-        raise ValueError("input_time_offsets must be whole frame numbers")
-    off = np.sort(off.astype(np.int64))  # the reference sorts the offsets (and not the weights): weight i belongs to the i-th smallest offset
+    off = check_times(input_time_offsets, "input_time_offsets")
     if int(pred_time_offset) != pred_time_offset:
         raise ValueError("pred_time_offset must be a whole frame number")
     if off[-1] > pred_time_offset:
@@ -214,9 +219,6 @@ class WeightEvaluator:
         self.n_series = 2 * kept_total
 
     # ------------------------------------------------------------------ evaluation
-    def _weights_dev(self, weights):
-        return weights_to_device(self, weights, len(self.input_time_offsets), "input time offset")
-
     def _enqueue_mae(self, w_dev, deg: int, mae_dev, scratch, stop_dev=None):
         import torch
 
@@ -228,7 +230,7 @@ class WeightEvaluator:
         import torch
 
         deg = _check_degree(deg)
-        w = self._weights_dev(weights)
+        w = weights_to_device(self, weights, len(self.input_time_offsets), "input time offset")
         P = int(w.shape[0])
         with torch.cuda.device(self._dev):
             mae = torch.empty((P,), dtype=torch.float64, device=self._dev)

@@ -38,8 +38,8 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import hip, yolo_spec
-from .controllers import PolyfitConfig, YoloConfig, _raise_on_overflow, _read_track_csv
-from .polyfit_opt import MAX_TIMES, SwarmResult, _check_degree, check_swarm_args, polyfit_config, swarm_search, weights_to_device
+from .controllers import PolyfitConfig, YoloConfig, _raise_on_overflow, _read_track_csv, check_device_frames
+from .polyfit_opt import SwarmResult, _check_degree, check_swarm_args, check_times, polyfit_config, swarm_search, weights_to_device
 from .resmlp import FoldedResMLP, from_torch_module
 from .sim import LOG_COLUMNS, ExperimentConfig, TimingConfig
 
@@ -59,6 +59,64 @@ def polyfit_classes(track: np.ndarray, cycle_frame_num: int, n_cycles: int, samp
     masks = (finite.astype(np.int64) << np.arange(len(st), dtype=np.int64)[None, :]).sum(axis=1)
     class_mask, cycle_class = np.unique(masks, return_inverse=True)
     return cycle_class.reshape(-1).astype(np.int32), class_mask.astype(np.int32)
+
+
+def sine_shares(M: int) -> np.ndarray:
+    """SineMotorController's profile (the share of a move made in each of the M moving frames), with numpy's cos as the reference computes it."""
+    return np.array([(np.cos((k * np.pi) / M) - np.cos(((k + 1) * np.pi) / M)) / 2 for k in range(M)], dtype=np.float64)
+
+
+@dataclass(frozen=True, eq=False)
+class LoopGeometry:
+    """The closed loop's sizes, derived once from the configs and needing no GPU: cycle length L = I imaging + M moving frames, the decision looks P
+    frames back; n_cycles cycles whose decision frame c L + I exists, n_log logged cycles (the last cycle's end never arrives), n_rows = n_log L rows."""
+
+    L: int
+    I: int
+    M: int
+    P: int
+    cam: tuple          # (w, h), as mic
+    mic: tuple
+    frame_shape: tuple  # (H, W): the platform position is clamped to it
+    n_cycles: int
+    n_log: int
+    n_rows: int
+    decision_frames: np.ndarray  # int64 [n_cycles]
+    config: object      # the wtk_replay_config of all that
+
+    @classmethod
+    def of(cls, timing_config: TimingConfig, experiment_config: ExperimentConfig, frame_shape: Optional[Sequence[int]] = None) -> "LoopGeometry":
+        """`frame_shape` (H, W): default DummyReader's.  Refuses what wtk_replay_scan / wtk_replay_rows refuse about an experiment (they do so again)."""
+        tc, ec = timing_config, experiment_config
+        cam, mic = tuple(int(v) for v in tc.camera_size_px), tuple(int(v) for v in tc.micro_size_px)
+        if frame_shape is None:
+            frame_shape = tuple(a + b for a, b in zip(ec.orig_resolution, (cam[0] // 2 * 2, cam[1] // 2 * 2)))
+        H, W = int(frame_shape[0]), int(frame_shape[1])
+        L, I, M, P, F = int(tc.cycle_frame_num), int(tc.imaging_frame_num), int(tc.moving_frame_num), int(tc.pred_frame_num), int(ec.num_frames)
+        if I < 1 or M < 1 or F - 1 < I:
+            raise ValueError("the experiment needs imaging_frame_num >= 1, moving_frame_num >= 1 and at least one decision frame")
+        if not 0 <= P <= I:
+            raise ValueError(f"pred_frame_num = {P} lies outside [0, imaging_frame_num = {I}]")
+        if cam[0] < mic[0] or cam[1] < mic[1] or min(mic) < 0:
+            raise ValueError(f"the camera {cam} is smaller than the microscope {mic}")
+        n_cycles, n_log = (F - 1 - I) // L + 1, (F - 1) // L
+        return cls(L, I, M, P, cam, mic, (H, W), n_cycles, n_log, n_log * L, np.arange(n_cycles, dtype=np.int64) * L + I,
+                   hip.replay_config(F, I, M, P, cam, mic, (W, H), ec.init_position))
+
+
+def _adopt(owner, g: LoopGeometry) -> None:
+    """Replay's and YoloReplay's public sizes are their geometry's."""
+    owner.geometry, owner._cfg, owner.frame_shape = g, g.config, g.frame_shape
+    owner.L, owner.I, owner.M, owner.P, owner.n_cycles, owner.n_log, owner.n_rows = g.L, g.I, g.M, g.P, g.n_cycles, g.n_log, g.n_rows
+
+
+def _result_of(g: LoopGeometry, pos, move, summary, row_ids, row_data, bbox=None, mse=None, detections=None) -> "ReplayResult":
+    """The ReplayResult of device pos / move [C, E, 2], summary [E, 6], kept rows [len(row_ids), R, 16], per-row errors [E, R] or None; after the wait."""
+    host = lambda t: None if t is None else t.cpu().numpy()  # noqa: E731
+    return ReplayResult(moves=host(move.permute(1, 0, 2).contiguous()), positions=host(pos.permute(1, 0, 2).contiguous()), summary=_summary_of(host(summary)),
+                        decision_frames=g.decision_frames.copy(), row_ids=row_ids,
+                        row_data=host(row_data) if row_ids else np.zeros((0, g.n_rows, hip.REPLAY_ROW_DOUBLES)), bbox_error=host(bbox), mse_error=host(mse),
+                        detections=detections)
 
 
 @dataclass
@@ -160,23 +218,10 @@ class Replay:
             raise ValueError(f"the track must be float64 [n_frames, 4] xywh, got {track.dtype} {tuple(track.shape)}")
         self.track = track.to(self._dev).contiguous()
         self.n_track = int(self.track.shape[0])
-        cam, mic = tuple(int(v) for v in tc.camera_size_px), tuple(int(v) for v in tc.micro_size_px)
-        if frame_shape is None:
-            frame_shape = tuple(a + b for a, b in zip(ec.orig_resolution, (cam[0] // 2 * 2, cam[1] // 2 * 2)))
-        self.frame_shape = (int(frame_shape[0]), int(frame_shape[1]))
-        self.L, self.I, self.M, self.P = int(tc.cycle_frame_num), int(tc.imaging_frame_num), int(tc.moving_frame_num), int(tc.pred_frame_num)
-        F = int(ec.num_frames)
-        if self.I < 1 or self.M < 1 or F - 1 < self.I:
-            raise ValueError("the experiment needs imaging_frame_num >= 1, moving_frame_num >= 1 and at least one decision frame")
-        self.n_cycles = (F - 1 - self.I) // self.L + 1  # cycles whose decision frame c L + I exists
-        self.n_log = (F - 1) // self.L                  # logged cycles: the last cycle's end never arrives
-        self.n_rows = self.n_log * self.L
+        _adopt(self, LoopGeometry.of(tc, ec, frame_shape))
         if self.n_rows > self.n_track:
-            raise ValueError(f"the track has {self.n_track} rows, the log of {F} frames needs {self.n_rows}")
-        self._cfg = hip.replay_config(F, self.I, self.M, self.P, cam, mic, (self.frame_shape[1], self.frame_shape[0]), ec.init_position)
-        # SineMotorController's profile, with numpy's cos as the reference computes it (never on the device)
-        share = np.array([(np.cos((k * np.pi) / self.M) - np.cos(((k + 1) * np.pi) / self.M)) / 2 for k in range(self.M)], dtype=np.float64)
-        self._share = torch.from_numpy(share).to(self._dev)
+            raise ValueError(f"the track has {self.n_track} rows, the log of {int(ec.num_frames)} frames needs {self.n_rows}")
+        self._share = torch.from_numpy(sine_shares(self.M)).to(self._dev)
         self._cycles = torch.arange(self.n_cycles, dtype=torch.int32, device=self._dev)
         self._track_f32 = None
         self._classes = {}  # sorted sample times -> (cycle_class, class_mask) on the device
@@ -188,12 +233,13 @@ class Replay:
 
         return torch.cuda.current_stream(self._dev).cuda_stream
 
-    def _empty(self, E: int, with_b: bool = False):
+    def _empty(self, E: int, with_b: bool = False, pred_dtype=None):
+        """Zeroed targets a, b (or None), valid of E experiments, and one predictor call's outputs pred [C, 2] (float64 unless named), ok [C]."""
         import torch
 
-        a = torch.zeros((self.n_cycles, E, 2), dtype=torch.float64, device=self._dev)
-        b = torch.zeros((self.n_cycles, E, 2), dtype=torch.float64, device=self._dev) if with_b else None
-        return a, b, torch.zeros((self.n_cycles, E), dtype=torch.int32, device=self._dev)
+        zeros = lambda shape, dtype: torch.zeros((self.n_cycles,) + shape, dtype=dtype, device=self._dev)  # noqa: E731
+        return (zeros((E, 2), torch.float64), zeros((E, 2), torch.float64) if with_b else None, zeros((E,), torch.int32),
+                zeros((2,), pred_dtype or torch.float64), zeros((), torch.int32))
 
     def csv(self) -> Targets:
         """CsvController: centre the camera on the head as seen pred_frame_num frames before the decision (one experiment: it has no parameters)."""
@@ -203,8 +249,7 @@ class Replay:
         """OptimalController: the median head centre of the next imaging phase (wtk_track_median_centers)."""
         import torch
 
-        a, _, valid = self._empty(1)
-        pred, ok = torch.zeros((self.n_cycles, 2), dtype=torch.float64, device=self._dev), torch.zeros((self.n_cycles,), dtype=torch.int32, device=self._dev)
+        a, _, valid, pred, ok = self._empty(1)
         with torch.cuda.device(self._dev):
             hip.track_median_centers(self.track, self.n_track, self._cycles, self.n_cycles, self.L, self.I, pred, ok, stream=self._stream())
         a[:, 0], valid[:, 0] = pred, ok
@@ -220,8 +265,7 @@ class Replay:
         if not configs:
             raise ValueError("at least one PolyfitConfig is needed")
         E = len(configs)
-        a, _, valid = self._empty(E)
-        pred, ok = torch.zeros((self.n_cycles, 2), dtype=torch.float64, device=self._dev), torch.zeros((self.n_cycles,), dtype=torch.int32, device=self._dev)
+        a, _, valid, pred, ok = self._empty(E)
         t_eval = self.L + self.I // 2
         with torch.cuda.device(self._dev):
             for e, cfg in enumerate(configs):
@@ -239,13 +283,11 @@ class Replay:
         tc = self.timing_config
         max_dist = max_speed * (tc.px_per_mm / tc.frames_per_sec) * list(folded.pred_frames)[0]
         net = hip.HipMLP(folded.layers, folded.n_blocks, folded.layers_per_block, device=self._dev.index)
-        a, b, valid = self._empty(1, with_b=True)
+        a, b, valid, pred, ok = self._empty(1, with_b=True, pred_dtype=torch.float32)
         with torch.cuda.device(self._dev):
             if self._track_f32 is None:
                 self._track_f32 = self.track.to(torch.float32).contiguous()
             anchors = (self._cycles * self.L + (self.I - self.P)).contiguous()
-            pred = torch.zeros((self.n_cycles, 2), dtype=torch.float32, device=self._dev)
-            ok = torch.zeros((self.n_cycles,), dtype=torch.int32, device=self._dev)
             net.predict_track(self._track_f32, self.n_track, anchors, self.n_cycles, list(folded.input_frames), pred, ok, stream=self._stream())
             bound = float(np.float32(max_dist))
             a[:, 0] = torch.clamp(pred, -bound, bound).to(torch.float64)
@@ -256,12 +298,7 @@ class Replay:
 
     # ------------------------------------------------------------------ populations of weight vectors
     def _sample_times(self, sample_times) -> tuple:
-        st = np.asarray(sample_times)
-        if st.ndim != 1 or not 1 <= st.size <= MAX_TIMES:
-            raise ValueError(f"sample_times must be 1..{MAX_TIMES} frame offsets (the device solver's limit)")
-        if not np.all(st == np.round(st)):
-            raise ValueError("sample_times must be whole frame numbers")
-        return tuple(int(t) for t in np.sort(st.astype(np.int64)))  # the reference sorts the times and not the weights
+        return tuple(int(t) for t in check_times(sample_times, "sample_times"))
 
     def polyfit_class_table(self, sample_times) -> tuple:
         """(cycle_class int32 [n_cycles], class_mask int32 [K]) device tensors for the sorted `sample_times`: derived from the track once (the first
@@ -274,13 +311,20 @@ class Replay:
             self._classes[st] = (torch.from_numpy(cycle_class).to(self._dev), torch.from_numpy(class_mask).to(self._dev))
         return self._classes[st]
 
-    def _weights_dev(self, weights, N: int):
-        return weights_to_device(self, weights, N, "sample time", min_rows=1)
-
     def _enqueue_population(self, w_dev, degree: int, st: tuple, classes, a, valid, scratch, stop_dev=None):
         cycle_class, class_mask = classes
         hip.replay_polyfit_targets(self.track, self.n_track, self.n_cycles, self.L, w_dev, int(w_dev.shape[0]), st, degree, self.L + self.I // 2, cycle_class,
                                    class_mask, int(class_mask.numel()), a, valid, scratch, scratch.numel(), stop_dev, stream=self._stream())
+
+    def _population_buffers(self, P: int, st: tuple, degree: int, alloc) -> tuple:
+        """For a population call: (Targets of P experiments with a / valid from `alloc`, the fit's scratch, the class table of the sample times `st`)."""
+        import torch
+
+        dev, C, classes = self._dev, self.n_cycles, self.polyfit_class_table(st)
+        self._last_times = st
+        n_scratch = hip.replay_polyfit_targets_scratch_doubles(int(classes[1].numel()), P, len(st), degree)
+        return (Targets("polyfit", P, alloc((C, P, 2), dtype=torch.float64, device=dev), None, alloc((C, P), dtype=torch.int32, device=dev)),
+                torch.empty((max(1, n_scratch),), dtype=torch.float64, device=dev), classes)
 
     def polyfit_population(self, weights, degree: int, sample_times) -> Targets:
         """`polyfit([PolyfitConfig(degree, sample_times, w) for w in weights])` in one call and with the same bits: `weights` [P, N] is a device float64
@@ -289,17 +333,11 @@ class Replay:
         import torch
 
         degree, st = _check_degree(degree), self._sample_times(sample_times)
-        w = self._weights_dev(weights, len(st))
-        P = int(w.shape[0])
-        classes = self.polyfit_class_table(st)
-        self._last_times = st
+        w = weights_to_device(self, weights, len(st), "sample time", min_rows=1)
+        tg, scratch, classes = self._population_buffers(int(w.shape[0]), st, degree, torch.empty)
         with torch.cuda.device(self._dev):
-            a = torch.empty((self.n_cycles, P, 2), dtype=torch.float64, device=self._dev)
-            valid = torch.empty((self.n_cycles, P), dtype=torch.int32, device=self._dev)
-            scratch = torch.empty((max(1, hip.replay_polyfit_targets_scratch_doubles(int(classes[1].numel()), P, len(st), degree)),), dtype=torch.float64,
-                                  device=self._dev)
-            self._enqueue_population(w, degree, st, classes, a, valid, scratch)
-        return Targets("polyfit", P, a, None, valid)
+            self._enqueue_population(w, degree, st, classes, tg.a, tg.valid, scratch)
+        return tg
 
     def _objective_kind(self, kind: str) -> int:
         if kind not in OBJECTIVES:
@@ -321,18 +359,23 @@ class Replay:
                              self._share, buf["pos"], buf["move"], buf["summary"], buf["scratch"], buf["scratch"].numel(), kind, out, stop_dev,
                              stream=self._stream())
 
+    def _check_targets(self, targets: Targets) -> int:
+        """E of targets this Replay can scan."""
+        if targets.kind not in KINDS:
+            raise ValueError(f"unknown kind {targets.kind!r}")
+        E = int(targets.E)
+        for t in (targets.a, targets.b, targets.valid):
+            if t is not None and (t.shape[0] != self.n_cycles or t.shape[1] != E or not t.is_contiguous()):
+                raise ValueError("targets must be contiguous [n_cycles, E, ...] tensors of this Replay")
+        return E
+
     def objective(self, targets: Targets, kind: str = "trimmed_bbox_error"):
         """The closed-loop error of every experiment of `targets` as a device float64 [E] tensor, enqueued on the current torch stream (no synchronisation):
         "trimmed_bbox_error" = Summary.trimmed_mean_bbox_error, "bbox_error" = mean_bbox_error, "mse_error" = mean_mse_error, "non_perfect" = non_perfect
         of `run(targets)`, bit for bit (the same sums, the same float64 division; 0 / 0 is NaN)."""
         import torch
 
-        if targets.kind not in KINDS:
-            raise ValueError(f"unknown kind {targets.kind!r}")
-        k, E = self._objective_kind(kind), int(targets.E)
-        for t in (targets.a, targets.b, targets.valid):
-            if t is not None and (t.shape[0] != self.n_cycles or t.shape[1] != E or not t.is_contiguous()):
-                raise ValueError("targets must be contiguous [n_cycles, E, ...] tensors of this Replay")
+        E, k = self._check_targets(targets), self._objective_kind(kind)
         with torch.cuda.device(self._dev):
             out = torch.empty((E,), dtype=torch.float64, device=self._dev)
             self._enqueue_objective(targets, k, self._objective_buffers(E), out)
@@ -363,14 +406,8 @@ class Replay:
                 raise ValueError(f"start must have shape [K, {N}] with K <= pop_size - 1, got {start.shape}")
             if not (np.isfinite(start).all() and (start >= lb).all() and (start <= ub).all()):
                 raise ValueError(f"start must lie inside [{lb}, {ub}]")
-        classes = self.polyfit_class_table(st)  # from the track, before any epoch is enqueued
-        self._last_times = st
-        with torch.cuda.device(self._dev):
-            dev, f64 = self._dev, torch.float64
-            tg = Targets("polyfit", P, torch.zeros((self.n_cycles, P, 2), dtype=f64, device=dev), None,
-                         torch.zeros((self.n_cycles, P), dtype=torch.int32, device=dev))
-            fit_scratch = torch.empty((max(1, hip.replay_polyfit_targets_scratch_doubles(int(classes[1].numel()), P, N, degree)),), dtype=f64, device=dev)
-            buf = self._objective_buffers(P)
+        tg, fit_scratch, classes = self._population_buffers(P, st, degree, torch.zeros)
+        buf = self._objective_buffers(P)
 
         def enqueue_error(pos, value, ctrl):
             self._enqueue_population(pos, degree, st, classes, tg.a, tg.valid, fit_scratch, stop_dev=ctrl)
@@ -390,20 +427,14 @@ class Replay:
         """Replay the E experiments of `targets`.  `rows`: the experiments whose full log rows are kept (16 doubles per row each)."""
         import torch
 
-        if targets.kind not in KINDS:
-            raise ValueError(f"unknown kind {targets.kind!r}")
-        E, C, R = int(targets.E), self.n_cycles, self.n_rows
-        for t in (targets.a, targets.b, targets.valid):
-            if t is not None and (t.shape[0] != C or t.shape[1] != E or not t.is_contiguous()):
-                raise ValueError("targets must be contiguous [n_cycles, E, ...] tensors of this Replay")
+        E, C, R = self._check_targets(targets), self.n_cycles, self.n_rows
         row_ids = sorted({int(e) for e in rows})
         if any(e < 0 or e >= E for e in row_ids):
             raise IndexError(f"rows names an experiment outside [0, {E})")
-        dev, f64, i32 = self._dev, torch.float64, torch.int32
+        dev, f64 = self._dev, torch.float64
         with torch.cuda.device(dev):
-            stream = self._stream()
-            pos = torch.empty((C, E, 2), dtype=i32, device=dev)
-            move = torch.empty((C, E, 2), dtype=i32, device=dev)
+            stream, buf = self._stream(), self._objective_buffers(E)
+            pos, move, summary, scratch = buf["pos"], buf["move"], buf["summary"], buf["scratch"]
             hip.replay_scan(self._cfg, KINDS[targets.kind], E, C, self.track, self.n_track, targets.a, targets.b, targets.valid, self._share, pos, move,
                             stream=stream)
             slot_host = np.full((E,), -1, dtype=np.int32)
@@ -412,20 +443,10 @@ class Replay:
             row_data = torch.empty((len(row_ids), R, hip.REPLAY_ROW_DOUBLES), dtype=f64, device=dev) if row_ids else None
             bbox = torch.empty((E, R), dtype=f64, device=dev) if per_row_errors else None
             mse = torch.empty((E, R), dtype=f64, device=dev) if per_row_errors else None
-            summary = torch.empty((E, hip.REPLAY_SUMMARY_DOUBLES), dtype=f64, device=dev)
-            n_scratch = hip.replay_scratch_doubles(E, R)
-            scratch = torch.empty((max(1, n_scratch),), dtype=f64, device=dev)
             hip.replay_rows(self._cfg, E, C, self.track, self.n_track, self._share, pos, move, slots, len(row_ids), row_data, bbox, mse, summary, scratch,
                             scratch.numel(), stream=stream)
             torch.cuda.current_stream(dev).synchronize()  # the one host synchronisation
-            s = summary.cpu().numpy()
-            res = ReplayResult(
-                moves=move.permute(1, 0, 2).contiguous().cpu().numpy(), positions=pos.permute(1, 0, 2).contiguous().cpu().numpy(),
-                summary=_summary_of(s),
-                decision_frames=np.arange(C, dtype=np.int64) * self.L + self.I, row_ids=row_ids,
-                row_data=row_data.cpu().numpy() if row_ids else np.zeros((0, R, hip.REPLAY_ROW_DOUBLES)),
-                bbox_error=bbox.cpu().numpy() if per_row_errors else None, mse_error=mse.cpu().numpy() if per_row_errors else None)
-        return res
+            return _result_of(self.geometry, pos, move, summary, row_ids, row_data, bbox, mse)
 
 
 def _summary_of(s: np.ndarray) -> Summary:
@@ -461,40 +482,19 @@ class YoloReplay:
         tc, ec, fr = timing_config, experiment_config, device_frames
         if yolo_config.recheck_margin > 0:
             raise ValueError("YoloReplay does not take recheck_margin > 0: the second look reads the first call's margins on the host, once per call")
-        if not getattr(fr, "is_cuda", False) or str(fr.dtype) != "torch.uint8" or fr.dim() not in (3, 4) or (fr.dim() == 4 and fr.shape[3] != 3):
-            raise hip.WtkError("device_frames must be a CUDA uint8 tensor [F,H,W] or [F,H,W,3]")
-        if not fr.is_contiguous():
-            raise hip.WtkError("device_frames must be contiguous")
-        F = int(ec.num_frames)
-        if int(fr.shape[0]) < F:
-            raise ValueError(f"device_frames holds {int(fr.shape[0])} frames, the experiment needs num_frames = {F}")
+        check_device_frames(fr)
+        if int(fr.shape[0]) < int(ec.num_frames):
+            raise ValueError(f"the frame tensor holds {int(fr.shape[0])} frames, the experiment needs num_frames = {int(ec.num_frames)}")
         self.timing_config, self.experiment_config, self.yolo_config = tc, ec, yolo_config
         self._frames, self._dev = fr, fr.device
-        cam, mic = tuple(int(v) for v in tc.camera_size_px), tuple(int(v) for v in tc.micro_size_px)
-        self.L, self.I, self.M, self.P = int(tc.cycle_frame_num), int(tc.imaging_frame_num), int(tc.moving_frame_num), int(tc.pred_frame_num)
-        # what wtk_replay_rows refuses, before anything is enqueued (the entry points refuse it again)
-        if self.I < 1 or self.M < 1 or F - 1 < self.I:
-            raise ValueError("the experiment needs imaging_frame_num >= 1, moving_frame_num >= 1 and at least one decision frame")
-        if not 0 <= self.P <= self.I:
-            raise ValueError(f"pred_frame_num = {self.P} lies outside [0, imaging_frame_num = {self.I}]")
-        if cam[0] < mic[0] or cam[1] < mic[1] or min(mic) < 0:
-            raise ValueError(f"the camera {cam} is smaller than the microscope {mic}")
-        H, W = int(fr.shape[1]), int(fr.shape[2])
-        if max(cam + (H, W)) > 8192:
+        _adopt(self, LoopGeometry.of(tc, ec, fr.shape[1:3]))
+        (H, W), cam, R = self.frame_shape, self.geometry.cam, self.n_rows
+        if max(cam + (H, W)) > 8192:  # (the YOLO entry points' own limit, not the scan's)
             raise ValueError("camera and frame sides up to 8192 pixels (wtk_replay_yolo_track)")
-        self.frame_shape = (H, W)
-        self.n_cycles = (F - 1 - self.I) // self.L + 1
-        self.n_log = (F - 1) // self.L
-        self.n_rows = R = self.n_log * self.L
         self.log_batch = self.L if log_batch is None else int(log_batch)
         if self.log_batch < 1:
             raise ValueError("log_batch must be at least 1")
-        self._cfg = hip.replay_config(F, self.I, self.M, self.P, cam, mic, (W, H), ec.init_position)
-        kw = dict(yolo_config.pred_kwargs)
-        self._imgsz, self._conf, self._iou = int(kw.pop("imgsz", 640)), float(kw.pop("conf", 0.25)), float(kw.pop("iou", 0.7))
-        if "max_det" in kw:
-            raise TypeError("predict() got multiple values for keyword argument 'max_det'")  # as HipYoloController.launch_views
-        self._view = cam
+        self._imgsz, self._conf, self._iou = yolo_config.call_params()
         net_hw = yolo_spec.letterbox_shape(cam[0], cam[1], self._imgsz)  # the view's shape is (rows = w, cols = h)
         model = self._model = yolo_config.load_model()
         # the cycle batch's handle first: where both calls share one handle (plan "latency") and it was too small for L, the model replaces it here
@@ -508,11 +508,10 @@ class YoloReplay:
         C, dev, i32, f32 = self.n_cycles, self._dev, torch.int32, torch.float32
         # the controller's deque holds the cycle's frames 0 .. I at the decision and it reads entry [-pred_frame_num] (entry 0 when that is 0)
         decision = list(range(self.I + 1))[-self.P]
-        share = np.array([(np.cos((k * np.pi) / self.M) - np.cos(((k + 1) * np.pi) / self.M)) / 2 for k in range(self.M)], dtype=np.float64)
         x0, y0 = (int(min(max(int(v), 0), m - 1)) for v, m in zip(ec.init_position, (W, H)))
         with torch.cuda.device(dev):
             self._stream = torch.cuda.Stream(device=dev)
-            self._share = torch.from_numpy(share).to(dev)
+            self._share = torch.from_numpy(sine_shares(self.M)).to(dev)
             self._pos0 = torch.tensor([x0, y0], dtype=i32, device=dev)
             self._decision_idx = (torch.arange(C, dtype=i32, device=dev) * self.L + decision).contiguous()
             self._log_idx = torch.arange(max(R, 1), dtype=i32, device=dev)
@@ -543,25 +542,22 @@ class YoloReplay:
             self._own.close()
             self._own = None
 
-    def _detectors(self) -> list:
-        return [self.step_detector] if self.log_detector is self.step_detector else [self.step_detector, self.log_detector]
-
     def _finish(self):
         self._stream.synchronize()  # the one host synchronisation
-        for det in self._detectors():
+        for det in {self.step_detector, self.log_detector}:  # (one handle where both calls share it)
             _raise_on_overflow(det)
 
+    def _call(self, det, idx, pos, n: int, rows, conf, anchor):
+        fr, (vw, vh) = self._frames, self.geometry.cam
+        det.predict_views(fr, fr.shape[0], fr.shape[1], fr.shape[2], fr.shape[3] if fr.dim() == 4 else 1, idx, pos, n, vw, vh, rows, conf, anchor,
+                          conf=self._conf, iou=self._iou, max_det=1, stream=self._stream.cuda_stream)
+
     def _step_call(self, c: int):
-        fr, (vw, vh) = self._frames, self._view
-        self.step_detector.predict_views(fr, fr.shape[0], fr.shape[1], fr.shape[2], fr.shape[3] if fr.dim() == 4 else 1, self._decision_idx[c:c + 1], self._pos[c],
-                                         1, vw, vh, self._step_rows[c], self._step_conf[c:c + 1], self._step_anchor[c:c + 1], conf=self._conf, iou=self._iou,
-                                         max_det=1, stream=self._stream.cuda_stream)
+        self._call(self.step_detector, self._decision_idx[c:c + 1], self._pos[c], 1, self._step_rows[c], self._step_conf[c:c + 1], self._step_anchor[c:c + 1])
 
     def _log_call(self, r0: int, n: int):
-        fr, (vw, vh) = self._frames, self._view
-        self.log_detector.predict_views(fr, fr.shape[0], fr.shape[1], fr.shape[2], fr.shape[3] if fr.dim() == 4 else 1, self._log_idx[r0:r0 + n],
-                                        self._frame_pos[r0:r0 + n], n, vw, vh, self._det[r0:r0 + n], self._det_conf[r0:r0 + n], self._det_anchor[r0:r0 + n],
-                                        conf=self._conf, iou=self._iou, max_det=1, stream=self._stream.cuda_stream)
+        r = slice(r0, r0 + n)
+        self._call(self.log_detector, self._log_idx[r], self._frame_pos[r], n, self._det[r], self._det_conf[r], self._det_anchor[r])
 
     def run(self) -> ReplayResult:
         """Enqueue the whole experiment and wait for it once.  Two runs give the same bits."""
@@ -584,6 +580,4 @@ class YoloReplay:
                                 self._scratch, self._scratch.numel(), stream=st)
                 detections = self._det[:R].clone()
             self._finish()
-            return ReplayResult(moves=self._move.permute(1, 0, 2).contiguous().cpu().numpy(), positions=self._pos.permute(1, 0, 2).contiguous().cpu().numpy(),
-                                summary=_summary_of(self._summary.cpu().numpy()), decision_frames=np.arange(C, dtype=np.int64) * self.L + self.I, row_ids=[0],
-                                row_data=self._rows.cpu().numpy(), bbox_error=None, mse_error=None, detections=detections)
+            return _result_of(self.geometry, self._pos, self._move, self._summary, [0], self._rows, detections=detections)
