@@ -628,6 +628,51 @@ int wtk_boxes(const uint8_t *frames_dev, int32_t n_frames, int32_t H, int32_t W,
               int32_t n_sel, int32_t diff_thresh, int32_t *boxes_dev, int64_t *area2_dev, uint8_t *mask_dev, int32_t *fault_count_dev,
               void *scratch, int64_t scratch_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The precise tracking error of a replayed population (csrc/replay.hip): ErrorCalculator.calculate_precise
+ * (eval/error_calculator.py:64-160) of every (experiment, logged frame) pair of a scan, with wtk_precise_error's counts and bits for the
+ * row wtk_replay_rows logs.  frames_dev [n_frames][H][W] gray with n_frames >= R: row r is frame r.  bg_dev [H][W].  A pixel is
+ * foreground where |frame - bg| > diff_thresh.
+ *
+ * wtk_replay_precise   one workgroup per logged frame.  The segmented mask of frame r depends on the frame, the background and the
+ *     track's row r only: it is built once, as an exclusive summed-area table in LDS over the row's discretised box grown by one pixel
+ *     (the logged box (x - cam) + cam moves an edge by at most one pixel), and every experiment is answered with two rectangle sums
+ *     (the logged worm box; worm x microscope, 0 where the intersection is empty).  A pair whose logged box is not inside the table's
+ *     region, and every pair of a frame whose table needs more than max_crop_px uint32 cells ((h + 3) x pitch, pitch = (w + 3) | 1 for a
+ *     w x h box away from the frame's edge), is computed by the direct walk over the crop, as wtk_precise_error does (a second launch
+ *     without LDS, which does nothing for frames that left no such pair): same counts, so max_crop_px never changes a bit.  max_crop_px = 0: the default, 160 KiB of LDS = 40960 cells; larger values mean the default.
+ *   err_dev [E][R] float64 (nullable): 1 - inside / total, 0 where total = 0, NaN for an illegal logged worm box.  counts_dev
+ *     [E][R][2] int32 (nullable): (total, inside), (0, 0) on NaN rows.
+ *   summary_dev [E][WTK_REPLAY_PRECISE_SUMMARY_DOUBLES]: [0] sum of err over the rows with a value (not NaN), [1] their number, [2] [3]
+ *     the same over the imaging rows of the cycles 1 .. n_log - 2 (DataAnalyzer.clean(trim_cycles=True, imaging_only=True)), [4] rows with
+ *     err > 1e-7, [5] NaN rows.  NaN rows enter no sum (pandas' mean of the column).  Sums are taken in wtk_replay_rows' fixed order
+ *     (chunks of 4096 rows, 256 lane-serial accumulators, a binary tree, chunk partials in index order): an experiment gives the same
+ *     bits alone and in any population.  scratch_dev: wtk_replay_precise_scratch_doubles(E, R) doubles (-1: negative sizes): the
+ *     E R pair errors, the chunk partials and R int32 flags.
+ * wtk_replay_precise_objective   wtk_replay_scan, wtk_replay_precise without per-pair output, then objective_dev[e] = one float64
+ *     division: WTK_REPLAY_POBJ_TRIMMED_PRECISE summary[2] / summary[3], _MEAN_PRECISE [0] / [1], _NON_PERFECT [4] / [1]; 0 / 0 is NaN.
+ * stop_dev (nullable): as for wtk_replay_objective.
+ * Refused (error code, nothing launched): what wtk_replay_rows refuses of the geometry, a required pointer that is null, n_frames < R,
+ *     (H, W) other than the config's (frame_h, frame_w), H * W > 2^30, max_crop_px < 0, scratch too small; the objective: what
+ *     wtk_replay_scan refuses, an unknown objective, the trimmed objective with fewer than 3 logged cycles.
+ * ------------------------------------------------------------------------------------------ */
+#define WTK_REPLAY_PRECISE_SUMMARY_DOUBLES 6
+#define WTK_REPLAY_POBJ_TRIMMED_PRECISE 0
+#define WTK_REPLAY_POBJ_MEAN_PRECISE 1
+#define WTK_REPLAY_POBJ_NON_PERFECT 2
+int64_t wtk_replay_precise_scratch_doubles(int32_t E, int64_t R);
+int wtk_replay_precise(const wtk_replay_config *cfg, int32_t E, int32_t n_cycles, const double *track_dev, int32_t n_track,
+                       const double *share_dev, const int32_t *pos_dev, const int32_t *move_dev, const uint8_t *frames_dev, int32_t n_frames,
+                       int32_t H, int32_t W, const uint8_t *bg_dev, double diff_thresh, int32_t max_crop_px, double *err_dev,
+                       int32_t *counts_dev, double *summary_dev, double *scratch_dev, int64_t scratch_doubles, const int32_t *stop_dev,
+                       void *stream);
+int wtk_replay_precise_objective(const wtk_replay_config *cfg, int32_t kind, int32_t E, int32_t n_cycles, const double *track_dev,
+                                 int32_t n_track, const double *a_dev, const double *b_dev, const int32_t *valid_dev,
+                                 const double *share_dev, int32_t *pos_dev, int32_t *move_dev, const uint8_t *frames_dev, int32_t n_frames,
+                                 int32_t H, int32_t W, const uint8_t *bg_dev, double diff_thresh, int32_t max_crop_px, double *summary_dev,
+                                 double *scratch_dev, int64_t scratch_doubles, int32_t objective, double *objective_dev,
+                                 const int32_t *stop_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,7 @@ simulate.ipynb loads the file too; here `load_config(path)` gives the controller
   python tools/optimize_polyfit_weights.py EXPERIMENT_FOLDER_OR_BBOXES_CSV [more logs ...] --out polyfit_config.json
          [--fps 60] [--imaging-ms 200 --pred-ms 40 --moving-ms 50] [--offsets -45 -39 ...] [--pred-offset 21] [--degrees 1 2 3]
          [--min-speed 0.1 --max-speed 2] [--seed 0] [--pop-size 100 --max-epoch 300 --max-early-stop 100]
-         [--closed-loop EXP_CONFIG_JSON [--camera-mm 4 4] [--micro-mm 0.32 0.32]]
+         [--closed-loop EXP_CONFIG_JSON [--camera-mm 4 4] [--micro-mm 0.32 0.32] [--precise FRAMES_NPY BACKGROUND_NPY]]
 
 A folder stands for its bboxes.csv, and its exp_config.json supplies frames_per_sec when --fps is not given.  Defaults are the notebook's: with L the
 cycle length in frames, offsets (-3L, -3L+6, -2L, -2L+6, -L, -L+6, 0, 3), target offset L + imaging_frames // 2, speed window 0.1 .. 2 px / frame.
@@ -17,7 +17,9 @@ config goes to <out stem>_deg<d>.json and the best one to --out.  Needs a GPU (t
 search per degree whose objective is the tracking error of the closed loop itself (Replay.optimize_polyfit on the FIRST log: the trimmed mean bbox
 error of the replayed experiment), started from the open-loop winner, so its result is never worse than that winner in the loop.  The result line then
 also holds `closed_loop_error_of_open_loop_weights`, `closed_loop_error` and `closed_loop_weights`, and the closed-loop config of the best degree goes to
-<out stem>_closed_loop.json.  The closed-loop error is piecewise constant in the weights (moves are whole pixels).  Without the option nothing changes."""
+<out stem>_closed_loop.json.  The closed-loop error is piecewise constant in the weights (moves are whole pixels).  Without the option nothing changes.
+With --precise FRAMES_NPY BACKGROUND_NPY (the experiment's gray frames, uint8 [F, H, W] with F >= the logged rows, and its background [H, W]) the
+closed-loop objective is the trimmed mean PRECISE error instead (Replay.attach_frames; the frames are held on the device and give the frame shape)."""
 import argparse
 import json
 import os
@@ -60,6 +62,7 @@ def main(argv=None):
     ap.add_argument("--closed-loop", default=None, metavar="EXP_CONFIG_JSON")
     ap.add_argument("--camera-mm", type=float, nargs=2, default=[4.0, 4.0])
     ap.add_argument("--micro-mm", type=float, nargs=2, default=[0.32, 0.32])
+    ap.add_argument("--precise", nargs=2, default=None, metavar=("FRAMES_NPY", "BACKGROUND_NPY"))
     args = ap.parse_args(argv)
 
     from wtracker_amd.polyfit_opt import WeightEvaluator
@@ -84,11 +87,23 @@ def main(argv=None):
     stem, ext = os.path.splitext(args.out)
     best = None
     rp = best_closed = None
+    objective = "trimmed_bbox_error"
+    if args.precise is not None and args.closed_loop is None:
+        ap.error("--precise goes with --closed-loop")
     if args.closed_loop is not None:
         from wtracker_amd.replay import Replay
 
         exp = ExperimentConfig.from_dict(json.load(open(args.closed_loop)))
-        rp = Replay(paths[0], TimingConfig(exp, args.imaging_ms, args.pred_ms, args.moving_ms, tuple(args.camera_mm), tuple(args.micro_mm)), exp, device=args.device)
+        frames = None
+        if args.precise is not None:
+            import numpy as np
+            import torch
+
+            frames, objective = torch.from_numpy(np.load(args.precise[0])).to(f"cuda:{args.device}"), "trimmed_precise_error"
+        rp = Replay(paths[0], TimingConfig(exp, args.imaging_ms, args.pred_ms, args.moving_ms, tuple(args.camera_mm), tuple(args.micro_mm)), exp,
+                    frame_shape=None if frames is None else frames.shape[1:3], device=args.device)
+        if frames is not None:
+            rp.attach_frames(frames, np.load(args.precise[1]))
     for deg in args.degrees:
         res = ev.optimize(deg, pop_size=args.pop_size, max_epoch=args.max_epoch, max_early_stop=args.max_early_stop, seed=args.seed)
         cfg = ev.to_config(deg, res.weights)
@@ -97,9 +112,9 @@ def main(argv=None):
         line = {"degree": deg, "mae": res.mae, "mae_uniform_weights": ev.eval([1.0] * len(offsets), deg), "epochs": res.epochs,
                 "series": ev.n_series, "cycles_per_log": ev.cycle_stats, "weights": cfg.weights}
         if rp is not None:
-            closed = rp.optimize_polyfit(deg, cfg.sample_times, pop_size=args.pop_size, max_epoch=args.max_epoch, max_early_stop=args.max_early_stop,
+            closed = rp.optimize_polyfit(deg, cfg.sample_times, objective=objective, pop_size=args.pop_size, max_epoch=args.max_epoch, max_early_stop=args.max_early_stop,
                                          seed=args.seed, start=[res.weights])
-            of_open = float(rp.objective(rp.polyfit_population([cfg.weights], deg, cfg.sample_times)).cpu().numpy()[0])
+            of_open = float(rp.objective(rp.polyfit_population([cfg.weights], deg, cfg.sample_times), objective).cpu().numpy()[0])
             line.update(closed_loop_error_of_open_loop_weights=of_open, closed_loop_error=closed.mae, closed_loop_epochs=closed.epochs,
                         closed_loop_weights=[float(w) for w in closed.weights])
             if best_closed is None or closed.mae < best_closed[0]:
@@ -111,7 +126,7 @@ def main(argv=None):
     print(f"wrote {args.out}: degree {best[1].degree}, MAE {best[0]:.6g} px")
     if best_closed is not None:
         save_config(best_closed[1], f"{stem}_closed_loop{ext}")
-        print(f"wrote {stem}_closed_loop{ext}: degree {best_closed[1].degree}, closed-loop trimmed mean bbox error {best_closed[0]:.6g}")
+        print(f"wrote {stem}_closed_loop{ext}: degree {best_closed[1].degree}, closed-loop {objective.replace('_', ' ')} {best_closed[0]:.6g}")
 
 
 if __name__ == "__main__":

@@ -15,7 +15,9 @@
 // (bbox_utils.py:118-167: x + w in the array's own dtype, floor / ceil, the int32 cast, clip to the frame, zero-area boxes illegal), the wave walks the
 // worm crop of the row's full frame and counts |frame - background| > thr (total) and the same pixels inside the worm / microscope intersection
 // (inside) with ballots; err = 1 - inside / total in float64, 0 where total = 0, NaN for an illegal worm box or a frame number outside [0, F).
+// The row's rules (discretize, intersect, crop_walk, precise_error_of) live in eval_device.h, shared with replay_precise_kernel (replay.hip).
 #include "wtk_internal.h"
+#include "eval_device.h"
 
 #include <algorithm>
 #include <climits>
@@ -187,22 +189,6 @@ template <bool kVec> __global__ __launch_bounds__(kBgThreads) void background_me
     store4<kVec>(a.bg, off, a.frame_bytes, out);
 }
 
-// numpy's float -> int32 cast on x86-64 (cvttsd2si): out of range and NaN give INT_MIN
-__device__ __forceinline__ int to_i32(double v) { return (v >= -2147483648.0 && v < 2147483648.0) ? (int)v : INT_MIN; }
-__device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-
-// BoxUtils.discretize of one xywh row to xyxy; false (and a zero box) when the row is illegal
-template <typename T> __device__ __forceinline__ bool discretize(const T *box, int H, int W, int &x1, int &y1, int &x2, int &y2) {
-    T x = box[0], y = box[1], w = box[2], h = box[3];
-    if (!(isfinite(x) && isfinite(y) && isfinite(w) && isfinite(h))) x = y = w = h = (T)0;
-    const T xr = x + w, yb = y + h; // BoxConverter.to_xyxy in the array's dtype
-    x1 = clampi(to_i32(floor((double)x)), W), y1 = clampi(to_i32(floor((double)y)), H);
-    x2 = clampi(to_i32(ceil((double)xr)), W), y2 = clampi(to_i32(ceil((double)yb)), H);
-    if (x2 - x1 > 0 && y2 - y1 > 0) return true;
-    x1 = y1 = x2 = y2 = 0;
-    return false;
-}
-
 template <typename T> __global__ __launch_bounds__(kPeThreads) void precise_error_kernel(const PreciseErrorArgs a) {
     const int lane = threadIdx.x & 63;
     const T *worm = reinterpret_cast<const T *>(a.worm);
@@ -220,36 +206,14 @@ template <typename T> __global__ __launch_bounds__(kPeThreads) void precise_erro
             continue;
         }
         discretize(mic + 4 * r, a.H, a.W, ml, mt, mr, mb); // an illegal microscope box is (0, 0, 0, 0): an empty intersection
-        const int il = max(wl, ml), it = max(wt, mt);
-        const int ir = il + max(0, min(wr, mr) - il), ib = it + max(0, min(wb, mb) - it);
-        const int cw = wr - wl, npx = cw * (wb - wt);
-        const long long base = (long long)f * a.H * a.W;
-        const uint8_t *fr = a.frames + base;
-        int total = 0, inside = 0;
-        for (int i0 = 0; i0 < npx; i0 += 64) { // wave-uniform trip count
-            const int i = i0 + lane;
-            bool fg = false, in = false;
-            if (i < npx) {
-                const int yy = i / cw, X = wl + (i - yy * cw), Y = wt + yy;
-                const long long o = (long long)Y * a.W + X;
-                fg = abs((int)fr[o] - (int)a.bg[o]) > a.thr;
-                in = fg && X >= il && X < ir && Y >= it && Y < ib;
-            }
-            total += __popcll(__ballot(fg));
-            inside += __popcll(__ballot(in));
-        }
+        int il, it, ir, ib, total, inside;
+        intersect(wl, wt, wr, wb, ml, mt, mr, mb, il, it, ir, ib);
+        crop_walk(a.frames + (long long)f * a.H * a.W, a.bg, a.W, a.thr, lane, wl, wt, wr, wb, il, it, ir, ib, total, inside);
         if (lane == 0) {
-            a.err[r] = total == 0 ? 0.0 : 1.0 - (double)inside / (double)total;
+            a.err[r] = precise_error_of(total, inside);
             if (a.counts) a.counts[2 * r] = total, a.counts[2 * r + 1] = inside;
         }
     }
-}
-
-// |frame - bg| > t for integer |frame - bg| in [0, 255]: > floor(t) for finite t
-int threshold_int(double t) {
-    if (std::isnan(t) || t >= 255.0) return 255; // nothing is foreground
-    if (t < 0.0) return -1;                      // everything is
-    return (int)std::floor(t);
 }
 
 } // namespace

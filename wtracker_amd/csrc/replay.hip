@@ -23,11 +23,17 @@
 //           position, where wtk_yolo_predict_views reads it; after the loop one thread per logged frame gives the frame's platform position (the
 //           detector's pos_xy for the log pass) and one thread per logged frame turns view-pixel detections into the absolute float64 track the rows
 //           kernel reads (TrackLogger's per-cycle float32 / float64 rule).  The motor is motor_steps() / frame_position(), shared with scan and rows.
+//   precise the reference's analysis metric (ErrorCalculator.calculate_precise: the share of the worm's segmented pixels outside the microscope view) of
+//           every (experiment, logged frame) pair, DESIGN.md section 19.  The segmented mask of frame r depends on the frame, the background and the
+//           track's row r only, so ONE workgroup per frame builds it once, as an exclusive summed-area table in LDS, and answers every experiment with
+//           two rectangle sums: O(F area + E F) pixel work, not O(E F area).  See replay_precise_kernel.
 //   A nullable stop flag (the swarm's ctrl word) turns the targets, the objective and, through them only, the scan and the rows reduction into no-ops.
 // Everything relies on -ffp-contract=off (the library's build flag): share * move + carry is a rounded product and a rounded sum, as in Python.
 #include "wtk_internal.h"
+#include "eval_device.h"
 #include "polyfit_solve.h"
 
+#include <algorithm>
 #include <cmath>
 
 using namespace wtk;
@@ -40,6 +46,10 @@ constexpr int kRowChunk = 4096; // logged rows per block of the rows kernel: the
 constexpr int kSummary = WTK_REPLAY_SUMMARY_DOUBLES;
 constexpr int kRowDoubles = WTK_REPLAY_ROW_DOUBLES;
 constexpr double kMoveMax = 1073741824.0; // 2^30: moves are kept as int32
+constexpr int kPreciseThreads = 256;
+constexpr int kPreciseSummary = WTK_REPLAY_PRECISE_SUMMARY_DOUBLES;
+constexpr int kPreciseLdsBytes = 160 * 1024;            // the CU's LDS: one workgroup per CU takes all of it at the default limit
+constexpr int kPreciseMaxCells = kPreciseLdsBytes / 4;  // uint32 cells of the largest table
 
 struct Geometry {
     int L, I, M, P;
@@ -93,10 +103,37 @@ struct PopArgs {
     const int *stop;
 };
 
+struct FinishArgs {
+    const double *partial; // [E][S][n]
+    double *summary;       // [E][n]
+    int E, S, n;
+    const int *stop;
+};
+
 struct ObjectiveArgs {
-    const double *summary; // [E][kSummary]
+    const double *summary; // [E][n]
     double *objective;     // [E]
-    int E, num, den;       // objective = summary[num] / summary[den]
+    int E, n, num, den;    // objective = summary[num] / summary[den]
+    const int *stop;
+};
+
+struct PreciseArgs {
+    Geometry g;
+    int E, C, S, n_log;
+    long long R;
+    const double *track;
+    const double *share;
+    const int *pos, *move; // [C][E][2]
+    const uint8_t *frames; // [n_frames][H][W] gray, row r is frame r
+    const uint8_t *bg;     // [H][W]
+    int H, W, thr;         // a pixel is foreground where |frame - bg| > thr
+    int max_cells;         // a frame whose table needs more uint32 cells walks its crops instead
+    double *pair;          // [R][E] the error of every pair, NaN = no value
+    int *walk;             // [R] != 0: the frame has pairs the table did not answer (replay_precise_walk_kernel)
+    double *err;           // [E][R] (nullable)
+    int *counts;           // [E][R][2] (total, inside) (nullable)
+    double *partial;       // [E][S][kPreciseSummary]
+    double *summary;       // [E][kPreciseSummary]
     const int *stop;
 };
 
@@ -172,6 +209,24 @@ __device__ __forceinline__ double finish_move(double v) {
     return fmin(fmax(rint(v), -kMoveMax), kMoveMax);
 }
 
+// The boxes of a log row from the platform position at its camera picture: camera and microscope corners, and the logged worm box, which is the track's
+// row made camera-relative (CsvController.predict) and absolute again (LoggingController); a non-finite row is logged as zeros.  (x - cam) + cam is not
+// always x: the rows kernel and the precise kernel both take the box from here.
+struct RowBoxes {
+    double cam_x, cam_y, mic_x, mic_y, mic_w, mic_h;
+    double wx, wy, ww, wh;
+};
+
+__device__ __forceinline__ RowBoxes row_boxes(const Geometry &g, const double *track_row, int px, int py) {
+    RowBoxes b;
+    b.cam_x = (double)(px - g.cam_w / 2), b.cam_y = (double)(py - g.cam_h / 2);
+    b.mic_x = (double)(px - g.mic_w / 2), b.mic_y = (double)(py - g.mic_h / 2);
+    b.mic_w = (double)g.mic_w, b.mic_h = (double)g.mic_h;
+    b.wx = (track_row[0] - b.cam_x) + b.cam_x, b.wy = (track_row[1] - b.cam_y) + b.cam_y, b.ww = track_row[2], b.wh = track_row[3];
+    if (!(isfinite(b.wx) && isfinite(b.wy) && isfinite(b.ww) && isfinite(b.wh))) b.wx = b.wy = b.ww = b.wh = 0.0;
+    return b;
+}
+
 __global__ __launch_bounds__(kScanThreads) void replay_scan_kernel(const ScanArgs a) {
     if (a.stop && *a.stop) return;
     const int e = blockIdx.x * kScanThreads + threadIdx.x;
@@ -228,12 +283,9 @@ __global__ __launch_bounds__(kRowThreads) void replay_rows_kernel(const RowsArgs
         const long long ce = (long long)c * a.E + e;
         int px, py;
         frame_position(g, a.share, a.pos, a.move, ce, step, px, py);
-        const double cam_x = (double)(px - g.cam_w / 2), cam_y = (double)(py - g.cam_h / 2);
-        const double mic_x = (double)(px - g.mic_w / 2), mic_y = (double)(py - g.mic_h / 2);
-        const double mic_w = (double)g.mic_w, mic_h = (double)g.mic_h;
-        // the logged worm box: camera-relative (CsvController.predict) and back (LoggingController), a non-finite row as zeros
-        double wx = (a.track[4 * r] - cam_x) + cam_x, wy = (a.track[4 * r + 1] - cam_y) + cam_y, ww = a.track[4 * r + 2], wh = a.track[4 * r + 3];
-        if (!(isfinite(wx) && isfinite(wy) && isfinite(ww) && isfinite(wh))) wx = wy = ww = wh = 0.0;
+        const RowBoxes b = row_boxes(g, a.track + 4 * r, px, py);
+        const double cam_x = b.cam_x, cam_y = b.cam_y, mic_x = b.mic_x, mic_y = b.mic_y, mic_w = b.mic_w, mic_h = b.mic_h;
+        const double wx = b.wx, wy = b.wy, ww = b.ww, wh = b.wh;
         // ErrorCalculator.calculate_bbox_error
         const double il = fmax(wx, mic_x), it = fmax(wy, mic_y);
         const double ir = fmin(wx + ww, mic_x + mic_w), ib = fmin(wy + wh, mic_y + mic_h);
@@ -270,14 +322,15 @@ __global__ __launch_bounds__(kRowThreads) void replay_rows_kernel(const RowsArgs
     if (threadIdx.x < kSummary) a.partial[((long long)e * a.S + s) * kSummary + threadIdx.x] = red[threadIdx.x][0];
 }
 
-__global__ __launch_bounds__(64) void replay_finish_kernel(const RowsArgs a) {
+// the chunk partials of every experiment added in index order (the rows reduction and the precise reduction)
+__global__ __launch_bounds__(64) void replay_finish_kernel(const FinishArgs a) {
     if (a.stop && *a.stop) return;
     const long long i = (long long)blockIdx.x * 64 + threadIdx.x;
-    if (i >= (long long)a.E * kSummary) return;
-    const long long e = i / kSummary;
-    const int q = (int)(i - e * kSummary);
+    if (i >= (long long)a.E * a.n) return;
+    const long long e = i / a.n;
+    const int q = (int)(i - e * a.n);
     double sum = 0.0;
-    for (int s = 0; s < a.S; ++s) sum += a.partial[(e * a.S + s) * kSummary + q];
+    for (int s = 0; s < a.S; ++s) sum += a.partial[(e * a.S + s) * a.n + q];
     a.summary[i] = sum;
 }
 
@@ -286,7 +339,180 @@ __global__ __launch_bounds__(64) void replay_objective_kernel(const ObjectiveArg
     const int e = blockIdx.x * 64 + threadIdx.x;
     if (e >= a.E) return;
     // the float64 division Summary's properties perform on the host (counts are exact doubles); 0 / 0 = NaN, which the swarm never lets win
-    a.objective[e] = a.summary[(long long)e * kSummary + a.num] / a.summary[(long long)e * kSummary + a.den];
+    a.objective[e] = a.summary[(long long)e * a.n + a.num] / a.summary[(long long)e * a.n + a.den];
+}
+
+// sum of the exclusive summed-area table over [l, r) x [t, b) in table coordinates; uint32 arithmetic wraps and the result is exact
+__device__ __forceinline__ int sat_rect(const unsigned *sat, int pitch, int l, int t, int r, int b) {
+    return (int)(sat[b * pitch + r] - sat[t * pitch + r] - sat[b * pitch + l] + sat[t * pitch + l]);
+}
+
+// The precise error of every experiment at ONE logged frame r = blockIdx.x (row r is frame r).
+//
+// Phase 1, once per frame.  The track's row r is discretised as BoxUtils.discretize does, grown by one pixel on every side (the logged box of an
+// experiment is the row after (x - cam) + cam, which moves an edge by at most one pixel: DESIGN.md section 19) and clipped to the frame: the padded
+// region, pw x ph pixels.  |frame - bg| > thr over it becomes an exclusive summed-area table of (ph + 1) x (pw + 1) uint32 in dynamic LDS:
+//   fill    a wave per region row, lane = column: byte loads of 64 consecutive pixels of the frame and of the background (row-contiguous; no alignment
+//           of the base or of W is assumed, and the region is a few dozen KB at most, read once), ds_write_b32 of consecutive words.
+//   rows    a thread per table row, serial along x.  Lane l of a 32-lane group reads word l * pitch + x: ds_read_b32 / ds_write_b32 bank on 32 words,
+//           so the 32 rows hit 32 different banks exactly when the pitch is ODD.  pitch = (pw + 1) | 1.
+//   columns a thread per table column, serial along y: lanes read consecutive words, conflict-free for any pitch.
+// A row pass of h threads x w steps leaves most of the block idle; it is O(w + h) LDS round trips per frame and runs once for all E experiments.
+//
+// Phase 2.  Threads stride over the experiments: platform position of (e, r) (frame_position), the row's boxes (row_boxes), both discretised, then
+// total = the table over the logged worm box and inside = the table over worm x microscope.  An EMPTY intersection is decided first: its corner may lie
+// outside the worm box and the table.  err = 1 - inside / total in float64, 0 where total = 0, NaN for an illegal worm box: precise_error_kernel's rules
+// (eval_device.h) and its counts.
+//
+// Exact fallback.  A pair whose logged box is not inside the padded region (never seen; an illegal track row with a legal logged box would be one) and
+// every pair of a frame whose table does not fit `max_cells` is left to replay_precise_walk_kernel, which this kernel tells through walk[r] whether
+// frame r has such a pair.  That kernel asks for no LDS, so its waves fill the CUs; here a block that holds 160 KiB would walk with 4 waves per CU
+// (measured: 4 x slower than the per-row kernel).  It walks the crop with crop_walk, precise_error_kernel's loop: the lanes that need it are collected
+// with a ballot and the whole wave walks them one after the other.  Both ways count the same pixels, so the limit never changes a bit.
+//
+// Occupancy: at the default limit a workgroup asks for all 160 KiB of LDS, so one workgroup (4 waves) runs per CU, 256 frames at a time on the device; a
+// handful of frames leaves most CUs idle, and nothing hides the latency of phase 1's dependent LDS passes.
+struct PreciseRegion {
+    int pl, pt, pr, pb; // the padded region of the frame, empty where the track's row is illegal
+    int pitch;          // of its table, in words
+    bool table;         // the table fits max_cells: replay_precise_kernel builds it
+};
+
+__device__ __forceinline__ PreciseRegion precise_region(const PreciseArgs &a, long long r) {
+    PreciseRegion g;
+    const bool track_legal = discretize(a.track + 4 * r, a.H, a.W, g.pl, g.pt, g.pr, g.pb);
+    if (track_legal) g.pl = max(g.pl - 1, 0), g.pt = max(g.pt - 1, 0), g.pr = min(g.pr + 1, a.W), g.pb = min(g.pb + 1, a.H);
+    g.pitch = (g.pr - g.pl + 1) | 1;
+    g.table = track_legal && (long long)(g.pb - g.pt + 1) * g.pitch <= a.max_cells;
+    return g;
+}
+
+// Phase 2 over the experiments of frame r.  kWalk = false: the pairs the table answers and the pairs without a value; returns whether a pair of this
+// thread is left to the walk.  kWalk = true: exactly those pairs, by the walk (`sat` is not read).  Every thread of the block must call it.
+template <bool kWalk> __device__ __forceinline__ bool precise_pairs(const PreciseArgs &a, long long r, const PreciseRegion &reg, const unsigned *sat) {
+    const Geometry g = a.g;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint8_t *fr = a.frames + r * a.H * a.W;
+    const int c = (int)(r / g.L), step = (int)(r - (long long)c * g.L);
+    bool left = false;
+    for (int e0 = wave * 64; e0 < a.E; e0 += kPreciseThreads) { // wave-uniform trip count: the ballot below sees the whole wave
+        const int e = e0 + lane;
+        int wl = 0, wt = 0, wr = 0, wb = 0, il = 0, it = 0, ir = 0, ib = 0, total = 0, inside = 0;
+        bool legal = false, walk = false;
+        if (e < a.E) {
+            int px, py, ml, mt, mr, mb;
+            frame_position(g, a.share, a.pos, a.move, (long long)c * a.E + e, step, px, py);
+            const RowBoxes b = row_boxes(g, a.track + 4 * r, px, py);
+            const double worm[4] = {b.wx, b.wy, b.ww, b.wh}, mic[4] = {b.mic_x, b.mic_y, b.mic_w, b.mic_h};
+            legal = discretize(worm, a.H, a.W, wl, wt, wr, wb);
+            if (legal) {
+                discretize(mic, a.H, a.W, ml, mt, mr, mb); // an illegal microscope box is (0, 0, 0, 0): an empty intersection
+                intersect(wl, wt, wr, wb, ml, mt, mr, mb, il, it, ir, ib);
+                walk = !(reg.table && wl >= reg.pl && wt >= reg.pt && wr <= reg.pr && wb <= reg.pb);
+                if (!kWalk && !walk) {
+                    total = sat_rect(sat, reg.pitch, wl - reg.pl, wt - reg.pt, wr - reg.pl, wb - reg.pt);
+                    inside = (ir > il && ib > it) ? sat_rect(sat, reg.pitch, il - reg.pl, it - reg.pt, ir - reg.pl, ib - reg.pt) : 0; // non-empty: inside the worm box
+                }
+            }
+        }
+        left |= walk;
+        if (kWalk) {
+            for (unsigned long long todo = __ballot(walk); todo; todo &= todo - 1) {
+                const int j = __ffsll((long long)todo) - 1;
+                int t, in;
+                crop_walk(fr, a.bg, a.W, a.thr, lane, __shfl(wl, j), __shfl(wt, j), __shfl(wr, j), __shfl(wb, j), __shfl(il, j), __shfl(it, j),
+                          __shfl(ir, j), __shfl(ib, j), t, in);
+                if (lane == j) total = t, inside = in;
+            }
+        }
+        if (e < a.E && walk == kWalk) {
+            const double err = legal ? precise_error_of(total, inside) : __builtin_nan("");
+            a.pair[r * a.E + e] = err;
+            if (a.err) a.err[(long long)e * a.R + r] = err;
+            if (a.counts) a.counts[2 * ((long long)e * a.R + r)] = total, a.counts[2 * ((long long)e * a.R + r) + 1] = inside;
+        }
+    }
+    return left;
+}
+
+__global__ __launch_bounds__(kPreciseThreads) void replay_precise_kernel(const PreciseArgs a) {
+    extern __shared__ unsigned sat[];
+    if (a.stop && *a.stop) return; // block-uniform
+    const long long r = blockIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint8_t *fr = a.frames + r * a.H * a.W;
+    const PreciseRegion reg = precise_region(a, r);
+    const int pl = reg.pl, pt = reg.pt, pw = reg.pr - reg.pl, ph = reg.pb - reg.pt, pitch = reg.pitch;
+    if (reg.table) { // block-uniform
+        for (int x = threadIdx.x; x <= pw; x += kPreciseThreads) sat[x] = 0u;
+        for (int y = 1 + threadIdx.x; y <= ph; y += kPreciseThreads) sat[y * pitch] = 0u;
+        for (int y = wave; y < ph; y += kPreciseThreads / 64) {
+            const long long o = (long long)(pt + y) * a.W + pl;
+            for (int x = lane; x < pw; x += 64) sat[(y + 1) * pitch + x + 1] = abs((int)fr[o + x] - (int)a.bg[o + x]) > a.thr ? 1u : 0u;
+        }
+        __syncthreads();
+        for (int y = 1 + threadIdx.x; y <= ph; y += kPreciseThreads) {
+            unsigned run = 0u;
+            for (int x = 1; x <= pw; ++x) run += sat[y * pitch + x], sat[y * pitch + x] = run;
+        }
+        __syncthreads();
+        for (int x = 1 + threadIdx.x; x <= pw; x += kPreciseThreads) {
+            unsigned run = 0u;
+            for (int y = 1; y <= ph; ++y) run += sat[y * pitch + x], sat[y * pitch + x] = run;
+        }
+        __syncthreads();
+    }
+    // any pair left to the walk?  The table's first word becomes the flag once every lookup is done: the kernel has no static LDS (__syncthreads_or
+    // would add some, and 160 KiB of dynamic LDS leave room for none)
+    const bool left = precise_pairs<false>(a, r, reg, sat);
+    __syncthreads();
+    if (threadIdx.x == 0) sat[0] = 0u;
+    __syncthreads();
+    if (left) sat[0] = 1u; // every writer writes the same value
+    __syncthreads();
+    if (threadIdx.x == 0) a.walk[r] = (int)sat[0];
+}
+
+// The pairs replay_precise_kernel left, by the direct walk over the crop: a block per frame, which returns at once where the frame has none.
+__global__ __launch_bounds__(kPreciseThreads) void replay_precise_walk_kernel(const PreciseArgs a) {
+    if (a.stop && *a.stop) return; // block-uniform
+    const long long r = blockIdx.x;
+    if (!a.walk[r]) return; // block-uniform
+    precise_pairs<true>(a, r, precise_region(a, r), nullptr);
+}
+
+// Per-experiment sums of the pairs' errors in the rows kernel's FIXED order: a block per (chunk of 4096 rows, experiment), thread t adds rows t, t + 256,
+// ... of the chunk in order, a binary tree in LDS, the finish launch adds the chunk partials in index order.  NaN rows have no value and enter no sum
+// (pandas' mean over the column).  Consecutive blocks are consecutive experiments of one chunk: their strided reads of `pair` [R][E] share cache lines.
+__global__ __launch_bounds__(kRowThreads) void replay_precise_reduce_kernel(const PreciseArgs a) {
+    __shared__ double red[kPreciseSummary][kRowThreads];
+    if (a.stop && *a.stop) return; // block-uniform
+    const Geometry g = a.g;
+    const int s = blockIdx.x / a.E, e = blockIdx.x - s * a.E;
+    double acc[kPreciseSummary];
+    for (int q = 0; q < kPreciseSummary; ++q) acc[q] = 0.0;
+    const long long r0 = (long long)s * kRowChunk;
+    for (int i = 0; i < kRowChunk / kRowThreads; ++i) {
+        const long long r = r0 + (long long)i * kRowThreads + threadIdx.x;
+        if (r >= a.R) continue;
+        const double err = a.pair[r * a.E + e];
+        if (isnan(err)) {
+            acc[5] += 1.0;
+            continue;
+        }
+        const int c = (int)(r / g.L), step = (int)(r - (long long)c * g.L);
+        acc[0] += err, acc[1] += 1.0;
+        if (step < g.I && c != 0 && c != a.n_log - 1) acc[2] += err, acc[3] += 1.0; // DataAnalyzer.clean(trim_cycles=True, imaging_only=True)
+        if (err > 1e-7) acc[4] += 1.0;
+    }
+    for (int q = 0; q < kPreciseSummary; ++q) red[q][threadIdx.x] = acc[q];
+    __syncthreads();
+    for (int half = kRowThreads / 2; half > 0; half >>= 1) {
+        if ((int)threadIdx.x < half)
+            for (int q = 0; q < kPreciseSummary; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + half];
+        __syncthreads();
+    }
+    if (threadIdx.x < kPreciseSummary) a.partial[((long long)e * a.S + s) * kPreciseSummary + threadIdx.x] = red[threadIdx.x][0];
 }
 
 // The YOLO controller between two single-frame detector calls: HipYoloController.provide_movement_vector on the row where the detector left it, then the
@@ -492,9 +718,13 @@ int prepare_rows(const char *who, const wtk_replay_config *cfg, int32_t E, int32
     return 0;
 }
 
+void launch_finish(const FinishArgs &f, hipStream_t st) {
+    hipLaunchKernelGGL(replay_finish_kernel, dim3((unsigned)(((long long)f.E * f.n + 63) / 64)), dim3(64), 0, st, f);
+}
+
 void launch_rows(const RowsArgs &r, hipStream_t st) {
     if (r.S > 0) hipLaunchKernelGGL(replay_rows_kernel, dim3((unsigned)((long long)r.S * r.E)), dim3(kRowThreads), 0, st, r);
-    hipLaunchKernelGGL(replay_finish_kernel, dim3((unsigned)(((long long)r.E * kSummary + 63) / 64)), dim3(64), 0, st, r);
+    launch_finish(FinishArgs{r.partial, r.summary, r.E, r.S, kSummary, r.stop}, st);
 }
 
 } // namespace
@@ -549,10 +779,103 @@ extern "C" int wtk_replay_objective(const wtk_replay_config *cfg, int32_t kind, 
     if (objective == WTK_REPLAY_OBJ_TRIMMED_BBOX && r.n_log < 3)
         return fail("wtk_replay_objective: the trimmed objective needs at least 3 logged cycles (the first and the last are dropped)");
     s.stop = r.stop = o.stop = stop_dev;
-    o.summary = summary_dev, o.objective = objective_dev, o.E = E;
+    o.summary = summary_dev, o.objective = objective_dev, o.E = E, o.n = kSummary;
     hipStream_t st = (hipStream_t)stream;
     launch_scan(s, st);
     launch_rows(r, st);
+    hipLaunchKernelGGL(replay_objective_kernel, dim3((unsigned)((E + 63) / 64)), dim3(64), 0, st, o);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- the precise error of a replayed population
+namespace {
+
+int prepare_precise(const char *who, const wtk_replay_config *cfg, int32_t E, int32_t n_cycles, const double *track_dev, int32_t n_track, const double *share_dev,
+                    const int32_t *pos_dev, const int32_t *move_dev, const uint8_t *frames_dev, int32_t n_frames, int32_t H, int32_t W, const uint8_t *bg_dev,
+                    double diff_thresh, int32_t max_crop_px, double *err_dev, int32_t *counts_dev, double *summary_dev, double *scratch_dev,
+                    int64_t scratch_doubles, PreciseArgs &p) {
+    const std::string w(who);
+    int n_log = 0;
+    if (check_config(who, cfg, WTK_REPLAY_OPTIMAL, E, n_cycles, n_track, p.g, n_log)) return 1;
+    if (!track_dev || !share_dev || !pos_dev || !move_dev || !frames_dev || !bg_dev || !summary_dev || !scratch_dev) return fail(w + ": null argument");
+    if (H != cfg->frame_h || W != cfg->frame_w) return fail(w + ": the frames' (H, W) differ from the config's frame");
+    if ((long long)H * W > (1ll << 30)) return fail(w + ": frames must be H x W gray with H * W <= 2^30");
+    if (max_crop_px < 0) return fail(w + ": negative max_crop_px (0 = the default)");
+    p.R = (long long)n_log * p.g.L;
+    if (n_frames < p.R) return fail(w + ": fewer frames than logged rows (row r is frame r)");
+    const long long S = (p.R + kRowChunk - 1) / kRowChunk;
+    if (p.R > INT32_MAX || S * E > INT32_MAX) return fail(w + ": too many blocks for one launch");
+    if (scratch_doubles < wtk_replay_precise_scratch_doubles(E, p.R)) return fail(w + ": scratch smaller than wtk_replay_precise_scratch_doubles(E, R)");
+    p.E = E, p.C = n_cycles, p.S = (int)S, p.n_log = n_log;
+    p.track = track_dev, p.share = share_dev, p.pos = pos_dev, p.move = move_dev, p.frames = frames_dev, p.bg = bg_dev;
+    p.H = H, p.W = W, p.thr = threshold_int(diff_thresh);
+    p.max_cells = max_crop_px == 0 ? kPreciseMaxCells : std::min((int)max_crop_px, kPreciseMaxCells);
+    p.pair = scratch_dev, p.partial = scratch_dev + p.R * E, p.walk = reinterpret_cast<int *>(p.partial + (long long)E * S * kPreciseSummary), p.err = err_dev, p.counts = counts_dev, p.summary = summary_dev;
+    return 0;
+}
+
+int launch_precise(const PreciseArgs &p, hipStream_t st) {
+    if (p.R > 0) {
+        // above 64 KiB of dynamic LDS a kernel needs the attribute (per device, so it is set at every call: a host-side table write)
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&replay_precise_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kPreciseLdsBytes));
+        hipLaunchKernelGGL(replay_precise_kernel, dim3((unsigned)p.R), dim3(kPreciseThreads), (size_t)p.max_cells * sizeof(unsigned), st, p);
+        hipLaunchKernelGGL(replay_precise_walk_kernel, dim3((unsigned)p.R), dim3(kPreciseThreads), 0, st, p);
+        hipLaunchKernelGGL(replay_precise_reduce_kernel, dim3((unsigned)((long long)p.S * p.E)), dim3(kRowThreads), 0, st, p);
+    }
+    launch_finish(FinishArgs{p.partial, p.summary, p.E, p.S, kPreciseSummary, p.stop}, st);
+    return 0;
+}
+
+} // namespace
+
+extern "C" int64_t wtk_replay_precise_scratch_doubles(int32_t E, int64_t R) {
+    if (E < 0 || R < 0) return -1;
+    return (int64_t)E * R + (int64_t)E * ((R + kRowChunk - 1) / kRowChunk) * kPreciseSummary + (R + 1) / 2; // pairs, chunk partials, [R] int32 walk flags
+}
+
+extern "C" int wtk_replay_precise(const wtk_replay_config *cfg, int32_t E, int32_t n_cycles, const double *track_dev, int32_t n_track,
+                                  const double *share_dev, const int32_t *pos_dev, const int32_t *move_dev, const uint8_t *frames_dev, int32_t n_frames,
+                                  int32_t H, int32_t W, const uint8_t *bg_dev, double diff_thresh, int32_t max_crop_px, double *err_dev,
+                                  int32_t *counts_dev, double *summary_dev, double *scratch_dev, int64_t scratch_doubles, const int32_t *stop_dev,
+                                  void *stream) {
+    PreciseArgs p = {};
+    if (prepare_precise("wtk_replay_precise", cfg, E, n_cycles, track_dev, n_track, share_dev, pos_dev, move_dev, frames_dev, n_frames, H, W, bg_dev,
+                        diff_thresh, max_crop_px, err_dev, counts_dev, summary_dev, scratch_dev, scratch_doubles, p))
+        return 1;
+    p.stop = stop_dev;
+    if (launch_precise(p, (hipStream_t)stream)) return 1;
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int wtk_replay_precise_objective(const wtk_replay_config *cfg, int32_t kind, int32_t E, int32_t n_cycles, const double *track_dev,
+                                            int32_t n_track, const double *a_dev, const double *b_dev, const int32_t *valid_dev, const double *share_dev,
+                                            int32_t *pos_dev, int32_t *move_dev, const uint8_t *frames_dev, int32_t n_frames, int32_t H, int32_t W,
+                                            const uint8_t *bg_dev, double diff_thresh, int32_t max_crop_px, double *summary_dev, double *scratch_dev,
+                                            int64_t scratch_doubles, int32_t objective, double *objective_dev, const int32_t *stop_dev, void *stream) {
+    const char *who = "wtk_replay_precise_objective";
+    ScanArgs s = {};
+    PreciseArgs p = {};
+    if (prepare_scan(who, cfg, kind, E, n_cycles, track_dev, n_track, a_dev, b_dev, valid_dev, share_dev, pos_dev, move_dev, s)) return 1;
+    if (prepare_precise(who, cfg, E, n_cycles, track_dev, n_track, share_dev, pos_dev, move_dev, frames_dev, n_frames, H, W, bg_dev, diff_thresh, max_crop_px,
+                        nullptr, nullptr, summary_dev, scratch_dev, scratch_doubles, p))
+        return 1;
+    if (!objective_dev) return fail(std::string(who) + ": null argument");
+    ObjectiveArgs o = {};
+    switch (objective) {
+    case WTK_REPLAY_POBJ_TRIMMED_PRECISE: o.num = 2, o.den = 3; break;
+    case WTK_REPLAY_POBJ_MEAN_PRECISE: o.num = 0, o.den = 1; break;
+    case WTK_REPLAY_POBJ_NON_PERFECT: o.num = 4, o.den = 1; break;
+    default: return fail(std::string(who) + ": unknown objective");
+    }
+    if (objective == WTK_REPLAY_POBJ_TRIMMED_PRECISE && p.n_log < 3)
+        return fail(std::string(who) + ": the trimmed objective needs at least 3 logged cycles (the first and the last are dropped)");
+    s.stop = p.stop = o.stop = stop_dev;
+    o.summary = summary_dev, o.objective = objective_dev, o.E = E, o.n = kPreciseSummary;
+    hipStream_t st = (hipStream_t)stream;
+    launch_scan(s, st);
+    if (launch_precise(p, st)) return 1;
     hipLaunchKernelGGL(replay_objective_kernel, dim3((unsigned)((E + 63) / 64)), dim3(64), 0, st, o);
     HIP_TRY(hipGetLastError());
     return 0;

@@ -129,6 +129,10 @@ SIGNATURES = {
     "wtk_replay_yolo_track": (_i32, [_pcfg, _i32, _vp, _vp, _vp, _vp]),
     "wtk_boxes_scratch_bytes": (_i64, [_i32, _i32, _i32]),
     "wtk_boxes": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "wtk_replay_precise_scratch_doubles": (_i64, [_i32, _i64]),
+    "wtk_replay_precise": (_i32, [_pcfg, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _f64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "wtk_replay_precise_objective": (_i32, [_pcfg, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _f64, _i32, _vp, _vp,
+                                            _i64, _i32, _vp, _vp, _vp]),
 }
 SYMBOLS = list(SIGNATURES)  # every symbol include/wtk_hip.h declares
 
@@ -480,6 +484,35 @@ def replay_objective(cfg: _ReplayConfig, kind: int, E: int, n_cycles: int, track
     _check(load().wtk_replay_objective(C.byref(cfg) if cfg is not None else None, kind, E, n_cycles, _ptr(track_dev), n_track, _ptr(a_dev), _ptr(b_dev),
                                        _ptr(valid_dev), _ptr(share_dev), _ptr(pos_dev), _ptr(move_dev), _ptr(summary_dev), _ptr(scratch_dev), scratch_doubles,
                                        objective, _ptr(objective_dev), _ptr(stop_dev), C.c_void_p(stream)), "wtk_replay_objective")
+
+
+REPLAY_PRECISE_SUMMARY_DOUBLES = 6
+REPLAY_PRECISE_OBJECTIVES = {"trimmed_precise_error": 0, "precise_error": 1, "precise_non_perfect": 2}  # WTK_REPLAY_POBJ_*
+
+
+def replay_precise_scratch_doubles(E: int, R: int) -> int:
+    return int(load().wtk_replay_precise_scratch_doubles(E, R))
+
+
+def replay_precise(cfg: _ReplayConfig, E: int, n_cycles: int, track_dev, n_track: int, share_dev, pos_dev, move_dev, frames_dev, n_frames: int, H: int, W: int,
+                   bg_dev, diff_thresh: float, max_crop_px: int, err_dev, counts_dev, summary_dev, scratch_dev, scratch_doubles: int, stop_dev=None,
+                   stream: int = 0):
+    """The precise error of every (experiment, logged frame) pair of a scan and its per-experiment summaries (wtk_replay_precise): frames_dev uint8
+    [n_frames, H, W], bg_dev uint8 [H, W]; err_dev float64 [E, R] and counts_dev int32 [E, R, 2] or None."""
+    _check(load().wtk_replay_precise(C.byref(cfg) if cfg is not None else None, E, n_cycles, _ptr(track_dev), n_track, _ptr(share_dev), _ptr(pos_dev),
+                                     _ptr(move_dev), _ptr(frames_dev), n_frames, H, W, _ptr(bg_dev), float(diff_thresh), int(max_crop_px), _ptr(err_dev),
+                                     _ptr(counts_dev), _ptr(summary_dev), _ptr(scratch_dev), scratch_doubles, _ptr(stop_dev), C.c_void_p(stream)),
+           "wtk_replay_precise")
+
+
+def replay_precise_objective(cfg: _ReplayConfig, kind: int, E: int, n_cycles: int, track_dev, n_track: int, a_dev, b_dev, valid_dev, share_dev, pos_dev,
+                             move_dev, frames_dev, n_frames: int, H: int, W: int, bg_dev, diff_thresh: float, max_crop_px: int, summary_dev, scratch_dev,
+                             scratch_doubles: int, objective: int, objective_dev, stop_dev=None, stream: int = 0):
+    """objective_dev[e] = the chosen precise-error figure of experiment e (wtk_replay_precise_objective): scan, precise and one division."""
+    _check(load().wtk_replay_precise_objective(C.byref(cfg) if cfg is not None else None, kind, E, n_cycles, _ptr(track_dev), n_track, _ptr(a_dev),
+                                               _ptr(b_dev), _ptr(valid_dev), _ptr(share_dev), _ptr(pos_dev), _ptr(move_dev), _ptr(frames_dev), n_frames, H, W,
+                                               _ptr(bg_dev), float(diff_thresh), int(max_crop_px), _ptr(summary_dev), _ptr(scratch_dev), scratch_doubles,
+                                               objective, _ptr(objective_dev), _ptr(stop_dev), C.c_void_p(stream)), "wtk_replay_precise_objective")
 
 
 def replay_yolo_step(cfg: _ReplayConfig, n_cycles: int, c: int, xywh_dev, share_dev, pos_dev, move_dev, stream: int = 0):

@@ -18,6 +18,15 @@ The closed-loop error is also the objective of a weight search (DESIGN.md sectio
     rp.objective(t)                                                     # device float64 [P], no synchronisation
     best = rp.optimize_polyfit(2, [-9, -6, -3, 0, 2, 4], start=[open_loop.weights])
 
+With the experiment's frames attached, the same calls give the reference's analysis metric, the precise error (ErrorCalculator.calculate_precise: the
+share of the worm's segmented pixels outside the microscope view), for the whole population: the segmented mask of a frame is built
+once, as a summed-area table in LDS, and every experiment is answered with two rectangle sums.
+
+    rp.attach_frames(device_frames, background, diff_thresh=20)        # CUDA uint8 [F, H, W], F >= n_rows; row r is frame r
+    res = rp.run(t, precise=True, per_row_errors=True)
+    res.precise_summary.trimmed_mean_precise_error                      # [E]; res.precise_error [E, R], res.precise_counts [E, R, 2]
+    rp.objective(t, "trimmed_precise_error")                            # and optimize_polyfit(..., objective="trimmed_precise_error")
+
 The YOLO controller's targets depend on the camera view, so its loop cannot be a scan over precomputed targets: `YoloReplay` enqueues the detector's
 single-frame call and a small control kernel per cycle, all on one stream, and the log's detections afterwards in batches:
 
@@ -45,6 +54,8 @@ from .sim import LOG_COLUMNS, ExperimentConfig, TimingConfig
 
 KINDS = {"csv": hip.REPLAY_CSV, "optimal": hip.REPLAY_OPTIMAL, "polyfit": hip.REPLAY_POLYFIT, "mlp": hip.REPLAY_MLP}
 OBJECTIVES = hip.REPLAY_OBJECTIVES  # name -> WTK_REPLAY_OBJ_*; each is the Summary property of the same name prefixed with `mean_` / `trimmed_mean_`
+# name -> WTK_REPLAY_POBJ_*: PreciseSummary.trimmed_mean_precise_error, .mean_precise_error, .non_perfect; they need attach_frames
+PRECISE_OBJECTIVES = hip.REPLAY_PRECISE_OBJECTIVES
 
 
 def polyfit_classes(track: np.ndarray, cycle_frame_num: int, n_cycles: int, sample_times) -> tuple:
@@ -160,9 +171,38 @@ class Summary:
         return self.mse_error_sum / self.rows
 
 
+@dataclass
+class PreciseSummary:
+    """Per-experiment figures of the precise error ([E] arrays).  Rows whose logged worm box is illegal (a missed detection, no area inside the frame)
+    have no value: they are counted in `nan_rows` and enter no sum, as in pandas' mean over DataAnalyzer's precise_error column.  `trimmed`: as Summary."""
+
+    precise_error_sum: np.ndarray
+    rows: np.ndarray  # rows with a value
+    trimmed_precise_error_sum: np.ndarray
+    trimmed_rows: np.ndarray
+    non_perfect_rows: np.ndarray  # rows with precise_error > 1e-7
+    nan_rows: np.ndarray
+
+    @property
+    def mean_precise_error(self) -> np.ndarray:
+        return self.precise_error_sum / self.rows
+
+    @property
+    def trimmed_mean_precise_error(self) -> np.ndarray:
+        return self.trimmed_precise_error_sum / self.trimmed_rows
+
+    @property
+    def non_perfect(self) -> np.ndarray:
+        return self.non_perfect_rows / self.rows
+
+
 class ReplayResult:
     """moves, positions [E, C, 2] int32 (the move of cycle c and the platform position at its start); summary; bbox_error / mse_error [E, R] float64 when
-    requested; the full log rows of the experiments named in `rows`; `detections` (YoloReplay only): device float32 [R, 4] xywh in view pixels."""
+    requested; the full log rows of the experiments named in `rows`; `detections` (YoloReplay only): device float32 [R, 4] xywh in view pixels.
+    After `Replay.run(precise=True)`: `precise_summary`, and with per-row errors `precise_error` [E, R] float64 (NaN = no value) and `precise_counts`
+    [E, R, 2] int32 (foreground pixels of the worm crop, those of them inside the microscope view); None otherwise."""
+
+    precise_summary = precise_error = precise_counts = None
 
     def __init__(self, moves, positions, summary, decision_frames, row_ids, row_data, bbox_error, mse_error, detections=None):
         self.moves, self.positions, self.summary, self.decision_frames = moves, positions, summary, decision_frames
@@ -226,6 +266,37 @@ class Replay:
         self._track_f32 = None
         self._classes = {}  # sorted sample times -> (cycle_class, class_mask) on the device
         self._last_times = None  # of the last polyfit_population / optimize_polyfit call (to_config's default)
+        self._frames = self._background = None  # attach_frames
+        self._diff_thresh = 20.0
+
+    def attach_frames(self, frames, background, diff_thresh: float = 20) -> None:
+        """The experiment's frames, for the precise error (`run(precise=True)`, the precise objectives): `frames` a contiguous CUDA uint8 [F, H, W]
+        tensor, read in place (row r of the log is frame r, so F >= n_rows; (H, W) is this Replay's frame_shape); `background` [H, W], host or device,
+        uint8 (evaluation.background) or floating with values in [0, 256), which are truncated as the reference's astype(int32) truncates them; a
+        pixel is segmented where |frame - background| > diff_thresh (DataAnalyzer.calc_precise_error's default: 20)."""
+        import torch
+
+        check_device_frames(frames)
+        if frames.dim() != 3:
+            raise ValueError("the precise error takes gray frames [F, H, W] only")
+        F, H, W = (int(v) for v in frames.shape)
+        if (H, W) != tuple(self.frame_shape):
+            raise ValueError(f"the frames are {H} x {W}, this Replay's frame is {self.frame_shape[0]} x {self.frame_shape[1]}")
+        if F < self.n_rows:
+            raise ValueError(f"{F} frames, the log has {self.n_rows} rows (row r is frame r)")
+        if H * W > 2 ** 30:
+            raise ValueError("frames of at most 2^30 pixels")
+        bg = background if hasattr(background, "dim") else torch.from_numpy(np.ascontiguousarray(background))
+        if tuple(bg.shape) != (H, W):
+            raise ValueError(f"the background must be [{H}, {W}], got {tuple(bg.shape)}")
+        if bg.dtype != torch.uint8:
+            if not bg.dtype.is_floating_point:
+                raise ValueError("the background must be uint8 or floating")
+            bg = bg.to(torch.float64).trunc()
+            if not bool(((bg >= 0) & (bg <= 255)).all()):
+                raise ValueError("a floating background must hold values in [0, 256)")
+            bg = bg.to(torch.uint8)
+        self._frames, self._background, self._diff_thresh = frames, bg.to(frames.device).contiguous(), float(diff_thresh)
 
     # ------------------------------------------------------------------ targets
     def _stream(self) -> int:
@@ -340,11 +411,19 @@ class Replay:
         return tg
 
     def _objective_kind(self, kind: str) -> int:
-        if kind not in OBJECTIVES:
-            raise ValueError(f"unknown objective {kind!r}: one of {sorted(OBJECTIVES)}")
-        if kind == "trimmed_bbox_error" and self.n_log < 3:
+        """The WTK_REPLAY_OBJ_* value of a name of OBJECTIVES, the WTK_REPLAY_POBJ_* value of a name of PRECISE_OBJECTIVES."""
+        if kind not in OBJECTIVES and kind not in PRECISE_OBJECTIVES:
+            raise ValueError(f"unknown objective {kind!r}: one of {sorted(OBJECTIVES)}, or with attach_frames one of {sorted(PRECISE_OBJECTIVES)}")
+        if kind in ("trimmed_bbox_error", "trimmed_precise_error") and self.n_log < 3:
             raise ValueError(f"the trimmed objective drops the first and the last logged cycle: the experiment logs {self.n_log}, at least 3 are needed")
+        if kind in PRECISE_OBJECTIVES:
+            self._need_frames()
+            return PRECISE_OBJECTIVES[kind]
         return OBJECTIVES[kind]
+
+    def _need_frames(self) -> None:
+        if self._frames is None:
+            raise ValueError("the precise error needs the experiment's frames: call attach_frames(frames, background) first")
 
     def _objective_buffers(self, E: int) -> dict:
         import torch
@@ -354,7 +433,21 @@ class Replay:
                     summary=torch.empty((E, hip.REPLAY_SUMMARY_DOUBLES), dtype=torch.float64, device=dev),
                     scratch=torch.empty((max(1, hip.replay_scratch_doubles(E, self.n_rows)),), dtype=torch.float64, device=dev))
 
+    def _precise_buffers(self, E: int) -> dict:
+        import torch
+
+        return dict(summary=torch.empty((E, hip.REPLAY_PRECISE_SUMMARY_DOUBLES), dtype=torch.float64, device=self._dev),
+                    scratch=torch.empty((max(1, hip.replay_precise_scratch_doubles(E, self.n_rows)),), dtype=torch.float64, device=self._dev))
+
     def _enqueue_objective(self, targets: Targets, kind: int, buf: dict, out, stop_dev=None):
+        """`kind`: _objective_kind's value; a precise objective where `buf` holds the precise buffers (_all_objective_buffers)."""
+        if "precise" in buf:
+            fr, pb = self._frames, buf["precise"]
+            hip.replay_precise_objective(self._cfg, KINDS[targets.kind], int(targets.E), self.n_cycles, self.track, self.n_track, targets.a, targets.b,
+                                         targets.valid, self._share, buf["pos"], buf["move"], fr, int(fr.shape[0]), int(fr.shape[1]), int(fr.shape[2]),
+                                         self._background, self._diff_thresh, 0, pb["summary"], pb["scratch"], pb["scratch"].numel(), kind, out, stop_dev,
+                                         stream=self._stream())
+            return
         hip.replay_objective(self._cfg, KINDS[targets.kind], int(targets.E), self.n_cycles, self.track, self.n_track, targets.a, targets.b, targets.valid,
                              self._share, buf["pos"], buf["move"], buf["summary"], buf["scratch"], buf["scratch"].numel(), kind, out, stop_dev,
                              stream=self._stream())
@@ -372,14 +465,21 @@ class Replay:
     def objective(self, targets: Targets, kind: str = "trimmed_bbox_error"):
         """The closed-loop error of every experiment of `targets` as a device float64 [E] tensor, enqueued on the current torch stream (no synchronisation):
         "trimmed_bbox_error" = Summary.trimmed_mean_bbox_error, "bbox_error" = mean_bbox_error, "mse_error" = mean_mse_error, "non_perfect" = non_perfect
-        of `run(targets)`, bit for bit (the same sums, the same float64 division; 0 / 0 is NaN)."""
+        of `run(targets)`, bit for bit (the same sums, the same float64 division; 0 / 0 is NaN).  With attached frames also "trimmed_precise_error" =
+        PreciseSummary.trimmed_mean_precise_error, "precise_error" = mean_precise_error, "precise_non_perfect" = non_perfect of `run(targets, precise=True)`."""
         import torch
 
         E, k = self._check_targets(targets), self._objective_kind(kind)
         with torch.cuda.device(self._dev):
             out = torch.empty((E,), dtype=torch.float64, device=self._dev)
-            self._enqueue_objective(targets, k, self._objective_buffers(E), out)
+            self._enqueue_objective(targets, k, self._all_objective_buffers(E, kind in PRECISE_OBJECTIVES), out)
         return out
+
+    def _all_objective_buffers(self, E: int, precise: bool) -> dict:
+        buf = self._objective_buffers(E)
+        if precise:
+            buf["precise"] = self._precise_buffers(E)
+        return buf
 
     def optimize_polyfit(self, degree: int, sample_times, objective: str = "trimmed_bbox_error", pop_size: int = 100, c1: float = 2.05, c2: float = 2.05,
                          max_epoch: int = 300, max_early_stop: int = 100, seed: int = 0, lb: float = 0.0, ub: float = 1.0, start=None,
@@ -407,7 +507,7 @@ class Replay:
             if not (np.isfinite(start).all() and (start >= lb).all() and (start <= ub).all()):
                 raise ValueError(f"start must lie inside [{lb}, {ub}]")
         tg, fit_scratch, classes = self._population_buffers(P, st, degree, torch.zeros)
-        buf = self._objective_buffers(P)
+        buf = self._all_objective_buffers(P, objective in PRECISE_OBJECTIVES)
 
         def enqueue_error(pos, value, ctrl):
             self._enqueue_population(pos, degree, st, classes, tg.a, tg.valid, fit_scratch, stop_dev=ctrl)
@@ -423,9 +523,15 @@ class Replay:
         return polyfit_config(degree, st, weights)
 
     # ------------------------------------------------------------------ the loop
-    def run(self, targets: Targets, rows: Sequence[int] = (0,), per_row_errors: bool = False) -> ReplayResult:
-        """Replay the E experiments of `targets`.  `rows`: the experiments whose full log rows are kept (16 doubles per row each)."""
+    def run(self, targets: Targets, rows: Sequence[int] = (0,), per_row_errors: bool = False, precise: bool = False,
+            _max_crop_px: int = 0) -> ReplayResult:
+        """Replay the E experiments of `targets`.  `rows`: the experiments whose full log rows are kept (16 doubles per row each).  `precise`: also the
+        precise error of every experiment on the attached frames (`precise_summary`; with `per_row_errors` `precise_error` and `precise_counts`).
+        `_max_crop_px` (tests): the table limit of wtk_replay_precise, 0 = the default; results do not depend on it."""
         import torch
+
+        if precise:
+            self._need_frames()
 
         E, C, R = self._check_targets(targets), self.n_cycles, self.n_rows
         row_ids = sorted({int(e) for e in rows})
@@ -445,12 +551,28 @@ class Replay:
             mse = torch.empty((E, R), dtype=f64, device=dev) if per_row_errors else None
             hip.replay_rows(self._cfg, E, C, self.track, self.n_track, self._share, pos, move, slots, len(row_ids), row_data, bbox, mse, summary, scratch,
                             scratch.numel(), stream=stream)
+            if precise:
+                fr, pb = self._frames, self._precise_buffers(E)
+                perr = torch.empty((E, R), dtype=f64, device=dev) if per_row_errors else None
+                pcounts = torch.empty((E, R, 2), dtype=torch.int32, device=dev) if per_row_errors else None
+                hip.replay_precise(self._cfg, E, C, self.track, self.n_track, self._share, pos, move, fr, int(fr.shape[0]), int(fr.shape[1]), int(fr.shape[2]),
+                                   self._background, self._diff_thresh, int(_max_crop_px), perr, pcounts, pb["summary"], pb["scratch"], pb["scratch"].numel(),
+                                   stream=stream)
             torch.cuda.current_stream(dev).synchronize()  # the one host synchronisation
-            return _result_of(self.geometry, pos, move, summary, row_ids, row_data, bbox, mse)
+            res = _result_of(self.geometry, pos, move, summary, row_ids, row_data, bbox, mse)
+            if precise:
+                res.precise_summary = _precise_summary_of(pb["summary"].cpu().numpy())
+                if per_row_errors:
+                    res.precise_error, res.precise_counts = perr.cpu().numpy(), pcounts.cpu().numpy()
+            return res
 
 
 def _summary_of(s: np.ndarray) -> Summary:
     return Summary(s[:, 0].copy(), s[:, 1].astype(np.int64), s[:, 2].copy(), s[:, 3].astype(np.int64), s[:, 4].astype(np.int64), s[:, 5].copy())
+
+
+def _precise_summary_of(s: np.ndarray) -> PreciseSummary:
+    return PreciseSummary(s[:, 0].copy(), s[:, 1].astype(np.int64), s[:, 2].copy(), s[:, 3].astype(np.int64), s[:, 4].astype(np.int64), s[:, 5].astype(np.int64))
 
 
 class YoloReplay:
