@@ -629,6 +629,97 @@ int wtk_boxes(const uint8_t *frames_dev, int32_t n_frames, int32_t H, int32_t W,
               void *scratch, int64_t scratch_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The reference's analysis of a replayed population (csrc/replay_analysis.hip): DataAnalyzer.initialize / clean /
+ * change_unit / describe / calc_anomalies / print_stats (eval/data_analyzer.py:54-107, 121-159, 178-213, 326-416) and the Plotter's
+ * per-cycle and per-cycle-step aggregates (eval/plotter.py:164-168, 203-213, 237-245) of every experiment of a scan, from the scan's
+ * pos_dev / move_dev.  Nothing of size [E][R][columns] is stored: a row's columns are recomputed where they are consumed, with the device
+ * functions wtk_replay_rows calls.  Everything enqueues on `stream`; nothing synchronises or allocates.
+ *
+ * Columns (WTK_ANALYSIS_COL_*) of logged row r of an experiment, float64 in the reference's order of operations: frame = time = r,
+ * cycle, cycle_step = r mod L, the row's 14 values plt_x .. wrm_h, wrm_center = wrm + size / 2 and mic_center likewise, wrm_speed_x =
+ * (wrm_center_x[r] - wrm_center_x[r - period]) / period (NaN for r < period; over the whole log, kept or not), wrm_speed = sqrt(sx sx +
+ * sy sy), worm_deviation_x = wrm_center_x - mic_center_x, worm_deviation = sqrt(dx dx + dy dy), bbox_error as wtk_replay_rows computes
+ * it.  Then every column is rounded as DataFrame.round(5) rounds: rint(v 1e5) / 1e5, half to even, non-finite values unchanged.
+ * precise_error is precise_pair_dev[r][e] unrounded ([R][E]: the first R E doubles of wtk_replay_precise's scratch_dev; NaN = no value).
+ * clean, on the rounded values and in this order: imaging_only keeps the rows of the imaging phase; use_bounds keeps a row where
+ * (wrm_x .. wrm_h all finite and wrm_x >= bounds[0], wrm_x + wrm_w <= bounds[2], wrm_y >= bounds[1], wrm_y + wrm_h <= bounds[3]) or the
+ * microscope box passes the same test (what the reference's in-place mask update makes of its has_pred rule); trim_cycles then drops
+ * cycle 0 and the LARGEST cycle among the rows that survived the first two (per experiment).  change_unit: the kept, rounded values
+ * times time_factor (time), dist_factor (positions, sizes, centres, deviations), speed_factor (speeds); errors, frame, cycle and
+ * cycle_step unchanged.  The caller passes (1, 1, 1) for unit "frame" and (ms_per_frame / 1000, mm_per_px 1000, their quotient) for "sec".
+ *
+ * Outputs (all nullable), over the kept rows of experiment e and the n_cols columns named in columns_host:
+ *   describe_dev [E][n_cols][5 + Q]   count of non-NaN values, mean, std (ddof 1, two passes about the computed mean), min, the Q
+ *       percentiles of percentiles_host (numpy's `linear`: pos = q (n - 1), lo = floor(pos), t = pos - lo; a + (b - a) t for t < 0.5,
+ *       else b - (b - a)(1 - t)), max.  Count 0: NaN but for the count; count 1: std NaN.
+ *   cycle_max_dev, cycle_mean_dev [E][n_log][n_cols]   per logged cycle, NaN values skipped, NaN where the cycle keeps none.
+ *   step_quantiles_dev [E][L][n_cols][Q], step_count_dev [E][L][n_cols] int32   the same percentiles and the count per cycle_step.
+ *   anomaly_counts_dev [E][7] int64   calc_anomalies on the unit-changed values: rows with wrm_speed >= min_speed, bbox_error >=
+ *       min_bbox_error, worm_deviation >= min_dist_error, wrm_w >= min_width, wrm_h >= min_height, (no_preds and a non-finite worm box),
+ *       any of them.  Comparisons with NaN are false; +inf switches a threshold off.  anomaly_mask_dev [E][R] uint8: bit k = kind k, 0 on
+ *       rows that are not kept.
+ *   stats_dev [E][4] int64   print_stats: removed rows, kept rows with a NaN in the worm box, distinct cycles kept, kept rows with
+ *       bbox_error > 1e-7.
+ * Sums have a fixed order that depends on R alone (thread t of 512 adds the segment's rows t, t + 512, ... in order, then a binary
+ * tree): an experiment gives the same bits alone and in any population.  Order statistics are exact: segments (the experiment, or one
+ * cycle step of it) of up to max_lds_rows rows are sorted in LDS, longer ones go through a radix select over recomputed values; both
+ * return the same bits.  max_lds_rows = 0: the default, 19960 (160 KiB of LDS); larger values mean the default.
+ * scratch_dev: wtk_replay_analysis_scratch_doubles(E, R, n_cols, Q) doubles (-1: negative sizes).
+ * Refused (error code, nothing launched): what wtk_replay_rows refuses of the geometry, a required pointer that is null, n_cols outside
+ * 1..WTK_ANALYSIS_MAX_COLUMNS, Q outside 0..WTK_ANALYSIS_MAX_PERCENTILES, an unknown column, a percentile outside [0, 1], period < 1,
+ * the precise_error column without precise_pair_dev, max_lds_rows < 0, scratch too small.
+ * ------------------------------------------------------------------------------------------ */
+#define WTK_ANALYSIS_COL_FRAME 0
+#define WTK_ANALYSIS_COL_CYCLE 1
+#define WTK_ANALYSIS_COL_PLT_X 2
+#define WTK_ANALYSIS_COL_PLT_Y 3
+#define WTK_ANALYSIS_COL_CAM_X 4
+#define WTK_ANALYSIS_COL_CAM_Y 5
+#define WTK_ANALYSIS_COL_CAM_W 6
+#define WTK_ANALYSIS_COL_CAM_H 7
+#define WTK_ANALYSIS_COL_MIC_X 8
+#define WTK_ANALYSIS_COL_MIC_Y 9
+#define WTK_ANALYSIS_COL_MIC_W 10
+#define WTK_ANALYSIS_COL_MIC_H 11
+#define WTK_ANALYSIS_COL_WRM_X 12
+#define WTK_ANALYSIS_COL_WRM_Y 13
+#define WTK_ANALYSIS_COL_WRM_W 14
+#define WTK_ANALYSIS_COL_WRM_H 15
+#define WTK_ANALYSIS_COL_TIME 16
+#define WTK_ANALYSIS_COL_CYCLE_STEP 17
+#define WTK_ANALYSIS_COL_WRM_CENTER_X 18
+#define WTK_ANALYSIS_COL_WRM_CENTER_Y 19
+#define WTK_ANALYSIS_COL_MIC_CENTER_X 20
+#define WTK_ANALYSIS_COL_MIC_CENTER_Y 21
+#define WTK_ANALYSIS_COL_WRM_SPEED_X 22
+#define WTK_ANALYSIS_COL_WRM_SPEED_Y 23
+#define WTK_ANALYSIS_COL_WRM_SPEED 24
+#define WTK_ANALYSIS_COL_WORM_DEVIATION_X 25
+#define WTK_ANALYSIS_COL_WORM_DEVIATION_Y 26
+#define WTK_ANALYSIS_COL_WORM_DEVIATION 27
+#define WTK_ANALYSIS_COL_BBOX_ERROR 28
+#define WTK_ANALYSIS_COL_PRECISE_ERROR 29
+#define WTK_ANALYSIS_N_COLUMNS 30
+#define WTK_ANALYSIS_MAX_COLUMNS 32
+#define WTK_ANALYSIS_MAX_PERCENTILES 16
+typedef struct wtk_replay_analysis_config {
+    double bounds[4];          /* x0, y0, x1, y1 (read where use_bounds != 0) */
+    double time_factor, dist_factor, speed_factor; /* change_unit; 1, 1, 1 for unit "frame" */
+    double min_speed, min_bbox_error, min_dist_error, min_width, min_height; /* calc_anomalies; +inf = off */
+    int32_t period;            /* frames the speed looks back (initialize) */
+    int32_t imaging_only, use_bounds, trim_cycles; /* clean */
+    int32_t no_preds;          /* calc_anomalies */
+    int32_t reserved;
+} wtk_replay_analysis_config;
+int64_t wtk_replay_analysis_scratch_doubles(int32_t E, int64_t R, int32_t n_cols, int32_t Q);
+int wtk_replay_analyze(const wtk_replay_config *cfg, const wtk_replay_analysis_config *acfg, int32_t E, int32_t n_cycles,
+                       const double *track_dev, int32_t n_track, const double *share_dev, const int32_t *pos_dev, const int32_t *move_dev,
+                       const double *precise_pair_dev, const int32_t *columns_host, int32_t n_cols, const double *percentiles_host,
+                       int32_t Q, int32_t max_lds_rows, double *describe_dev, double *cycle_max_dev, double *cycle_mean_dev,
+                       double *step_quantiles_dev, int32_t *step_count_dev, int64_t *anomaly_counts_dev, uint8_t *anomaly_mask_dev,
+                       int64_t *stats_dev, double *scratch_dev, int64_t scratch_doubles, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * The precise tracking error of a replayed population (csrc/replay.hip): ErrorCalculator.calculate_precise
  * (eval/error_calculator.py:64-160) of every (experiment, logged frame) pair of a scan, with wtk_precise_error's counts and bits for the
  * row wtk_replay_rows logs.  frames_dev [n_frames][H][W] gray with n_frames >= R: row r is frame r.  bg_dev [H][W].  A pixel is

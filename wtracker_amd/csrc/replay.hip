@@ -32,6 +32,7 @@
 #include "wtk_internal.h"
 #include "eval_device.h"
 #include "polyfit_solve.h"
+#include "replay_device.h"
 
 #include <algorithm>
 #include <cmath>
@@ -51,11 +52,6 @@ constexpr int kPreciseSummary = WTK_REPLAY_PRECISE_SUMMARY_DOUBLES;
 constexpr int kPreciseLdsBytes = 160 * 1024;            // the CU's LDS: one workgroup per CU takes all of it at the default limit
 constexpr int kPreciseMaxCells = kPreciseLdsBytes / 4;  // uint32 cells of the largest table
 
-struct Geometry {
-    int L, I, M, P;
-    int cam_w, cam_h, mic_w, mic_h;
-    int x_max, y_max; // frame_w - 1, frame_h - 1: the clamp of the platform position
-};
 
 struct ScanArgs {
     Geometry g;
@@ -177,55 +173,12 @@ struct PopRecordView {
     __device__ __forceinline__ double w(int j) const { return r[(pop_off_w(n_times, K) + j) * P]; }
 };
 
-// one step of SineMotorController.step + ViewController.move_position on one axis
-__device__ __forceinline__ void motor_axis(double share, double mv, double &carry, int &pos, int pos_max) {
-    const double want = share * mv + carry;
-    const double took = rint(want); // round half to even: Python's round on a float
-    carry = want - took;
-    pos = (int)fmin(fmax((double)pos + took, 0.0), (double)pos_max);
-}
-
-// `steps` motor steps of the move (mx, my) from (px, py), the carry starting at zero: what a cycle's moving phase does to the platform (steps = M) and what
-// has happened to it before a frame of that phase (steps < M).  The ONE statement of the motor: the scan, the rows and the YOLO loop's kernels all call it.
-__device__ __forceinline__ void motor_steps(const Geometry &g, const double *share, int steps, double mx, double my, int &px, int &py) {
-    double cx = 0.0, cy = 0.0;
-    for (int k = 0; k < steps; ++k) {
-        const double sh = share[k];
-        motor_axis(sh, mx, cx, px, g.x_max);
-        motor_axis(sh, my, cy, py, g.y_max);
-    }
-}
-
-// the platform position at the camera picture of step `step` of a cycle, from the cycle's start position and move ([C][E][2] entry ce)
-__device__ __forceinline__ void frame_position(const Geometry &g, const double *share, const int *pos, const int *move, long long ce, int step, int &px, int &py) {
-    px = pos[2 * ce], py = pos[2 * ce + 1];
-    const int done = step <= g.I ? 0 : (step - g.I > g.M ? g.M : step - g.I); // motor steps taken before this frame's camera picture
-    if (done > 0) motor_steps(g, share, done, (double)move[2 * ce], (double)move[2 * ce + 1], px, py);
-}
-
 // the controller's move on one axis from the camera corner; a non-finite result is no move, a huge one saturates at +-2^30
 __device__ __forceinline__ double finish_move(double v) {
     if (!isfinite(v)) return 0.0;
     return fmin(fmax(rint(v), -kMoveMax), kMoveMax);
 }
 
-// The boxes of a log row from the platform position at its camera picture: camera and microscope corners, and the logged worm box, which is the track's
-// row made camera-relative (CsvController.predict) and absolute again (LoggingController); a non-finite row is logged as zeros.  (x - cam) + cam is not
-// always x: the rows kernel and the precise kernel both take the box from here.
-struct RowBoxes {
-    double cam_x, cam_y, mic_x, mic_y, mic_w, mic_h;
-    double wx, wy, ww, wh;
-};
-
-__device__ __forceinline__ RowBoxes row_boxes(const Geometry &g, const double *track_row, int px, int py) {
-    RowBoxes b;
-    b.cam_x = (double)(px - g.cam_w / 2), b.cam_y = (double)(py - g.cam_h / 2);
-    b.mic_x = (double)(px - g.mic_w / 2), b.mic_y = (double)(py - g.mic_h / 2);
-    b.mic_w = (double)g.mic_w, b.mic_h = (double)g.mic_h;
-    b.wx = (track_row[0] - b.cam_x) + b.cam_x, b.wy = (track_row[1] - b.cam_y) + b.cam_y, b.ww = track_row[2], b.wh = track_row[3];
-    if (!(isfinite(b.wx) && isfinite(b.wy) && isfinite(b.ww) && isfinite(b.wh))) b.wx = b.wy = b.ww = b.wh = 0.0;
-    return b;
-}
 
 __global__ __launch_bounds__(kScanThreads) void replay_scan_kernel(const ScanArgs a) {
     if (a.stop && *a.stop) return;
@@ -286,12 +239,7 @@ __global__ __launch_bounds__(kRowThreads) void replay_rows_kernel(const RowsArgs
         const RowBoxes b = row_boxes(g, a.track + 4 * r, px, py);
         const double cam_x = b.cam_x, cam_y = b.cam_y, mic_x = b.mic_x, mic_y = b.mic_y, mic_w = b.mic_w, mic_h = b.mic_h;
         const double wx = b.wx, wy = b.wy, ww = b.ww, wh = b.wh;
-        // ErrorCalculator.calculate_bbox_error
-        const double il = fmax(wx, mic_x), it = fmax(wy, mic_y);
-        const double ir = fmin(wx + ww, mic_x + mic_w), ib = fmin(wy + wh, mic_y + mic_h);
-        const double iw = fmax(0.0, ir - il), ih = fmax(0.0, ib - it);
-        const double inter = iw * ih, total = ww * wh;
-        const double err = total == 0.0 ? 0.0 : 1.0 - inter / total;
+        const double err = row_bbox_error(b); // ErrorCalculator.calculate_bbox_error
         // ErrorCalculator.calculate_mse_error: mean over the two axes of the squared centre distance
         const double dx = (wx + ww / 2) - (mic_x + mic_w / 2), dy = (wy + wh / 2) - (mic_y + mic_h / 2);
         const double mse = (dx * dx + dy * dy) / 2;
@@ -654,39 +602,13 @@ __global__ __launch_bounds__(64) void replay_polyfit_eval_kernel(const PopArgs a
     a.valid[cp] = 1;
 }
 
-// the refusals both entry points share; fills the geometry and the counts derived from it
-int check_config(const char *who, const wtk_replay_config *cfg, int32_t kind, int32_t E, int32_t n_cycles, int32_t n_track, Geometry &g, int &n_log) {
-    const std::string w(who);
-    if (!cfg) return fail(w + ": null argument");
-    if (kind < WTK_REPLAY_CSV || kind > WTK_REPLAY_MLP) return fail(w + ": unknown kind");
-    if (E < 1) return fail(w + ": at least one experiment (E >= 1)");
-    if (cfg->moving_frame_num < 1) return fail(w + ": moving_frame_num must be at least 1");
-    if (cfg->imaging_frame_num < 1) return fail(w + ": imaging_frame_num must be at least 1");
-    if (cfg->pred_frame_num > cfg->imaging_frame_num) return fail(w + ": pred_frame_num lies beyond imaging_frame_num");
-    if (cfg->pred_frame_num < (kind == WTK_REPLAY_CSV ? 1 : 0)) return fail(w + ": pred_frame_num must be at least 1 for the CSV kind (the controller has not seen the decision frame yet)");
-    if (cfg->num_frames < 1 || n_track < 0) return fail(w + ": negative size");
-    if (cfg->cam_w < cfg->mic_w || cfg->cam_h < cfg->mic_h) return fail(w + ": the camera is smaller than the microscope");
-    if (cfg->mic_w < 0 || cfg->mic_h < 0) return fail(w + ": negative microscope size");
-    if (cfg->frame_w < 1 || cfg->frame_h < 1) return fail(w + ": empty frame");
-    const long long L = (long long)cfg->imaging_frame_num + cfg->moving_frame_num;
-    if (L > INT32_MAX) return fail(w + ": cycle too long");
-    n_log = (int)((cfg->num_frames - 1) / L); // the last cycle is never logged (its end never arrives)
-    if ((long long)n_log * L > n_track) return fail(w + ": the track is shorter than the logged rows");
-    if (n_cycles < 1 || n_cycles < n_log) return fail(w + ": n_cycles must cover every logged cycle (and be at least 1)");
-    if ((long long)(n_cycles - 1) * L + cfg->imaging_frame_num > (long long)cfg->num_frames - 1)
-        return fail(w + ": the decision frame of cycle n_cycles - 1 lies beyond the experiment's frames");
-    g.L = (int)L, g.I = cfg->imaging_frame_num, g.M = cfg->moving_frame_num, g.P = cfg->pred_frame_num;
-    g.cam_w = cfg->cam_w, g.cam_h = cfg->cam_h, g.mic_w = cfg->mic_w, g.mic_h = cfg->mic_h;
-    g.x_max = cfg->frame_w - 1, g.y_max = cfg->frame_h - 1;
-    return 0;
-}
 
 // checks and argument structs of the two steps, apart from their launches: wtk_replay_objective refuses before anything is enqueued
 int prepare_scan(const char *who, const wtk_replay_config *cfg, int32_t kind, int32_t E, int32_t n_cycles, const double *track_dev, int32_t n_track,
                  const double *a_dev, const double *b_dev, const int32_t *valid_dev, const double *share_dev, int32_t *pos_dev, int32_t *move_dev, ScanArgs &s) {
     const std::string w(who);
     int n_log = 0;
-    if (check_config(who, cfg, kind, E, n_cycles, n_track, s.g, n_log)) return 1;
+    if (replay_check_config(who, cfg, kind, E, n_cycles, n_track, s.g, n_log)) return 1;
     if (!track_dev || !share_dev || !pos_dev || !move_dev) return fail(w + ": null argument");
     if (kind != WTK_REPLAY_CSV && (!a_dev || !valid_dev)) return fail(w + ": null targets");
     if (kind == WTK_REPLAY_MLP && !b_dev) return fail(w + ": null origins (b_dev) for the MLP kind");
@@ -704,7 +626,7 @@ int prepare_rows(const char *who, const wtk_replay_config *cfg, int32_t E, int32
                  double *mse_err_dev, double *summary_dev, double *scratch_dev, int64_t scratch_doubles, RowsArgs &r) {
     const std::string w(who);
     int n_log = 0;
-    if (check_config(who, cfg, WTK_REPLAY_OPTIMAL, E, n_cycles, n_track, r.g, n_log)) return 1;
+    if (replay_check_config(who, cfg, WTK_REPLAY_OPTIMAL, E, n_cycles, n_track, r.g, n_log)) return 1;
     if (!track_dev || !share_dev || !pos_dev || !move_dev || !summary_dev || !scratch_dev) return fail(w + ": null argument");
     if ((row_slot_dev == nullptr) != (rows_dev == nullptr) || n_slots < 0 || (rows_dev && n_slots < 1))
         return fail(w + ": row_slot_dev, rows_dev and n_slots >= 1 go together");
@@ -797,7 +719,7 @@ int prepare_precise(const char *who, const wtk_replay_config *cfg, int32_t E, in
                     int64_t scratch_doubles, PreciseArgs &p) {
     const std::string w(who);
     int n_log = 0;
-    if (check_config(who, cfg, WTK_REPLAY_OPTIMAL, E, n_cycles, n_track, p.g, n_log)) return 1;
+    if (replay_check_config(who, cfg, WTK_REPLAY_OPTIMAL, E, n_cycles, n_track, p.g, n_log)) return 1;
     if (!track_dev || !share_dev || !pos_dev || !move_dev || !frames_dev || !bg_dev || !summary_dev || !scratch_dev) return fail(w + ": null argument");
     if (H != cfg->frame_h || W != cfg->frame_w) return fail(w + ": the frames' (H, W) differ from the config's frame");
     if ((long long)H * W > (1ll << 30)) return fail(w + ": frames must be H x W gray with H * W <= 2^30");
@@ -918,7 +840,7 @@ namespace {
 int check_yolo(const char *who, const wtk_replay_config *cfg, int32_t n_cycles, Geometry &g, long long &R) {
     int n_log = 0;
     // (the track these calls stand for is the detector's own output: it always has the R logged rows; pred_frame_num = 0 is the controller's oldest frame)
-    if (check_config(who, cfg, WTK_REPLAY_OPTIMAL, 1, n_cycles, INT32_MAX, g, n_log)) return 1;
+    if (replay_check_config(who, cfg, WTK_REPLAY_OPTIMAL, 1, n_cycles, INT32_MAX, g, n_log)) return 1;
     if (g.cam_w > 8192 || g.cam_h > 8192 || cfg->frame_w > 8192 || cfg->frame_h > 8192)
         return fail(std::string(who) + ": camera and frame sizes up to 8192 (the float32 sums of the log are exact in the rows' float64 round trip below 2^13)");
     R = (long long)n_log * g.L;

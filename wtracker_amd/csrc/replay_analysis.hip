@@ -1,0 +1,507 @@
+// The reference's analysis of a replayed population on the device: what DataAnalyzer.initialize / clean / change_unit / describe /
+// calc_anomalies / print_stats (wtracker/eval/data_analyzer.py:54-107, 121-159, 178-213, 326-416) and the Plotter's per-cycle and per-cycle-step
+// aggregates (wtracker/eval/plotter.py:164-168, 203-213, 237-245) compute from ONE log with pandas, for every experiment of a scan at once.
+//
+// Nothing of size [E][R][columns] is ever stored.  A row's columns are a few dozen flops away from the scan's pos / move (frame_position, row_boxes,
+// row_bbox_error: the functions the rows kernel calls), so every kernel recomputes the value where it consumes it:
+//   last     one block per experiment: the largest cycle number among the rows that survive imaging_only and bounds.  trim_cycles drops cycle 0 and THAT
+//            cycle (DataAnalyzer.clean takes data["cycle"].max() after the first two filters), so the mask of a row is final only once this is known.
+//   segment  the hot path: one workgroup per (experiment, column, segment), the segment being the whole experiment (describe) or one cycle step
+//            (the distributions of plot_cycle_error).  Count, mean and std (two passes, about the computed mean) in a FIXED order: thread t adds the
+//            segment's rows t, t + 512, ... in order, then a binary tree in LDS; the order depends on the row count alone, so an experiment gives the same
+//            bits alone and in any population.  Order statistics, two ways that return the same bits:
+//              sort    the kept non-NaN values as order-preserving 64-bit keys in dynamic LDS (up to 160 KiB: 19960 keys beside the tree's buffer), a
+//                      bitonic network in which every comparator sends the smaller key to the lower index: with the indices >= n imagined to hold
+//                      +infinity no comparator ever moves one of them, so leaving out the comparators that touch them sorts any n, a power of two or not.
+//                      Then min, max and every requested rank are reads.
+//              select  for segments longer than the LDS holds: a most-significant-digit radix select, 8 passes of 8 bits over the recomputed values,
+//                      all ranks (min, max, both neighbours of every percentile) at once, a 256-bin histogram per rank in static LDS (integer atomics:
+//                      the counts do not depend on the order of arrival).  It finds the key of each rank exactly.
+//            The way is chosen on the host from the segment's row count (an upper bound of the kept count), so it is uniform over a launch.
+//   cycle    one thread per (experiment, cycle, column): max and mean (rows in order) of the kept non-NaN values: groupby(["log_num", "cycle"]).
+//   flags    one block per experiment: calc_anomalies' six masks per kept row (bit flags, optionally written out), their counts, print_stats' figures.
+//            Integer counts only.
+// Every value is written with plain C++ stores.  Everything relies on -ffp-contract=off and on HIP's float64 sqrt and division being the correctly
+// rounded ones (they are without fast-math flags: OCML's sqrt refines the hardware estimate to the IEEE result).
+#include "wtk_internal.h"
+#include "replay_device.h"
+
+#include <algorithm>
+#include <cmath>
+
+using namespace wtk;
+
+namespace {
+
+constexpr int kAnaThreads = 512;
+constexpr int kAnaLdsBytes = 160 * 1024; // the CU's LDS: one workgroup per CU takes all of it at the default limit
+constexpr int kAnaHeaderWords = 8;       // 64-bit words in front of the tree's buffer: word 0 holds the key counter
+constexpr int kAnaMaxKeys = (kAnaLdsBytes - (kAnaHeaderWords + kAnaThreads) * 8) / 8; // 19960
+constexpr int kMaxCols = WTK_ANALYSIS_MAX_COLUMNS;
+constexpr int kMaxQ = WTK_ANALYSIS_MAX_PERCENTILES;
+constexpr int kMaxRanks = 2 * kMaxQ + 2;
+
+struct AnaArgs {
+    Geometry g;
+    int E, C, n_log;
+    long long R;
+    const double *track, *share;
+    const int *pos, *move;  // [C][E][2]
+    const double *pair;     // [R][E] precise error of every pair, NaN = no value (nullable)
+    wtk_replay_analysis_config c;
+    int n_cols, Q;
+    int cols[kMaxCols];
+    double q[kMaxQ];
+    int by_step;            // the segment launch: 0 = one segment per (experiment, column), 1 = one per cycle step
+    int *last_cycle;        // [E] scratch: the largest cycle surviving imaging_only and bounds, -1 where none does
+    double *describe;       // [E][n_cols][5 + Q]
+    double *cycle_max, *cycle_mean; // [E][n_log][n_cols]
+    double *step_q;         // [E][L][n_cols][Q]
+    int *step_count;        // [E][L][n_cols]
+    long long *anomaly_counts; // [E][7]
+    uint8_t *anomaly_mask;  // [E][R]
+    long long *stats;       // [E][4]
+};
+
+// one logged row's columns after DataAnalyzer.initialize: float64, the reference's order of operations, every one rounded as DataFrame.round(5) rounds
+struct AnaRow {
+    double plt_x, plt_y, cam_x, cam_y, cam_w, cam_h, mic_x, mic_y, mic_w, mic_h, wx, wy, ww, wh;
+    double wcx, wcy, mcx, mcy, sx, sy, sp, dx, dy, dev, err, precise;
+    int c, step;
+    bool pre; // survives clean's imaging_only and bounds
+};
+
+__device__ __forceinline__ double round5(double v) { return isfinite(v) ? rint(v * 1e5) / 1e5 : v; }
+
+__device__ __forceinline__ RowBoxes boxes_of_row(const AnaArgs &a, int e, long long r, int &c, int &step, int &px, int &py) {
+    c = (int)(r / a.g.L), step = (int)(r - (long long)c * a.g.L);
+    frame_position(a.g, a.share, a.pos, a.move, (long long)c * a.E + e, step, px, py);
+    return row_boxes(a.g, a.track + 4 * r, px, py);
+}
+
+__device__ __forceinline__ AnaRow ana_row(const AnaArgs &a, int e, long long r) {
+    AnaRow w;
+    int px, py;
+    const RowBoxes b = boxes_of_row(a, e, r, w.c, w.step, px, py);
+    const double wcx = b.wx + b.ww / 2, wcy = b.wy + b.wh / 2, mcx = b.mic_x + b.mic_w / 2, mcy = b.mic_y + b.mic_h / 2; // _calc_centers
+    double sx = __builtin_nan(""), sy = __builtin_nan("");
+    if (r >= a.c.period) { // _calc_speed: Series.diff(period) over the whole uncleaned log, divided by time.diff(period) = period
+        int pc, ps, ppx, ppy;
+        const RowBoxes p = boxes_of_row(a, e, r - a.c.period, pc, ps, ppx, ppy);
+        const double n = (double)a.c.period;
+        sx = (wcx - (p.wx + p.ww / 2)) / n, sy = (wcy - (p.wy + p.wh / 2)) / n;
+    }
+    const double dx = wcx - mcx, dy = wcy - mcy; // _calc_worm_deviation
+    w.plt_x = round5((double)px), w.plt_y = round5((double)py);
+    w.cam_x = round5(b.cam_x), w.cam_y = round5(b.cam_y), w.cam_w = round5((double)a.g.cam_w), w.cam_h = round5((double)a.g.cam_h);
+    w.mic_x = round5(b.mic_x), w.mic_y = round5(b.mic_y), w.mic_w = round5(b.mic_w), w.mic_h = round5(b.mic_h);
+    w.wx = round5(b.wx), w.wy = round5(b.wy), w.ww = round5(b.ww), w.wh = round5(b.wh);
+    w.wcx = round5(wcx), w.wcy = round5(wcy), w.mcx = round5(mcx), w.mcy = round5(mcy);
+    w.sx = round5(sx), w.sy = round5(sy), w.sp = round5(sqrt(sx * sx + sy * sy));
+    w.dx = round5(dx), w.dy = round5(dy), w.dev = round5(sqrt(dx * dx + dy * dy));
+    w.err = round5(row_bbox_error(b));
+    w.precise = a.pair ? a.pair[r * a.E + e] : __builtin_nan(""); // assigned after the rounding (calc_precise_error): unrounded
+    // clean, on the rounded values.  The reference's `mask_wrm = has_pred; mask_wrm &= ...` updates has_pred in place, so its `~has_pred` is the negation
+    // of the finished worm mask: it keeps (has_pred and the worm box inside) or the microscope box inside.
+    bool pre = !a.c.imaging_only || w.step < a.g.I;
+    if (pre && a.c.use_bounds) {
+        const double *bd = a.c.bounds;
+        const bool has_pred = isfinite(w.wx) && isfinite(w.wy) && isfinite(w.ww) && isfinite(w.wh);
+        const bool wrm_in = w.wx >= bd[0] && w.wx + w.ww <= bd[2] && w.wy >= bd[1] && w.wy + w.wh <= bd[3];
+        const bool mic_in = w.mic_x >= bd[0] && w.mic_x + w.mic_w <= bd[2] && w.mic_y >= bd[1] && w.mic_y + w.mic_h <= bd[3];
+        pre = (has_pred && wrm_in) || mic_in;
+    }
+    w.pre = pre;
+    return w;
+}
+
+__device__ __forceinline__ bool ana_keep(const AnaArgs &a, const AnaRow &w, int last) { return w.pre && (!a.c.trim_cycles || (w.c != 0 && w.c != last)); }
+
+// the column's value of a row in the requested unit (change_unit: one multiplication of the rounded value; the factors are 1 for unit "frame")
+__device__ __forceinline__ double ana_value(const AnaArgs &a, const AnaRow &w, long long r, int col) {
+    const double tf = a.c.time_factor, ds = a.c.dist_factor, sf = a.c.speed_factor;
+    switch (col) {
+    case WTK_ANALYSIS_COL_FRAME: return (double)r;
+    case WTK_ANALYSIS_COL_CYCLE: return (double)w.c;
+    case WTK_ANALYSIS_COL_PLT_X: return w.plt_x * ds;
+    case WTK_ANALYSIS_COL_PLT_Y: return w.plt_y * ds;
+    case WTK_ANALYSIS_COL_CAM_X: return w.cam_x * ds;
+    case WTK_ANALYSIS_COL_CAM_Y: return w.cam_y * ds;
+    case WTK_ANALYSIS_COL_CAM_W: return w.cam_w * ds;
+    case WTK_ANALYSIS_COL_CAM_H: return w.cam_h * ds;
+    case WTK_ANALYSIS_COL_MIC_X: return w.mic_x * ds;
+    case WTK_ANALYSIS_COL_MIC_Y: return w.mic_y * ds;
+    case WTK_ANALYSIS_COL_MIC_W: return w.mic_w * ds;
+    case WTK_ANALYSIS_COL_MIC_H: return w.mic_h * ds;
+    case WTK_ANALYSIS_COL_WRM_X: return w.wx * ds;
+    case WTK_ANALYSIS_COL_WRM_Y: return w.wy * ds;
+    case WTK_ANALYSIS_COL_WRM_W: return w.ww * ds;
+    case WTK_ANALYSIS_COL_WRM_H: return w.wh * ds;
+    case WTK_ANALYSIS_COL_TIME: return (double)r * tf;
+    case WTK_ANALYSIS_COL_CYCLE_STEP: return (double)w.step;
+    case WTK_ANALYSIS_COL_WRM_CENTER_X: return w.wcx * ds;
+    case WTK_ANALYSIS_COL_WRM_CENTER_Y: return w.wcy * ds;
+    case WTK_ANALYSIS_COL_MIC_CENTER_X: return w.mcx * ds;
+    case WTK_ANALYSIS_COL_MIC_CENTER_Y: return w.mcy * ds;
+    case WTK_ANALYSIS_COL_WRM_SPEED_X: return w.sx * sf;
+    case WTK_ANALYSIS_COL_WRM_SPEED_Y: return w.sy * sf;
+    case WTK_ANALYSIS_COL_WRM_SPEED: return w.sp * sf;
+    case WTK_ANALYSIS_COL_WORM_DEVIATION_X: return w.dx * ds;
+    case WTK_ANALYSIS_COL_WORM_DEVIATION_Y: return w.dy * ds;
+    case WTK_ANALYSIS_COL_WORM_DEVIATION: return w.dev * ds;
+    case WTK_ANALYSIS_COL_BBOX_ERROR: return w.err;
+    default: return w.precise; // WTK_ANALYSIS_COL_PRECISE_ERROR (the entry point refuses every other id)
+    }
+}
+
+__global__ __launch_bounds__(kAnaThreads) void analysis_last_cycle_kernel(const AnaArgs a) {
+    __shared__ int best[kAnaThreads];
+    const int e = blockIdx.x;
+    if (!a.c.use_bounds) { // imaging_only alone keeps step 0 of every cycle (block-uniform)
+        if (threadIdx.x == 0) a.last_cycle[e] = a.n_log - 1;
+        return;
+    }
+    int mine = -1;
+    for (long long r = threadIdx.x; r < a.R; r += kAnaThreads) {
+        const AnaRow w = ana_row(a, e, r);
+        if (w.pre) mine = max(mine, w.c);
+    }
+    best[threadIdx.x] = mine;
+    __syncthreads();
+    for (int half = kAnaThreads / 2; half > 0; half >>= 1) {
+        if ((int)threadIdx.x < half) best[threadIdx.x] = max(best[threadIdx.x], best[threadIdx.x + half]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) a.last_cycle[e] = best[0];
+}
+
+// a (experiment, column, segment) workgroup's share of the work
+struct Segment {
+    int e, j, col, seg, last;
+    long long n_rows; // rows of the segment, kept or not
+    __device__ __forceinline__ long long row(long long k, int L) const { return seg < 0 ? k : seg + k * L; }
+};
+
+__device__ __forceinline__ Segment segment_of(const AnaArgs &a) {
+    Segment s;
+    const int n_seg = a.by_step ? a.g.L : 1;
+    const int idx = blockIdx.x;
+    const int sg = idx % n_seg;
+    s.j = (idx / n_seg) % a.n_cols, s.e = idx / (n_seg * a.n_cols);
+    s.col = a.cols[s.j], s.seg = a.by_step ? sg : -1;
+    s.n_rows = a.by_step ? (a.R > sg ? (a.R - sg + a.g.L - 1) / a.g.L : 0) : a.R;
+    s.last = a.c.trim_cycles ? a.last_cycle[s.e] : -1;
+    return s;
+}
+
+// the k-th row of the segment: its value where the row is kept and the value is not NaN
+__device__ __forceinline__ bool segment_value(const AnaArgs &a, const Segment &s, long long k, double &v) {
+    const long long r = s.row(k, a.g.L);
+    const AnaRow w = ana_row(a, s.e, r);
+    if (!ana_keep(a, w, s.last)) return false;
+    v = ana_value(a, w, r, s.col);
+    return !isnan(v);
+}
+
+// the block's sum in a fixed order: a binary tree over the threads' values; every thread gets it
+__device__ __forceinline__ double block_sum(double *red, double v) {
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int half = kAnaThreads / 2; half > 0; half >>= 1) {
+        if ((int)threadIdx.x < half) red[threadIdx.x] += red[threadIdx.x + half];
+        __syncthreads();
+    }
+    const double sum = red[0];
+    __syncthreads();
+    return sum;
+}
+
+// order-preserving 64-bit keys of float64 values (-0.0 sorts before 0.0; no NaN is ever a key)
+__device__ __forceinline__ unsigned long long to_key(double v) {
+    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double from_key(unsigned long long k) {
+    return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
+}
+
+// the ranks a segment of n values needs: [0] min, [1] max, [2 + 2 i], [3 + 2 i] the neighbours of percentile i; numpy's `linear` rule
+__device__ __forceinline__ void percentile_rank(double q, long long n, long long &lo, long long &hi, double &t) {
+    const double pos = q * (double)(n - 1);
+    const double fl = floor(pos);
+    lo = (long long)fl, t = pos - fl;
+    hi = lo + 1 < n ? lo + 1 : n - 1;
+}
+__device__ __forceinline__ double lerp_linear(double x, double y, double t) { return t < 0.5 ? x + (y - x) * t : y - (y - x) * (1 - t); }
+
+// thread 0 writes the segment's results: count, mean, std, min, percentiles, max (describe) or percentiles and count (cycle steps)
+__device__ __forceinline__ void write_segment(const AnaArgs &a, const Segment &s, long long n, double mean, double ss, double vmin, double vmax, const double *pct) {
+    const double nanv = __builtin_nan("");
+    if (!a.by_step) {
+        double *o = a.describe + ((long long)s.e * a.n_cols + s.j) * (5 + a.Q);
+        o[0] = (double)n;
+        o[1] = n > 0 ? mean : nanv;
+        o[2] = n > 1 ? sqrt(ss / (double)(n - 1)) : nanv;
+        o[3] = n > 0 ? vmin : nanv;
+        for (int i = 0; i < a.Q; ++i) o[4 + i] = n > 0 ? pct[i] : nanv;
+        o[4 + a.Q] = n > 0 ? vmax : nanv;
+    } else {
+        const long long at = ((long long)s.e * a.g.L + s.seg) * a.n_cols + s.j;
+        if (a.step_count) a.step_count[at] = (int)n;
+        if (a.step_q)
+            for (int i = 0; i < a.Q; ++i) a.step_q[at * a.Q + i] = n > 0 ? pct[i] : nanv;
+    }
+}
+
+// count, mean and the sum of squares about the mean of the segment, each thread over its rows in order.  kKeys: the values also go to LDS as keys.
+template <bool kKeys>
+__device__ __forceinline__ void segment_moments(const AnaArgs &a, const Segment &s, double *red, unsigned long long *keys, int *key_count, int max_keys,
+                                                long long &n, double &mean, double &ss) {
+    double sum = 0.0, cnt = 0.0;
+    for (long long k = threadIdx.x; k < s.n_rows; k += kAnaThreads) {
+        double v;
+        if (!segment_value(a, s, k, v)) continue;
+        sum += v, cnt += 1.0;
+        if (kKeys) {
+            const int at = atomicAdd(key_count, 1); // the order of arrival does not matter: the keys are sorted next
+            if (at < max_keys) keys[at] = to_key(v);
+        }
+    }
+    n = (long long)block_sum(red, cnt); // exact: counts are small integers
+    mean = block_sum(red, sum) / (double)n;
+    double part = 0.0;
+    if (n > 1) {
+        for (long long k = threadIdx.x; k < s.n_rows; k += kAnaThreads) {
+            double v;
+            if (segment_value(a, s, k, v)) part += (v - mean) * (v - mean);
+        }
+    }
+    ss = block_sum(red, part);
+}
+
+__global__ __launch_bounds__(kAnaThreads) void analysis_segment_sort_kernel(const AnaArgs a, const int max_keys) {
+    extern __shared__ unsigned long long lds64[];
+    int *key_count = reinterpret_cast<int *>(lds64);
+    double *red = reinterpret_cast<double *>(lds64 + kAnaHeaderWords);
+    unsigned long long *keys = lds64 + kAnaHeaderWords + kAnaThreads;
+    const Segment s = segment_of(a);
+    if (threadIdx.x == 0) *key_count = 0;
+    __syncthreads();
+    long long n;
+    double mean, ss;
+    segment_moments<true>(a, s, red, keys, key_count, max_keys, n, mean, ss);
+    const int m = min((int)n, max_keys); // n <= n_rows <= max_keys: the host chose this kernel for that
+    // bitonic network, every comparator min-to-low-index: a flip pass (partner i ^ (k - 1)) and disperse passes (partner i ^ j) per merge size k
+    for (int k = 2; (k >> 1) < m; k <<= 1) {
+        for (int i = threadIdx.x; i < m; i += kAnaThreads) {
+            const int l = i ^ (k - 1);
+            if (l > i && l < m) {
+                const unsigned long long x = keys[i], y = keys[l];
+                if (x > y) keys[i] = y, keys[l] = x;
+            }
+        }
+        __syncthreads();
+        for (int j = k >> 2; j > 0; j >>= 1) {
+            for (int i = threadIdx.x; i < m; i += kAnaThreads) {
+                const int l = i ^ j;
+                if (l > i && l < m) {
+                    const unsigned long long x = keys[i], y = keys[l];
+                    if (x > y) keys[i] = y, keys[l] = x;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    if (threadIdx.x == 0) {
+        double pct[kMaxQ];
+        for (int i = 0; i < a.Q && m > 0; ++i) {
+            long long lo, hi;
+            double t;
+            percentile_rank(a.q[i], m, lo, hi, t);
+            pct[i] = lerp_linear(from_key(keys[lo]), from_key(keys[hi]), t);
+        }
+        write_segment(a, s, m, mean, ss, m > 0 ? from_key(keys[0]) : 0.0, m > 0 ? from_key(keys[m - 1]) : 0.0, pct);
+    }
+}
+
+__global__ __launch_bounds__(kAnaThreads) void analysis_segment_select_kernel(const AnaArgs a) {
+    __shared__ double red[kAnaThreads];
+    __shared__ unsigned hist[kMaxRanks][256];
+    __shared__ unsigned long long prefix[kMaxRanks]; // the digits found so far, in place
+    __shared__ long long remain[kMaxRanks];          // the rank among the values that share the prefix
+    const Segment s = segment_of(a);
+    long long n;
+    double mean, ss;
+    segment_moments<false>(a, s, red, nullptr, nullptr, 0, n, mean, ss);
+    const int n_ranks = 2 + 2 * a.Q;
+    if (n > 0) { // block-uniform
+        if ((int)threadIdx.x < n_ranks) {
+            long long rank = threadIdx.x == 0 ? 0 : n - 1;
+            if (threadIdx.x >= 2) {
+                long long lo, hi;
+                double t;
+                percentile_rank(a.q[(threadIdx.x - 2) >> 1], n, lo, hi, t);
+                rank = (threadIdx.x & 1) ? hi : lo;
+            }
+            remain[threadIdx.x] = rank, prefix[threadIdx.x] = 0ull;
+        }
+        for (int shift = 56; shift >= 0; shift -= 8) {
+            for (int i = threadIdx.x; i < n_ranks * 256; i += kAnaThreads) hist[i >> 8][i & 255] = 0u;
+            __syncthreads();
+            for (long long k = threadIdx.x; k < s.n_rows; k += kAnaThreads) {
+                double v;
+                if (!segment_value(a, s, k, v)) continue;
+                const unsigned long long key = to_key(v);
+                const unsigned digit = (unsigned)(key >> shift) & 255u;
+                for (int i = 0; i < n_ranks; ++i)
+                    if (shift == 56 || ((key ^ prefix[i]) >> (shift + 8)) == 0ull) atomicAdd(&hist[i][digit], 1u);
+            }
+            __syncthreads();
+            if ((int)threadIdx.x < n_ranks) {
+                long long rem = remain[threadIdx.x];
+                unsigned d = 0;
+                for (; d < 255u && rem >= (long long)hist[threadIdx.x][d]; ++d) rem -= (long long)hist[threadIdx.x][d];
+                remain[threadIdx.x] = rem, prefix[threadIdx.x] |= (unsigned long long)d << shift;
+            }
+            __syncthreads();
+        }
+    }
+    if (threadIdx.x == 0) {
+        double pct[kMaxQ];
+        for (int i = 0; i < a.Q && n > 0; ++i) {
+            long long lo, hi;
+            double t;
+            percentile_rank(a.q[i], n, lo, hi, t);
+            pct[i] = lerp_linear(from_key(prefix[2 + 2 * i]), from_key(prefix[3 + 2 * i]), t);
+        }
+        write_segment(a, s, n, mean, ss, n > 0 ? from_key(prefix[0]) : 0.0, n > 0 ? from_key(prefix[1]) : 0.0, pct);
+    }
+}
+
+// groupby(["log_num", "cycle"]) max / mean of every requested column over the kept rows: NaN where the cycle has no kept non-NaN value
+__global__ __launch_bounds__(256) void analysis_cycle_kernel(const AnaArgs a) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long long)a.E * a.n_log * a.n_cols) return;
+    const int j = (int)(idx % a.n_cols), c = (int)((idx / a.n_cols) % a.n_log), e = (int)(idx / ((long long)a.n_cols * a.n_log));
+    const int last = a.c.trim_cycles ? a.last_cycle[e] : -1;
+    double vmax = 0.0, sum = 0.0;
+    int n = 0;
+    for (int step = 0; step < a.g.L; ++step) {
+        const long long r = (long long)c * a.g.L + step;
+        const AnaRow w = ana_row(a, e, r);
+        if (!ana_keep(a, w, last)) continue;
+        const double v = ana_value(a, w, r, a.cols[j]);
+        if (isnan(v)) continue;
+        vmax = n == 0 ? v : fmax(vmax, v);
+        sum += v, ++n;
+    }
+    const double nanv = __builtin_nan("");
+    if (a.cycle_max) a.cycle_max[idx] = n > 0 ? vmax : nanv;
+    if (a.cycle_mean) a.cycle_mean[idx] = n > 0 ? sum / (double)n : nanv;
+}
+
+// calc_anomalies and print_stats over the kept rows of one experiment; counts are integers, added with LDS atomics
+__global__ __launch_bounds__(kAnaThreads) void analysis_flags_kernel(const AnaArgs a) {
+    __shared__ int cnt[12]; // [0..5] the six anomaly kinds, [6] any, [7] kept rows, [8] no-pred rows, [9] rows with bbox_error > 1e-7, [10] cycles with a kept row
+    const int e = blockIdx.x;
+    if (threadIdx.x < 12) cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const int last = a.c.trim_cycles ? a.last_cycle[e] : -1;
+    for (long long r = threadIdx.x; r < a.R; r += kAnaThreads) {
+        const AnaRow w = ana_row(a, e, r);
+        unsigned bits = 0u;
+        if (ana_keep(a, w, last)) {
+            // on the values calc_anomalies sees: after change_unit; a comparison with NaN is false
+            bits |= w.sp * a.c.speed_factor >= a.c.min_speed ? 1u : 0u;
+            bits |= w.err >= a.c.min_bbox_error ? 2u : 0u;
+            bits |= w.dev * a.c.dist_factor >= a.c.min_dist_error ? 4u : 0u;
+            bits |= w.ww * a.c.dist_factor >= a.c.min_width ? 8u : 0u;
+            bits |= w.wh * a.c.dist_factor >= a.c.min_height ? 16u : 0u;
+            const bool finite = isfinite(w.wx) && isfinite(w.wy) && isfinite(w.ww) && isfinite(w.wh);
+            bits |= (a.c.no_preds && !finite) ? 32u : 0u;
+            for (int k = 0; k < 6; ++k)
+                if ((bits >> k) & 1u) atomicAdd(&cnt[k], 1);
+            if (bits) atomicAdd(&cnt[6], 1);
+            atomicAdd(&cnt[7], 1);
+            if (isnan(w.wx) || isnan(w.wy) || isnan(w.ww) || isnan(w.wh)) atomicAdd(&cnt[8], 1);
+            if (w.err > 1e-7) atomicAdd(&cnt[9], 1);
+        }
+        if (a.anomaly_mask) a.anomaly_mask[(long long)e * a.R + r] = (uint8_t)bits;
+    }
+    for (int c = threadIdx.x; c < a.n_log; c += kAnaThreads) {
+        bool any = false;
+        for (int step = 0; step < a.g.L && !any; ++step) any = ana_keep(a, ana_row(a, e, (long long)c * a.g.L + step), last);
+        if (any) atomicAdd(&cnt[10], 1);
+    }
+    __syncthreads();
+    if (threadIdx.x < 7 && a.anomaly_counts) a.anomaly_counts[(long long)e * 7 + threadIdx.x] = cnt[threadIdx.x];
+    if (threadIdx.x == 0 && a.stats) {
+        long long *o = a.stats + (long long)e * 4;
+        o[0] = a.R - cnt[7], o[1] = cnt[8], o[2] = cnt[10], o[3] = cnt[9];
+    }
+}
+
+} // namespace
+
+extern "C" int64_t wtk_replay_analysis_scratch_doubles(int32_t E, int64_t R, int32_t n_cols, int32_t Q) {
+    if (E < 0 || R < 0 || n_cols < 0 || Q < 0) return -1;
+    return ((int64_t)E + 1) / 2; // [E] int32: the last surviving cycle of every experiment
+}
+
+extern "C" int wtk_replay_analyze(const wtk_replay_config *cfg, const wtk_replay_analysis_config *acfg, int32_t E, int32_t n_cycles,
+                                  const double *track_dev, int32_t n_track, const double *share_dev, const int32_t *pos_dev, const int32_t *move_dev,
+                                  const double *precise_pair_dev, const int32_t *columns_host, int32_t n_cols, const double *percentiles_host, int32_t Q,
+                                  int32_t max_lds_rows, double *describe_dev, double *cycle_max_dev, double *cycle_mean_dev, double *step_quantiles_dev,
+                                  int32_t *step_count_dev, int64_t *anomaly_counts_dev, uint8_t *anomaly_mask_dev, int64_t *stats_dev, double *scratch_dev,
+                                  int64_t scratch_doubles, void *stream) {
+    const std::string w("wtk_replay_analyze");
+    AnaArgs a = {};
+    if (!acfg) return fail(w + ": null argument");
+    if (replay_check_config("wtk_replay_analyze", cfg, WTK_REPLAY_OPTIMAL, E, n_cycles, n_track, a.g, a.n_log)) return 1;
+    if (!track_dev || !share_dev || !pos_dev || !move_dev || !columns_host || !scratch_dev || (Q > 0 && !percentiles_host)) return fail(w + ": null argument");
+    if (n_cols < 1 || n_cols > kMaxCols) return fail(w + ": 1.." + std::to_string(kMaxCols) + " columns");
+    if (Q < 0 || Q > kMaxQ) return fail(w + ": 0.." + std::to_string(kMaxQ) + " percentiles");
+    if (acfg->period < 1) return fail(w + ": period must be at least 1");
+    if (max_lds_rows < 0) return fail(w + ": negative max_lds_rows (0 = the default)");
+    for (int j = 0; j < n_cols; ++j) {
+        if (columns_host[j] < 0 || columns_host[j] >= WTK_ANALYSIS_N_COLUMNS) return fail(w + ": unknown column");
+        if (columns_host[j] == WTK_ANALYSIS_COL_PRECISE_ERROR && !precise_pair_dev) return fail(w + ": the precise_error column needs precise_pair_dev");
+        a.cols[j] = columns_host[j];
+    }
+    for (int i = 0; i < Q; ++i) {
+        if (!(percentiles_host[i] >= 0.0 && percentiles_host[i] <= 1.0)) return fail(w + ": percentile outside [0, 1]");
+        a.q[i] = percentiles_host[i];
+    }
+    a.R = (long long)a.n_log * a.g.L;
+    if (a.R > INT32_MAX || (long long)E * n_cols * a.g.L > INT32_MAX || ((long long)E * a.n_log * n_cols + 255) / 256 > INT32_MAX)
+        return fail(w + ": too many blocks for one launch");
+    if (scratch_doubles < wtk_replay_analysis_scratch_doubles(E, a.R, n_cols, Q)) return fail(w + ": scratch smaller than wtk_replay_analysis_scratch_doubles(E, R, n_cols, Q)");
+    a.E = E, a.C = n_cycles, a.track = track_dev, a.share = share_dev, a.pos = pos_dev, a.move = move_dev, a.pair = precise_pair_dev;
+    a.c = *acfg, a.n_cols = n_cols, a.Q = Q, a.last_cycle = reinterpret_cast<int *>(scratch_dev);
+    a.describe = describe_dev, a.cycle_max = cycle_max_dev, a.cycle_mean = cycle_mean_dev, a.step_q = step_quantiles_dev, a.step_count = step_count_dev;
+    a.anomaly_counts = reinterpret_cast<long long *>(anomaly_counts_dev), a.anomaly_mask = anomaly_mask_dev, a.stats = reinterpret_cast<long long *>(stats_dev);
+    hipStream_t st = (hipStream_t)stream;
+    const int max_keys = max_lds_rows == 0 ? kAnaMaxKeys : std::min((int)max_lds_rows, kAnaMaxKeys);
+    const bool segments = describe_dev || step_quantiles_dev || step_count_dev;
+    // above 64 KiB of dynamic LDS a kernel needs the attribute (per device, so it is set at every call: a host-side table write)
+    if (segments) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&analysis_segment_sort_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kAnaLdsBytes));
+    if (a.c.trim_cycles) hipLaunchKernelGGL(analysis_last_cycle_kernel, dim3((unsigned)E), dim3(kAnaThreads), 0, st, a);
+    for (int by_step = 0; by_step < 2; ++by_step) {
+        if (by_step ? !(step_quantiles_dev || step_count_dev) : !describe_dev) continue;
+        a.by_step = by_step;
+        const long long seg_rows = by_step ? (long long)a.n_log : a.R; // the longest segment's rows: an upper bound of its kept values
+        const unsigned grid = (unsigned)((long long)E * n_cols * (by_step ? a.g.L : 1));
+        if (seg_rows <= max_keys) {
+            const size_t lds = (size_t)(kAnaHeaderWords + kAnaThreads + std::max(seg_rows, 1ll)) * 8;
+            hipLaunchKernelGGL(analysis_segment_sort_kernel, dim3(grid), dim3(kAnaThreads), lds, st, a, (int)std::max(seg_rows, 1ll));
+        } else {
+            hipLaunchKernelGGL(analysis_segment_select_kernel, dim3(grid), dim3(kAnaThreads), 0, st, a);
+        }
+    }
+    a.by_step = 0;
+    if ((cycle_max_dev || cycle_mean_dev) && a.n_log > 0)
+        hipLaunchKernelGGL(analysis_cycle_kernel, dim3((unsigned)(((long long)E * a.n_log * n_cols + 255) / 256)), dim3(256), 0, st, a);
+    if (anomaly_counts_dev || anomaly_mask_dev || stats_dev) hipLaunchKernelGGL(analysis_flags_kernel, dim3((unsigned)E), dim3(kAnaThreads), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}

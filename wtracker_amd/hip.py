@@ -45,6 +45,12 @@ class _ReplayConfig(C.Structure):
                                          "frame_w", "frame_h", "init_x", "init_y")]
 
 
+class _AnalysisConfig(C.Structure):
+    _fields_ = ([("bounds", C.c_double * 4)] + [(n, C.c_double) for n in ("time_factor", "dist_factor", "speed_factor", "min_speed", "min_bbox_error",
+                                                                          "min_dist_error", "min_width", "min_height")]
+                + [(n, C.c_int32) for n in ("period", "imaging_only", "use_bounds", "trim_cycles", "no_preds", "reserved")])
+
+
 class _YoloDesc(C.Structure):
     _fields_ = [("device", C.c_int32), ("dtype", C.c_int32), ("imgsz_h", C.c_int32), ("imgsz_w", C.c_int32),
                 ("max_batch", C.c_int32), ("nc", C.c_int32), ("width_mult", C.c_float), ("depth_mult", C.c_float),
@@ -53,6 +59,7 @@ class _YoloDesc(C.Structure):
 
 _vp, _i32, _i64, _f32, _f64, _size = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_size_t
 _pvp, _pi32, _pi64, _pf32, _pf64, _pcfg = C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_f32), C.POINTER(_f64), C.POINTER(_ReplayConfig)
+_pacfg = C.POINTER(_AnalysisConfig)
 
 # The C ABI, one row per symbol of include/wtk_hip.h and in its order: name -> (restype, argtypes).  load() applies it and nothing else declares a
 # signature; tests/test_abi.py compares every row with the header's prototype, kind by kind (pointer, int32, int64, size_t, float, double).
@@ -129,6 +136,9 @@ SIGNATURES = {
     "wtk_replay_yolo_track": (_i32, [_pcfg, _i32, _vp, _vp, _vp, _vp]),
     "wtk_boxes_scratch_bytes": (_i64, [_i32, _i32, _i32]),
     "wtk_boxes": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "wtk_replay_analysis_scratch_doubles": (_i64, [_i32, _i64, _i32, _i32]),
+    "wtk_replay_analyze": (_i32, [_pcfg, _pacfg, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                  _vp, _i64, _vp]),
     "wtk_replay_precise_scratch_doubles": (_i64, [_i32, _i64]),
     "wtk_replay_precise": (_i32, [_pcfg, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _f64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "wtk_replay_precise_objective": (_i32, [_pcfg, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _f64, _i32, _vp, _vp,
@@ -513,6 +523,40 @@ def replay_precise_objective(cfg: _ReplayConfig, kind: int, E: int, n_cycles: in
                                                _ptr(b_dev), _ptr(valid_dev), _ptr(share_dev), _ptr(pos_dev), _ptr(move_dev), _ptr(frames_dev), n_frames, H, W,
                                                _ptr(bg_dev), float(diff_thresh), int(max_crop_px), _ptr(summary_dev), _ptr(scratch_dev), scratch_doubles,
                                                objective, _ptr(objective_dev), _ptr(stop_dev), C.c_void_p(stream)), "wtk_replay_precise_objective")
+
+
+# WTK_ANALYSIS_COL_*: the columns of DataAnalyzer's table, in the header's order
+ANALYSIS_COLUMNS = ["frame", "cycle", "plt_x", "plt_y", "cam_x", "cam_y", "cam_w", "cam_h", "mic_x", "mic_y", "mic_w", "mic_h", "wrm_x", "wrm_y", "wrm_w", "wrm_h",
+                    "time", "cycle_step", "wrm_center_x", "wrm_center_y", "mic_center_x", "mic_center_y", "wrm_speed_x", "wrm_speed_y", "wrm_speed",
+                    "worm_deviation_x", "worm_deviation_y", "worm_deviation", "bbox_error", "precise_error"]
+ANALYSIS_MAX_COLUMNS, ANALYSIS_MAX_PERCENTILES = 32, 16
+
+
+def replay_analysis_config(period: int, imaging_only: bool, bounds, trim_cycles: bool, factors: Sequence[float], min_speed: float, min_bbox_error: float,
+                           min_dist_error: float, min_width: float, min_height: float, no_preds: bool) -> _AnalysisConfig:
+    """The wtk_replay_analysis_config of an analysis; `bounds` (x0, y0, x1, y1) or None, `factors` (time, distance, speed)."""
+    b = (C.c_double * 4)(*(float(v) for v in (bounds if bounds is not None else (0, 0, 0, 0))))
+    return _AnalysisConfig(b, float(factors[0]), float(factors[1]), float(factors[2]), float(min_speed), float(min_bbox_error), float(min_dist_error),
+                           float(min_width), float(min_height), int(period), int(bool(imaging_only)), int(bounds is not None), int(bool(trim_cycles)),
+                           int(bool(no_preds)), 0)
+
+
+def replay_analysis_scratch_doubles(E: int, R: int, n_cols: int, Q: int) -> int:
+    return int(load().wtk_replay_analysis_scratch_doubles(E, R, n_cols, Q))
+
+
+def replay_analyze(cfg: _ReplayConfig, acfg: _AnalysisConfig, E: int, n_cycles: int, track_dev, n_track: int, share_dev, pos_dev, move_dev, precise_pair_dev,
+                   columns: Sequence[int], percentiles: Sequence[float], max_lds_rows: int, describe_dev, cycle_max_dev, cycle_mean_dev, step_quantiles_dev,
+                   step_count_dev, anomaly_counts_dev, anomaly_mask_dev, stats_dev, scratch_dev, scratch_doubles: int, stream: int = 0):
+    """DataAnalyzer's statistics of every experiment of a scan (wtk_replay_analyze); `columns`: WTK_ANALYSIS_COL_* ids; every output is a device tensor
+    or None: describe [E, n_cols, 5 + Q], cycle_max / cycle_mean [E, n_log, n_cols], step_quantiles [E, L, n_cols, Q] float64, step_count [E, L, n_cols]
+    int32, anomaly_counts [E, 7] and stats [E, 4] int64, anomaly_mask [E, R] uint8."""
+    cols, q = np.ascontiguousarray(columns, dtype=np.int32), np.ascontiguousarray(percentiles, dtype=np.float64)
+    _check(load().wtk_replay_analyze(C.byref(cfg) if cfg is not None else None, C.byref(acfg) if acfg is not None else None, E, n_cycles, _ptr(track_dev),
+                                     n_track, _ptr(share_dev), _ptr(pos_dev), _ptr(move_dev), _ptr(precise_pair_dev), _ptr(cols), len(cols), _ptr(q), len(q),
+                                     int(max_lds_rows), _ptr(describe_dev), _ptr(cycle_max_dev), _ptr(cycle_mean_dev), _ptr(step_quantiles_dev),
+                                     _ptr(step_count_dev), _ptr(anomaly_counts_dev), _ptr(anomaly_mask_dev), _ptr(stats_dev), _ptr(scratch_dev), scratch_doubles,
+                                     C.c_void_p(stream)), "wtk_replay_analyze")
 
 
 def replay_yolo_step(cfg: _ReplayConfig, n_cycles: int, c: int, xywh_dev, share_dev, pos_dev, move_dev, stream: int = 0):

@@ -34,12 +34,23 @@ single-frame call and a small control kernel per cycle, all on one stream, and t
     res = yr.run()                    # a ReplayResult with E = 1, bit for bit the host loop's moves and log; one host synchronisation
     res.detections                    # device float32 [R, 4], view pixels
 
-There is no CPU fallback: without a visible GPU the constructors raise.  Not covered: `StepMotorController`, DataAnalyzer's speed and unit columns, the
-YOLO controller's second look (YoloConfig.recheck_margin).
+The reference's analysis workflow (DataAnalyzer.initialize / clean / change_unit / describe / calc_anomalies / print_stats and the Plotter's per-cycle
+and per-cycle-step aggregates) of every experiment of a population, on the device (csrc/replay_analysis.hip):
+
+    spec = Analysis(period=10, trim_cycles=True, imaging_only=True, bounds=(40, 40, 1500, 1300), unit="sec",
+                    columns=["wrm_speed", "worm_deviation", "bbox_error"], percentiles=[0.5, 0.95], min_bbox_error=0.5)
+    res = rp.run(t, analysis=spec)                                      # also YoloReplay.run(analysis=spec)
+    res.analysis.describe                                               # [E, n_cols, 5 + Q]; .describe_table(e), .print_stats(e)
+    res.analysis.cycle_max, res.analysis.step_quantiles, res.analysis.anomaly_counts, res.analysis.stats
+    rp.analyze(t, spec)                                                 # the same as device tensors, no synchronisation
+
+There is no CPU fallback: without a visible GPU the constructors raise.  Not covered: `StepMotorController`, DataAnalyzer's `remove_cycle` and
+`save` / `load`, the plots themselves, the YOLO controller's second look (YoloConfig.recheck_margin).
 """
 from __future__ import annotations
 
 import csv as _csv
+import math
 import os
 from dataclasses import dataclass
 from typing import Optional, Sequence
@@ -196,13 +207,129 @@ class PreciseSummary:
         return self.non_perfect_rows / self.rows
 
 
+ANALYSIS_COLUMNS = hip.ANALYSIS_COLUMNS  # the columns of DataAnalyzer's table; the position is the WTK_ANALYSIS_COL_* id
+ANOMALY_KINDS = ("speed", "bbox_error", "dist_error", "width", "height", "no_pred")  # bit k of anomaly_mask, column k of anomaly_counts (column 6: any)
+
+
+@dataclass
+class Analysis:
+    """What to compute of every replayed experiment, in the reference's terms: `period` of DataAnalyzer.initialize; `trim_cycles`, `imaging_only`,
+    `bounds` (x0, y0, x1, y1) of clean (trim_cycles drops cycle 0 and the largest cycle that survives the other two filters); `unit` "frame" or "sec"
+    of change_unit; `columns` (names of ANALYSIS_COLUMNS) and `percentiles` (in [0, 1]) of describe and of the per-cycle and per-cycle-step
+    aggregates; the thresholds of calc_anomalies (`min_size` for both sides of the worm box; inf = off), applied to the unit-changed values.
+    `anomaly_mask`: also return the per-row bit flags [E, R]."""
+
+    period: int = 10
+    trim_cycles: bool = False
+    imaging_only: bool = False
+    bounds: Optional[Sequence[float]] = None
+    unit: str = "frame"
+    columns: Sequence[str] = ("wrm_speed", "worm_deviation", "bbox_error")
+    percentiles: Sequence[float] = (0.25, 0.5, 0.75)
+    no_preds: bool = True
+    min_bbox_error: float = math.inf
+    min_dist_error: float = math.inf
+    min_speed: float = math.inf
+    min_size: float = math.inf
+    anomaly_mask: bool = False
+
+    def column_ids(self) -> list:
+        unknown = [c for c in self.columns if c not in ANALYSIS_COLUMNS]
+        if unknown or not self.columns:
+            raise ValueError(f"unknown analysis columns {unknown}: one or more of {ANALYSIS_COLUMNS}")
+        if len(self.columns) > hip.ANALYSIS_MAX_COLUMNS or len(self.percentiles) > hip.ANALYSIS_MAX_PERCENTILES:
+            raise ValueError(f"at most {hip.ANALYSIS_MAX_COLUMNS} columns and {hip.ANALYSIS_MAX_PERCENTILES} percentiles")
+        return [ANALYSIS_COLUMNS.index(c) for c in self.columns]
+
+    def factors(self, timing_config: TimingConfig) -> tuple:
+        """(time, distance, speed) factors of change_unit(unit), as the reference computes them."""
+        if self.unit == "frame":
+            return (1.0, 1.0, 1.0)
+        if self.unit != "sec":
+            raise ValueError(f"unit must be 'frame' or 'sec', got {self.unit!r}")
+        dist, tf = timing_config.mm_per_px * 1000, timing_config.ms_per_frame / 1000
+        return (tf, dist, dist / tf)
+
+    def config(self, timing_config: TimingConfig):
+        if self.bounds is not None and len(self.bounds) != 4:
+            raise ValueError("bounds must be (x0, y0, x1, y1)")
+        return hip.replay_analysis_config(self.period, self.imaging_only, self.bounds, self.trim_cycles, self.factors(timing_config), self.min_speed,
+                                          self.min_bbox_error, self.min_dist_error, self.min_size, self.min_size, self.no_preds)
+
+
+@dataclass
+class AnalysisResult:
+    """The analysis of E experiments (numpy arrays after `run`, device tensors from `Replay.analyze`): describe [E, n_cols, 5 + Q] (count, mean, std,
+    min, the percentiles, max over the kept rows), cycle_max / cycle_mean [E, n_log, n_cols], step_quantiles [E, L, n_cols, Q], step_count
+    [E, L, n_cols], anomaly_counts [E, 7] (ANOMALY_KINDS and any), stats [E, 4] (removed rows, kept rows without a prediction, distinct cycles kept,
+    kept rows with bbox_error > 1e-7), anomaly_mask [E, R] uint8 bit flags or None.  NaN: no value (an empty segment, the std of a single row)."""
+
+    columns: list
+    percentiles: list
+    n_rows: int
+    describe: object
+    cycle_max: object
+    cycle_mean: object
+    step_quantiles: object
+    step_count: object
+    anomaly_counts: object
+    stats: object
+    anomaly_mask: object = None
+
+    @property
+    def describe_index(self) -> list:
+        """The row names of DataAnalyzer.describe's table."""
+        return ["count", "mean", "std", "min"] + [f"{100 * q:g}%" for q in self.percentiles] + ["max"]
+
+    def describe_table(self, e: int):
+        """Experiment e's describe table as DataAnalyzer.describe lays it out: (row names, column names, values [5 + Q, n_cols])."""
+        return self.describe_index, list(self.columns), np.asarray(self.describe[e]).T.copy()
+
+    def print_stats(self, e: int) -> None:
+        """DataAnalyzer.print_stats for experiment e."""
+        removed, no_pred, cycles, non_perfect = (int(v) for v in self.stats[e])
+        kept = self.n_rows - removed
+        pct = lambda a, b: round(100 * a / b, 3) if b else float("nan")  # noqa: E731
+        print(f"Count of Removed Frames: {removed} ({pct(removed, self.n_rows)}%)")
+        print(f"Count of No-Pred Frames: {no_pred} ({pct(no_pred, kept)}%)")
+        print(f"Total Num of Cycles: {cycles}")
+        print(f"Non Perfect Predictions: {pct(non_perfect, kept)}%")
+
+
+def _enqueue_analysis(geometry: "LoopGeometry", timing_config, spec: Analysis, E: int, track, n_track: int, share, pos, move, pair, stream: int,
+                      max_lds_rows: int = 0) -> AnalysisResult:
+    """wtk_replay_analyze on a scan's pos / move: an AnalysisResult of device tensors.  `pair`: the per-pair precise errors [R, E] or None."""
+    import torch
+
+    g, dev = geometry, pos.device
+    cols, q = spec.column_ids(), [float(v) for v in spec.percentiles]
+    n, Q, f64 = len(cols), len(q), torch.float64
+    out = AnalysisResult(list(spec.columns), q, g.n_rows, torch.empty((E, n, 5 + Q), dtype=f64, device=dev), torch.empty((E, g.n_log, n), dtype=f64, device=dev),
+                         torch.empty((E, g.n_log, n), dtype=f64, device=dev), torch.empty((E, g.L, n, Q), dtype=f64, device=dev),
+                         torch.empty((E, g.L, n), dtype=torch.int32, device=dev), torch.empty((E, 7), dtype=torch.int64, device=dev),
+                         torch.empty((E, 4), dtype=torch.int64, device=dev),
+                         torch.empty((E, g.n_rows), dtype=torch.uint8, device=dev) if spec.anomaly_mask else None)
+    scratch = torch.empty((max(1, hip.replay_analysis_scratch_doubles(E, g.n_rows, n, Q)),), dtype=f64, device=dev)
+    hip.replay_analyze(g.config, spec.config(timing_config), E, g.n_cycles, track, n_track, share, pos, move, pair, cols, q, int(max_lds_rows), out.describe,
+                       out.cycle_max, out.cycle_mean, out.step_quantiles, out.step_count, out.anomaly_counts, out.anomaly_mask, out.stats, scratch,
+                       scratch.numel(), stream=stream)
+    return out
+
+
+def _analysis_to_host(a: AnalysisResult) -> AnalysisResult:
+    host = lambda t: None if t is None else t.cpu().numpy()  # noqa: E731
+    return AnalysisResult(a.columns, a.percentiles, a.n_rows, host(a.describe), host(a.cycle_max), host(a.cycle_mean), host(a.step_quantiles), host(a.step_count),
+                          host(a.anomaly_counts), host(a.stats), host(a.anomaly_mask))
+
+
 class ReplayResult:
     """moves, positions [E, C, 2] int32 (the move of cycle c and the platform position at its start); summary; bbox_error / mse_error [E, R] float64 when
     requested; the full log rows of the experiments named in `rows`; `detections` (YoloReplay only): device float32 [R, 4] xywh in view pixels.
     After `Replay.run(precise=True)`: `precise_summary`, and with per-row errors `precise_error` [E, R] float64 (NaN = no value) and `precise_counts`
-    [E, R, 2] int32 (foreground pixels of the worm crop, those of them inside the microscope view); None otherwise."""
+    [E, R, 2] int32 (foreground pixels of the worm crop, those of them inside the microscope view); None otherwise.  After `run(analysis=spec)`:
+    `analysis`, an AnalysisResult of numpy arrays."""
 
-    precise_summary = precise_error = precise_counts = None
+    precise_summary = precise_error = precise_counts = analysis = None
 
     def __init__(self, moves, positions, summary, decision_frames, row_ids, row_data, bbox_error, mse_error, detections=None):
         self.moves, self.positions, self.summary, self.decision_frames = moves, positions, summary, decision_frames
@@ -522,17 +649,36 @@ class Replay:
             raise ValueError("no sample times yet: pass sample_times, or call optimize_polyfit / polyfit_population first")
         return polyfit_config(degree, st, weights)
 
+    def analyze(self, targets: Targets, spec: Analysis, _max_lds_rows: int = 0) -> AnalysisResult:
+        """DataAnalyzer's statistics of every experiment of `targets` as an AnalysisResult of DEVICE tensors, enqueued on the current torch stream (no
+        synchronisation; `objective` is the pattern): the scan and wtk_replay_analyze, the arrays `run(targets, analysis=spec).analysis` holds, bit for
+        bit.  The precise_error column is `run`'s (it needs wtk_replay_precise's per-pair errors)."""
+        import torch
+
+        E = self._check_targets(targets)
+        if "precise_error" in spec.columns:
+            raise ValueError("the precise_error column is computed by run(precise=True, analysis=...)")
+        with torch.cuda.device(self._dev):
+            stream, buf = self._stream(), self._objective_buffers(E)
+            hip.replay_scan(self._cfg, KINDS[targets.kind], E, self.n_cycles, self.track, self.n_track, targets.a, targets.b, targets.valid, self._share,
+                            buf["pos"], buf["move"], stream=stream)
+            return _enqueue_analysis(self.geometry, self.timing_config, spec, E, self.track, self.n_track, self._share, buf["pos"], buf["move"], None, stream,
+                                     _max_lds_rows)
+
     # ------------------------------------------------------------------ the loop
     def run(self, targets: Targets, rows: Sequence[int] = (0,), per_row_errors: bool = False, precise: bool = False,
-            _max_crop_px: int = 0) -> ReplayResult:
+            _max_crop_px: int = 0, analysis: Optional[Analysis] = None, _max_lds_rows: int = 0) -> ReplayResult:
         """Replay the E experiments of `targets`.  `rows`: the experiments whose full log rows are kept (16 doubles per row each).  `precise`: also the
         precise error of every experiment on the attached frames (`precise_summary`; with `per_row_errors` `precise_error` and `precise_counts`).
-        `_max_crop_px` (tests): the table limit of wtk_replay_precise, 0 = the default; results do not depend on it."""
+        `analysis`: also DataAnalyzer's statistics of every experiment (`res.analysis`; the precise_error column needs `precise`).
+        `_max_crop_px` (tests): the table limit of wtk_replay_precise, 0 = the default; results do not depend on it.  `_max_lds_rows` (tests): the
+        longest segment wtk_replay_analyze sorts in LDS, 0 = the default; results do not depend on it."""
         import torch
 
         if precise:
             self._need_frames()
-
+        if analysis is not None and "precise_error" in analysis.columns and not precise:
+            raise ValueError("the precise_error column needs run(precise=True) on attached frames")
         E, C, R = self._check_targets(targets), self.n_cycles, self.n_rows
         row_ids = sorted({int(e) for e in rows})
         if any(e < 0 or e >= E for e in row_ids):
@@ -558,8 +704,14 @@ class Replay:
                 hip.replay_precise(self._cfg, E, C, self.track, self.n_track, self._share, pos, move, fr, int(fr.shape[0]), int(fr.shape[1]), int(fr.shape[2]),
                                    self._background, self._diff_thresh, int(_max_crop_px), perr, pcounts, pb["summary"], pb["scratch"], pb["scratch"].numel(),
                                    stream=stream)
+            ana = None
+            if analysis is not None:  # (the per-pair errors [R, E] are the first R E doubles of wtk_replay_precise's scratch)
+                ana = _enqueue_analysis(self.geometry, self.timing_config, analysis, E, self.track, self.n_track, self._share, pos, move,
+                                        pb["scratch"] if precise else None, stream, _max_lds_rows)
             torch.cuda.current_stream(dev).synchronize()  # the one host synchronisation
             res = _result_of(self.geometry, pos, move, summary, row_ids, row_data, bbox, mse)
+            if ana is not None:
+                res.analysis = _analysis_to_host(ana)
             if precise:
                 res.precise_summary = _precise_summary_of(pb["summary"].cpu().numpy())
                 if per_row_errors:
@@ -681,10 +833,13 @@ class YoloReplay:
         r = slice(r0, r0 + n)
         self._call(self.log_detector, self._log_idx[r], self._frame_pos[r], n, self._det[r], self._det_conf[r], self._det_anchor[r])
 
-    def run(self) -> ReplayResult:
-        """Enqueue the whole experiment and wait for it once.  Two runs give the same bits."""
+    def run(self, analysis: Optional[Analysis] = None) -> ReplayResult:
+        """Enqueue the whole experiment and wait for it once.  Two runs give the same bits.  `analysis`: also DataAnalyzer's statistics of the log
+        (`res.analysis`, E = 1; the precise_error column is Replay's)."""
         import torch
 
+        if analysis is not None and "precise_error" in analysis.columns:
+            raise ValueError("YoloReplay has no precise_error column")
         C, R, dev = self.n_cycles, self.n_rows, self._dev
         with torch.cuda.device(dev):
             st = self._stream.cuda_stream
@@ -701,5 +856,11 @@ class YoloReplay:
                 hip.replay_rows(self._cfg, 1, C, self._track, R, self._share, self._pos, self._move, self._slots, 1, self._rows, None, None, self._summary,
                                 self._scratch, self._scratch.numel(), stream=st)
                 detections = self._det[:R].clone()
+                ana = None
+                if analysis is not None:
+                    ana = _enqueue_analysis(self.geometry, self.timing_config, analysis, 1, self._track, R, self._share, self._pos, self._move, None, st)
             self._finish()
-            return _result_of(self.geometry, self._pos, self._move, self._summary, [0], self._rows, detections=detections)
+            res = _result_of(self.geometry, self._pos, self._move, self._summary, [0], self._rows, detections=detections)
+            if ana is not None:
+                res.analysis = _analysis_to_host(ana)
+            return res
