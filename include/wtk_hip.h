@@ -153,7 +153,12 @@ int wtk_yolo_plan(wtk_yolo *h);
 
 /* frames: DEVICE pointer, uint8, [B][H][W][C] with C = 1 (gray; replicated to 3 channels as
  * yolo_controller.py:68-69 does) or C = 3 (BGR).  H x W is letterboxed to imgsz_h x imgsz_w
- * (identity when equal).  Outputs (DEVICE pointers, may be NULL except out_xywh):
+ * (identity when equal): resized by r = min(imgsz_h / H, imgsz_w / W) and padded with 114 to exactly imgsz_h x imgsz_w, the image
+ * centred (LetterBox(auto=False)).  One exception makes a handle created at the reference's own network shape for these frames
+ * (LetterBox(auto=True) at imgsz S = max(imgsz_h, imgsz_w): wtracker_amd.yolo_spec.letterbox_shape) resize as the reference does:
+ * where r' = min(S / H, S / W) gives a resized image that still fits the handle, r' is used.  The two differ only when the short
+ * side's product rounds DOWN onto the handle's side (435 x 579 into 288 x 384: 288 x 384, not 288 x 383).  The boxes are mapped
+ * back as scale_boxes does, from the two shapes alone.  Outputs (DEVICE pointers, may be NULL except out_xywh):
  *   out_xywh   [B][4] fp32: x_topleft, y_topleft, w, h in input-image pixels; 4 x NaN = none
  *   out_conf   [B]    fp32: score of the kept detection (0 when none)
  *   out_anchor [B]    int32: anchor index of the kept detection (-1 when none)

@@ -19,18 +19,30 @@ extern "C" int wtk_debug_stamps(unsigned long long *host, size_t n_words) {
 }
 #endif
 
-// ultralytics LetterBox geometry (auto=False: pad to exactly imgsz) + scale_boxes inverse
+// ultralytics LetterBox geometry + scale_boxes inverse: the ONE place the letterbox kernels and the head get their numbers from.
+// Forward (LetterBox): the reference scales by r = min(imgsz / H, imgsz / W) and pads the resized image up to the next stride multiple (auto=True), so a
+// handle created at that shape (yolo_spec.letterbox_shape) has imgsz = max(Sh, Sw), and the short side of the resized image may be a product that was
+// rounded DOWN onto Sh (435 x 579 at 384: 288.50 -> 288 rows, 384 columns; r taken from the handle's short side, 288 / 435, would give 383 columns).
+// So r comes from S = max(Sh, Sw) whenever the resized image fits the handle, and from r = min(Sh / H, Sw / W) (pad to exactly Sh x Sw, auto=False)
+// otherwise.  The two rules differ only where the short side binds and H * r rounds onto Sh, i.e. only on a letterbox_shape handle.
+// Inverse (scale_boxes) recomputes gain and padding from the two shapes alone, in doubles; only the results are rounded to float.
 static void letterbox_geom(int H, int W, int Sh, int Sw, int &new_h, int &new_w, int &top, int &left, float &gain, float &pad_x, float &pad_y) {
-    const double r = std::min((double)Sh / H, (double)Sw / W);
+    const int S = std::max(Sh, Sw);
+    double r = std::min((double)S / H, (double)S / W);
     new_w = (int)std::nearbyint(W * r);
     new_h = (int)std::nearbyint(H * r);
+    if (new_h > Sh || new_w > Sw) {
+        r = std::min((double)Sh / H, (double)Sw / W);
+        new_w = (int)std::nearbyint(W * r);
+        new_h = (int)std::nearbyint(H * r);
+    }
     const double dw = (Sw - new_w) / 2.0, dh = (Sh - new_h) / 2.0;
     top = (int)std::nearbyint(dh - 0.1);
     left = (int)std::nearbyint(dw - 0.1);
-    // scale_boxes recomputes gain/pad from the two shapes
-    gain = (float)std::min((double)Sh / H, (double)Sw / W);
-    pad_x = (float)std::nearbyint((Sw - W * (double)gain) / 2.0 - 0.1);
-    pad_y = (float)std::nearbyint((Sh - H * (double)gain) / 2.0 - 0.1);
+    const double g = std::min((double)Sh / H, (double)Sw / W);
+    gain = (float)g;
+    pad_x = (float)std::nearbyint((Sw - W * g) / 2.0 - 0.1);
+    pad_y = (float)std::nearbyint((Sh - H * g) / 2.0 - 0.1);
 }
 
 // outputs of the general NMS path (max_det >= 1 rows per image)
