@@ -113,7 +113,10 @@ typedef struct wtk_yolo_desc {
     int32_t imgsz_w;    /* network input width  (multiple of 32) */
     int32_t max_batch;  /* frames per forward pass the workspace is sized for */
     int32_t nc;         /* number of classes, 1 .. 80 (1 for the worm detector, yolo_train_config.yaml:27; 80 = a stock YOLOv8 head) */
-    float width_mult;   /* 0.50 for YOLOv8s */
+    float width_mult;   /* 0.50 for YOLOv8s.  Width rule: every channel width of the scale (64, 128, 256, 512, 1024, each capped at max_channels, times
+                         * width_mult, rounded up to 8) a multiple of 16, and the stem (the first of them) at most 64: YOLOv8 n, s, m and l.  wtk_yolo_create
+                         * refuses YOLOv8x (width 1.25: an 80-channel stem) with a message that names the stem width and the limit.  WTK_F16X3: multiples
+                         * of 64 (stem: 32 or 64), i.e. s and l. */
     float depth_mult;   /* 0.33 for YOLOv8s */
     int32_t max_channels; /* 1024 for YOLOv8s */
     int32_t n_convs;    /* must equal wtk_yolo_conv_count(width, depth, maxch, nc) */

@@ -352,7 +352,7 @@ def unobservable_blobs(scale="s", nc: int = 1, dtype: str = "fp16", plan: str = 
       shared bottleneck scratch (every plan): m.i.cv1 of every bottleneck but a C2f's last;
       fused front (front_fused_kernel: fp16 at scale s; front_fused_split_kernel: f16x3): model.0, model.1 unless WTK_FRONT_DEBUG=1;
       fused C2f tail (c2f32_fused_kernel, fp16 at scale s): model.2.m.0.cv1 and model.2.m.0.cv2;
-      fp16 implicit-GEMM tail (model.3 -> model.4.cv1 at scale s, model.5 -> model.6.cv1 at scale n): the strided 3x3;
+      fp16 implicit-GEMM tail (model.3 -> model.4.cv1 at scale s, model.5 -> model.6.cv1 at scale n, model.1 -> model.2.cv1 at scale l): the strided 3x3;
       folded Detect 1x1 tails (throughput plan, fp16 / f16x3, 64-wide box / 128-wide class towers): cv2.i.1 (box), cv3.i.1 (class;
       f16x3 unless WTK_NO_SPLIT_CLS_TAIL=1; nc <= 32)."""
     env = env or {}
@@ -371,7 +371,9 @@ def unobservable_blobs(scale="s", nc: int = 1, dtype: str = "fp16", plan: str = 
     if dtype == "fp16" and c[1] == 64 and n[0] == 1 and not on("WTK_NO_FUSED_C2F"):  # c2f_fused_eligible: hidden width 32, one bottleneck
         out += ["model.2.m.0.cv1", "model.2.m.0.cv2"]
     if dtype == "fp16" and not on("WTK_NO_IGEMM_TAIL"):  # a strided 3x3 of 128 couts whose only reader is the 1x1 128 -> 128 behind it
-        out += [f"model.{i}" for i, ci in ((3, c[2]), (5, c[3]), (7, c[4])) if ci == 128]
+        # (fuse_strided_tails walks every op: model.1 -> model.2.cv1 qualifies too where model.1 has 128 couts — scale l; the 1x1 behind a strided
+        # 3x3 of the backbone is a C2f's cv1, as wide as the 3x3, and the 3x3's only reader)
+        out += [f"model.{i}" for i, ci in ((1, c[1]), (3, c[2]), (5, c[3]), (7, c[4])) if ci == 128]
     if dtype in ("fp16", "f16x3") and plan == "throughput" and not on("WTK_NO_FUSED_TAIL") and not on("WTK_NO_HALO") and str(env.get("WTK_HALO_SLABS", "3")) != "2":
         if dims["hb"] == 64:
             out += [f"model.22.cv2.{i}.1" for i in range(3)]

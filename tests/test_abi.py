@@ -85,7 +85,7 @@ def test_every_environment_switch_is_documented():
         assert not re.search(r"\b%s\b" % name, readme), name
 
 
-@pytest.mark.parametrize("scale,nc", [("n", 1), ("s", 1), ("s", 80), ("m", 3)])
+@pytest.mark.parametrize("scale,nc", [("n", 1), ("s", 1), ("s", 80), ("m", 3), ("l", 1), ("x", 1)])
 def test_conv_table_matches_python_spec(hip_lib, scale, nc):
     w, d, m = ys.scale_params(scale)
     assert hip.yolo_conv_table(w, d, m, nc) == ys.conv_table(scale, nc)

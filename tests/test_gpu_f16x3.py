@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+from harness.conf_ref import oracle_conf
 from oracle import yolo_oracle as yo
 from wtracker_amd import frames as fr
 from wtracker_amd import hip
@@ -23,19 +24,25 @@ def _det(scale, hw, dtype, max_batch, nc=1, seed=0):
     return w, det, ys.model_dims(width, depth, maxch, nc)
 
 
-@pytest.mark.parametrize("size,B", [(128, 2), (256, 3), (352, 2)])
-def test_f16x3_head_logits_and_boxes_match_oracle(hip_lib, size, B):
-    w, det, dims = _det("s", (size, size), "f16x3", B)
+@pytest.mark.parametrize("scale,size,B", [pytest.param("s", 128, 2, id="128-2"), pytest.param("s", 256, 3, id="256-3"), pytest.param("s", 352, 2, id="352-2"),
+                                          pytest.param("l", 128, 2, id="l-128-2")])
+def test_f16x3_head_logits_and_boxes_match_oracle(hip_lib, scale, size, B):
+    """Scale l (widths 64 ... 512, six bottlenecks on a C2f, 256-wide class towers) beside s.  Its calibrated synthetic logits peak near -4.3, so its
+    threshold comes from the restatement's own scores (harness/conf_ref.py; frame seed 31: tests/test_gpu_yolo.py, E2E_FRAME_SEED)."""
+    w, det, dims = _det(scale, (size, size), "f16x3", B)
     oracle = yo.YoloOracle(w, dims)
-    frames, _ = fr.synthetic_frames(B, size, seed=11)
+    frames, _ = fr.synthetic_frames(B, size, seed=11 if scale == "s" else 31)
     with torch.no_grad():
         x, hw = yo.preprocess(list(frames), size)
         box_o, cls_o = oracle.forward(x)
-    xywh, conf, anchor = det.predict_host(frames, conf=0.1)
+    cf = 0.1 if scale == "s" else oracle_conf(cls_o.numpy(), 2 * F32_LOGIT_ATOL)[0]
+    xywh, conf, anchor = det.predict_host(frames, conf=cf)
     box_g, cls_g = det.debug_head(B)
     np.testing.assert_allclose(cls_g, cls_o.numpy(), rtol=1e-3, atol=F32_LOGIT_ATOL)
     np.testing.assert_allclose(box_g, box_o.numpy(), rtol=1e-3, atol=F32_LOGIT_ATOL)
-    xywh_o, conf_o, anchor_o = yo.postprocess(box_o, cls_o, (size, size), hw, conf=0.1)
+    xywh_o, conf_o, anchor_o = yo.postprocess(box_o, cls_o, (size, size), hw, conf=cf)
+    if scale != "s":
+        assert (anchor_o >= 0).any() and (anchor_o < 0).any() and np.isnan(xywh_o[anchor_o < 0]).all()
     np.testing.assert_array_equal(anchor, anchor_o)
     np.testing.assert_allclose(xywh, xywh_o, rtol=0, atol=F32_BOX_ATOL)
     np.testing.assert_allclose(conf, conf_o, rtol=0, atol=1e-4)
@@ -177,10 +184,13 @@ def test_f16x3_full_size_survivors_equal_oracle(hip_lib, size, B):
 
 
 def test_f16x3_rejects_scales_it_cannot_split(hip_lib):
-    w = ys.synthetic_weights("n", 1, seed=0)
-    depth, width, maxch = ys.SCALES["n"]
-    with pytest.raises(hip.WtkError, match="WTK_F16X3"):
-        hip.HipYolo(w, (128, 128), 1, dtype="f16x3", nc=1, width=width, depth=depth, max_channels=maxch)
+    for scale in ("n", "m"):  # widths 16 ... 256 and 48 ... 576: not multiples of 64
+        assert not ys.split_capable(scale)
+        w = ys.synthetic_weights(scale, 1, seed=0)
+        depth, width, maxch = ys.SCALES[scale]
+        with pytest.raises(hip.WtkError, match="WTK_F16X3"):
+            hip.HipYolo(w, (128, 128), 1, dtype="f16x3", nc=1, width=width, depth=depth, max_channels=maxch)
+    assert ys.split_capable("s") and ys.split_capable("l")
 
 
 def test_closed_loop_controller_in_auto_precision_equals_oracle_controller(hip_lib, tmp_path):

@@ -44,7 +44,7 @@ def _frames(B, H, W, seed=0):
     return np.random.default_rng(seed).integers(0, 256, size=(B, H, W), dtype=np.uint8)
 
 
-@pytest.mark.parametrize("scale,nc", [("s", 1), ("s", 20), ("s", 80), ("n", 1), ("n", 80)])
+@pytest.mark.parametrize("scale,nc", [("s", 1), ("s", 20), ("s", 80), ("n", 1), ("n", 80), ("m", 1), ("m", 20), ("l", 1), ("x", 1)])
 def test_graph_mirror_checks_the_oracle_to_zero_error(scale, nc):
     w = ys.synthetic_weights(scale, nc, seed=0)
     frames = _frames(2, 64, 96, seed=1)
@@ -159,9 +159,92 @@ def test_honest_arithmetic_of_each_mode_passes_with_composites(net):
     assert all(r.carried for r in rep.layers if r.name in ("model.2.cv1", "model.2.cv2", "model.4.cv1", "model.22.cv2.0.2", "model.22.cv3.2.2"))
 
 
+# ---- scales m and l: widths that are no power of two (48 ... 576), C2f depths [2, 4, 4, 2] and [3, 6, 6, 3] ---------------------------------
+WIDE = [("m", "fp32"), ("m", "fp16"), ("l", "fp32"), ("l", "f16x3"), ("l", "fp16")]  # f16x3 does not exist at m (ys.split_capable)
+WIDE_MAX_K = {"m": 9 * 576, "l": 9 * 512}
+
+
+@pytest.fixture(scope="module")
+def wide():
+    """scale -> (weights, frames, mode -> emulated tensors).  Seed 0: the draw the m and l gain tables were calibrated for."""
+    frames = _frames(2, 64, 96, seed=5)
+    out = {}
+    for scale in ("m", "l"):
+        w = ys.synthetic_weights(scale, 1, seed=0)
+        out[scale] = (w, frames, {m: emulate(w, frames, scale, 1, m) for s, m in WIDE if s == scale})
+    return out
+
+
+@pytest.mark.parametrize("scale,mode", WIDE)
+def test_honest_arithmetic_passes_its_bounds_at_scales_m_and_l(wide, scale, mode):
+    """The MODES constants were derived at scale s; they hold unchanged through four (m) and six (l) chained bottlenecks."""
+    w, frames, emu = wide[scale]
+    rep = lr.check_network(lr.DictSource(emu[mode]), w, frames, scale, 1, mode, label="emulated")
+    print(rep.table())
+    rep.assert_ok()
+    assert len(rep.layers) == len(ys.conv_table(scale, 1))
+    assert max(r.K for r in rep.layers) == WIDE_MAX_K[scale] and (scale, WIDE_MAX_K[scale]) in (("m", 5184), ("l", 4608))
+    # fp16 through six residual adds uses half of its per-element bound (0.50 measured at l): 0.6 here, 0.5 stays for scale s above
+    assert max(r.worst for r in rep.layers) < 0.6 and max(r.rms / r.rho for r in rep.layers) < 0.5, rep.table()
+    # the synthetic draw is calibrated: nothing near the fp16 range (uncalibrated, scale l reaches 3.5e5 behind model.15)
+    assert max(float(t.abs().max()) for t in emu[mode].values()) < 64.0
+
+
+@pytest.mark.parametrize("scale,dtype", [("m", "fp16"), ("l", "fp16"), ("l", "f16x3")])
+def test_honest_arithmetic_passes_with_composites_at_scales_m_and_l(wide, scale, dtype):
+    w, frames, emu = wide[scale]
+    unobs = lr.unobservable_blobs(scale, 1, dtype, "throughput")
+    rep = lr.check_network(lr.DictSource(emu[dtype]), w, frames, scale, 1, dtype, unobservable=unobs)
+    rep.assert_ok()
+    assert sum(r.family == "unobservable" for r in rep.layers) == len(unobs)
+    # a chain of shared-scratch bottlenecks: every m.i.cv2 but the last reads a composite, and so does the box tail
+    assert all(r.carried for r in rep.layers if r.name in ("model.4.m.0.cv2", "model.6.m.2.cv2", "model.22.cv2.1.2"))
+
+
+@pytest.mark.parametrize("mode,c0,blk", [("fp32", 92, 4), ("fp16", 64, 32)])
+def test_skipped_k_block_in_the_last_chunk_of_a_96_channel_3x3_fails(wide, mode, c0, blk):
+    """model.4.m.2.cv1 at m: 96 input channels are three 32-channel chunks (fp32) or one and a half 64-channel chunks (fp16)."""
+    name = "model.4.m.2.cv1"
+
+    def plant(y, L, x, r, W, b):
+        assert L.cin == 96 and L.cout == 96 and L.k == 3
+        xs = x.clone()
+        xs[:, c0:c0 + blk] = 0
+        yy = F.silu(F.conv2d(xs, W, b, stride=L.stride, padding=L.k // 2))
+        y[1, 80:96, :4, :4] = yy[1, 80:96, :4, :4].float()  # one tile: the last 16 couts x 4 x 4 pixels of frame 1
+        return y
+    net = wide["m"]
+    _failing(*_planted(net, mode, name, plant, scale="m")[:1], net[0], net[1], mode, name, scale="m")
+
+
+@pytest.mark.parametrize("mode", ["fp32", "fp16"])
+def test_two_output_channels_swapped_in_the_last_partial_cout_tile_fails(wide, mode):
+    """model.8.m.0.cv1 at m: 288 couts are four and a half 64-cout tiles (stored as 320) and nine 32-cout tiles; channels 256 ... 287 are the last."""
+    name = "model.8.m.0.cv1"
+
+    def plant(y, L, *_):
+        assert L.cout == 288
+        y[:, [259, 284]] = y[:, [284, 259]]
+        return y
+    net = wide["m"]
+    _failing(*_planted(net, mode, name, plant, scale="m")[:1], net[0], net[1], mode, name, scale="m")
+
+
+@pytest.mark.parametrize("mode", ["fp32", "fp16"])
+def test_residual_not_added_on_the_fourth_bottleneck_fails(wide, mode):
+    """model.6.m.3.cv2 at m: the residual is the third bottleneck's output, at channel offset 4 * 192 of a 6c-wide concat buffer."""
+    name = "model.6.m.3.cv2"
+
+    def plant(y, L, x, r, W, b):
+        assert r is not None and L.cin == 192
+        return (y.double() - r).float()
+    net = wide["m"]
+    _failing(*_planted(net, mode, name, plant, scale="m")[:1], net[0], net[1], mode, name, scale="m")
+
+
 # ---- planted defects --------------------------------------------------------------------------------------------------------------------
-def _ref_layer(emu, w, frames, name, x_override=None):
-    graph = lr.layer_graph("s", 1)
+def _ref_layer(emu, w, frames, name, x_override=None, scale="s"):
+    graph = lr.layer_graph(scale, 1)
     by = {L.name: L for L in graph}
     L = by[name]
     x, r = _inputs(L, {k: v.double() for k, v in emu.items()}, lr.stem_input(frames), by)
@@ -171,18 +254,18 @@ def _ref_layer(emu, w, frames, name, x_override=None):
     return L, x, r, W, b
 
 
-def _failing(emu, w, frames, mode, name):
-    rep = lr.check_network(lr.DictSource(emu), w, frames, "s", 1, mode)
+def _failing(emu, w, frames, mode, name, scale="s"):
+    rep = lr.check_network(lr.DictSource(emu), w, frames, scale, 1, mode)
     bad = {r.name: r for r in rep.failed}
     assert name in bad, rep.table()
     assert rep.failed[0].name == name, rep.table()  # found where it is: no layer before it fails (its consumers read the defective tensor)
     return bad[name]
 
 
-def _planted(net, mode, name, f):
+def _planted(net, mode, name, f, scale="s"):
     w, frames, emu = net
     t = dict(emu[mode])
-    t[name] = f(t[name].clone(), *_ref_layer(t, w, frames, name))
+    t[name] = f(t[name].clone(), *_ref_layer(t, w, frames, name, scale=scale))
     return t, w, frames
 
 
@@ -297,3 +380,28 @@ def test_unobservable_lists_follow_the_switches():
     assert lr.unobservable_blobs("s", 1, "f16x3", "latency") == shared + ["model.0", "model.1"]
     assert "model.22.cv3.0.1" not in lr.unobservable_blobs("s", 80, "fp16", "throughput")
     assert lr.unobservable_blobs("n", 1, "fp16", "throughput") == shared + ["model.5"] + [f"model.22.cv2.{i}.1" for i in range(3)]
+    # scales m and l: deeper C2f blocks (all bottlenecks of one C2f write ONE m.i.cv1 scratch tensor, Planner::c2f), a 64-wide box tower whose
+    # last 1x1 is folded in the fp16 / f16x3 throughput plans (fuse_detect_tails), and at l in fp16 the implicit-GEMM tail on model.1 (128 couts,
+    # stride 2) -> model.2.cv1 (128 -> 128), which fuse_strided_tails finds wherever it is (first seen on the GPU: model.1 read back stale and
+    # failed with model.2.cv1 behind it until this list named it).  Nothing else: no 32 / 64 front, no one-bottleneck 32-wide C2f, class towers
+    # 192 / 256 wide
+    box = [f"model.22.cv2.{i}.1" for i in range(3)]
+    tail = {("l", "fp16"): ["model.1"]}
+    for scale, n in (("m", [2, 4, 4, 2]), ("l", [3, 6, 6, 3])):
+        reps = zip(("model.2", "model.4", "model.6", "model.8", "model.12", "model.15", "model.18", "model.21"), n + [n[3]] * 4)
+        shared = [f"{p}.m.{i}.cv1" for p, r in reps for i in range(r - 1)]
+        assert len(shared) == sum(n) + 4 * n[3] - 8
+        for plan in ("throughput", "latency"):
+            assert lr.unobservable_blobs(scale, 1, "fp32", plan) == shared
+        for dt in ("fp16",) + (("f16x3",) if ys.split_capable(scale) else ()):
+            t = tail.get((scale, dt), [])
+            assert lr.unobservable_blobs(scale, 1, dt, "throughput") == shared + t + box
+            assert lr.unobservable_blobs(scale, 80, dt, "throughput") == shared + t + box
+            assert lr.unobservable_blobs(scale, 1, dt, "throughput", off) == shared
+            assert lr.unobservable_blobs(scale, 1, dt, "throughput", {"WTK_NO_HALO": "1"}) == shared + t  # (a strided 3x3 is an implicit GEMM anyway)
+            assert lr.unobservable_blobs(scale, 1, dt, "throughput", {"WTK_NO_IGEMM_TAIL": "1"}) == shared + box
+        if ys.split_capable(scale):
+            assert lr.unobservable_blobs(scale, 1, "f16x3", "latency") == shared  # the front of a 64-wide stem is not the fused one
+    assert ys.split_capable("l") and not ys.split_capable("m") and not ys.split_capable("x")
+    assert [f"model.4.m.{i}.cv1" in lr.unobservable_blobs("m", 1, "fp32", "throughput") for i in range(4)] == [True, True, True, False]
+    assert [f"model.6.m.{i}.cv1" in lr.unobservable_blobs("l", 1, "fp32", "throughput") for i in range(6)] == [True] * 5 + [False]

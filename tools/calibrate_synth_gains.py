@@ -50,7 +50,7 @@ def calibrate(scale: str, size: int = 320, n_frames: int = 4, seed: int = 0) -> 
 
 
 if __name__ == "__main__":
-    # default: the seed-0 tables of scales n and s;  `--seeds 1 2 3`: per-seed tables for scale s (synth_gain_s_seed<k>.json) — the factors are
+    # default: the seed-0 tables of scales n, s, m and l;  `--seeds 1 2 3`: per-seed tables for scale s (synth_gain_s_seed<k>.json) — the factors are
     # a property of the weight DRAW (measured round 3: with the seed-0 table a seed-1 net saturates every class score at 1.0)
     os.makedirs(os.path.join(ROOT, "wtracker_amd", "data"), exist_ok=True)
     if "--seeds" in sys.argv:
@@ -60,7 +60,7 @@ if __name__ == "__main__":
             json.dump(g, open(path, "w"), indent=0)
             print("s seed", seed, "gains min %.3f max %.3f" % (min(g.values()), max(g.values())), "->", path)
         sys.exit(0)
-    for scale in ("n", "s"):
+    for scale in ("n", "s", "m", "l"):
         g = calibrate(scale)
         path = os.path.join(ROOT, "wtracker_amd", "data", f"synth_gain_{scale}.json")
         json.dump(g, open(path, "w"), indent=0)

@@ -612,6 +612,9 @@ static int validate_desc(wtk_yolo **out, const wtk_yolo_desc *d, int32_t plan, M
     }
     for (int i = 0; i < 5; ++i)
         if (dims.c[i] % 16 != 0) return fail("wtk_yolo_create: channel widths must be multiples of 16 for this build");
+    // the stem kernel (stem_pool.hip: launch_stem) exists for 16, 32, 48 and 64 couts: YOLOv8 n / s / m / l; x (width 1.25) has an 80-cout stem
+    if (dims.c[0] > 64)
+        return fail("wtk_yolo_create: the stem (model.0) is " + std::to_string(dims.c[0]) + " channels wide; this build has stem kernels for at most 64 (YOLOv8 n, s, m and l)");
     if (dims.hb % 16 || dims.hc % 16) return fail("wtk_yolo_create: head widths must be multiples of 16");
     if (d->dtype == WTK_F16X3) {
         for (int i = 0; i < 5; ++i)

@@ -22,6 +22,8 @@ SCALES = {
     "n": (0.33, 0.25, 1024),
     "s": (0.33, 0.50, 1024),
     "m": (0.67, 0.75, 768),
+    "l": (1.0, 1.0, 512),
+    "x": (1.0, 1.25, 512),  # described, not runnable: wtk_yolo_create refuses a stem wider than 64 (include/wtk_hip.h)
 }
 REG_MAX = 16
 STRIDES = (8, 16, 32)
@@ -146,7 +148,7 @@ _DATA_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data")
 
 
 def _stored_gains(scale, seed: int = 0) -> dict:
-    """Per-conv scale factors measured once by tools/calibrate_synth_gains.py (63 floats per scale).  They belong to a weight DRAW:
+    """Per-conv scale factors measured once by tools/calibrate_synth_gains.py (one float per conv: 63 at n and s, 83 at m, 103 at l).  They belong to a weight DRAW:
     seed 0 uses synth_gain_<scale>.json, another seed its own synth_gain_<scale>_seed<k>.json where one was calibrated (scale s, seeds
     1-3) and the seed-0 table otherwise (with it a different draw may drift: seed 1 at scale s saturates every class score)."""
     if isinstance(scale, str):
