@@ -32,7 +32,11 @@ ENVS = {
     "ungrouped": {"WTK_SK_GROUP": "0", "WTK_SK_AUTOTUNE": "0"},
 }
 # the `full` matrix (handles above 16 frames: the sparse region, the list grids, ws64, the persistent window form, the 1280 geometry) runs in one
-FULL_ENVS = {"full": {"WTK_SK_AUTOTUNE": "0"}}
+FULL_ENVS = {
+    "full": {"WTK_SK_AUTOTUNE": "0"},
+    # the window launchers' remaining branches: two weight slabs, one tile per block, 256-pixel blocks only (NWB = 2 in fp16 and fp32; no pkernel, no ws64)
+    "two-slab": {"WTK_SK_AUTOTUNE": "0", "WTK_HALO_SLABS": "2", "WTK_HALO_PERSIST": "0", "WTK_HALO_SMALL_BLOCKS": "0"},
+}
 TRACE_FIXTURE_FULL = os.path.join(ROOT, "tests", "golden", "launch_trace_full.json")
 TRACES = {"quick": (ENVS, TRACE_FIXTURE, 900), "full": (FULL_ENVS, TRACE_FIXTURE_FULL, 1500)}
 HOST_ONLY = ["--cuda-host-only", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function", "-Wno-unused-variable"]

@@ -25,6 +25,7 @@ int stub_live_execs(void);
 int stub_open_captures(void);
 unsigned long long stub_kernel_launches(const char *substr);
 void stub_set_verbose(int);
+void stub_selftest_window_variant(int bn);
 long long stub_fail_malloc(long long n);
 // the slice of the HIP API the driver itself needs (device buffers of a caller)
 int hipMalloc(void **, size_t);
@@ -505,9 +506,15 @@ static int selftest() {
     v = stub_violations();
     hipFree(buf2), hipFree(buf2);
     expect("double free", v);
+    v = stub_violations();
+    // a window launch whose symbol names another instantiation than halo_variant derives from its arguments (launch_checks.inc); the right one passes
+    stub_selftest_window_variant(128);
+    CHECK(stub_violations() == v, "the variant check flags a launch of the instantiation its arguments ask for");
+    stub_selftest_window_variant(64);
+    expect("launch of another window instantiation than its arguments ask for", v);
     hipFree(buf);
     std::fprintf(stderr, "[hostsan] selftest: %d of %d deliberate violations flagged\n", flagged, expected);
-    return flagged == expected ? 0 : 1;
+    return flagged == expected && !g_fail ? 0 : 1;
 }
 
 // the closing report and checks of every mode but the selftest

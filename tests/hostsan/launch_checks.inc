@@ -95,6 +95,20 @@ static void check_halo_args(const char *kn, const wtk::HaloArgs &a, int es, bool
     if (a.CoutPad < a.Cout) fail(kn, "CoutPad < Cout");
 }
 
+// The window family: the instantiation a launch names (the template integers of its symbol: conv3x3_halo_kernel<T, BN, NHALO, MINW, NWB, HROWS, BMT, TAIL,
+// SPLIT>, conv3x3_halo_pkernel<T, BN, HROWS>) must be the one wtk::halo_variant derives from the launch's own argument struct
+static void check_halo_variant(const char *kn, const TArgs &t, bool persistent, const wtk::HaloArgs &a) {
+    const std::vector<long long> &i = t.ints;
+    if (i.size() != (persistent ? 2u : 8u) || t.f16 == t.f32) return fail(kn, "template arguments of the symbol not understood");
+    const wtk::HaloVariant named = persistent ? wtk::HaloVariant{t.f16, (int)i[0], 2, 2, 3, (int)i[1], 256, 0, 0, 1}
+                                              : wtk::HaloVariant{t.f16, (int)i[0], (int)i[1], (int)i[2], (int)i[3], (int)i[4], (int)i[5], (int)i[6], (int)i[7], 0};
+    wtk::HaloVariant v;
+    if (!wtk::halo_variant(a, named.split ? wtk::HALO_SPLIT : t.f16 ? wtk::HALO_F16 : wtk::HALO_F32, &v))
+        fail(kn, "halo_variant has no instantiation for the arguments of this launch");
+    else if (!(v == named))
+        fail(kn, "the launched instantiation is not the one halo_variant names for its arguments");
+}
+
 // returns the size of the kernel's argument struct (args[0]) for the launch trace, 0 for a kernel that is not listed here
 static size_t check_launch(const std::string &name, dim3 grid, dim3 block, void **args) {
     (void)grid, (void)block;
@@ -156,6 +170,17 @@ static size_t check_launch(const std::string &name, dim3 grid, dim3 block, void 
         // conv3x3_halo_kernel<T, BN, NHALO, MINW, NWB, HROWS, BMT, TAIL, SPLIT>
         const bool split = !persistent && t.ints.size() >= 8 && t.ints.back() == 1;
         check_halo_args(persistent ? "conv3x3_halo_pkernel" : "conv3x3_halo_kernel", *reinterpret_cast<const wtk::HaloArgs *>(args[0]), t.f16 ? 2 : 4, split, false);
+        check_halo_variant(persistent ? "conv3x3_halo_pkernel" : "conv3x3_halo_kernel", t, persistent, *reinterpret_cast<const wtk::HaloArgs *>(args[0]));
+    } else if (has("halo_list_kernel")) {
+        // halo_list_kernel<TAIL>: every member, on the block size of the list and without the knobs the list kernel does not read, must come out as the list
+        // kernel's fixed tile.  (bytes stays 0: the recorded traces hash no argument struct for this kernel.)
+        const TArgs t = parse_targs(name, "halo_list_kernel");
+        wtk::HaloVariant want = wtk::kHaloListVariant, v;
+        want.tail = !t.ints.empty() && t.ints[0] == 1;
+        for (wtk::HaloArgs m : reinterpret_cast<const wtk::HaloListArgs *>(args[0])->m) {
+            m.bm = want.bmt, m.deep = 0;
+            if (!wtk::halo_variant(m, wtk::HALO_SPLIT, &v) || !(v == want)) fail("halo_list_kernel", "a member does not come out as kHaloListVariant");
+        }
     } else if (has("conv3x3_ws64_kernel")) {
         bytes = sizeof(wtk::HaloArgs);
         check_halo_args("conv3x3_ws64_kernel", *reinterpret_cast<const wtk::HaloArgs *>(args[0]), 2, false, false);
@@ -257,3 +282,12 @@ static size_t check_launch(const std::string &name, dim3 grid, dim3 block, void 
 }
 
 } // namespace stubchk
+
+// selftest hook (driver.cpp): the variant check on a launch of conv3x3_halo_kernel<fp16, bn, 2, 2, 3, 432, 256, false, false> whose arguments — 64 -> 128
+// channels, three slabs, 256-pixel blocks — ask for the 128-cout tile of that shape
+extern "C" void stub_selftest_window_variant(int bn) {
+    wtk::HaloArgs a{};
+    a.Cin = 64, a.Cout = a.CoutPad = 128, a.strips = a.blocks_per_strip = 1, a.slabs = 3;
+    const std::string name = "conv3x3_halo_kernelIDF16_Li" + std::to_string(bn) + "ELi2ELi2ELi3ELi432ELi256ELb0ELb0EE";
+    stubchk::check_halo_variant("conv3x3_halo_kernel", stubchk::parse_targs(name, "conv3x3_halo_kernel"), false, a);
+}

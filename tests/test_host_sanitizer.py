@@ -26,9 +26,10 @@ def _ok(r):
 
 
 def test_launch_layer_flags_deliberate_violations():
-    """The checker checks: eleven protocol / memory violations committed on purpose through the stub's HIP API are all reported."""
+    """The checker checks: eleven protocol / memory violations committed on purpose through the stub's HIP API, and a window launch whose symbol
+    names another instantiation than its arguments ask for, are all reported."""
     r = hostsan.run("selftest")
-    assert r.returncode == 0 and "11 of 11 deliberate violations flagged" in r.stdout, r.stdout[-3000:]
+    assert r.returncode == 0 and "12 of 12 deliberate violations flagged" in r.stdout, r.stdout[-3000:]
 
 
 @pytest.mark.parametrize("env", list(hostsan.ENVS.values()), ids=list(hostsan.ENVS))  # default, suite-env, ungrouped: see tests/hostsan/build.py
@@ -83,6 +84,6 @@ def test_host_side_is_clean_over_the_full_matrix():
 
 def test_full_matrix_launch_trace_matches_the_recorded_one():
     """The same pin over the `full` matrix (tests/golden/launch_trace_full.json, recorded on the commit BEFORE wtk_yolo_create_planned was split into passes): the
-    handles above 16 frames, which the quick matrix never creates — the sparse region and the list grids, ws64, the persistent window form, the 1280 geometry.
+    handles above 16 frames, which the quick matrix never creates — the sparse region and the list grids, ws64, the persistent window form, the 1280 geometry; and in a second environment the two-slab window kernels.
     Re-recorded with `python tests/hostsan/build.py trace full --record`."""
     _trace_matches("full")

@@ -24,7 +24,7 @@ int main(int argc, char **argv) {
     wtk::HaloArgs a{};
     a.in = din, a.in_ld = C, a.N = N, a.H = HW, a.W = HW, a.Cin = C, a.Cout = CO, a.CoutPad = CO, a.w = dw, a.bias = db, a.out = dout, a.out_ld = CO, a.act = 1, a.Kpad = 9 * C, a.zeros = dz, a.slabs = slabs;
     wtk::halo_geometry_stacked(N, HW, HW, wtk::halo_rows_max(CO, slabs), &a.S, &a.pitch, &a.strips, &a.blocks_per_strip);
-    const int bn = wtk::halo_cout_tile(CO);
+    const int bn = wtk::halo_cout_tile(CO, wtk::HALO_F16);
     const long long blocks = (long long)a.strips * a.blocks_per_strip * (CO / bn);
     CK(hipMalloc(&dst, blocks * 8 * 4 * 8));
     CK(hipMemset(dst, 0, blocks * 8 * 4 * 8));

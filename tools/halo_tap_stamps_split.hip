@@ -20,7 +20,7 @@ int main(int argc, char **argv) {
     wtk::HaloArgs a{};
     a.in = din, a.in_ld = 2 * C, a.N = N, a.H = HW, a.W = HW, a.Cin = 2 * C, a.Cout = CO, a.CoutPad = CO, a.w = dw, a.bias = db, a.out = dout, a.out_ld = 2 * CO, a.act = 1, a.Kpad = 9 * 2 * C, a.zeros = dz, a.slabs = 3; // pseudo-channels
     wtk::halo_geometry_stacked(N, HW, HW, wtk::kHaloRowsMax, &a.S, &a.pitch, &a.strips, &a.blocks_per_strip);
-    const int bn = wtk::split_halo_cout_tile(CO);
+    const int bn = wtk::halo_cout_tile(CO, wtk::HALO_SPLIT);
     const long long blocks = (long long)a.strips * a.blocks_per_strip * (CO / bn);
     CK(hipMalloc(&dst, blocks * 8 * 4 * 8)); CK(hipMemset(dst, 0, blocks * 8 * 4 * 8));
     a.dbg_stamps = dst;

@@ -405,120 +405,125 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_pkernel(const HaloArgs a)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the final tile's duplicate requests must not outlive the block's LDS
 }
 
-template <typename T, int BN, int HROWS> hipError_t launch_hp(HaloArgs a, int num_cus, hipStream_t stream) {
-    const long long tiles = (long long)a.strips * a.blocks_per_strip * (a.CoutPad / BN);
-    if (tiles <= 0 || tiles > 0x3fffffffLL || num_cus < 8) return hipErrorInvalidValue;
-    if (kBM + 2 * a.pitch + 2 > HROWS || (a.Cin / (8 * Elem<T>::CE)) % 2 != 0) return hipErrorInvalidValue;
-    a.d_nct = make_fastdiv((unsigned)(a.CoutPad / BN));
-    a.d_bps = make_fastdiv((unsigned)a.blocks_per_strip);
-    a.d_strips = make_fastdiv((unsigned)a.strips);
-    a.d_pitch = make_fastdiv((unsigned)a.pitch);
-    a.d_h1 = make_fastdiv((unsigned)(a.H + 1));
-    const long long cap = num_cus / 8 * 8; // one block per CU (156-160 KB of LDS); a multiple of 8 keeps a block's tiles on its XCD label
-    const unsigned grid = (unsigned)(tiles < cap ? tiles : cap);
-    a.grid = (int)grid;
-    hipLaunchKernelGGL((conv3x3_halo_pkernel<T, BN, HROWS>), dim3(grid), dim3(512), 0, stream, a);
-    return hipGetLastError();
+// The instantiations the library holds, one row each: `v` (halo_variant, below) -> launch.  ROW2: the row at 256 and at 128 pixels per block.
+hipError_t launch_variant(const HaloArgs &a, const HaloVariant &v, hipStream_t stream) {
+    using H = _Float16;
+    constexpr int MAX = kHaloRowsMax, SMALL = kHaloRowsSmall;
+#define LAUNCH(...) { hipLaunchKernelGGL((__VA_ARGS__), dim3((unsigned)a.grid), dim3(512), 0, stream, a); return hipGetLastError(); }
+#define ROW(T, BN, NHALO, MINW, NWB, HROWS, BMT, TAIL, SPLIT) \
+    if (v == HaloVariant{sizeof(T) == 2, BN, NHALO, MINW, NWB, HROWS, BMT, TAIL, SPLIT, 0}) LAUNCH(conv3x3_halo_kernel<T, BN, NHALO, MINW, NWB, HROWS, BMT, TAIL, SPLIT>)
+#define ROW2(T, BN, NHALO, MINW, NWB, HROWS, TAIL, SPLIT) ROW(T, BN, NHALO, MINW, NWB, HROWS, 256, TAIL, SPLIT) ROW(T, BN, NHALO, MINW, NWB, HROWS, 128, TAIL, SPLIT)
+#define PROW(T, BN, HROWS) if (v == HaloVariant{sizeof(T) == 2, BN, 2, 2, 3, HROWS, kBM, 0, 0, 1}) LAUNCH(conv3x3_halo_pkernel<T, BN, HROWS>)
+    // 128 / 192 couts on two window buffers; 64 couts on one buffer and four blocks' worth of registers when the layer is a single channel chunk, on two
+    // otherwise.  Three weight slabs + counted vmcnt (192 couts: room for 352-row windows only), or the two-slab / vmcnt(0) schedule at 256 pixels
+    ROW2(H, 128, 2, 2, 3, MAX, false, false) ROW(H, 128, 2, 2, 2, MAX, 256, false, false) ROW2(float, 128, 2, 2, 3, MAX, false, false) ROW(float, 128, 2, 2, 2, MAX, 256, false, false)
+    ROW2(H, 192, 2, 2, 3, SMALL, false, false) ROW(H, 192, 2, 2, 2, MAX, 256, false, false) ROW2(float, 192, 2, 2, 3, SMALL, false, false) ROW(float, 192, 2, 2, 2, MAX, 256, false, false)
+    ROW2(H, 64, 1, 4, 3, MAX, false, false) ROW(H, 64, 1, 4, 2, MAX, 256, false, false) ROW2(float, 64, 1, 4, 3, MAX, false, false) ROW(float, 64, 1, 4, 2, MAX, 256, false, false)
+    ROW2(H, 64, 2, 2, 3, MAX, false, false) ROW(H, 64, 2, 2, 2, MAX, 256, false, false) ROW2(float, 64, 2, 2, 3, MAX, false, false) ROW(float, 64, 2, 2, 2, MAX, 256, false, false)
+    // ... with the fused 1x1 tail (fp16, three slabs)
+    ROW2(H, 128, 2, 2, 3, MAX, true, false) ROW2(H, 64, 1, 4, 3, MAX, true, false) ROW2(H, 64, 2, 2, 3, MAX, true, false)
+    // split-fp16 operands: three slabs, plain and with the tail; the six-slab ring of the 64-cout x 128-pixel tile
+    ROW2(H, 128, 2, 2, 3, MAX, false, true) ROW2(H, 64, 2, 2, 3, MAX, false, true) ROW(H, 64, 2, 1, 6, MAX, 128, false, true)
+    ROW2(H, 128, 2, 2, 3, MAX, true, true) ROW2(H, 64, 2, 2, 3, MAX, true, true)
+    // persistent form
+    PROW(H, 128, MAX) PROW(H, 192, SMALL) PROW(float, 128, MAX) PROW(float, 192, SMALL)
+#undef LAUNCH
+#undef ROW
+#undef ROW2
+#undef PROW
+    return hipErrorInvalidValue; // (halo_variant names rows of this table alone)
 }
 
-template <typename T, int BN, int NHALO, int MINW, int NWB, int HROWS, int BMT = 256, bool TAIL = false, bool SPLIT = false> hipError_t launch_h(HaloArgs a, hipStream_t stream) {
-    const long long blocks = (long long)a.strips * a.blocks_per_strip * (a.CoutPad / BN);
-    if (blocks <= 0 || blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-    if (BMT + 2 * a.pitch + 2 > HROWS || (long long)a.blocks_per_strip * BMT < (long long)a.N * (a.H + 1) * a.pitch) return hipErrorInvalidValue;
-    // live mask: word-aligned, and every unit a block looks at lies inside its strip's row of the mask
-    if (a.live_off && ((a.live_off & 3u) || (a.live_ld & 1) || (long long)a.live_ld * 128 < (long long)a.blocks_per_strip * BMT)) return hipErrorInvalidValue;
-    a.d_nct = make_fastdiv((unsigned)(a.CoutPad / BN));
-    a.d_bps = make_fastdiv((unsigned)a.blocks_per_strip);
-    a.d_strips = make_fastdiv((unsigned)a.strips);
-    a.d_pitch = make_fastdiv((unsigned)a.pitch);
-    a.d_h1 = make_fastdiv((unsigned)(a.H + 1));
-    a.grid = (int)blocks;
-    hipLaunchKernelGGL((conv3x3_halo_kernel<T, BN, NHALO, MINW, NWB, HROWS, BMT, TAIL, SPLIT>), dim3((unsigned)blocks), dim3(512), 0, stream, a);
-    return hipGetLastError();
+// strip geometry as halo_geometry_stacked lays it out, inside the largest window
+bool halo_strips_ok(const HaloArgs &a) {
+    return a.pitch == (a.strips == 1 ? a.S + 1 : a.S + 2) && kBM + 2 * a.pitch + 2 <= kHaloRowsMax && a.strips * a.S >= a.W && (a.strips != 1 || a.S == a.W);
 }
 
-// The variant of one tile shape (T, BN, NHALO, MINW): weight ring (nwb = 3, or 2 = the two-slab / vmcnt(0) schedule, 256-pixel blocks only), pixels per
-// block and fused tail.  A 192-cout tile with three slabs only leaves room for 352-row windows (the planner then cuts wide maps into strips of <= 45 columns).
-template <typename T, int BN, int NHALO, int MINW, bool SPLIT = false> hipError_t launch_h_tile(const HaloArgs &a, int nwb, int bm, hipStream_t stream) {
-    constexpr int HR3 = BN == 192 ? kHaloRowsSmall : kHaloRowsMax;
-    if (a.tail_w) { // validated by the caller: fp16, 64- or 128-cout tile, three slabs
-        if constexpr (sizeof(T) == 2 && BN != 192)
-            return bm == 128 ? launch_h<T, BN, NHALO, MINW, 3, kHaloRowsMax, 128, true, SPLIT>(a, stream) : launch_h<T, BN, NHALO, MINW, 3, kHaloRowsMax, 256, true, SPLIT>(a, stream);
-        return hipErrorInvalidValue;
-    }
-    if (nwb != 2) return bm == 128 ? launch_h<T, BN, NHALO, MINW, 3, HR3, 128, false, SPLIT>(a, stream) : launch_h<T, BN, NHALO, MINW, 3, HR3, 256, false, SPLIT>(a, stream);
-    if constexpr (!SPLIT) {
-        if (bm == kBM) return launch_h<T, BN, NHALO, MINW, 2, kHaloRowsMax>(a, stream);
-    }
-    return hipErrorInvalidValue;
+// A launch on split operands, tile and grid apart: every channel count / offset of `a` but Cout / CoutPad in pseudo-channels (2 x real)
+bool split_args_ok(const HaloArgs &a) {
+    if (a.Cout != a.CoutPad || a.in_ld % 64 || a.in_coff % 64 || a.out_ld % 64 || a.out_coff % 64 || a.Kpad != 9 * a.Cin || !halo_strips_ok(a)) return false;
+    // fused 1x1 tail: 64 -> 64 couts (box towers), split weights [64][tail_kpad = 128 pseudo-channels]; 128 -> <= 32 stored couts with fp32 output
+    // (class towers), split weights [32][tail_kpad = 256 pseudo-channels]
+    if (a.tail_w && a.Cout == 128) {
+        if (a.res || a.out2 || !a.tail_bias || !a.tail_out || a.tail_kpad != 256 || a.tail_cout < 1 || a.tail_cout > 32 || !a.tail_f32 || a.tail_ld % 4 || a.tail_coff % 4) return false;
+    } else if (a.tail_w && (a.Cout != 64 || a.res || a.out2 || !a.tail_bias || !a.tail_out || a.tail_kpad != 128 || a.tail_cout != 64 || (a.tail_f32 ? (a.tail_ld % 4 || a.tail_coff % 4) : (a.tail_ld % 64 || a.tail_coff % 64))))
+        return false;
+    return !(a.res && (a.res_ld % 64 || a.res_coff % 64)) && !(a.out2 && (a.out2_ld % 64 || a.out2_coff % 64));
 }
-// ... and the tile shape of a layer: 128 / 192 couts on two window buffers; 64 couts on one buffer and four blocks' worth of registers when the layer is a
-// single channel chunk, on two otherwise
-template <typename T> hipError_t launch_h_any(const HaloArgs &a, int bn, int nchunks, int nwb, int bm, hipStream_t stream) {
-    if (bn == 128) return launch_h_tile<T, 128, 2, 2>(a, nwb, bm, stream);
-    if (bn == 192) return launch_h_tile<T, 192, 2, 2>(a, nwb, bm, stream);
-    if (nchunks == 1) return launch_h_tile<T, 64, 1, 4>(a, nwb, bm, stream);
-    return launch_h_tile<T, 64, 2, 2>(a, nwb, bm, stream);
+
+// What both launchers do behind their argument checks: the grid of `v` must cover the strips' stacked rows inside its window; FastDiv fields, grid, launch
+hipError_t launch_h(HaloArgs a, const HaloVariant &v, hipStream_t stream) {
+    const long long tiles = (long long)a.strips * a.blocks_per_strip * (a.CoutPad / v.bn);
+    if (tiles <= 0 || tiles > (v.persistent ? 0x3fffffffLL : 0x7fffffffLL) || (v.persistent && a.persist_cus < 8)) return hipErrorInvalidValue;
+    if (v.bmt + 2 * a.pitch + 2 > v.hrows || (long long)a.blocks_per_strip * v.bmt < (long long)a.N * (a.H + 1) * a.pitch) return hipErrorInvalidValue;
+    // live mask (one tile per block): word-aligned, and every unit a block looks at lies inside its strip's row of the mask
+    if (!v.persistent && a.live_off && ((a.live_off & 3u) || (a.live_ld & 1) || (long long)a.live_ld * 128 < (long long)a.blocks_per_strip * v.bmt)) return hipErrorInvalidValue;
+    a.d_nct = make_fastdiv((unsigned)(a.CoutPad / v.bn)), a.d_bps = make_fastdiv((unsigned)a.blocks_per_strip), a.d_strips = make_fastdiv((unsigned)a.strips);
+    a.d_pitch = make_fastdiv((unsigned)a.pitch), a.d_h1 = make_fastdiv((unsigned)(a.H + 1));
+    const long long cap = a.persist_cus / 8 * 8; // persistent: one block per CU (156-160 KB of LDS); a multiple of 8 keeps a block's tiles on its XCD label
+    a.grid = (int)(v.persistent && cap < tiles ? cap : tiles);
+    return launch_variant(a, v, stream);
 }
 
 } // namespace
 
-bool halo_eligible(int k, int stride, int cin, int is_f16) {
-    const int cch = is_f16 ? 64 : 32;
-    return k == 3 && stride == 1 && cin % cch == 0;
-}
+bool halo_eligible(int k, int stride, int cin, int is_f16) { return k == 3 && stride == 1 && cin % (is_f16 ? 64 : 32) == 0; }
 
 // split-fp16 operands: real channel counts here; 64- or 128-cout tiles only (two accumulator sets)
 bool split_halo_eligible(int k, int stride, int cin, int cout) { return k == 3 && stride == 1 && cin % 32 == 0 && cout % 64 == 0; }
-int split_halo_cout_tile(int cout_stored) { return cout_stored % 128 == 0 ? 128 : 64; }
 
-// Every channel count / offset of `a` but Cout / CoutPad in pseudo-channels (2 x real); three weight slabs, one tile per block
-hipError_t launch_conv3x3_halo_split(const HaloArgs &a, hipStream_t stream) {
-    const int bn = (a.narrow && !a.tail_w) ? 64 : split_halo_cout_tile(a.Cout);
-    if (a.Cin % 64 != 0 || a.CoutPad % bn != 0 || a.Cout != a.CoutPad || a.slabs == 2) return hipErrorInvalidValue;
-    // fused 1x1 tail: 64 -> 64 couts (box towers), split weights [64][tail_kpad = 128 pseudo-channels]; 128 -> <= 32 stored couts with fp32 output
-    // (class towers), split weights [32][tail_kpad = 256 pseudo-channels]
-    if (a.tail_w && a.Cout == 128) {
-        if (a.res || a.out2 || !a.tail_bias || !a.tail_out || a.tail_kpad != 256 || a.tail_cout < 1 || a.tail_cout > 32 || !a.tail_f32 || a.tail_ld % 4 || a.tail_coff % 4) return hipErrorInvalidValue;
-    } else if (a.tail_w && (a.Cout != 64 || a.res || a.out2 || !a.tail_bias || !a.tail_out || a.tail_kpad != 128 || a.tail_cout != 64 || (a.tail_f32 ? (a.tail_ld % 4 || a.tail_coff % 4) : (a.tail_ld % 64 || a.tail_coff % 64))))
-        return hipErrorInvalidValue;
-    if (a.in_ld % 64 || a.in_coff % 64 || a.out_ld % 64 || a.out_coff % 64 || a.Kpad != 9 * a.Cin) return hipErrorInvalidValue;
-    if (a.pitch != (a.strips == 1 ? a.S + 1 : a.S + 2) || kBM + 2 * a.pitch + 2 > kHaloRowsMax || a.strips * a.S < a.W || (a.strips == 1 && a.S != a.W))
-        return hipErrorInvalidValue;
-    const int bm = a.bm == 128 ? 128 : kBM;
-    if ((long long)a.blocks_per_strip * bm < (long long)a.N * (a.H + 1) * a.pitch) return hipErrorInvalidValue;
-    if (a.res && (a.res_ld % 64 || a.res_coff % 64)) return hipErrorInvalidValue;
-    if (a.out2 && (a.out2_ld % 64 || a.out2_coff % 64)) return hipErrorInvalidValue;
-    // six-slab ring: the 64-cout x 128-pixel tile only (the 256-pixel tile, 24 MFMAs per wave and tap, measured the same with either ring)
-    if (bn == 64 && !a.tail_w && a.deep && bm == 128) return launch_h<_Float16, 64, 2, 1, 6, kHaloRowsMax, 128, false, true>(a, stream);
-    return bn == 128 ? launch_h_tile<_Float16, 128, 2, 2, true>(a, 3, bm, stream) : launch_h_tile<_Float16, 64, 2, 2, true>(a, 3, bm, stream);
+int halo_cout_tile(int cout_stored, int mode) { return cout_stored % 128 == 0 ? 128 : (mode != HALO_SPLIT && cout_stored % 192 == 0) ? 192 : 64; }
+
+bool halo_variant(const HaloArgs &a, int mode, HaloVariant *v) {
+    const bool split = mode == HALO_SPLIT, f16 = mode != HALO_F32, tail = a.tail_w != nullptr;
+    const int cch = f16 ? 64 : 32; // channels of a.Cin per 128-byte window row (split: pseudo-channels)
+    // narrow: 64-cout tiles for a thin grid (small handles); a layer with a fused tail keeps its own tile
+    const int bn = (a.narrow && !tail && a.CoutPad % 64 == 0) ? 64 : halo_cout_tile(a.Cout, mode);
+    const int bm = a.bm == 128 ? 128 : kBM, nwb = a.slabs == 2 ? 2 : 3, nchunks = a.Cin / cch;
+    if (a.Cin % cch != 0 || a.CoutPad % bn != 0) return false;
+    // the fused 1x1 tail exists for the fp16 64-cout (-> 64) and 128-cout (-> 32) three-slab variants only; the two-slab / vmcnt(0) schedule for plain
+    // 256-pixel blocks of fp16 / fp32 operands
+    if ((tail && (!f16 || bn == 192)) || (nwb == 2 && (tail || split || bm != kBM))) return false;
+    // one tile per block on two window buffers; 192 couts with three slabs: 352-row windows (the planner then cuts wide maps into strips of <= 45 columns)
+    *v = HaloVariant{f16, bn, 2, 2, nwb, (bn == 192 && nwb == 3) ? kHaloRowsSmall : kHaloRowsMax, bm, tail, split, 0};
+    const long long tiles = (long long)a.strips * a.blocks_per_strip * (a.CoutPad / bn);
+    if (split) {
+        // six-slab ring: the 64-cout x 128-pixel tile only (the 256-pixel tile, 24 MFMAs per wave and tap, measured the same with either ring)
+        if (bn == 64 && !tail && a.deep && bm == 128) v->minw = 1, v->nwb = 6;
+    } else if (nwb == 3 && !tail && bm == kBM && a.persist_cus > 0 && 2 * tiles >= 3 * (long long)a.persist_cus && nchunks % 2 == 0 && bn != 64) {
+        // persistent form only where a block gets to walk several tiles (measured: -5..-8 % at 6-7 tiles per CU, -1..2 % at 1.75, but
+        // +4 % when every block has exactly one tile: its per-tile bookkeeping then buys nothing)
+        v->persistent = 1;
+    } else if (bn == 64 && nchunks == 1) {
+        v->nhalo = 1, v->minw = 4; // a single channel chunk: one window buffer, four blocks' worth of registers
+    }
+    return true;
 }
 
-// The three levels of one box-tower stage from a live-tile list.  Each member must be what launch_conv3x3_halo_split would run on ONE 64-cout tile (the same
-// checks), all with or all without the fused 64 -> 64 tail; every unit of its stacked flat outputs must fit a list entry.
+hipError_t launch_conv3x3_halo_split(const HaloArgs &a, hipStream_t stream) {
+    HaloVariant v;
+    if (!halo_variant(a, HALO_SPLIT, &v) || !split_args_ok(a)) return hipErrorInvalidValue;
+    return launch_h(a, v, stream);
+}
+
+// The three levels of one box-tower stage from a live-tile list.  Each member must be what launch_conv3x3_halo_split takes, a single cout tile of the list
+// kernel's width, all with or all without the fused 64 -> 64 tail; every unit of its stacked flat outputs must fit a list entry.
 hipError_t launch_conv3x3_halo_list(const HaloListArgs &g0, unsigned grid, hipStream_t stream) {
     HaloListArgs g = g0;
     if (!g.list || !g.count || grid == 0 || grid > 0x7fffffffu) return hipErrorInvalidValue;
     const bool tail = g.m[0].tail_w != nullptr;
     for (HaloArgs &a : g.m) {
-        if (a.Cin % 64 != 0 || a.Cout != 64 || a.CoutPad != 64 || a.slabs == 2 || a.res || a.out2 || (a.tail_w != nullptr) != tail) return hipErrorInvalidValue;
-        if (tail && (!a.tail_bias || !a.tail_out || a.tail_kpad != 128 || a.tail_cout != 64 || (a.tail_f32 ? (a.tail_ld % 4 || a.tail_coff % 4) : (a.tail_ld % 64 || a.tail_coff % 64))))
-            return hipErrorInvalidValue;
-        if (a.in_ld % 64 || a.in_coff % 64 || a.out_ld % 64 || a.out_coff % 64 || a.Kpad != 9 * a.Cin) return hipErrorInvalidValue;
-        if (a.pitch != (a.strips == 1 ? a.S + 1 : a.S + 2) || kBM + 2 * a.pitch + 2 > kHaloRowsMax || a.strips * a.S < a.W || (a.strips == 1 && a.S != a.W))
-            return hipErrorInvalidValue;
+        HaloVariant v;
+        if (!halo_variant(a, HALO_SPLIT, &v) || v.bn != kHaloListVariant.bn || a.CoutPad != v.bn || v.tail != tail || a.res || a.out2 || !split_args_ok(a)) return hipErrorInvalidValue;
         if (a.strips > (1 << kHaloListStripBits) || ((long long)a.N * (a.H + 1) * a.pitch + 127) / 128 > (1ll << kHaloListUnitBits)) return hipErrorInvalidValue;
         a.d_pitch = make_fastdiv((unsigned)a.pitch);
         a.d_h1 = make_fastdiv((unsigned)(a.H + 1));
     }
-    if (tail)
-        hipLaunchKernelGGL((halo_list_kernel<true>), dim3(grid), dim3(512), 0, stream, g);
-    else
-        hipLaunchKernelGGL((halo_list_kernel<false>), dim3(grid), dim3(512), 0, stream, g);
+    hipLaunchKernelGGL(tail ? halo_list_kernel<true> : halo_list_kernel<false>, dim3(grid), dim3(512), 0, stream, g);
     return hipGetLastError();
 }
 
-int halo_rows_max(int cout_stored, int slabs) { return (slabs == 3 && halo_cout_tile(cout_stored) == 192) ? kHaloRowsSmall : kHaloRowsMax; }
+int halo_rows_max(int cout_stored, int slabs) { return (slabs == 3 && halo_cout_tile(cout_stored, HALO_F16) == 192) ? kHaloRowsSmall : kHaloRowsMax; }
 
 void halo_geometry(int H, int W, int rows_max, int *S, int *pitch, int *strips, int *blocks_per_strip, int bm) {
     const int smax = (rows_max - kBM - 2) / 2 - 2; // 256 + 2*(S+2) + 2 <= rows_max (the same strips for both block sizes)
@@ -529,41 +534,21 @@ void halo_geometry(int H, int W, int rows_max, int *S, int *pitch, int *strips, 
 }
 
 void halo_geometry_stacked(int N, int H, int W, int rows_max, int *S, int *pitch, int *strips, int *blocks_per_strip, int bm) {
-    const int smax = (rows_max - kBM - 2) / 2 - 2; // 256 + 2*(S+2) + 2 <= rows_max (the same strips for both block sizes)
-    *strips = (W + smax - 1) / smax;
-    *S = (W + *strips - 1) / *strips;
-    *pitch = *strips == 1 ? *S + 1 : *S + 2; // one strip: the zero column right of a row is the one left of the next row
+    halo_geometry(H, W, rows_max, S, pitch, strips, blocks_per_strip, bm);
+    if (*strips == 1) *pitch = *S + 1; // one strip: the zero column right of a row is the one left of the next row
     *blocks_per_strip = (int)(((long long)N * (H + 1) * *pitch + bm - 1) / bm);
 }
 
-int halo_cout_tile(int cout_stored) { return cout_stored % 128 == 0 ? 128 : (cout_stored % 192 == 0 ? 192 : 64); }
-
 hipError_t launch_conv3x3_halo(const HaloArgs &a, int is_f16, hipStream_t stream) {
-    const int ce = is_f16 ? 8 : 4;
-    const int cch = 8 * ce;
-    const int bn = (a.narrow && !a.tail_w && a.CoutPad % 64 == 0) ? 64 : halo_cout_tile(a.Cout); // narrow: 64-cout tiles for a thin grid (small handles)
-    if (a.Cin % cch != 0 || a.CoutPad % bn != 0 || a.Cout > a.CoutPad || a.Cout % (bn == 192 ? 24 : 16) != 0) return hipErrorInvalidValue;
-    if (a.in_ld % ce || a.in_coff % ce || a.out_ld % ce || a.out_coff % ce || a.Kpad % cch || a.Kpad < 9 * a.Cin) return hipErrorInvalidValue;
-    if (a.pitch != (a.strips == 1 ? a.S + 1 : a.S + 2) || kBM + 2 * a.pitch + 2 > kHaloRowsMax || a.strips * a.S < a.W || (a.strips == 1 && a.S != a.W))
+    const int ce = is_f16 ? 8 : 4, cch = 8 * ce;
+    HaloVariant v;
+    if (!halo_variant(a, is_f16 ? HALO_F16 : HALO_F32, &v)) return hipErrorInvalidValue;
+    if (a.Cout > a.CoutPad || a.Cout % (v.bn == 192 ? 24 : 16) != 0) return hipErrorInvalidValue;
+    if (a.in_ld % ce || a.in_coff % ce || a.out_ld % ce || a.out_coff % ce || a.Kpad % cch || a.Kpad < 9 * a.Cin || !halo_strips_ok(a)) return hipErrorInvalidValue;
+    if (a.tail_w && (a.Cout != v.bn || a.CoutPad != v.bn || a.res || a.out2 || !a.tail_bias || !a.tail_out || a.tail_kpad < v.bn || a.tail_kpad % 8 || a.tail_ld % 8 || a.tail_coff % 8))
         return hipErrorInvalidValue;
-    if (a.tail_w && (!is_f16 || (bn != 64 && bn != 128) || a.Cout != bn || a.CoutPad != bn || a.res || a.out2 || !a.tail_bias || !a.tail_out ||
-                     a.tail_kpad < bn || a.tail_kpad % 8 || a.tail_ld % 8 || a.tail_coff % 8 || a.slabs == 2))
-        return hipErrorInvalidValue; // the fused 1x1 tail exists for the fp16 64-cout (-> 64) and 128-cout (-> 32) three-slab variants only
-    const int bm = a.bm == 128 ? 128 : kBM;
-    if ((long long)a.blocks_per_strip * bm < (long long)a.N * (a.H + 1) * a.pitch) return hipErrorInvalidValue;
-    if (a.res && (a.res_ld % ce || a.res_coff % ce)) return hipErrorInvalidValue;
-    if (a.out2 && (a.out2_ld % ce || a.out2_coff % ce)) return hipErrorInvalidValue;
-    const int nchunks = a.Cin / cch;
-    // persistent form only where a block gets to walk several tiles (measured: -5..-8 % at 6-7 tiles per CU, -1..2 % at 1.75, but
-    // +4 % when every block has exactly one tile: its per-tile bookkeeping then buys nothing)
-    const long long tiles = (long long)a.strips * a.blocks_per_strip * (a.CoutPad / bn);
-    if (a.slabs != 2 && !a.tail_w && bm == kBM && a.persist_cus > 0 && 2 * tiles >= 3 * (long long)a.persist_cus && nchunks % 2 == 0 && (bn == 128 || bn == 192)) {
-        if (is_f16) return bn == 128 ? launch_hp<_Float16, 128, kHaloRowsMax>(a, a.persist_cus, stream) : launch_hp<_Float16, 192, kHaloRowsSmall>(a, a.persist_cus, stream);
-        return bn == 128 ? launch_hp<float, 128, kHaloRowsMax>(a, a.persist_cus, stream) : launch_hp<float, 192, kHaloRowsSmall>(a, a.persist_cus, stream);
-    }
-    // one tile per block: three weight slabs + counted vmcnt (default), or the two-slab / vmcnt(0) schedule (slabs == 2)
-    const int nwb = a.slabs == 2 ? 2 : 3;
-    return is_f16 ? launch_h_any<_Float16>(a, bn, nchunks, nwb, bm, stream) : launch_h_any<float>(a, bn, nchunks, nwb, bm, stream);
+    if ((a.res && (a.res_ld % ce || a.res_coff % ce)) || (a.out2 && (a.out2_ld % ce || a.out2_coff % ce))) return hipErrorInvalidValue;
+    return launch_h(a, v, stream);
 }
 
 } // namespace wtk

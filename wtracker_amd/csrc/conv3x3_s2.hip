@@ -266,22 +266,26 @@ __global__ __launch_bounds__(512, 2) void conv3x3_s2_kernel(const HaloArgs a) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the last chunk's duplicate requests must not outlive the block's LDS
 }
 
-template <int BMT, bool SPLIT = false> hipError_t launch_s2(HaloArgs a, hipStream_t stream) {
+// Behind both launchers' channel checks: one strip (pitch = W + 1), blocks of a.bm = 128 or (default) 256 pixels over its stacked rows; FastDiv fields, grid
+template <bool SPLIT> hipError_t launch_s2(HaloArgs a, hipStream_t stream) {
+    const int bm = a.bm == 128 ? 128 : 256;
+    if (a.strips != 1 || a.S != a.W || a.pitch != a.W + 1 || bm + a.pitch + 2 > kS2Rows) return hipErrorInvalidValue;
+    if ((long long)a.blocks_per_strip * bm < (long long)a.N * (a.H + 1) * a.pitch) return hipErrorInvalidValue;
     const long long blocks = (long long)a.blocks_per_strip * (a.CoutPad / 128);
     if (blocks <= 0 || blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-    a.d_nct = make_fastdiv((unsigned)(a.CoutPad / 128));
-    a.d_bps = make_fastdiv((unsigned)a.blocks_per_strip);
-    a.d_strips = make_fastdiv(1u);
-    a.d_pitch = make_fastdiv((unsigned)a.pitch);
-    a.d_h1 = make_fastdiv((unsigned)(a.H + 1));
+    a.d_nct = make_fastdiv((unsigned)(a.CoutPad / 128)), a.d_bps = make_fastdiv((unsigned)a.blocks_per_strip), a.d_strips = make_fastdiv(1u);
+    a.d_pitch = make_fastdiv((unsigned)a.pitch), a.d_h1 = make_fastdiv((unsigned)(a.H + 1));
     a.grid = (int)blocks;
-    hipLaunchKernelGGL((conv3x3_s2_kernel<BMT, SPLIT>), dim3((unsigned)blocks), dim3(512), 0, stream, a);
+    if (bm == 128)
+        hipLaunchKernelGGL((conv3x3_s2_kernel<128, SPLIT>), dim3((unsigned)blocks), dim3(512), 0, stream, a);
+    else
+        hipLaunchKernelGGL((conv3x3_s2_kernel<256, SPLIT>), dim3((unsigned)blocks), dim3(512), 0, stream, a);
     return hipGetLastError();
 }
 
 } // namespace
 
-// stride-2 window kernel: a.H / a.W are the OUTPUT map; one strip (pitch = W + 1); a.bm = 128 selects the half-size block
+// stride-2 window kernel: a.H / a.W are the OUTPUT map
 bool s2win_eligible(int k, int stride, int cin, int cout, int cout_pad, int is_f16, int wo, bool plain) {
     // cin >= 128: the 64-channel strided conv (model.3) keeps the implicit-GEMM kernel, whose fused-tail form (model.3 + model.4.cv1) must stay
     // bit-identical to its stand-alone form (test_fused_kernels_equal_layer_by_layer switches the fusion off and on)
@@ -291,10 +295,7 @@ bool s2win_eligible(int k, int stride, int cin, int cout, int cout_pad, int is_f
 hipError_t launch_conv3x3_s2(const HaloArgs &a, hipStream_t stream) {
     if (a.Cin % 64 || a.CoutPad % 128 || a.Cout > a.CoutPad || a.Cout % 16 || a.out2 || a.tail_w || a.res || a.Kpad < 9 * a.Cin || a.Kpad % 64) return hipErrorInvalidValue;
     if (a.in_ld % 8 || a.in_coff % 8 || a.out_ld % 8 || a.out_coff % 8) return hipErrorInvalidValue;
-    const int bm = a.bm == 128 ? 128 : 256;
-    if (a.strips != 1 || a.S != a.W || a.pitch != a.W + 1 || bm + a.pitch + 2 > kS2Rows) return hipErrorInvalidValue;
-    if ((long long)a.blocks_per_strip * bm < (long long)a.N * (a.H + 1) * a.pitch) return hipErrorInvalidValue;
-    return bm == 128 ? launch_s2<128>(a, stream) : launch_s2<256>(a, stream);
+    return launch_s2<false>(a, stream);
 }
 
 // split-fp16 operands: real channel counts here
@@ -305,10 +306,7 @@ bool split_s2win_eligible(int k, int stride, int cin, int cout, int cout_pad, in
 hipError_t launch_conv3x3_s2_split(const HaloArgs &a, hipStream_t stream) {
     if (a.Cin % 64 || a.CoutPad % 128 || a.Cout != a.CoutPad || a.out2 || a.tail_w || a.res || a.Kpad != 9 * a.Cin) return hipErrorInvalidValue;
     if (a.in_ld % 64 || a.in_coff % 64 || a.out_ld % 64 || a.out_coff % 64) return hipErrorInvalidValue;
-    const int bm = a.bm == 128 ? 128 : 256;
-    if (a.strips != 1 || a.S != a.W || a.pitch != a.W + 1 || bm + a.pitch + 2 > kS2Rows) return hipErrorInvalidValue;
-    if ((long long)a.blocks_per_strip * bm < (long long)a.N * (a.H + 1) * a.pitch) return hipErrorInvalidValue;
-    return bm == 128 ? launch_s2<128, true>(a, stream) : launch_s2<256, true>(a, stream);
+    return launch_s2<true>(a, stream);
 }
 
 } // namespace wtk

@@ -288,7 +288,15 @@ struct HaloArgs {
 static_assert(sizeof(HaloArgs) == 288, "live_off / live_ld fill padding: the struct of a dense launch is what it was before the live mask");
 bool halo_eligible(int k, int stride, int cin, int is_f16);
 bool split_halo_eligible(int k, int stride, int cin, int cout); // split-fp16 operands (real channel counts)
-int split_halo_cout_tile(int cout_stored);
+enum HaloMode { HALO_F32 = 0, HALO_F16 = 1, HALO_SPLIT = 2 }; // operands of a window launch (HALO_SPLIT: launch_conv3x3_halo_split)
+int halo_cout_tile(int cout_stored, int mode);                // cout tile of a layer before any occupancy rule: 128, 192 (not split) or 64
+// One instantiation of the family: conv3x3_halo_kernel<T, bn, nhalo, minw, nwb, hrows, bmt, tail, split>, or (persistent) conv3x3_halo_pkernel<T, bn, hrows>,
+// whose other fields say what that kernel is: two window buffers, two blocks' worth of registers, three slabs, 256 pixels per tile.  f16: T is _Float16, not float
+struct HaloVariant { int f16, bn, nhalo, minw, nwb, hrows, bmt, tail, split, persistent; };
+inline bool operator==(const HaloVariant &x, const HaloVariant &y) { return __builtin_memcmp(&x, &y, sizeof(x)) == 0; } // (ten ints: no padding)
+// The ONE place where filled arguments become an instantiation (cout tile, pixels per block, weight ring, window buffers, fused tail, persistent form): a pure
+// function of `a`, false where the family has no instantiation for it.  The launchers run what it names; wtk_run.hip and tests/hostsan ask it.
+bool halo_variant(const HaloArgs &a, int mode, HaloVariant *v);
 hipError_t launch_conv3x3_halo_split(const HaloArgs &a, hipStream_t stream); // channel counts / offsets but Cout in pseudo-channels
 // One stage of the sparse Detect box towers over all three levels in ONE launch (halo_list_kernel): block b < *count runs the tile list[b] names, with the split
 // 64-cout x 128-pixel instantiation (plain, or with the fused 64 -> 64 tail when the members carry one); a block beyond the count exits at once.  A list entry
@@ -300,6 +308,7 @@ struct HaloListArgs {
     const unsigned *list;
     const unsigned *count;
 };
+constexpr HaloVariant kHaloListVariant = {1, 64, 2, 2, 3, kHaloRowsMax, 128, 0, 1, 0}; // the tile of halo_list_kernel<TAIL> (tail: as its members carry one)
 hipError_t launch_conv3x3_halo_list(const HaloListArgs &g, unsigned grid, hipStream_t stream); // grid: the host's upper bound of *count
 bool split_s2win_eligible(int k, int stride, int cin, int cout, int cout_pad, int wo, bool plain); // real channel counts
 hipError_t launch_conv3x3_s2_split(const HaloArgs &a, hipStream_t stream);
@@ -308,7 +317,6 @@ void halo_geometry(int H, int W, int rows_max, int *S, int *pitch, int *strips, 
 // conv3x3_halo.hip: the N images of a strip are stacked vertically with ONE shared zero row between neighbours, and a map that
 // fits one strip shares ONE zero column between the right border of a row and the left border of the next (pitch = W + 1)
 void halo_geometry_stacked(int N, int H, int W, int rows_max, int *S, int *pitch, int *strips, int *blocks_per_strip, int bm = 256);
-int halo_cout_tile(int cout_stored);
 hipError_t launch_conv3x3_halo(const HaloArgs &a, int is_f16, hipStream_t stream);
 // 3x3 / stride-2 convs (fp16, 128-cout tiles) through an LDS-resident window of the four input parity planes; H / W of the args
 // are the OUTPUT map, `plain` = no residual / second output / fused tail / second source

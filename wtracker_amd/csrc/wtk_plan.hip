@@ -166,7 +166,7 @@ static int pack_conv(wtk_yolo *h, Op &op, const std::vector<const float *> &w_pa
     op.K = op.k * op.k * op.cin;
     op.Kpad = (op.K + 8 * ce - 1) / (8 * ce) * (8 * ce);
     if (h->split) op.Kpad = op.K; // cin % 32 == 0 (checked at create): rows of 2 K halves, no K tail
-    const int bn = op.halo == 2 ? 32 : (op.halo ? (h->split ? split_halo_cout_tile(op.cout) : halo_cout_tile(op.cout)) : conv_cfg_bn(op.cfg));
+    const int bn = op.halo == 2 ? 32 : (op.halo ? halo_cout_tile(op.cout, h->split ? HALO_SPLIT : h->is_f16 ? HALO_F16 : HALO_F32) : conv_cfg_bn(op.cfg));
     op.cout_pad = (op.cout + bn - 1) / bn * bn;
     std::vector<float> wf((size_t)op.cout_pad * op.Kpad, 0.f), bf(op.cout_pad, 0.f);
     int row = 0;

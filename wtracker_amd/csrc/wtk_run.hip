@@ -51,7 +51,39 @@ struct NmsOut {
     int max_det;
     int *out_cls, *out_count;
 };
-static HeadArgs head_args(wtk_yolo *h, int B, int H, int W, float conf, float *out_xywh, float *out_conf, int *out_anchor) {
+// the batch rows are camera views of full frames (wtk_yolo_predict_views) — crop + letterbox in one kernel
+struct ViewSrc {
+    const int32_t *pos_xy, *frame_index;
+    int view_w, view_h, n_frames;
+};
+
+// A forward pass while it is enqueued: what the caller asked for, its lanes and, in profiling mode, the event brackets and counters of the kernel classes.
+// Two lanes: the caller's stream runs backbone + PAN + the P5 tower; the P3 / P4 Detect towers run on the side streams as soon as their feature map is
+// complete and fill the tails of the small PAN kernels.  Profiling keeps everything on one stream so the per-class event brackets stay meaningful.
+struct Pass {
+    wtk_yolo *h;
+    const uint8_t *net_in; // the caller's frames; the network-size frames once enqueue_input has run
+    int B, C;
+    hipStream_t main_st;    // the caller's stream
+    int32_t H, W;           // the image scale_boxes maps back to: the frames, or (enqueue_input) the views cut from them
+    float conf, *out_xywh, *out_conf;
+    int32_t *out_anchor;
+    const ViewSrc *vs = nullptr;
+    const NmsOut *nms = nullptr;
+    bool two_lanes = false;
+    unsigned side_used = 0; // bit i: side_stream[i] carries work of this pass
+    const struct SparseBox *sparse = nullptr; // this pass leaves the box towers to enqueue_sparse_tail
+    int cur_class = -1, nev = 0;
+    int ev_class[wtk_yolo::kProfEvents];
+    long long launches[wtk_yolo::kProfKernels] = {};
+    double flops[wtk_yolo::kProfKernels] = {};
+    double op_flops(const Op &o) const { return 2.0 * B * o.macs_per_image; } // algorithmic: 2 x output pixels x cout x (cin x k x k)
+    void count(ProfClass cls, double fl = 0.0) { ++launches[cls], flops[cls] += fl; }
+};
+
+static HeadArgs head_args(const Pass &p) {
+    wtk_yolo *h = p.h;
+    const float conf = p.conf;
     HeadArgs a;
     std::memset(&a, 0, sizeof(a));
     for (int i = 0; i < 3; ++i) {
@@ -62,34 +94,31 @@ static HeadArgs head_args(wtk_yolo *h, int B, int H, int W, float conf, float *o
     }
     a.cls_ld = h->cls_ld;
     a.nc = h->dims.nc;
-    a.N = B;
+    a.N = p.B;
     a.conf = conf;
     int nh, nw, top, left;
-    letterbox_geom(H, W, h->S_h, h->S_w, nh, nw, top, left, a.gain, a.pad_x, a.pad_y);
-    a.img_w = (float)W;
-    a.img_h = (float)H;
-    a.out_xywh = out_xywh;
-    a.out_conf = out_conf;
-    a.out_anchor = out_anchor;
+    letterbox_geom(p.H, p.W, h->S_h, h->S_w, nh, nw, top, left, a.gain, a.pad_x, a.pad_y);
+    a.img_w = (float)p.W, a.img_h = (float)p.H;
+    a.out_xywh = p.out_xywh, a.out_conf = p.out_conf, a.out_anchor = p.out_anchor;
     a.out_margin = h->o_margin;
     a.status = h->status_dev;
     a.conf_logit = conf > 0.f && conf < 1.f ? std::log(conf / (1.f - conf)) : (conf <= 0.f ? -INFINITY : INFINITY);
     return a;
 }
-static int run_head(wtk_yolo *h, int B, int H, int W, float conf, float *out_xywh, float *out_conf, int *out_anchor, hipStream_t st,
-                    const NmsOut *nms = nullptr) {
-    const HeadArgs a = head_args(h, B, H, W, conf, out_xywh, out_conf, out_anchor);
-    if (nms) {
+static int run_head(const Pass &p) { // (the test hooks behind the decode entry points: a pass that is nothing else)
+    const HeadArgs a = head_args(p);
+    if (const NmsOut *nms = p.nms) {
+        const wtk_yolo *h = p.h;
         NmsArgs q;
         std::memset(&q, 0, sizeof(q));
         q.h = a;
         q.iou = nms->iou, q.max_det = nms->max_det;
         q.scratch_score = h->nms_score, q.scratch_cls = h->nms_cls, q.scratch_box = h->nms_box;
-        q.out_xywh = out_xywh, q.out_conf = out_conf, q.out_anchor = out_anchor, q.out_cls = nms->out_cls, q.out_count = nms->out_count;
-        HIP_TRY(launch_head_nms(q, 0, st)); // the Detect outputs are fp32 tensors in both modes
+        q.out_xywh = a.out_xywh, q.out_conf = a.out_conf, q.out_anchor = a.out_anchor, q.out_cls = nms->out_cls, q.out_count = nms->out_count;
+        HIP_TRY(launch_head_nms(q, 0, p.main_st)); // the Detect outputs are fp32 tensors in both modes
         return 0;
     }
-    HIP_TRY(launch_head(a, 0, st)); // the Detect outputs are fp32 tensors in both modes
+    HIP_TRY(launch_head(a, 0, p.main_st)); // the Detect outputs are fp32 tensors in both modes
     return 0;
 }
 
@@ -215,7 +244,8 @@ static HaloArgs s2win_args(const wtk_yolo *h, const Op &op, const ConvArgs &a) {
     return g;
 }
 
-// stride-1 3x3 on an LDS-resident window (op.halo 1: conv3x3_halo.hip, 2: conv3x3_c32.hip): the kernel of the family, its strip geometry and tile shape
+static int halo_mode(const wtk_yolo *h) { return h->split ? HALO_SPLIT : h->is_f16 ? HALO_F16 : HALO_F32; }
+// stride-1 3x3 on an LDS-resident window (op.halo 1: conv3x3_halo.hip, 2: conv3x3_c32.hip): the kernel of the family, its strip geometry and tile-shape knobs
 static void resolve_window(const wtk_yolo *h, const Op &op, ConvLaunch &r) {
     const int B = r.a.N, H = r.a.H, W = r.a.W;
     HaloArgs &g = r.g;
@@ -238,23 +268,20 @@ static void resolve_window(const wtk_yolo *h, const Op &op, ConvLaunch &r) {
     }
     r.kind = h->split ? L_HALO_SPLIT : L_HALO;
     halo_geometry_stacked(B, H, W, rows_max, &g.S, &g.pitch, &g.strips, &g.blocks_per_strip);
-    if (h->halo_slabs == 3 || h->split) {
-        // small maps: halve the blocks when 256-pixel blocks leave at least half of the CUs without work
-        const long long tiles = (long long)g.strips * g.blocks_per_strip * (op.cout_pad / (h->split ? split_halo_cout_tile(op.cout) : halo_cout_tile(op.cout)));
-        if (h->halo_small_blocks && 2 * tiles <= h->num_cus) {
-            g.bm = 128;
-            halo_geometry_stacked(B, H, W, rows_max, &g.S, &g.pitch, &g.strips, &g.blocks_per_strip, 128);
-            // still under half of the CUs with 128-pixel blocks (a small handle's cycle batch on the 24 x 24 maps): 64-cout tiles as well —
-            // each block then walks the same taps over half the couts
-            if (h->small_narrow && h->split && op.tail_op < 0 && op.cout_pad % 128 == 0 && 2LL * g.strips * g.blocks_per_strip * (op.cout_pad / 128) <= h->num_cus)
-                g.narrow = 1;
-        }
+    // the tiles of the launch as `g` stands, on the cout tile halo_variant names for it (no instantiation: no rule applies, and the launcher refuses `g`)
+    HaloVariant v{};
+    auto tiles = [&]() { return halo_variant(g, halo_mode(h), &v) ? (long long)g.strips * g.blocks_per_strip * (op.cout_pad / v.bn) : 1LL << 40; };
+    // small maps: halve the blocks when 256-pixel blocks leave at least half of the CUs without work
+    if ((h->halo_slabs == 3 || h->split) && h->halo_small_blocks && 2 * tiles() <= h->num_cus) {
+        g.bm = 128;
+        halo_geometry_stacked(B, H, W, rows_max, &g.S, &g.pitch, &g.strips, &g.blocks_per_strip, 128);
+        // still under half of the CUs with 128-pixel blocks (a small handle's cycle batch on the 24 x 24 maps): 64-cout tiles as well —
+        // each block then walks the same taps over half the couts
+        if (h->small_narrow && h->split && op.tail_op < 0 && 2 * tiles() <= h->num_cus && v.bn > 64) g.narrow = 1;
     }
     // fp32 handles: the exact-fp32 matrix instructions make these layers arithmetic bound, so a grid on under three quarters of the CUs (a small
     // handle's 48 x 48 maps: 141-150 blocks of 128 / 192 couts) is cut into 64-cout tiles (Detect P3 first convs 205 us, class tower 139 us before)
-    if (h->small_narrow && !h->split && op.tail_op < 0 && op.cout_pad % 64 == 0 && halo_cout_tile(op.cout) != 64 &&
-        4LL * g.strips * g.blocks_per_strip * (op.cout_pad / halo_cout_tile(op.cout)) <= 3LL * h->num_cus)
-        g.narrow = 1;
+    if (h->small_narrow && !h->split && op.tail_op < 0 && op.cout_pad % 64 == 0 && 4 * tiles() <= 3LL * h->num_cus && v.bn > 64) g.narrow = 1;
     // Small f16x3 handles: the 64-cout window tiles on the six-slab ring with fragment prefetch (conv3x3_halo.hip; bit-identical to the
     // three-slab kernel).  A cycle batch's 24 x 24 layers 19.4 -> 15.9 us each; the 256-pixel tiles and the large handles measure the
     // same either way (profiles/r05_notes.md section 7), so those keep the three-slab kernel.  WTK_HALO_DEEP: 0 off, 1 small handles
@@ -262,7 +289,8 @@ static void resolve_window(const wtk_yolo *h, const Op &op, ConvLaunch &r) {
     if (h->halo_deep) g.deep = 1;
 }
 
-// The kernel of one conv op at batch B, its profile class and its arguments: every eligibility test and occupancy rule, in the order they apply.
+// The kernel of one conv op at batch B, its profile class and its arguments: every eligibility test and every occupancy rule that needs the handle, in the order
+// they apply (the window family's rules set knobs of HaloArgs — bm, narrow, deep, slabs, persist_cus —, which halo_variant turns into an instantiation).
 static int resolve_conv(const wtk_yolo *h, const Op &op, int B, ConvLaunch &r) {
     const Buf &ib = h->bufs[op.in_buf], &ob = h->bufs[op.out_buf];
     r.cls = op.sk ? PROF_IGEMM : (op.halo == 2 ? PROF_C32 : (op.halo ? PROF_HALO : PROF_IGEMM));
@@ -337,7 +365,8 @@ static bool resolve_sparse(const wtk_yolo *h, int B, SparseBox &sp) {
         ConvLaunch r0, r1;
         if (resolve_conv(h, o0, B, r0) || resolve_conv(h, b1, B, r1)) return false;
         if (r0.kind != L_HALO_SPLIT || r1.kind != L_HALO_SPLIT || r0.g.res || r0.g.out2 || r1.g.res || r1.g.out2) return false;
-        if (split_halo_cout_tile(o0.cout) != 64 || r0.g.narrow || r1.g.narrow) return false; // the dense launch must already run on 64-cout tiles
+        HaloVariant v0, v1; // the dense launches must already run on the list kernel's cout tile, by their layers' own width (not cut into it for a thin grid)
+        if (!halo_variant(r0.g, HALO_SPLIT, &v0) || !halo_variant(r1.g, HALO_SPLIT, &v1) || v0.bn != kHaloListVariant.bn || v1.bn != kHaloListVariant.bn || r0.g.narrow || r1.g.narrow) return false;
         if (r0.g.S != r1.g.S || r0.g.pitch != r1.g.pitch || r0.g.strips != r1.g.strips) return false;
         sparse_mask_add_level(m, l, B, h->lh[l], r0.g.pitch, r0.g.strips);
         if (m.bytes > h->live_mask_bytes) return false;
@@ -408,31 +437,6 @@ static int issue_conv(wtk_yolo *h, const Op &op, const ConvLaunch &r, hipStream_
     return 0;
 }
 
-// `vs` != nullptr: the batch rows are camera views of full frames (wtk_yolo_predict_views) — crop + letterbox in one kernel.
-struct ViewSrc {
-    const int32_t *pos_xy, *frame_index;
-    int view_w, view_h, n_frames;
-};
-
-// A forward pass while it is enqueued: its lanes and, in profiling mode, the event brackets and counters of the kernel classes.
-// Two lanes: the caller's stream runs backbone + PAN + the P5 tower; the P3 / P4 Detect towers run on the side streams as soon as their feature map is
-// complete and fill the tails of the small PAN kernels.  Profiling keeps everything on one stream so the per-class event brackets stay meaningful.
-struct Pass {
-    wtk_yolo *h;
-    const uint8_t *net_in; // the network-size frames
-    int B, C;
-    hipStream_t main_st;    // the caller's stream
-    bool two_lanes = false;
-    unsigned side_used = 0; // bit i: side_stream[i] carries work of this pass
-    const struct SparseBox *sparse = nullptr; // this pass leaves the box towers to enqueue_sparse_tail
-    int cur_class = -1, nev = 0;
-    int ev_class[wtk_yolo::kProfEvents];
-    long long launches[wtk_yolo::kProfKernels] = {};
-    double flops[wtk_yolo::kProfKernels] = {};
-    double op_flops(const Op &o) const { return 2.0 * B * o.macs_per_image; } // algorithmic: 2 x output pixels x cout x (cin x k x k)
-    void count(ProfClass cls, double fl = 0.0) { ++launches[cls], flops[cls] += fl; }
-};
-
 // profiling: the launches that follow belong to class `cls` (a new event bracket when the class changes)
 static int mark(Pass &p, ProfClass cls) {
     if (!p.h->profiling || cls == p.cur_class || p.nev >= wtk_yolo::kProfEvents - 1) return 0;
@@ -442,13 +446,15 @@ static int mark(Pass &p, ProfClass cls) {
 }
 
 // letterbox (or view crop + letterbox) into the staging image when the frames are not network-size already; H x W becomes the image scale_boxes maps back to
-static int enqueue_input(Pass &p, const uint8_t *frames_dev, int32_t &H, int32_t &W, const ViewSrc *vs) {
+static int enqueue_input(Pass &p) {
     wtk_yolo *h = p.h;
+    const ViewSrc *vs = p.vs;
+    int32_t &H = p.H, &W = p.W;
     float g, px, py;
     if (vs) {
         ViewLetterboxArgs va;
         std::memset(&va, 0, sizeof(va));
-        va.frames = frames_dev, va.frame_index = vs->frame_index, va.pos_xy = vs->pos_xy, va.dst = h->lb_dev;
+        va.frames = p.net_in, va.frame_index = vs->frame_index, va.pos_xy = vs->pos_xy, va.dst = h->lb_dev;
         va.N = p.B, va.H = H, va.W = W, va.C = p.C, va.F = vs->n_frames;
         va.view_w = vs->view_w, va.view_h = vs->view_h, va.Sh = h->S_h, va.Sw = h->S_w;
         va.rows = vs->view_w, va.cols = vs->view_h; // frame[y : y + w, x : x + h], view_controller.py:171
@@ -459,7 +465,7 @@ static int enqueue_input(Pass &p, const uint8_t *frames_dev, int32_t &H, int32_t
     } else if (H != h->S_h || W != h->S_w) {
         LetterboxArgs la;
         std::memset(&la, 0, sizeof(la));
-        la.src = frames_dev, la.dst = h->lb_dev;
+        la.src = p.net_in, la.dst = h->lb_dev;
         la.N = p.B, la.H = H, la.W = W, la.C = p.C, la.Sh = h->S_h, la.Sw = h->S_w;
         letterbox_geom(H, W, h->S_h, h->S_w, la.new_h, la.new_w, la.top, la.left, g, px, py);
         HIP_TRY(launch_letterbox(la, p.main_st));
@@ -611,11 +617,12 @@ static int enqueue_levels(Pass &p, size_t first_op) {
 // window grids are the host's bound of the live tiles.  The masked form (WTK_SPARSE_LIST=0) clears the mask, selects, and runs the six window launches of the
 // levels as full grids whose blocks look their units up in the mask.  In profiling mode the window launches are a class of their own with 0 FLOPs (the host does
 // not know the live tiles), so the roofline does not credit the window kernel with work it skipped.
-static int enqueue_sparse_tail(Pass &p, const SparseBox &sp, int H, int W, float conf, float *out_xywh, float *out_conf, int *out_anchor) {
+static int enqueue_sparse_tail(Pass &p) {
     wtk_yolo *h = p.h;
+    const SparseBox &sp = *p.sparse;
     hipStream_t st = p.main_st;
     HeadSparseArgs hs = sp.hs;
-    hs.h = head_args(h, p.B, H, W, conf, out_xywh, out_conf, out_anchor);
+    hs.h = head_args(p);
     if (mark(p, PROF_HEAD)) return 1;
     if (!hs.list[0]) HIP_TRY(hipMemsetAsync(hs.live, 0, h->live_mask_bytes, st));
     HIP_TRY(launch_head_select_sparse(hs, st));
@@ -670,15 +677,15 @@ static int complete_box_towers(wtk_yolo *h) {
 // No allocation, no synchronisation (profiling mode excepted): safe inside a caller's stream capture.  A pass that is being CAPTURED stays dense: the handle
 // remembers on the host whether its last pass left the box towers sparse (sparse_B, for the debug entry points), and a captured pass runs when its graph is
 // replayed, not when it is enqueued — the host could not know which kind of pass ran last.
-static int yolo_enqueue_pass(wtk_yolo *h, const uint8_t *frames_dev, int32_t B, int32_t H, int32_t W, int32_t C, float conf, float *out_xywh,
-                             float *out_conf, int32_t *out_anchor, hipStream_t st, const ViewSrc *vs, const NmsOut *nms) {
-    Pass p{h, frames_dev, B, C, st};
+static int yolo_enqueue_pass(Pass p) { // a fresh pass (the caller's frames, batch, stream and request), by value: this function's to fill
+    wtk_yolo *h = p.h;
+    hipStream_t st = p.main_st;
     SparseBox sp;
-    if (!nms && resolve_sparse(h, B, sp)) { // max_det = 1: the box towers only where the survivors need them
+    if (!p.nms && resolve_sparse(h, p.B, sp)) { // max_det = 1: the box towers only where the survivors need them
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) p.sparse = &sp;
     }
-    if (enqueue_input(p, frames_dev, H, W, vs)) return 1;
+    if (enqueue_input(p)) return 1;
     const bool grouped = h->latency && h->sk_group && !h->lat_sched.empty();
     if (!grouped && h->use_side && h->side_streams > 0 && !h->profiling && ensure_side_streams(h)) return 1;
     p.two_lanes = !grouped && h->use_side && h->side_streams > 0 && h->side_stream[1] && !h->profiling;
@@ -696,11 +703,11 @@ static int yolo_enqueue_pass(wtk_yolo *h, const uint8_t *frames_dev, int32_t B, 
             HIP_TRY(hipStreamWaitEvent(st, h->side_done[i], 0));
         }
     if (p.sparse) {
-        if (enqueue_sparse_tail(p, sp, H, W, conf, out_xywh, out_conf, out_anchor)) return 1;
+        if (enqueue_sparse_tail(p)) return 1;
     } else {
         h->sparse_B = 0; // a dense pass computes every box logit
         if (mark(p, PROF_HEAD)) return 1;
-        if (run_head(h, B, H, W, conf, out_xywh, out_conf, out_anchor, st, nms)) return 1;
+        if (run_head(p)) return 1;
         p.count(PROF_HEAD);
     }
     if (!h->profiling) return 0;
@@ -722,8 +729,9 @@ static int yolo_enqueue_pass(wtk_yolo *h, const uint8_t *frames_dev, int32_t B, 
 // activations), every grouped launch between two events, launch i running its candidate number (pass mod candidates_i) — and every launch keeps the
 // (tile, forms) that took the least time.  The cost model that otherwise decides is calibrated on a few layers of one network at one size; the choice
 // enters no arithmetic (tests/test_gpu_latency.py: every tile and form gives the same bits), so timing noise can cost microseconds, never results.
-static int sk_autotune(wtk_yolo *h, const uint8_t *frames_dev, int32_t B, int32_t H, int32_t W, int32_t C, float conf, float *out_xywh, float *out_conf,
-                       int32_t *out_anchor, hipStream_t st, const ViewSrc *vs, const NmsOut *nms) {
+static int sk_autotune(const Pass &p) {
+    wtk_yolo *h = p.h;
+    hipStream_t st = p.main_st;
     const size_t n = h->lat_sched.size();
     while (h->tune_ev.size() < 2 * n) {
         hipEvent_t e;
@@ -736,7 +744,7 @@ static int sk_autotune(wtk_yolo *h, const uint8_t *frames_dev, int32_t B, int32_
     int rc = 0;
     for (size_t pass = 0; pass < most * kReps && !rc; ++pass) {
         h->tune_pass = (int)pass;
-        rc = yolo_enqueue_pass(h, frames_dev, B, H, W, C, conf, out_xywh, out_conf, out_anchor, st, vs, nms);
+        rc = yolo_enqueue_pass(p);
         h->tune_pass = -1;
         if (rc) break;
         if (hipStreamSynchronize(st) != hipSuccess) {
@@ -765,20 +773,20 @@ static int sk_autotune(wtk_yolo *h, const uint8_t *frames_dev, int32_t B, int32_
             if (ms[i] < ms[b] * 0.97f) b = i; // (the model's choice unless another is clearly faster)
         h->sk_choices[key] = cands[b];
     }
-    h->sk_tuned.push_back(B);
+    h->sk_tuned.push_back(p.B);
     return 0;
 }
 
-static int yolo_enqueue(wtk_yolo *h, const uint8_t *frames_dev, int32_t B, int32_t H, int32_t W, int32_t C, float conf, float *out_xywh, float *out_conf,
-                        int32_t *out_anchor, hipStream_t st, const ViewSrc *vs = nullptr, const NmsOut *nms = nullptr) {
+static int yolo_enqueue(const Pass &p) {
+    wtk_yolo *h = p.h;
     if (h->latency && h->sk_group && h->sk_autotune && !h->lat_sched.empty() && !h->profiling && h->tune_pass < 0 &&
-        std::find(h->sk_tuned.begin(), h->sk_tuned.end(), (int)B) == h->sk_tuned.end()) {
+        std::find(h->sk_tuned.begin(), h->sk_tuned.end(), p.B) == h->sk_tuned.end()) {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) { // (a capture cannot be timed: it keeps the cost model's choices)
-            if (sk_autotune(h, frames_dev, B, H, W, C, conf, out_xywh, out_conf, out_anchor, st, vs, nms)) return 1;
+        if (hipStreamIsCapturing(p.main_st, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) { // (a capture cannot be timed: it keeps the cost model's choices)
+            if (sk_autotune(p)) return 1;
         }
     }
-    return yolo_enqueue_pass(h, frames_dev, B, H, W, C, conf, out_xywh, out_conf, out_anchor, st, vs, nms);
+    return yolo_enqueue_pass(p);
 }
 
 // staging image of the network input (letterbox / view), allocated once
@@ -802,7 +810,7 @@ extern "C" int wtk_yolo_predict(wtk_yolo *h, const uint8_t *frames_dev, int32_t 
     DEVICE_GUARD(h);
     hipStream_t st = (hipStream_t)stream;
     if ((H != h->S_h || W != h->S_w) && ensure_staging(h, st)) return 1;
-    return yolo_enqueue(h, frames_dev, B, H, W, C, conf, out_xywh, out_conf, out_anchor, st);
+    return yolo_enqueue(Pass{h, frames_dev, B, C, st, H, W, conf, out_xywh, out_conf, out_anchor});
 }
 
 extern "C" int wtk_yolo_predict_nms(wtk_yolo *h, const uint8_t *frames_dev, int32_t B, int32_t H, int32_t W, int32_t C, float conf, float iou,
@@ -820,7 +828,7 @@ extern "C" int wtk_yolo_predict_nms(wtk_yolo *h, const uint8_t *frames_dev, int3
     if ((H != h->S_h || W != h->S_w) && ensure_staging(h, st)) return 1;
     if (ensure_nms_scratch(h, st)) return 1;
     const NmsOut nms{iou, max_det, out_cls, out_count};
-    return yolo_enqueue(h, frames_dev, B, H, W, C, conf, out_xywh, out_conf, out_anchor, st, nullptr, &nms);
+    return yolo_enqueue(Pass{h, frames_dev, B, C, st, H, W, conf, out_xywh, out_conf, out_anchor, nullptr, &nms});
 }
 
 extern "C" int wtk_yolo_predict_views(wtk_yolo *h, const uint8_t *frames_dev, int32_t n_frames, int32_t H, int32_t W, int32_t C,
@@ -838,7 +846,7 @@ extern "C" int wtk_yolo_predict_views(wtk_yolo *h, const uint8_t *frames_dev, in
     hipStream_t st = (hipStream_t)stream;
     if (ensure_staging(h, st)) return 1;
     const ViewSrc vs{pos_xy_dev, frame_index_dev, view_w, view_h, n_frames};
-    return yolo_enqueue(h, frames_dev, B, H, W, C, conf, out_xywh, out_conf, out_anchor, st, &vs);
+    return yolo_enqueue(Pass{h, frames_dev, B, C, st, H, W, conf, out_xywh, out_conf, out_anchor, &vs});
 }
 
 extern "C" int wtk_yolo_predict_host(wtk_yolo *h, const uint8_t *frames_host, int32_t B, int32_t H, int32_t W, int32_t C, float conf,
@@ -995,7 +1003,7 @@ extern "C" int wtk_yolo_decode_nms_host(wtk_yolo *h, const float *box_host, cons
         return fail_hip("wtk_yolo_decode_nms_host: hipMalloc", e);
     }
     const NmsOut nms{iou, max_det, d_cls, d_count};
-    int rc = run_head(h, B, H, W, conf, d_xywh, d_conf, d_anchor, nullptr, &nms);
+    int rc = run_head(Pass{h, nullptr, B, 0, nullptr, H, W, conf, d_xywh, d_conf, d_anchor, nullptr, &nms});
     if (!rc) {
         if ((e = hipMemcpy(out_xywh, d_xywh, rows * 16, hipMemcpyDeviceToHost)) != hipSuccess) rc = fail_hip("wtk_yolo_decode_nms_host: copy", e);
         if (!rc && out_conf && (e = hipMemcpy(out_conf, d_conf, rows * 4, hipMemcpyDeviceToHost)) != hipSuccess) rc = fail_hip("copy", e);
@@ -1013,7 +1021,7 @@ extern "C" int wtk_yolo_decode_host(wtk_yolo *h, const float *box_host, const fl
     DEVICE_GUARD(h);
     HIP_TRY(hipDeviceSynchronize());
     if (upload_head_logits(h, box_host, cls_host, B)) return 1;
-    if (run_head(h, B, H, W, conf, h->o_xywh, h->o_conf, h->o_anchor, nullptr)) return 1;
+    if (run_head(Pass{h, nullptr, B, 0, nullptr, H, W, conf, h->o_xywh, h->o_conf, h->o_anchor})) return 1;
     HIP_TRY(hipMemcpy(out_xywh, h->o_xywh, sizeof(float) * 4 * B, hipMemcpyDeviceToHost));
     if (out_conf) HIP_TRY(hipMemcpy(out_conf, h->o_conf, sizeof(float) * B, hipMemcpyDeviceToHost));
     if (out_anchor) HIP_TRY(hipMemcpy(out_anchor, h->o_anchor, sizeof(int) * B, hipMemcpyDeviceToHost));
