@@ -204,7 +204,8 @@ int wtk_yolo_decode_host(wtk_yolo *h, const float *box_host /*[B][A][64]*/,
  *                        normal range the hi half is a subnormal (spacing 2^-24) and the lo half carries the rest times 2^11, so the pair still
  *                        holds the weight to an ABSOLUTE error of ~2^-36 — far below the rounding of the products it takes part in;
  *   at run time          every max_det = 1 / NMS call reads every class logit: an activation that overflowed anywhere in the network reaches the
- *                        head as inf / NaN in its receptive field, and the head kernels then raise WTK_STATUS_NONFINITE (sticky).
+ *                        head as inf / NaN in its receptive field, and the head kernels then raise WTK_STATUS_NONFINITE (sticky).  They also
+ *                        raise it for an inf / NaN among the box logits they decode: the survivor's (max_det = 1), every candidate's (NMS).
  * wtk_yolo_status: the flags as of the work the caller has synchronised with (no device call: the word lives in pinned host memory);
  * clear != 0 resets the sticky bits.  A WTK_F32 handle reports NONFINITE only for inf / NaN that fp32 itself produces. */
 #define WTK_STATUS_NONFINITE 1

@@ -275,9 +275,11 @@ __global__ __launch_bounds__(64) void head_decode_kernel(const HeadSparseArgs q)
 // ---------------------------------------------------------------------------------------------------------------
 constexpr float kNmsMaxWh = 7680.f;
 
-template <typename T> __device__ __forceinline__ void decode_anchor(const HeadArgs &a, int n, int lvl, int j, int Al, float (&xyxy)[4]) {
+// Returns whether one of the anchor's 64 box logits is inf / NaN (the range guard of a CANDIDATE's box: head_row flags the survivor's).
+template <typename T> __device__ __forceinline__ bool decode_anchor(const HeadArgs &a, int n, int lvl, int j, int Al, float (&xyxy)[4]) {
     const T *b = reinterpret_cast<const T *>(a.box[lvl]) + ((long long)n * Al + j) * 64;
     float dist[4];
+    bool bad = false;
 #pragma unroll
     for (int side = 0; side < 4; ++side) {
         float x[16];
@@ -285,6 +287,7 @@ template <typename T> __device__ __forceinline__ void decode_anchor(const HeadAr
 #pragma unroll
         for (int k = 0; k < 16; ++k) {
             x[k] = ldf(b + side * 16 + k);
+            bad |= not_finite(x[k]);
             mx = fmaxf(mx, x[k]);
         }
         float sum = 0.f;
@@ -305,6 +308,7 @@ template <typename T> __device__ __forceinline__ void decode_anchor(const HeadAr
     const float cx = (x1 + x2) / 2.f * stride, cy = (y1 + y2) / 2.f * stride;
     const float w = (x2 - x1) * stride, h = (y2 - y1) * stride;
     xyxy[0] = cx - w / 2.f, xyxy[1] = cy - h / 2.f, xyxy[2] = cx + w / 2.f, xyxy[3] = cy + h / 2.f;
+    return bad;
 }
 
 template <typename T>
@@ -343,7 +347,8 @@ __global__ __launch_bounds__(1024) void head_nms_kernel(const NmsArgs q) {
         cl[i] = mk;
         if (cand) {
             float b4[4];
-            decode_anchor<T>(a, n, lvl, j, Al, b4);
+            if (decode_anchor<T>(a, n, lvl, j, Al, b4) && a.status)
+                __hip_atomic_fetch_or(a.status, kStatusNonFinite, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             bx[4 * i + 0] = b4[0], bx[4 * i + 1] = b4[1], bx[4 * i + 2] = b4[2], bx[4 * i + 3] = b4[3];
         }
     }
@@ -421,17 +426,14 @@ __global__ __launch_bounds__(1024) void head_nms_kernel(const NmsArgs q) {
     if (threadIdx.x == 0 && q.out_count) q.out_count[n] = count;
 }
 
-hipError_t launch_head_nms(const NmsArgs &a, int is_f16, hipStream_t stream) {
+// the Detect outputs are fp32 tensors in every mode: every head kernel is launched on float logits
+hipError_t launch_head_nms(const NmsArgs &a, hipStream_t stream) {
     if (a.h.N <= 0 || a.h.nc < 1 || a.h.cls_ld < a.h.nc || a.max_det < 1 || !a.scratch_score || !a.scratch_cls || !a.scratch_box || !a.out_xywh)
         return hipErrorInvalidValue;
-    if (is_f16)
-        hipLaunchKernelGGL((head_nms_kernel<_Float16>), dim3(a.h.N), dim3(1024), 0, stream, a);
-    else
-        hipLaunchKernelGGL((head_nms_kernel<float>), dim3(a.h.N), dim3(1024), 0, stream, a);
+    hipLaunchKernelGGL((head_nms_kernel<float>), dim3(a.h.N), dim3(1024), 0, stream, a);
     return hipGetLastError();
 }
 
-// the Detect outputs are fp32 tensors in every mode
 hipError_t launch_head_select_sparse(const HeadSparseArgs &a, hipStream_t stream) {
     if (a.h.N <= 0 || a.h.nc < 1 || a.h.cls_ld < a.h.nc || !a.live || !a.sel_anchor || !a.sel_score) return hipErrorInvalidValue;
     if ((reinterpret_cast<uintptr_t>(a.live) & 3u) || (a.list[0] && (!a.list[1] || !a.count))) return hipErrorInvalidValue;
@@ -446,12 +448,9 @@ hipError_t launch_head_decode(const HeadSparseArgs &a, hipStream_t stream) {
     return hipGetLastError();
 }
 
-hipError_t launch_head(const HeadArgs &a, int is_f16, hipStream_t stream) {
+hipError_t launch_head(const HeadArgs &a, hipStream_t stream) {
     if (a.N <= 0 || a.nc < 1 || a.cls_ld < a.nc) return hipErrorInvalidValue;
-    if (is_f16)
-        hipLaunchKernelGGL((head_select_kernel<_Float16>), dim3(a.N), dim3(1024), 0, stream, a);
-    else
-        hipLaunchKernelGGL((head_select_kernel<float>), dim3(a.N), dim3(1024), 0, stream, a);
+    hipLaunchKernelGGL((head_select_kernel<float>), dim3(a.N), dim3(1024), 0, stream, a);
     return hipGetLastError();
 }
 

@@ -457,8 +457,8 @@ hipError_t pool_init_attributes();
 // Head: DFL decode + thresholded arg-max selection (max_det = 1) + scale_boxes + xyxy->xywh.
 // ---------------------------------------------------------------------------------------------
 struct HeadArgs {
-    const void *box[3]; // per level [N][h*w][64] DFL logits (storage dtype)
-    const void *cls[3]; // per level [N][h*w][cls_ld] class logits (storage dtype)
+    const void *box[3]; // per level [N][h*w][64] DFL logits (fp32 in every mode)
+    const void *cls[3]; // per level [N][h*w][cls_ld] class logits (fp32 in every mode)
     int cls_ld;
     int nc;
     int lh[3], lw[3]; // level map sizes
@@ -476,7 +476,7 @@ struct HeadArgs {
     float conf_logit; // log(conf / (1 - conf))
     int *status;      // nullable: sticky flags of the handle in pinned HOST memory (bit 0: a non-finite head logit was read; wtk_yolo_status)
 };
-hipError_t launch_head(const HeadArgs &a, int is_f16, hipStream_t stream);
+hipError_t launch_head(const HeadArgs &a, hipStream_t stream);
 
 // The same head in two kernels around the SPARSE Detect box towers (max_det = 1 calls of throughput-plan handles, wtk_run.hip): head_select_kernel_sparse scans
 // the class logits as head_select_kernel does (same order, tie rule, margin, range guard), leaves the survivor of every frame in sel_anchor / sel_score and marks
@@ -518,7 +518,7 @@ struct NmsArgs {
     int *out_anchor;      // [N][max_det] or null
     int *out_count;       // [N] or null
 };
-hipError_t launch_head_nms(const NmsArgs &a, int is_f16, hipStream_t stream);
+hipError_t launch_head_nms(const NmsArgs &a, hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------------
 // ResMLP (mlp.hip)

@@ -115,10 +115,10 @@ static int run_head(const Pass &p) { // (the test hooks behind the decode entry 
         q.iou = nms->iou, q.max_det = nms->max_det;
         q.scratch_score = h->nms_score, q.scratch_cls = h->nms_cls, q.scratch_box = h->nms_box;
         q.out_xywh = a.out_xywh, q.out_conf = a.out_conf, q.out_anchor = a.out_anchor, q.out_cls = nms->out_cls, q.out_count = nms->out_count;
-        HIP_TRY(launch_head_nms(q, 0, p.main_st)); // the Detect outputs are fp32 tensors in both modes
+        HIP_TRY(launch_head_nms(q, p.main_st));
         return 0;
     }
-    HIP_TRY(launch_head(a, 0, p.main_st)); // the Detect outputs are fp32 tensors in both modes
+    HIP_TRY(launch_head(a, p.main_st));
     return 0;
 }
 
