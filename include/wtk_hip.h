@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define WTK_ABI_VERSION 7 /* 7: + wtk_yolo_create_planned / wtk_yolo_plan, wtk_yolo_status (additive); 2: + wtk_yolo_predict_views / _nms, wtk_track_*, wtk_comm_*; 3: + WTK_F16X3, wtk_recheck_*; 4: + wtk_recheck_select_counted; 5: + wtk_recheck_enqueue / _scatter; 6: + wtk_hybrid_*; still 7: + wtk_background, wtk_precise_error (additive: every earlier entry point is unchanged); still 7: + wtk_polyfit_*; still 7: + wtk_replay_* (additive); still 7: + wtk_replay_polyfit_targets / _scratch_doubles, wtk_replay_objective (additive); still 7: + wtk_replay_yolo_step / _positions / _track (additive) */
+#define WTK_ABI_VERSION 7 /* 7: + wtk_yolo_create_planned / wtk_yolo_plan, wtk_yolo_status (additive); 2: + wtk_yolo_predict_views / _nms, wtk_track_*, wtk_comm_*; 3: + WTK_F16X3, wtk_recheck_*; 4: + wtk_recheck_select_counted; 5: + wtk_recheck_enqueue / _scatter; 6: + wtk_hybrid_*; still 7: + wtk_background, wtk_precise_error (additive: every earlier entry point is unchanged); still 7: + wtk_polyfit_*; still 7: + wtk_replay_* (additive); still 7: + wtk_replay_polyfit_targets / _scratch_doubles, wtk_replay_objective (additive); still 7: + wtk_replay_yolo_step / _positions / _track (additive); still 7: + wtk_mlp_trainer_* (additive) */
 
 typedef enum wtk_dtype {
     WTK_F32 = 0, /* fp32 storage, exact-fp32 MFMA (v_mfma_f32_16x16x4_f32): parity mode   */
@@ -85,6 +85,69 @@ int wtk_mlp_predict_track(wtk_mlp *h, const float *track_dev, int32_t n_frames,
                           const int32_t *input_frames_host, int32_t n_in,
                           float *pred_dev /*[n_samples][2]*/, int32_t *valid_dev /*[n_samples]*/,
                           void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Training a population of ResMLP predictors, one workgroup per model.
+ * Replaces: MLPTrainer.train_batch / test_batch / fit   wtracker/neural/training.py:61-130,267-333
+ *           over RMLP in train mode                      wtracker/neural/mlp.py:51-188
+ *           with the optimizers of neural/config.py:28-33 (lr and weight_decay given, the rest torch's defaults).
+ *
+ * State of ONE model, `n_state` floats: for every layer in execution order W [out][in], b [out] and, with BatchNorm, gamma [out], beta [out]
+ *     (the n_train trainable floats); behind them, for every BatchNorm layer in order, running_mean [out], running_var [out].
+ *     num_batches_tracked is the handle's step counter (the caller adds it to the initial value).
+ * Every call trains / evaluates all n_models models in ONE launch on `stream`; x / y are shared device arrays [n][in] / [n][out] fp32.
+ *   grad        train-mode forward + backward of one batch (rows 0 .. batch - 1): grad_dev [n_models][n_train], loss_dev [n_models].  No step, no statistics update.
+ *   train_epoch model e walks rows order_dev[e][0 .. n - 1] (null: 0 .. n - 1) in batches of batch_size (the last may be partial): forward, loss, backward,
+ *               optimizer step with lr_dev[e] / weight_decay_dev[e].  An order entry outside [0, n) is clamped into it (no load leaves x / y): callers validate.  loss_dev / num_correct_dev [n_models][ceil(n / batch_size)]; num_correct = samples with
+ *               ||pred - y||_2 < 1 (training.py:317).  Models with active_dev[e] == 0 are skipped (active_dev null: all run).
+ *   step        train_epoch with n = batch and no order: the same bits.
+ *   eval_epoch  eval-mode forward (running statistics) of rows 0 .. n - 1 in batches; pred_dev [n_models][n][out] (optional).  track_best != 0 keeps the early-stopping
+ *               state of training.py:119-128 per model (2: forget the state of earlier calls first, as a new Trainer.fit starts from best_val_loss = None):
+ *               curr = the batch losses added in fp32 in batch order, divided by their number; curr < best (strict) copies the state to the best slot and resets the
+ *               counter, otherwise the counter grows and, with patience > 0 and counter >= patience, active_dev[e] is cleared.
+ *   get_state   which = 0 state, 1 best state ([n_models][n_state]), 2 / 3 first / second optimizer moment ([n_models][n_train]); steps_host [n_models] (optional) =
+ *               optimizer steps taken (which = 1: at the best state).  Synchronises `stream`.
+ * Refused: widths above 128, more than 64 layers, an activation other than ReLU / none, a loss other than mse / l1, batch_size outside [1, max_batch <= 1024],
+ *     and, for a model with BatchNorm, a batch of one sample (batch_size 1 or a last partial batch of 1): train-mode BatchNorm needs more than 1 value per channel.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct wtk_mlp_trainer wtk_mlp_trainer;
+typedef struct wtk_mlp_train_layer {
+    int32_t in_dim;
+    int32_t out_dim;
+    int32_t relu;       /* 1: ReLU, 0: none */
+    int32_t batch_norm; /* 1: BatchNorm1d between the Linear and the activation */
+} wtk_mlp_train_layer;
+#define WTK_LOSS_MSE 0
+#define WTK_LOSS_L1 1
+#define WTK_OPT_ADAM 0
+#define WTK_OPT_ADAMW 1
+#define WTK_OPT_SGD 2
+#define WTK_OPT_RMSPROP 3
+typedef struct wtk_mlp_trainer_desc {
+    int32_t device;
+    int32_t n_models;
+    int32_t n_layers; /* 1 (input) + n_blocks * layers_per_block + 1 (output) */
+    int32_t n_blocks;
+    int32_t layers_per_block;
+    int32_t loss;      /* WTK_LOSS_* */
+    int32_t optimizer; /* WTK_OPT_*  */
+    int32_t max_batch; /* largest batch_size of any later call */
+    const wtk_mlp_train_layer *layers;
+    const float *state; /* host, [n_models][n_state]: the initial state of every model */
+} wtk_mlp_trainer_desc;
+int64_t wtk_mlp_trainer_state_floats(const wtk_mlp_trainer_desc *desc, int64_t *n_train_out);
+int wtk_mlp_trainer_create(wtk_mlp_trainer **out, const wtk_mlp_trainer_desc *desc);
+void wtk_mlp_trainer_destroy(wtk_mlp_trainer *h);
+int wtk_mlp_trainer_grad(wtk_mlp_trainer *h, const float *x_dev, const float *y_dev, int32_t batch, float *grad_dev, float *loss_dev, void *stream);
+int wtk_mlp_trainer_step(wtk_mlp_trainer *h, const float *x_dev, const float *y_dev, int32_t batch, const double *lr_dev, const double *weight_decay_dev,
+                         float *loss_dev, int32_t *num_correct_dev, void *stream);
+int wtk_mlp_trainer_train_epoch(wtk_mlp_trainer *h, const float *x_dev, const float *y_dev, int32_t n, const int32_t *order_dev, int32_t batch_size,
+                                const double *lr_dev, const double *weight_decay_dev, int32_t *active_dev, float *loss_dev, int32_t *num_correct_dev,
+                                void *stream);
+int wtk_mlp_trainer_eval_epoch(wtk_mlp_trainer *h, const float *x_dev, const float *y_dev, int32_t n, int32_t batch_size, int32_t patience,
+                               int32_t track_best, int32_t *active_dev, float *loss_dev, int32_t *num_correct_dev, float *pred_dev, void *stream);
+int wtk_mlp_trainer_get_state(wtk_mlp_trainer *h, int32_t which, float *state_host, int32_t *steps_host, void *stream);
+int wtk_mlp_trainer_get_stopping(wtk_mlp_trainer *h, float *best_loss_host, int32_t *has_best_host, int32_t *no_improve_host, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * YOLOv8 detector (single image size per handle).

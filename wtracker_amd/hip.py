@@ -35,6 +35,15 @@ class _MlpDesc(C.Structure):
                 ("layers", C.POINTER(_MlpLayer))]
 
 
+class _MlpTrainLayer(C.Structure):
+    _fields_ = [("in_dim", C.c_int32), ("out_dim", C.c_int32), ("relu", C.c_int32), ("batch_norm", C.c_int32)]
+
+
+class _MlpTrainerDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("device", "n_models", "n_layers", "n_blocks", "layers_per_block", "loss", "optimizer", "max_batch")] + [
+        ("layers", C.POINTER(_MlpTrainLayer)), ("state", C.POINTER(C.c_float))]
+
+
 class _ConvBlob(C.Structure):
     _fields_ = [("cout", C.c_int32), ("cin", C.c_int32), ("k", C.c_int32), ("stride", C.c_int32), ("act", C.c_int32),
                 ("reserved", C.c_int32), ("weight", C.POINTER(C.c_float)), ("bias", C.POINTER(C.c_float))]
@@ -72,6 +81,15 @@ SIGNATURES = {
     "wtk_mlp_forward": (_i32, [_vp, _vp, _i32, _vp, _vp]),
     "wtk_mlp_forward_host": (_i32, [_vp, _vp, _i32, _vp]),
     "wtk_mlp_predict_track": (_i32, [_vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
+    "wtk_mlp_trainer_state_floats": (_i64, [C.POINTER(_MlpTrainerDesc), _pi64]),
+    "wtk_mlp_trainer_create": (_i32, [_pvp, C.POINTER(_MlpTrainerDesc)]),
+    "wtk_mlp_trainer_destroy": (None, [_vp]),
+    "wtk_mlp_trainer_grad": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "wtk_mlp_trainer_step": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "wtk_mlp_trainer_train_epoch": (_i32, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "wtk_mlp_trainer_eval_epoch": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "wtk_mlp_trainer_get_state": (_i32, [_vp, _i32, _vp, _vp, _vp]),
+    "wtk_mlp_trainer_get_stopping": (_i32, [_vp, _vp, _vp, _vp, _vp]),
     "wtk_yolo_conv_count": (_i32, [_f32, _f32, _i32, _i32]),
     "wtk_yolo_conv_info": (_i32, [_f32, _f32, _i32, _i32, _i32, _pi32, _pi32, _pi32, _pi32, _pi32, C.c_char_p, _size]),
     "wtk_yolo_create": (_i32, [_pvp, C.POINTER(_YoloDesc)]),
