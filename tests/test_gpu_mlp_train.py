@@ -103,10 +103,17 @@ def test_step_teacher_forced_against_torch_optim(hip_lib, opt, wd):
     sd, acts, X, y = tr.make_case(tr.NOTEBOOK, 17, 21)
     lr = 1e-3
     t = HipMLPTrainer(_model(sd, acts), optimizer=opt, lr=lr, weight_decay=wd, max_batch=17)
-    Xd, yd = _dev(X), _dev(y)
+    worst = _teacher_forced_steps(t, sd, acts, _dev(X), _dev(y), opt, lr, wd)
+    print(f"\n[mlp_train] step {opt:<8} wd {wd:<5} worst {worst:.2f} ulp of max(|p|, |update|) (allowed {STEP_ULPS[opt]})")
+    t.close()
+
+
+def _teacher_forced_steps(t, sd, acts, Xd, yd, opt, lr, wd, steps=3):
+    """`steps` consecutive steps of handle t, each checked against the real torch.optim optimizer fed the device's own gradient and moments (shared with
+    tests/test_gpu_mlp_train_shapes.py).  Returns the worst deviation in units in the last place of max(|p|, |update|)."""
     keys = tr.trainable_keys(sd, acts)
     worst = 0.0
-    for step in range(3):
+    for step in range(steps):
         p0 = t.state_dict(0)
         m0, v0, n0 = t.moments(0)
         assert n0 == step
@@ -139,8 +146,7 @@ def test_step_teacher_forced_against_torch_optim(hip_lib, opt, wd):
                 if name in st:
                     u = np.abs(v1[k].astype(np.float64) - st[name].numpy()) / _ulp(np.maximum(v1[k], gk * gk))
                     assert u.max() <= 8, (opt, step, k, name, float(u.max()))
-    print(f"\n[mlp_train] step {opt:<8} wd {wd:<5} worst {worst:.2f} ulp of max(|p|, |update|) (allowed {STEP_ULPS[opt]})")
-    t.close()
+    return worst
 
 
 @pytest.mark.parametrize("i", [[c[0:1] + c[3:4] for c in GRAD_CASES].index(k) for k in (("tiny", 17), ("notebook", 128), ("wide-global", 17))],

@@ -424,7 +424,9 @@ __global__ __launch_bounds__(kTrainThreads) void mlp_train_kernel(const MlpTrain
                 if (a.opt_kind == OPT_ADAMW) {
                     p = p * decay;
                 } else if (wd != 0.f) {
-                    g = g + wd * p;
+                    // grad.add(param, alpha = weight_decay) is ONE fma in torch.  Where g ~ -wd p the sum cancels, and the second rounding of a separate
+                    // multiply (half a unit in the last place of wd p, any fraction of what is left) is what Adam / RMSprop then normalise into the step
+                    g = fmaf(wd, p, g);
                 }
                 if (a.opt_kind == OPT_ADAM || a.opt_kind == OPT_ADAMW) {
                     float m = Mo[i], v = Vo[i];
