@@ -60,6 +60,7 @@ def test_grad_matches_float64_within_four_times_torch_float32(hip_lib, i):
     loss_bound = 4.0 * max(abs(L32 - L64), 2.0 ** -24 * abs(L64))
     t = HipMLPTrainer(_model(sd, acts), loss_fn=loss, max_batch=batch)
     assert (t.n_state > LDS_STATE_FLOATS) == (name == "wide-global")
+    assert (t.n_state, t.n_train) == t.library_state_floats()
     Ld, gd = t.grad(_dev(X), _dev(y))
     Ld2, gd2 = t.grad(_dev(X), _dev(y))
     err = tr.grad_error(gd[0], r64["grads"])

@@ -12,13 +12,11 @@
 // The optional gather front-end is the batched form of MLPController.provide_movement_vector
 // (wtracker/sim/sim_controllers/mlp_controllers.py:38-56): 7 boxes of the track at
 // anchor + input_frames, NaN / out-of-range guard, x/y made relative to the first box's corner.
-#include "wtk_kernels.h"
+#include "wtk_device.h"
 
 #include <type_traits>
 
 namespace wtk {
-
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 constexpr int kLdAct = kMlpMaxDim + 4; // LDS row stride (floats), +4 breaks the power-of-two stride
 constexpr int kMlpLdsParams = 32768 - 64; // floats of the parameter blob staged in LDS (the fast path may read 63 floats past the blob)

@@ -94,8 +94,8 @@ class HipMLPTrainer:
     """E models of one structure trained side by side.  `models`: one or a list of live `WormPredictor`s, or state dicts (numpy / torch values under the
     reference's key names; optional entries "activations" — 'relu' / 'none' per MLPLayer —, "input_frames", "pred_frames").
 
-    `max_batch` (default 256, at most 1024) is the largest batch_size any later call may use; it sizes the per-model activation scratch, allocated once:
-    (5 + 2 layers + blocks) x max_batch x 512 bytes — the notebook's model: 2.9 MB per model at 128, 5.9 MB at 256, 23.6 MB at 1024 (E = 256: 6 GB)."""
+    `max_batch` (default 256, at most 1024) is the largest batch_size any later call may use; it sizes the per-model activation scratch, allocated once
+    (TrainScratch in csrc/mlp_train.hip) — the notebook's model: 2.9 MB per model at 128, 5.9 MB at 256, 23.6 MB at 1024 (E = 256: 6 GB)."""
 
     def __init__(self, models, loss_fn: str = "mse", optimizer: str = "adam", lr=1e-3, weight_decay=1e-5, max_batch: int = DEFAULT_MAX_BATCH, device: int = 0):
         import torch
@@ -135,6 +135,9 @@ class HipMLPTrainer:
             larr[i] = hip._MlpTrainLayer(s[1], s[0], int(r), int(bool(b)))
         desc = hip._MlpTrainerDesc(device, self.E, len(shapes), self.n_blocks, self.layers_per_block, LOSSES[loss_fn], OPTIMIZERS[optimizer], int(max_batch), larr,
                                    state.ctypes.data_as(C.POINTER(C.c_float)))
+        self._layers = larr
+        if self.library_state_floats() != (self.n_state, self.n_train):  # _pack names the keys, the library lays them out (state_layout, csrc/mlp_train.hip)
+            raise WtkError(f"ResMLP trainer: the packed state has (n_state, n_train) = {(self.n_state, self.n_train)}, the library lays out {self.library_state_floats()}")
         self._h = C.c_void_p()
         hip._check(hip.load().wtk_mlp_trainer_create(C.byref(self._h), C.byref(desc)), "wtk_mlp_trainer_create")
         self.max_batch = int(max_batch)
@@ -144,6 +147,12 @@ class HipMLPTrainer:
         self.active = torch.ones(self.E, dtype=torch.int32, device=self._dev)
 
     # ------------------------------------------------------------------ plumbing
+    def library_state_floats(self):
+        """(n_state, n_train) of this structure as the library lays a state out (wtk_mlp_trainer_state_floats; needs no device)."""
+        desc = hip._MlpTrainerDesc(0, self.E, len(self._layers), self.n_blocks, self.layers_per_block, 0, 0, 1, self._layers, None)
+        n_train = C.c_int64()
+        return int(hip.load().wtk_mlp_trainer_state_floats(C.byref(desc), C.byref(n_train))), int(n_train.value)
+
     def _per_model(self, v, name):
         import torch
 
