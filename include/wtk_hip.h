@@ -616,7 +616,7 @@ int wtk_replay_rows(const wtk_replay_config *cfg, int32_t E, int32_t n_cycles, c
                     int64_t scratch_doubles, void *stream);
 
 /* ------------------------------------------------------------------------------------------
- * The closed-loop error as the objective of the Polyfit weight search (csrc/replay.hip).
+ * The closed-loop error as the objective of the Polyfit weight search (csrc/replay_targets.hip, csrc/replay.hip).
  *
  * wtk_replay_polyfit_targets   the per-cycle Polyfit targets of P weight vectors in one call: a_dev [n_cycles][P][2], valid_dev
  *     [n_cycles][P], what wtk_replay_scan reads.  weights_dev [P][n_times] doubles on the device (the swarm's position buffer); one degree,
@@ -652,7 +652,7 @@ int wtk_replay_objective(const wtk_replay_config *cfg, int32_t kind, int32_t E, 
                          double *objective_dev, const int32_t *stop_dev, void *stream);
 
 /* ------------------------------------------------------------------------------------------
- * The YOLO controller's closed loop from device-resident state (csrc/replay.hip): the one experiment kind whose
+ * The YOLO controller's closed loop from device-resident state (csrc/replay_yolo.hip): the one experiment kind whose
  * targets depend on the camera view.  E = 1; pos_dev / move_dev are the scan's [n_cycles][1][2] arrays, filled cycle by cycle.  The caller
  * writes pos_dev[0] (the clamped init position) and then enqueues, per cycle c on ONE stream: wtk_yolo_predict_views (B = 1,
  * pos_xy_dev = pos_dev + 2 c, the controller's decision view) and wtk_replay_yolo_step.  Nothing goes to the host in between.
@@ -792,7 +792,7 @@ int wtk_replay_analyze(const wtk_replay_config *cfg, const wtk_replay_analysis_c
                        int64_t *stats_dev, double *scratch_dev, int64_t scratch_doubles, void *stream);
 
 /* ------------------------------------------------------------------------------------------
- * The precise tracking error of a replayed population (csrc/replay.hip): ErrorCalculator.calculate_precise
+ * The precise tracking error of a replayed population (csrc/replay_precise.hip): ErrorCalculator.calculate_precise
  * (eval/error_calculator.py:64-160) of every (experiment, logged frame) pair of a scan, with wtk_precise_error's counts and bits for the
  * row wtk_replay_rows logs.  frames_dev [n_frames][H][W] gray with n_frames >= R: row r is frame r.  bg_dev [H][W].  A pixel is
  * foreground where |frame - bg| > diff_thresh.

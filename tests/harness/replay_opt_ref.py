@@ -1,4 +1,4 @@
-"""TEST INFRASTRUCTURE: numpy statement of the class grouping behind wtk_replay_polyfit_targets (wtracker_amd/csrc/replay.hip).
+"""TEST INFRASTRUCTURE: numpy statement of the class grouping behind wtk_replay_polyfit_targets (wtracker_amd/csrc/replay_targets.hip).
 
 The least-squares problem of a cycle's fit is `A c = diag(w) y` with `A = diag(w) V(t) / scl` over the samples of the cycle that exist (inside the track,
 finite centre): `A` depends on the weights and on WHICH samples exist, never on the centres.  So the cycles of a track fall into classes by that set,

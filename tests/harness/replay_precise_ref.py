@@ -1,4 +1,4 @@
-"""TEST INFRASTRUCTURE: numpy restatement of replay_precise_kernel and its reduction (wtracker_amd/csrc/replay.hip), and the
+"""TEST INFRASTRUCTURE: numpy restatement of replay_precise_kernel and its reduction (wtracker_amd/csrc/replay_precise.hip), and the
 scenarios its tests share.
 
   precise(...)     per (experiment, frame): the padded table of the frame, two rectangle sums, the empty-intersection guard, the fallback rule
@@ -27,7 +27,7 @@ def threshold_int(t: float) -> int:
 
 
 def frame_positions(g: rr.Geometry, pos: np.ndarray, move: np.ndarray) -> np.ndarray:
-    """The platform position at every logged frame's camera picture: float64 [R, E, 2] (frame_position of replay.hip)."""
+    """The platform position at every logged frame's camera picture: float64 [R, E, 2] (frame_position of replay_device.h)."""
     L, R, E = g.L, g.n_log * g.L, pos.shape[1]
     share = rr.share_table(g.M)
     pmax = np.array([g.frame_wh[0] - 1, g.frame_wh[1] - 1], dtype=np.float64)
@@ -42,7 +42,7 @@ def frame_positions(g: rr.Geometry, pos: np.ndarray, move: np.ndarray) -> np.nda
 
 
 def logged_boxes(g: rr.Geometry, track_row: np.ndarray, p: np.ndarray):
-    """(worm [E, 4], mic [E, 4]) float64 of one frame from the platform positions p [E, 2] (row_boxes of replay.hip)."""
+    """(worm [E, 4], mic [E, 4]) float64 of one frame from the platform positions p [E, 2] (row_boxes of replay_device.h)."""
     cam = p - np.array([g.cam[0] // 2, g.cam[1] // 2], dtype=np.float64)
     mic_xy = p - np.array([g.mic[0] // 2, g.mic[1] // 2], dtype=np.float64)
     E = len(p)

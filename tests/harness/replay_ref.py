@@ -157,6 +157,25 @@ def rows(g: Geometry, track: np.ndarray, pos: np.ndarray, move: np.ndarray, e: i
     return res
 
 
+def long_track(F: int, period: int) -> np.ndarray:
+    """A seeded head track [F, 4] with exact duplicates, NaN rows, and rows whose centre differs from the one `period` frames before by -1e-6, 0 and +1e-6
+    (speeds that round to -0.0 and +0.0)."""
+    rng = np.random.default_rng(77)
+    pos = np.array([700.0, 600.0])
+    heading = 0.3
+    out = np.empty((F, 4))
+    for i in range(F):
+        heading += rng.normal(0.0, 0.15)
+        pos = 300 + (pos + max(0.2, rng.normal(2.5, 1.0)) * np.array([math.cos(heading), math.sin(heading)]) - 300) % 800  # folded back: a few large jumps
+        w, h = np.round(13.8 + rng.normal(0, 0.6), 1), np.round(14.6 + rng.normal(0, 0.6), 1)  # one decimal: widths and heights repeat
+        out[i] = (pos[0] - w / 2, pos[1] - h / 2, w, h)
+    for r0 in range(50, F - 40, 397):
+        out[r0 + 1:r0 + 2 * period + 1] = out[r0]  # exact duplicates: zero speed, equal values in every column
+        out[r0 + 20 + period] = out[r0 + 20] + (-1e-6, 1e-6, 0, 0)
+    out[[11, 300, 301, 4100, F - 5]] = np.nan
+    return out
+
+
 # ------------------------------------------------------------------------------------------------- per-cycle targets (host)
 def _table(track):
     return np.vstack([track, np.full((1, 4), np.nan)])

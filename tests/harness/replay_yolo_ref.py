@@ -1,4 +1,4 @@
-"""TEST INFRASTRUCTURE: numpy restatement of the YOLO controller's device loop (wtracker_amd/csrc/replay.hip: replay_yolo_step_kernel,
+"""TEST INFRASTRUCTURE: numpy restatement of the YOLO controller's device loop (wtracker_amd/csrc/replay_yolo.hip: replay_yolo_step_kernel,
 replay_yolo_positions_kernel, replay_yolo_track_kernel; wtracker_amd.replay.YoloReplay), driven by any `predict_views`-like callable.
 
   move_rule(row, cam)      HipYoloController.provide_movement_vector on a float32 row, every operation in the dtype numpy 2 gives it

@@ -208,6 +208,32 @@ def test_summaries_against_the_devices_own_rows(population):
     assert (s.non_perfect_rows > 0).all() and np.allclose(s.mean_bbox_error, res.bbox_error.mean(axis=1), rtol=1e-12)
 
 
+def test_summary_sums_have_the_fixed_orders_bits_across_chunks(torch_mod):
+    """R = 915 x 9 = 8235 = 2 x 4096 + 43 rows (harness long_track, seed 77; the Polyfit pair of test_gpu_replay_analysis.py's long run): two full chunks
+    and a ragged one per experiment, so the finish launch adds three partials.  The three sums are the BYTES of replay_ref._tree_sum, the statement of
+    the kernel's order, over the device's own per-row arrays; the counts are exact.  tests/test_replay_ref.py shows that on this track a sum changes
+    its bits when the chunk is halved, so another order does not pass here."""
+    from wtracker_amd.replay import Replay
+
+    ec = ExperimentConfig("long", 8236, 60, (1600, 1400), 90, (700, 600))
+    tc = TimingConfig(ec, 100, 40, 50, (4, 4), (0.32, 0.32))
+    rp = Replay(rr.long_track(8236, 3), tc, ec)
+    assert (rp.L, rp.n_rows) == (9, 8235)
+    tg = rp.polyfit([PolyfitConfig(1, [-5, -3, -1, 0, 1], None), PolyfitConfig(2, [-8, -6, -4, -2, 0, 1], [1, 1, 2, 3, 4, 5])])
+    res = rp.run(tg, per_row_errors=True)
+    R, s = rp.n_rows, res.summary
+    r0 = np.arange(R)
+    trimmed = (r0 % rp.L < rp.I) & (r0 // rp.L != 0) & (r0 // rp.L != rp.n_log - 1)  # as replay_ref.rows masks the trimmed sum
+    for e in range(2):
+        err, mse = np.asarray(res.bbox_error[e]), np.asarray(res.mse_error[e])
+        for name, x in (("bbox_error_sum", err), ("trimmed_bbox_error_sum", np.where(trimmed, err, 0.0)), ("mse_error_sum", mse)):
+            got, want = float(getattr(s, name)[e]), rr._tree_sum(x)
+            print(e, name, got.hex(), want.hex())
+            assert np.float64(got).tobytes() == np.float64(want).tobytes(), (e, name)
+        assert s.rows[e] == R and s.trimmed_rows[e] == trimmed.sum() and s.non_perfect_rows[e] == (err > 1e-7).sum()
+        assert 0 < s.non_perfect_rows[e] < R
+
+
 # ------------------------------------------------------------------------------------------------- refusals
 def test_refusals_touch_no_memory(torch_mod, hard):
     torch = torch_mod

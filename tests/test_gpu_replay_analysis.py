@@ -6,7 +6,6 @@ relative.  The device's float64 sqrt and division are the correctly rounded ones
 
 On the parent commit `Replay.run` has no `analysis` argument: every test here fails there."""
 import json
-import math
 import os
 
 import numpy as np
@@ -178,25 +177,6 @@ def test_an_experiment_gives_the_same_bits_in_any_population(torch_mod, gold):
         assert_bits_equal(six, k, host, k, "Replay.analyze")
 
 
-def long_track(F: int, period: int) -> np.ndarray:
-    """A seeded head track [F, 4] with exact duplicates, NaN rows, and rows whose centre differs from the one `period` frames before by -1e-6, 0 and +1e-6
-    (speeds that round to -0.0 and +0.0)."""
-    rng = np.random.default_rng(77)
-    pos = np.array([700.0, 600.0])
-    heading = 0.3
-    out = np.empty((F, 4))
-    for i in range(F):
-        heading += rng.normal(0.0, 0.15)
-        pos = 300 + (pos + max(0.2, rng.normal(2.5, 1.0)) * np.array([math.cos(heading), math.sin(heading)]) - 300) % 800  # folded back: a few large jumps
-        w, h = np.round(13.8 + rng.normal(0, 0.6), 1), np.round(14.6 + rng.normal(0, 0.6), 1)  # one decimal: widths and heights repeat
-        out[i] = (pos[0] - w / 2, pos[1] - h / 2, w, h)
-    for r0 in range(50, F - 40, 397):
-        out[r0 + 1:r0 + 2 * period + 1] = out[r0]  # exact duplicates: zero speed, equal values in every column
-        out[r0 + 20 + period] = out[r0 + 20] + (-1e-6, 1e-6, 0, 0)
-    out[[11, 300, 301, 4100, F - 5]] = np.nan
-    return out
-
-
 @pytest.fixture(scope="module")
 def long_run(torch_mod):
     """R = 915 x 9 = 8235 = 2 x 4096 + 43 rows (R is a multiple of the cycle length, so 2 x 4096 + 37 cannot be had at L = 9; 8235 also crosses the rows
@@ -205,7 +185,7 @@ def long_run(torch_mod):
 
     ec = ExperimentConfig("long", 8236, 60, (1600, 1400), 90, (700, 600))
     tc = TimingConfig(ec, 100, 40, 50, (4, 4), (0.32, 0.32))
-    rp = Replay(long_track(8236, 3), tc, ec)
+    rp = Replay(rr.long_track(8236, 3), tc, ec)
     assert (rp.L, rp.n_rows) == (9, 8235)
     spec = ar.Spec(period=3, trim_cycles=True, imaging_only=False, bounds=(380, 380, 1020, 1020), columns=("wrm_speed_x", "wrm_speed", "worm_deviation_x",
                    "bbox_error", "wrm_w", "cycle_step"), percentiles=(0.0, 0.05, 0.5, 0.95, 0.999, 1.0), min_speed=4.0, min_bbox_error=0.5,

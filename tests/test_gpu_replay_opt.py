@@ -1,4 +1,4 @@
-"""The closed-loop error as the objective of the Polyfit weight search, on the MI355X (csrc/replay.hip: wtk_replay_polyfit_targets, wtk_replay_objective;
+"""The closed-loop error as the objective of the Polyfit weight search, on the MI355X (csrc/replay_targets.hip: wtk_replay_polyfit_targets, csrc/replay.hip: wtk_replay_objective;
 wtracker_amd.replay: polyfit_population, objective, optimize_polyfit).  Everything runs on tests/golden/replay_hard.npz at 100 ms
 imaging (L = 5, 80 cycles of which 79 are logged, NaN rows 6, 31, 33, 120, 251 and 388) and is held to what the existing per-config route gives: rp.polyfit(configs), rp.run and Summary."""
 import json

@@ -1,4 +1,4 @@
-"""The precise tracking error of a replayed population on the MI355X (replay_precise_kernel of csrc/replay.hip) against its numpy
+"""The precise tracking error of a replayed population on the MI355X (replay_precise_kernel of csrc/replay_precise.hip) against its numpy
 restatement (tests/harness/replay_precise_ref.py, pinned by tests/test_replay_precise_ref.py to the real reference) and against the per-row kernel that
 was there before (evaluation.precise_error_from_log on the replayed log)."""
 import math

@@ -1,4 +1,4 @@
-"""wtracker_amd.replay.YoloReplay on the MI355X: the YOLO controller's closed loop from device-resident state (csrc/replay.hip: wtk_replay_yolo_step,
+"""wtracker_amd.replay.YoloReplay on the MI355X: the YOLO controller's closed loop from device-resident state (csrc/replay_yolo.hip: wtk_replay_yolo_step,
 _positions, _track) against the host frame loop it replaces (Simulator + TrackLogger + HipYoloController on device frames: same handles, same kernels, same
 inputs, so the same BITS) and against the pinned numpy restatement (tests/harness/replay_yolo_ref.py, held to the host loop by tests/test_replay_yolo_ref.py)."""
 import json

@@ -84,7 +84,7 @@ def test_the_entry_points_are_declared_bound_and_built():
 
     for name in ("wtk_replay_polyfit_targets", "wtk_replay_polyfit_targets_scratch_doubles", "wtk_replay_objective"):
         assert name in hip.SYMBOLS
-    assert "replay.hip" in _build.SOURCES and "polyfit_solve.h" in _build.HEADERS
+    assert "replay.hip" in _build.SOURCES and "replay_targets.hip" in _build.SOURCES and "polyfit_solve.h" in _build.HEADERS
     assert sorted(hip.REPLAY_OBJECTIVES.values()) == [0, 1, 2, 3]
 
 

@@ -151,6 +151,32 @@ def test_hard_fixture_has_the_properties_it_exists_for(golden_dir):
         assert ties > 0  # exact .5 ties: round-half-to-even decides
 
 
+def test_the_long_tracks_sums_show_the_chunking(monkeypatch):
+    """What test_gpu_replay.py::test_summary_sums_have_the_fixed_orders_bits_across_chunks rests on: on long_track (seed 77) at R = 8235 with that test's two
+    Polyfit experiments, at least one of the three sums of _tree_sum changes its bits when ROW_CHUNK is halved (the bbox error sum of experiment 1 does),
+    so a reduction in another order cannot pass the bit comparison."""
+    ec = ExperimentConfig("long", 8236, 60, (1600, 1400), 90, (700, 600))
+    g = rr.Geometry.of(TimingConfig(ec, 100, 40, 50, (4, 4), (0.32, 0.32)), ec)
+    assert (g.L, g.n_log * g.L) == (9, 2 * rr.ROW_CHUNK + 43)
+    track = rr.long_track(8236, 3)
+    tg = [rr.targets_polyfit(g, track, 1, [-5, -3, -1, 0, 1]), rr.targets_polyfit(g, track, 2, [-8, -6, -4, -2, 0, 1], [1, 1, 2, 3, 4, 5])]
+    pos, move = rr.scan(rr.POLYFIT, g, track, np.stack([a for a, _ in tg], axis=1), None, np.stack([v for _, v in tg], axis=1), E=2)
+    differ = []
+    for e in range(2):
+        res = rr.rows(g, track, pos, move, e, summaries=False)
+        r = res["rows"]
+        trimmed = (r[:, 15] == 0) & (r[:, 14] != 0) & (r[:, 14] != g.n_log - 1)
+        for name, x in (("bbox", res["bbox_error"]), ("trimmed", np.where(trimmed, res["bbox_error"], 0.0)), ("mse", res["mse_error"])):
+            full = rr._tree_sum(x)
+            with monkeypatch.context() as m:
+                m.setattr(rr, "ROW_CHUNK", rr.ROW_CHUNK // 2)
+                halved = rr._tree_sum(x)
+            if np.float64(full).tobytes() != np.float64(halved).tobytes():
+                differ.append((e, name))
+    assert differ, "no sum of this track depends on the chunking: choose another seed"
+    assert (1, "bbox") in differ
+
+
 # ------------------------------------------------------------------------------------------------- the Python layer's shared rules (no GPU)
 # (num_frames, (imaging, pred, moving) ms at 60 frames/s, hand-counted (n_cycles, n_log) or None)
 GEOMETRY_CASES = [(7, (100, 40, 50), (1, 0)),      # I, M, P = 6, 3, 3: the decision frame 6 exists, no cycle ends: nothing is logged

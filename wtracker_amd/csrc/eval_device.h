@@ -1,6 +1,6 @@
 // The rules of the precise tracking error (ErrorCalculator.calculate_precise, wtracker/eval/error_calculator.py:64-160) that more than one kernel
 // needs, stated once: numpy's float -> int32 cast, BoxUtils.discretize (bbox_utils.py:118-167), the integer form of the foreground threshold, the
-// worm / microscope intersection and the wave's walk over a worm crop.  precise_error_kernel (eval_ops.hip) and replay_precise_kernel (replay.hip)
+// worm / microscope intersection and the wave's walk over a worm crop.  precise_error_kernel (eval_ops.hip) and replay_precise_kernel (replay_precise.hip)
 // call these functions, so a log row and a replayed (experiment, frame) pair with the same boxes get the same counts.
 #pragma once
 #include <climits>

@@ -15,7 +15,7 @@
 // (bbox_utils.py:118-167: x + w in the array's own dtype, floor / ceil, the int32 cast, clip to the frame, zero-area boxes illegal), the wave walks the
 // worm crop of the row's full frame and counts |frame - background| > thr (total) and the same pixels inside the worm / microscope intersection
 // (inside) with ballots; err = 1 - inside / total in float64, 0 where total = 0, NaN for an illegal worm box or a frame number outside [0, F).
-// The row's rules (discretize, intersect, crop_walk, precise_error_of) live in eval_device.h, shared with replay_precise_kernel (replay.hip).
+// The row's rules (discretize, intersect, crop_walk, precise_error_of) live in eval_device.h, shared with replay_precise_kernel (replay_precise.hip).
 #include "wtk_internal.h"
 #include "eval_device.h"
 

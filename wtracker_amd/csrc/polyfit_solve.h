@@ -5,7 +5,7 @@
 //   polyfit_keeps     numpy's cut for one singular direction
 //   polyfit_eval_axes solve for both axes' coefficients and evaluate c / scl at t_eval     (what depends on the centres)
 // Callers: track_ops.hip (one fit per cycle of a track: factor + eval), polyfit_opt.hip (one fit per candidate weight vector: factor, then its own linear
-// functional), replay.hip (one factor per (sample set, particle) kept in scratch, one eval per (cycle, particle) over that record).  The library is built
+// functional), replay_targets.hip (one factor per (sample set, particle) kept in scratch, one eval per (cycle, particle) over that record).  The library is built
 // with -ffp-contract=off, so equal inputs give equal bits through every caller.  Device code only; kTrackMaxTimes / kTrackMaxCoef come from wtk_kernels.h.
 #pragma once
 #include "wtk_kernels.h"
@@ -112,7 +112,7 @@ __device__ __forceinline__ bool polyfit_keeps(double s2e, double s2max, int n) {
     return s2e > rcond * rcond * s2max;
 }
 
-// The factor as the solve reads it, wherever it lives: PolyfitLocal over a factor in the thread's own memory, PopRecordView (replay.hip) over a record in
+// The factor as the solve reads it, wherever it lives: PolyfitLocal over a factor in the thread's own memory, PopRecordView (replay_targets.hip) over a record in
 // global scratch.  A view has L(j, e), V(q, e), s2(e), scl(q) and w(j), the compacted weight of sample j.
 struct PolyfitLocal {
     const PolyfitFactor &f;

@@ -2,7 +2,7 @@
 // calc_anomalies / print_stats (wtracker/eval/data_analyzer.py:54-107, 121-159, 178-213, 326-416) and the Plotter's per-cycle and per-cycle-step
 // aggregates (wtracker/eval/plotter.py:164-168, 203-213, 237-245) compute from ONE log with pandas, for every experiment of a scan at once.
 //
-// Nothing of size [E][R][columns] is ever stored.  A row's columns are a few dozen flops away from the scan's pos / move (frame_position, row_boxes,
+// Nothing of size [E][R][columns] is ever stored.  A row's columns are a few dozen flops away from the scan's pos / move (replay_row,
 // row_bbox_error: the functions the rows kernel calls), so every kernel recomputes the value where it consumes it:
 //   last     one block per experiment: the largest cycle number among the rows that survive imaging_only and bounds.  trim_cycles drops cycle 0 and THAT
 //            cycle (DataAnalyzer.clean takes data["cycle"].max() after the first two filters), so the mask of a row is final only once this is known.
@@ -42,11 +42,7 @@ constexpr int kMaxQ = WTK_ANALYSIS_MAX_PERCENTILES;
 constexpr int kMaxRanks = 2 * kMaxQ + 2;
 
 struct AnaArgs {
-    Geometry g;
-    int E, C, n_log;
-    long long R;
-    const double *track, *share;
-    const int *pos, *move;  // [C][E][2]
+    ReplayView v;
     const double *pair;     // [R][E] precise error of every pair, NaN = no value (nullable)
     wtk_replay_analysis_config c;
     int n_cols, Q;
@@ -73,37 +69,31 @@ struct AnaRow {
 
 __device__ __forceinline__ double round5(double v) { return isfinite(v) ? rint(v * 1e5) / 1e5 : v; }
 
-__device__ __forceinline__ RowBoxes boxes_of_row(const AnaArgs &a, int e, long long r, int &c, int &step, int &px, int &py) {
-    c = (int)(r / a.g.L), step = (int)(r - (long long)c * a.g.L);
-    frame_position(a.g, a.share, a.pos, a.move, (long long)c * a.E + e, step, px, py);
-    return row_boxes(a.g, a.track + 4 * r, px, py);
-}
-
 __device__ __forceinline__ AnaRow ana_row(const AnaArgs &a, int e, long long r) {
     AnaRow w;
-    int px, py;
-    const RowBoxes b = boxes_of_row(a, e, r, w.c, w.step, px, py);
+    const ReplayRow row = replay_row(a.v, e, r);
+    const RowBoxes &b = row.b;
+    w.c = row.at.c, w.step = row.at.step;
     const double wcx = b.wx + b.ww / 2, wcy = b.wy + b.wh / 2, mcx = b.mic_x + b.mic_w / 2, mcy = b.mic_y + b.mic_h / 2; // _calc_centers
     double sx = __builtin_nan(""), sy = __builtin_nan("");
     if (r >= a.c.period) { // _calc_speed: Series.diff(period) over the whole uncleaned log, divided by time.diff(period) = period
-        int pc, ps, ppx, ppy;
-        const RowBoxes p = boxes_of_row(a, e, r - a.c.period, pc, ps, ppx, ppy);
+        const RowBoxes p = replay_row(a.v, e, r - a.c.period).b;
         const double n = (double)a.c.period;
         sx = (wcx - (p.wx + p.ww / 2)) / n, sy = (wcy - (p.wy + p.wh / 2)) / n;
     }
     const double dx = wcx - mcx, dy = wcy - mcy; // _calc_worm_deviation
-    w.plt_x = round5((double)px), w.plt_y = round5((double)py);
-    w.cam_x = round5(b.cam_x), w.cam_y = round5(b.cam_y), w.cam_w = round5((double)a.g.cam_w), w.cam_h = round5((double)a.g.cam_h);
+    w.plt_x = round5((double)row.px), w.plt_y = round5((double)row.py);
+    w.cam_x = round5(b.cam_x), w.cam_y = round5(b.cam_y), w.cam_w = round5((double)a.v.g.cam_w), w.cam_h = round5((double)a.v.g.cam_h);
     w.mic_x = round5(b.mic_x), w.mic_y = round5(b.mic_y), w.mic_w = round5(b.mic_w), w.mic_h = round5(b.mic_h);
     w.wx = round5(b.wx), w.wy = round5(b.wy), w.ww = round5(b.ww), w.wh = round5(b.wh);
     w.wcx = round5(wcx), w.wcy = round5(wcy), w.mcx = round5(mcx), w.mcy = round5(mcy);
     w.sx = round5(sx), w.sy = round5(sy), w.sp = round5(sqrt(sx * sx + sy * sy));
     w.dx = round5(dx), w.dy = round5(dy), w.dev = round5(sqrt(dx * dx + dy * dy));
     w.err = round5(row_bbox_error(b));
-    w.precise = a.pair ? a.pair[r * a.E + e] : __builtin_nan(""); // assigned after the rounding (calc_precise_error): unrounded
+    w.precise = a.pair ? a.pair[r * a.v.E + e] : __builtin_nan(""); // assigned after the rounding (calc_precise_error): unrounded
     // clean, on the rounded values.  The reference's `mask_wrm = has_pred; mask_wrm &= ...` updates has_pred in place, so its `~has_pred` is the negation
     // of the finished worm mask: it keeps (has_pred and the worm box inside) or the microscope box inside.
-    bool pre = !a.c.imaging_only || w.step < a.g.I;
+    bool pre = !a.c.imaging_only || w.step < a.v.g.I;
     if (pre && a.c.use_bounds) {
         const double *bd = a.c.bounds;
         const bool has_pred = isfinite(w.wx) && isfinite(w.wy) && isfinite(w.ww) && isfinite(w.wh);
@@ -158,11 +148,11 @@ __global__ __launch_bounds__(kAnaThreads) void analysis_last_cycle_kernel(const 
     __shared__ int best[kAnaThreads];
     const int e = blockIdx.x;
     if (!a.c.use_bounds) { // imaging_only alone keeps step 0 of every cycle (block-uniform)
-        if (threadIdx.x == 0) a.last_cycle[e] = a.n_log - 1;
+        if (threadIdx.x == 0) a.last_cycle[e] = a.v.n_log - 1;
         return;
     }
     int mine = -1;
-    for (long long r = threadIdx.x; r < a.R; r += kAnaThreads) {
+    for (long long r = threadIdx.x; r < a.v.R; r += kAnaThreads) {
         const AnaRow w = ana_row(a, e, r);
         if (w.pre) mine = max(mine, w.c);
     }
@@ -184,19 +174,19 @@ struct Segment {
 
 __device__ __forceinline__ Segment segment_of(const AnaArgs &a) {
     Segment s;
-    const int n_seg = a.by_step ? a.g.L : 1;
+    const int n_seg = a.by_step ? a.v.g.L : 1;
     const int idx = blockIdx.x;
     const int sg = idx % n_seg;
     s.j = (idx / n_seg) % a.n_cols, s.e = idx / (n_seg * a.n_cols);
     s.col = a.cols[s.j], s.seg = a.by_step ? sg : -1;
-    s.n_rows = a.by_step ? (a.R > sg ? (a.R - sg + a.g.L - 1) / a.g.L : 0) : a.R;
+    s.n_rows = a.by_step ? (a.v.R > sg ? (a.v.R - sg + a.v.g.L - 1) / a.v.g.L : 0) : a.v.R;
     s.last = a.c.trim_cycles ? a.last_cycle[s.e] : -1;
     return s;
 }
 
 // the k-th row of the segment: its value where the row is kept and the value is not NaN
 __device__ __forceinline__ bool segment_value(const AnaArgs &a, const Segment &s, long long k, double &v) {
-    const long long r = s.row(k, a.g.L);
+    const long long r = s.row(k, a.v.g.L);
     const AnaRow w = ana_row(a, s.e, r);
     if (!ana_keep(a, w, s.last)) return false;
     v = ana_value(a, w, r, s.col);
@@ -246,7 +236,7 @@ __device__ __forceinline__ void write_segment(const AnaArgs &a, const Segment &s
         for (int i = 0; i < a.Q; ++i) o[4 + i] = n > 0 ? pct[i] : nanv;
         o[4 + a.Q] = n > 0 ? vmax : nanv;
     } else {
-        const long long at = ((long long)s.e * a.g.L + s.seg) * a.n_cols + s.j;
+        const long long at = ((long long)s.e * a.v.g.L + s.seg) * a.n_cols + s.j;
         if (a.step_count) a.step_count[at] = (int)n;
         if (a.step_q)
             for (int i = 0; i < a.Q; ++i) a.step_q[at * a.Q + i] = n > 0 ? pct[i] : nanv;
@@ -381,13 +371,13 @@ __global__ __launch_bounds__(kAnaThreads) void analysis_segment_select_kernel(co
 // groupby(["log_num", "cycle"]) max / mean of every requested column over the kept rows: NaN where the cycle has no kept non-NaN value
 __global__ __launch_bounds__(256) void analysis_cycle_kernel(const AnaArgs a) {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long long)a.E * a.n_log * a.n_cols) return;
-    const int j = (int)(idx % a.n_cols), c = (int)((idx / a.n_cols) % a.n_log), e = (int)(idx / ((long long)a.n_cols * a.n_log));
+    if (idx >= (long long)a.v.E * a.v.n_log * a.n_cols) return;
+    const int j = (int)(idx % a.n_cols), c = (int)((idx / a.n_cols) % a.v.n_log), e = (int)(idx / ((long long)a.n_cols * a.v.n_log));
     const int last = a.c.trim_cycles ? a.last_cycle[e] : -1;
     double vmax = 0.0, sum = 0.0;
     int n = 0;
-    for (int step = 0; step < a.g.L; ++step) {
-        const long long r = (long long)c * a.g.L + step;
+    for (int step = 0; step < a.v.g.L; ++step) {
+        const long long r = (long long)c * a.v.g.L + step;
         const AnaRow w = ana_row(a, e, r);
         if (!ana_keep(a, w, last)) continue;
         const double v = ana_value(a, w, r, a.cols[j]);
@@ -407,7 +397,7 @@ __global__ __launch_bounds__(kAnaThreads) void analysis_flags_kernel(const AnaAr
     if (threadIdx.x < 12) cnt[threadIdx.x] = 0;
     __syncthreads();
     const int last = a.c.trim_cycles ? a.last_cycle[e] : -1;
-    for (long long r = threadIdx.x; r < a.R; r += kAnaThreads) {
+    for (long long r = threadIdx.x; r < a.v.R; r += kAnaThreads) {
         const AnaRow w = ana_row(a, e, r);
         unsigned bits = 0u;
         if (ana_keep(a, w, last)) {
@@ -426,18 +416,18 @@ __global__ __launch_bounds__(kAnaThreads) void analysis_flags_kernel(const AnaAr
             if (isnan(w.wx) || isnan(w.wy) || isnan(w.ww) || isnan(w.wh)) atomicAdd(&cnt[8], 1);
             if (w.err > 1e-7) atomicAdd(&cnt[9], 1);
         }
-        if (a.anomaly_mask) a.anomaly_mask[(long long)e * a.R + r] = (uint8_t)bits;
+        if (a.anomaly_mask) a.anomaly_mask[(long long)e * a.v.R + r] = (uint8_t)bits;
     }
-    for (int c = threadIdx.x; c < a.n_log; c += kAnaThreads) {
+    for (int c = threadIdx.x; c < a.v.n_log; c += kAnaThreads) {
         bool any = false;
-        for (int step = 0; step < a.g.L && !any; ++step) any = ana_keep(a, ana_row(a, e, (long long)c * a.g.L + step), last);
+        for (int step = 0; step < a.v.g.L && !any; ++step) any = ana_keep(a, ana_row(a, e, (long long)c * a.v.g.L + step), last);
         if (any) atomicAdd(&cnt[10], 1);
     }
     __syncthreads();
     if (threadIdx.x < 7 && a.anomaly_counts) a.anomaly_counts[(long long)e * 7 + threadIdx.x] = cnt[threadIdx.x];
     if (threadIdx.x == 0 && a.stats) {
         long long *o = a.stats + (long long)e * 4;
-        o[0] = a.R - cnt[7], o[1] = cnt[8], o[2] = cnt[10], o[3] = cnt[9];
+        o[0] = a.v.R - cnt[7], o[1] = cnt[8], o[2] = cnt[10], o[3] = cnt[9];
     }
 }
 
@@ -457,8 +447,8 @@ extern "C" int wtk_replay_analyze(const wtk_replay_config *cfg, const wtk_replay
     const std::string w("wtk_replay_analyze");
     AnaArgs a = {};
     if (!acfg) return fail(w + ": null argument");
-    if (replay_check_config("wtk_replay_analyze", cfg, WTK_REPLAY_OPTIMAL, E, n_cycles, n_track, a.g, a.n_log)) return 1;
-    if (!track_dev || !share_dev || !pos_dev || !move_dev || !columns_host || !scratch_dev || (Q > 0 && !percentiles_host)) return fail(w + ": null argument");
+    if (replay_view("wtk_replay_analyze", cfg, WTK_REPLAY_OPTIMAL, E, n_cycles, track_dev, n_track, share_dev, pos_dev, move_dev, a.v)) return 1;
+    if (!columns_host || !scratch_dev || (Q > 0 && !percentiles_host)) return fail(w + ": null argument");
     if (n_cols < 1 || n_cols > kMaxCols) return fail(w + ": 1.." + std::to_string(kMaxCols) + " columns");
     if (Q < 0 || Q > kMaxQ) return fail(w + ": 0.." + std::to_string(kMaxQ) + " percentiles");
     if (acfg->period < 1) return fail(w + ": period must be at least 1");
@@ -472,12 +462,10 @@ extern "C" int wtk_replay_analyze(const wtk_replay_config *cfg, const wtk_replay
         if (!(percentiles_host[i] >= 0.0 && percentiles_host[i] <= 1.0)) return fail(w + ": percentile outside [0, 1]");
         a.q[i] = percentiles_host[i];
     }
-    a.R = (long long)a.n_log * a.g.L;
-    if (a.R > INT32_MAX || (long long)E * n_cols * a.g.L > INT32_MAX || ((long long)E * a.n_log * n_cols + 255) / 256 > INT32_MAX)
+    if (a.v.R > INT32_MAX || (long long)E * n_cols * a.v.g.L > INT32_MAX || ((long long)E * a.v.n_log * n_cols + 255) / 256 > INT32_MAX)
         return fail(w + ": too many blocks for one launch");
-    if (scratch_doubles < wtk_replay_analysis_scratch_doubles(E, a.R, n_cols, Q)) return fail(w + ": scratch smaller than wtk_replay_analysis_scratch_doubles(E, R, n_cols, Q)");
-    a.E = E, a.C = n_cycles, a.track = track_dev, a.share = share_dev, a.pos = pos_dev, a.move = move_dev, a.pair = precise_pair_dev;
-    a.c = *acfg, a.n_cols = n_cols, a.Q = Q, a.last_cycle = reinterpret_cast<int *>(scratch_dev);
+    if (scratch_doubles < wtk_replay_analysis_scratch_doubles(E, a.v.R, n_cols, Q)) return fail(w + ": scratch smaller than wtk_replay_analysis_scratch_doubles(E, R, n_cols, Q)");
+    a.pair = precise_pair_dev, a.c = *acfg, a.n_cols = n_cols, a.Q = Q, a.last_cycle = reinterpret_cast<int *>(scratch_dev);
     a.describe = describe_dev, a.cycle_max = cycle_max_dev, a.cycle_mean = cycle_mean_dev, a.step_q = step_quantiles_dev, a.step_count = step_count_dev;
     a.anomaly_counts = reinterpret_cast<long long *>(anomaly_counts_dev), a.anomaly_mask = anomaly_mask_dev, a.stats = reinterpret_cast<long long *>(stats_dev);
     hipStream_t st = (hipStream_t)stream;
@@ -489,8 +477,8 @@ extern "C" int wtk_replay_analyze(const wtk_replay_config *cfg, const wtk_replay
     for (int by_step = 0; by_step < 2; ++by_step) {
         if (by_step ? !(step_quantiles_dev || step_count_dev) : !describe_dev) continue;
         a.by_step = by_step;
-        const long long seg_rows = by_step ? (long long)a.n_log : a.R; // the longest segment's rows: an upper bound of its kept values
-        const unsigned grid = (unsigned)((long long)E * n_cols * (by_step ? a.g.L : 1));
+        const long long seg_rows = by_step ? (long long)a.v.n_log : a.v.R; // the longest segment's rows: an upper bound of its kept values
+        const unsigned grid = (unsigned)((long long)E * n_cols * (by_step ? a.v.g.L : 1));
         if (seg_rows <= max_keys) {
             const size_t lds = (size_t)(kAnaHeaderWords + kAnaThreads + std::max(seg_rows, 1ll)) * 8;
             hipLaunchKernelGGL(analysis_segment_sort_kernel, dim3(grid), dim3(kAnaThreads), lds, st, a, (int)std::max(seg_rows, 1ll));
@@ -499,8 +487,8 @@ extern "C" int wtk_replay_analyze(const wtk_replay_config *cfg, const wtk_replay
         }
     }
     a.by_step = 0;
-    if ((cycle_max_dev || cycle_mean_dev) && a.n_log > 0)
-        hipLaunchKernelGGL(analysis_cycle_kernel, dim3((unsigned)(((long long)E * a.n_log * n_cols + 255) / 256)), dim3(256), 0, st, a);
+    if ((cycle_max_dev || cycle_mean_dev) && a.v.n_log > 0)
+        hipLaunchKernelGGL(analysis_cycle_kernel, dim3((unsigned)(((long long)E * a.v.n_log * n_cols + 255) / 256)), dim3(256), 0, st, a);
     if (anomaly_counts_dev || anomaly_mask_dev || stats_dev) hipLaunchKernelGGL(analysis_flags_kernel, dim3((unsigned)E), dim3(kAnaThreads), 0, st, a);
     HIP_TRY(hipGetLastError());
     return 0;

@@ -1,19 +1,51 @@
-// The closed loop's device functions that more than one translation unit calls (replay.hip, replay_analysis.hip): the geometry, the ONE statement of the
-// motor, the platform position of a logged frame, the boxes and the bbox error of a log row, and the host-side refusals of an experiment's geometry.
+// What the closed loop's translation units share (replay.hip, replay_precise.hip, replay_yolo.hip, replay_analysis.hip): the geometry and the view of
+// a scanned population with the ONE host function that fills it, the ONE statement of the motor, "row r of experiment e" (cycle, step, platform position,
+// boxes), the bbox error of a log row, the fixed chunking of the per-experiment sums with its tree reduction, the summaries' slots, and the declarations of
+// the host launchers that cross translation units (defined in replay.hip).
 // Everything relies on -ffp-contract=off (the library's build flag): share * move + carry is a rounded product and a rounded sum, as in Python.
 #pragma once
 #include "wtk_internal.h"
 
 #include <cmath>
+#include <functional>
 #include <string>
 
 namespace wtk {
+
+constexpr int kRowThreads = 256;
+constexpr int kRowChunk = 4096; // logged rows per block of a reducing kernel: the FIXED chunking of the reductions
+constexpr double kMoveMax = 1073741824.0; // 2^30: moves are kept as int32
+
+// chunks of R logged rows: the blocks per experiment of a reducing kernel and the partials the finish launch adds
+__host__ __device__ inline long long chunk_count(long long R) { return (R + kRowChunk - 1) / kRowChunk; }
+
+// slots of wtk_replay_rows' summary (include/wtk_hip.h documents them as [0]..[5])
+enum RowsSlot { kRowsErr = 0, kRowsCount, kRowsTrimmedErr, kRowsTrimmedCount, kRowsNonPerfect, kRowsMse, kSummary };
+// slots of wtk_replay_precise's summary: rows without a value (NaN) enter no sum and are counted apart
+enum PreciseSlot { kPreciseErr = 0, kPreciseCount, kPreciseTrimmedErr, kPreciseTrimmedCount, kPreciseNonPerfect, kPreciseNan, kPreciseSummary };
+static_assert(kSummary == WTK_REPLAY_SUMMARY_DOUBLES && kPreciseSummary == WTK_REPLAY_PRECISE_SUMMARY_DOUBLES, "summary widths of the C ABI");
 
 struct Geometry {
     int L, I, M, P;
     int cam_w, cam_h, mic_w, mic_h;
     int x_max, y_max; // frame_w - 1, frame_h - 1: the clamp of the platform position
 };
+
+// A scanned population as the kernels behind the scan read it: E experiments over C cycles, of which n_log are logged as R = n_log * L rows.
+struct ReplayView {
+    Geometry g;
+    int E, C, n_log;
+    long long R;         // logged rows per experiment
+    const double *track; // [n_track][4] xywh: row r is logged frame r
+    const double *share; // [M]
+    const int *pos, *move; // [C][E][2] position at cycle start and the cycle's move
+};
+
+// the controller's move on one axis from the camera corner; a non-finite result is no move, a huge one saturates at +-2^30
+__device__ __forceinline__ double finish_move(double v) {
+    if (!isfinite(v)) return 0.0;
+    return fmin(fmax(rint(v), -kMoveMax), kMoveMax);
+}
 
 // one step of SineMotorController.step + ViewController.move_position on one axis
 __device__ __forceinline__ void motor_axis(double share, double mv, double &carry, int &pos, int pos_max) {
@@ -59,6 +91,37 @@ __device__ __forceinline__ RowBoxes row_boxes(const Geometry &g, const double *t
     return b;
 }
 
+// where logged row r lies in the loop: the same for every experiment (a kernel that answers many experiments of one row divides once)
+struct RowCycle {
+    int c, step; // cycle and step in it
+};
+
+__device__ __forceinline__ RowCycle row_cycle(const Geometry &g, long long r) {
+    RowCycle at;
+    at.c = (int)(r / g.L), at.step = (int)(r - (long long)at.c * g.L);
+    return at;
+}
+
+// the rows DataAnalyzer.clean(trim_cycles=True, imaging_only=True) keeps: the imaging phase of every logged cycle but the first and the last
+__device__ __forceinline__ bool row_trimmed(const ReplayView &v, RowCycle at) { return at.step < v.g.I && at.c != 0 && at.c != v.n_log - 1; }
+
+// Row r of experiment e: the platform position at its camera picture and its boxes.
+struct ReplayRow {
+    RowCycle at;
+    int px, py;
+    RowBoxes b;
+};
+
+__device__ __forceinline__ ReplayRow replay_row(const ReplayView &v, int e, long long r, RowCycle at) {
+    ReplayRow w;
+    w.at = at;
+    frame_position(v.g, v.share, v.pos, v.move, (long long)at.c * v.E + e, at.step, w.px, w.py);
+    w.b = row_boxes(v.g, v.track + 4 * r, w.px, w.py);
+    return w;
+}
+
+__device__ __forceinline__ ReplayRow replay_row(const ReplayView &v, int e, long long r) { return replay_row(v, e, r, row_cycle(v.g, r)); }
+
 // ErrorCalculator.calculate_bbox_error of a row: the share of the logged worm box outside the microscope box, 0 where the box has no area
 __device__ __forceinline__ double row_bbox_error(const RowBoxes &b) {
     const double il = fmax(b.wx, b.mic_x), it = fmax(b.wy, b.mic_y);
@@ -68,9 +131,31 @@ __device__ __forceinline__ double row_bbox_error(const RowBoxes &b) {
     return total == 0.0 ? 0.0 : 1.0 - inter / total;
 }
 
-// the refusals both entry points share; fills the geometry and the counts derived from it
-inline int replay_check_config(const char *who, const wtk_replay_config *cfg, int32_t kind, int32_t E, int32_t n_cycles, int32_t n_track, Geometry &g, int &n_log) {
+// a row counts as non-perfect above this error (print_stats' "Non Perfect Predictions")
+__device__ __forceinline__ bool non_perfect(double err) { return err > 1e-7; }
+
+// The per-experiment sums' FIXED order inside a chunk: every thread of the block has added the chunk's rows t, t + 256, ... in order into acc; here a
+// binary tree over the 256 threads in LDS, and the chunk's N partials stored at `partial` (the finish launch adds the chunks in index order).  The
+// chunking depends on the row count only: an experiment gives the same bits alone and inside any population.  No floating-point atomics.
+// (The lane-serial loop stays in the two kernels: handed over as a callable, the precise reduction's sums went to scratch memory.)
+template <int N> __device__ __forceinline__ void chunk_reduce(double (&red)[N][kRowThreads], const double (&acc)[N], double *partial) {
+    for (int q = 0; q < N; ++q) red[q][threadIdx.x] = acc[q];
+    __syncthreads();
+    for (int half = kRowThreads / 2; half > 0; half >>= 1) {
+        if ((int)threadIdx.x < half)
+            for (int q = 0; q < N; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + half];
+        __syncthreads();
+    }
+    if (threadIdx.x < N) partial[threadIdx.x] = red[threadIdx.x][0];
+}
+
+// The view of an entry point's scanned population: the refusals every entry point shares (`kind` matters to the scan alone: every reader of a scanned
+// population passes WTK_REPLAY_OPTIMAL), the arrays every reader needs, the geometry and the counts derived from it.  The YOLO loop's entry points, whose
+// track is their own output, take the geometry and the counts alone (arrays_required = false) and refuse their own nulls.
+inline int replay_view(const char *who, const wtk_replay_config *cfg, int32_t kind, int32_t E, int32_t n_cycles, const double *track_dev, int32_t n_track,
+                       const double *share_dev, const int32_t *pos_dev, const int32_t *move_dev, ReplayView &v, bool arrays_required = true) {
     const std::string w(who);
+    Geometry &g = v.g;
     if (!cfg) return fail(w + ": null argument");
     if (kind < WTK_REPLAY_CSV || kind > WTK_REPLAY_MLP) return fail(w + ": unknown kind");
     if (E < 1) return fail(w + ": at least one experiment (E >= 1)");
@@ -84,7 +169,7 @@ inline int replay_check_config(const char *who, const wtk_replay_config *cfg, in
     if (cfg->frame_w < 1 || cfg->frame_h < 1) return fail(w + ": empty frame");
     const long long L = (long long)cfg->imaging_frame_num + cfg->moving_frame_num;
     if (L > INT32_MAX) return fail(w + ": cycle too long");
-    n_log = (int)((cfg->num_frames - 1) / L); // the last cycle is never logged (its end never arrives)
+    const int n_log = (int)((cfg->num_frames - 1) / L); // the last cycle is never logged (its end never arrives)
     if ((long long)n_log * L > n_track) return fail(w + ": the track is shorter than the logged rows");
     if (n_cycles < 1 || n_cycles < n_log) return fail(w + ": n_cycles must cover every logged cycle (and be at least 1)");
     if ((long long)(n_cycles - 1) * L + cfg->imaging_frame_num > (long long)cfg->num_frames - 1)
@@ -92,7 +177,45 @@ inline int replay_check_config(const char *who, const wtk_replay_config *cfg, in
     g.L = (int)L, g.I = cfg->imaging_frame_num, g.M = cfg->moving_frame_num, g.P = cfg->pred_frame_num;
     g.cam_w = cfg->cam_w, g.cam_h = cfg->cam_h, g.mic_w = cfg->mic_w, g.mic_h = cfg->mic_h;
     g.x_max = cfg->frame_w - 1, g.y_max = cfg->frame_h - 1;
+    if (arrays_required && (!track_dev || !share_dev || !pos_dev || !move_dev)) return fail(w + ": null argument");
+    v.E = E, v.C = n_cycles, v.n_log = n_log, v.R = (long long)n_log * L;
+    v.track = track_dev, v.share = share_dev, v.pos = pos_dev, v.move = move_dev;
     return 0;
 }
+
+// ---- host launchers that cross translation units, defined in replay.hip
+struct ScanArgs {
+    Geometry g;
+    int kind, E, C;
+    int init_x, init_y;
+    const double *track; // [n_track][4] xywh
+    int n_track;
+    const double *a;  // [C][E][2] (CSV: unused)
+    const double *b;  // [C][E][2] (MLP only)
+    const int *valid; // [C][E] (CSV: unused)
+    const double *share; // [M]
+    int *pos;  // [C][E][2]
+    int *move; // [C][E][2]
+    const int *stop; // nullable: *stop != 0 -> the launch touches nothing (the objective entry points only)
+};
+
+// checks and argument struct of the scan, apart from its launch: the objective entry points refuse before anything is enqueued
+int prepare_scan(const char *who, const wtk_replay_config *cfg, int32_t kind, int32_t E, int32_t n_cycles, const double *track_dev, int32_t n_track,
+                 const double *a_dev, const double *b_dev, const int32_t *valid_dev, const double *share_dev, int32_t *pos_dev, int32_t *move_dev, ScanArgs &s);
+void launch_scan(const ScanArgs &s, hipStream_t st);
+// the chunk partials [E][S][n] of every experiment added in index order into summary [E][n] (the rows reduction and the precise reduction)
+void launch_finish(const double *partial, double *summary, int E, int S, int n, const int *stop, hipStream_t st);
+
+// an objective: the division of two summary slots its id stands for
+struct ObjectiveRule {
+    int id, num, den;    // objective = summary[num] / summary[den]
+    bool needs_3_cycles; // the trimmed rows: the first and the last logged cycle are dropped
+};
+
+// The tail of an objective entry point.  Refuses (null objective_dev, an id outside `rules`, a trimmed objective with fewer than 3 logged cycles) before
+// anything is enqueued; otherwise calls `produce`, which enqueues the launches that leave the [E][width] summary at summary_dev (non-zero: it failed),
+// and enqueues the division behind them.  Every one of those launches reads the same nullable stop flag.
+int enqueue_objective(const char *who, const ObjectiveRule *rules, int n_rules, int32_t objective, const double *summary_dev, int width, int32_t E, int n_log,
+                      double *objective_dev, const int32_t *stop_dev, hipStream_t st, const std::function<int()> &produce);
 
 } // namespace wtk

@@ -1,6 +1,6 @@
 """Closed-loop replay of track-driven experiments on the device, with tracking error: what the reference's `Simulator` + `SineMotorController` +
 `LoggingController` (sim/simulator.py:140-194, sim/motor_controllers.py:58-88, sim_controllers/logging_controller.py:145-185) produce frame by frame for
-one experiment, for a whole population of controller configurations at once (csrc/replay.hip).
+one experiment, for a whole population of controller configurations at once (csrc/replay.hip and the replay_*.hip files it names).
 
     rp = Replay(track, timing_config, experiment_config)
     res = rp.run(rp.polyfit([PolyfitConfig(2, [-9, -6, -3, 0, 2, 4], w) for w in weight_vectors]), rows=[0])
