@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define WTK_ABI_VERSION 7 /* 7: + wtk_yolo_create_planned / wtk_yolo_plan, wtk_yolo_status (additive); 2: + wtk_yolo_predict_views / _nms, wtk_track_*, wtk_comm_*; 3: + WTK_F16X3, wtk_recheck_*; 4: + wtk_recheck_select_counted; 5: + wtk_recheck_enqueue / _scatter; 6: + wtk_hybrid_*; still 7: + wtk_background, wtk_precise_error (additive: every earlier entry point is unchanged); still 7: + wtk_polyfit_*; still 7: + wtk_replay_* (additive); still 7: + wtk_replay_polyfit_targets / _scratch_doubles, wtk_replay_objective (additive); still 7: + wtk_replay_yolo_step / _positions / _track (additive); still 7: + wtk_mlp_trainer_* (additive) */
+#define WTK_ABI_VERSION 7 /* 7: + wtk_yolo_create_planned / wtk_yolo_plan, wtk_yolo_status (additive); 2: + wtk_yolo_predict_views / _nms, wtk_track_*, wtk_comm_*; 3: + WTK_F16X3, wtk_recheck_*; 4: + wtk_recheck_select_counted; 5: + wtk_recheck_enqueue / _scatter; 6: + wtk_hybrid_*; still 7: + wtk_background, wtk_precise_error (additive: every earlier entry point is unchanged); still 7: + wtk_polyfit_*; still 7: + wtk_replay_* (additive); still 7: + wtk_replay_polyfit_targets / _scratch_doubles, wtk_replay_objective (additive); still 7: + wtk_replay_yolo_step / _positions / _track (additive); still 7: + wtk_mlp_trainer_* (additive); still 7: + wtk_mlp_folded_floats / _fold_state_host, wtk_mlp_trainer_fold / _keep_scored / _get_scores, wtk_replay_mlp_targets / _waves (additive) */
 
 typedef enum wtk_dtype {
     WTK_F32 = 0, /* fp32 storage, exact-fp32 MFMA (v_mfma_f32_16x16x4_f32): parity mode   */
@@ -148,6 +148,31 @@ int wtk_mlp_trainer_eval_epoch(wtk_mlp_trainer *h, const float *x_dev, const flo
                                int32_t track_best, int32_t *active_dev, float *loss_dev, int32_t *num_correct_dev, float *pred_dev, void *stream);
 int wtk_mlp_trainer_get_state(wtk_mlp_trainer *h, int32_t which, float *state_host, int32_t *steps_host, void *stream);
 int wtk_mlp_trainer_get_stopping(wtk_mlp_trainer *h, float *best_loss_host, int32_t *has_best_host, int32_t *no_improve_host, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * A trained population as inference parameters, and the best state by a caller's score.
+ * Blob of ONE model, wtk_mlp_folded_floats(...) floats: what wtk_mlp_create builds from folded layers — per layer W [out_pad][in_pad] (in_pad = in_dim
+ *     rounded up to 4, out_pad = out_dim rounded up to 16, padding 0), then b [out_pad]; the whole rounded up to 4 floats.
+ * The fold is resmlp._fold's, bit for bit: float64 arithmetic cast to float32 at the end, s = gamma / sqrt(running_var + 1e-5), W' = W s,
+ *     b' = (b - running_mean) s + beta (product and sum rounded separately); layers without BatchNorm pass through unchanged.
+ *   folded_floats    the blob size of a structure (batch_norm is not looked at), -1 for a structure wtk_mlp_create refuses.  Needs no device.
+ *   fold_state_host  blob_host = the fold of one model's state_host (the layout above wtk_mlp_trainer_create).  Needs no device: the same function the
+ *                    device runs, compiled for the host.
+ *   trainer_fold     blob_dev [n_models][folded_floats] = the fold of every model's state, one launch on `stream`; which = 0 the current state, 1 the best
+ *                    state by validation loss, 4 the best state by score (refused before the first keep_scored call).
+ *   keep_scored      for every model with active_dev[e] != 0 (null: all): where score_dev[e] is finite and strictly below the stored score, or no score is
+ *                    stored yet, the current state and step count are copied to a third slot and the score is stored.  NaN and +-inf never win; a tie keeps
+ *                    the earlier state.  One launch on `stream`.  The slot (n_models x n_state floats) is allocated and filled with the initial state by the
+ *                    FIRST call: that call allocates device memory and uploads; later calls only launch.
+ *   get_state        which = 4 reads the slot (steps_host: the steps at the kept state); before any keep_scored call it is the initial state.
+ *   get_scores       best_score_host [n_models] (NaN where has_score_host[e] == 0).  Synchronises `stream`.
+ * ------------------------------------------------------------------------------------------ */
+int64_t wtk_mlp_folded_floats(const wtk_mlp_train_layer *layers, int32_t n_layers, int32_t n_blocks, int32_t layers_per_block);
+int wtk_mlp_fold_state_host(const wtk_mlp_train_layer *layers, int32_t n_layers, int32_t n_blocks, int32_t layers_per_block, const float *state_host,
+                            float *blob_host);
+int wtk_mlp_trainer_fold(wtk_mlp_trainer *h, int32_t which, float *blob_dev /*[n_models][folded_floats]*/, void *stream);
+int wtk_mlp_trainer_keep_scored(wtk_mlp_trainer *h, const double *score_dev /*[n_models]*/, const int32_t *active_dev, void *stream);
+int wtk_mlp_trainer_get_scores(wtk_mlp_trainer *h, double *best_score_host, int32_t *has_score_host, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * YOLOv8 detector (single image size per handle).
@@ -650,6 +675,28 @@ int wtk_replay_objective(const wtk_replay_config *cfg, int32_t kind, int32_t E, 
                          const double *a_dev, const double *b_dev, const int32_t *valid_dev, const double *share_dev, int32_t *pos_dev,
                          int32_t *move_dev, double *summary_dev, double *scratch_dev, int64_t scratch_doubles, int32_t objective,
                          double *objective_dev, const int32_t *stop_dev, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The per-cycle ResMLP targets of a population of E models of one structure in one call: what Replay.mlp computes model by model
+ * (wtk_mlp_predict_track, the float32 clip, the first box's corner), in the layout wtk_replay_scan reads for WTK_REPLAY_MLP, bit for bit.
+ *   layers ...        the structure (in_dim, out_dim, relu of every layer; batch_norm is not looked at), as for wtk_mlp_folded_floats
+ *   blob_dev          [E][wtk_mlp_folded_floats(...)] float32, 16-byte aligned: wtk_mlp_trainer_fold's output, or host-folded blobs uploaded
+ *   track32_dev       [n_track][4] float32 xywh, 16-byte aligned (the gather's track);  track_dev: the float64 track (the corner b)
+ *   anchors_dev       [n_cycles] anchor frames; the gather reads frames anchor + input_frames_host[j], j < n_in
+ *   a_dev             [n_cycles][E][2] = (double)clamp(prediction, -bound, bound) in float32 with NaN kept; 0 where the sample is invalid
+ *   b_dev             [n_cycles][E][2] = track_dev's (x, y) at clamp(anchor + input_frames_host[0], 0, n_track - 1)
+ *   valid_dev         [n_cycles][E] = 0 where a gathered frame lies outside the track or a box is not finite
+ * One launch on `stream`; nothing is allocated, nothing waited for.  stop_dev (nullable): when *stop_dev != 0 the launch writes nothing.
+ * One workgroup per (model, run of 16-cycle tiles) stages the blob in LDS once; wtk_replay_mlp_targets_waves(blob floats) is the number of wavefronts
+ * that fit next to it (at most 8; blobs above 32704 floats are read from global memory).
+ * Refused (error code, nothing launched): out_dim != 2, n_in outside 1..16 or n_in * 4 != in_dim, E < 1, n_cycles < 1, n_track < 1, a structure
+ *     wtk_mlp_create refuses, a required pointer that is null or misaligned.
+ * ------------------------------------------------------------------------------------------ */
+int wtk_replay_mlp_targets(const wtk_mlp_train_layer *layers, int32_t n_layers, int32_t n_blocks, int32_t layers_per_block, const float *blob_dev, int32_t E,
+                           const float *track32_dev, const double *track_dev, int32_t n_track, const int32_t *anchors_dev, int32_t n_cycles,
+                           const int32_t *input_frames_host, int32_t n_in, float bound, double *a_dev, double *b_dev, int32_t *valid_dev,
+                           const int32_t *stop_dev, void *stream);
+int32_t wtk_replay_mlp_targets_waves(int64_t blob_floats);
 
 /* ------------------------------------------------------------------------------------------
  * The YOLO controller's closed loop from device-resident state (csrc/replay_yolo.hip): the one experiment kind whose

@@ -12,56 +12,9 @@
 // The optional gather front-end is the batched form of MLPController.provide_movement_vector
 // (wtracker/sim/sim_controllers/mlp_controllers.py:38-56): 7 boxes of the track at
 // anchor + input_frames, NaN / out-of-range guard, x/y made relative to the first box's corner.
-#include "wtk_device.h"
-
-#include <type_traits>
+#include "mlp_forward.h"
 
 namespace wtk {
-
-constexpr int kLdAct = kMlpMaxDim + 4; // LDS row stride (floats), +4 breaks the power-of-two stride
-constexpr int kMlpLdsParams = 32768 - 64; // floats of the parameter blob staged in LDS (the fast path may read 63 floats past the blob)
-
-// y[16][out_pad] = act(W x + b); src/dst are LDS [16][kLdAct]
-// FAST (parameters in LDS): all fragments of a 64-deep K slice are fetched first — 32 LDS reads in flight instead of a
-// read -> wait -> MFMA round trip per k step — then the MFMA chain runs (same k order: bit-identical results).  Reads past
-// in_pad stay inside the activation row / the LDS parameter array and are never multiplied.
-template <bool FAST, typename P> // P: const float * into LDS or global memory
-__device__ __forceinline__ void mlp_layer(P params, const MlpLayerDev &L, const float *src, float *dst, int lane) {
-    const int r = lane & 15, g = lane >> 4;
-    P W = params + L.w_off;
-    P bvec = params + L.b_off;
-    for (int n0 = 0; n0 < L.out_pad; n0 += 16) {
-        floatx4 acc = {0.f, 0.f, 0.f, 0.f};
-        P wrow = W + (n0 + r) * L.in_pad;
-        if constexpr (FAST) {
-            for (int kb = 0; kb < L.in_pad; kb += 64) {
-                float xa[16], wb[16];
-#pragma unroll
-                for (int ks = 0; ks < 16; ++ks) {
-                    xa[ks] = src[r * kLdAct + kb + 4 * ks + g];
-                    wb[ks] = wrow[kb + 4 * ks + g];
-                }
-#pragma unroll
-                for (int ks = 0; ks < 16; ++ks)
-                    if (kb + 4 * ks < L.in_pad) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[ks], wb[ks], acc, 0, 0, 0);
-            }
-        } else {
-            for (int k0 = 0; k0 < L.in_pad; k0 += 4) {
-                const float xa = src[r * kLdAct + k0 + g]; // A[row = sample r][k = k0 + g]
-                const float wb = wrow[k0 + g];             // B[k = k0 + g][col = out n0 + r]
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(xa, wb, acc, 0, 0, 0);
-            }
-        }
-        // lane holds D[row = 4g + i][col = r]: sample 4g+i, out n0+r
-        const float b = bvec[n0 + r];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            float v = acc[i] + b;
-            if (L.relu) v = fmaxf(v, 0.f);
-            dst[(4 * g + i) * kLdAct + n0 + r] = v;
-        }
-    }
-}
 
 __global__ __launch_bounds__(64) void mlp_kernel(const MlpArgs a) {
     __shared__ float bufA[16 * kLdAct];
@@ -93,64 +46,16 @@ __global__ __launch_bounds__(64) void mlp_kernel(const MlpArgs a) {
         if (lane < 16) {
             const int s = s0 + lane;
             int ok = s < a.B;
-            float x0 = 0.f, y0 = 0.f;
-            if (ok) {
-                const int t = a.anchor_frames[s];
-                for (int j = 0; j < a.n_in; ++j) {
-                    const int f = t + a.input_frames[j];
-                    if (f < 0 || f >= a.n_frames) {
-                        ok = 0;
-                        break;
-                    }
-                    const float4 b = *reinterpret_cast<const float4 *>(a.track + (long long)f * 4);
-                    if (!(isfinite(b.x) && isfinite(b.y) && isfinite(b.z) && isfinite(b.w))) {
-                        ok = 0;
-                        break;
-                    }
-                    if (j == 0) {
-                        x0 = b.x;
-                        y0 = b.y;
-                    }
-                    float *d = &bufA[lane * kLdAct + j * 4];
-                    d[0] = b.x - x0;
-                    d[1] = b.y - y0;
-                    d[2] = b.z;
-                    d[3] = b.w;
-                }
-                if (!ok)
-                    for (int k = 0; k < a.in_dim; ++k) bufA[lane * kLdAct + k] = 0.f;
-            }
+            if (ok) ok = mlp_gather_sample(a.track, a.n_frames, a.anchor_frames[s], a.input_frames, a.n_in, a.in_dim, &bufA[lane * kLdAct]);
             s_valid[lane] = ok;
         }
     }
     __syncthreads();
 
-    auto run = [&](auto fast_tag, auto params) __attribute__((always_inline)) {
-        constexpr bool FAST = decltype(fast_tag)::value;
-        int li = 0;
-        // input layer -> h
-        mlp_layer<FAST>(params, s_layers[li++], bufA, bufH, lane);
-        __syncthreads();
-        for (int b = 0; b < a.n_blocks; ++b) {
-            const float *src = bufH;
-            float *dst = bufA;
-            for (int l = 0; l < a.layers_per_block; ++l) {
-                mlp_layer<FAST>(params, s_layers[li++], src, dst, lane);
-                __syncthreads();
-                src = dst;
-                dst = (dst == bufA) ? bufB : bufA;
-            }
-            // h <- h + block(h)
-            for (int i = lane; i < 16 * kLdAct; i += 64) bufH[i] += src[i];
-            __syncthreads();
-        }
-        mlp_layer<FAST>(params, s_layers[li], bufH, bufA, lane);
-        __syncthreads();
-    };
     if (in_lds)
-        run(std::true_type{}, static_cast<const float *>(wlds));
+        mlp_forward_tile<true>(static_cast<const float *>(wlds), s_layers, a.n_blocks, a.layers_per_block, bufA, bufB, bufH, lane);
     else
-        run(std::false_type{}, a.params);
+        mlp_forward_tile<false>(a.params, s_layers, a.n_blocks, a.layers_per_block, bufA, bufB, bufH, lane);
     for (int i = lane; i < 16 * a.out_dim; i += 64) {
         const int s = i / a.out_dim, k = i - s * a.out_dim;
         if (s0 + s < a.B) {

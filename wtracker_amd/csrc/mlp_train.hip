@@ -23,6 +23,7 @@
 // a BatchNorm layer 6 forward and 5 backward, the notebook's model 198 per training step and 26 per eval batch.
 #include "wtk_device.h"
 #include "wtk_internal.h"
+#include "mlp_fold.h" // MlpTrainLayerDev, the blob layout, mlp_fold_row
 
 #include <cmath>
 #include <string>
@@ -40,13 +41,6 @@ constexpr float kBnEps = 1e-5f, kBnMomentum = 0.1f;
 enum { TRAIN_STEP = 0, TRAIN_GRAD = 1, TRAIN_EVAL = 2 };
 enum { LOSS_MSE = 0, LOSS_L1 = 1 };
 enum { OPT_ADAM = 0, OPT_ADAMW = 1, OPT_SGD = 2, OPT_RMSPROP = 3 };
-
-struct MlpTrainLayerDev {
-    int in_dim, out_dim, relu, bn;
-    int w_off, b_off, g_off, be_off; // float offsets in the state: trainable section
-    int rm_off, rv_off;              // ... and in the buffer section behind it (bn only)
-    int pad_[2];
-};
 
 // Which layer feeds which: layer 0 is the input layer, layer n_layers - 1 the output layer (a plain Linear on the residual stream), and the layers
 // between them form blocks of layers_per_block, each block adding its last layer's output to the residual stream it read: h <- h + block(h).
@@ -554,6 +548,32 @@ __global__ __launch_bounds__(kTrainThreads) void mlp_train_kernel(const MlpTrain
     }
 }
 
+// ---- the inference blob of every model from its state (mlp_fold.h): one workgroup per (model, layer), one thread per padded output row
+__global__ __launch_bounds__(kMlpMaxDim) void mlp_fold_kernel(const float *state, int n_state, const MlpTrainLayerDev *layers, int n_layers, float *blob, int blob_floats) {
+    const int e = blockIdx.x, i = blockIdx.y, o = threadIdx.x;
+    int off = 0;
+    for (int j = 0; j < i; ++j) off += mlp_layer_blob_floats(layers[j].in_dim, layers[j].out_dim);
+    const MlpTrainLayerDev T = layers[i];
+    float *dst = blob + (size_t)e * blob_floats;
+    if (o < mlp_out_pad(T.out_dim)) mlp_fold_row(T, off, o, state + (size_t)e * n_state, dst);
+    if (i == n_layers - 1 && o == 0) // the blob's round-up to 4 floats
+        for (int k = off + mlp_layer_blob_floats(T.in_dim, T.out_dim); k < blob_floats; ++k) dst[k] = 0.f;
+}
+
+// ---- the best state by a caller's score: a finite score[e] strictly below the stored one (or the first one) copies the state and the step count.
+// NaN and +-inf never win, a tie keeps the earlier state.  One workgroup per model; the decision is read by every thread before thread 0 stores it.
+__global__ __launch_bounds__(256) void mlp_keep_scored_kernel(const float *state, int n_state, const int *steps, const double *score, const int *active, float *scored,
+                                                              int *scored_steps, double *best_score, int *has_score) {
+    const int e = blockIdx.x;
+    if (active && active[e] == 0) return; // block uniform
+    const double s = score[e];
+    const bool take = isfinite(s) && (!has_score[e] || s < best_score[e]);
+    __syncthreads();
+    if (!take) return;
+    for (int i = threadIdx.x; i < n_state; i += 256) scored[(size_t)e * n_state + i] = state[(size_t)e * n_state + i];
+    if (threadIdx.x == 0) best_score[e] = s, has_score[e] = 1, scored_steps[e] = steps[e];
+}
+
 } // namespace wtk
 
 // =====================================================================================================================================================
@@ -567,6 +587,13 @@ struct wtk_mlp_trainer {
     int n_state = 0, n_train = 0, any_bn = 0;
     MlpTrainArgs base{};
     std::vector<void *> allocs;
+    // the state kept by a caller's score (wtk_mlp_trainer_keep_scored): allocated by the first call, the initial state until a score wins
+    std::vector<float> initial; // host, [n_models][n_state]
+    std::vector<wtk_mlp_train_layer> structure;
+    float *scored = nullptr;
+    int *scored_steps = nullptr, *has_score = nullptr;
+    double *best_score = nullptr;
+    int64_t blob_floats = 0;
 };
 
 static int trainer_alloc(wtk_mlp_trainer *h, void **p, size_t bytes, bool zero) {
@@ -667,6 +694,9 @@ extern "C" int wtk_mlp_trainer_create(wtk_mlp_trainer **out, const wtk_mlp_train
     a.n_state = n_state, a.n_train = n_train, a.max_batch = d->max_batch;
     a.loss_kind = d->loss, a.opt_kind = d->optimizer, a.in_dim = L[0].in_dim, a.out_dim = L.back().out_dim;
     a.use_lds = n_state <= kTrainLdsFloats;
+    h->initial.assign(d->state, d->state + E * n_state);
+    h->structure.assign(d->layers, d->layers + d->n_layers);
+    h->blob_floats = mlp_blob_layout(d->layers, d->n_layers, d->n_blocks, d->layers_per_block, nullptr, nullptr);
     *out = h;
     return 0;
 }
@@ -725,14 +755,20 @@ extern "C" int wtk_mlp_trainer_eval_epoch(wtk_mlp_trainer *h, const float *x_dev
 
 extern "C" int wtk_mlp_trainer_get_state(wtk_mlp_trainer *h, int32_t which, float *state_host, int32_t *steps_host, void *stream) {
     if (!h || !state_host) return fail("wtk_mlp_trainer_get_state: null argument");
-    if (which < 0 || which > 3) return fail("wtk_mlp_trainer_get_state: which must be 0 (state), 1 (best state), 2 (first moment) or 3 (second moment)");
+    if (which < 0 || which > 4)
+        return fail("wtk_mlp_trainer_get_state: which must be 0 (state), 1 (best state), 2 (first moment), 3 (second moment) or 4 (best state by score)");
     DEVICE_GUARD(h);
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     const MlpTrainArgs &a = h->base;
-    const float *src = which == 0 ? a.state : which == 1 ? a.best : which == 2 ? a.m : a.v;
-    const size_t per = which <= 1 ? h->n_state : h->n_train;
+    if (which == 4 && !h->scored) { // no score yet: the initial state
+        std::memcpy(state_host, h->initial.data(), h->initial.size() * sizeof(float));
+        if (steps_host) std::memset(steps_host, 0, (size_t)h->n_models * 4);
+        return 0;
+    }
+    const float *src = which == 0 ? a.state : which == 1 ? a.best : which == 2 ? a.m : which == 3 ? a.v : h->scored;
+    const size_t per = (which <= 1 || which == 4) ? h->n_state : h->n_train;
     HIP_TRY(hipMemcpy(state_host, src, (size_t)h->n_models * per * 4, hipMemcpyDeviceToHost));
-    if (steps_host) HIP_TRY(hipMemcpy(steps_host, which == 1 ? a.best_steps : a.steps, (size_t)h->n_models * 4, hipMemcpyDeviceToHost));
+    if (steps_host) HIP_TRY(hipMemcpy(steps_host, which == 1 ? a.best_steps : which == 4 ? h->scored_steps : a.steps, (size_t)h->n_models * 4, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -744,5 +780,76 @@ extern "C" int wtk_mlp_trainer_get_stopping(wtk_mlp_trainer *h, float *best_loss
     HIP_TRY(hipMemcpy(best_loss_host, a.best_loss, (size_t)h->n_models * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(has_best_host, a.has_best, (size_t)h->n_models * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(no_improve_host, a.no_improve, (size_t)h->n_models * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// =====================================================================================================================================================
+// Folding a population for inference, and keeping the best state by a caller's score
+// =====================================================================================================================================================
+extern "C" int64_t wtk_mlp_folded_floats(const wtk_mlp_train_layer *layers, int32_t n_layers, int32_t n_blocks, int32_t layers_per_block) {
+    return mlp_blob_layout(layers, n_layers, n_blocks, layers_per_block, nullptr, nullptr);
+}
+
+extern "C" int wtk_mlp_fold_state_host(const wtk_mlp_train_layer *layers, int32_t n_layers, int32_t n_blocks, int32_t layers_per_block, const float *state_host,
+                                       float *blob_host) {
+    if (!layers || !state_host || !blob_host) return fail("wtk_mlp_fold_state_host: null argument");
+    const char *why = "";
+    std::vector<MlpLayerDev> B(n_layers > 0 ? n_layers : 0);
+    const int64_t F = mlp_blob_layout(layers, n_layers, n_blocks, layers_per_block, B.data(), &why);
+    if (F < 0) return fail(std::string("wtk_mlp_fold_state_host: ") + why);
+    std::vector<MlpTrainLayerDev> T(n_layers);
+    for (int i = 0; i < n_layers; ++i) T[i] = MlpTrainLayerDev{}, T[i].in_dim = layers[i].in_dim, T[i].out_dim = layers[i].out_dim, T[i].bn = layers[i].batch_norm ? 1 : 0;
+    state_layout(layers, n_layers, nullptr, T.data());
+    for (int i = 0; i < n_layers; ++i)
+        for (int o = 0; o < B[i].out_pad; ++o) mlp_fold_row(T[i], B[i].w_off, o, state_host, blob_host);
+    for (int64_t k = B[n_layers - 1].b_off + B[n_layers - 1].out_pad; k < F; ++k) blob_host[k] = 0.f;
+    return 0;
+}
+
+extern "C" int wtk_mlp_trainer_fold(wtk_mlp_trainer *h, int32_t which, float *blob_dev, void *stream) {
+    if (!h || !blob_dev) return fail("wtk_mlp_trainer_fold: null argument");
+    if (which != 0 && which != 1 && which != 4) return fail("wtk_mlp_trainer_fold: which must be 0 (state), 1 (best state) or 4 (best state by score)");
+    if (h->blob_floats < 0) return fail("wtk_mlp_trainer_fold: the structure has no inference blob (wtk_mlp_folded_floats)");
+    if (which == 4 && !h->scored) return fail("wtk_mlp_trainer_fold: no state was kept by score yet (wtk_mlp_trainer_keep_scored)");
+    DEVICE_GUARD(h);
+    const MlpTrainArgs &a = h->base;
+    const float *src = which == 0 ? a.state : which == 1 ? a.best : h->scored;
+    hipLaunchKernelGGL(mlp_fold_kernel, dim3(h->n_models, a.n_layers), dim3(kMlpMaxDim), 0, (hipStream_t)stream, src, h->n_state, a.layers, a.n_layers, blob_dev,
+                       (int)h->blob_floats);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int wtk_mlp_trainer_keep_scored(wtk_mlp_trainer *h, const double *score_dev, const int32_t *active_dev, void *stream) {
+    if (!h || !score_dev) return fail("wtk_mlp_trainer_keep_scored: null argument");
+    DEVICE_GUARD(h);
+    const size_t E = (size_t)h->n_models;
+    if (!h->scored) { // the first call allocates the slot and fills it with the initial state
+        float *scored = nullptr;
+        if (trainer_alloc(h, (void **)&scored, E * h->n_state * 4, false) || trainer_alloc(h, (void **)&h->scored_steps, E * 4, true) ||
+            trainer_alloc(h, (void **)&h->has_score, E * 4, true) || trainer_alloc(h, (void **)&h->best_score, E * 8, true))
+            return 1;
+        HIP_TRY(hipMemcpy(scored, h->initial.data(), E * h->n_state * 4, hipMemcpyHostToDevice));
+        h->scored = scored;
+    }
+    const MlpTrainArgs &a = h->base;
+    hipLaunchKernelGGL(mlp_keep_scored_kernel, dim3(h->n_models), dim3(256), 0, (hipStream_t)stream, a.state, h->n_state, a.steps, score_dev, active_dev, h->scored,
+                       h->scored_steps, h->best_score, h->has_score);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int wtk_mlp_trainer_get_scores(wtk_mlp_trainer *h, double *best_score_host, int32_t *has_score_host, void *stream) {
+    if (!h || !best_score_host || !has_score_host) return fail("wtk_mlp_trainer_get_scores: null argument");
+    DEVICE_GUARD(h);
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    if (!h->scored) {
+        for (int e = 0; e < h->n_models; ++e) best_score_host[e] = NAN, has_score_host[e] = 0;
+        return 0;
+    }
+    HIP_TRY(hipMemcpy(best_score_host, h->best_score, (size_t)h->n_models * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(has_score_host, h->has_score, (size_t)h->n_models * 4, hipMemcpyDeviceToHost));
+    for (int e = 0; e < h->n_models; ++e)
+        if (!has_score_host[e]) best_score_host[e] = NAN; // no score stored yet
     return 0;
 }

@@ -1,6 +1,7 @@
 // C ABI of libwtk_hip.so (see include/wtk_hip.h), part 1: errors and versions, the ResMLP, the batched per-cycle predictors, the second-look
 // helpers and the view crop.  The detector handle lives in wtk_plan.hip / wtk_run.hip, the hybrid object in wtk_hybrid.hip (wtk_internal.h).
 #include "wtk_internal.h"
+#include "mlp_fold.h"
 
 #include <algorithm>
 #include <cmath>
@@ -74,34 +75,17 @@ extern "C" int wtk_mlp_create(wtk_mlp **out, const wtk_mlp_desc *d) {
     if (wtk_device_count() <= d->device) return fail("wtk_mlp_create: no such HIP device (is a GPU visible?)");
     DEVICE_GUARD(d);
     std::vector<MlpLayerDev> L(d->n_layers);
-    std::vector<float> blob;
+    const char *why = "";
+    const int64_t n_blob = mlp_blob_layout(d->layers, d->n_layers, d->n_blocks, d->layers_per_block, L.data(), &why); // the layout, stated once (mlp_fold.h)
+    if (n_blob < 0) return fail(std::string("wtk_mlp_create: ") + why);
+    std::vector<float> blob((size_t)n_blob, 0.f); // the kernel copies it to LDS in float4 units
     for (int i = 0; i < d->n_layers; ++i) {
         const wtk_mlp_layer &s = d->layers[i];
-        if (s.in_dim <= 0 || s.out_dim <= 0 || s.in_dim > kMlpMaxDim || s.out_dim > kMlpMaxDim) return fail("wtk_mlp_create: layer dim out of range");
-        if (i > 0) {
-            const bool block_first = (i - 1) % std::max(d->layers_per_block, 1) == 0 && i < d->n_layers - 1;
-            const int prev_out = (block_first || i == d->n_layers - 1) ? L[0].out_dim : L[i - 1].out_dim;
-            if (s.in_dim != prev_out) return fail("wtk_mlp_create: layer dims do not chain");
-        }
-        MlpLayerDev &l = L[i];
-        l.in_dim = s.in_dim;
-        l.out_dim = s.out_dim;
-        l.in_pad = (s.in_dim + 3) / 4 * 4;
-        l.out_pad = (s.out_dim + 15) / 16 * 16;
-        l.relu = s.relu;
-        l.w_off = (int)blob.size();
-        blob.resize(blob.size() + (size_t)l.out_pad * l.in_pad, 0.f);
+        const MlpLayerDev &l = L[i];
         for (int o = 0; o < s.out_dim; ++o)
             for (int k = 0; k < s.in_dim; ++k) blob[l.w_off + (size_t)o * l.in_pad + k] = s.weight[(size_t)o * s.in_dim + k];
-        l.b_off = (int)blob.size();
-        blob.resize(blob.size() + l.out_pad, 0.f);
         for (int o = 0; o < s.out_dim; ++o) blob[l.b_off + o] = s.bias[o];
-        l.pad_ = 0;
     }
-    // every block must return to the residual width
-    for (int b = 0; b < d->n_blocks; ++b)
-        if (L[d->layers_per_block * (b + 1)].out_dim != L[0].out_dim) return fail("wtk_mlp_create: block output dim != residual dim");
-    blob.resize((blob.size() + 3) / 4 * 4, 0.f); // the kernel copies it to LDS in float4 units
     wtk_mlp *h = new wtk_mlp();
     h->device = d->device;
     h->n_params = (int)blob.size();

@@ -90,6 +90,11 @@ SIGNATURES = {
     "wtk_mlp_trainer_eval_epoch": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "wtk_mlp_trainer_get_state": (_i32, [_vp, _i32, _vp, _vp, _vp]),
     "wtk_mlp_trainer_get_stopping": (_i32, [_vp, _vp, _vp, _vp, _vp]),
+    "wtk_mlp_folded_floats": (_i64, [C.POINTER(_MlpTrainLayer), _i32, _i32, _i32]),
+    "wtk_mlp_fold_state_host": (_i32, [C.POINTER(_MlpTrainLayer), _i32, _i32, _i32, _vp, _vp]),
+    "wtk_mlp_trainer_fold": (_i32, [_vp, _i32, _vp, _vp]),
+    "wtk_mlp_trainer_keep_scored": (_i32, [_vp, _vp, _vp, _vp]),
+    "wtk_mlp_trainer_get_scores": (_i32, [_vp, _vp, _vp, _vp]),
     "wtk_yolo_conv_count": (_i32, [_f32, _f32, _i32, _i32]),
     "wtk_yolo_conv_info": (_i32, [_f32, _f32, _i32, _i32, _i32, _pi32, _pi32, _pi32, _pi32, _pi32, C.c_char_p, _size]),
     "wtk_yolo_create": (_i32, [_pvp, C.POINTER(_YoloDesc)]),
@@ -149,6 +154,8 @@ SIGNATURES = {
     "wtk_replay_polyfit_targets_scratch_doubles": (_i64, [_i32, _i32, _i32, _i32]),
     "wtk_replay_polyfit_targets": (_i32, [_vp, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _f64, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp]),
     "wtk_replay_objective": (_i32, [_pcfg, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "wtk_replay_mlp_targets": (_i32, [C.POINTER(_MlpTrainLayer), _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _f32, _vp, _vp, _vp, _vp, _vp]),
+    "wtk_replay_mlp_targets_waves": (_i32, [_i64]),
     "wtk_replay_yolo_step": (_i32, [_pcfg, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "wtk_replay_yolo_positions": (_i32, [_pcfg, _i32, _vp, _vp, _vp, _vp, _vp]),
     "wtk_replay_yolo_track": (_i32, [_pcfg, _i32, _vp, _vp, _vp, _vp]),
@@ -594,6 +601,45 @@ def replay_yolo_track(cfg: _ReplayConfig, n_cycles: int, xywh_dev, frame_pos_dev
     """View-pixel detections float32 [R, 4] -> the absolute float64 track [R, 4] wtk_replay_rows reads (wtk_replay_yolo_track)."""
     _check(load().wtk_replay_yolo_track(C.byref(cfg) if cfg is not None else None, n_cycles, _ptr(xywh_dev), _ptr(frame_pos_dev), _ptr(track_dev),
                                         C.c_void_p(stream)), "wtk_replay_yolo_track")
+
+
+def mlp_structure(shapes_relu: Sequence[tuple]):
+    """The wtk_mlp_train_layer array of a structure: [(in_dim, out_dim, relu)] in execution order (batch_norm is left 0: the blob does not depend on it)."""
+    arr = (_MlpTrainLayer * len(shapes_relu))()
+    for i, (k, n, relu) in enumerate(shapes_relu):
+        arr[i] = _MlpTrainLayer(int(k), int(n), int(bool(relu)), 0)
+    return arr
+
+
+def mlp_folded_floats(layers, n_blocks: int, layers_per_block: int) -> int:
+    """Floats of one model's inference blob (wtk_mlp_folded_floats; needs no device): -1 for a structure wtk_mlp_create refuses."""
+    return int(load().wtk_mlp_folded_floats(layers, len(layers), int(n_blocks), int(layers_per_block)))
+
+
+def mlp_fold_state_host(layers, n_blocks: int, layers_per_block: int, state: np.ndarray) -> np.ndarray:
+    """The inference blob of one model's unfolded float32 state (wtk_mlp_fold_state_host; needs no device).  `layers`: a _MlpTrainLayer array
+    with the batch_norm flags of the state."""
+    F = mlp_folded_floats(layers, n_blocks, layers_per_block)
+    if F < 0:
+        raise WtkError("wtk_mlp_folded_floats: the structure has no inference blob")
+    state = np.ascontiguousarray(state, dtype=np.float32)
+    blob = np.empty(F, dtype=np.float32)
+    _check(load().wtk_mlp_fold_state_host(layers, len(layers), int(n_blocks), int(layers_per_block), _ptr(state), _ptr(blob)), "wtk_mlp_fold_state_host")
+    return blob
+
+
+def replay_mlp_targets(layers, n_blocks: int, layers_per_block: int, blob_dev, E: int, track32_dev, track_dev, n_track: int, anchors_dev, n_cycles: int,
+                       input_frames: Sequence[int], bound: float, a_dev, b_dev, valid_dev, stop_dev=None, stream: int = 0):
+    """MLP targets of E device-resident folded models in one call (wtk_replay_mlp_targets): a_dev, b_dev [n_cycles, E, 2], valid_dev [n_cycles, E]."""
+    inf = np.ascontiguousarray(input_frames, dtype=np.int32)
+    _check(load().wtk_replay_mlp_targets(layers, len(layers), int(n_blocks), int(layers_per_block), _ptr(blob_dev), int(E), _ptr(track32_dev), _ptr(track_dev),
+                                         int(n_track), _ptr(anchors_dev), int(n_cycles), _ptr(inf), len(inf), C.c_float(bound), _ptr(a_dev), _ptr(b_dev),
+                                         _ptr(valid_dev), _ptr(stop_dev), C.c_void_p(stream)), "wtk_replay_mlp_targets")
+
+
+def replay_mlp_targets_waves(blob_floats: int) -> int:
+    """Wavefronts per workgroup wtk_replay_mlp_targets runs next to a blob of that size (before the cap by the number of tiles)."""
+    return int(load().wtk_replay_mlp_targets_waves(int(blob_floats)))
 
 
 # -------------------------------------------------------------------------------------------------

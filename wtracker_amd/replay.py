@@ -60,7 +60,7 @@ import numpy as np
 from . import hip, yolo_spec
 from .controllers import PolyfitConfig, YoloConfig, _raise_on_overflow, _read_track_csv, check_device_frames
 from .polyfit_opt import SwarmResult, _check_degree, check_swarm_args, check_times, polyfit_config, swarm_search, weights_to_device
-from .resmlp import FoldedResMLP, from_torch_module
+from .resmlp import FoldedResMLP, from_torch_module, pack_blob
 from .sim import LOG_COLUMNS, ExperimentConfig, TimingConfig
 
 KINDS = {"csv": hip.REPLAY_CSV, "optimal": hip.REPLAY_OPTIMAL, "polyfit": hip.REPLAY_POLYFIT, "mlp": hip.REPLAY_MLP}
@@ -81,6 +81,19 @@ def polyfit_classes(track: np.ndarray, cycle_frame_num: int, n_cycles: int, samp
     masks = (finite.astype(np.int64) << np.arange(len(st), dtype=np.int64)[None, :]).sum(axis=1)
     class_mask, cycle_class = np.unique(masks, return_inverse=True)
     return cycle_class.reshape(-1).astype(np.int32), class_mask.astype(np.int32)
+
+
+def mlp_clip_bound(timing_config: TimingConfig, max_speed: float, pred_frames) -> float:
+    """The float32 bound MLPController clips a prediction to: the distance a worm of `max_speed` mm/s covers until the first predicted frame."""
+    max_dist = max_speed * (timing_config.px_per_mm / timing_config.frames_per_sec) * list(pred_frames)[0]
+    return float(np.float32(max_dist))
+
+
+def population_frames(input_frames, pred_frames) -> tuple:
+    """(input_frames, pred_frames) of a population as int lists; refuses a population that does not say which frames its models read and predict."""
+    if input_frames is None or pred_frames is None or len(input_frames) == 0 or len(pred_frames) == 0:
+        raise ValueError("mlp_population needs the models' input_frames and pred_frames (a trainer built from state dicts takes them as entries of the dict)")
+    return [int(v) for v in input_frames], [int(v) for v in pred_frames]
 
 
 def sine_shares(M: int) -> np.ndarray:
@@ -391,6 +404,7 @@ class Replay:
         self._share = torch.from_numpy(sine_shares(self.M)).to(self._dev)
         self._cycles = torch.arange(self.n_cycles, dtype=torch.int32, device=self._dev)
         self._track_f32 = None
+        self._anchors = None  # mlp_population's anchor frames
         self._classes = {}  # sorted sample times -> (cycle_class, class_mask) on the device
         self._last_times = None  # of the last polyfit_population / optimize_polyfit call (to_config's default)
         self._frames = self._background = None  # attach_frames
@@ -478,8 +492,7 @@ class Replay:
         import torch
 
         folded: FoldedResMLP = model if isinstance(model, FoldedResMLP) else from_torch_module(model)
-        tc = self.timing_config
-        max_dist = max_speed * (tc.px_per_mm / tc.frames_per_sec) * list(folded.pred_frames)[0]
+        bound = mlp_clip_bound(self.timing_config, max_speed, folded.pred_frames)
         net = hip.HipMLP(folded.layers, folded.n_blocks, folded.layers_per_block, device=self._dev.index)
         a, b, valid, pred, ok = self._empty(1, with_b=True, pred_dtype=torch.float32)
         with torch.cuda.device(self._dev):
@@ -487,12 +500,53 @@ class Replay:
                 self._track_f32 = self.track.to(torch.float32).contiguous()
             anchors = (self._cycles * self.L + (self.I - self.P)).contiguous()
             net.predict_track(self._track_f32, self.n_track, anchors, self.n_cycles, list(folded.input_frames), pred, ok, stream=self._stream())
-            bound = float(np.float32(max_dist))
             a[:, 0] = torch.clamp(pred, -bound, bound).to(torch.float64)
             first = (anchors.to(torch.int64) + int(list(folded.input_frames)[0])).clamp(0, self.n_track - 1)  # only read where the sample is valid
             b[:, 0] = self.track[first, :2]
             valid[:, 0] = ok
         return Targets("mlp", 1, a, b, valid, keep=net)  # nothing is waited for: the handle lives as long as its targets
+
+    def mlp_population(self, models, max_speed: float = 0.9, which="current") -> Targets:
+        """`mlp(model)` of every model of a population in one call and with the same bits (wtk_replay_mlp_targets).  `models`: a
+        `HipMLPTrainer` — its states are folded on the device (`which`: "current", "best" by validation loss, "scored" by keep_scored / fit(closed_loop=...)),
+        nothing leaves the device and nothing is waited for — or a list of `FoldedResMLP` / live `WormPredictor`s of one structure, folded on the host and
+        uploaded once.  Experiment e of the result is model e."""
+        import torch
+
+        from .training import HipMLPTrainer, state_slot
+
+        state_slot(which)
+        if isinstance(models, HipMLPTrainer):
+            xi, yi = population_frames(models.input_frames, models.pred_frames)
+            (layers, n_blocks, per_block), E = models.blob_structure(), models.E
+            if models.out_dim != 2:
+                raise ValueError(f"the replay takes predictors of one frame (out_dim 2), the trainer's models have out_dim {models.out_dim}")
+            blob = models.folded_blob(which)
+        else:
+            folded = [m if isinstance(m, FoldedResMLP) else from_torch_module(m) for m in models]
+            if not folded:
+                raise ValueError("at least one model is needed")
+            f0, E = folded[0], len(folded)
+            xi, yi = population_frames(f0.input_frames, f0.pred_frames)
+            key = lambda f: ([(w.shape, bool(r)) for w, _, r in f.layers], f.n_blocks, f.layers_per_block, list(f.input_frames), list(f.pred_frames))  # noqa: E731
+            if any(key(f) != key(f0) for f in folded[1:]):
+                raise ValueError("all models of a population must have the same structure, input_frames and pred_frames")
+            if f0.out_dim != 2:
+                raise ValueError(f"the replay takes predictors of one frame (out_dim 2), the models have out_dim {f0.out_dim}")
+            layers, n_blocks, per_block = hip.mlp_structure([(w.shape[1], w.shape[0], r) for w, _, r in f0.layers]), f0.n_blocks, f0.layers_per_block
+            blob = torch.from_numpy(np.stack([pack_blob(f) for f in folded])).to(self._dev)
+        bound = mlp_clip_bound(self.timing_config, max_speed, yi)
+        dev, C = self._dev, self.n_cycles
+        tg = Targets("mlp", E, torch.empty((C, E, 2), dtype=torch.float64, device=dev), torch.empty((C, E, 2), dtype=torch.float64, device=dev),
+                     torch.empty((C, E), dtype=torch.int32, device=dev), keep=blob)
+        with torch.cuda.device(dev):
+            if self._track_f32 is None:
+                self._track_f32 = self.track.to(torch.float32).contiguous()
+            if self._anchors is None:
+                self._anchors = (self._cycles * self.L + (self.I - self.P)).contiguous()
+            hip.replay_mlp_targets(layers, n_blocks, per_block, blob, E, self._track_f32, self.track, self.n_track, self._anchors, C, xi, bound, tg.a, tg.b,
+                                   tg.valid, stream=self._stream())
+        return tg
 
     # ------------------------------------------------------------------ populations of weight vectors
     def _sample_times(self, sample_times) -> tuple:

@@ -91,6 +91,22 @@ def fold_state_dict(sd: Mapping[str, np.ndarray], input_frames: Sequence[int], p
     return FoldedResMLP(layers, n_blocks, per_block, [int(v) for v in input_frames], [int(v) for v in pred_frames])
 
 
+def pack_blob(folded: FoldedResMLP) -> np.ndarray:
+    """The padded float32 parameter blob wtk_mlp_create builds from folded layers (and wtk_mlp_trainer_fold from a trainer's state): per layer
+    W [ceil16(out)][ceil4(in)] with zero padding, then b [ceil16(out)]."""
+    parts = []
+    for w, b, _ in folded.layers:
+        w, b = np.asarray(w, dtype=np.float32), np.asarray(b, dtype=np.float32)
+        n, k = w.shape
+        wp = np.zeros(((n + 15) // 16 * 16, (k + 3) // 4 * 4), dtype=np.float32)
+        wp[:n, :k] = w
+        bp = np.zeros(wp.shape[0], dtype=np.float32)
+        bp[:n] = b
+        parts += [wp.ravel(), bp]
+    blob = np.concatenate(parts)
+    return np.concatenate([blob, np.zeros(-blob.size % 4, dtype=np.float32)])
+
+
 def load_npz(path: str) -> FoldedResMLP:
     """Load a fixture written by tests/golden/make_golden.py (state-dict tensors + IOConfig)."""
     z = np.load(path)

@@ -24,6 +24,18 @@ OPTIMIZERS = {"adam": 0, "adamw": 1, "sgd": 2, "rmsprop": 3}  # the keys of the 
 MAX_BATCH = 1024
 LDS_STATE_FLOATS = 36864  # kTrainLdsFloats (csrc/mlp_train.hip): a model state above this trains from global memory
 DEFAULT_MAX_BATCH = 256  # the reference's TrainConfig.batch_size (neural/config.py:67)
+# the states a trainer keeps per model, by name -> `which` of wtk_mlp_trainer_get_state / _fold: the current one, the one of the epoch with the lowest
+# validation loss, the one of the lowest score handed to keep_scored (fit(closed_loop=...): the closed-loop error)
+STATE_SLOTS = {"current": 0, "best": 1, "scored": 4}
+
+
+def state_slot(which) -> int:
+    """`which` of the library for a name of STATE_SLOTS; True / False keep their meaning of state_dict(best=...): best / current."""
+    if isinstance(which, (bool, np.bool_)):
+        return 1 if which else 0
+    if which not in STATE_SLOTS:
+        raise ValueError(f"unknown state {which!r}: one of {sorted(STATE_SLOTS)}")
+    return STATE_SLOTS[which]
 
 
 @dataclass
@@ -35,6 +47,7 @@ class FitResult:
     train_acc: list = field(default_factory=list)
     test_loss: list = field(default_factory=list)
     test_acc: list = field(default_factory=list)
+    closed_loop: list = field(default_factory=list)  # fit(closed_loop=...): the closed-loop objective after every epoch the model ran
 
 
 def train_test_split(n: int, fraction: float = 0.8, seed: int = 42, device=None):
@@ -295,16 +308,22 @@ class HipMLPTrainer:
 
     # ------------------------------------------------------------------ fit
     def fit(self, X_train, y_train, X_test, y_test, num_epochs: int, batch_size: int = 128, early_stopping: Optional[int] = None, shuffle: bool = True, seed: int = 42,
-            order=None) -> list:
+            order=None, closed_loop=None, closed_loop_objective: str = "trimmed_bbox_error", max_speed: float = 0.9) -> list:
         """Trainer.fit for every model: one train launch and one test launch per epoch, one small readback per epoch (the `active` flags).  `order`: a callable
         epoch -> int32 [E, n] / [n] tensor, or a fixed tensor, instead of the seeded per-epoch, per-model torch.randperm.  Returns one FitResult per model.
-        As the reference's fit, every call starts its early stopping afresh (best_val_loss = None); the parameters and optimizer moments carry on."""
+        As the reference's fit, every call starts its early stopping afresh (best_val_loss = None); the parameters and optimizer moments carry on.
+
+        `closed_loop`: a `Replay`.  After every test epoch the population is folded and replayed on it (Replay.mlp_population, Replay.objective with
+        `closed_loop_objective`, a precise one where frames are attached) and the state with the lowest score so far is kept per model (keep_scored, with the
+        epoch's `active` flags as they were before the test epoch: a model is scored for every epoch it trained): three more enqueues, no host wait.
+        The scores come back once, at the end, in FitResult.closed_loop; state_dict / folded(best="scored") read the kept state.  Early stopping stays
+        keyed to the validation loss.  The scores kept by earlier fits or keep_scored calls stay in the comparison."""
         import torch
 
         n, n_test = int(X_train.shape[0]), int(X_test.shape[0])
         gen = torch.Generator().manual_seed(int(seed))
         self.active.fill_(1)
-        tr_loss, tr_nc, te_loss, te_nc, ran = [], [], [], [], []
+        tr_loss, tr_nc, te_loss, te_nc, ran, cl = [], [], [], [], [], []
         for epoch in range(int(num_epochs)):
             own = order is None
             if order is not None:
@@ -317,11 +336,16 @@ class HipMLPTrainer:
             a, b = self.train_epoch(X_train, y_train, o, batch_size, active=self.active, check_order=not own)
             c, d = self.test_epoch(X_test, y_test, batch_size, patience=early_stopping, track_best=True, active=self.active, reset_best=epoch == 0)
             tr_loss.append(a), tr_nc.append(b), te_loss.append(c), te_nc.append(d), ran.append(was)
+            if closed_loop is not None:
+                score = closed_loop.objective(closed_loop.mlp_population(self, max_speed=max_speed, which="current"), closed_loop_objective)
+                self.keep_scored(score, active=was)
+                cl.append(score)
             if early_stopping is not None and not bool(self.active.any().item()):  # the one readback of the epoch
                 break
         ran = torch.stack(ran).cpu().numpy().astype(bool)  # [epochs, E]
         tr_loss, te_loss = torch.stack(tr_loss).cpu().numpy(), torch.stack(te_loss).cpu().numpy()
         tr_nc, te_nc = torch.stack(tr_nc).cpu().numpy(), torch.stack(te_nc).cpu().numpy()
+        cl = torch.stack(cl).cpu().numpy() if cl else None  # [epochs, E]
         results = []
         for e in range(self.E):
             r = FitResult(int(ran[:, e].sum()))
@@ -330,21 +354,24 @@ class HipMLPTrainer:
                 r.test_loss += [float(v) for v in te_loss[ep, e]]
                 r.train_acc.append(100.0 * float(tr_nc[ep, e].sum()) / n)
                 r.test_acc.append(100.0 * float(te_nc[ep, e].sum()) / n_test)
+                if cl is not None:
+                    r.closed_loop.append(float(cl[ep, e]))
             results.append(r)
         return results
 
     # ------------------------------------------------------------------ reading the models back
     def _get(self, which: int):
-        per = self.n_state if which <= 1 else self.n_train
+        per = self.n_state if which in (0, 1, 4) else self.n_train
         buf = np.empty((self.E, per), dtype=np.float32)
         steps = np.empty(self.E, dtype=np.int32)
         hip._check(hip.load().wtk_mlp_trainer_get_state(self._h, which, hip._ptr(buf), hip._ptr(steps), self._stream()), "wtk_mlp_trainer_get_state")
         return buf, steps
 
-    def state_dict(self, e: int = 0, best: bool = False) -> dict:
+    def state_dict(self, e: int = 0, best=False) -> dict:
         """Model e under the reference's key names (numpy arrays): what fold_state_dict, a real WormPredictor's load_state_dict (through torch.as_tensor) and
-        Replay.mlp (through .folded) take.  best: the state of the epoch with the lowest validation loss (the initial state before the first test epoch)."""
-        buf, steps = self._get(1 if best else 0)
+        Replay.mlp (through .folded) take.  best: the state of the epoch with the lowest validation loss (the initial state before the first test epoch);
+        best="scored": the state of the lowest score keep_scored was handed (the initial state before the first score)."""
+        buf, steps = self._get(state_slot(best))
         sd = self._unpack(buf[e])
         for b, n0 in self._nbt0[e].items():
             sd[b + ".num_batches_tracked"] = np.asarray(n0 + int(steps[e]), dtype=np.int64)
@@ -352,6 +379,43 @@ class HipMLPTrainer:
         for p, b, _ in self._rows:
             order += [p + ".weight", p + ".bias"] + ([b + ".weight", b + ".bias", b + ".running_mean", b + ".running_var", b + ".num_batches_tracked"] if b else [])
         return {k: sd[k] for k in order}
+
+    # ------------------------------------------------------------------ the population as inference parameters; the best state by a caller's score
+    def blob_structure(self) -> tuple:
+        """(wtk_mlp_train_layer array, n_blocks, layers_per_block) of this structure, as wtk_mlp_folded_floats / wtk_replay_mlp_targets take it."""
+        return self._layers, self.n_blocks, self.layers_per_block
+
+    def folded_blob(self, which="current"):
+        """Every model's padded inference blob as a device float32 [E, F] tensor (wtk_mlp_trainer_fold: BatchNorm folded on the device with
+        resmlp._fold's bits, wtk_mlp_create's layout).  One launch on the current stream; nothing leaves the device, nothing is waited for."""
+        import torch
+
+        w = state_slot(which)
+        F = hip.mlp_folded_floats(*self.blob_structure())
+        if F < 0:
+            raise WtkError("ResMLP trainer: the structure has no inference blob (wtk_mlp_folded_floats)")
+        blob = torch.empty((self.E, F), dtype=torch.float32, device=self._dev)
+        with torch.cuda.device(self._dev):
+            hip._check(hip.load().wtk_mlp_trainer_fold(self._h, w, hip._ptr(blob), self._stream()), "wtk_mlp_trainer_fold")
+        return blob
+
+    def keep_scored(self, score, active=None) -> None:
+        """Per model with active[e] != 0 (None: all): where score[e] (device float64 [E], lower is better) is finite and strictly below the kept one, or
+        none is kept yet, keep the current state as the "scored" state.  One launch; the first call allocates the slot (E x n_state floats)."""
+        import torch
+
+        if not (isinstance(score, torch.Tensor) and score.is_cuda and score.dtype == torch.float64 and tuple(score.shape) == (self.E,) and score.is_contiguous()):
+            raise ValueError(f"score must be a contiguous CUDA float64 tensor [{self.E}]")
+        if active is not None and not (active.is_cuda and active.dtype == torch.int32 and tuple(active.shape) == (self.E,) and active.is_contiguous()):
+            raise ValueError(f"active must be a contiguous CUDA int32 tensor [{self.E}]")
+        with torch.cuda.device(self._dev):
+            hip._check(hip.load().wtk_mlp_trainer_keep_scored(self._h, hip._ptr(score), hip._ptr(active), self._stream()), "wtk_mlp_trainer_keep_scored")
+
+    def scores(self):
+        """(kept score float64 [E], NaN where none is kept; has-score int32 [E]) as numpy arrays."""
+        best, has = np.empty(self.E, np.float64), np.empty(self.E, np.int32)
+        hip._check(hip.load().wtk_mlp_trainer_get_scores(self._h, hip._ptr(best), hip._ptr(has), self._stream()), "wtk_mlp_trainer_get_scores")
+        return best, has
 
     def moments(self, e: int = 0):
         """(first, second) optimizer moment of model e as {key: array} (exp_avg, exp_avg_sq of Adam / AdamW; square_avg of RMSprop is the second), steps taken."""
@@ -364,7 +428,7 @@ class HipMLPTrainer:
         hip._check(hip.load().wtk_mlp_trainer_get_stopping(self._h, hip._ptr(best), hip._ptr(has), hip._ptr(cnt), self._stream()), "wtk_mlp_trainer_get_stopping")
         return best, has, cnt
 
-    def folded(self, e: int = 0, best: bool = False, input_frames: Optional[Sequence[int]] = None, pred_frames: Optional[Sequence[int]] = None) -> FoldedResMLP:
+    def folded(self, e: int = 0, best=False, input_frames: Optional[Sequence[int]] = None, pred_frames: Optional[Sequence[int]] = None) -> FoldedResMLP:
         xi = input_frames if input_frames is not None else (self.input_frames if self.input_frames is not None else [])
         yi = pred_frames if pred_frames is not None else (self.pred_frames if self.pred_frames is not None else [])
         return fold_state_dict(self.state_dict(e, best), list(xi), list(yi), self.activations)
