@@ -677,6 +677,69 @@ int wtk_replay_objective(const wtk_replay_config *cfg, int32_t kind, int32_t E, 
                          double *objective_dev, const int32_t *stop_dev, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * A population replayed on a SET of T tracks at once, with a pooled objective (csrc/replay_set.hip).
+ *
+ * All tracks share the timing, camera and microscope entries of `cfg` (its num_frames, frame_w, frame_h, init_x, init_y are not read: they
+ * are each track's own, in the table).  The tracks lie in ONE "super-track" track_dev [n_super][4], n_super a multiple of L: track t
+ * starts at row cyc_off L, holds its n_track rows, then NaN rows up to the end of its slot of max(n_cycles, ceil(n_track / L)) cycles, then
+ * guard_cycles further all-NaN cycles.  Every targets entry point treats a NaN row as it treats a row outside the track, so ONE call of
+ * wtk_replay_polyfit_targets / wtk_replay_mlp_targets / wtk_track_polyfit / wtk_track_median_centers / wtk_mlp_predict_track over the
+ * super-track, with n_cycles = n_super / L, gives every cycle of every track the bits the call on that track alone gives, as long as
+ * no frame offset from a cycle's start reaches further than guard_cycles L frames.  All per-cycle arrays (a_dev, b_dev, valid_dev,
+ * pos_dev, move_dev) are indexed by the super-track's cycle: [n_super / L][E]...; track t's cycles are the contiguous slice from cyc_off.
+ * The NaN fill is the caller's: the entry points check the table, never the rows.
+ *
+ * wtk_replay_set_track   one table entry.  The caller fills every field; the derived ones (n_cycles' range, n_log = (num_frames - 1) / L,
+ *     R = n_log L, chunk0 = the sum of ceil(R / 4096) over the tracks before) are checked against the others.  tracks_host [T] is read by
+ *     the checks, tracks_dev [T] (the same bytes, uploaded once by the caller) by the kernels.
+ * wtk_replay_set_scan   wtk_replay_scan of every (track, experiment): one lane each, sequential over the track's cycles from the track's own
+ *     clamped init position, with the track's own clamp and (CSV) row count.  Out: pos_dev / move_dev [n_super / L][E][2]; cycles of no
+ *     track are not written.
+ * wtk_replay_set_rows   wtk_replay_rows' reduction (no row, per-row or slot output) of every (track, experiment): one block per
+ *     (experiment, chunk of 4096 rows of one track), the same lane order and tree; the trimmed rows drop the first and the last logged
+ *     cycle of EVERY track (DataAnalyzer.clean works per log).  One finish launch adds, per (experiment, slot), each track's chunk partials
+ *     in index order into track_summary_dev [T][E][WTK_REPLAY_SUMMARY_DOUBLES] (bit-equal to wtk_replay_rows' summary of that track alone)
+ *     and those, in track order from 0.0, into summary_dev [E][WTK_REPLAY_SUMMARY_DOUBLES].  No floating-point atomics: a (track,
+ *     experiment) pair gives the same bits for any E, any T and any place in the set.  scratch_dev: wtk_replay_set_scratch_doubles(
+ *     tracks_host, T, cycle_frame_num, E) doubles (-1: a bad table).
+ * wtk_replay_set_objective   scan, rows, and in the finish launch objective_dev[e] = one float64 division of the POOLED slots (the ids of
+ *     wtk_replay_objective: sums over all tracks / counts over all tracks, the mean over the rows of all logs); track_objective_dev
+ *     [T][E] (nullable): the same division of each track's slots.  0 / 0 is NaN.  Three launches whatever T is.  T = 1 gives
+ *     wtk_replay_objective's bits.
+ * stop_dev (nullable): as for wtk_replay_objective.
+ * Refused (error code, nothing launched): T < 1, for track t (named by index) what wtk_replay_scan / wtk_replay_rows refuse of an
+ *     experiment, an entry whose derived fields contradict the others, an init position outside the frame, a slot that overlaps the slot
+ *     and guard before it or ends beyond n_super, guard_cycles < 0, n_super not a multiple of L, (experiment, chunk) blocks >= 2^31,
+ *     T > 65535, the trimmed objective where any track logs fewer than 3 cycles, an unknown objective, scratch too small,
+ *     a required pointer that is null.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct wtk_replay_set_track {
+    int64_t R;          /* logged rows: n_log L */
+    int32_t cyc_off;    /* first cycle of the track in the super-track; its first row is cyc_off L */
+    int32_t n_track;    /* rows of the track itself */
+    int32_t num_frames; /* ExperimentConfig.num_frames of this track */
+    int32_t n_cycles;   /* cycles scanned: n_log <= n_cycles, decision frame of the last one < num_frames */
+    int32_t n_log;      /* (num_frames - 1) / L */
+    int32_t x_max, y_max;   /* frame_w - 1, frame_h - 1: the clamp of this track's platform position */
+    int32_t init_x, init_y; /* ExperimentConfig.init_position, clamped to the frame */
+    int32_t chunk0;     /* first chunk of the track: the sum of ceil(R / 4096) over the tracks before it */
+} wtk_replay_set_track;
+int wtk_replay_set_scan(const wtk_replay_config *cfg, const wtk_replay_set_track *tracks_host, const wtk_replay_set_track *tracks_dev, int32_t T,
+                        int32_t guard_cycles, int32_t kind, int32_t E, const double *track_dev, int32_t n_super, const double *a_dev,
+                        const double *b_dev, const int32_t *valid_dev, const double *share_dev, int32_t *pos_dev, int32_t *move_dev,
+                        const int32_t *stop_dev, void *stream);
+int64_t wtk_replay_set_scratch_doubles(const wtk_replay_set_track *tracks_host, int32_t T, int32_t cycle_frame_num, int32_t E);
+int wtk_replay_set_rows(const wtk_replay_config *cfg, const wtk_replay_set_track *tracks_host, const wtk_replay_set_track *tracks_dev, int32_t T,
+                        int32_t guard_cycles, int32_t E, const double *track_dev, int32_t n_super, const double *share_dev,
+                        const int32_t *pos_dev, const int32_t *move_dev, double *track_summary_dev, double *summary_dev, double *scratch_dev,
+                        int64_t scratch_doubles, const int32_t *stop_dev, void *stream);
+int wtk_replay_set_objective(const wtk_replay_config *cfg, const wtk_replay_set_track *tracks_host, const wtk_replay_set_track *tracks_dev,
+                             int32_t T, int32_t guard_cycles, int32_t kind, int32_t E, const double *track_dev, int32_t n_super,
+                             const double *a_dev, const double *b_dev, const int32_t *valid_dev, const double *share_dev, int32_t *pos_dev,
+                             int32_t *move_dev, double *track_summary_dev, double *summary_dev, double *scratch_dev, int64_t scratch_doubles,
+                             int32_t objective, double *objective_dev, double *track_objective_dev, const int32_t *stop_dev, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * The per-cycle ResMLP targets of a population of E models of one structure in one call: what Replay.mlp computes model by model
  * (wtk_mlp_predict_track, the float32 clip, the first box's corner), in the layout wtk_replay_scan reads for WTK_REPLAY_MLP, bit for bit.
  *   layers ...        the structure (in_dim, out_dim, relu of every layer; batch_norm is not looked at), as for wtk_mlp_folded_floats

@@ -6,7 +6,7 @@ simulate.ipynb loads the file too; here `load_config(path)` gives the controller
   python tools/optimize_polyfit_weights.py EXPERIMENT_FOLDER_OR_BBOXES_CSV [more logs ...] --out polyfit_config.json
          [--fps 60] [--imaging-ms 200 --pred-ms 40 --moving-ms 50] [--offsets -45 -39 ...] [--pred-offset 21] [--degrees 1 2 3]
          [--min-speed 0.1 --max-speed 2] [--seed 0] [--pop-size 100 --max-epoch 300 --max-early-stop 100]
-         [--closed-loop EXP_CONFIG_JSON [--camera-mm 4 4] [--micro-mm 0.32 0.32] [--precise FRAMES_NPY BACKGROUND_NPY]]
+         [--closed-loop EXP_CONFIG_JSON [one per log ...] [--camera-mm 4 4] [--micro-mm 0.32 0.32] [--precise FRAMES_NPY BACKGROUND_NPY]]
 
 A folder stands for its bboxes.csv, and its exp_config.json supplies frames_per_sec when --fps is not given.  Defaults are the notebook's: with L the
 cycle length in frames, offsets (-3L, -3L+6, -2L, -2L+6, -L, -L+6, 0, 3), target offset L + imaging_frames // 2, speed window 0.1 .. 2 px / frame.
@@ -14,12 +14,14 @@ With several --degrees every degree is searched (the notebook's "assess each deg
 config goes to <out stem>_deg<d>.json and the best one to --out.  Needs a GPU (there is no CPU fallback).
 
 --closed-loop EXP_CONFIG_JSON (the reference's exp_config.json: num_frames, frames_per_sec, orig_resolution, px_per_mm, init_position) adds a second
-search per degree whose objective is the tracking error of the closed loop itself (Replay.optimize_polyfit on the FIRST log: the trimmed mean bbox
-error of the replayed experiment), started from the open-loop winner, so its result is never worse than that winner in the loop.  The result line then
+search per degree whose objective is the tracking error of the closed loop itself (Replay.optimize_polyfit: the trimmed mean bbox error of the replayed
+experiment), started from the open-loop winner, so its result is never worse than that winner in the loop.  With several logs the experiments are
+replayed together and the error is pooled over the rows of all of them (ReplaySet.optimize_polyfit); give one EXP_CONFIG_JSON for all logs or one per log.  The result line then
 also holds `closed_loop_error_of_open_loop_weights`, `closed_loop_error` and `closed_loop_weights`, and the closed-loop config of the best degree goes to
 <out stem>_closed_loop.json.  The closed-loop error is piecewise constant in the weights (moves are whole pixels).  Without the option nothing changes.
 With --precise FRAMES_NPY BACKGROUND_NPY (the experiment's gray frames, uint8 [F, H, W] with F >= the logged rows, and its background [H, W]) the
-closed-loop objective is the trimmed mean PRECISE error instead (Replay.attach_frames; the frames are held on the device and give the frame shape)."""
+closed-loop objective is the trimmed mean PRECISE error instead (Replay.attach_frames; the frames are held on the device and give the frame shape);
+it takes one log."""
 import argparse
 import json
 import os
@@ -59,7 +61,7 @@ def main(argv=None):
     ap.add_argument("--max-epoch", type=int, default=300)
     ap.add_argument("--max-early-stop", type=int, default=100)
     ap.add_argument("--device", type=int, default=0)
-    ap.add_argument("--closed-loop", default=None, metavar="EXP_CONFIG_JSON")
+    ap.add_argument("--closed-loop", default=None, nargs="+", metavar="EXP_CONFIG_JSON")
     ap.add_argument("--camera-mm", type=float, nargs=2, default=[4.0, 4.0])
     ap.add_argument("--micro-mm", type=float, nargs=2, default=[0.32, 0.32])
     ap.add_argument("--precise", nargs=2, default=None, metavar=("FRAMES_NPY", "BACKGROUND_NPY"))
@@ -91,17 +93,25 @@ def main(argv=None):
     if args.precise is not None and args.closed_loop is None:
         ap.error("--precise goes with --closed-loop")
     if args.closed_loop is not None:
-        from wtracker_amd.replay import Replay
+        from wtracker_amd.replay import Replay, ReplaySet
 
-        exp = ExperimentConfig.from_dict(json.load(open(args.closed_loop)))
+        if len(args.closed_loop) not in (1, len(paths)):
+            ap.error(f"--closed-loop takes one exp_config.json for all logs or one per log ({len(paths)})")
+        if args.precise is not None and len(paths) > 1:
+            ap.error("--precise takes one log (the frames belong to one experiment)")
+        exps = [ExperimentConfig.from_dict(json.load(open(c))) for c in args.closed_loop]
+        exp = exps[0]
+        loop_tc = TimingConfig(exp, args.imaging_ms, args.pred_ms, args.moving_ms, tuple(args.camera_mm), tuple(args.micro_mm))
         frames = None
         if args.precise is not None:
             import numpy as np
             import torch
 
             frames, objective = torch.from_numpy(np.load(args.precise[0])).to(f"cuda:{args.device}"), "trimmed_precise_error"
-        rp = Replay(paths[0], TimingConfig(exp, args.imaging_ms, args.pred_ms, args.moving_ms, tuple(args.camera_mm), tuple(args.micro_mm)), exp,
-                    frame_shape=None if frames is None else frames.shape[1:3], device=args.device)
+        if len(paths) > 1:
+            rp = ReplaySet(paths, loop_tc, exp if len(exps) == 1 else exps, device=args.device)
+        else:
+            rp = Replay(paths[0], loop_tc, exp, frame_shape=None if frames is None else frames.shape[1:3], device=args.device)
         if frames is not None:
             rp.attach_frames(frames, np.load(args.precise[1]))
     for deg in args.degrees:

@@ -16,6 +16,7 @@
 // Everything relies on -ffp-contract=off (the library's build flag): share * move + carry is a rounded product and a rounded sum, as in Python.
 //
 // The rest of the closed loop, each over replay_device.h (the population's view, the motor, the row, the chunk reduction):
+//   replay_set.hip       the same scan and rows reduction of a population on a SET of tracks in one call, with a pooled objective
 //   replay_targets.hip   the per-cycle Polyfit targets of a whole population of weight vectors, in the layout the scan reads
 //   replay_yolo.hip      the YOLO controller's loop, whose targets depend on the camera view: the control kernels between the detector's calls
 //   replay_precise.hip   the precise error (segmented pixels outside the microscope view) of every (experiment, logged frame) pair, and its objective
@@ -50,50 +51,11 @@ struct ObjectiveArgs {
     const int *stop;
 };
 
-constexpr ObjectiveRule kObjectives[] = {
-    {WTK_REPLAY_OBJ_TRIMMED_BBOX, kRowsTrimmedErr, kRowsTrimmedCount, true},
-    {WTK_REPLAY_OBJ_MEAN_BBOX, kRowsErr, kRowsCount, false},
-    {WTK_REPLAY_OBJ_MEAN_MSE, kRowsMse, kRowsCount, false},
-    {WTK_REPLAY_OBJ_NON_PERFECT, kRowsNonPerfect, kRowsCount, false},
-};
-
 __global__ __launch_bounds__(kScanThreads) void replay_scan_kernel(const ScanArgs a) {
     if (a.stop && *a.stop) return;
     const int e = blockIdx.x * kScanThreads + threadIdx.x;
     if (e >= a.E) return;
-    const Geometry g = a.g;
-    int px = a.init_x < 0 ? 0 : (a.init_x > g.x_max ? g.x_max : a.init_x), py = a.init_y < 0 ? 0 : (a.init_y > g.y_max ? g.y_max : a.init_y);
-    const double half_w = (double)g.cam_w / 2, half_h = (double)g.cam_h / 2;
-    for (int c = 0; c < a.C; ++c) {
-        const long long ce = (long long)c * a.E + e;
-        a.pos[2 * ce] = px, a.pos[2 * ce + 1] = py;
-        const double cam_x = (double)(px - g.cam_w / 2), cam_y = (double)(py - g.cam_h / 2);
-        double mx = 0.0, my = 0.0;
-        if (a.kind == WTK_REPLAY_CSV) {
-            const long long f = (long long)c * g.L + g.I - g.P; // the frame the controller saw P frames before the decision
-            if (f >= 0 && f < a.n_track) {
-                const double x = a.track[4 * f], y = a.track[4 * f + 1], w = a.track[4 * f + 2], h = a.track[4 * f + 3];
-                if (isfinite(x) && isfinite(y) && isfinite(w) && isfinite(h)) {
-                    mx = finish_move(((x - cam_x) + w / 2) - half_w);
-                    my = finish_move(((y - cam_y) + h / 2) - half_h);
-                }
-            }
-        } else if (a.valid[ce]) {
-            const double ax = a.a[2 * ce], ay = a.a[2 * ce + 1];
-            if (a.kind == WTK_REPLAY_OPTIMAL) {
-                mx = finish_move(ax - (cam_x + half_w));
-                my = finish_move(ay - (cam_y + half_h));
-            } else if (a.kind == WTK_REPLAY_POLYFIT) {
-                mx = finish_move((ax - cam_x) - half_w);
-                my = finish_move((ay - cam_y) - half_h);
-            } else {
-                mx = finish_move(ax + (a.b[2 * ce] - (cam_x + half_w)));
-                my = finish_move(ay + (a.b[2 * ce + 1] - (cam_y + half_h)));
-            }
-        }
-        a.move[2 * ce] = (int)mx, a.move[2 * ce + 1] = (int)my;
-        motor_steps(g, a.share, g.M, mx, my, px, py);
-    }
+    scan_experiment(a, e);
 }
 
 __global__ __launch_bounds__(kRowThreads) void replay_rows_kernel(const RowsArgs a) {
@@ -111,10 +73,8 @@ __global__ __launch_bounds__(kRowThreads) void replay_rows_kernel(const RowsArgs
         if (r >= v.R) continue;
         const ReplayRow w = replay_row(v, e, r);
         const RowBoxes &b = w.b;
-        const double err = row_bbox_error(b); // ErrorCalculator.calculate_bbox_error
-        // ErrorCalculator.calculate_mse_error: mean over the two axes of the squared centre distance
-        const double dx = (b.wx + b.ww / 2) - (b.mic_x + b.mic_w / 2), dy = (b.wy + b.wh / 2) - (b.mic_y + b.mic_h / 2);
-        const double mse = (dx * dx + dy * dy) / 2;
+        double err, mse;
+        row_accumulate(v, w, acc, err, mse);
         if (a.bbox_err) a.bbox_err[(long long)e * v.R + r] = err;
         if (a.mse_err) a.mse_err[(long long)e * v.R + r] = mse;
         if (slot >= 0 && a.rows) {
@@ -125,10 +85,6 @@ __global__ __launch_bounds__(kRowThreads) void replay_rows_kernel(const RowsArgs
             o[10] = b.wx, o[11] = b.wy, o[12] = b.ww, o[13] = b.wh;
             o[14] = (double)w.at.c, o[15] = w.at.step < v.g.I ? 0.0 : 1.0; // imaging / moving
         }
-        acc[kRowsErr] += err, acc[kRowsCount] += 1.0;
-        if (row_trimmed(v, w.at)) acc[kRowsTrimmedErr] += err, acc[kRowsTrimmedCount] += 1.0;
-        if (non_perfect(err)) acc[kRowsNonPerfect] += 1.0;
-        acc[kRowsMse] += mse;
     }
     chunk_reduce(red, acc, a.partial + ((long long)e * a.S + s) * kSummary);
 }
@@ -256,7 +212,7 @@ extern "C" int wtk_replay_objective(const wtk_replay_config *cfg, int32_t kind, 
         return 1;
     s.stop = r.stop = stop_dev;
     hipStream_t st = (hipStream_t)stream;
-    return enqueue_objective(who, kObjectives, (int)std::size(kObjectives), objective, summary_dev, kSummary, E, r.v.n_log, objective_dev, stop_dev, st, [&] {
+    return enqueue_objective(who, kRowsObjectives, (int)std::size(kRowsObjectives), objective, summary_dev, kSummary, E, r.v.n_log, objective_dev, stop_dev, st, [&] {
         launch_scan(s, st);
         launch_rows(r, st);
         return 0;

@@ -1,5 +1,5 @@
-// What the closed loop's translation units share (replay.hip, replay_precise.hip, replay_yolo.hip, replay_analysis.hip): the geometry and the view of
-// a scanned population with the ONE host function that fills it, the ONE statement of the motor, "row r of experiment e" (cycle, step, platform position,
+// What the closed loop's translation units share (replay.hip, replay_set.hip, replay_precise.hip, replay_yolo.hip, replay_analysis.hip): the geometry and the view of
+// a scanned population with the ONE host function that fills it, the ONE statement of the motor and of the scan, "row r of experiment e" (cycle, step, platform position,
 // boxes), the bbox error of a log row, the fixed chunking of the per-experiment sums with its tree reduction, the summaries' slots, and the declarations of
 // the host launchers that cross translation units (defined in replay.hip).
 // Everything relies on -ffp-contract=off (the library's build flag): share * move + carry is a rounded product and a rounded sum, as in Python.
@@ -199,6 +199,58 @@ struct ScanArgs {
     const int *stop; // nullable: *stop != 0 -> the launch touches nothing (the objective entry points only)
 };
 
+// The scan of ONE experiment over the C cycles of `a`, from the clamped init position: the move of each cycle from the kind's expression (float64, the
+// reference's operation order), then the motor's M steps.  The ONE statement of the scan: replay_scan_kernel runs it per experiment, the set's scan per
+// (track, experiment) on that track's slice of the arrays.
+__device__ __forceinline__ void scan_experiment(const ScanArgs &a, int e) {
+    const Geometry g = a.g;
+    int px = a.init_x < 0 ? 0 : (a.init_x > g.x_max ? g.x_max : a.init_x), py = a.init_y < 0 ? 0 : (a.init_y > g.y_max ? g.y_max : a.init_y);
+    const double half_w = (double)g.cam_w / 2, half_h = (double)g.cam_h / 2;
+    for (int c = 0; c < a.C; ++c) {
+        const long long ce = (long long)c * a.E + e;
+        a.pos[2 * ce] = px, a.pos[2 * ce + 1] = py;
+        const double cam_x = (double)(px - g.cam_w / 2), cam_y = (double)(py - g.cam_h / 2);
+        double mx = 0.0, my = 0.0;
+        if (a.kind == WTK_REPLAY_CSV) {
+            const long long f = (long long)c * g.L + g.I - g.P; // the frame the controller saw P frames before the decision
+            if (f >= 0 && f < a.n_track) {
+                const double x = a.track[4 * f], y = a.track[4 * f + 1], w = a.track[4 * f + 2], h = a.track[4 * f + 3];
+                if (isfinite(x) && isfinite(y) && isfinite(w) && isfinite(h)) {
+                    mx = finish_move(((x - cam_x) + w / 2) - half_w);
+                    my = finish_move(((y - cam_y) + h / 2) - half_h);
+                }
+            }
+        } else if (a.valid[ce]) {
+            const double ax = a.a[2 * ce], ay = a.a[2 * ce + 1];
+            if (a.kind == WTK_REPLAY_OPTIMAL) {
+                mx = finish_move(ax - (cam_x + half_w));
+                my = finish_move(ay - (cam_y + half_h));
+            } else if (a.kind == WTK_REPLAY_POLYFIT) {
+                mx = finish_move((ax - cam_x) - half_w);
+                my = finish_move((ay - cam_y) - half_h);
+            } else {
+                mx = finish_move(ax + (a.b[2 * ce] - (cam_x + half_w)));
+                my = finish_move(ay + (a.b[2 * ce + 1] - (cam_y + half_h)));
+            }
+        }
+        a.move[2 * ce] = (int)mx, a.move[2 * ce + 1] = (int)my;
+        motor_steps(g, a.share, g.M, mx, my, px, py);
+    }
+}
+
+// What a reducing kernel adds of one logged row into its kSummary lane sums, and the row's two errors: the ONE statement of the summary's slots.
+__device__ __forceinline__ void row_accumulate(const ReplayView &v, const ReplayRow &w, double (&acc)[kSummary], double &err, double &mse) {
+    const RowBoxes &b = w.b;
+    err = row_bbox_error(b); // ErrorCalculator.calculate_bbox_error
+    // ErrorCalculator.calculate_mse_error: mean over the two axes of the squared centre distance
+    const double dx = (b.wx + b.ww / 2) - (b.mic_x + b.mic_w / 2), dy = (b.wy + b.wh / 2) - (b.mic_y + b.mic_h / 2);
+    mse = (dx * dx + dy * dy) / 2;
+    acc[kRowsErr] += err, acc[kRowsCount] += 1.0;
+    if (row_trimmed(v, w.at)) acc[kRowsTrimmedErr] += err, acc[kRowsTrimmedCount] += 1.0;
+    if (non_perfect(err)) acc[kRowsNonPerfect] += 1.0;
+    acc[kRowsMse] += mse;
+}
+
 // checks and argument struct of the scan, apart from its launch: the objective entry points refuse before anything is enqueued
 int prepare_scan(const char *who, const wtk_replay_config *cfg, int32_t kind, int32_t E, int32_t n_cycles, const double *track_dev, int32_t n_track,
                  const double *a_dev, const double *b_dev, const int32_t *valid_dev, const double *share_dev, int32_t *pos_dev, int32_t *move_dev, ScanArgs &s);
@@ -210,6 +262,14 @@ void launch_finish(const double *partial, double *summary, int E, int S, int n, 
 struct ObjectiveRule {
     int id, num, den;    // objective = summary[num] / summary[den]
     bool needs_3_cycles; // the trimmed rows: the first and the last logged cycle are dropped
+};
+
+// the objectives over wtk_replay_rows' summary (WTK_REPLAY_OBJ_*): one track's (replay.hip) and a set's pooled slots (replay_set.hip)
+inline constexpr ObjectiveRule kRowsObjectives[] = {
+    {WTK_REPLAY_OBJ_TRIMMED_BBOX, kRowsTrimmedErr, kRowsTrimmedCount, true},
+    {WTK_REPLAY_OBJ_MEAN_BBOX, kRowsErr, kRowsCount, false},
+    {WTK_REPLAY_OBJ_MEAN_MSE, kRowsMse, kRowsCount, false},
+    {WTK_REPLAY_OBJ_NON_PERFECT, kRowsNonPerfect, kRowsCount, false},
 };
 
 // The tail of an objective entry point.  Refuses (null objective_dev, an id outside `rules`, a trimmed objective with fewer than 3 logged cycles) before

@@ -1,0 +1,251 @@
+// A population replayed on a SET of T tracks of different lengths in one call, with an objective pooled over the tracks.
+//
+// The tracks lie in one guarded "super-track" (include/wtk_hip.h states the layout): track t starts at cycle cyc_off of it, and every per-cycle array
+// ([n_super / L][E]...) holds the track's cycles as one contiguous slice.  So a (track, experiment) pair is replay.hip's experiment on a VIEW: the
+// super-track and the scan's arrays from the track's offset on, the track's own clamp, counts and init position.  Both kernels build that view and run
+// replay_device.h's statements on it (scan_experiment; replay_row, row_accumulate, chunk_reduce), which is why a pair has wtk_replay_scan's and
+// wtk_replay_rows' bits for any E, any T and any place in the set.
+//   scan    one lane per (track, experiment), a block's lanes on one track, sequential over the track's cycles
+//   rows    one block per (experiment, global chunk): the chunks of all tracks are numbered through (chunk0 = prefix sum of chunk_count(R_t)); the block
+//           finds its track by a search in that table and reduces the chunk's rows as replay_rows_kernel does
+//   finish  per (experiment, slot): each track's chunk partials in index order -> track_summary[t][e]; those in track order from 0.0 -> summary[e]; the
+//           one float64 division of the pooled slots (and, where asked for, of each track's)
+// Three launches whatever T is.  No floating-point atomics.  Every launch reads the nullable stop flag and touches nothing once it is up.
+#include "wtk_internal.h"
+#include "replay_device.h"
+
+#include <algorithm>
+
+using namespace wtk;
+
+namespace {
+
+constexpr int kScanThreads = 64;
+constexpr int kFinishExperiments = 8; // per block of the finish launch: 8 experiments x 8 lanes, of which kSummary add
+
+struct SetArgs {
+    Geometry g; // x_max / y_max are each track's own
+    const wtk_replay_set_track *tracks; // [T] on the device
+    int T, E, kind;
+    int S; // chunks of all tracks
+    const double *track; // the super-track
+    const double *a, *b;
+    const int *valid;
+    const double *share;
+    int *pos, *move;        // [n_super / L][E][2]
+    double *partial;        // [E][S][kSummary]
+    double *track_summary;  // [T][E][kSummary]
+    double *summary;        // [E][kSummary]
+    double *objective;      // [E] (nullable)
+    double *track_objective; // [T][E] (nullable)
+    int num, den;           // objective = slot num / slot den
+    const int *stop;
+};
+
+__device__ __forceinline__ Geometry track_geometry(const SetArgs &a, const wtk_replay_set_track &tr) {
+    Geometry g = a.g;
+    g.x_max = tr.x_max, g.y_max = tr.y_max;
+    return g;
+}
+
+__global__ __launch_bounds__(kScanThreads) void replay_set_scan_kernel(const SetArgs a) {
+    if (a.stop && *a.stop) return;
+    const int t = blockIdx.y, e = blockIdx.x * kScanThreads + threadIdx.x; // the track is block-uniform: its view stays in scalar registers, as replay_scan_kernel's
+    if (e >= a.E) return;
+    const wtk_replay_set_track tr = a.tracks[t];
+    const long long c0 = (long long)tr.cyc_off * a.E; // the track's slice of the cycle-major arrays
+    ScanArgs s;
+    s.g = track_geometry(a, tr), s.kind = a.kind, s.E = a.E, s.C = tr.n_cycles, s.init_x = tr.init_x, s.init_y = tr.init_y;
+    s.track = a.track + 4 * (long long)tr.cyc_off * a.g.L, s.n_track = tr.n_track;
+    s.a = a.a ? a.a + 2 * c0 : nullptr, s.b = a.b ? a.b + 2 * c0 : nullptr, s.valid = a.valid ? a.valid + c0 : nullptr;
+    s.share = a.share, s.pos = a.pos + 2 * c0, s.move = a.move + 2 * c0, s.stop = nullptr;
+    scan_experiment(s, e);
+}
+
+__global__ __launch_bounds__(kRowThreads) void replay_set_rows_kernel(const SetArgs a) {
+    __shared__ double red[kSummary][kRowThreads];
+    if (a.stop && *a.stop) return; // block-uniform
+    const int e = blockIdx.x / a.S, gs = blockIdx.x - e * a.S;
+    int lo = 0, hi = a.T - 1; // the last track whose first chunk is <= gs (a track without rows has no chunk and is never found)
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (a.tracks[mid].chunk0 <= gs) lo = mid;
+        else hi = mid - 1;
+    }
+    const wtk_replay_set_track tr = a.tracks[lo];
+    const long long c0 = (long long)tr.cyc_off * a.E;
+    ReplayView v;
+    v.g = track_geometry(a, tr), v.E = a.E, v.C = tr.n_cycles, v.n_log = tr.n_log, v.R = tr.R;
+    v.track = a.track + 4 * (long long)tr.cyc_off * a.g.L, v.share = a.share, v.pos = a.pos + 2 * c0, v.move = a.move + 2 * c0;
+    double acc[kSummary];
+    for (int q = 0; q < kSummary; ++q) acc[q] = 0.0;
+    const long long r0 = (long long)(gs - tr.chunk0) * kRowChunk;
+    for (int i = 0; i < kRowChunk / kRowThreads; ++i) {
+        const long long r = r0 + (long long)i * kRowThreads + threadIdx.x;
+        if (r >= v.R) continue;
+        double err, mse;
+        row_accumulate(v, replay_row(v, e, r), acc, err, mse);
+    }
+    chunk_reduce(red, acc, a.partial + ((long long)e * a.S + gs) * kSummary);
+}
+
+__global__ __launch_bounds__(kFinishExperiments * 8) void replay_set_finish_kernel(const SetArgs a) {
+    __shared__ double of_track[kFinishExperiments][8];
+    if (a.stop && *a.stop) return; // block-uniform
+    const int el = threadIdx.x >> 3, q = threadIdx.x & 7;
+    const int e = blockIdx.x * kFinishExperiments + el;
+    const bool adds = e < a.E && q < kSummary;
+    double pooled = 0.0;
+    for (int t = 0; t < a.T; ++t) { // (T is block-uniform: so are the barriers)
+        double sum = 0.0;
+        if (adds) {
+            const int s0 = a.tracks[t].chunk0, s1 = t + 1 < a.T ? a.tracks[t + 1].chunk0 : a.S;
+            for (int s = s0; s < s1; ++s) sum += a.partial[((long long)e * a.S + s) * kSummary + q];
+            a.track_summary[((long long)t * a.E + e) * kSummary + q] = sum;
+            pooled += sum;
+        }
+        if (a.track_objective) {
+            of_track[el][q] = sum;
+            __syncthreads();
+            if (q == 0 && e < a.E) a.track_objective[(long long)t * a.E + e] = of_track[el][a.num] / of_track[el][a.den];
+            __syncthreads();
+        }
+    }
+    if (adds) a.summary[(long long)e * kSummary + q] = pooled;
+    if (a.objective) {
+        of_track[el][q] = pooled;
+        __syncthreads();
+        // the float64 division Summary's properties perform on the host (counts are exact doubles); 0 / 0 = NaN, which the swarm never lets win
+        if (q == 0 && e < a.E) a.objective[e] = of_track[el][a.num] / of_track[el][a.den];
+    }
+}
+
+// The checks of the table every entry point shares: each track as replay_view sees it (reported with its index), the derived fields, the slots and
+// guards.  Leaves the shared geometry in a.g, the chunk count in a.S and the smallest n_log in min_log.
+int set_view(const char *who, const wtk_replay_config *cfg, const wtk_replay_set_track *host, const wtk_replay_set_track *dev, int32_t T, int32_t guard_cycles,
+             int32_t kind, int32_t E, const double *track_dev, int32_t n_super, const double *share_dev, const int32_t *pos_dev, const int32_t *move_dev, SetArgs &a,
+             int &min_log) {
+    const std::string w(who);
+    if (!cfg || !host || !dev) return fail(w + ": null argument");
+    if (T < 1) return fail(w + ": at least one track (T >= 1)");
+    if (guard_cycles < 0) return fail(w + ": negative guard_cycles");
+    long long chunks = 0, end_before = 0; // end_before: the first cycle behind the slot and guard of the track before
+    min_log = INT32_MAX;
+    for (int t = 0; t < T; ++t) {
+        const wtk_replay_set_track &tr = host[t];
+        const std::string wt = w + ": track " + std::to_string(t);
+        wtk_replay_config c = *cfg;
+        c.num_frames = tr.num_frames, c.frame_w = tr.x_max < INT32_MAX ? tr.x_max + 1 : 0, c.frame_h = tr.y_max < INT32_MAX ? tr.y_max + 1 : 0;
+        c.init_x = tr.init_x, c.init_y = tr.init_y;
+        ReplayView v = {};
+        if (replay_view(wt.c_str(), &c, kind, E, tr.n_cycles, track_dev, tr.n_track, share_dev, pos_dev, move_dev, v)) return 1;
+        if (tr.n_log != v.n_log || tr.R != v.R) return fail(wt + ": n_log and R must be (num_frames - 1) / L and n_log L");
+        if (tr.init_x < 0 || tr.init_x > tr.x_max || tr.init_y < 0 || tr.init_y > tr.y_max) return fail(wt + ": the init position must be clamped to the frame");
+        if (tr.chunk0 != chunks) return fail(wt + ": chunk0 must be the sum of the chunk counts of the tracks before it");
+        if (tr.cyc_off < end_before) return fail(wt + ": its slot overlaps the slot or the guard of the track before it (or cyc_off is negative)");
+        const long long L = v.g.L, slot = std::max<long long>(tr.n_cycles, (tr.n_track + L - 1) / L);
+        end_before = tr.cyc_off + slot + guard_cycles;
+        if (n_super < 0 || n_super % L != 0 || end_before * L > n_super) return fail(wt + ": its slot and guard end beyond the super-track (n_super must be a multiple of L)");
+        chunks += chunk_count(v.R);
+        min_log = std::min(min_log, v.n_log);
+        a.g = v.g;
+    }
+    if (chunks * E > INT32_MAX) return fail(w + ": too many (experiment, chunk) blocks for one launch");
+    if (T > 65535) return fail(w + ": at most 65535 tracks (the scan's grid)");
+    a.tracks = dev, a.T = T, a.E = E, a.kind = kind, a.S = (int)chunks, a.track = track_dev, a.share = share_dev;
+    a.pos = const_cast<int *>(pos_dev), a.move = const_cast<int *>(move_dev);
+    return 0;
+}
+
+int set_targets(const char *who, int32_t kind, const double *a_dev, const double *b_dev, const int32_t *valid_dev, SetArgs &a) {
+    const std::string w(who);
+    if (kind != WTK_REPLAY_CSV && (!a_dev || !valid_dev)) return fail(w + ": null targets");
+    if (kind == WTK_REPLAY_MLP && !b_dev) return fail(w + ": null origins (b_dev) for the MLP kind");
+    a.a = a_dev, a.b = b_dev, a.valid = valid_dev;
+    return 0;
+}
+
+int set_sums(const char *who, const wtk_replay_set_track *host, int32_t T, double *track_summary_dev, double *summary_dev, double *scratch_dev, int64_t scratch_doubles,
+             SetArgs &a) {
+    const std::string w(who);
+    if (!track_summary_dev || !summary_dev || !scratch_dev) return fail(w + ": null argument");
+    if (scratch_doubles < wtk_replay_set_scratch_doubles(host, T, a.g.L, a.E)) return fail(w + ": scratch smaller than wtk_replay_set_scratch_doubles(tracks_host, T, L, E)");
+    a.track_summary = track_summary_dev, a.summary = summary_dev, a.partial = scratch_dev;
+    return 0;
+}
+
+void launch_set_scan(const SetArgs &a, hipStream_t st) {
+    hipLaunchKernelGGL(replay_set_scan_kernel, dim3((unsigned)((a.E + kScanThreads - 1) / kScanThreads), (unsigned)a.T), dim3(kScanThreads), 0, st, a);
+}
+
+void launch_set_rows(const SetArgs &a, hipStream_t st) {
+    if (a.S > 0) hipLaunchKernelGGL(replay_set_rows_kernel, dim3((unsigned)((long long)a.S * a.E)), dim3(kRowThreads), 0, st, a);
+    hipLaunchKernelGGL(replay_set_finish_kernel, dim3((unsigned)((a.E + kFinishExperiments - 1) / kFinishExperiments)), dim3(kFinishExperiments * 8), 0, st, a);
+}
+
+} // namespace
+
+extern "C" int wtk_replay_set_scan(const wtk_replay_config *cfg, const wtk_replay_set_track *tracks_host, const wtk_replay_set_track *tracks_dev, int32_t T,
+                                   int32_t guard_cycles, int32_t kind, int32_t E, const double *track_dev, int32_t n_super, const double *a_dev,
+                                   const double *b_dev, const int32_t *valid_dev, const double *share_dev, int32_t *pos_dev, int32_t *move_dev,
+                                   const int32_t *stop_dev, void *stream) {
+    const char *who = "wtk_replay_set_scan";
+    SetArgs a = {};
+    int min_log = 0;
+    if (set_view(who, cfg, tracks_host, tracks_dev, T, guard_cycles, kind, E, track_dev, n_super, share_dev, pos_dev, move_dev, a, min_log)) return 1;
+    if (set_targets(who, kind, a_dev, b_dev, valid_dev, a)) return 1;
+    a.stop = stop_dev;
+    launch_set_scan(a, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int64_t wtk_replay_set_scratch_doubles(const wtk_replay_set_track *tracks_host, int32_t T, int32_t cycle_frame_num, int32_t E) {
+    if (!tracks_host || T < 1 || cycle_frame_num < 1 || E < 0) return -1;
+    int64_t chunks = 0;
+    for (int t = 0; t < T; ++t) {
+        if (tracks_host[t].n_log < 0) return -1;
+        chunks += chunk_count((long long)tracks_host[t].n_log * cycle_frame_num);
+    }
+    return (int64_t)E * chunks * kSummary;
+}
+
+extern "C" int wtk_replay_set_rows(const wtk_replay_config *cfg, const wtk_replay_set_track *tracks_host, const wtk_replay_set_track *tracks_dev, int32_t T,
+                                   int32_t guard_cycles, int32_t E, const double *track_dev, int32_t n_super, const double *share_dev,
+                                   const int32_t *pos_dev, const int32_t *move_dev, double *track_summary_dev, double *summary_dev, double *scratch_dev,
+                                   int64_t scratch_doubles, const int32_t *stop_dev, void *stream) {
+    const char *who = "wtk_replay_set_rows";
+    SetArgs a = {};
+    int min_log = 0;
+    if (set_view(who, cfg, tracks_host, tracks_dev, T, guard_cycles, WTK_REPLAY_OPTIMAL, E, track_dev, n_super, share_dev, pos_dev, move_dev, a, min_log)) return 1;
+    if (set_sums(who, tracks_host, T, track_summary_dev, summary_dev, scratch_dev, scratch_doubles, a)) return 1;
+    a.stop = stop_dev;
+    launch_set_rows(a, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int wtk_replay_set_objective(const wtk_replay_config *cfg, const wtk_replay_set_track *tracks_host, const wtk_replay_set_track *tracks_dev,
+                                        int32_t T, int32_t guard_cycles, int32_t kind, int32_t E, const double *track_dev, int32_t n_super,
+                                        const double *a_dev, const double *b_dev, const int32_t *valid_dev, const double *share_dev, int32_t *pos_dev,
+                                        int32_t *move_dev, double *track_summary_dev, double *summary_dev, double *scratch_dev, int64_t scratch_doubles,
+                                        int32_t objective, double *objective_dev, double *track_objective_dev, const int32_t *stop_dev, void *stream) {
+    const char *who = "wtk_replay_set_objective";
+    const std::string w(who);
+    SetArgs a = {};
+    int min_log = 0;
+    if (set_view(who, cfg, tracks_host, tracks_dev, T, guard_cycles, kind, E, track_dev, n_super, share_dev, pos_dev, move_dev, a, min_log)) return 1;
+    if (set_targets(who, kind, a_dev, b_dev, valid_dev, a)) return 1;
+    if (set_sums(who, tracks_host, T, track_summary_dev, summary_dev, scratch_dev, scratch_doubles, a)) return 1;
+    if (!objective_dev) return fail(w + ": null argument");
+    const ObjectiveRule *rule = std::find_if(std::begin(kRowsObjectives), std::end(kRowsObjectives), [&](const ObjectiveRule &r) { return r.id == objective; });
+    if (rule == std::end(kRowsObjectives)) return fail(w + ": unknown objective");
+    if (rule->needs_3_cycles && min_log < 3)
+        return fail(w + ": the trimmed objective needs at least 3 logged cycles of every track (the first and the last of each are dropped)");
+    a.objective = objective_dev, a.track_objective = track_objective_dev, a.num = rule->num, a.den = rule->den, a.stop = stop_dev;
+    hipStream_t st = (hipStream_t)stream;
+    launch_set_scan(a, st);
+    launch_set_rows(a, st);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}

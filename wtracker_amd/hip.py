@@ -54,6 +54,11 @@ class _ReplayConfig(C.Structure):
                                          "frame_w", "frame_h", "init_x", "init_y")]
 
 
+class _ReplaySetTrack(C.Structure):
+    _fields_ = [("R", C.c_int64)] + [(n, C.c_int32) for n in ("cyc_off", "n_track", "num_frames", "n_cycles", "n_log", "x_max", "y_max", "init_x", "init_y",
+                                                              "chunk0")]
+
+
 class _AnalysisConfig(C.Structure):
     _fields_ = ([("bounds", C.c_double * 4)] + [(n, C.c_double) for n in ("time_factor", "dist_factor", "speed_factor", "min_speed", "min_bbox_error",
                                                                           "min_dist_error", "min_width", "min_height")]
@@ -69,6 +74,7 @@ class _YoloDesc(C.Structure):
 _vp, _i32, _i64, _f32, _f64, _size = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_size_t
 _pvp, _pi32, _pi64, _pf32, _pf64, _pcfg = C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_f32), C.POINTER(_f64), C.POINTER(_ReplayConfig)
 _pacfg = C.POINTER(_AnalysisConfig)
+_ptrk = C.POINTER(_ReplaySetTrack)
 
 # The C ABI, one row per symbol of include/wtk_hip.h and in its order: name -> (restype, argtypes).  load() applies it and nothing else declares a
 # signature; tests/test_abi.py compares every row with the header's prototype, kind by kind (pointer, int32, int64, size_t, float, double).
@@ -154,6 +160,11 @@ SIGNATURES = {
     "wtk_replay_polyfit_targets_scratch_doubles": (_i64, [_i32, _i32, _i32, _i32]),
     "wtk_replay_polyfit_targets": (_i32, [_vp, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _f64, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp]),
     "wtk_replay_objective": (_i32, [_pcfg, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "wtk_replay_set_scan": (_i32, [_pcfg, _ptrk, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "wtk_replay_set_scratch_doubles": (_i64, [_ptrk, _i32, _i32, _i32]),
+    "wtk_replay_set_rows": (_i32, [_pcfg, _ptrk, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "wtk_replay_set_objective": (_i32, [_pcfg, _ptrk, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp,
+                                        _vp, _vp]),
     "wtk_replay_mlp_targets": (_i32, [C.POINTER(_MlpTrainLayer), _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _f32, _vp, _vp, _vp, _vp, _vp]),
     "wtk_replay_mlp_targets_waves": (_i32, [_i64]),
     "wtk_replay_yolo_step": (_i32, [_pcfg, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
@@ -519,6 +530,67 @@ def replay_objective(cfg: _ReplayConfig, kind: int, E: int, n_cycles: int, track
     _check(load().wtk_replay_objective(C.byref(cfg) if cfg is not None else None, kind, E, n_cycles, _ptr(track_dev), n_track, _ptr(a_dev), _ptr(b_dev),
                                        _ptr(valid_dev), _ptr(share_dev), _ptr(pos_dev), _ptr(move_dev), _ptr(summary_dev), _ptr(scratch_dev), scratch_doubles,
                                        objective, _ptr(objective_dev), _ptr(stop_dev), C.c_void_p(stream)), "wtk_replay_objective")
+
+
+ROW_CHUNK = 4096  # kRowChunk (csrc/replay_device.h): logged rows per block of a reducing kernel
+
+
+class ReplaySetTable:
+    """The track table of a set of tracks in one super-track (wtk_replay_set_track [T]): `host` the ctypes array the entry points check, `dev` the
+    same bytes on the device (uploaded here, once).  `tracks`: per track a dict of cyc_off, n_track, num_frames, n_cycles, n_log, frame_wh, init_position
+    (clamped here, as the scan clamps it); R and chunk0 are derived."""
+
+    def __init__(self, tracks: Sequence[dict], cycle_frame_num: int, guard_cycles: int, n_super: int, device=None):
+        self.T, self.L, self.guard_cycles, self.n_super = len(tracks), int(cycle_frame_num), int(guard_cycles), int(n_super)
+        self.host = (_ReplaySetTrack * max(1, self.T))()
+        chunk0 = 0
+        for t, tr in enumerate(tracks):
+            (W, H), R = tr["frame_wh"], int(tr["n_log"]) * self.L
+            x, y = (int(min(max(int(v), 0), int(m) - 1)) for v, m in zip(tr["init_position"], (W, H)))
+            self.host[t] = _ReplaySetTrack(R, int(tr["cyc_off"]), int(tr["n_track"]), int(tr["num_frames"]), int(tr["n_cycles"]), int(tr["n_log"]), int(W) - 1,
+                                           int(H) - 1, x, y, chunk0)
+            chunk0 += (R + ROW_CHUNK - 1) // ROW_CHUNK
+        self.n_chunks = chunk0
+        self.dev = None
+        if device is not None:
+            import torch
+
+            raw = np.frombuffer(bytes(self.host), dtype=np.uint8).copy()
+            self.dev = torch.from_numpy(raw).to(device)
+
+    def _args(self):
+        return self.host, _ptr(self.dev), self.T, self.guard_cycles
+
+
+def replay_set_scan(cfg: _ReplayConfig, table: ReplaySetTable, kind: int, E: int, track_dev, a_dev, b_dev, valid_dev, share_dev, pos_dev, move_dev, stop_dev=None,
+                    stream: int = 0):
+    """wtk_replay_scan of every (track, experiment) of a set (wtk_replay_set_scan); per-cycle arrays are [n_super / L, E, ...] device tensors."""
+    _check(load().wtk_replay_set_scan(C.byref(cfg) if cfg is not None else None, *table._args(), kind, E, _ptr(track_dev), table.n_super, _ptr(a_dev),
+                                      _ptr(b_dev), _ptr(valid_dev), _ptr(share_dev), _ptr(pos_dev), _ptr(move_dev), _ptr(stop_dev), C.c_void_p(stream)),
+           "wtk_replay_set_scan")
+
+
+def replay_set_scratch_doubles(table: ReplaySetTable, E: int) -> int:
+    return int(load().wtk_replay_set_scratch_doubles(table.host, table.T, table.L, E))
+
+
+def replay_set_rows(cfg: _ReplayConfig, table: ReplaySetTable, E: int, track_dev, share_dev, pos_dev, move_dev, track_summary_dev, summary_dev, scratch_dev,
+                    scratch_doubles: int, stop_dev=None, stream: int = 0):
+    """Per-track summaries [T, E, 6] and the pooled summary [E, 6] from a set scan's positions and moves (wtk_replay_set_rows)."""
+    _check(load().wtk_replay_set_rows(C.byref(cfg) if cfg is not None else None, *table._args(), E, _ptr(track_dev), table.n_super, _ptr(share_dev),
+                                      _ptr(pos_dev), _ptr(move_dev), _ptr(track_summary_dev), _ptr(summary_dev), _ptr(scratch_dev), scratch_doubles,
+                                      _ptr(stop_dev), C.c_void_p(stream)), "wtk_replay_set_rows")
+
+
+def replay_set_objective(cfg: _ReplayConfig, table: ReplaySetTable, kind: int, E: int, track_dev, a_dev, b_dev, valid_dev, share_dev, pos_dev, move_dev,
+                         track_summary_dev, summary_dev, scratch_dev, scratch_doubles: int, objective: int, objective_dev, track_objective_dev=None,
+                         stop_dev=None, stream: int = 0):
+    """objective_dev[e] = the chosen closed-loop error of experiment e pooled over the set's tracks (wtk_replay_set_objective); track_objective_dev
+    [T, E] (optional): the same of each track."""
+    _check(load().wtk_replay_set_objective(C.byref(cfg) if cfg is not None else None, *table._args(), kind, E, _ptr(track_dev), table.n_super, _ptr(a_dev),
+                                           _ptr(b_dev), _ptr(valid_dev), _ptr(share_dev), _ptr(pos_dev), _ptr(move_dev), _ptr(track_summary_dev),
+                                           _ptr(summary_dev), _ptr(scratch_dev), scratch_doubles, objective, _ptr(objective_dev), _ptr(track_objective_dev),
+                                           _ptr(stop_dev), C.c_void_p(stream)), "wtk_replay_set_objective")
 
 
 REPLAY_PRECISE_SUMMARY_DOUBLES = 6

@@ -44,6 +44,13 @@ and per-cycle-step aggregates) of every experiment of a population, on the devic
     res.analysis.cycle_max, res.analysis.step_quantiles, res.analysis.anomaly_counts, res.analysis.stats
     rp.analyze(t, spec)                                                 # the same as device tensors, no synchronisation
 
+Several recordings in one objective: a population replayed on T tracks of different lengths in a number of launches that
+does not depend on T, the error pooled over the rows of all logs; the search and the trainer's closed loop run on the set unchanged:
+
+    rs = ReplaySet([track0, "bboxes1.csv", track2], timing_config, [ec0, ec1, ec2])
+    rs.objective(rs.polyfit_population(weights_dev, 2, times))          # device float64 [P]; per_track=True -> [T, P]
+    rs.optimize_polyfit(2, times, start=[open_loop.weights]); trainer.fit(..., closed_loop=rs); rs.replay(t)   # the plain Replay of track t
+
 There is no CPU fallback: without a visible GPU the constructors raise.  Not covered: `StepMotorController`, DataAnalyzer's `remove_cycle` and
 `save` / `load`, the plots themselves, the YOLO controller's second look (YoloConfig.recheck_margin).
 """
@@ -771,6 +778,223 @@ class Replay:
                 if per_row_errors:
                     res.precise_error, res.precise_counts = perr.cpu().numpy(), pcounts.cpu().numpy()
             return res
+
+
+DEFAULT_REACH = 64  # frames from a cycle's start: beyond the notebook's Polyfit sample times and the shipped ResMLPs' input frames
+
+
+@dataclass
+class ReplaySetResult:
+    """`ReplaySet.run`: `summary` the pooled Summary ([E] arrays: the sums and counts of all tracks' rows), `track_summary[t]` track t's Summary,
+    `moves[t]` / `positions[t]` int32 [E, C_t, 2] of track t."""
+
+    summary: Summary
+    track_summary: list
+    moves: list
+    positions: list
+
+
+class _SuperTrack(Replay):
+    """The super-track of a ReplaySet as a Replay: every targets builder and the swarm of `optimize_polyfit` run on it unchanged, over all cycles of all
+    tracks at once; the objective behind them is the set's (wtk_replay_set_objective).  Private to ReplaySet: it has no loop of its own."""
+
+    def __init__(self, owner: "ReplaySet", track, timing_config, experiment_config, device: int):
+        super().__init__(track, timing_config, experiment_config, None, device)
+        self._set = owner
+
+    def _objective_kind(self, kind: str) -> int:
+        return self._set._objective_kind(kind)
+
+    def _all_objective_buffers(self, E: int, precise: bool) -> dict:
+        return self._set._objective_buffers(E)
+
+    def _enqueue_objective(self, targets: Targets, kind: int, buf: dict, out, stop_dev=None):
+        self._set._enqueue_objective(targets, kind, buf, out, stop_dev=stop_dev)
+
+
+class ReplaySet:
+    """The closed loop of a population of controller configurations on SEVERAL tracks at once, with an objective pooled over them (DESIGN.md section
+    26): what one `Replay` per track and a host loop around them compute, in a number of launches that does not depend on the number of tracks.
+
+        rs = ReplaySet([track0_dev, "bboxes1.csv", track2], timing_config, experiment_configs)
+        tg = rs.polyfit_population(weights_dev, 1, offsets)     # also csv(), optimal(), polyfit(cfgs), mlp(model), mlp_population(...)
+        rs.objective(tg, "trimmed_bbox_error")                  # device float64 [E], pooled; per_track=True -> [T, E]
+        res = rs.run(tg)                                        # res.summary (pooled), res.track_summary[t], res.moves[t], res.positions[t]
+        rs.optimize_polyfit(1, offsets, start=[...], seed=0)    # Replay.optimize_polyfit's search over the pooled objective
+        trainer.fit(..., closed_loop=rs)
+
+    `tracks`: what `Replay` takes, one per track.  All tracks share `timing_config`; `experiment_configs` is one ExperimentConfig or one per track
+    (num_frames, init_position and the default frame shape are each track's own), `frame_shapes` None or one (H, W) / None per track.  On the device
+    the tracks lie in one float64 [N, 4] "super-track": track t from row cyc_off[t] L, NaN rows up to the end of its whole-cycle slot, then
+    ceil(reach / L) all-NaN guard cycles.  The targets entry points treat a NaN row as a row outside the track, so one call over the super-track gives
+    every cycle of every track the bits of the per-track call; `reach` (frames, default max(DEFAULT_REACH, L + I)) bounds how far from a cycle's start
+    a sample time or an input frame may lie, and a call that reaches further is refused.  Targets are [n_super_cycles, E, ...]; track t's cycles are the
+    slice from cyc_off[t].
+
+    The pooled objective is sum of the tracks' sums / sum of their counts: the mean over the rows of all logs (the reference's Plotter concatenates
+    them); the trimmed rows drop the first and the last logged cycle of EVERY track.  A (track, experiment) pair has the bits of `Replay` on that track
+    alone.  Logs, Analysis and the precise error stay with `rs.replay(t)`."""
+
+    def __init__(self, tracks, timing_config: TimingConfig, experiment_configs, frame_shapes=None, reach: Optional[int] = None, device: int = 0):
+        if hip.device_count() < 1:
+            raise hip.WtkError("ReplaySet needs a GPU: no HIP device visible (there is no CPU fallback)")
+        import dataclasses
+
+        import torch
+
+        tracks = list(tracks)
+        if not tracks:
+            raise ValueError("at least one track is needed")
+        T = len(tracks)
+        ecs = [experiment_configs] * T if isinstance(experiment_configs, ExperimentConfig) else list(experiment_configs)
+        shapes = [None] * T if frame_shapes is None else list(frame_shapes)
+        if len(ecs) != T or len(shapes) != T:
+            raise ValueError(f"{T} tracks: experiment_configs must be one config or {T}, frame_shapes None or {T}")
+        self.timing_config, self.experiment_configs, self.T = timing_config, ecs, T
+        self._dev = torch.device("cuda", device)
+        self._replays = [Replay(tr, timing_config, ec, fs, device) for tr, ec, fs in zip(tracks, ecs, shapes)]
+        g0 = self._replays[0].geometry
+        self.L, self.I, self.M, self.P = L, I, _, P = g0.L, g0.I, g0.M, g0.P
+        self.n_cycles, self.n_log, self.n_rows = ([getattr(rp, k) for rp in self._replays] for k in ("n_cycles", "n_log", "n_rows"))
+        self.frame_shapes = [rp.frame_shape for rp in self._replays]
+        self.reach = max(DEFAULT_REACH, L + I) if reach is None else int(reach)
+        if self.reach < 1:
+            raise ValueError("reach must be at least 1 frame")
+        self.guard_cycles = guard = -(-self.reach // L)
+        rows, off = [], 0
+        for rp in self._replays:
+            rows.append(dict(cyc_off=off, n_track=rp.n_track, num_frames=int(rp.experiment_config.num_frames), n_cycles=rp.n_cycles, n_log=rp.n_log,
+                             frame_wh=(rp.frame_shape[1], rp.frame_shape[0]), init_position=rp.experiment_config.init_position))
+            off += max(rp.n_cycles, -(-rp.n_track // L)) + guard
+        self.cyc_off, self.n_super_cycles = [r["cyc_off"] for r in rows], off
+        with torch.cuda.device(self._dev):
+            track = torch.full((off * L, 4), float("nan"), dtype=torch.float64, device=self._dev)
+            for rp, o in zip(self._replays, self.cyc_off):
+                track[o * L:o * L + rp.n_track] = rp.track
+            self._table = hip.ReplaySetTable(rows, L, guard, off * L, device=self._dev)
+        # the super-track as a Replay whose scanned cycles are all n_super_cycles: the targets builders and the swarm run on it
+        ec = dataclasses.replace(ecs[0], num_frames=(off - 1) * L + I + 1)
+        self._super = _SuperTrack(self, track, timing_config, ec, device)
+
+    def replay(self, t: int) -> Replay:
+        """The plain `Replay` of track t: logs, Analysis and the precise error stay there."""
+        return self._replays[t]
+
+    # ------------------------------------------------------------------ targets: the super-track's, after the reach is checked
+    def _check_reach(self, what: str, offsets) -> None:
+        far = max(abs(int(o)) for o in offsets)
+        if far > self.reach:
+            raise ValueError(f"{what} lie up to {far} frames from a cycle's start, beyond this ReplaySet's reach = {self.reach} (the guard between two "
+                             "tracks): build the set with a larger reach")
+
+    def csv(self) -> Targets:
+        return Targets("csv", 1)
+
+    def optimal(self) -> Targets:
+        """`Replay.optimal` of every track in one call (the median reads the next imaging phase: within any guard)."""
+        return self._super.optimal()
+
+    def polyfit(self, configs: Sequence[PolyfitConfig]) -> Targets:
+        """`Replay.polyfit(configs)` of every track: one call per config, whatever T is."""
+        configs = list(configs)
+        for cfg in configs:
+            self._check_reach("sample_times", cfg.sample_times)
+        return self._super.polyfit(configs)
+
+    def polyfit_population(self, weights, degree: int, sample_times) -> Targets:
+        """`Replay.polyfit_population` of every track: two launches whatever P and T are."""
+        self._check_reach("sample_times", check_times(sample_times, "sample_times"))
+        return self._super.polyfit_population(weights, degree, sample_times)
+
+    def _check_input_frames(self, input_frames) -> None:
+        self._check_reach("input_frames", [self.I - self.P + int(f) for f in input_frames])
+
+    def mlp(self, model, max_speed: float = 0.9) -> Targets:
+        """`Replay.mlp(model)` of every track in one call."""
+        folded = model if isinstance(model, FoldedResMLP) else from_torch_module(model)
+        self._check_input_frames(folded.input_frames)
+        return self._super.mlp(folded, max_speed)
+
+    def mlp_population(self, models, max_speed: float = 0.9, which="current") -> Targets:
+        """`Replay.mlp_population` of every track: one launch whatever E and T are."""
+        from .training import HipMLPTrainer
+
+        if not isinstance(models, HipMLPTrainer):
+            models = [m if isinstance(m, FoldedResMLP) else from_torch_module(m) for m in models]
+        frames = models.input_frames if isinstance(models, HipMLPTrainer) else (models[0].input_frames if models else None)
+        if frames is not None:
+            self._check_input_frames(frames)
+        return self._super.mlp_population(models, max_speed, which)
+
+    # ------------------------------------------------------------------ objective
+    def _objective_kind(self, kind: str) -> int:
+        if kind in PRECISE_OBJECTIVES:
+            raise ValueError(f"{kind!r} needs the frames of every track: a ReplaySet has none; use rs.replay(t), which takes attach_frames")
+        if kind not in OBJECTIVES:
+            raise ValueError(f"unknown objective {kind!r}: one of {sorted(OBJECTIVES)}")
+        if kind == "trimmed_bbox_error" and min(self.n_log) < 3:
+            t = int(np.argmin(self.n_log))
+            raise ValueError(f"the trimmed objective drops the first and the last logged cycle of every track: track {t} logs {self.n_log[t]}, at least 3 are needed")
+        return OBJECTIVES[kind]
+
+    def _objective_buffers(self, E: int) -> dict:
+        import torch
+
+        dev, C, n = self._dev, self.n_super_cycles, hip.REPLAY_SUMMARY_DOUBLES
+        return dict(pos=torch.empty((C, E, 2), dtype=torch.int32, device=dev), move=torch.empty((C, E, 2), dtype=torch.int32, device=dev),
+                    track_summary=torch.empty((self.T, E, n), dtype=torch.float64, device=dev), summary=torch.empty((E, n), dtype=torch.float64, device=dev),
+                    scratch=torch.empty((max(1, hip.replay_set_scratch_doubles(self._table, E)),), dtype=torch.float64, device=dev))
+
+    def _enqueue_objective(self, targets: Targets, kind: int, buf: dict, out, track_out=None, stop_dev=None):
+        sp = self._super
+        hip.replay_set_objective(sp._cfg, self._table, KINDS[targets.kind], int(targets.E), sp.track, targets.a, targets.b, targets.valid, sp._share, buf["pos"],
+                                 buf["move"], buf["track_summary"], buf["summary"], buf["scratch"], buf["scratch"].numel(), kind, out, track_out, stop_dev,
+                                 stream=sp._stream())
+
+    def _check_targets(self, targets: Targets) -> int:
+        return self._super._check_targets(targets)
+
+    def objective(self, targets: Targets, kind: str = "trimmed_bbox_error", per_track: bool = False):
+        """The closed-loop error of every experiment of `targets`, pooled over the tracks, as a device float64 [E] tensor, enqueued on the current torch
+        stream (no synchronisation): the division of `run(targets).summary`'s slots, bit for bit.  `per_track`: instead the [T, E] tensor of each
+        track's own error, `rs.replay(t).objective`'s bits.  The precise objectives are `rs.replay(t)`'s."""
+        import torch
+
+        E, k = self._check_targets(targets), self._objective_kind(kind)
+        with torch.cuda.device(self._dev):
+            out = torch.empty((E,), dtype=torch.float64, device=self._dev)
+            each = torch.empty((self.T, E), dtype=torch.float64, device=self._dev) if per_track else None
+            self._enqueue_objective(targets, k, self._objective_buffers(E), out, each)
+        return each if per_track else out
+
+    def optimize_polyfit(self, degree: int, sample_times, objective: str = "trimmed_bbox_error", **swarm) -> SwarmResult:
+        """`Replay.optimize_polyfit` (its arguments, its search) for the weights of lowest POOLED closed-loop error over the set's tracks."""
+        self._check_reach("sample_times", check_times(sample_times, "sample_times"))
+        return self._super.optimize_polyfit(degree, sample_times, objective, **swarm)
+
+    def to_config(self, degree: int, weights, sample_times=None) -> PolyfitConfig:
+        return self._super.to_config(degree, weights, sample_times)
+
+    # ------------------------------------------------------------------ the loop
+    def run(self, targets: Targets, precise: bool = False, analysis: Optional[Analysis] = None) -> ReplaySetResult:
+        """Replay the E experiments of `targets` on every track: scan, rows reduction, one synchronisation.  Frames, logs and `analysis` belong to one
+        track: they are `rs.replay(t).run`'s."""
+        import torch
+
+        if precise or analysis is not None:
+            raise ValueError("the precise error and the analysis are per track: use rs.replay(t).run(..., precise=True / analysis=spec)")
+        E, sp = self._check_targets(targets), self._super
+        with torch.cuda.device(self._dev):
+            stream, buf = sp._stream(), self._objective_buffers(E)
+            hip.replay_set_scan(sp._cfg, self._table, KINDS[targets.kind], E, sp.track, targets.a, targets.b, targets.valid, sp._share, buf["pos"], buf["move"],
+                                stream=stream)
+            hip.replay_set_rows(sp._cfg, self._table, E, sp.track, sp._share, buf["pos"], buf["move"], buf["track_summary"], buf["summary"], buf["scratch"],
+                                buf["scratch"].numel(), stream=stream)
+            torch.cuda.current_stream(self._dev).synchronize()  # the one host synchronisation
+            per = buf["track_summary"].cpu().numpy()
+            cut = lambda x, t: x[self.cyc_off[t]:self.cyc_off[t] + self.n_cycles[t]].permute(1, 0, 2).contiguous().cpu().numpy()  # noqa: E731
+            return ReplaySetResult(_summary_of(buf["summary"].cpu().numpy()), [_summary_of(per[t]) for t in range(self.T)],
+                                   [cut(buf["move"], t) for t in range(self.T)], [cut(buf["pos"], t) for t in range(self.T)])
 
 
 def _summary_of(s: np.ndarray) -> Summary:
