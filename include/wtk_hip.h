@@ -740,6 +740,58 @@ int wtk_replay_set_objective(const wtk_replay_config *cfg, const wtk_replay_set_
                              int32_t objective, double *objective_dev, double *track_objective_dev, const int32_t *stop_dev, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The PRECISE error of a population on a set of tracks (csrc/replay_set.hip): wtk_replay_precise (below) of every
+ * (track, experiment) of a set scan, each track with its own frames, background, frame shape and threshold, in a number of launches that
+ * does not depend on T, and the objective pooled over the rows of all tracks.
+ *
+ * wtk_replay_set_frames   one entry per track, beside wtk_replay_set_track: frames [n_frames][H][W] gray uint8 on the device (row r of the
+ *     track is frame r, n_frames >= R), bg [H][W], (H, W) = the track's (y_max + 1, x_max + 1), diff_thresh (a pixel is foreground where
+ *     |frame - bg| > diff_thresh), row0 = the sum of R over the tracks before it.  frames_host [T] is read by the checks, frames_dev [T]
+ *     (the same bytes, uploaded once by the caller) by the kernels.
+ * wtk_replay_set_precise   from a set scan's pos_dev / move_dev: one workgroup per logged row of ALL tracks (global row rho = row0 + r),
+ *     which finds its track by a search on row0 and runs wtk_replay_precise's per-frame statements on that track's view and frames; the
+ *     walk launch likewise; the reduction one block per (experiment, chunk of 4096 rows of one track), the trimmed rows dropping the first
+ *     and the last logged cycle of EVERY track; the set's finish launch.  Four launches whatever T is.  max_crop_px as for
+ *     wtk_replay_precise: it never changes a bit.
+ *   err_dev [E][sum R] float64 (nullable), counts_dev [E][sum R][2] int32 (nullable): track t's rows are the columns from row0.
+ *   track_summary_dev [T][E][WTK_REPLAY_PRECISE_SUMMARY_DOUBLES]: bit-equal to wtk_replay_precise's summary of that track alone;
+ *     summary_dev [E][...]: those added in track order from 0.0.  No floating-point atomics.
+ *   scratch_dev: wtk_replay_set_precise_scratch_doubles(tracks_host, T, cycle_frame_num, E) doubles (-1: a bad table): E sum R pair
+ *     errors ([sum R][E], track t's block from row0 E), E S 6 chunk partials (S = the chunks of all tracks), ceil(sum R / 2) doubles of
+ *     int32 flags.
+ * wtk_replay_set_precise_objective   wtk_replay_set_scan, the above without per-pair output, and in the finish launch objective_dev[e] =
+ *     one float64 division of the POOLED slots for a WTK_REPLAY_POBJ_* id; track_objective_dev [T][E] (nullable): the same of each
+ *     track's slots, wtk_replay_precise_objective's bits.  0 / 0 is NaN.  Five launches whatever T is.
+ * stop_dev (nullable): as for wtk_replay_objective.
+ * Refused (error code, nothing launched): everything wtk_replay_set_rows / wtk_replay_set_objective refuse of the track table; for track
+ *     t (named by index) a null frames or background pointer, (H, W) other than the track's, H * W > 2^30, n_frames < R, a diff_thresh that
+ *     is not finite, row0 that is not the prefix sum of R; max_crop_px < 0, sum R >= 2^31, S E >= 2^31, scratch too small, an unknown
+ *     objective, the trimmed objective where any track logs fewer than 3 cycles, a required pointer that is null.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct wtk_replay_set_frames {
+    const uint8_t *frames; /* [n_frames][H][W] gray, on the device */
+    const uint8_t *bg;     /* [H][W], on the device */
+    double diff_thresh;
+    int64_t row0;          /* first global logged row of the track: the sum of R over the tracks before it */
+    int32_t n_frames, H, W;
+    int32_t reserved;
+} wtk_replay_set_frames;
+int64_t wtk_replay_set_precise_scratch_doubles(const wtk_replay_set_track *tracks_host, int32_t T, int32_t cycle_frame_num, int32_t E);
+int wtk_replay_set_precise(const wtk_replay_config *cfg, const wtk_replay_set_track *tracks_host, const wtk_replay_set_track *tracks_dev,
+                           const wtk_replay_set_frames *frames_host, const wtk_replay_set_frames *frames_dev, int32_t T, int32_t guard_cycles,
+                           int32_t E, const double *track_dev, int32_t n_super, const double *share_dev, const int32_t *pos_dev,
+                           const int32_t *move_dev, int32_t max_crop_px, double *err_dev, int32_t *counts_dev, double *track_summary_dev,
+                           double *summary_dev, double *scratch_dev, int64_t scratch_doubles, const int32_t *stop_dev, void *stream);
+int wtk_replay_set_precise_objective(const wtk_replay_config *cfg, const wtk_replay_set_track *tracks_host,
+                                     const wtk_replay_set_track *tracks_dev, const wtk_replay_set_frames *frames_host,
+                                     const wtk_replay_set_frames *frames_dev, int32_t T, int32_t guard_cycles, int32_t kind, int32_t E,
+                                     const double *track_dev, int32_t n_super, const double *a_dev, const double *b_dev,
+                                     const int32_t *valid_dev, const double *share_dev, int32_t *pos_dev, int32_t *move_dev,
+                                     int32_t max_crop_px, double *track_summary_dev, double *summary_dev, double *scratch_dev,
+                                     int64_t scratch_doubles, int32_t objective, double *objective_dev, double *track_objective_dev,
+                                     const int32_t *stop_dev, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * The per-cycle ResMLP targets of a population of E models of one structure in one call: what Replay.mlp computes model by model
  * (wtk_mlp_predict_track, the float32 clip, the first box's corner), in the layout wtk_replay_scan reads for WTK_REPLAY_MLP, bit for bit.
  *   layers ...        the structure (in_dim, out_dim, relu of every layer; batch_norm is not looked at), as for wtk_mlp_folded_floats

@@ -6,7 +6,7 @@ simulate.ipynb loads the file too; here `load_config(path)` gives the controller
   python tools/optimize_polyfit_weights.py EXPERIMENT_FOLDER_OR_BBOXES_CSV [more logs ...] --out polyfit_config.json
          [--fps 60] [--imaging-ms 200 --pred-ms 40 --moving-ms 50] [--offsets -45 -39 ...] [--pred-offset 21] [--degrees 1 2 3]
          [--min-speed 0.1 --max-speed 2] [--seed 0] [--pop-size 100 --max-epoch 300 --max-early-stop 100]
-         [--closed-loop EXP_CONFIG_JSON [one per log ...] [--camera-mm 4 4] [--micro-mm 0.32 0.32] [--precise FRAMES_NPY BACKGROUND_NPY]]
+         [--closed-loop EXP_CONFIG_JSON [one per log ...] [--camera-mm 4 4] [--micro-mm 0.32 0.32] [--precise FRAMES_NPY BACKGROUND_NPY [one pair per log ...]]]
 
 A folder stands for its bboxes.csv, and its exp_config.json supplies frames_per_sec when --fps is not given.  Defaults are the notebook's: with L the
 cycle length in frames, offsets (-3L, -3L+6, -2L, -2L+6, -L, -L+6, 0, 3), target offset L + imaging_frames // 2, speed window 0.1 .. 2 px / frame.
@@ -20,8 +20,9 @@ replayed together and the error is pooled over the rows of all of them (ReplaySe
 also holds `closed_loop_error_of_open_loop_weights`, `closed_loop_error` and `closed_loop_weights`, and the closed-loop config of the best degree goes to
 <out stem>_closed_loop.json.  The closed-loop error is piecewise constant in the weights (moves are whole pixels).  Without the option nothing changes.
 With --precise FRAMES_NPY BACKGROUND_NPY (the experiment's gray frames, uint8 [F, H, W] with F >= the logged rows, and its background [H, W]) the
-closed-loop objective is the trimmed mean PRECISE error instead (Replay.attach_frames; the frames are held on the device and give the frame shape);
-it takes one log."""
+closed-loop objective is the trimmed mean PRECISE error instead (Replay.attach_frames; the frames are held on the device and give the frame shape).
+With several logs give one FRAMES_NPY BACKGROUND_NPY pair per log, in the logs' order: the search runs on the ReplaySet with every log's frames
+attached (ReplaySet.attach_frames) and the precise error is pooled over the rows of all logs."""
 import argparse
 import json
 import os
@@ -64,7 +65,7 @@ def main(argv=None):
     ap.add_argument("--closed-loop", default=None, nargs="+", metavar="EXP_CONFIG_JSON")
     ap.add_argument("--camera-mm", type=float, nargs=2, default=[4.0, 4.0])
     ap.add_argument("--micro-mm", type=float, nargs=2, default=[0.32, 0.32])
-    ap.add_argument("--precise", nargs=2, default=None, metavar=("FRAMES_NPY", "BACKGROUND_NPY"))
+    ap.add_argument("--precise", nargs="+", default=None, metavar="FRAMES_NPY BACKGROUND_NPY")
     args = ap.parse_args(argv)
 
     from wtracker_amd.polyfit_opt import WeightEvaluator
@@ -97,8 +98,8 @@ def main(argv=None):
 
         if len(args.closed_loop) not in (1, len(paths)):
             ap.error(f"--closed-loop takes one exp_config.json for all logs or one per log ({len(paths)})")
-        if args.precise is not None and len(paths) > 1:
-            ap.error("--precise takes one log (the frames belong to one experiment)")
+        if args.precise is not None and len(args.precise) != 2 * len(paths):
+            ap.error(f"--precise takes one FRAMES_NPY BACKGROUND_NPY pair per log ({len(paths)} logs: {2 * len(paths)} files)")
         exps = [ExperimentConfig.from_dict(json.load(open(c))) for c in args.closed_loop]
         exp = exps[0]
         loop_tc = TimingConfig(exp, args.imaging_ms, args.pred_ms, args.moving_ms, tuple(args.camera_mm), tuple(args.micro_mm))
@@ -107,13 +108,17 @@ def main(argv=None):
             import numpy as np
             import torch
 
-            frames, objective = torch.from_numpy(np.load(args.precise[0])).to(f"cuda:{args.device}"), "trimmed_precise_error"
+            frames = [torch.from_numpy(np.load(p)).to(f"cuda:{args.device}") for p in args.precise[0::2]]
+            backgrounds, objective = [np.load(p) for p in args.precise[1::2]], "trimmed_precise_error"
         if len(paths) > 1:
-            rp = ReplaySet(paths, loop_tc, exp if len(exps) == 1 else exps, device=args.device)
+            shapes = None if frames is None else [tuple(fr.shape[1:3]) for fr in frames]
+            rp = ReplaySet(paths, loop_tc, exp if len(exps) == 1 else exps, shapes, device=args.device)
+            if frames is not None:
+                rp.attach_frames(frames, backgrounds)
         else:
-            rp = Replay(paths[0], loop_tc, exp, frame_shape=None if frames is None else frames.shape[1:3], device=args.device)
-        if frames is not None:
-            rp.attach_frames(frames, np.load(args.precise[1]))
+            rp = Replay(paths[0], loop_tc, exp, frame_shape=None if frames is None else frames[0].shape[1:3], device=args.device)
+            if frames is not None:
+                rp.attach_frames(frames[0], backgrounds[0])
     for deg in args.degrees:
         res = ev.optimize(deg, pop_size=args.pop_size, max_epoch=args.max_epoch, max_early_stop=args.max_early_stop, seed=args.seed)
         cfg = ev.to_config(deg, res.weights)

@@ -57,11 +57,12 @@ __device__ __forceinline__ void crop_walk(const uint8_t *fr, const uint8_t *bg, 
 // err of a row from its counts: float64, 0 where nothing is foreground
 __device__ __forceinline__ double precise_error_of(int total, int inside) { return total == 0 ? 0.0 : 1.0 - (double)inside / (double)total; }
 
-// |frame - bg| > t for integer |frame - bg| in [0, 255]: > floor(t) for finite t
-inline int threshold_int(double t) {
-    if (std::isnan(t) || t >= 255.0) return 255; // nothing is foreground
-    if (t < 0.0) return -1;                      // everything is
-    return (int)std::floor(t);
+// |frame - bg| > t for integer |frame - bg| in [0, 255]: > floor(t) for finite t.  The entry points of one track call it on the host; a set's kernels
+// call it per block on the threshold of the block's track (the frames table holds the double).
+__host__ __device__ inline int threshold_int(double t) {
+    if (t != t || t >= 255.0) return 255; // (NaN) nothing is foreground
+    if (t < 0.0) return -1;               // everything is
+    return (int)floor(t);
 }
 
 } // namespace wtk

@@ -137,7 +137,8 @@ __device__ __forceinline__ bool non_perfect(double err) { return err > 1e-7; }
 // The per-experiment sums' FIXED order inside a chunk: every thread of the block has added the chunk's rows t, t + 256, ... in order into acc; here a
 // binary tree over the 256 threads in LDS, and the chunk's N partials stored at `partial` (the finish launch adds the chunks in index order).  The
 // chunking depends on the row count only: an experiment gives the same bits alone and inside any population.  No floating-point atomics.
-// (The lane-serial loop stays in the two kernels: handed over as a callable, the precise reduction's sums went to scratch memory.)
+// (The lane-serial loop stays with its kernels, the precise one as replay_precise_device.h's precise_chunk_rows on the caller's acc array: handed over
+// as a callable, the precise reduction's sums went to scratch memory.)
 template <int N> __device__ __forceinline__ void chunk_reduce(double (&red)[N][kRowThreads], const double (&acc)[N], double *partial) {
     for (int q = 0; q < N; ++q) red[q][threadIdx.x] = acc[q];
     __syncthreads();

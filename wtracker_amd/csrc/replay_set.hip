@@ -11,8 +11,16 @@
 //   finish  per (experiment, slot): each track's chunk partials in index order -> track_summary[t][e]; those in track order from 0.0 -> summary[e]; the
 //           one float64 division of the pooled slots (and, where asked for, of each track's)
 // Three launches whatever T is.  No floating-point atomics.  Every launch reads the nullable stop flag and touches nothing once it is up.
+//
+// The PRECISE error of the set, each track with its own frames, background, frame shape and threshold (the frames table):
+//   table   one block per GLOBAL logged row (row0 = prefix sum of R): the block finds its track by a search in the frames table, fills a PreciseArgs
+//           for that track alone and runs replay_precise_device.h's precise_frame on the track's row, as replay_precise_kernel does
+//   walk    the same lookup, precise_walk_frame
+//   reduce  one block per (experiment, global chunk), replay_precise_reduce_kernel's lane order and tree on the rows of the chunk's track
+//   finish  the finish launch above on the precise partials (both summaries are 6 wide) with the precise objective's slots
+// After the scan that is five launches whatever T is, and the frames of all tracks fill the device together.
 #include "wtk_internal.h"
-#include "replay_device.h"
+#include "replay_precise_device.h"
 
 #include <algorithm>
 
@@ -120,6 +128,87 @@ __global__ __launch_bounds__(kFinishExperiments * 8) void replay_set_finish_kern
     }
 }
 
+// ---- the precise error of the set
+struct SetPreciseArgs {
+    SetArgs s;                           // the view of the scanned set; partial, the summaries and the objective are the PRECISE ones
+    const wtk_replay_set_frames *frames; // [T] on the device
+    long long rows;                      // logged rows of all tracks
+    int max_cells;
+    double *pair; // [rows][E]: track t's [R_t][E] block starts at row0_t E
+    int *walk;    // [rows]
+    double *err;  // [E][rows] (nullable)
+    int *counts;  // [E][rows][2] (nullable)
+};
+
+// the last track whose first global row is <= rho (a track without rows shares its row0 with the next one and is never found); block-uniform, so the
+// search and the view built from it stay in scalar registers, as replay_set_rows_kernel's search on chunk0
+__device__ __forceinline__ int track_of_row(const SetPreciseArgs &a, long long rho) {
+    int lo = 0, hi = a.s.T - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (a.frames[mid].row0 <= rho) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ ReplayView track_view(const SetArgs &a, const wtk_replay_set_track &tr) {
+    const long long c0 = (long long)tr.cyc_off * a.E;
+    ReplayView v;
+    v.g = track_geometry(a, tr), v.E = a.E, v.C = tr.n_cycles, v.n_log = tr.n_log, v.R = tr.R;
+    v.track = a.track + 4 * (long long)tr.cyc_off * a.g.L, v.share = a.share, v.pos = a.pos + 2 * c0, v.move = a.move + 2 * c0;
+    return v;
+}
+
+// track t of the set as replay_precise_kernel's arguments: the track's view, frames and threshold; the output bases at the track's first global row
+__device__ __forceinline__ PreciseArgs track_precise(const SetPreciseArgs &a, int t) {
+    const wtk_replay_set_frames fr = a.frames[t];
+    PreciseArgs p;
+    p.v = track_view(a.s, a.s.tracks[t]);
+    p.frames = fr.frames, p.bg = fr.bg, p.H = fr.H, p.W = fr.W, p.thr = threshold_int(fr.diff_thresh);
+    p.max_cells = a.max_cells, p.S = 0, p.out_rows = a.rows;
+    p.pair = a.pair + fr.row0 * a.s.E, p.walk = a.walk + fr.row0;
+    p.err = a.err ? a.err + fr.row0 : nullptr, p.counts = a.counts ? a.counts + 2 * fr.row0 : nullptr;
+    p.partial = nullptr, p.summary = nullptr, p.stop = nullptr;
+    return p;
+}
+
+__global__ __launch_bounds__(kPreciseThreads) void replay_set_precise_kernel(const SetPreciseArgs a) {
+    extern __shared__ unsigned sat[];
+    if (a.s.stop && *a.s.stop) return; // block-uniform
+    const long long rho = blockIdx.x;
+    const int t = track_of_row(a, rho);
+    precise_frame(track_precise(a, t), rho - a.frames[t].row0, sat);
+}
+
+__global__ __launch_bounds__(kPreciseThreads) void replay_set_precise_walk_kernel(const SetPreciseArgs a) {
+    if (a.s.stop && *a.s.stop) return; // block-uniform
+    const long long rho = blockIdx.x;
+    if (!a.walk[rho]) return; // block-uniform
+    const int t = track_of_row(a, rho);
+    precise_walk_frame(track_precise(a, t), rho - a.frames[t].row0);
+}
+
+// Consecutive blocks are consecutive experiments of one chunk, as replay_precise_reduce_kernel's.
+__global__ __launch_bounds__(kRowThreads) void replay_set_precise_reduce_kernel(const SetPreciseArgs a) {
+    __shared__ double red[kPreciseSummary][kRowThreads];
+    if (a.s.stop && *a.s.stop) return; // block-uniform
+    const int gs = blockIdx.x / a.s.E, e = blockIdx.x - gs * a.s.E;
+    int lo = 0, hi = a.s.T - 1; // the last track whose first chunk is <= gs, as replay_set_rows_kernel
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (a.s.tracks[mid].chunk0 <= gs) lo = mid;
+        else hi = mid - 1;
+    }
+    const wtk_replay_set_track tr = a.s.tracks[lo];
+    const ReplayView v = track_view(a.s, tr); // the track's own n_log: its first and last logged cycle are trimmed
+    double acc[kPreciseSummary];
+    for (int q = 0; q < kPreciseSummary; ++q) acc[q] = 0.0;
+    precise_chunk_rows(v, a.pair + a.frames[lo].row0 * a.s.E, e, (long long)(gs - tr.chunk0) * kRowChunk, acc);
+    chunk_reduce(red, acc, a.s.partial + ((long long)e * a.s.S + gs) * kPreciseSummary);
+}
+static_assert((int)kPreciseSummary == (int)kSummary, "replay_set_finish_kernel adds the precise partials too");
+
 // The checks of the table every entry point shares: each track as replay_view sees it (reported with its index), the derived fields, the slots and
 // guards.  Leaves the shared geometry in a.g, the chunk count in a.S and the smallest n_log in min_log.
 int set_view(const char *who, const wtk_replay_config *cfg, const wtk_replay_set_track *host, const wtk_replay_set_track *dev, int32_t T, int32_t guard_cycles,
@@ -178,9 +267,60 @@ void launch_set_scan(const SetArgs &a, hipStream_t st) {
     hipLaunchKernelGGL(replay_set_scan_kernel, dim3((unsigned)((a.E + kScanThreads - 1) / kScanThreads), (unsigned)a.T), dim3(kScanThreads), 0, st, a);
 }
 
+void launch_set_finish(const SetArgs &a, hipStream_t st) {
+    hipLaunchKernelGGL(replay_set_finish_kernel, dim3((unsigned)((a.E + kFinishExperiments - 1) / kFinishExperiments)), dim3(kFinishExperiments * 8), 0, st, a);
+}
+
 void launch_set_rows(const SetArgs &a, hipStream_t st) {
     if (a.S > 0) hipLaunchKernelGGL(replay_set_rows_kernel, dim3((unsigned)((long long)a.S * a.E)), dim3(kRowThreads), 0, st, a);
-    hipLaunchKernelGGL(replay_set_finish_kernel, dim3((unsigned)((a.E + kFinishExperiments - 1) / kFinishExperiments)), dim3(kFinishExperiments * 8), 0, st, a);
+    launch_set_finish(a, st);
+}
+
+// the scratch of wtk_replay_set_precise in doubles from its start: the pairs' errors [rows][E], the chunk partials [E][S][6], the [rows] int32 walk flags
+inline long long set_precise_off_partial(long long E, long long rows) { return E * rows; }
+inline long long set_precise_off_walk(long long E, long long rows, long long S) { return set_precise_off_partial(E, rows) + E * S * kPreciseSummary; }
+inline long long set_precise_scratch(long long E, long long rows, long long S) { return set_precise_off_walk(E, rows, S) + (rows + 1) / 2; }
+
+// The checks of the frames table against the track table set_view has accepted (each reported with the track's index), and the precise outputs.
+int set_frames(const char *who, const wtk_replay_set_track *host, const wtk_replay_set_frames *frames_host, const wtk_replay_set_frames *frames_dev, int32_t T,
+               int32_t max_crop_px, double *err_dev, int32_t *counts_dev, double *track_summary_dev, double *summary_dev, double *scratch_dev,
+               int64_t scratch_doubles, SetPreciseArgs &p) {
+    const std::string w(who);
+    if (!frames_host || !frames_dev || !track_summary_dev || !summary_dev || !scratch_dev) return fail(w + ": null argument");
+    long long rows = 0;
+    for (int t = 0; t < T; ++t) {
+        const wtk_replay_set_frames &fr = frames_host[t];
+        const std::string wt = w + ": track " + std::to_string(t);
+        if (!fr.frames || !fr.bg) return fail(wt + ": null frames or background");
+        if (fr.H != host[t].y_max + 1 || fr.W != host[t].x_max + 1) return fail(wt + ": the frames' (H, W) differ from the track's frame (y_max + 1, x_max + 1)");
+        if ((long long)fr.H * fr.W > (1ll << 30)) return fail(wt + ": frames must be H x W gray with H * W <= 2^30");
+        if (fr.n_frames < host[t].R) return fail(wt + ": fewer frames than logged rows (row r is frame r)");
+        if (!std::isfinite(fr.diff_thresh)) return fail(wt + ": diff_thresh must be finite");
+        if (fr.row0 != rows) return fail(wt + ": row0 must be the sum of R over the tracks before it");
+        rows += host[t].R;
+    }
+    if (max_crop_px < 0) return fail(w + ": negative max_crop_px (0 = the default)");
+    const long long E = p.s.E, S = p.s.S;
+    if (rows > INT32_MAX || S * E > INT32_MAX) return fail(w + ": too many blocks for one launch");
+    if (scratch_doubles < set_precise_scratch(E, rows, S))
+        return fail(w + ": scratch smaller than wtk_replay_set_precise_scratch_doubles(tracks_host, T, L, E)");
+    p.frames = frames_dev, p.rows = rows, p.max_cells = precise_max_cells(max_crop_px);
+    p.pair = scratch_dev, p.s.partial = scratch_dev + set_precise_off_partial(E, rows);
+    p.walk = reinterpret_cast<int *>(scratch_dev + set_precise_off_walk(E, rows, S));
+    p.err = err_dev, p.counts = counts_dev, p.s.track_summary = track_summary_dev, p.s.summary = summary_dev;
+    return 0;
+}
+
+int launch_set_precise(const SetPreciseArgs &p, hipStream_t st) {
+    if (p.rows > 0) {
+        // above 64 KiB of dynamic LDS a kernel needs the attribute (per device, so it is set at every call: a host-side table write)
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&replay_set_precise_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kPreciseLdsBytes));
+        hipLaunchKernelGGL(replay_set_precise_kernel, dim3((unsigned)p.rows), dim3(kPreciseThreads), (size_t)p.max_cells * sizeof(unsigned), st, p);
+        hipLaunchKernelGGL(replay_set_precise_walk_kernel, dim3((unsigned)p.rows), dim3(kPreciseThreads), 0, st, p);
+        hipLaunchKernelGGL(replay_set_precise_reduce_kernel, dim3((unsigned)((long long)p.s.S * p.s.E)), dim3(kRowThreads), 0, st, p);
+    }
+    launch_set_finish(p.s, st);
+    return 0;
 }
 
 } // namespace
@@ -246,6 +386,62 @@ extern "C" int wtk_replay_set_objective(const wtk_replay_config *cfg, const wtk_
     hipStream_t st = (hipStream_t)stream;
     launch_set_scan(a, st);
     launch_set_rows(a, st);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int64_t wtk_replay_set_precise_scratch_doubles(const wtk_replay_set_track *tracks_host, int32_t T, int32_t cycle_frame_num, int32_t E) {
+    if (!tracks_host || T < 1 || cycle_frame_num < 1 || E < 0) return -1;
+    int64_t chunks = 0, rows = 0;
+    for (int t = 0; t < T; ++t) {
+        if (tracks_host[t].n_log < 0) return -1;
+        const long long R = (long long)tracks_host[t].n_log * cycle_frame_num;
+        chunks += chunk_count(R), rows += R;
+    }
+    return set_precise_scratch(E, rows, chunks);
+}
+
+extern "C" int wtk_replay_set_precise(const wtk_replay_config *cfg, const wtk_replay_set_track *tracks_host, const wtk_replay_set_track *tracks_dev,
+                                      const wtk_replay_set_frames *frames_host, const wtk_replay_set_frames *frames_dev, int32_t T, int32_t guard_cycles,
+                                      int32_t E, const double *track_dev, int32_t n_super, const double *share_dev, const int32_t *pos_dev,
+                                      const int32_t *move_dev, int32_t max_crop_px, double *err_dev, int32_t *counts_dev, double *track_summary_dev,
+                                      double *summary_dev, double *scratch_dev, int64_t scratch_doubles, const int32_t *stop_dev, void *stream) {
+    const char *who = "wtk_replay_set_precise";
+    SetPreciseArgs p = {};
+    int min_log = 0;
+    if (set_view(who, cfg, tracks_host, tracks_dev, T, guard_cycles, WTK_REPLAY_OPTIMAL, E, track_dev, n_super, share_dev, pos_dev, move_dev, p.s, min_log)) return 1;
+    if (set_frames(who, tracks_host, frames_host, frames_dev, T, max_crop_px, err_dev, counts_dev, track_summary_dev, summary_dev, scratch_dev, scratch_doubles, p))
+        return 1;
+    p.s.stop = stop_dev;
+    if (launch_set_precise(p, (hipStream_t)stream)) return 1;
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int wtk_replay_set_precise_objective(const wtk_replay_config *cfg, const wtk_replay_set_track *tracks_host, const wtk_replay_set_track *tracks_dev,
+                                                const wtk_replay_set_frames *frames_host, const wtk_replay_set_frames *frames_dev, int32_t T,
+                                                int32_t guard_cycles, int32_t kind, int32_t E, const double *track_dev, int32_t n_super, const double *a_dev,
+                                                const double *b_dev, const int32_t *valid_dev, const double *share_dev, int32_t *pos_dev, int32_t *move_dev,
+                                                int32_t max_crop_px, double *track_summary_dev, double *summary_dev, double *scratch_dev,
+                                                int64_t scratch_doubles, int32_t objective, double *objective_dev, double *track_objective_dev,
+                                                const int32_t *stop_dev, void *stream) {
+    const char *who = "wtk_replay_set_precise_objective";
+    const std::string w(who);
+    SetPreciseArgs p = {};
+    int min_log = 0;
+    if (set_view(who, cfg, tracks_host, tracks_dev, T, guard_cycles, kind, E, track_dev, n_super, share_dev, pos_dev, move_dev, p.s, min_log)) return 1;
+    if (set_targets(who, kind, a_dev, b_dev, valid_dev, p.s)) return 1;
+    if (set_frames(who, tracks_host, frames_host, frames_dev, T, max_crop_px, nullptr, nullptr, track_summary_dev, summary_dev, scratch_dev, scratch_doubles, p))
+        return 1;
+    if (!objective_dev) return fail(w + ": null argument");
+    const ObjectiveRule *rule = std::find_if(std::begin(kPreciseObjectives), std::end(kPreciseObjectives), [&](const ObjectiveRule &r) { return r.id == objective; });
+    if (rule == std::end(kPreciseObjectives)) return fail(w + ": unknown objective");
+    if (rule->needs_3_cycles && min_log < 3)
+        return fail(w + ": the trimmed objective needs at least 3 logged cycles of every track (the first and the last of each are dropped)");
+    p.s.objective = objective_dev, p.s.track_objective = track_objective_dev, p.s.num = rule->num, p.s.den = rule->den, p.s.stop = stop_dev;
+    hipStream_t st = (hipStream_t)stream;
+    launch_set_scan(p.s, st);
+    if (launch_set_precise(p, st)) return 1;
     HIP_TRY(hipGetLastError());
     return 0;
 }

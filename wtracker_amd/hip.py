@@ -59,6 +59,11 @@ class _ReplaySetTrack(C.Structure):
                                                               "chunk0")]
 
 
+class _ReplaySetFrames(C.Structure):
+    _fields_ = [("frames", C.c_void_p), ("bg", C.c_void_p), ("diff_thresh", C.c_double), ("row0", C.c_int64), ("n_frames", C.c_int32), ("H", C.c_int32),
+                ("W", C.c_int32), ("reserved", C.c_int32)]
+
+
 class _AnalysisConfig(C.Structure):
     _fields_ = ([("bounds", C.c_double * 4)] + [(n, C.c_double) for n in ("time_factor", "dist_factor", "speed_factor", "min_speed", "min_bbox_error",
                                                                           "min_dist_error", "min_width", "min_height")]
@@ -75,6 +80,7 @@ _vp, _i32, _i64, _f32, _f64, _size = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 _pvp, _pi32, _pi64, _pf32, _pf64, _pcfg = C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_f32), C.POINTER(_f64), C.POINTER(_ReplayConfig)
 _pacfg = C.POINTER(_AnalysisConfig)
 _ptrk = C.POINTER(_ReplaySetTrack)
+_pfrm = C.POINTER(_ReplaySetFrames)
 
 # The C ABI, one row per symbol of include/wtk_hip.h and in its order: name -> (restype, argtypes).  load() applies it and nothing else declares a
 # signature; tests/test_abi.py compares every row with the header's prototype, kind by kind (pointer, int32, int64, size_t, float, double).
@@ -165,6 +171,10 @@ SIGNATURES = {
     "wtk_replay_set_rows": (_i32, [_pcfg, _ptrk, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "wtk_replay_set_objective": (_i32, [_pcfg, _ptrk, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp,
                                         _vp, _vp]),
+    "wtk_replay_set_precise_scratch_doubles": (_i64, [_ptrk, _i32, _i32, _i32]),
+    "wtk_replay_set_precise": (_i32, [_pcfg, _ptrk, _vp, _pfrm, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "wtk_replay_set_precise_objective": (_i32, [_pcfg, _ptrk, _vp, _pfrm, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp,
+                                                _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     "wtk_replay_mlp_targets": (_i32, [C.POINTER(_MlpTrainLayer), _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _f32, _vp, _vp, _vp, _vp, _vp]),
     "wtk_replay_mlp_targets_waves": (_i32, [_i64]),
     "wtk_replay_yolo_step": (_i32, [_pcfg, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
@@ -595,6 +605,60 @@ def replay_set_objective(cfg: _ReplayConfig, table: ReplaySetTable, kind: int, E
 
 REPLAY_PRECISE_SUMMARY_DOUBLES = 6
 REPLAY_PRECISE_OBJECTIVES = {"trimmed_precise_error": 0, "precise_error": 1, "precise_non_perfect": 2}  # WTK_REPLAY_POBJ_*
+
+
+class ReplaySetFrames:
+    """The frames table of a set of tracks (wtk_replay_set_frames [T]), beside its ReplaySetTable: `host` the ctypes array the entry points check,
+    `dev` the same bytes on the device (uploaded here, once).  `entries`: per track a dict of frames (device pointer), bg (device pointer), n_frames, H,
+    W, diff_thresh; row0 is derived from the table's R.  The caller keeps the tensors behind the pointers alive."""
+
+    def __init__(self, table: ReplaySetTable, entries: Sequence[dict], device=None):
+        if len(entries) != table.T:
+            raise WtkError(f"the frames table needs one entry per track: {table.T} tracks, {len(entries)} entries")
+        self.T = table.T
+        self.host = (_ReplaySetFrames * max(1, self.T))()
+        row0 = 0
+        for t, fr in enumerate(entries):
+            self.host[t] = _ReplaySetFrames(int(fr["frames"]), int(fr["bg"]), float(fr["diff_thresh"]), row0, int(fr["n_frames"]), int(fr["H"]), int(fr["W"]), 0)
+            row0 += int(table.host[t].R)
+        self.n_rows = row0
+        self.dev = None
+        if device is not None:
+            import torch
+
+            raw = np.frombuffer(bytes(self.host), dtype=np.uint8).copy()
+            self.dev = torch.from_numpy(raw).to(device)
+
+    def _args(self):
+        return self.host, _ptr(self.dev)
+
+
+def replay_set_precise_scratch_doubles(table: ReplaySetTable, E: int) -> int:
+    return int(load().wtk_replay_set_precise_scratch_doubles(table.host, table.T, table.L, E))
+
+
+def replay_set_precise(cfg: _ReplayConfig, table: ReplaySetTable, frames: ReplaySetFrames, E: int, track_dev, share_dev, pos_dev, move_dev, max_crop_px: int,
+                       err_dev, counts_dev, track_summary_dev, summary_dev, scratch_dev, scratch_doubles: int, stop_dev=None, stream: int = 0):
+    """The precise error of every (track, experiment, logged frame) of a set scan (wtk_replay_set_precise): per-track summaries [T, E, 6], the pooled
+    summary [E, 6]; err_dev float64 [E, sum R] and counts_dev int32 [E, sum R, 2] or None."""
+    host, dev, T, guard = table._args()
+    _check(load().wtk_replay_set_precise(C.byref(cfg) if cfg is not None else None, host, dev, *frames._args(), T, guard, E, _ptr(track_dev), table.n_super,
+                                         _ptr(share_dev), _ptr(pos_dev), _ptr(move_dev), int(max_crop_px), _ptr(err_dev), _ptr(counts_dev),
+                                         _ptr(track_summary_dev), _ptr(summary_dev), _ptr(scratch_dev), scratch_doubles, _ptr(stop_dev), C.c_void_p(stream)),
+           "wtk_replay_set_precise")
+
+
+def replay_set_precise_objective(cfg: _ReplayConfig, table: ReplaySetTable, frames: ReplaySetFrames, kind: int, E: int, track_dev, a_dev, b_dev, valid_dev,
+                                 share_dev, pos_dev, move_dev, max_crop_px: int, track_summary_dev, summary_dev, scratch_dev, scratch_doubles: int,
+                                 objective: int, objective_dev, track_objective_dev=None, stop_dev=None, stream: int = 0):
+    """objective_dev[e] = the chosen precise-error figure of experiment e pooled over the set's tracks (wtk_replay_set_precise_objective);
+    track_objective_dev [T, E] (optional): the same of each track."""
+    host, dev, T, guard = table._args()
+    _check(load().wtk_replay_set_precise_objective(C.byref(cfg) if cfg is not None else None, host, dev, *frames._args(), T, guard, kind, E, _ptr(track_dev),
+                                                   table.n_super, _ptr(a_dev), _ptr(b_dev), _ptr(valid_dev), _ptr(share_dev), _ptr(pos_dev), _ptr(move_dev),
+                                                   int(max_crop_px), _ptr(track_summary_dev), _ptr(summary_dev), _ptr(scratch_dev), scratch_doubles, objective,
+                                                   _ptr(objective_dev), _ptr(track_objective_dev), _ptr(stop_dev), C.c_void_p(stream)),
+           "wtk_replay_set_precise_objective")
 
 
 def replay_precise_scratch_doubles(E: int, R: int) -> int:

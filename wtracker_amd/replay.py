@@ -51,6 +51,13 @@ does not depend on T, the error pooled over the rows of all logs; the search and
     rs.objective(rs.polyfit_population(weights_dev, 2, times))          # device float64 [P]; per_track=True -> [T, P]
     rs.optimize_polyfit(2, times, start=[open_loop.weights]); trainer.fit(..., closed_loop=rs); rs.replay(t)   # the plain Replay of track t
 
+With every track's frames attached the set gives the precise error too: each track with its own frames, background, frame shape
+and threshold, five launches whatever T is, per-track summaries with `rs.replay(t)`'s bits and the objective pooled over the rows of all logs:
+
+    rs.attach_frames([frames0, frames1, frames2], [bg0, bg1, bg2], diff_thresh=20)
+    rs.objective(tg, "trimmed_precise_error")                           # also per_track=True, optimize_polyfit(..., objective=...), fit(closed_loop=rs, ...)
+    rs.run(tg, precise=True).precise_summary                            # .track_precise_summary[t]; per_row_errors=True: .precise_error[t], .precise_counts[t]
+
 There is no CPU fallback: without a visible GPU the constructors raise.  Not covered: `StepMotorController`, DataAnalyzer's `remove_cycle` and
 `save` / `load`, the plots themselves, the YOLO controller's second look (YoloConfig.recheck_margin).
 """
@@ -786,12 +793,17 @@ DEFAULT_REACH = 64  # frames from a cycle's start: beyond the notebook's Polyfit
 @dataclass
 class ReplaySetResult:
     """`ReplaySet.run`: `summary` the pooled Summary ([E] arrays: the sums and counts of all tracks' rows), `track_summary[t]` track t's Summary,
-    `moves[t]` / `positions[t]` int32 [E, C_t, 2] of track t."""
+    `moves[t]` / `positions[t]` int32 [E, C_t, 2] of track t.  With `precise`: `precise_summary` the pooled PreciseSummary, `track_precise_summary[t]`
+    track t's; with `per_row_errors` also `precise_error[t]` float64 [E, R_t] and `precise_counts[t]` int32 [E, R_t, 2]."""
 
     summary: Summary
     track_summary: list
     moves: list
     positions: list
+    precise_summary: Optional[PreciseSummary] = None
+    track_precise_summary: Optional[list] = None
+    precise_error: Optional[list] = None
+    precise_counts: Optional[list] = None
 
 
 class _SuperTrack(Replay):
@@ -806,7 +818,7 @@ class _SuperTrack(Replay):
         return self._set._objective_kind(kind)
 
     def _all_objective_buffers(self, E: int, precise: bool) -> dict:
-        return self._set._objective_buffers(E)
+        return self._set._objective_buffers(E, precise)
 
     def _enqueue_objective(self, targets: Targets, kind: int, buf: dict, out, stop_dev=None):
         self._set._enqueue_objective(targets, kind, buf, out, stop_dev=stop_dev)
@@ -833,7 +845,8 @@ class ReplaySet:
 
     The pooled objective is sum of the tracks' sums / sum of their counts: the mean over the rows of all logs (the reference's Plotter concatenates
     them); the trimmed rows drop the first and the last logged cycle of EVERY track.  A (track, experiment) pair has the bits of `Replay` on that track
-    alone.  Logs, Analysis and the precise error stay with `rs.replay(t)`."""
+    alone.  After `attach_frames` the precise error works the same way: `rs.objective(tg, "trimmed_precise_error")`,
+    `rs.run(tg, precise=True)`, the search and the trainer's closed loop with a precise objective.  Logs and Analysis stay with `rs.replay(t)`."""
 
     def __init__(self, tracks, timing_config: TimingConfig, experiment_configs, frame_shapes=None, reach: Optional[int] = None, device: int = 0):
         if hip.device_count() < 1:
@@ -875,10 +888,44 @@ class ReplaySet:
         # the super-track as a Replay whose scanned cycles are all n_super_cycles: the targets builders and the swarm run on it
         ec = dataclasses.replace(ecs[0], num_frames=(off - 1) * L + I + 1)
         self._super = _SuperTrack(self, track, timing_config, ec, device)
+        self._frames_table = None
 
     def replay(self, t: int) -> Replay:
-        """The plain `Replay` of track t: logs, Analysis and the precise error stay there."""
+        """The plain `Replay` of track t: logs and Analysis stay there (and the precise error of one track)."""
         return self._replays[t]
+
+    def attach_frames(self, frames, backgrounds, diff_thresh=20) -> None:
+        """Every track's frames, for the precise error of the set (`run(precise=True)`, the precise objectives): `frames` and `backgrounds` are
+        sequences of T entries, `diff_thresh` one threshold or T.  Entry t is what `Replay.attach_frames` of `rs.replay(t)` takes and is attached there
+        too (its checks; that Replay then computes the same track alone); a refusal names the track.  All frames lie on the set's device; the set
+        keeps the tensors alive."""
+        frames, backgrounds = list(frames), list(backgrounds)
+        thr = list(diff_thresh) if isinstance(diff_thresh, (list, tuple, np.ndarray)) else [diff_thresh] * self.T
+        if len(frames) != self.T or len(backgrounds) != self.T or len(thr) != self.T:
+            raise ValueError(f"{self.T} tracks: frames and backgrounds must hold {self.T} entries each, diff_thresh one value or {self.T}")
+        for t, fr in enumerate(frames):  # (Replay.attach_frames takes frames of any device: the set's kernels read all tracks in one launch)
+            if not hasattr(fr, "device") or fr.device != self._dev:
+                raise ValueError(f"track {t}: the frames must be a tensor on the set's device {self._dev}, got {getattr(fr, 'device', type(fr).__name__)}")
+            if not math.isfinite(float(thr[t])):
+                raise ValueError(f"track {t}: diff_thresh must be finite")
+        self._frames_table = None  # (its pointers are the tensors the per-track Replays hold: a refusal half way leaves no table behind)
+        for t, (rp, fr, bg) in enumerate(zip(self._replays, frames, backgrounds)):
+            try:
+                rp.attach_frames(fr, bg, thr[t])
+            except ValueError as err:
+                raise ValueError(f"track {t}: {err}") from None
+        entries = [dict(frames=rp._frames.data_ptr(), bg=rp._background.data_ptr(), n_frames=int(rp._frames.shape[0]), H=int(rp._frames.shape[1]),
+                        W=int(rp._frames.shape[2]), diff_thresh=rp._diff_thresh) for rp in self._replays]
+        import torch
+
+        self._frame_tensors = [(rp._frames, rp._background) for rp in self._replays]  # the table's pointers stay valid whatever the Replays do later
+        with torch.cuda.device(self._dev):
+            self._frames_table = hip.ReplaySetFrames(self._table, entries, device=self._dev)
+
+    def _need_frames(self) -> None:
+        if self._frames_table is None:
+            raise ValueError("the precise error of a set needs the frames of every track: call rs.attach_frames(frames, backgrounds) first "
+                             "(or use rs.replay(t), which takes attach_frames, for one track)")
 
     # ------------------------------------------------------------------ targets: the super-track's, after the reach is checked
     def _check_reach(self, what: str, offsets) -> None:
@@ -928,25 +975,38 @@ class ReplaySet:
 
     # ------------------------------------------------------------------ objective
     def _objective_kind(self, kind: str) -> int:
+        """The WTK_REPLAY_OBJ_* value of a name of OBJECTIVES, the WTK_REPLAY_POBJ_* value of a name of PRECISE_OBJECTIVES."""
+        if kind not in OBJECTIVES and kind not in PRECISE_OBJECTIVES:
+            raise ValueError(f"unknown objective {kind!r}: one of {sorted(OBJECTIVES)}, or with attach_frames one of {sorted(PRECISE_OBJECTIVES)}")
         if kind in PRECISE_OBJECTIVES:
-            raise ValueError(f"{kind!r} needs the frames of every track: a ReplaySet has none; use rs.replay(t), which takes attach_frames")
-        if kind not in OBJECTIVES:
-            raise ValueError(f"unknown objective {kind!r}: one of {sorted(OBJECTIVES)}")
-        if kind == "trimmed_bbox_error" and min(self.n_log) < 3:
+            self._need_frames()
+        if kind in ("trimmed_bbox_error", "trimmed_precise_error") and min(self.n_log) < 3:
             t = int(np.argmin(self.n_log))
             raise ValueError(f"the trimmed objective drops the first and the last logged cycle of every track: track {t} logs {self.n_log[t]}, at least 3 are needed")
-        return OBJECTIVES[kind]
+        return PRECISE_OBJECTIVES[kind] if kind in PRECISE_OBJECTIVES else OBJECTIVES[kind]
 
-    def _objective_buffers(self, E: int) -> dict:
+    def _objective_buffers(self, E: int, precise: bool = False) -> dict:
+        """The scan's arrays and the summaries and scratch of the rows reduction, or (`precise`) of the precise error: _enqueue_objective tells by
+        the "precise" entry which objective the buffers are for."""
         import torch
 
-        dev, C, n = self._dev, self.n_super_cycles, hip.REPLAY_SUMMARY_DOUBLES
-        return dict(pos=torch.empty((C, E, 2), dtype=torch.int32, device=dev), move=torch.empty((C, E, 2), dtype=torch.int32, device=dev),
-                    track_summary=torch.empty((self.T, E, n), dtype=torch.float64, device=dev), summary=torch.empty((E, n), dtype=torch.float64, device=dev),
-                    scratch=torch.empty((max(1, hip.replay_set_scratch_doubles(self._table, E)),), dtype=torch.float64, device=dev))
+        dev, C, n = self._dev, self.n_super_cycles, hip.REPLAY_PRECISE_SUMMARY_DOUBLES if precise else hip.REPLAY_SUMMARY_DOUBLES
+        n_scratch = hip.replay_set_precise_scratch_doubles(self._table, E) if precise else hip.replay_set_scratch_doubles(self._table, E)
+        buf = dict(pos=torch.empty((C, E, 2), dtype=torch.int32, device=dev), move=torch.empty((C, E, 2), dtype=torch.int32, device=dev),
+                   track_summary=torch.empty((self.T, E, n), dtype=torch.float64, device=dev), summary=torch.empty((E, n), dtype=torch.float64, device=dev),
+                   scratch=torch.empty((max(1, n_scratch),), dtype=torch.float64, device=dev))
+        if precise:
+            buf["precise"] = True
+        return buf
 
     def _enqueue_objective(self, targets: Targets, kind: int, buf: dict, out, track_out=None, stop_dev=None):
+        """`kind`: _objective_kind's value; a precise objective where `buf` holds the precise buffers (_objective_buffers(E, precise=True))."""
         sp = self._super
+        if "precise" in buf:
+            hip.replay_set_precise_objective(sp._cfg, self._table, self._frames_table, KINDS[targets.kind], int(targets.E), sp.track, targets.a, targets.b,
+                                             targets.valid, sp._share, buf["pos"], buf["move"], 0, buf["track_summary"], buf["summary"], buf["scratch"],
+                                             buf["scratch"].numel(), kind, out, track_out, stop_dev, stream=sp._stream())
+            return
         hip.replay_set_objective(sp._cfg, self._table, KINDS[targets.kind], int(targets.E), sp.track, targets.a, targets.b, targets.valid, sp._share, buf["pos"],
                                  buf["move"], buf["track_summary"], buf["summary"], buf["scratch"], buf["scratch"].numel(), kind, out, track_out, stop_dev,
                                  stream=sp._stream())
@@ -957,14 +1017,15 @@ class ReplaySet:
     def objective(self, targets: Targets, kind: str = "trimmed_bbox_error", per_track: bool = False):
         """The closed-loop error of every experiment of `targets`, pooled over the tracks, as a device float64 [E] tensor, enqueued on the current torch
         stream (no synchronisation): the division of `run(targets).summary`'s slots, bit for bit.  `per_track`: instead the [T, E] tensor of each
-        track's own error, `rs.replay(t).objective`'s bits.  The precise objectives are `rs.replay(t)`'s."""
+        track's own error, `rs.replay(t).objective`'s bits.  After `attach_frames` also the names of PRECISE_OBJECTIVES: the division of
+        `run(targets, precise=True).precise_summary`'s slots, pooled over the rows of all tracks' logs."""
         import torch
 
         E, k = self._check_targets(targets), self._objective_kind(kind)
         with torch.cuda.device(self._dev):
             out = torch.empty((E,), dtype=torch.float64, device=self._dev)
             each = torch.empty((self.T, E), dtype=torch.float64, device=self._dev) if per_track else None
-            self._enqueue_objective(targets, k, self._objective_buffers(E), out, each)
+            self._enqueue_objective(targets, k, self._objective_buffers(E, kind in PRECISE_OBJECTIVES), out, each)
         return each if per_track else out
 
     def optimize_polyfit(self, degree: int, sample_times, objective: str = "trimmed_bbox_error", **swarm) -> SwarmResult:
@@ -976,13 +1037,18 @@ class ReplaySet:
         return self._super.to_config(degree, weights, sample_times)
 
     # ------------------------------------------------------------------ the loop
-    def run(self, targets: Targets, precise: bool = False, analysis: Optional[Analysis] = None) -> ReplaySetResult:
-        """Replay the E experiments of `targets` on every track: scan, rows reduction, one synchronisation.  Frames, logs and `analysis` belong to one
-        track: they are `rs.replay(t).run`'s."""
+    def run(self, targets: Targets, precise: bool = False, analysis: Optional[Analysis] = None, per_row_errors: bool = False,
+            _max_crop_px: int = 0) -> ReplaySetResult:
+        """Replay the E experiments of `targets` on every track: scan, rows reduction, one synchronisation.  `precise` (after `attach_frames`): also
+        the precise error of every experiment on every track's frames (`precise_summary` pooled, `track_precise_summary[t]`; with `per_row_errors`
+        `precise_error[t]` and `precise_counts[t]`).  Logs and `analysis` belong to one track: they are `rs.replay(t).run`'s.
+        `_max_crop_px` (tests): the table limit of wtk_replay_set_precise, 0 = the default; results do not depend on it."""
         import torch
 
-        if precise or analysis is not None:
+        if analysis is not None:
             raise ValueError("the precise error and the analysis are per track: use rs.replay(t).run(..., precise=True / analysis=spec)")
+        if precise:
+            self._need_frames()
         E, sp = self._check_targets(targets), self._super
         with torch.cuda.device(self._dev):
             stream, buf = sp._stream(), self._objective_buffers(E)
@@ -990,11 +1056,28 @@ class ReplaySet:
                                 stream=stream)
             hip.replay_set_rows(sp._cfg, self._table, E, sp.track, sp._share, buf["pos"], buf["move"], buf["track_summary"], buf["summary"], buf["scratch"],
                                 buf["scratch"].numel(), stream=stream)
+            if precise:
+                n, rows = hip.REPLAY_PRECISE_SUMMARY_DOUBLES, self._frames_table.n_rows
+                ptrack, ppooled = torch.empty((self.T, E, n), dtype=torch.float64, device=self._dev), torch.empty((E, n), dtype=torch.float64, device=self._dev)
+                pscratch = torch.empty((max(1, hip.replay_set_precise_scratch_doubles(self._table, E)),), dtype=torch.float64, device=self._dev)
+                perr = torch.empty((E, rows), dtype=torch.float64, device=self._dev) if per_row_errors else None
+                pcounts = torch.empty((E, rows, 2), dtype=torch.int32, device=self._dev) if per_row_errors else None
+                hip.replay_set_precise(sp._cfg, self._table, self._frames_table, E, sp.track, sp._share, buf["pos"], buf["move"], int(_max_crop_px), perr,
+                                       pcounts, ptrack, ppooled, pscratch, pscratch.numel(), stream=stream)
             torch.cuda.current_stream(self._dev).synchronize()  # the one host synchronisation
             per = buf["track_summary"].cpu().numpy()
             cut = lambda x, t: x[self.cyc_off[t]:self.cyc_off[t] + self.n_cycles[t]].permute(1, 0, 2).contiguous().cpu().numpy()  # noqa: E731
-            return ReplaySetResult(_summary_of(buf["summary"].cpu().numpy()), [_summary_of(per[t]) for t in range(self.T)],
-                                   [cut(buf["move"], t) for t in range(self.T)], [cut(buf["pos"], t) for t in range(self.T)])
+            res = ReplaySetResult(_summary_of(buf["summary"].cpu().numpy()), [_summary_of(per[t]) for t in range(self.T)],
+                                  [cut(buf["move"], t) for t in range(self.T)], [cut(buf["pos"], t) for t in range(self.T)])
+            if precise:
+                pper = ptrack.cpu().numpy()
+                res.precise_summary, res.track_precise_summary = _precise_summary_of(ppooled.cpu().numpy()), [_precise_summary_of(pper[t]) for t in range(self.T)]
+                if per_row_errors:
+                    row0 = np.concatenate([[0], np.cumsum(self.n_rows)])
+                    err, counts = perr.cpu().numpy(), pcounts.cpu().numpy()
+                    res.precise_error = [np.ascontiguousarray(err[:, row0[t]:row0[t + 1]]) for t in range(self.T)]
+                    res.precise_counts = [np.ascontiguousarray(counts[:, row0[t]:row0[t + 1]]) for t in range(self.T)]
+            return res
 
 
 def _summary_of(s: np.ndarray) -> Summary:
