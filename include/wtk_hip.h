@@ -236,8 +236,12 @@ void wtk_yolo_destroy(wtk_yolo *h);
  * forward pass: ~0.1 s once; WTK_SK_AUTOTUNE=0 keeps the cost model's); the choice changes no result bit.
  * Launches are eager.
  * The plan never changes per call: within a handle a frame's logits do not depend on the batch it arrives in.  Both plans meet the
- * same tolerances against the fp32 restatement; they are not bit-identical to each other (K is summed in a different order). */
-typedef enum wtk_plan { WTK_PLAN_AUTO = 0, WTK_PLAN_THROUGHPUT = 1, WTK_PLAN_LATENCY = 2 } wtk_plan;
+ * same tolerances against the fp32 restatement; they are not bit-identical to each other (K is summed in a different order).
+ * WTK_PLAN_C2F_TAIL is a flag, or'ed into any of the three: on WTK_F16X3 throughput-plan handles of more than 16 frames the first C2f's closing 1x1
+ * (model.2.cv2) runs inside the kernel of the 3x3 before it (model.2.m.0.cv2), whose output then never reaches memory — one launch and 0.64 GB of
+ * traffic per 64 frames at 640 x 640 fewer, every result bit kept.  Other handles ignore it.  A flag and not the default because it changes what such a
+ * handle launches; the Python binding always sets it.  WTK_NO_C2F_SPLIT_TAIL=1 in the environment overrides it (A/B). */
+typedef enum wtk_plan { WTK_PLAN_AUTO = 0, WTK_PLAN_THROUGHPUT = 1, WTK_PLAN_LATENCY = 2, WTK_PLAN_C2F_TAIL = 0x100 } wtk_plan;
 int wtk_yolo_create_planned(wtk_yolo **out, const wtk_yolo_desc *desc, int32_t plan);
 /* The plan a handle runs on: WTK_PLAN_THROUGHPUT or WTK_PLAN_LATENCY (-1 on a null handle). */
 int wtk_yolo_plan(wtk_yolo *h);

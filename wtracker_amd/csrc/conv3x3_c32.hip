@@ -338,6 +338,240 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c32_split_kernel(const HaloArg
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// The split kernel above with the C2f block's closing 1x1 (model.2.cv2: 96 -> 64 channels, SiLU) in its epilogue: the bottleneck output
+// z = SiLU(conv) + y1 never reaches HBM, and y1 is fetched once.  After the epilogue's arithmetic lane (lr, lg) holds channels 8 lg .. 8 lg + 7
+// of pixel lr of tile j — the B fragment of v_mfma_f32_16x16x32_f16 for a 32-channel K block — and so do the residual registers (y1) and a
+// second pair of 16-byte loads 32 channels lower (y0): the 1x1's three K blocks [y0 | y1 | z] are in registers in fragment form, no pixel
+// goes through LDS and no wave needs another wave's data.  Arithmetic and K order are conv_igemm_kernel's split form (per block hi.hi into
+// c2, lo_w.hi then hi_w.lo into c2l, accumulators from the bias), so the result has the bits of the two launches this replaces.
+// LDS: the 1x1's weights are 3 blocks x 64 couts x 128-byte rows = 24 KB, which two 80 KB blocks per CU cannot both add.  One 512-thread
+// block per CU instead: two four-wave halves, each with the plain kernel's tile loop on its own 44 KB window buffer and its own tiles, and
+// ONE copy of the weights (36 + 24 KB): 148 KB.  A barrier now spans both halves; every wave executes the same number of them (a half
+// without a tile in the last round only keeps the count).  The halves run in lock step: with half 1 one barrier behind half 0 (one half
+// multiplying while the other is in its epilogue) the pass measured the same (profiles/r23_notes.md), so the simpler form stays.
+// Weight rows of the 1x1: LDS row = block * 64 + cout, key and lane -> row map of a 16-cout-per-lane tile (tile_weight_key<16>): lane (lr, lg)
+// ends up with couts 16 lg .. 16 lg + 15 of its pixel.
+__global__ __launch_bounds__(512) void conv3x3_c32_split_kernel_cv2(const HaloArgs a) {
+    constexpr int TC = 2, TP = 4, NV = 8, TC2 = 4, NV2 = 16;
+    __shared__ __attribute__((aligned(16))) char win2[2][kSplitRows * 128];
+    __shared__ __attribute__((aligned(16))) char wts[9 * 32 * 128];
+    __shared__ __attribute__((aligned(16))) char wts2[3 * 64 * 128];
+    __shared__ __attribute__((aligned(16))) float bias2s[64];
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave8 = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int half = wave8 >> 2, wave = wave8 & 3; // the half of the block, the wave inside it (= pixel quarter of the half's tile)
+    const int lr = lane & 15, lg = lane >> 4;
+    char *win = win2[half];
+
+    // ---- this half's tiles: XCD x owns tiles [start, start + count), the halves of its blocks take them round-robin
+    int ntiles = a.N * a.strips * a.blocks_per_strip;
+    if (a.n_dyn) ntiles = min(max(*a.n_dyn, 0), a.N) * a.strips * a.blocks_per_strip;
+    const int per = 2 * (a.grid >> 3); // halves per XCD
+    const XcdRange xr = xcd_range(blockIdx.x, a.grid, ntiles);
+    const int start = xr.first, count = xr.count;
+    const int t0 = 2 * (int)(blockIdx.x >> 3);
+    if (t0 >= count) return; // block-uniform
+    const int rounds = (count - t0 + per - 1) / per; // tiles of half 0 = barrier rounds of the block (half 1 has as many or one fewer)
+    int t = t0 + half;
+
+    const int pitch = a.pitch;
+    const int halo_rows = kBM + 2 * pitch + 2;
+    const _Float16 *wgt = reinterpret_cast<const _Float16 *>(a.w);
+    const _Float16 *wgt2 = reinterpret_cast<const _Float16 *>(a.tail_w);
+    _Float16 *tout = reinterpret_cast<_Float16 *>(a.tail_out);
+    const _Float16 *res = reinterpret_cast<const _Float16 *>(a.res);
+    const int cb = lg * NV, cb2 = lg * NV2; // this lane's eight channels of the 3x3, its sixteen couts of the 1x1
+
+    struct Tile {
+        int n, xs, o0;
+    };
+    auto geometry = [&](int tile) {
+        unsigned v = (unsigned)tile;
+        unsigned q = fdiv(v, a.d_bps);
+        Tile g;
+        g.o0 = (int)(v - q * (unsigned)a.blocks_per_strip) * kBM;
+        v = q;
+        q = fdiv(v, a.d_strips);
+        g.xs = (int)(v - q * (unsigned)a.strips) * a.S;
+        g.n = (int)q;
+        return g;
+    };
+    auto pixel = [&](const Tile &g, int j) -> long long {
+        const unsigned o = (unsigned)(g.o0 + wave * 64 + j * 16 + lr);
+        const unsigned y = fdiv(o, a.d_pitch);
+        const int x = (int)(o - y * (unsigned)pitch);
+        if ((int)y >= a.H || x >= a.S || g.xs + x >= a.W) return -1;
+        return ((long long)g.n * a.H + (int)y) * a.W + g.xs + x;
+    };
+    // The window, in buffer form (lds_dma_buf: the resource spans the tile's image, rows outside it take the out-of-range offset and land
+    // zeros).  hipcc does not see these requests, which is the point: the epilogue that follows them reads registers and the 1x1's weights
+    // in LDS, and must not be made to wait for the next window.  The barrier that publishes a window is preceded by s_waitcnt vmcnt(0).
+    auto request_window = [&](const Tile &g) {
+        const rsrc_t rs = make_rsrc(reinterpret_cast<const _Float16 *>(a.in) + (long long)g.n * a.H * a.W * a.in_ld + a.in_coff);
+#pragma unroll
+        for (int k = 0; k < kSplitPiecesPerWave; ++k) {
+            const int piece = wave + 4 * k;
+            const int hr = piece * 8 + (lane >> 3);
+            const int lc = tile_src_chunk(lane & 7, tile_pixel_key(hr));
+            const unsigned flat = (unsigned)(g.o0 + hr);
+            const unsigned r = fdiv(flat, a.d_pitch);
+            const int cc = (int)(flat - r * (unsigned)pitch);
+            const int iy = (int)r - 1, ix = g.xs + cc - 1;
+            const bool ok = hr < halo_rows && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
+            lds_dma_buf(rs, ok ? (unsigned)(((iy * a.W + ix) * a.in_ld + lc * 8) * 2) : 0xffffffffu, 0u, win + piece * 1024);
+        }
+    };
+    // y0 and y1 of a tile's pixels, raw (junk positions read pixel 0): [j][0] = eight hi halves, [j][1] = their lo halves; y0 lies one
+    // 32-channel block (64 pseudo-channels) below the residual y1
+    auto request_y = [&](const Tile &g, half8 (&y0)[TP][2], half8 (&y1)[TP][2]) {
+#pragma unroll
+        for (int j = 0; j < TP; ++j) {
+            const long long pix = pixel(g, j);
+            const _Float16 *p = res + (pix < 0 ? 0 : pix) * a.res_ld + a.res_coff + cb;
+            y0[j][0] = *reinterpret_cast<const half8 *>(p - 64);
+            y0[j][1] = *reinterpret_cast<const half8 *>(p - 32);
+            y1[j][0] = *reinterpret_cast<const half8 *>(p);
+            y1[j][1] = *reinterpret_cast<const half8 *>(p + 32);
+        }
+    };
+
+    // ---- both weight sets, once, by all eight waves: the nine 3x3 slabs (LDS row = tap*32 + cout, 36 pieces), the 1x1's three K blocks (24 pieces)
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        const int piece = wave8 + 8 * k;
+        if (piece < 36) {
+            const int row = piece * 8 + (lane >> 3);
+            const int tap = row >> 5, co = row & 31;
+            const int lc = tile_src_chunk(lane & 7, tile_weight_key<NV>(co));
+            lds_dma16(reinterpret_cast<const char *>(wgt + (long long)co * a.Kpad + tap * 64 + lc * 8), wts + piece * 1024);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int piece = wave8 + 8 * k;
+        const int row = piece * 8 + (lane >> 3);
+        const int blk = row >> 6, co = row & 63;
+        const int lc = tile_src_chunk(lane & 7, tile_weight_key<NV2>(co));
+        lds_dma16(reinterpret_cast<const char *>(wgt2 + (long long)co * a.tail_kpad + blk * 64 + lc * 8), wts2 + piece * 1024);
+    }
+    Tile cur = geometry(start + min(t, count - 1));
+    if (t < count) request_window(cur);
+    if (tid < 64) bias2s[tid] = a.tail_bias[tid];
+
+    floatx4 bias4[TC];
+#pragma unroll
+    for (int i = 0; i < TC; ++i) bias4[i] = (floatx4){a.bias[cb + i * 4 + 0], a.bias[cb + i * 4 + 1], a.bias[cb + i * 4 + 2], a.bias[cb + i * 4 + 3]};
+
+    const int wrow_l = (lr >> 2) * NV + (lr & 3); // + 4*i per cout tile, + tap*32
+    const unsigned wfrag0 = tile_chunk_off(wrow_l, lg, tile_weight_key<NV>(wrow_l));
+    const int wrow2_l = (lr >> 2) * NV2 + (lr & 3); // + 4*i per cout tile, + block*64
+    const unsigned wfrag2 = tile_chunk_off(wrow2_l, lg, tile_weight_key<NV2>(wrow2_l));
+    const int prow0 = wave * 64 + lr;
+
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads(); // both weight sets, the 1x1's bias and both halves' first windows have landed
+
+    for (int round = 0; round < rounds; ++round) {
+        const bool active = t < count; // half-uniform; false only for half 1 in the last round
+        floatx4 acc[TC][TP], acc1[TC][TP];
+        half8 y0[TP][2], y1[TP][2];
+        if (active) {
+            request_y(cur, y0, y1); // in flight during the multiply phase
+#pragma unroll
+            for (int i = 0; i < TC; ++i)
+#pragma unroll
+                for (int j = 0; j < TP; ++j) acc[i][j] = bias4[i], acc1[i][j] = (floatx4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int tap = 0; tap < 9; ++tap) {
+                const int base = prow0 + (tap / 3) * pitch + (tap % 3);
+                const unsigned pa = tile_pixel_off(base, lg); // tiles j: + j*2048 (key unchanged); lo halves: ^ 64
+                half8 ph[TP], pl[TP], wh[TC], wl[TC];
+#pragma unroll
+                for (int j = 0; j < TP; ++j) ph[j] = *reinterpret_cast<const half8 *>(win + pa + j * 2048);
+#pragma unroll
+                for (int i = 0; i < TC; ++i) wh[i] = *reinterpret_cast<const half8 *>(wts + tap * 4096 + wfrag0 + i * 512);
+#pragma unroll
+                for (int i = 0; i < TC; ++i) wl[i] = *reinterpret_cast<const half8 *>(wts + tap * 4096 + tile_khalf1(wfrag0) + i * 512);
+#pragma unroll
+                for (int j = 0; j < TP; ++j) pl[j] = *reinterpret_cast<const half8 *>(win + tile_khalf1(pa) + j * 2048);
+#pragma unroll
+                for (int i = 0; i < TC; ++i)
+#pragma unroll
+                    for (int j = 0; j < TP; ++j) {
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[i], ph[j], acc[i][j], 0, 0, 0);
+                        acc1[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[i], ph[j], acc1[i][j], 0, 0, 0);
+                    }
+#pragma unroll
+                for (int i = 0; i < TC; ++i)
+#pragma unroll
+                    for (int j = 0; j < TP; ++j) acc1[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[i], pl[j], acc1[i][j], 0, 0, 0);
+            }
+            // y0 / y1 are taken here, behind the multiply phase that hid their latency: from now on they are values in registers to hipcc, and no
+            // wait for them can land behind the window requests below
+#pragma unroll
+            for (int j = 0; j < TP; ++j) asm volatile("" : "+v"(y0[j][0]), "+v"(y0[j][1]), "+v"(y1[j][0]), "+v"(y1[j][1]));
+        }
+
+        __syncthreads(); // this half is done reading its window: the next tile's requests go out before this tile's epilogue
+        if (active) {
+            t += per;
+            Tile nxt = cur;
+            if (t < count) { // half-uniform
+                nxt = geometry(start + t);
+                request_window(nxt);
+            }
+
+            // ---- epilogue, one pixel tile at a time: z in registers, then the 1x1 over [y0 | y1 | z] for the lane's 16 couts
+#pragma unroll
+            for (int j = 0; j < TP; ++j) {
+                half8 zh, zl;
+                {
+                    float v[NV];
+#pragma unroll
+                    for (int i = 0; i < TC; ++i)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) v[i * 4 + r] = wtk_split_value(acc[i][j][r], acc1[i][j][r]);
+                    wtk_silu_scaled_run<NV>(v);
+#pragma unroll
+                    for (int e = 0; e < NV; ++e) v[e] += wtk_split_value((float)y1[j][0][e], (float)y1[j][1][e]);
+                    split_pack8(v, zh, zl); // what wtk_split_store would have written and the 1x1 read back
+                }
+                floatx4 c2[TC2], c2l[TC2];
+#pragma unroll
+                for (int i = 0; i < TC2; ++i) c2[i] = *reinterpret_cast<const floatx4 *>(bias2s + cb2 + i * 4), c2l[i] = (floatx4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int blk = 0; blk < 3; ++blk) { // K order of the concat: y0, y1, z
+                    const half8 ph = blk == 0 ? y0[j][0] : blk == 1 ? y1[j][0] : zh;
+                    const half8 pl = blk == 0 ? y0[j][1] : blk == 1 ? y1[j][1] : zl;
+#pragma unroll
+                    for (int i = 0; i < TC2; ++i) {
+                        const half8 wh = *reinterpret_cast<const half8 *>(wts2 + blk * 8192 + wfrag2 + i * 512);
+                        const half8 wl = *reinterpret_cast<const half8 *>(wts2 + blk * 8192 + tile_khalf1(wfrag2) + i * 512);
+                        c2[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, ph, c2[i], 0, 0, 0);
+                        c2l[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, ph, c2l[i], 0, 0, 0);
+                        c2l[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, pl, c2l[i], 0, 0, 0);
+                    }
+                }
+                const long long pix = pixel(cur, j);
+                if (pix >= 0) {
+                    float v2[NV2];
+#pragma unroll
+                    for (int i = 0; i < TC2; ++i)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) v2[i * 4 + r] = wtk_split_value(c2[i][r], c2l[i][r]);
+                    wtk_silu_scaled_run<NV2>(v2);
+                    wtk_split_store<NV2>(tout + pix * a.tail_ld + a.tail_coff, cb2, v2);
+                }
+            }
+            cur = nxt;
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads(); // the next tile's window has landed
+    }
+}
+
 } // namespace
 
 bool c32_eligible(int k, int stride, int cin, int cout_stored, int is_f16, bool has_out2) {
@@ -368,8 +602,11 @@ bool c32_split_eligible(int k, int stride, int cin, int cout, bool plain_out) { 
 int c32_split_rows_max() { return kSplitRows; }
 
 hipError_t launch_conv3x3_c32_split(HaloArgs a, hipStream_t stream) {
-    if (a.Cin != 64 || a.Cout != 32 || a.CoutPad != 32 || a.out2 || a.tail_w || a.Kpad != 9 * 64) return hipErrorInvalidValue;
+    if (a.Cin != 64 || a.Cout != 32 || a.CoutPad != 32 || a.out2 || a.Kpad != 9 * 64) return hipErrorInvalidValue;
     if (a.in_ld % 64 || a.in_coff % 64 || a.out_ld % 64 || a.out_coff % 64) return hipErrorInvalidValue;
+    // fused 1x1 (conv3x3_c32_split_kernel_cv2): 96 -> 64 channels with SiLU over [y0 | y1 | z], y1 = the residual, y0 the 32 channels below it, split output
+    if (a.tail_w && 2LL * a.H * a.W * a.in_ld >= 0x7fffffffLL) return hipErrorInvalidValue; // that kernel addresses an image's window rows by 32-bit byte offsets
+    if (a.tail_w && (!a.res || a.res_coff < 64 || !a.act || a.tail_kpad != 3 * 64 || a.tail_cout != 64 || a.tail_f32 || a.tail_ld % 64 || a.tail_coff % 64)) return hipErrorInvalidValue;
     if (a.res && (a.res_ld % 64 || a.res_coff % 64)) return hipErrorInvalidValue;
     if (a.pitch != a.S + 2 || kBM + 2 * a.pitch + 2 > kSplitRows || a.strips * a.S < a.W) return hipErrorInvalidValue;
     if (a.blocks_per_strip * kBM < a.H * a.pitch) return hipErrorInvalidValue;
@@ -380,6 +617,12 @@ hipError_t launch_conv3x3_c32_split(HaloArgs a, hipStream_t stream) {
     a.d_pitch = make_fastdiv((unsigned)a.pitch);
     // two persistent blocks per CU (80 KB of LDS each), a multiple of 8 so that every XCD gets the same number of them
     const long long cus = a.persist_cus > 0 ? a.persist_cus : 256;
+    if (a.tail_w) { // one 512-thread block per CU (148 KB of LDS), each half of a block a tile walker
+        const long long blocks2 = std::max(8LL, std::min(cus, ((tiles + 1) / 2 + 7) / 8 * 8) / 8 * 8);
+        a.grid = (int)blocks2;
+        hipLaunchKernelGGL(conv3x3_c32_split_kernel_cv2, dim3((unsigned)blocks2), dim3(512), 0, stream, a);
+        return hipGetLastError();
+    }
     long long blocks = std::min(2 * cus, (tiles + 7) / 8 * 8);
     blocks = std::max(8LL, blocks / 8 * 8);
     a.grid = (int)blocks;

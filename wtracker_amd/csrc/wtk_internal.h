@@ -100,7 +100,7 @@ struct Op {
     int out_buf = -1, out_coff = 0;
     int out2_buf = -1, out2_coff = 0;
     int res_buf = -1, res_coff = 0;
-    int tail_op = -1; // index of a 1x1 op (64 -> 64, no activation) computed in this op's epilogue (conv3x3_halo fused tail)
+    int tail_op = -1; // index of a 1x1 op computed in this op's epilogue (the Detect towers' last 1x1 in conv3x3_halo, model.4.cv1 in conv_igemm, model.2.cv2 in conv3x3_c32's split form)
     int folded = 0;   // 1: this op runs inside another op's kernel
     int in2_buf = -1, in2_coff = 0, in2_split = 0; // half-resolution source of the first in2_split input channels (ConvArgs::in2)
     int cout = 0, cout_pad = 0, k = 1, stride = 1, act = 1;
@@ -189,6 +189,8 @@ struct wtk_yolo {
     int use_wide = 1;  // WTK_NO_WIDE_1X1=1: every 1x1 conv through conv_igemm_kernel (A/B switch)
     int use_c2f = 0;   // ops[3..5] (model.2.m.0.cv1, m.0.cv2, model.2.cv2) run as ONE fused kernel (c2f_fused.hip)
     int use_front = 0; // ops[0..2] (stem, model.1, model.2.cv1) run as ONE fused kernel (front_fused.hip)
+    int c2f_tail_asked = 0; // the create call carried WTK_PLAN_C2F_TAIL
+    int c2f_tail_op = -1; // f16x3: the op (model.2.m.0.cv2) whose kernel also runs model.2.cv2 and does not store its own output z (wtk_plan.hip: fuse_c2f_split_tail)
     // Sparse Detect box towers (wtk_run.hip: resolve_sparse; DESIGN.md "Sparse box towers").  det[i]: the ops of level i's towers that a sparse call treats
     // differently — op0 the shared first 3x3 of both towers (run as its class half in place, as its box half behind the head's selection), box1 / box2 the rest
     // of the box tower.  The live mask, sel_anchor and sel_score belong to the handle (two lanes run two handles concurrently); the mask lies behind the zero

@@ -331,6 +331,8 @@ hipError_t launch_conv3x3_c32(HaloArgs a, hipStream_t stream);
 // ... and the split-fp16 form of the 32 -> 32 channel layers (one 128-byte [hi32 | lo32] row per pixel); real channel counts here
 bool c32_split_eligible(int k, int stride, int cin, int cout, bool plain_out);
 int c32_split_rows_max();
+// With tail_w set (tail_cout 64, tail_kpad 3 * 64, split tail_out): a C2f's closing 1x1 with SiLU over [y0 | y1 | z] in the epilogue, where z is this conv's
+// output (not stored), y1 its residual and y0 the 32 channels below y1 in the same buffer (conv3x3_c32_split_kernel_cv2)
 hipError_t launch_conv3x3_c32_split(HaloArgs a, hipStream_t stream); // channel counts / offsets but Cout in pseudo-channels
 
 // ---------------------------------------------------------------------------------------------

@@ -403,6 +403,7 @@ struct PlanSwitches {
     bool sk_finish;            // WTK_SK_FINISH=1
     bool no_fused_front;       // WTK_NO_FUSED_FRONT=1
     bool no_fused_c2f;         // WTK_NO_FUSED_C2F=1
+    bool no_c2f_split_tail;    // WTK_NO_C2F_SPLIT_TAIL=1
 };
 
 // Every library-side switch of a handle, read once when it is created: the handle's own fields directly, the rest into PlanSwitches.
@@ -437,6 +438,7 @@ PlanSwitches read_switches(wtk_yolo *h) {
     s.sk_finish = env_int("WTK_SK_FINISH", 0) == 1;
     s.no_fused_front = env_int("WTK_NO_FUSED_FRONT", 0) == 1;
     s.no_fused_c2f = env_int("WTK_NO_FUSED_C2F", 0) == 1;
+    s.no_c2f_split_tail = env_int("WTK_NO_C2F_SPLIT_TAIL", 0) == 1;
     return s;
 }
 } // namespace
@@ -860,6 +862,40 @@ static void choose_fused_front(wtk_yolo *h, const PlanSwitches &sw) {
     }
 }
 
+// f16x3, throughput plan, handles above 16 frames: the first C2f's closing 1x1 (model.2.cv2, 96 -> 64 channels over [y0 | y1 | z]) runs in the epilogue of the
+// bottleneck's second 3x3 (model.2.m.0.cv2, which forms z = SiLU(conv) + y1) — conv3x3_c32.hip: conv3x3_c32_split_kernel_cv2.  z, which nobody else reads,
+// is not stored, and y1 is fetched once: 650 MB of 13.4 GB per 64 frames at 640 x 640, one launch fewer.  Handles of at most 16 frames and latency-plan
+// handles keep every launch they had (tests/golden/launch_trace.json pins them).  The caller asks for it in the create call (WTK_PLAN_C2F_TAIL or'ed into
+// the plan, include/wtk_hip.h; hip.HipYolo always does): a create call without the flag plans what it planned before, which is what
+// tests/golden/launch_trace_full.json records for the large f16x3 handles.  WTK_NO_C2F_SPLIT_TAIL=1 keeps the two launches on a handle that asked (A/B
+// switch, and the reference of tests/test_gpu_c2f_split_tail.py).  A test hook that reads z first runs the unfused launch (wtk_run.hip: complete_c2f_z).
+static void fuse_c2f_split_tail(wtk_yolo *h, const PlanSwitches &sw) {
+    if (!h->c2f_tail_asked || !h->split || h->latency || h->max_batch <= 16 || sw.no_c2f_split_tail || h->ops.size() <= 6 || h->dims.n[0] != 1) return;
+    // ops[2..5] are model.2.cv1, m.0.cv1, m.0.cv2 and model.2.cv2 by construction
+    Op &cv1 = h->ops[2], &m1 = h->ops[3], &m2 = h->ops[4], &cv2 = h->ops[5];
+    if (cv1.kind != OP_CONV || m1.kind != OP_CONV || m2.kind != OP_CONV || cv2.kind != OP_CONV) return;
+    const int cat = cv2.in_buf, y0 = cv2.in_coff;
+    // hidden width 32, one bottleneck with a shortcut, both 3x3 convs on conv3x3_c32_split_kernel
+    if (m1.halo != 2 || m2.halo != 2 || m1.sk || m2.sk || cv2.sk || m2.cin != 32 || m2.cout != 32 || !m2.act || m2.tail_op >= 0 || m2.folded || m2.out2_buf >= 0) return;
+    if (cv1.out_buf != cat || cv1.out_coff != y0 || m2.res_buf != cat || m2.res_coff != y0 + 32 || m2.out_buf != cat || m2.out_coff != y0 + 64) return;
+    // the plain 96 -> 64 1x1 with SiLU, one destination, split output
+    if (cv2.k != 1 || cv2.stride != 1 || cv2.cin != 96 || cv2.cout != 64 || cv2.cout_pad != 64 || !cv2.act || cv2.out2_buf >= 0 || cv2.res_buf >= 0 || cv2.in2_buf >= 0 ||
+        cv2.folded || cv2.tail_op >= 0 || h->bufs[cv2.out_buf].f32)
+        return;
+    const Buf &tb = h->bufs[m2.in_buf];
+    if (4LL * tb.h * tb.w * tb.C >= 0x7fffffffLL) return; // the fused kernel addresses an image of its input (split: 4 bytes per value) by 32-bit byte offsets
+    for (size_t j = 0; j < h->ops.size(); ++j) { // nobody but cv2 reads z
+        const Op &o = h->ops[j];
+        if (j == 5) continue;
+        if (o.in_buf == cat && o.in_coff < y0 + 96 && o.in_coff + o.cin > y0 + 64) return;
+        if (o.res_buf == cat && o.res_coff < y0 + 96 && o.res_coff + o.cout > y0 + 64) return;
+        if (o.in2_buf == cat) return;
+    }
+    m2.tail_op = 5;
+    cv2.folded = 1;
+    h->c2f_tail_op = 4;
+}
+
 // Activation workspace — every tensor gets its own allocation (288 GB HBM: no liveness reuse needed) —, the output rows and the status word.
 static int alloc_workspace(wtk_yolo *h) {
     for (Buf &b : h->bufs)
@@ -901,6 +937,8 @@ static int alloc_sparse_region(wtk_yolo *h) {
 }
 
 extern "C" int wtk_yolo_create_planned(wtk_yolo **out, const wtk_yolo_desc *d, int32_t plan) {
+    const bool c2f_tail_asked = (plan & WTK_PLAN_C2F_TAIL) != 0; // a flag next to the plan: the rest of `plan` is one of the three plans
+    plan &= ~(int32_t)WTK_PLAN_C2F_TAIL;
     ModelDims dims;
     std::vector<ConvSpec> specs;
     if (validate_desc(out, d, plan, dims, specs)) return 1;
@@ -909,12 +947,14 @@ extern "C" int wtk_yolo_create_planned(wtk_yolo **out, const wtk_yolo_desc *d, i
     std::unique_ptr<wtk_yolo, void (*)(wtk_yolo *)> owner(new wtk_yolo(), wtk_yolo_destroy); // a failed create releases whatever the passes allocated
     wtk_yolo *h = owner.get();
     PlanSwitches sw;
+    h->c2f_tail_asked = c2f_tail_asked;
     if (init_handle(h, d, dims, plan, sw) || build_graph(h, d, specs, sw)) return 1;
     fuse_strided_tails(h, sw);
     for (const Op &op : h->ops) h->macs_per_frame += op.macs_per_image;
     if (mark_split_k(h, sw)) return 1;
     sk_schedule(h);
     choose_fused_front(h, sw);
+    fuse_c2f_split_tail(h, sw);
     if (alloc_workspace(h) || alloc_sparse_region(h)) return 1;
     // streams (side streams, the host entry points' stream) are taken from the process pool at first use: a handle that never runs
     // with side streams (the hybrid's second look) or never sees a host call does not occupy a hardware queue slot

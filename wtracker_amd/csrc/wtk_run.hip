@@ -673,6 +673,18 @@ static int complete_box_towers(wtk_yolo *h) {
     return 0;
 }
 
+// The same for the first C2f's bottleneck output z on a handle that runs model.2.cv2 inside model.2.m.0.cv2's kernel (wtk_plan.hip: fuse_c2f_split_tail):
+// the forward pass never stores z, so the test hook that reads it first runs the unfused launch at its batch size.  Its inputs (m.0.cv1's output, y1 in
+// the concat buffer) still hold the last pass's values, and the plain kernel forms z with the fused kernel's arithmetic.  The device is idle when this is called.
+static int complete_c2f_z(wtk_yolo *h, int B) {
+    Op m2 = h->ops[h->c2f_tail_op];
+    m2.tail_op = -1;
+    ConvLaunch r;
+    if (resolve_conv(h, m2, B, r) || issue_conv(h, m2, r, nullptr)) return 1;
+    HIP_TRY(hipDeviceSynchronize());
+    return 0;
+}
+
 // Enqueue one forward pass on `st`: input (letterbox / view) -> front -> ops or dependency levels -> join the side streams -> head -> profile read-out.
 // No allocation, no synchronisation (profiling mode excepted): safe inside a caller's stream capture.  A pass that is being CAPTURED stays dense: the handle
 // remembers on the host whether its last pass left the box towers sparse (sparse_B, for the debug entry points), and a captured pass runs when its graph is
@@ -965,6 +977,7 @@ extern "C" int wtk_yolo_debug_tensor(wtk_yolo *h, int32_t conv_index, int32_t B,
         const int oi = (int)(op - h->ops.data());
         if (!raw && (oi == h->det[l].op0 || oi == h->det[l].box1 || oi == h->det[l].box2) && complete_box_towers(h)) return 1;
     }
+    if (!raw && h->c2f_tail_op >= 0 && op == &h->ops[h->c2f_tail_op] && complete_c2f_z(h, B)) return 1; // z, which the fused launch does not store
     std::vector<char> tmp(px * b.C * (b.f32 ? 4 : h->esize));
     HIP_TRY(hipMemcpy(tmp.data(), b.ptr, tmp.size(), hipMemcpyDeviceToHost));
     std::vector<float> full(px * b.C);

@@ -852,6 +852,7 @@ def yolo_conv_table(width: float, depth: float, max_channels: int, nc: int) -> l
 
 STATUS_NONFINITE = 1
 PLANS = {"auto": 0, "throughput": 1, "latency": 2}
+PLAN_C2F_TAIL = 0x100  # WTK_PLAN_C2F_TAIL, a flag next to the plan
 
 
 class HipYolo:
@@ -883,7 +884,9 @@ class HipYolo:
         desc = _YoloDesc(device, DTYPES[dtype], int(imgsz[0]), int(imgsz[1]), int(max_batch), nc, width, depth, max_channels,
                          len(table), arr)
         self._h = C.c_void_p()
-        _check(lib.wtk_yolo_create_planned(C.byref(self._h), C.byref(desc), PLANS[plan]), "wtk_yolo_create_planned")
+        # every handle made here asks for model.2.cv2 inside model.2.m.0.cv2's kernel (include/wtk_hip.h: WTK_PLAN_C2F_TAIL; handles it does not apply to ignore it)
+        rc = lib.wtk_yolo_create_planned(C.byref(self._h), C.byref(desc), PLANS[plan] | PLAN_C2F_TAIL)
+        _check(rc, "wtk_yolo_create_planned")
         self.plan = "latency" if lib.wtk_yolo_plan(self._h) == PLANS["latency"] else "throughput"
         self._keep = []  # the library copied everything to the device
         self.imgsz = (int(imgsz[0]), int(imgsz[1]))
