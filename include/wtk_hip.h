@@ -958,6 +958,51 @@ int wtk_replay_analyze(const wtk_replay_config *cfg, const wtk_replay_analysis_c
                        int64_t *stats_dev, double *scratch_dev, int64_t scratch_doubles, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The analysis of a population replayed on a SET of tracks (csrc/replay_set_analysis.hip): what the reference's Plotter
+ * computes from several logs at once (eval/plotter.py:37-40: every log through its own DataAnalyzer.initialize / clean / change_unit, the
+ * cleaned frames concatenated with a log_num column), from a set scan's pos_dev / move_dev.  Log (t, e) is wtk_replay_analyze's experiment e
+ * on track t alone: frame, time, cycle and cycle_step count from the track's own row 0, wrm_speed is NaN on the first `period` rows of every
+ * track, and trim_cycles drops cycle 0 and that log's own largest surviving cycle.
+ *
+ * Per-track outputs (all nullable), each bit-equal to wtk_replay_analyze's output on that track alone, for any E, any T, any place of the track
+ * in the set and any max_lds_rows.  With row0[t] = the sum of R and log0[t] = the sum of n_log over the tracks before t:
+ *   track_describe_dev [T][E][n_cols][5 + Q], track_step_quantiles_dev [T][E][L][n_cols][Q], track_step_count_dev [T][E][L][n_cols] int32,
+ *   track_anomaly_counts_dev [T][E][7] int64, track_stats_dev [T][E][4] int64:  track t's block is the t-th.
+ *   cycle_max_dev, cycle_mean_dev [E][sum n_log][n_cols]:  track t's cycles are the rows log0[t] .. log0[t] + n_log - 1 of every experiment (all
+ *       of it is groupby(["log_num", "cycle"]) of the concatenation).
+ *   anomaly_mask_dev [E][sum R] uint8:  track t's rows are the columns from row0[t] (wtk_replay_set_precise's err_dev layout).
+ * Pooled outputs (all nullable): the statistics over the concatenation of the T cleaned logs of experiment e, in track order.
+ *   describe_dev [E][n_cols][5 + Q], step_quantiles_dev [E][L][n_cols][Q], step_count_dev [E][L][n_cols] int32.  Count, min, max and every
+ *       percentile are exact: the order statistics of the union of the kept non-NaN values under numpy's `linear` rule.  Mean and std in a
+ *       fixed order: sum_t = track t's sum with wtk_replay_analyze's bits; S = (...((sum_0 + sum_1) + sum_2)...) over the tracks that keep a
+ *       value, starting from the first such track's own sum (not from 0.0); N = the sum of the counts; mean = S / N; ss_t = the sum of
+ *       (v - mean)^2 about the POOLED mean in the per-track order, chained the same way; std = sqrt(SS / (N - 1)).  N = 0: NaN but for the
+ *       count; N = 1: std NaN.  T = 1: the per-track bits.
+ *   anomaly_counts_dev [E][7], stats_dev [E][4] int64: integer sums over the tracks (distinct cycles: distinct (log_num, cycle) pairs).
+ * precise_rows_dev (nullable) [E][sum R]: the precise_error column, unrounded: wtk_replay_set_precise's err_dev.
+ * No floating-point atomics: an experiment gives the same bits alone and in any population; the pooled bits depend on the order of the tracks
+ * through the chain above only.  Segments are sorted in LDS or go through the radix select as for wtk_replay_analyze; the way is chosen per
+ * launch from max_lds_rows (0 = 19960): by the longest track for the per-track launches, by the sum over the tracks for the pooled ones.
+ * Nine launches with every output asked for, whatever T is (DESIGN.md section 28 lists them).  Everything enqueues on `stream`; nothing synchronises or allocates.
+ * scratch_dev: wtk_replay_set_analysis_scratch_doubles(tracks_host, T, cycle_frame_num, E, n_cols, Q) doubles (-1: a bad table or negative
+ *     sizes): the prefix sums row0 / log0, the per-(track, experiment) last cycles and integer counts.
+ * Refused (error code, nothing launched), a track named by its index: everything wtk_replay_set_rows refuses of the track table; everything
+ *     wtk_replay_analyze refuses of the spec (the precise_error column without precise_rows_dev); T E n_cols L or the cycle launch's blocks
+ *     >= 2^31; sum R >= 2^31; scratch too small; a required pointer that is null.
+ * ------------------------------------------------------------------------------------------ */
+int64_t wtk_replay_set_analysis_scratch_doubles(const wtk_replay_set_track *tracks_host, int32_t T, int32_t cycle_frame_num, int32_t E,
+                                                int32_t n_cols, int32_t Q);
+int wtk_replay_set_analyze(const wtk_replay_config *cfg, const wtk_replay_analysis_config *acfg, const wtk_replay_set_track *tracks_host,
+                           const wtk_replay_set_track *tracks_dev, int32_t T, int32_t guard_cycles, int32_t E, const double *track_dev,
+                           int32_t n_super, const double *share_dev, const int32_t *pos_dev, const int32_t *move_dev,
+                           const double *precise_rows_dev, const int32_t *columns_host, int32_t n_cols, const double *percentiles_host,
+                           int32_t Q, int32_t max_lds_rows, double *track_describe_dev, double *cycle_max_dev, double *cycle_mean_dev,
+                           double *track_step_quantiles_dev, int32_t *track_step_count_dev, int64_t *track_anomaly_counts_dev,
+                           uint8_t *anomaly_mask_dev, int64_t *track_stats_dev, double *describe_dev, double *step_quantiles_dev,
+                           int32_t *step_count_dev, int64_t *anomaly_counts_dev, int64_t *stats_dev, double *scratch_dev,
+                           int64_t scratch_doubles, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * The precise tracking error of a replayed population (csrc/replay_precise.hip): ErrorCalculator.calculate_precise
  * (eval/error_calculator.py:64-160) of every (experiment, logged frame) pair of a scan, with wtk_precise_error's counts and bits for the
  * row wtk_replay_rows logs.  frames_dev [n_frames][H][W] gray with n_frames >= R: row r is frame r.  bg_dev [H][W].  A pixel is

@@ -8,8 +8,8 @@ import sys
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libwtk_hip.so")
-SOURCES = ["wtk_api.hip", "wtk_plan.hip", "wtk_run.hip", "wtk_hybrid.hip", "conv_igemm.hip", "conv_sk.hip", "conv1x1_wide.hip", "conv3x3_halo.hip", "conv3x3_ws64.hip", "conv3x3_s2.hip", "conv3x3_c32.hip", "front_fused.hip", "front_fused_split.hip", "c2f_fused.hip", "stem_pool.hip", "head.hip", "mlp.hip", "mlp_train.hip", "mlp_population.hip", "track_ops.hip", "comm.hip", "eval_ops.hip", "polyfit_opt.hip", "replay.hip", "replay_set.hip", "replay_precise.hip", "replay_targets.hip", "replay_yolo.hip", "box_ops.hip", "replay_analysis.hip"]
-HEADERS = ["wtk_kernels.h", "wtk_device.h", "conv3x3_window.h", "conv3x3_halo_tile.h", "wtk_internal.h", "polyfit_solve.h", "eval_device.h", "replay_device.h", "replay_precise_device.h", "mlp_fold.h", "mlp_forward.h", os.path.join("..", "..", "include", "wtk_hip.h")]
+SOURCES = ["wtk_api.hip", "wtk_plan.hip", "wtk_run.hip", "wtk_hybrid.hip", "conv_igemm.hip", "conv_sk.hip", "conv1x1_wide.hip", "conv3x3_halo.hip", "conv3x3_ws64.hip", "conv3x3_s2.hip", "conv3x3_c32.hip", "front_fused.hip", "front_fused_split.hip", "c2f_fused.hip", "stem_pool.hip", "head.hip", "mlp.hip", "mlp_train.hip", "mlp_population.hip", "track_ops.hip", "comm.hip", "eval_ops.hip", "polyfit_opt.hip", "replay.hip", "replay_set.hip", "replay_precise.hip", "replay_targets.hip", "replay_yolo.hip", "box_ops.hip", "replay_analysis.hip", "replay_set_analysis.hip"]
+HEADERS = ["wtk_kernels.h", "wtk_device.h", "conv3x3_window.h", "conv3x3_halo_tile.h", "wtk_internal.h", "polyfit_solve.h", "eval_device.h", "replay_device.h", "replay_precise_device.h", "replay_set_device.h", "replay_analysis_device.h", "mlp_fold.h", "mlp_forward.h", os.path.join("..", "..", "include", "wtk_hip.h")]
 
 
 def _hipcc() -> str:

@@ -21,6 +21,7 @@
 // After the scan that is five launches whatever T is, and the frames of all tracks fill the device together.
 #include "wtk_internal.h"
 #include "replay_precise_device.h"
+#include "replay_set_device.h"
 
 #include <algorithm>
 
@@ -30,31 +31,6 @@ namespace {
 
 constexpr int kScanThreads = 64;
 constexpr int kFinishExperiments = 8; // per block of the finish launch: 8 experiments x 8 lanes, of which kSummary add
-
-struct SetArgs {
-    Geometry g; // x_max / y_max are each track's own
-    const wtk_replay_set_track *tracks; // [T] on the device
-    int T, E, kind;
-    int S; // chunks of all tracks
-    const double *track; // the super-track
-    const double *a, *b;
-    const int *valid;
-    const double *share;
-    int *pos, *move;        // [n_super / L][E][2]
-    double *partial;        // [E][S][kSummary]
-    double *track_summary;  // [T][E][kSummary]
-    double *summary;        // [E][kSummary]
-    double *objective;      // [E] (nullable)
-    double *track_objective; // [T][E] (nullable)
-    int num, den;           // objective = slot num / slot den
-    const int *stop;
-};
-
-__device__ __forceinline__ Geometry track_geometry(const SetArgs &a, const wtk_replay_set_track &tr) {
-    Geometry g = a.g;
-    g.x_max = tr.x_max, g.y_max = tr.y_max;
-    return g;
-}
 
 __global__ __launch_bounds__(kScanThreads) void replay_set_scan_kernel(const SetArgs a) {
     if (a.stop && *a.stop) return;
@@ -152,14 +128,6 @@ __device__ __forceinline__ int track_of_row(const SetPreciseArgs &a, long long r
     return lo;
 }
 
-__device__ __forceinline__ ReplayView track_view(const SetArgs &a, const wtk_replay_set_track &tr) {
-    const long long c0 = (long long)tr.cyc_off * a.E;
-    ReplayView v;
-    v.g = track_geometry(a, tr), v.E = a.E, v.C = tr.n_cycles, v.n_log = tr.n_log, v.R = tr.R;
-    v.track = a.track + 4 * (long long)tr.cyc_off * a.g.L, v.share = a.share, v.pos = a.pos + 2 * c0, v.move = a.move + 2 * c0;
-    return v;
-}
-
 // track t of the set as replay_precise_kernel's arguments: the track's view, frames and threshold; the output bases at the track's first global row
 __device__ __forceinline__ PreciseArgs track_precise(const SetPreciseArgs &a, int t) {
     const wtk_replay_set_frames fr = a.frames[t];
@@ -208,43 +176,6 @@ __global__ __launch_bounds__(kRowThreads) void replay_set_precise_reduce_kernel(
     chunk_reduce(red, acc, a.s.partial + ((long long)e * a.s.S + gs) * kPreciseSummary);
 }
 static_assert((int)kPreciseSummary == (int)kSummary, "replay_set_finish_kernel adds the precise partials too");
-
-// The checks of the table every entry point shares: each track as replay_view sees it (reported with its index), the derived fields, the slots and
-// guards.  Leaves the shared geometry in a.g, the chunk count in a.S and the smallest n_log in min_log.
-int set_view(const char *who, const wtk_replay_config *cfg, const wtk_replay_set_track *host, const wtk_replay_set_track *dev, int32_t T, int32_t guard_cycles,
-             int32_t kind, int32_t E, const double *track_dev, int32_t n_super, const double *share_dev, const int32_t *pos_dev, const int32_t *move_dev, SetArgs &a,
-             int &min_log) {
-    const std::string w(who);
-    if (!cfg || !host || !dev) return fail(w + ": null argument");
-    if (T < 1) return fail(w + ": at least one track (T >= 1)");
-    if (guard_cycles < 0) return fail(w + ": negative guard_cycles");
-    long long chunks = 0, end_before = 0; // end_before: the first cycle behind the slot and guard of the track before
-    min_log = INT32_MAX;
-    for (int t = 0; t < T; ++t) {
-        const wtk_replay_set_track &tr = host[t];
-        const std::string wt = w + ": track " + std::to_string(t);
-        wtk_replay_config c = *cfg;
-        c.num_frames = tr.num_frames, c.frame_w = tr.x_max < INT32_MAX ? tr.x_max + 1 : 0, c.frame_h = tr.y_max < INT32_MAX ? tr.y_max + 1 : 0;
-        c.init_x = tr.init_x, c.init_y = tr.init_y;
-        ReplayView v = {};
-        if (replay_view(wt.c_str(), &c, kind, E, tr.n_cycles, track_dev, tr.n_track, share_dev, pos_dev, move_dev, v)) return 1;
-        if (tr.n_log != v.n_log || tr.R != v.R) return fail(wt + ": n_log and R must be (num_frames - 1) / L and n_log L");
-        if (tr.init_x < 0 || tr.init_x > tr.x_max || tr.init_y < 0 || tr.init_y > tr.y_max) return fail(wt + ": the init position must be clamped to the frame");
-        if (tr.chunk0 != chunks) return fail(wt + ": chunk0 must be the sum of the chunk counts of the tracks before it");
-        if (tr.cyc_off < end_before) return fail(wt + ": its slot overlaps the slot or the guard of the track before it (or cyc_off is negative)");
-        const long long L = v.g.L, slot = std::max<long long>(tr.n_cycles, (tr.n_track + L - 1) / L);
-        end_before = tr.cyc_off + slot + guard_cycles;
-        if (n_super < 0 || n_super % L != 0 || end_before * L > n_super) return fail(wt + ": its slot and guard end beyond the super-track (n_super must be a multiple of L)");
-        chunks += chunk_count(v.R);
-        min_log = std::min(min_log, v.n_log);
-        a.g = v.g;
-    }
-    if (chunks * E > INT32_MAX) return fail(w + ": too many (experiment, chunk) blocks for one launch");
-    if (T > 65535) return fail(w + ": at most 65535 tracks (the scan's grid)");
-    a.tracks = dev, a.T = T, a.E = E, a.kind = kind, a.S = (int)chunks, a.track = track_dev, a.share = share_dev;
-    a.pos = const_cast<int *>(pos_dev), a.move = const_cast<int *>(move_dev);
-    return 0;
-}
 
 int set_targets(const char *who, int32_t kind, const double *a_dev, const double *b_dev, const int32_t *valid_dev, SetArgs &a) {
     const std::string w(who);
@@ -324,6 +255,42 @@ int launch_set_precise(const SetPreciseArgs &p, hipStream_t st) {
 }
 
 } // namespace
+
+// (declared in replay_set_device.h: replay_set_analysis.hip checks its table with it too)
+int wtk::set_view(const char *who, const wtk_replay_config *cfg, const wtk_replay_set_track *host, const wtk_replay_set_track *dev, int32_t T, int32_t guard_cycles,
+             int32_t kind, int32_t E, const double *track_dev, int32_t n_super, const double *share_dev, const int32_t *pos_dev, const int32_t *move_dev, SetArgs &a,
+             int &min_log) {
+    const std::string w(who);
+    if (!cfg || !host || !dev) return fail(w + ": null argument");
+    if (T < 1) return fail(w + ": at least one track (T >= 1)");
+    if (guard_cycles < 0) return fail(w + ": negative guard_cycles");
+    long long chunks = 0, end_before = 0; // end_before: the first cycle behind the slot and guard of the track before
+    min_log = INT32_MAX;
+    for (int t = 0; t < T; ++t) {
+        const wtk_replay_set_track &tr = host[t];
+        const std::string wt = w + ": track " + std::to_string(t);
+        wtk_replay_config c = *cfg;
+        c.num_frames = tr.num_frames, c.frame_w = tr.x_max < INT32_MAX ? tr.x_max + 1 : 0, c.frame_h = tr.y_max < INT32_MAX ? tr.y_max + 1 : 0;
+        c.init_x = tr.init_x, c.init_y = tr.init_y;
+        ReplayView v = {};
+        if (replay_view(wt.c_str(), &c, kind, E, tr.n_cycles, track_dev, tr.n_track, share_dev, pos_dev, move_dev, v)) return 1;
+        if (tr.n_log != v.n_log || tr.R != v.R) return fail(wt + ": n_log and R must be (num_frames - 1) / L and n_log L");
+        if (tr.init_x < 0 || tr.init_x > tr.x_max || tr.init_y < 0 || tr.init_y > tr.y_max) return fail(wt + ": the init position must be clamped to the frame");
+        if (tr.chunk0 != chunks) return fail(wt + ": chunk0 must be the sum of the chunk counts of the tracks before it");
+        if (tr.cyc_off < end_before) return fail(wt + ": its slot overlaps the slot or the guard of the track before it (or cyc_off is negative)");
+        const long long L = v.g.L, slot = std::max<long long>(tr.n_cycles, (tr.n_track + L - 1) / L);
+        end_before = tr.cyc_off + slot + guard_cycles;
+        if (n_super < 0 || n_super % L != 0 || end_before * L > n_super) return fail(wt + ": its slot and guard end beyond the super-track (n_super must be a multiple of L)");
+        chunks += chunk_count(v.R);
+        min_log = std::min(min_log, v.n_log);
+        a.g = v.g;
+    }
+    if (chunks * E > INT32_MAX) return fail(w + ": too many (experiment, chunk) blocks for one launch");
+    if (T > 65535) return fail(w + ": at most 65535 tracks (the scan's grid)");
+    a.tracks = dev, a.T = T, a.E = E, a.kind = kind, a.S = (int)chunks, a.track = track_dev, a.share = share_dev;
+    a.pos = const_cast<int *>(pos_dev), a.move = const_cast<int *>(move_dev);
+    return 0;
+}
 
 extern "C" int wtk_replay_set_scan(const wtk_replay_config *cfg, const wtk_replay_set_track *tracks_host, const wtk_replay_set_track *tracks_dev, int32_t T,
                                    int32_t guard_cycles, int32_t kind, int32_t E, const double *track_dev, int32_t n_super, const double *a_dev,

@@ -185,6 +185,9 @@ SIGNATURES = {
     "wtk_replay_analysis_scratch_doubles": (_i64, [_i32, _i64, _i32, _i32]),
     "wtk_replay_analyze": (_i32, [_pcfg, _pacfg, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                   _vp, _i64, _vp]),
+    "wtk_replay_set_analysis_scratch_doubles": (_i64, [_ptrk, _i32, _i32, _i32, _i32, _i32]),
+    "wtk_replay_set_analyze": (_i32, [_pcfg, _pacfg, _ptrk, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp,
+                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "wtk_replay_precise_scratch_doubles": (_i64, [_i32, _i64]),
     "wtk_replay_precise": (_i32, [_pcfg, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _f64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "wtk_replay_precise_objective": (_i32, [_pcfg, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _f64, _i32, _vp, _vp,
@@ -718,6 +721,28 @@ def replay_analyze(cfg: _ReplayConfig, acfg: _AnalysisConfig, E: int, n_cycles: 
                                      int(max_lds_rows), _ptr(describe_dev), _ptr(cycle_max_dev), _ptr(cycle_mean_dev), _ptr(step_quantiles_dev),
                                      _ptr(step_count_dev), _ptr(anomaly_counts_dev), _ptr(anomaly_mask_dev), _ptr(stats_dev), _ptr(scratch_dev), scratch_doubles,
                                      C.c_void_p(stream)), "wtk_replay_analyze")
+
+
+def replay_set_analysis_scratch_doubles(table: ReplaySetTable, E: int, n_cols: int, Q: int) -> int:
+    return int(load().wtk_replay_set_analysis_scratch_doubles(table.host, table.T, table.L, E, n_cols, Q))
+
+
+def replay_set_analyze(cfg: _ReplayConfig, acfg: _AnalysisConfig, table: ReplaySetTable, E: int, track_dev, share_dev, pos_dev, move_dev, precise_rows_dev,
+                       columns: Sequence[int], percentiles: Sequence[float], max_lds_rows: int, track_outputs: Sequence, pooled_outputs: Sequence, scratch_dev,
+                       scratch_doubles: int, stream: int = 0):
+    """DataAnalyzer's statistics of every (track, experiment) of a set scan and of every experiment over the concatenation of its logs
+    (wtk_replay_set_analyze).  `track_outputs`: the eight per-track device tensors or None, in the header's order: describe [T, E, n_cols, 5 + Q],
+    cycle_max / cycle_mean [E, sum n_log, n_cols], step_quantiles [T, E, L, n_cols, Q], step_count [T, E, L, n_cols] int32, anomaly_counts [T, E, 7]
+    int64, anomaly_mask [E, sum R] uint8, stats [T, E, 4] int64.  `pooled_outputs`: the five pooled ones: describe [E, n_cols, 5 + Q], step_quantiles
+    [E, L, n_cols, Q], step_count [E, L, n_cols] int32, anomaly_counts [E, 7], stats [E, 4] int64.  precise_rows_dev: float64 [E, sum R] or None."""
+    if len(track_outputs) != 8 or len(pooled_outputs) != 5:
+        raise WtkError("wtk_replay_set_analyze takes eight per-track and five pooled outputs (None where one is not wanted)")
+    cols, q = np.ascontiguousarray(columns, dtype=np.int32), np.ascontiguousarray(percentiles, dtype=np.float64)
+    host, dev, T, guard = table._args()
+    _check(load().wtk_replay_set_analyze(C.byref(cfg) if cfg is not None else None, C.byref(acfg) if acfg is not None else None, host, dev, T, guard, E,
+                                         _ptr(track_dev), table.n_super, _ptr(share_dev), _ptr(pos_dev), _ptr(move_dev), _ptr(precise_rows_dev), _ptr(cols),
+                                         len(cols), _ptr(q), len(q), int(max_lds_rows), *(_ptr(t) for t in track_outputs), *(_ptr(t) for t in pooled_outputs),
+                                         _ptr(scratch_dev), scratch_doubles, C.c_void_p(stream)), "wtk_replay_set_analyze")
 
 
 def replay_yolo_step(cfg: _ReplayConfig, n_cycles: int, c: int, xywh_dev, share_dev, pos_dev, move_dev, stream: int = 0):

@@ -58,6 +58,12 @@ and threshold, five launches whatever T is, per-track summaries with `rs.replay(
     rs.objective(tg, "trimmed_precise_error")                           # also per_track=True, optimize_polyfit(..., objective=...), fit(closed_loop=rs, ...)
     rs.run(tg, precise=True).precise_summary                            # .track_precise_summary[t]; per_row_errors=True: .precise_error[t], .precise_counts[t]
 
+The analysis of the set: every log through its own initialize / clean / change_unit, then the statistics of each log and of the
+concatenation of all logs, as the reference's Plotter takes them; a percentile over all recordings is exact, not a combination of per-track ones:
+
+    res = rs.run_analysis(tg, spec)                                     # res.analysis.pooled.describe [E, n_cols, 5 + Q]; .track[t] = rs.replay(t)'s bits
+    rs.analyze(tg, spec)                                                # the same as device tensors, no synchronisation; precise=True: precise_error
+
 There is no CPU fallback: without a visible GPU the constructors raise.  Not covered: `StepMotorController`, DataAnalyzer's `remove_cycle` and
 `save` / `load`, the plots themselves, the YOLO controller's second look (YoloConfig.recheck_margin).
 """
@@ -344,9 +350,22 @@ def _enqueue_analysis(geometry: "LoopGeometry", timing_config, spec: Analysis, E
 
 
 def _analysis_to_host(a: AnalysisResult) -> AnalysisResult:
-    host = lambda t: None if t is None else t.cpu().numpy()  # noqa: E731
+    host = lambda t: None if t is None else np.ascontiguousarray(t.cpu().numpy())  # noqa: E731  (a set's per-track cycle arrays and masks are slices)
     return AnalysisResult(a.columns, a.percentiles, a.n_rows, host(a.describe), host(a.cycle_max), host(a.cycle_mean), host(a.step_quantiles), host(a.step_count),
                           host(a.anomaly_counts), host(a.stats), host(a.anomaly_mask))
+
+
+@dataclass
+class SetAnalysisResult:
+    """The analysis of E experiments replayed on T tracks (`ReplaySet.analyze` / `run_analysis`).  `track[t]`: the AnalysisResult
+    of log t of every experiment, bit-equal to `rs.replay(t).analyze` on that track alone.  `pooled`: the same statistics over the concatenation of the T
+    cleaned logs of an experiment in track order, as the reference's Plotter concatenates them: describe, step_quantiles and step_count over all kept
+    rows (order statistics exact), anomaly_counts and stats summed over the tracks, n_rows the rows of all logs; its cycle_max / cycle_mean
+    [E, sum n_log, n_cols] are groupby(["log_num", "cycle"]) (track t's cycles follow those of the tracks before it) and its anomaly_mask
+    [E, sum R] the tracks' masks side by side."""
+
+    pooled: AnalysisResult
+    track: list
 
 
 class ReplayResult:
@@ -804,6 +823,7 @@ class ReplaySetResult:
     track_precise_summary: Optional[list] = None
     precise_error: Optional[list] = None
     precise_counts: Optional[list] = None
+    analysis: Optional[SetAnalysisResult] = None  # run_analysis: a SetAnalysisResult of numpy arrays
 
 
 class _SuperTrack(Replay):
@@ -846,7 +866,8 @@ class ReplaySet:
     The pooled objective is sum of the tracks' sums / sum of their counts: the mean over the rows of all logs (the reference's Plotter concatenates
     them); the trimmed rows drop the first and the last logged cycle of EVERY track.  A (track, experiment) pair has the bits of `Replay` on that track
     alone.  After `attach_frames` the precise error works the same way: `rs.objective(tg, "trimmed_precise_error")`,
-    `rs.run(tg, precise=True)`, the search and the trainer's closed loop with a precise objective.  Logs and Analysis stay with `rs.replay(t)`."""
+    `rs.run(tg, precise=True)`, the search and the trainer's closed loop with a precise objective.  The analysis of the set, per log and over the
+    concatenation of all logs, is `rs.analyze(tg, spec)` / `rs.run_analysis(tg, spec)`.  Logs stay with `rs.replay(t)`."""
 
     def __init__(self, tracks, timing_config: TimingConfig, experiment_configs, frame_shapes=None, reach: Optional[int] = None, device: int = 0):
         if hip.device_count() < 1:
@@ -891,7 +912,7 @@ class ReplaySet:
         self._frames_table = None
 
     def replay(self, t: int) -> Replay:
-        """The plain `Replay` of track t: logs and Analysis stay there (and the precise error of one track)."""
+        """The plain `Replay` of track t: logs and per-row log output stay there (and the analysis and the precise error of one track alone)."""
         return self._replays[t]
 
     def attach_frames(self, frames, backgrounds, diff_thresh=20) -> None:
@@ -1041,12 +1062,84 @@ class ReplaySet:
             _max_crop_px: int = 0) -> ReplaySetResult:
         """Replay the E experiments of `targets` on every track: scan, rows reduction, one synchronisation.  `precise` (after `attach_frames`): also
         the precise error of every experiment on every track's frames (`precise_summary` pooled, `track_precise_summary[t]`; with `per_row_errors`
-        `precise_error[t]` and `precise_counts[t]`).  Logs and `analysis` belong to one track: they are `rs.replay(t).run`'s.
+        `precise_error[t]` and `precise_counts[t]`).  Logs belong to one track: they are `rs.replay(t).run`'s; the analysis of the set is
+        `run_analysis(targets, spec)` (this method's `analysis` argument stays refused).
         `_max_crop_px` (tests): the table limit of wtk_replay_set_precise, 0 = the default; results do not depend on it."""
-        import torch
-
         if analysis is not None:
             raise ValueError("the precise error and the analysis are per track: use rs.replay(t).run(..., precise=True / analysis=spec)")
+        return self._run(targets, precise, per_row_errors, _max_crop_px, None, 0)
+
+    def run_analysis(self, targets: Targets, spec: Analysis, precise: bool = False, per_row_errors: bool = False, _max_lds_rows: int = 0) -> ReplaySetResult:
+        """`run(targets, precise, per_row_errors)` and, as `res.analysis`, the SetAnalysisResult of `analyze(targets, spec, precise)` as numpy arrays:
+        one scan serves both, and the host synchronises once.  The precise_error column needs `precise` (after `attach_frames`)."""
+        return self._run(targets, precise, per_row_errors, 0, spec, _max_lds_rows)
+
+    def _check_analysis(self, spec: Analysis, precise: bool) -> None:
+        if "precise_error" in spec.columns and not precise:
+            raise ValueError("the precise_error column needs precise=True on attached frames (rs.attach_frames)")
+        if precise:
+            self._need_frames()
+
+    def _enqueue_precise(self, E: int, buf: dict, per_row: bool, counts: bool, max_crop_px: int, stream: int) -> dict:
+        """wtk_replay_set_precise behind a set scan: its summaries, and where asked for the per-row errors [E, sum R] and counts."""
+        import torch
+
+        n, rows, dev, sp = hip.REPLAY_PRECISE_SUMMARY_DOUBLES, self._frames_table.n_rows, self._dev, self._super
+        out = dict(track=torch.empty((self.T, E, n), dtype=torch.float64, device=dev), pooled=torch.empty((E, n), dtype=torch.float64, device=dev),
+                   scratch=torch.empty((max(1, hip.replay_set_precise_scratch_doubles(self._table, E)),), dtype=torch.float64, device=dev),
+                   err=torch.empty((E, rows), dtype=torch.float64, device=dev) if per_row else None,
+                   counts=torch.empty((E, rows, 2), dtype=torch.int32, device=dev) if counts else None)
+        hip.replay_set_precise(sp._cfg, self._table, self._frames_table, E, sp.track, sp._share, buf["pos"], buf["move"], int(max_crop_px), out["err"],
+                               out["counts"], out["track"], out["pooled"], out["scratch"], out["scratch"].numel(), stream=stream)
+        return out
+
+    def _enqueue_analysis(self, spec: Analysis, E: int, pos, move, precise_rows, stream: int, max_lds_rows: int) -> SetAnalysisResult:
+        """wtk_replay_set_analyze on a set scan's pos / move: a SetAnalysisResult of device tensors.  `precise_rows`: the per-row precise errors
+        [E, sum R] or None.  The per-track cycle aggregates and masks are slices of the packed arrays, which are the pooled result's."""
+        import torch
+
+        dev, T, L = self._dev, self.T, self.L
+        cols, q = spec.column_ids(), [float(v) for v in spec.percentiles]
+        n, Q, f64, i64 = len(cols), len(q), torch.float64, torch.int64
+        rows, logs = int(sum(self.n_rows)), int(sum(self.n_log))
+        new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)  # noqa: E731
+        mask = new((E, rows), torch.uint8) if spec.anomaly_mask else None
+        per = [new((T, E, n, 5 + Q), f64), new((E, logs, n), f64), new((E, logs, n), f64), new((T, E, L, n, Q), f64), new((T, E, L, n), torch.int32),
+               new((T, E, 7), i64), mask, new((T, E, 4), i64)]
+        pooled = [new((E, n, 5 + Q), f64), new((E, L, n, Q), f64), new((E, L, n), torch.int32), new((E, 7), i64), new((E, 4), i64)]
+        scratch = new((max(1, hip.replay_set_analysis_scratch_doubles(self._table, E, n, Q)),), f64)
+        sp = self._super
+        hip.replay_set_analyze(sp._cfg, spec.config(self.timing_config), self._table, E, sp.track, sp._share, pos, move, precise_rows, cols, q,
+                               int(max_lds_rows), per, pooled, scratch, scratch.numel(), stream=stream)
+        row0, log0 = np.concatenate([[0], np.cumsum(self.n_rows)]), np.concatenate([[0], np.cumsum(self.n_log)])
+        names = list(spec.columns)
+        track = [AnalysisResult(names, q, self.n_rows[t], per[0][t], per[1][:, log0[t]:log0[t + 1]], per[2][:, log0[t]:log0[t + 1]], per[3][t], per[4][t],
+                                per[5][t], per[7][t], None if mask is None else mask[:, row0[t]:row0[t + 1]]) for t in range(T)]
+        return SetAnalysisResult(AnalysisResult(names, q, rows, pooled[0], per[1], per[2], pooled[1], pooled[2], pooled[3], pooled[4], mask), track)
+
+    def analyze(self, targets: Targets, spec: Analysis, precise: bool = False, _max_lds_rows: int = 0) -> SetAnalysisResult:
+        """DataAnalyzer's statistics of every experiment of `targets` on every track and over the concatenation of its T cleaned logs, as a
+        SetAnalysisResult of DEVICE tensors, enqueued on the current torch stream (no synchronisation; `Replay.analyze` is the pattern): the set's scan,
+        with `precise` wtk_replay_set_precise, and wtk_replay_set_analyze, in a number of launches that does not depend on T.  `track[t]` has
+        `rs.replay(t).analyze(targets of t, spec)`'s bits; a pooled percentile is the percentile of all kept rows of all logs, which no combination of
+        per-track results gives.  `precise` (after `attach_frames`): the precise_error column, from the set's per-row errors.  `_max_lds_rows` (tests):
+        the longest segment wtk_replay_set_analyze sorts in LDS, 0 = the default; results do not depend on it."""
+        import torch
+
+        E, sp = self._check_targets(targets), self._super
+        self._check_analysis(spec, precise)
+        with torch.cuda.device(self._dev):
+            stream, buf = sp._stream(), self._objective_buffers(E)
+            hip.replay_set_scan(sp._cfg, self._table, KINDS[targets.kind], E, sp.track, targets.a, targets.b, targets.valid, sp._share, buf["pos"], buf["move"],
+                                stream=stream)
+            pr = self._enqueue_precise(E, buf, True, False, 0, stream) if precise else None
+            return self._enqueue_analysis(spec, E, buf["pos"], buf["move"], pr["err"] if precise else None, stream, _max_lds_rows)
+
+    def _run(self, targets: Targets, precise: bool, per_row_errors: bool, _max_crop_px: int, spec: Optional[Analysis], _max_lds_rows: int) -> ReplaySetResult:
+        import torch
+
+        if spec is not None:
+            self._check_analysis(spec, precise)
         if precise:
             self._need_frames()
         E, sp = self._check_targets(targets), self._super
@@ -1057,13 +1150,11 @@ class ReplaySet:
             hip.replay_set_rows(sp._cfg, self._table, E, sp.track, sp._share, buf["pos"], buf["move"], buf["track_summary"], buf["summary"], buf["scratch"],
                                 buf["scratch"].numel(), stream=stream)
             if precise:
-                n, rows = hip.REPLAY_PRECISE_SUMMARY_DOUBLES, self._frames_table.n_rows
-                ptrack, ppooled = torch.empty((self.T, E, n), dtype=torch.float64, device=self._dev), torch.empty((E, n), dtype=torch.float64, device=self._dev)
-                pscratch = torch.empty((max(1, hip.replay_set_precise_scratch_doubles(self._table, E)),), dtype=torch.float64, device=self._dev)
-                perr = torch.empty((E, rows), dtype=torch.float64, device=self._dev) if per_row_errors else None
-                pcounts = torch.empty((E, rows, 2), dtype=torch.int32, device=self._dev) if per_row_errors else None
-                hip.replay_set_precise(sp._cfg, self._table, self._frames_table, E, sp.track, sp._share, buf["pos"], buf["move"], int(_max_crop_px), perr,
-                                       pcounts, ptrack, ppooled, pscratch, pscratch.numel(), stream=stream)
+                pr = self._enqueue_precise(E, buf, per_row_errors or (spec is not None and "precise_error" in spec.columns), per_row_errors, _max_crop_px, stream)
+                ptrack, ppooled, perr, pcounts = pr["track"], pr["pooled"], pr["err"], pr["counts"]
+            ana = None
+            if spec is not None:
+                ana = self._enqueue_analysis(spec, E, buf["pos"], buf["move"], perr if precise else None, stream, _max_lds_rows)
             torch.cuda.current_stream(self._dev).synchronize()  # the one host synchronisation
             per = buf["track_summary"].cpu().numpy()
             cut = lambda x, t: x[self.cyc_off[t]:self.cyc_off[t] + self.n_cycles[t]].permute(1, 0, 2).contiguous().cpu().numpy()  # noqa: E731
@@ -1077,6 +1168,8 @@ class ReplaySet:
                     err, counts = perr.cpu().numpy(), pcounts.cpu().numpy()
                     res.precise_error = [np.ascontiguousarray(err[:, row0[t]:row0[t + 1]]) for t in range(self.T)]
                     res.precise_counts = [np.ascontiguousarray(counts[:, row0[t]:row0[t + 1]]) for t in range(self.T)]
+            if ana is not None:
+                res.analysis = SetAnalysisResult(_analysis_to_host(ana.pooled), [_analysis_to_host(a) for a in ana.track])
             return res
 
 
