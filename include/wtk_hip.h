@@ -684,7 +684,7 @@ int wtk_replay_objective(const wtk_replay_config *cfg, int32_t kind, int32_t E, 
  * A population replayed on a SET of T tracks at once, with a pooled objective (csrc/replay_set.hip).
  *
  * All tracks share the timing, camera and microscope entries of `cfg` (its num_frames, frame_w, frame_h, init_x, init_y are not read: they
- * are each track's own, in the table).  The tracks lie in ONE "super-track" track_dev [n_super][4], n_super a multiple of L: track t
+ * are each track's own, in the table; the *_geom entry points further down give every track its own camera and microscope too).  The tracks lie in ONE "super-track" track_dev [n_super][4], n_super a multiple of L: track t
  * starts at row cyc_off L, holds its n_track rows, then NaN rows up to the end of its slot of max(n_cycles, ceil(n_track / L)) cycles, then
  * guard_cycles further all-NaN cycles.  Every targets entry point treats a NaN row as it treats a row outside the track, so ONE call of
  * wtk_replay_polyfit_targets / wtk_replay_mlp_targets / wtk_track_polyfit / wtk_track_median_centers / wtk_mlp_predict_track over the
@@ -796,6 +796,61 @@ int wtk_replay_set_precise_objective(const wtk_replay_config *cfg, const wtk_rep
                                      const int32_t *stop_dev, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * A set whose recordings were taken at different scales: every track with its own camera size, microscope size and
+ * unit factors, as the reference derives a TimingConfig's pixel sizes and DataAnalyzer.change_unit's factors from the recording's own
+ * px_per_mm.  The cycle structure (imaging_frame_num, moving_frame_num, pred_frame_num) stays `cfg`'s for all tracks.
+ *
+ * wtk_replay_set_geometry   one entry per track, beside wtk_replay_set_track: the camera and microscope sizes in pixels that `cfg` holds for
+ *     all tracks elsewhere, and change_unit's (time, distance, speed) factors that wtk_replay_analysis_config holds for all tracks
+ *     elsewhere.  geom_host [T] is read by the checks, geom_dev [T] (the same bytes, uploaded once by the caller) by the kernels.
+ * The *_geom entry points are the entry points of the same name without the suffix, with the table: every (track, experiment) pair has the
+ *     bits of the single-track entry point called with the track's own sizes in its wtk_replay_config (and, for the analysis, the track's
+ *     factors in its wtk_replay_analysis_config); pooled figures add the tracks as before.  The same launches: their number does not depend
+ *     on T.  geom_host = geom_dev = NULL: `cfg`'s sizes and `acfg`'s factors for every track, which is what the entry points without the
+ *     suffix pass.  The factors are read by wtk_replay_set_analyze_geom alone (there `acfg`'s three factors are not read when a table is given).
+ * Refused (error code, nothing launched) beyond what the entry point without the suffix refuses: one of the two table pointers null and
+ *     the other not; for track t (named by index) a camera smaller than the microscope or a negative microscope size; in the analysis a
+ *     factor that is not finite.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct wtk_replay_set_geometry {
+    int32_t cam_w, cam_h, mic_w, mic_h;            /* TimingConfig.camera_size_px, micro_size_px of this track */
+    double time_factor, dist_factor, speed_factor; /* change_unit of this track's log; 1, 1, 1 for unit "frame" */
+} wtk_replay_set_geometry;
+int wtk_replay_set_scan_geom(const wtk_replay_config *cfg, const wtk_replay_set_track *tracks_host, const wtk_replay_set_track *tracks_dev,
+                             const wtk_replay_set_geometry *geom_host, const wtk_replay_set_geometry *geom_dev, int32_t T, int32_t guard_cycles,
+                             int32_t kind, int32_t E, const double *track_dev, int32_t n_super, const double *a_dev, const double *b_dev,
+                             const int32_t *valid_dev, const double *share_dev, int32_t *pos_dev, int32_t *move_dev, const int32_t *stop_dev,
+                             void *stream);
+int wtk_replay_set_rows_geom(const wtk_replay_config *cfg, const wtk_replay_set_track *tracks_host, const wtk_replay_set_track *tracks_dev,
+                             const wtk_replay_set_geometry *geom_host, const wtk_replay_set_geometry *geom_dev, int32_t T, int32_t guard_cycles,
+                             int32_t E, const double *track_dev, int32_t n_super, const double *share_dev, const int32_t *pos_dev,
+                             const int32_t *move_dev, double *track_summary_dev, double *summary_dev, double *scratch_dev,
+                             int64_t scratch_doubles, const int32_t *stop_dev, void *stream);
+int wtk_replay_set_objective_geom(const wtk_replay_config *cfg, const wtk_replay_set_track *tracks_host, const wtk_replay_set_track *tracks_dev,
+                                  const wtk_replay_set_geometry *geom_host, const wtk_replay_set_geometry *geom_dev, int32_t T,
+                                  int32_t guard_cycles, int32_t kind, int32_t E, const double *track_dev, int32_t n_super, const double *a_dev,
+                                  const double *b_dev, const int32_t *valid_dev, const double *share_dev, int32_t *pos_dev, int32_t *move_dev,
+                                  double *track_summary_dev, double *summary_dev, double *scratch_dev, int64_t scratch_doubles,
+                                  int32_t objective, double *objective_dev, double *track_objective_dev, const int32_t *stop_dev,
+                                  void *stream);
+int wtk_replay_set_precise_geom(const wtk_replay_config *cfg, const wtk_replay_set_track *tracks_host, const wtk_replay_set_track *tracks_dev,
+                                const wtk_replay_set_geometry *geom_host, const wtk_replay_set_geometry *geom_dev,
+                                const wtk_replay_set_frames *frames_host, const wtk_replay_set_frames *frames_dev, int32_t T,
+                                int32_t guard_cycles, int32_t E, const double *track_dev, int32_t n_super, const double *share_dev,
+                                const int32_t *pos_dev, const int32_t *move_dev, int32_t max_crop_px, double *err_dev, int32_t *counts_dev,
+                                double *track_summary_dev, double *summary_dev, double *scratch_dev, int64_t scratch_doubles,
+                                const int32_t *stop_dev, void *stream);
+int wtk_replay_set_precise_objective_geom(const wtk_replay_config *cfg, const wtk_replay_set_track *tracks_host,
+                                          const wtk_replay_set_track *tracks_dev, const wtk_replay_set_geometry *geom_host,
+                                          const wtk_replay_set_geometry *geom_dev, const wtk_replay_set_frames *frames_host,
+                                          const wtk_replay_set_frames *frames_dev, int32_t T, int32_t guard_cycles, int32_t kind, int32_t E,
+                                          const double *track_dev, int32_t n_super, const double *a_dev, const double *b_dev,
+                                          const int32_t *valid_dev, const double *share_dev, int32_t *pos_dev, int32_t *move_dev,
+                                          int32_t max_crop_px, double *track_summary_dev, double *summary_dev, double *scratch_dev,
+                                          int64_t scratch_doubles, int32_t objective, double *objective_dev, double *track_objective_dev,
+                                          const int32_t *stop_dev, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * The per-cycle ResMLP targets of a population of E models of one structure in one call: what Replay.mlp computes model by model
  * (wtk_mlp_predict_track, the float32 clip, the first box's corner), in the layout wtk_replay_scan reads for WTK_REPLAY_MLP, bit for bit.
  *   layers ...        the structure (in_dim, out_dim, relu of every layer; batch_norm is not looked at), as for wtk_mlp_folded_floats
@@ -816,6 +871,14 @@ int wtk_replay_mlp_targets(const wtk_mlp_train_layer *layers, int32_t n_layers, 
                            const int32_t *input_frames_host, int32_t n_in, float bound, double *a_dev, double *b_dev, int32_t *valid_dev,
                            const int32_t *stop_dev, void *stream);
 int32_t wtk_replay_mlp_targets_waves(int64_t blob_floats);
+/* wtk_replay_mlp_targets with a clip bound per cycle: bounds_dev [n_cycles] float32 on the device, cycle c's prediction is clamped to
+ * +-bounds_dev[c] (a set whose tracks were recorded at different px_per_mm: MLPController's bound max_speed px_per_mm / fps pred_frames[0]
+ * is the track's own).  The same launch; a constant array gives wtk_replay_mlp_targets' bits.  Refused beyond what
+ * wtk_replay_mlp_targets refuses: a null bounds_dev. */
+int wtk_replay_mlp_targets_bounds(const wtk_mlp_train_layer *layers, int32_t n_layers, int32_t n_blocks, int32_t layers_per_block, const float *blob_dev,
+                                  int32_t E, const float *track32_dev, const double *track_dev, int32_t n_track, const int32_t *anchors_dev,
+                                  int32_t n_cycles, const int32_t *input_frames_host, int32_t n_in, const float *bounds_dev, double *a_dev,
+                                  double *b_dev, int32_t *valid_dev, const int32_t *stop_dev, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * The YOLO controller's closed loop from device-resident state (csrc/replay_yolo.hip): the one experiment kind whose
@@ -1001,6 +1064,20 @@ int wtk_replay_set_analyze(const wtk_replay_config *cfg, const wtk_replay_analys
                            uint8_t *anomaly_mask_dev, int64_t *track_stats_dev, double *describe_dev, double *step_quantiles_dev,
                            int32_t *step_count_dev, int64_t *anomaly_counts_dev, int64_t *stats_dev, double *scratch_dev,
                            int64_t scratch_doubles, void *stream);
+/* wtk_replay_set_analyze with the per-track geometry table (wtk_replay_set_geometry above): log (t, e) is
+ * wtk_replay_analyze's experiment e on track t alone with the track's camera and microscope sizes and with the track's three factors in the
+ * place of acfg's; the pooled statistics are taken over the values so converted, as the reference concatenates logs that each went through
+ * their own change_unit.  acfg's bounds and thresholds stay one for all tracks.  NULL tables: wtk_replay_set_analyze. */
+int wtk_replay_set_analyze_geom(const wtk_replay_config *cfg, const wtk_replay_analysis_config *acfg, const wtk_replay_set_track *tracks_host,
+                                const wtk_replay_set_track *tracks_dev, const wtk_replay_set_geometry *geom_host,
+                                const wtk_replay_set_geometry *geom_dev, int32_t T, int32_t guard_cycles, int32_t E, const double *track_dev,
+                                int32_t n_super, const double *share_dev, const int32_t *pos_dev, const int32_t *move_dev,
+                                const double *precise_rows_dev, const int32_t *columns_host, int32_t n_cols, const double *percentiles_host,
+                                int32_t Q, int32_t max_lds_rows, double *track_describe_dev, double *cycle_max_dev, double *cycle_mean_dev,
+                                double *track_step_quantiles_dev, int32_t *track_step_count_dev, int64_t *track_anomaly_counts_dev,
+                                uint8_t *anomaly_mask_dev, int64_t *track_stats_dev, double *describe_dev, double *step_quantiles_dev,
+                                int32_t *step_count_dev, int64_t *anomaly_counts_dev, int64_t *stats_dev, double *scratch_dev,
+                                int64_t scratch_doubles, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * The precise tracking error of a replayed population (csrc/replay_precise.hip): ErrorCalculator.calculate_precise

@@ -7,6 +7,7 @@ simulate.ipynb loads the file too; here `load_config(path)` gives the controller
          [--fps 60] [--imaging-ms 200 --pred-ms 40 --moving-ms 50] [--offsets -45 -39 ...] [--pred-offset 21] [--degrees 1 2 3]
          [--min-speed 0.1 --max-speed 2] [--seed 0] [--pop-size 100 --max-epoch 300 --max-early-stop 100]
          [--closed-loop EXP_CONFIG_JSON [one per log ...] [--camera-mm 4 4] [--micro-mm 0.32 0.32] [--precise FRAMES_NPY BACKGROUND_NPY [one pair per log ...]]]
+         [--closed-loop-scales EXP_CONFIG_JSON one per log ...]
 
 A folder stands for its bboxes.csv, and its exp_config.json supplies frames_per_sec when --fps is not given.  Defaults are the notebook's: with L the
 cycle length in frames, offsets (-3L, -3L+6, -2L, -2L+6, -L, -L+6, 0, 3), target offset L + imaging_frames // 2, speed window 0.1 .. 2 px / frame.
@@ -22,7 +23,12 @@ also holds `closed_loop_error_of_open_loop_weights`, `closed_loop_error` and `cl
 With --precise FRAMES_NPY BACKGROUND_NPY (the experiment's gray frames, uint8 [F, H, W] with F >= the logged rows, and its background [H, W]) the
 closed-loop objective is the trimmed mean PRECISE error instead (Replay.attach_frames; the frames are held on the device and give the frame shape).
 With several logs give one FRAMES_NPY BACKGROUND_NPY pair per log, in the logs' order: the search runs on the ReplaySet with every log's frames
-attached (ReplaySet.attach_frames) and the precise error is pooled over the rows of all logs."""
+attached (ReplaySet.attach_frames) and the precise error is pooled over the rows of all logs.
+
+--closed-loop-scales EXP_CONFIG_JSON ... (one per log, in the logs' order; in the place of --closed-loop) is for logs recorded at DIFFERENT px_per_mm: every
+log gets the TimingConfig of its own exp_config.json, so --camera-mm and --micro-mm become that log's own camera and microscope in pixels
+(ReplaySet.from_experiments), where --closed-loop replays every log with the pixel sizes of the first exp_config.json.  The
+frame counts of --imaging-ms / --pred-ms / --moving-ms must come out equal for all logs (recordings at one frame rate)."""
 import argparse
 import json
 import os
@@ -63,6 +69,7 @@ def main(argv=None):
     ap.add_argument("--max-early-stop", type=int, default=100)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--closed-loop", default=None, nargs="+", metavar="EXP_CONFIG_JSON")
+    ap.add_argument("--closed-loop-scales", default=None, nargs="+", metavar="EXP_CONFIG_JSON")
     ap.add_argument("--camera-mm", type=float, nargs=2, default=[4.0, 4.0])
     ap.add_argument("--micro-mm", type=float, nargs=2, default=[0.32, 0.32])
     ap.add_argument("--precise", nargs="+", default=None, metavar="FRAMES_NPY BACKGROUND_NPY")
@@ -91,6 +98,13 @@ def main(argv=None):
     best = None
     rp = best_closed = None
     objective = "trimmed_bbox_error"
+    per_log = args.closed_loop_scales is not None
+    if per_log:
+        if args.closed_loop is not None:
+            ap.error("--closed-loop-scales stands in the place of --closed-loop: give one of them")
+        if len(args.closed_loop_scales) != len(paths):
+            ap.error(f"--closed-loop-scales takes one exp_config.json per log ({len(paths)})")
+        args.closed_loop = args.closed_loop_scales
     if args.precise is not None and args.closed_loop is None:
         ap.error("--precise goes with --closed-loop")
     if args.closed_loop is not None:
@@ -112,7 +126,11 @@ def main(argv=None):
             backgrounds, objective = [np.load(p) for p in args.precise[1::2]], "trimmed_precise_error"
         if len(paths) > 1:
             shapes = None if frames is None else [tuple(fr.shape[1:3]) for fr in frames]
-            rp = ReplaySet(paths, loop_tc, exp if len(exps) == 1 else exps, shapes, device=args.device)
+            if per_log:  # every log with the TimingConfig of its own recording
+                rp = ReplaySet.from_experiments(paths, exps, args.imaging_ms, args.pred_ms, args.moving_ms, tuple(args.camera_mm), tuple(args.micro_mm),
+                                                frame_shapes=shapes, device=args.device)
+            else:
+                rp = ReplaySet(paths, loop_tc, exp if len(exps) == 1 else exps, shapes, device=args.device)
             if frames is not None:
                 rp.attach_frames(frames, backgrounds)
         else:

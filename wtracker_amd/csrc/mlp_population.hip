@@ -35,6 +35,7 @@ struct MlpPopArgs {
     int input_frames[kMlpMaxInputFrames];
     int n_in;
     float bound;
+    const float *bounds; // [C] (nullable: `bound` for every cycle)
     double *a, *b; // [C][E][2]
     int *valid;    // [C][E]
     const int *stop;
@@ -87,9 +88,10 @@ __global__ __launch_bounds__(kPopMaxWaves * 64) void mlp_population_kernel(const
             const int r = lane >> 1, k = lane & 1, s = s0 + r;
             const size_t ce = (size_t)s * a.E + e;
             // torch.clamp: min(max(x, -bound), bound) with NaN kept (fmaxf / fminf would drop it)
+            const float bound = a.bounds ? a.bounds[s] : a.bound;
             float v = bufA[r * kLdAct + k];
-            v = v < -a.bound ? -a.bound : v;
-            v = v > a.bound ? a.bound : v;
+            v = v < -bound ? -bound : v;
+            v = v > bound ? bound : v;
             a.a[2 * ce + k] = ok[r] ? (double)v : 0.0;
             long long first = (long long)a.anchors[s] + a.input_frames[0];
             first = first < 0 ? 0 : (first > a.n_track - 1 ? a.n_track - 1 : first);
@@ -110,11 +112,12 @@ int pop_waves(int lds_floats) {
 
 } // namespace
 
-extern "C" int wtk_replay_mlp_targets(const wtk_mlp_train_layer *layers, int32_t n_layers, int32_t n_blocks, int32_t layers_per_block, const float *blob_dev, int32_t E,
-                                      const float *track32_dev, const double *track_dev, int32_t n_track, const int32_t *anchors_dev, int32_t n_cycles,
-                                      const int32_t *input_frames_host, int32_t n_in, float bound, double *a_dev, double *b_dev, int32_t *valid_dev,
-                                      const int32_t *stop_dev, void *stream) {
-    const char *who = "wtk_replay_mlp_targets";
+namespace {
+
+// both forms of the entry point: one bound for every cycle, or bounds_dev [n_cycles]
+int mlp_targets(const char *who, const wtk_mlp_train_layer *layers, int32_t n_layers, int32_t n_blocks, int32_t layers_per_block, const float *blob_dev, int32_t E,
+                const float *track32_dev, const double *track_dev, int32_t n_track, const int32_t *anchors_dev, int32_t n_cycles, const int32_t *input_frames_host,
+                int32_t n_in, float bound, const float *bounds_dev, double *a_dev, double *b_dev, int32_t *valid_dev, const int32_t *stop_dev, void *stream) {
     if (!layers || !blob_dev || !track32_dev || !track_dev || !anchors_dev || !input_frames_host || !a_dev || !b_dev || !valid_dev)
         return fail(std::string(who) + ": null argument");
     const char *why = "";
@@ -128,7 +131,7 @@ extern "C" int wtk_replay_mlp_targets(const wtk_mlp_train_layer *layers, int32_t
     MlpPopArgs a = {};
     a.blob = blob_dev, a.blob_floats = (int)F, a.E = E, a.track32 = track32_dev, a.track = track_dev, a.n_track = n_track, a.anchors = anchors_dev, a.C = n_cycles;
     for (int i = 0; i < kMlpMaxInputFrames; ++i) a.input_frames[i] = i < n_in ? input_frames_host[i] : 0;
-    a.n_in = n_in, a.bound = bound, a.a = a_dev, a.b = b_dev, a.valid = valid_dev, a.stop = stop_dev;
+    a.n_in = n_in, a.bound = bound, a.bounds = bounds_dev, a.a = a_dev, a.b = b_dev, a.valid = valid_dev, a.stop = stop_dev;
     a.n_layers = n_layers, a.n_blocks = n_blocks, a.layers_per_block = layers_per_block, a.in_dim = layers[0].in_dim;
     for (int i = 0; i < n_layers; ++i) a.l_in[i] = (unsigned char)(layers[i].in_dim - 1), a.l_out[i] = (unsigned char)(layers[i].out_dim - 1), a.l_relu[i] = layers[i].relu ? 1 : 0;
     a.in_lds = F <= kMlpLdsParams;
@@ -149,6 +152,25 @@ extern "C" int wtk_replay_mlp_targets(const wtk_mlp_train_layer *layers, int32_t
     hipLaunchKernelGGL(mlp_population_kernel, dim3((unsigned)E, (unsigned)groups), dim3(waves * 64), dyn, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+} // namespace
+
+extern "C" int wtk_replay_mlp_targets(const wtk_mlp_train_layer *layers, int32_t n_layers, int32_t n_blocks, int32_t layers_per_block, const float *blob_dev, int32_t E,
+                                      const float *track32_dev, const double *track_dev, int32_t n_track, const int32_t *anchors_dev, int32_t n_cycles,
+                                      const int32_t *input_frames_host, int32_t n_in, float bound, double *a_dev, double *b_dev, int32_t *valid_dev,
+                                      const int32_t *stop_dev, void *stream) {
+    return mlp_targets("wtk_replay_mlp_targets", layers, n_layers, n_blocks, layers_per_block, blob_dev, E, track32_dev, track_dev, n_track, anchors_dev, n_cycles,
+                       input_frames_host, n_in, bound, nullptr, a_dev, b_dev, valid_dev, stop_dev, stream);
+}
+
+extern "C" int wtk_replay_mlp_targets_bounds(const wtk_mlp_train_layer *layers, int32_t n_layers, int32_t n_blocks, int32_t layers_per_block, const float *blob_dev,
+                                             int32_t E, const float *track32_dev, const double *track_dev, int32_t n_track, const int32_t *anchors_dev,
+                                             int32_t n_cycles, const int32_t *input_frames_host, int32_t n_in, const float *bounds_dev, double *a_dev,
+                                             double *b_dev, int32_t *valid_dev, const int32_t *stop_dev, void *stream) {
+    if (!bounds_dev) return fail("wtk_replay_mlp_targets_bounds: null argument");
+    return mlp_targets("wtk_replay_mlp_targets_bounds", layers, n_layers, n_blocks, layers_per_block, blob_dev, E, track32_dev, track_dev, n_track, anchors_dev,
+                       n_cycles, input_frames_host, n_in, 0.f, bounds_dev, a_dev, b_dev, valid_dev, stop_dev, stream);
 }
 
 extern "C" int32_t wtk_replay_mlp_targets_waves(int64_t blob_floats) {

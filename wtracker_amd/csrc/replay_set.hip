@@ -12,6 +12,10 @@
 //           one float64 division of the pooled slots (and, where asked for, of each track's)
 // Three launches whatever T is.  No floating-point atomics.  Every launch reads the nullable stop flag and touches nothing once it is up.
 //
+// Recordings at different scales: the *_geom entry points take a per-track geometry table (camera and microscope sizes; the
+// analysis also reads its unit factors), which replay_set_device.h's track_geometry puts into the track's view in the place of cfg's sizes.  The
+// kernels, the launches and the order of every sum are the same; the entry points without the suffix pass no table.
+//
 // The PRECISE error of the set, each track with its own frames, background, frame shape and threshold (the frames table):
 //   table   one block per GLOBAL logged row (row0 = prefix sum of R): the block finds its track by a search in the frames table, fills a PreciseArgs
 //           for that track alone and runs replay_precise_device.h's precise_frame on the track's row, as replay_precise_kernel does
@@ -39,7 +43,7 @@ __global__ __launch_bounds__(kScanThreads) void replay_set_scan_kernel(const Set
     const wtk_replay_set_track tr = a.tracks[t];
     const long long c0 = (long long)tr.cyc_off * a.E; // the track's slice of the cycle-major arrays
     ScanArgs s;
-    s.g = track_geometry(a, tr), s.kind = a.kind, s.E = a.E, s.C = tr.n_cycles, s.init_x = tr.init_x, s.init_y = tr.init_y;
+    s.g = track_geometry(a, t, tr), s.kind = a.kind, s.E = a.E, s.C = tr.n_cycles, s.init_x = tr.init_x, s.init_y = tr.init_y;
     s.track = a.track + 4 * (long long)tr.cyc_off * a.g.L, s.n_track = tr.n_track;
     s.a = a.a ? a.a + 2 * c0 : nullptr, s.b = a.b ? a.b + 2 * c0 : nullptr, s.valid = a.valid ? a.valid + c0 : nullptr;
     s.share = a.share, s.pos = a.pos + 2 * c0, s.move = a.move + 2 * c0, s.stop = nullptr;
@@ -57,10 +61,7 @@ __global__ __launch_bounds__(kRowThreads) void replay_set_rows_kernel(const SetA
         else hi = mid - 1;
     }
     const wtk_replay_set_track tr = a.tracks[lo];
-    const long long c0 = (long long)tr.cyc_off * a.E;
-    ReplayView v;
-    v.g = track_geometry(a, tr), v.E = a.E, v.C = tr.n_cycles, v.n_log = tr.n_log, v.R = tr.R;
-    v.track = a.track + 4 * (long long)tr.cyc_off * a.g.L, v.share = a.share, v.pos = a.pos + 2 * c0, v.move = a.move + 2 * c0;
+    const ReplayView v = track_view(a, lo, tr);
     double acc[kSummary];
     for (int q = 0; q < kSummary; ++q) acc[q] = 0.0;
     const long long r0 = (long long)(gs - tr.chunk0) * kRowChunk;
@@ -132,7 +133,7 @@ __device__ __forceinline__ int track_of_row(const SetPreciseArgs &a, long long r
 __device__ __forceinline__ PreciseArgs track_precise(const SetPreciseArgs &a, int t) {
     const wtk_replay_set_frames fr = a.frames[t];
     PreciseArgs p;
-    p.v = track_view(a.s, a.s.tracks[t]);
+    p.v = track_view(a.s, t, a.s.tracks[t]);
     p.frames = fr.frames, p.bg = fr.bg, p.H = fr.H, p.W = fr.W, p.thr = threshold_int(fr.diff_thresh);
     p.max_cells = a.max_cells, p.S = 0, p.out_rows = a.rows;
     p.pair = a.pair + fr.row0 * a.s.E, p.walk = a.walk + fr.row0;
@@ -169,7 +170,7 @@ __global__ __launch_bounds__(kRowThreads) void replay_set_precise_reduce_kernel(
         else hi = mid - 1;
     }
     const wtk_replay_set_track tr = a.s.tracks[lo];
-    const ReplayView v = track_view(a.s, tr); // the track's own n_log: its first and last logged cycle are trimmed
+    const ReplayView v = track_view(a.s, lo, tr); // the track's own n_log: its first and last logged cycle are trimmed
     double acc[kPreciseSummary];
     for (int q = 0; q < kPreciseSummary; ++q) acc[q] = 0.0;
     precise_chunk_rows(v, a.pair + a.frames[lo].row0 * a.s.E, e, (long long)(gs - tr.chunk0) * kRowChunk, acc);
@@ -257,13 +258,15 @@ int launch_set_precise(const SetPreciseArgs &p, hipStream_t st) {
 } // namespace
 
 // (declared in replay_set_device.h: replay_set_analysis.hip checks its table with it too)
-int wtk::set_view(const char *who, const wtk_replay_config *cfg, const wtk_replay_set_track *host, const wtk_replay_set_track *dev, int32_t T, int32_t guard_cycles,
-             int32_t kind, int32_t E, const double *track_dev, int32_t n_super, const double *share_dev, const int32_t *pos_dev, const int32_t *move_dev, SetArgs &a,
-             int &min_log) {
+int wtk::set_view(const char *who, const wtk_replay_config *cfg, const wtk_replay_set_track *host, const wtk_replay_set_track *dev,
+                  const wtk_replay_set_geometry *geom_host, const wtk_replay_set_geometry *geom_dev, int32_t T, int32_t guard_cycles, int32_t kind, int32_t E,
+                  const double *track_dev, int32_t n_super, const double *share_dev, const int32_t *pos_dev, const int32_t *move_dev, SetArgs &a,
+                  int &min_log) {
     const std::string w(who);
     if (!cfg || !host || !dev) return fail(w + ": null argument");
     if (T < 1) return fail(w + ": at least one track (T >= 1)");
     if (guard_cycles < 0) return fail(w + ": negative guard_cycles");
+    if ((geom_host == nullptr) != (geom_dev == nullptr)) return fail(w + ": the geometry table needs its host and its device copy (or neither)");
     long long chunks = 0, end_before = 0; // end_before: the first cycle behind the slot and guard of the track before
     min_log = INT32_MAX;
     for (int t = 0; t < T; ++t) {
@@ -272,6 +275,7 @@ int wtk::set_view(const char *who, const wtk_replay_config *cfg, const wtk_repla
         wtk_replay_config c = *cfg;
         c.num_frames = tr.num_frames, c.frame_w = tr.x_max < INT32_MAX ? tr.x_max + 1 : 0, c.frame_h = tr.y_max < INT32_MAX ? tr.y_max + 1 : 0;
         c.init_x = tr.init_x, c.init_y = tr.init_y;
+        if (geom_host) c.cam_w = geom_host[t].cam_w, c.cam_h = geom_host[t].cam_h, c.mic_w = geom_host[t].mic_w, c.mic_h = geom_host[t].mic_h;
         ReplayView v = {};
         if (replay_view(wt.c_str(), &c, kind, E, tr.n_cycles, track_dev, tr.n_track, share_dev, pos_dev, move_dev, v)) return 1;
         if (tr.n_log != v.n_log || tr.R != v.R) return fail(wt + ": n_log and R must be (num_frames - 1) / L and n_log L");
@@ -287,19 +291,22 @@ int wtk::set_view(const char *who, const wtk_replay_config *cfg, const wtk_repla
     }
     if (chunks * E > INT32_MAX) return fail(w + ": too many (experiment, chunk) blocks for one launch");
     if (T > 65535) return fail(w + ": at most 65535 tracks (the scan's grid)");
-    a.tracks = dev, a.T = T, a.E = E, a.kind = kind, a.S = (int)chunks, a.track = track_dev, a.share = share_dev;
+    a.tracks = dev, a.geom = geom_dev, a.T = T, a.E = E, a.kind = kind, a.S = (int)chunks, a.track = track_dev, a.share = share_dev;
     a.pos = const_cast<int *>(pos_dev), a.move = const_cast<int *>(move_dev);
     return 0;
 }
 
-extern "C" int wtk_replay_set_scan(const wtk_replay_config *cfg, const wtk_replay_set_track *tracks_host, const wtk_replay_set_track *tracks_dev, int32_t T,
-                                   int32_t guard_cycles, int32_t kind, int32_t E, const double *track_dev, int32_t n_super, const double *a_dev,
-                                   const double *b_dev, const int32_t *valid_dev, const double *share_dev, int32_t *pos_dev, int32_t *move_dev,
-                                   const int32_t *stop_dev, void *stream) {
-    const char *who = "wtk_replay_set_scan";
+extern "C" int wtk_replay_set_scan_geom(const wtk_replay_config *cfg, const wtk_replay_set_track *tracks_host, const wtk_replay_set_track *tracks_dev,
+                                        const wtk_replay_set_geometry *geom_host, const wtk_replay_set_geometry *geom_dev, int32_t T, int32_t guard_cycles,
+                                        int32_t kind, int32_t E, const double *track_dev, int32_t n_super, const double *a_dev, const double *b_dev,
+                                        const int32_t *valid_dev, const double *share_dev, int32_t *pos_dev, int32_t *move_dev, const int32_t *stop_dev,
+                                        void *stream) {
+    const char *who = geom_host || geom_dev ? "wtk_replay_set_scan_geom" : "wtk_replay_set_scan";
     SetArgs a = {};
     int min_log = 0;
-    if (set_view(who, cfg, tracks_host, tracks_dev, T, guard_cycles, kind, E, track_dev, n_super, share_dev, pos_dev, move_dev, a, min_log)) return 1;
+    if (set_view(who, cfg, tracks_host, tracks_dev, geom_host, geom_dev, T, guard_cycles, kind, E, track_dev, n_super, share_dev, pos_dev, move_dev, a,
+                 min_log))
+        return 1;
     if (set_targets(who, kind, a_dev, b_dev, valid_dev, a)) return 1;
     a.stop = stop_dev;
     launch_set_scan(a, (hipStream_t)stream);
@@ -317,14 +324,17 @@ extern "C" int64_t wtk_replay_set_scratch_doubles(const wtk_replay_set_track *tr
     return (int64_t)E * chunks * kSummary;
 }
 
-extern "C" int wtk_replay_set_rows(const wtk_replay_config *cfg, const wtk_replay_set_track *tracks_host, const wtk_replay_set_track *tracks_dev, int32_t T,
-                                   int32_t guard_cycles, int32_t E, const double *track_dev, int32_t n_super, const double *share_dev,
-                                   const int32_t *pos_dev, const int32_t *move_dev, double *track_summary_dev, double *summary_dev, double *scratch_dev,
-                                   int64_t scratch_doubles, const int32_t *stop_dev, void *stream) {
-    const char *who = "wtk_replay_set_rows";
+extern "C" int wtk_replay_set_rows_geom(const wtk_replay_config *cfg, const wtk_replay_set_track *tracks_host, const wtk_replay_set_track *tracks_dev,
+                                        const wtk_replay_set_geometry *geom_host, const wtk_replay_set_geometry *geom_dev, int32_t T, int32_t guard_cycles,
+                                        int32_t E, const double *track_dev, int32_t n_super, const double *share_dev, const int32_t *pos_dev,
+                                        const int32_t *move_dev, double *track_summary_dev, double *summary_dev, double *scratch_dev,
+                                        int64_t scratch_doubles, const int32_t *stop_dev, void *stream) {
+    const char *who = geom_host || geom_dev ? "wtk_replay_set_rows_geom" : "wtk_replay_set_rows";
     SetArgs a = {};
     int min_log = 0;
-    if (set_view(who, cfg, tracks_host, tracks_dev, T, guard_cycles, WTK_REPLAY_OPTIMAL, E, track_dev, n_super, share_dev, pos_dev, move_dev, a, min_log)) return 1;
+    if (set_view(who, cfg, tracks_host, tracks_dev, geom_host, geom_dev, T, guard_cycles, WTK_REPLAY_OPTIMAL, E, track_dev, n_super, share_dev, pos_dev, move_dev, a,
+                 min_log))
+        return 1;
     if (set_sums(who, tracks_host, T, track_summary_dev, summary_dev, scratch_dev, scratch_doubles, a)) return 1;
     a.stop = stop_dev;
     launch_set_rows(a, (hipStream_t)stream);
@@ -332,16 +342,20 @@ extern "C" int wtk_replay_set_rows(const wtk_replay_config *cfg, const wtk_repla
     return 0;
 }
 
-extern "C" int wtk_replay_set_objective(const wtk_replay_config *cfg, const wtk_replay_set_track *tracks_host, const wtk_replay_set_track *tracks_dev,
-                                        int32_t T, int32_t guard_cycles, int32_t kind, int32_t E, const double *track_dev, int32_t n_super,
-                                        const double *a_dev, const double *b_dev, const int32_t *valid_dev, const double *share_dev, int32_t *pos_dev,
-                                        int32_t *move_dev, double *track_summary_dev, double *summary_dev, double *scratch_dev, int64_t scratch_doubles,
-                                        int32_t objective, double *objective_dev, double *track_objective_dev, const int32_t *stop_dev, void *stream) {
-    const char *who = "wtk_replay_set_objective";
+extern "C" int wtk_replay_set_objective_geom(const wtk_replay_config *cfg, const wtk_replay_set_track *tracks_host, const wtk_replay_set_track *tracks_dev,
+                                             const wtk_replay_set_geometry *geom_host, const wtk_replay_set_geometry *geom_dev, int32_t T,
+                                             int32_t guard_cycles, int32_t kind, int32_t E, const double *track_dev, int32_t n_super, const double *a_dev,
+                                             const double *b_dev, const int32_t *valid_dev, const double *share_dev, int32_t *pos_dev, int32_t *move_dev,
+                                             double *track_summary_dev, double *summary_dev, double *scratch_dev, int64_t scratch_doubles,
+                                             int32_t objective, double *objective_dev, double *track_objective_dev, const int32_t *stop_dev,
+                                             void *stream) {
+    const char *who = geom_host || geom_dev ? "wtk_replay_set_objective_geom" : "wtk_replay_set_objective";
     const std::string w(who);
     SetArgs a = {};
     int min_log = 0;
-    if (set_view(who, cfg, tracks_host, tracks_dev, T, guard_cycles, kind, E, track_dev, n_super, share_dev, pos_dev, move_dev, a, min_log)) return 1;
+    if (set_view(who, cfg, tracks_host, tracks_dev, geom_host, geom_dev, T, guard_cycles, kind, E, track_dev, n_super, share_dev, pos_dev, move_dev, a,
+                 min_log))
+        return 1;
     if (set_targets(who, kind, a_dev, b_dev, valid_dev, a)) return 1;
     if (set_sums(who, tracks_host, T, track_summary_dev, summary_dev, scratch_dev, scratch_doubles, a)) return 1;
     if (!objective_dev) return fail(w + ": null argument");
@@ -368,15 +382,19 @@ extern "C" int64_t wtk_replay_set_precise_scratch_doubles(const wtk_replay_set_t
     return set_precise_scratch(E, rows, chunks);
 }
 
-extern "C" int wtk_replay_set_precise(const wtk_replay_config *cfg, const wtk_replay_set_track *tracks_host, const wtk_replay_set_track *tracks_dev,
-                                      const wtk_replay_set_frames *frames_host, const wtk_replay_set_frames *frames_dev, int32_t T, int32_t guard_cycles,
-                                      int32_t E, const double *track_dev, int32_t n_super, const double *share_dev, const int32_t *pos_dev,
-                                      const int32_t *move_dev, int32_t max_crop_px, double *err_dev, int32_t *counts_dev, double *track_summary_dev,
-                                      double *summary_dev, double *scratch_dev, int64_t scratch_doubles, const int32_t *stop_dev, void *stream) {
-    const char *who = "wtk_replay_set_precise";
+extern "C" int wtk_replay_set_precise_geom(const wtk_replay_config *cfg, const wtk_replay_set_track *tracks_host, const wtk_replay_set_track *tracks_dev,
+                                           const wtk_replay_set_geometry *geom_host, const wtk_replay_set_geometry *geom_dev,
+                                           const wtk_replay_set_frames *frames_host, const wtk_replay_set_frames *frames_dev, int32_t T,
+                                           int32_t guard_cycles, int32_t E, const double *track_dev, int32_t n_super, const double *share_dev,
+                                           const int32_t *pos_dev, const int32_t *move_dev, int32_t max_crop_px, double *err_dev, int32_t *counts_dev,
+                                           double *track_summary_dev, double *summary_dev, double *scratch_dev, int64_t scratch_doubles,
+                                           const int32_t *stop_dev, void *stream) {
+    const char *who = geom_host || geom_dev ? "wtk_replay_set_precise_geom" : "wtk_replay_set_precise";
     SetPreciseArgs p = {};
     int min_log = 0;
-    if (set_view(who, cfg, tracks_host, tracks_dev, T, guard_cycles, WTK_REPLAY_OPTIMAL, E, track_dev, n_super, share_dev, pos_dev, move_dev, p.s, min_log)) return 1;
+    if (set_view(who, cfg, tracks_host, tracks_dev, geom_host, geom_dev, T, guard_cycles, WTK_REPLAY_OPTIMAL, E, track_dev, n_super, share_dev, pos_dev, move_dev, p.s,
+                 min_log))
+        return 1;
     if (set_frames(who, tracks_host, frames_host, frames_dev, T, max_crop_px, err_dev, counts_dev, track_summary_dev, summary_dev, scratch_dev, scratch_doubles, p))
         return 1;
     p.s.stop = stop_dev;
@@ -385,18 +403,22 @@ extern "C" int wtk_replay_set_precise(const wtk_replay_config *cfg, const wtk_re
     return 0;
 }
 
-extern "C" int wtk_replay_set_precise_objective(const wtk_replay_config *cfg, const wtk_replay_set_track *tracks_host, const wtk_replay_set_track *tracks_dev,
-                                                const wtk_replay_set_frames *frames_host, const wtk_replay_set_frames *frames_dev, int32_t T,
-                                                int32_t guard_cycles, int32_t kind, int32_t E, const double *track_dev, int32_t n_super, const double *a_dev,
-                                                const double *b_dev, const int32_t *valid_dev, const double *share_dev, int32_t *pos_dev, int32_t *move_dev,
-                                                int32_t max_crop_px, double *track_summary_dev, double *summary_dev, double *scratch_dev,
-                                                int64_t scratch_doubles, int32_t objective, double *objective_dev, double *track_objective_dev,
-                                                const int32_t *stop_dev, void *stream) {
-    const char *who = "wtk_replay_set_precise_objective";
+extern "C" int wtk_replay_set_precise_objective_geom(const wtk_replay_config *cfg, const wtk_replay_set_track *tracks_host,
+                                                     const wtk_replay_set_track *tracks_dev, const wtk_replay_set_geometry *geom_host,
+                                                     const wtk_replay_set_geometry *geom_dev, const wtk_replay_set_frames *frames_host,
+                                                     const wtk_replay_set_frames *frames_dev, int32_t T, int32_t guard_cycles, int32_t kind, int32_t E,
+                                                     const double *track_dev, int32_t n_super, const double *a_dev, const double *b_dev,
+                                                     const int32_t *valid_dev, const double *share_dev, int32_t *pos_dev, int32_t *move_dev,
+                                                     int32_t max_crop_px, double *track_summary_dev, double *summary_dev, double *scratch_dev,
+                                                     int64_t scratch_doubles, int32_t objective, double *objective_dev, double *track_objective_dev,
+                                                     const int32_t *stop_dev, void *stream) {
+    const char *who = geom_host || geom_dev ? "wtk_replay_set_precise_objective_geom" : "wtk_replay_set_precise_objective";
     const std::string w(who);
     SetPreciseArgs p = {};
     int min_log = 0;
-    if (set_view(who, cfg, tracks_host, tracks_dev, T, guard_cycles, kind, E, track_dev, n_super, share_dev, pos_dev, move_dev, p.s, min_log)) return 1;
+    if (set_view(who, cfg, tracks_host, tracks_dev, geom_host, geom_dev, T, guard_cycles, kind, E, track_dev, n_super, share_dev, pos_dev, move_dev, p.s,
+                 min_log))
+        return 1;
     if (set_targets(who, kind, a_dev, b_dev, valid_dev, p.s)) return 1;
     if (set_frames(who, tracks_host, frames_host, frames_dev, T, max_crop_px, nullptr, nullptr, track_summary_dev, summary_dev, scratch_dev, scratch_doubles, p))
         return 1;
@@ -411,4 +433,53 @@ extern "C" int wtk_replay_set_precise_objective(const wtk_replay_config *cfg, co
     if (launch_set_precise(p, st)) return 1;
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+// ---- the entry points without a geometry table: cfg's camera and microscope for every track
+extern "C" int wtk_replay_set_scan(const wtk_replay_config *cfg, const wtk_replay_set_track *tracks_host, const wtk_replay_set_track *tracks_dev, int32_t T,
+                                   int32_t guard_cycles, int32_t kind, int32_t E, const double *track_dev, int32_t n_super, const double *a_dev,
+                                   const double *b_dev, const int32_t *valid_dev, const double *share_dev, int32_t *pos_dev, int32_t *move_dev,
+                                   const int32_t *stop_dev, void *stream) {
+    return wtk_replay_set_scan_geom(cfg, tracks_host, tracks_dev, nullptr, nullptr, T, guard_cycles, kind, E, track_dev, n_super, a_dev, b_dev, valid_dev, share_dev,
+                                    pos_dev, move_dev, stop_dev, stream);
+}
+
+extern "C" int wtk_replay_set_rows(const wtk_replay_config *cfg, const wtk_replay_set_track *tracks_host, const wtk_replay_set_track *tracks_dev, int32_t T,
+                                   int32_t guard_cycles, int32_t E, const double *track_dev, int32_t n_super, const double *share_dev,
+                                   const int32_t *pos_dev, const int32_t *move_dev, double *track_summary_dev, double *summary_dev, double *scratch_dev,
+                                   int64_t scratch_doubles, const int32_t *stop_dev, void *stream) {
+    return wtk_replay_set_rows_geom(cfg, tracks_host, tracks_dev, nullptr, nullptr, T, guard_cycles, E, track_dev, n_super, share_dev, pos_dev, move_dev,
+                                    track_summary_dev, summary_dev, scratch_dev, scratch_doubles, stop_dev, stream);
+}
+
+extern "C" int wtk_replay_set_objective(const wtk_replay_config *cfg, const wtk_replay_set_track *tracks_host, const wtk_replay_set_track *tracks_dev,
+                                        int32_t T, int32_t guard_cycles, int32_t kind, int32_t E, const double *track_dev, int32_t n_super,
+                                        const double *a_dev, const double *b_dev, const int32_t *valid_dev, const double *share_dev, int32_t *pos_dev,
+                                        int32_t *move_dev, double *track_summary_dev, double *summary_dev, double *scratch_dev, int64_t scratch_doubles,
+                                        int32_t objective, double *objective_dev, double *track_objective_dev, const int32_t *stop_dev, void *stream) {
+    return wtk_replay_set_objective_geom(cfg, tracks_host, tracks_dev, nullptr, nullptr, T, guard_cycles, kind, E, track_dev, n_super, a_dev, b_dev, valid_dev,
+                                         share_dev, pos_dev, move_dev, track_summary_dev, summary_dev, scratch_dev, scratch_doubles, objective, objective_dev,
+                                         track_objective_dev, stop_dev, stream);
+}
+
+extern "C" int wtk_replay_set_precise(const wtk_replay_config *cfg, const wtk_replay_set_track *tracks_host, const wtk_replay_set_track *tracks_dev,
+                                      const wtk_replay_set_frames *frames_host, const wtk_replay_set_frames *frames_dev, int32_t T, int32_t guard_cycles,
+                                      int32_t E, const double *track_dev, int32_t n_super, const double *share_dev, const int32_t *pos_dev,
+                                      const int32_t *move_dev, int32_t max_crop_px, double *err_dev, int32_t *counts_dev, double *track_summary_dev,
+                                      double *summary_dev, double *scratch_dev, int64_t scratch_doubles, const int32_t *stop_dev, void *stream) {
+    return wtk_replay_set_precise_geom(cfg, tracks_host, tracks_dev, nullptr, nullptr, frames_host, frames_dev, T, guard_cycles, E, track_dev, n_super, share_dev,
+                                       pos_dev, move_dev, max_crop_px, err_dev, counts_dev, track_summary_dev, summary_dev, scratch_dev, scratch_doubles, stop_dev,
+                                       stream);
+}
+
+extern "C" int wtk_replay_set_precise_objective(const wtk_replay_config *cfg, const wtk_replay_set_track *tracks_host, const wtk_replay_set_track *tracks_dev,
+                                                const wtk_replay_set_frames *frames_host, const wtk_replay_set_frames *frames_dev, int32_t T,
+                                                int32_t guard_cycles, int32_t kind, int32_t E, const double *track_dev, int32_t n_super, const double *a_dev,
+                                                const double *b_dev, const int32_t *valid_dev, const double *share_dev, int32_t *pos_dev, int32_t *move_dev,
+                                                int32_t max_crop_px, double *track_summary_dev, double *summary_dev, double *scratch_dev,
+                                                int64_t scratch_doubles, int32_t objective, double *objective_dev, double *track_objective_dev,
+                                                const int32_t *stop_dev, void *stream) {
+    return wtk_replay_set_precise_objective_geom(cfg, tracks_host, tracks_dev, nullptr, nullptr, frames_host, frames_dev, T, guard_cycles, kind, E, track_dev,
+                                                 n_super, a_dev, b_dev, valid_dev, share_dev, pos_dev, move_dev, max_crop_px, track_summary_dev, summary_dev,
+                                                 scratch_dev, scratch_doubles, objective, objective_dev, track_objective_dev, stop_dev, stream);
 }

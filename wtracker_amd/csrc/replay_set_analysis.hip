@@ -69,10 +69,15 @@ __global__ void set_analysis_prefix_kernel(const SetAnaArgs a) {
     a.row0[a.s.T] = rows, a.log0[a.s.T] = logs;
 }
 
-// track `tr` as wtk_replay_analyze's arguments: its view and the spec (the statements of a row read nothing else)
-__device__ __forceinline__ AnaArgs track_args(const SetAnaArgs &a, const wtk_replay_set_track &tr) {
+// track t (entry `tr`) as wtk_replay_analyze's arguments: its view and the spec (the statements of a row read nothing else).  With a geometry table
+// the spec's change_unit factors are the track's own: every statement below that converts a value reads them from here, never from a.c.
+__device__ __forceinline__ AnaArgs track_args(const SetAnaArgs &a, int t, const wtk_replay_set_track &tr) {
     AnaArgs p = {};
-    p.v = track_view(a.s, tr), p.pair = nullptr, p.c = a.c;
+    p.v = track_view(a.s, t, tr), p.pair = nullptr, p.c = a.c;
+    if (a.s.geom) {
+        const wtk_replay_set_geometry tg = a.s.geom[t];
+        p.c.time_factor = tg.time_factor, p.c.dist_factor = tg.dist_factor, p.c.speed_factor = tg.speed_factor;
+    }
     return p;
 }
 
@@ -91,7 +96,7 @@ __global__ __launch_bounds__(kAnaThreads) void set_analysis_last_cycle_kernel(co
         if (threadIdx.x == 0) a.last_cycle[blockIdx.x] = tr.n_log - 1;
         return;
     }
-    const AnaArgs p = track_args(a, tr);
+    const AnaArgs p = track_args(a, t, tr);
     int mine = -1;
     for (long long r = threadIdx.x; r < p.v.R; r += kAnaThreads) {
         const AnaRow w = ana_row(p, e, r); // (the precise error is no part of clean)
@@ -133,7 +138,7 @@ struct TrackPart {
 __device__ __forceinline__ TrackPart track_part(const SetAnaArgs &a, const SetSegment &s, int t) {
     const wtk_replay_set_track tr = a.s.tracks[t];
     TrackPart tp;
-    tp.p = track_args(a, tr), tp.row0 = a.row0[t];
+    tp.p = track_args(a, t, tr), tp.row0 = a.row0[t];
     tp.n_rows = s.seg < 0 ? tr.R : (tr.R > s.seg ? (tr.R - s.seg + a.s.g.L - 1) / a.s.g.L : 0);
     tp.last = a.c.trim_cycles ? a.last_cycle[(long long)t * a.s.E + s.e] : -1;
     return tp;
@@ -246,7 +251,9 @@ __global__ __launch_bounds__(kAnaThreads) void set_analysis_segment_sort_kernel(
     }
 }
 
-__global__ __launch_bounds__(kAnaThreads) void set_analysis_segment_select_kernel(const SetAnaArgs a) {
+// (waves per SIMD pinned at 4, i.e. at most 128 VGPRs, which is what the kernel took before the geometry table's pointer and factors: left to itself
+// the compiler now spills more scalars into vector lanes, ends at 135 and halves the workgroups per CU; with the pin it ends at 125, no scratch)
+__global__ __launch_bounds__(kAnaThreads) __attribute__((amdgpu_waves_per_eu(4, 4))) void set_analysis_segment_select_kernel(const SetAnaArgs a) {
     __shared__ double red[kAnaThreads];
     __shared__ unsigned hist[kMaxRanks][256];
     __shared__ unsigned long long prefix[kMaxRanks]; // the digits found so far, in place
@@ -301,7 +308,7 @@ __global__ __launch_bounds__(256) void set_analysis_cycle_kernel(const SetAnaArg
         if (a.log0[mid] <= gc) lo = mid;
         else hi = mid - 1;
     }
-    const AnaArgs p = track_args(a, a.s.tracks[lo]);
+    const AnaArgs p = track_args(a, lo, a.s.tracks[lo]);
     const long long row0 = a.row0[lo];
     const int c = (int)(gc - a.log0[lo]);
     const int last = a.c.trim_cycles ? a.last_cycle[(long long)lo * a.s.E + e] : -1;
@@ -327,7 +334,7 @@ __global__ __launch_bounds__(kAnaThreads) void set_analysis_flags_kernel(const S
     const int t = blockIdx.x / a.s.E, e = blockIdx.x - t * a.s.E;
     if (threadIdx.x < 12) cnt[threadIdx.x] = 0;
     __syncthreads();
-    const AnaArgs p = track_args(a, a.s.tracks[t]);
+    const AnaArgs p = track_args(a, t, a.s.tracks[t]);
     const long long row0 = a.row0[t];
     const int last = a.c.trim_cycles ? a.last_cycle[blockIdx.x] : -1;
     for (long long r = threadIdx.x; r < p.v.R; r += kAnaThreads) {
@@ -335,11 +342,11 @@ __global__ __launch_bounds__(kAnaThreads) void set_analysis_flags_kernel(const S
         unsigned bits = 0u;
         if (ana_keep(p, w, last)) {
             // analysis_flags_kernel's statements, on the values calc_anomalies sees: after change_unit; a comparison with NaN is false
-            bits |= w.sp * a.c.speed_factor >= a.c.min_speed ? 1u : 0u;
+            bits |= w.sp * p.c.speed_factor >= a.c.min_speed ? 1u : 0u;
             bits |= w.err >= a.c.min_bbox_error ? 2u : 0u;
-            bits |= w.dev * a.c.dist_factor >= a.c.min_dist_error ? 4u : 0u;
-            bits |= w.ww * a.c.dist_factor >= a.c.min_width ? 8u : 0u;
-            bits |= w.wh * a.c.dist_factor >= a.c.min_height ? 16u : 0u;
+            bits |= w.dev * p.c.dist_factor >= a.c.min_dist_error ? 4u : 0u;
+            bits |= w.ww * p.c.dist_factor >= a.c.min_width ? 8u : 0u;
+            bits |= w.wh * p.c.dist_factor >= a.c.min_height ? 16u : 0u;
             const bool finite = isfinite(w.wx) && isfinite(w.wy) && isfinite(w.ww) && isfinite(w.wh);
             bits |= (a.c.no_preds && !finite) ? 32u : 0u;
             for (int k = 0; k < 6; ++k)
@@ -396,20 +403,27 @@ extern "C" int64_t wtk_replay_set_analysis_scratch_doubles(const wtk_replay_set_
     return set_ana_scratch(T, E);
 }
 
-extern "C" int wtk_replay_set_analyze(const wtk_replay_config *cfg, const wtk_replay_analysis_config *acfg, const wtk_replay_set_track *tracks_host,
-                                      const wtk_replay_set_track *tracks_dev, int32_t T, int32_t guard_cycles, int32_t E, const double *track_dev,
-                                      int32_t n_super, const double *share_dev, const int32_t *pos_dev, const int32_t *move_dev, const double *precise_rows_dev,
-                                      const int32_t *columns_host, int32_t n_cols, const double *percentiles_host, int32_t Q, int32_t max_lds_rows,
-                                      double *track_describe_dev, double *cycle_max_dev, double *cycle_mean_dev, double *track_step_quantiles_dev,
-                                      int32_t *track_step_count_dev, int64_t *track_anomaly_counts_dev, uint8_t *anomaly_mask_dev, int64_t *track_stats_dev,
-                                      double *describe_dev, double *step_quantiles_dev, int32_t *step_count_dev, int64_t *anomaly_counts_dev, int64_t *stats_dev,
-                                      double *scratch_dev, int64_t scratch_doubles, void *stream) {
-    const char *who = "wtk_replay_set_analyze";
+extern "C" int wtk_replay_set_analyze_geom(const wtk_replay_config *cfg, const wtk_replay_analysis_config *acfg, const wtk_replay_set_track *tracks_host,
+                                           const wtk_replay_set_track *tracks_dev, const wtk_replay_set_geometry *geom_host,
+                                           const wtk_replay_set_geometry *geom_dev, int32_t T, int32_t guard_cycles, int32_t E, const double *track_dev,
+                                           int32_t n_super, const double *share_dev, const int32_t *pos_dev, const int32_t *move_dev,
+                                           const double *precise_rows_dev, const int32_t *columns_host, int32_t n_cols, const double *percentiles_host,
+                                           int32_t Q, int32_t max_lds_rows, double *track_describe_dev, double *cycle_max_dev, double *cycle_mean_dev,
+                                           double *track_step_quantiles_dev, int32_t *track_step_count_dev, int64_t *track_anomaly_counts_dev,
+                                           uint8_t *anomaly_mask_dev, int64_t *track_stats_dev, double *describe_dev, double *step_quantiles_dev,
+                                           int32_t *step_count_dev, int64_t *anomaly_counts_dev, int64_t *stats_dev, double *scratch_dev,
+                                           int64_t scratch_doubles, void *stream) {
+    const char *who = geom_host || geom_dev ? "wtk_replay_set_analyze_geom" : "wtk_replay_set_analyze";
     const std::string w(who);
     SetAnaArgs a = {};
     int min_log = 0;
     if (!acfg) return fail(w + ": null argument");
-    if (set_view(who, cfg, tracks_host, tracks_dev, T, guard_cycles, WTK_REPLAY_OPTIMAL, E, track_dev, n_super, share_dev, pos_dev, move_dev, a.s, min_log)) return 1;
+    if (set_view(who, cfg, tracks_host, tracks_dev, geom_host, geom_dev, T, guard_cycles, WTK_REPLAY_OPTIMAL, E, track_dev, n_super, share_dev, pos_dev, move_dev, a.s,
+                 min_log))
+        return 1;
+    for (int t = 0; geom_host && t < T; ++t)
+        if (!std::isfinite(geom_host[t].time_factor) || !std::isfinite(geom_host[t].dist_factor) || !std::isfinite(geom_host[t].speed_factor))
+            return fail(w + ": track " + std::to_string(t) + ": the unit factors must be finite");
     if (!scratch_dev) return fail(w + ": null argument");
     if (analysis_spec(w, acfg, columns_host, n_cols, percentiles_host, Q, max_lds_rows, precise_rows_dev != nullptr, "precise_rows_dev", a.cols, a.q)) return 1;
     long long rows = 0, logs = 0, max_rows = 0, max_logs = 0;
@@ -465,4 +479,19 @@ extern "C" int wtk_replay_set_analyze(const wtk_replay_config *cfg, const wtk_re
     }
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+// (no geometry table: cfg's sizes and acfg's factors for every track)
+extern "C" int wtk_replay_set_analyze(const wtk_replay_config *cfg, const wtk_replay_analysis_config *acfg, const wtk_replay_set_track *tracks_host,
+                                      const wtk_replay_set_track *tracks_dev, int32_t T, int32_t guard_cycles, int32_t E, const double *track_dev,
+                                      int32_t n_super, const double *share_dev, const int32_t *pos_dev, const int32_t *move_dev, const double *precise_rows_dev,
+                                      const int32_t *columns_host, int32_t n_cols, const double *percentiles_host, int32_t Q, int32_t max_lds_rows,
+                                      double *track_describe_dev, double *cycle_max_dev, double *cycle_mean_dev, double *track_step_quantiles_dev,
+                                      int32_t *track_step_count_dev, int64_t *track_anomaly_counts_dev, uint8_t *anomaly_mask_dev, int64_t *track_stats_dev,
+                                      double *describe_dev, double *step_quantiles_dev, int32_t *step_count_dev, int64_t *anomaly_counts_dev, int64_t *stats_dev,
+                                      double *scratch_dev, int64_t scratch_doubles, void *stream) {
+    return wtk_replay_set_analyze_geom(cfg, acfg, tracks_host, tracks_dev, nullptr, nullptr, T, guard_cycles, E, track_dev, n_super, share_dev, pos_dev, move_dev,
+                                       precise_rows_dev, columns_host, n_cols, percentiles_host, Q, max_lds_rows, track_describe_dev, cycle_max_dev, cycle_mean_dev,
+                                       track_step_quantiles_dev, track_step_count_dev, track_anomaly_counts_dev, anomaly_mask_dev, track_stats_dev, describe_dev,
+                                       step_quantiles_dev, step_count_dev, anomaly_counts_dev, stats_dev, scratch_dev, scratch_doubles, stream);
 }

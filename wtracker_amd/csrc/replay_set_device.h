@@ -9,6 +9,7 @@ namespace wtk {
 struct SetArgs {
     Geometry g; // x_max / y_max are each track's own
     const wtk_replay_set_track *tracks; // [T] on the device
+    const wtk_replay_set_geometry *geom; // [T] on the device (nullable: g's camera and microscope for every track)
     int T, E, kind;
     int S; // chunks of all tracks
     const double *track; // the super-track
@@ -25,24 +26,32 @@ struct SetArgs {
     const int *stop;
 };
 
-__device__ __forceinline__ Geometry track_geometry(const SetArgs &a, const wtk_replay_set_track &tr) {
+// The ONE place a track's Geometry is made: the set's cycle structure, the track's own clamp and, where the set has a geometry table (DESIGN.md section
+// 29), the track's own camera and microscope.  `t` is uniform wherever this is called, so the branch and the loads stay scalar.
+__device__ __forceinline__ Geometry track_geometry(const SetArgs &a, int t, const wtk_replay_set_track &tr) {
     Geometry g = a.g;
     g.x_max = tr.x_max, g.y_max = tr.y_max;
+    if (a.geom) {
+        const wtk_replay_set_geometry tg = a.geom[t];
+        g.cam_w = tg.cam_w, g.cam_h = tg.cam_h, g.mic_w = tg.mic_w, g.mic_h = tg.mic_h;
+    }
     return g;
 }
 
-// track `tr` of the set as a scanned population: the super-track and the scan's arrays from the track's offset on, the track's own clamp and counts
-__device__ __forceinline__ ReplayView track_view(const SetArgs &a, const wtk_replay_set_track &tr) {
+// track t (entry `tr`) of the set as a scanned population: the super-track and the scan's arrays from the track's offset on, the track's own geometry and counts
+__device__ __forceinline__ ReplayView track_view(const SetArgs &a, int t, const wtk_replay_set_track &tr) {
     const long long c0 = (long long)tr.cyc_off * a.E;
     ReplayView v;
-    v.g = track_geometry(a, tr), v.E = a.E, v.C = tr.n_cycles, v.n_log = tr.n_log, v.R = tr.R;
+    v.g = track_geometry(a, t, tr), v.E = a.E, v.C = tr.n_cycles, v.n_log = tr.n_log, v.R = tr.R;
     v.track = a.track + 4 * (long long)tr.cyc_off * a.g.L, v.share = a.share, v.pos = a.pos + 2 * c0, v.move = a.move + 2 * c0;
     return v;
 }
 
 // The checks of the table every entry point shares: each track as replay_view sees it (reported with its index), the derived fields, the slots and
-// guards.  Leaves the shared geometry in a.g, the chunk count in a.S and the smallest n_log in min_log.
-int set_view(const char *who, const wtk_replay_config *cfg, const wtk_replay_set_track *host, const wtk_replay_set_track *dev, int32_t T, int32_t guard_cycles,
+// guards.  Leaves the shared geometry in a.g, the chunk count in a.S and the smallest n_log in min_log.  geom_host / geom_dev: the per-track geometry
+// table or both null; with it every track is checked with its own camera and microscope (a.g then holds the last track's: track_geometry overrides them).
+int set_view(const char *who, const wtk_replay_config *cfg, const wtk_replay_set_track *host, const wtk_replay_set_track *dev,
+             const wtk_replay_set_geometry *geom_host, const wtk_replay_set_geometry *geom_dev, int32_t T, int32_t guard_cycles,
              int32_t kind, int32_t E, const double *track_dev, int32_t n_super, const double *share_dev, const int32_t *pos_dev, const int32_t *move_dev, SetArgs &a,
              int &min_log);
 

@@ -64,6 +64,10 @@ class _ReplaySetFrames(C.Structure):
                 ("W", C.c_int32), ("reserved", C.c_int32)]
 
 
+class _ReplaySetGeometry(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("cam_w", "cam_h", "mic_w", "mic_h")] + [(n, C.c_double) for n in ("time_factor", "dist_factor", "speed_factor")]
+
+
 class _AnalysisConfig(C.Structure):
     _fields_ = ([("bounds", C.c_double * 4)] + [(n, C.c_double) for n in ("time_factor", "dist_factor", "speed_factor", "min_speed", "min_bbox_error",
                                                                           "min_dist_error", "min_width", "min_height")]
@@ -81,6 +85,7 @@ _pvp, _pi32, _pi64, _pf32, _pf64, _pcfg = C.POINTER(_vp), C.POINTER(_i32), C.POI
 _pacfg = C.POINTER(_AnalysisConfig)
 _ptrk = C.POINTER(_ReplaySetTrack)
 _pfrm = C.POINTER(_ReplaySetFrames)
+_pgeo = C.POINTER(_ReplaySetGeometry)
 
 # The C ABI, one row per symbol of include/wtk_hip.h and in its order: name -> (restype, argtypes).  load() applies it and nothing else declares a
 # signature; tests/test_abi.py compares every row with the header's prototype, kind by kind (pointer, int32, int64, size_t, float, double).
@@ -175,8 +180,18 @@ SIGNATURES = {
     "wtk_replay_set_precise": (_i32, [_pcfg, _ptrk, _vp, _pfrm, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "wtk_replay_set_precise_objective": (_i32, [_pcfg, _ptrk, _vp, _pfrm, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp,
                                                 _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "wtk_replay_set_scan_geom": (_i32, [_pcfg, _ptrk, _vp, _pgeo, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "wtk_replay_set_rows_geom": (_i32, [_pcfg, _ptrk, _vp, _pgeo, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "wtk_replay_set_objective_geom": (_i32, [_pcfg, _ptrk, _vp, _pgeo, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
+                                             _i32, _vp, _vp, _vp, _vp]),
+    "wtk_replay_set_precise_geom": (_i32, [_pcfg, _ptrk, _vp, _pgeo, _vp, _pfrm, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp,
+                                           _i64, _vp, _vp]),
+    "wtk_replay_set_precise_objective_geom": (_i32, [_pcfg, _ptrk, _vp, _pgeo, _vp, _pfrm, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                     _i32, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     "wtk_replay_mlp_targets": (_i32, [C.POINTER(_MlpTrainLayer), _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _f32, _vp, _vp, _vp, _vp, _vp]),
     "wtk_replay_mlp_targets_waves": (_i32, [_i64]),
+    "wtk_replay_mlp_targets_bounds": (_i32, [C.POINTER(_MlpTrainLayer), _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp,
+                                             _vp]),
     "wtk_replay_yolo_step": (_i32, [_pcfg, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "wtk_replay_yolo_positions": (_i32, [_pcfg, _i32, _vp, _vp, _vp, _vp, _vp]),
     "wtk_replay_yolo_track": (_i32, [_pcfg, _i32, _vp, _vp, _vp, _vp]),
@@ -188,6 +203,8 @@ SIGNATURES = {
     "wtk_replay_set_analysis_scratch_doubles": (_i64, [_ptrk, _i32, _i32, _i32, _i32, _i32]),
     "wtk_replay_set_analyze": (_i32, [_pcfg, _pacfg, _ptrk, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp,
                                       _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "wtk_replay_set_analyze_geom": (_i32, [_pcfg, _pacfg, _ptrk, _vp, _pgeo, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp,
+                                           _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "wtk_replay_precise_scratch_doubles": (_i64, [_i32, _i64]),
     "wtk_replay_precise": (_i32, [_pcfg, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _f64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "wtk_replay_precise_objective": (_i32, [_pcfg, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _f64, _i32, _vp, _vp,
@@ -575,10 +592,39 @@ class ReplaySetTable:
         return self.host, _ptr(self.dev), self.T, self.guard_cycles
 
 
+class ReplaySetGeometry:
+    """The per-track geometry table of a set (wtk_replay_set_geometry [T]), beside its ReplaySetTable: `host` the ctypes array the entry points check,
+    `dev` the same bytes on the device (uploaded here, once).  `entries`: per track a dict of cam (w, h), mic (w, h) in pixels and factors (time,
+    distance, speed) of change_unit.  Passed as `geom=` to the replay_set_* calls; None there means the config's sizes for every track."""
+
+    def __init__(self, entries: Sequence[dict], device=None):
+        self.T = len(entries)
+        self.host = (_ReplaySetGeometry * max(1, self.T))()
+        for t, g in enumerate(entries):
+            (cw, ch), (mw, mh), (tf, df, sf) = g["cam"], g["mic"], g["factors"]
+            self.host[t] = _ReplaySetGeometry(int(cw), int(ch), int(mw), int(mh), float(tf), float(df), float(sf))
+        self.dev = None
+        if device is not None:
+            import torch
+
+            raw = np.frombuffer(bytes(self.host), dtype=np.uint8).copy()
+            self.dev = torch.from_numpy(raw).to(device)
+
+
+def _geom_args(table: ReplaySetTable, geom: Optional[ReplaySetGeometry]):
+    """(tracks_host, tracks_dev, geom_host, geom_dev, T, guard_cycles) of a *_geom entry point."""
+    if geom is not None and geom.T != table.T:
+        raise WtkError(f"the geometry table needs one entry per track: {table.T} tracks, {geom.T} entries")
+    host, dev, T, guard = table._args()
+    return host, dev, (geom.host if geom is not None else None), (_ptr(geom.dev) if geom is not None else None), T, guard
+
+
 def replay_set_scan(cfg: _ReplayConfig, table: ReplaySetTable, kind: int, E: int, track_dev, a_dev, b_dev, valid_dev, share_dev, pos_dev, move_dev, stop_dev=None,
-                    stream: int = 0):
-    """wtk_replay_scan of every (track, experiment) of a set (wtk_replay_set_scan); per-cycle arrays are [n_super / L, E, ...] device tensors."""
-    _check(load().wtk_replay_set_scan(C.byref(cfg) if cfg is not None else None, *table._args(), kind, E, _ptr(track_dev), table.n_super, _ptr(a_dev),
+                    stream: int = 0, geom: Optional[ReplaySetGeometry] = None):
+    """wtk_replay_scan of every (track, experiment) of a set (wtk_replay_set_scan); per-cycle arrays are [n_super / L, E, ...] device tensors.
+    `geom` (here and in the calls below): the set's ReplaySetGeometry, which selects the *_geom entry point of the same name."""
+    fn, head = (load().wtk_replay_set_scan, table._args()) if geom is None else (load().wtk_replay_set_scan_geom, _geom_args(table, geom))
+    _check(fn(C.byref(cfg) if cfg is not None else None, *head, kind, E, _ptr(track_dev), table.n_super, _ptr(a_dev),
                                       _ptr(b_dev), _ptr(valid_dev), _ptr(share_dev), _ptr(pos_dev), _ptr(move_dev), _ptr(stop_dev), C.c_void_p(stream)),
            "wtk_replay_set_scan")
 
@@ -588,19 +634,21 @@ def replay_set_scratch_doubles(table: ReplaySetTable, E: int) -> int:
 
 
 def replay_set_rows(cfg: _ReplayConfig, table: ReplaySetTable, E: int, track_dev, share_dev, pos_dev, move_dev, track_summary_dev, summary_dev, scratch_dev,
-                    scratch_doubles: int, stop_dev=None, stream: int = 0):
+                    scratch_doubles: int, stop_dev=None, stream: int = 0, geom: Optional[ReplaySetGeometry] = None):
     """Per-track summaries [T, E, 6] and the pooled summary [E, 6] from a set scan's positions and moves (wtk_replay_set_rows)."""
-    _check(load().wtk_replay_set_rows(C.byref(cfg) if cfg is not None else None, *table._args(), E, _ptr(track_dev), table.n_super, _ptr(share_dev),
+    fn, head = (load().wtk_replay_set_rows, table._args()) if geom is None else (load().wtk_replay_set_rows_geom, _geom_args(table, geom))
+    _check(fn(C.byref(cfg) if cfg is not None else None, *head, E, _ptr(track_dev), table.n_super, _ptr(share_dev),
                                       _ptr(pos_dev), _ptr(move_dev), _ptr(track_summary_dev), _ptr(summary_dev), _ptr(scratch_dev), scratch_doubles,
                                       _ptr(stop_dev), C.c_void_p(stream)), "wtk_replay_set_rows")
 
 
 def replay_set_objective(cfg: _ReplayConfig, table: ReplaySetTable, kind: int, E: int, track_dev, a_dev, b_dev, valid_dev, share_dev, pos_dev, move_dev,
                          track_summary_dev, summary_dev, scratch_dev, scratch_doubles: int, objective: int, objective_dev, track_objective_dev=None,
-                         stop_dev=None, stream: int = 0):
+                         stop_dev=None, stream: int = 0, geom: Optional[ReplaySetGeometry] = None):
     """objective_dev[e] = the chosen closed-loop error of experiment e pooled over the set's tracks (wtk_replay_set_objective); track_objective_dev
     [T, E] (optional): the same of each track."""
-    _check(load().wtk_replay_set_objective(C.byref(cfg) if cfg is not None else None, *table._args(), kind, E, _ptr(track_dev), table.n_super, _ptr(a_dev),
+    fn, head = (load().wtk_replay_set_objective, table._args()) if geom is None else (load().wtk_replay_set_objective_geom, _geom_args(table, geom))
+    _check(fn(C.byref(cfg) if cfg is not None else None, *head, kind, E, _ptr(track_dev), table.n_super, _ptr(a_dev),
                                            _ptr(b_dev), _ptr(valid_dev), _ptr(share_dev), _ptr(pos_dev), _ptr(move_dev), _ptr(track_summary_dev),
                                            _ptr(summary_dev), _ptr(scratch_dev), scratch_doubles, objective, _ptr(objective_dev), _ptr(track_objective_dev),
                                            _ptr(stop_dev), C.c_void_p(stream)), "wtk_replay_set_objective")
@@ -641,11 +689,12 @@ def replay_set_precise_scratch_doubles(table: ReplaySetTable, E: int) -> int:
 
 
 def replay_set_precise(cfg: _ReplayConfig, table: ReplaySetTable, frames: ReplaySetFrames, E: int, track_dev, share_dev, pos_dev, move_dev, max_crop_px: int,
-                       err_dev, counts_dev, track_summary_dev, summary_dev, scratch_dev, scratch_doubles: int, stop_dev=None, stream: int = 0):
+                       err_dev, counts_dev, track_summary_dev, summary_dev, scratch_dev, scratch_doubles: int, stop_dev=None, stream: int = 0,
+                       geom: Optional[ReplaySetGeometry] = None):
     """The precise error of every (track, experiment, logged frame) of a set scan (wtk_replay_set_precise): per-track summaries [T, E, 6], the pooled
     summary [E, 6]; err_dev float64 [E, sum R] and counts_dev int32 [E, sum R, 2] or None."""
-    host, dev, T, guard = table._args()
-    _check(load().wtk_replay_set_precise(C.byref(cfg) if cfg is not None else None, host, dev, *frames._args(), T, guard, E, _ptr(track_dev), table.n_super,
+    fn, (*head, T, guard) = (load().wtk_replay_set_precise, table._args()) if geom is None else (load().wtk_replay_set_precise_geom, _geom_args(table, geom))
+    _check(fn(C.byref(cfg) if cfg is not None else None, *head, *frames._args(), T, guard, E, _ptr(track_dev), table.n_super,
                                          _ptr(share_dev), _ptr(pos_dev), _ptr(move_dev), int(max_crop_px), _ptr(err_dev), _ptr(counts_dev),
                                          _ptr(track_summary_dev), _ptr(summary_dev), _ptr(scratch_dev), scratch_doubles, _ptr(stop_dev), C.c_void_p(stream)),
            "wtk_replay_set_precise")
@@ -653,11 +702,13 @@ def replay_set_precise(cfg: _ReplayConfig, table: ReplaySetTable, frames: Replay
 
 def replay_set_precise_objective(cfg: _ReplayConfig, table: ReplaySetTable, frames: ReplaySetFrames, kind: int, E: int, track_dev, a_dev, b_dev, valid_dev,
                                  share_dev, pos_dev, move_dev, max_crop_px: int, track_summary_dev, summary_dev, scratch_dev, scratch_doubles: int,
-                                 objective: int, objective_dev, track_objective_dev=None, stop_dev=None, stream: int = 0):
+                                 objective: int, objective_dev, track_objective_dev=None, stop_dev=None, stream: int = 0,
+                                 geom: Optional[ReplaySetGeometry] = None):
     """objective_dev[e] = the chosen precise-error figure of experiment e pooled over the set's tracks (wtk_replay_set_precise_objective);
     track_objective_dev [T, E] (optional): the same of each track."""
-    host, dev, T, guard = table._args()
-    _check(load().wtk_replay_set_precise_objective(C.byref(cfg) if cfg is not None else None, host, dev, *frames._args(), T, guard, kind, E, _ptr(track_dev),
+    fn, (*head, T, guard) = ((load().wtk_replay_set_precise_objective, table._args()) if geom is None
+                             else (load().wtk_replay_set_precise_objective_geom, _geom_args(table, geom)))
+    _check(fn(C.byref(cfg) if cfg is not None else None, *head, *frames._args(), T, guard, kind, E, _ptr(track_dev),
                                                    table.n_super, _ptr(a_dev), _ptr(b_dev), _ptr(valid_dev), _ptr(share_dev), _ptr(pos_dev), _ptr(move_dev),
                                                    int(max_crop_px), _ptr(track_summary_dev), _ptr(summary_dev), _ptr(scratch_dev), scratch_doubles, objective,
                                                    _ptr(objective_dev), _ptr(track_objective_dev), _ptr(stop_dev), C.c_void_p(stream)),
@@ -729,7 +780,7 @@ def replay_set_analysis_scratch_doubles(table: ReplaySetTable, E: int, n_cols: i
 
 def replay_set_analyze(cfg: _ReplayConfig, acfg: _AnalysisConfig, table: ReplaySetTable, E: int, track_dev, share_dev, pos_dev, move_dev, precise_rows_dev,
                        columns: Sequence[int], percentiles: Sequence[float], max_lds_rows: int, track_outputs: Sequence, pooled_outputs: Sequence, scratch_dev,
-                       scratch_doubles: int, stream: int = 0):
+                       scratch_doubles: int, stream: int = 0, geom: Optional[ReplaySetGeometry] = None):
     """DataAnalyzer's statistics of every (track, experiment) of a set scan and of every experiment over the concatenation of its logs
     (wtk_replay_set_analyze).  `track_outputs`: the eight per-track device tensors or None, in the header's order: describe [T, E, n_cols, 5 + Q],
     cycle_max / cycle_mean [E, sum n_log, n_cols], step_quantiles [T, E, L, n_cols, Q], step_count [T, E, L, n_cols] int32, anomaly_counts [T, E, 7]
@@ -738,8 +789,8 @@ def replay_set_analyze(cfg: _ReplayConfig, acfg: _AnalysisConfig, table: ReplayS
     if len(track_outputs) != 8 or len(pooled_outputs) != 5:
         raise WtkError("wtk_replay_set_analyze takes eight per-track and five pooled outputs (None where one is not wanted)")
     cols, q = np.ascontiguousarray(columns, dtype=np.int32), np.ascontiguousarray(percentiles, dtype=np.float64)
-    host, dev, T, guard = table._args()
-    _check(load().wtk_replay_set_analyze(C.byref(cfg) if cfg is not None else None, C.byref(acfg) if acfg is not None else None, host, dev, T, guard, E,
+    fn, head = (load().wtk_replay_set_analyze, table._args()) if geom is None else (load().wtk_replay_set_analyze_geom, _geom_args(table, geom))
+    _check(fn(C.byref(cfg) if cfg is not None else None, C.byref(acfg) if acfg is not None else None, *head, E,
                                          _ptr(track_dev), table.n_super, _ptr(share_dev), _ptr(pos_dev), _ptr(move_dev), _ptr(precise_rows_dev), _ptr(cols),
                                          len(cols), _ptr(q), len(q), int(max_lds_rows), *(_ptr(t) for t in track_outputs), *(_ptr(t) for t in pooled_outputs),
                                          _ptr(scratch_dev), scratch_doubles, C.c_void_p(stream)), "wtk_replay_set_analyze")
@@ -791,8 +842,15 @@ def mlp_fold_state_host(layers, n_blocks: int, layers_per_block: int, state: np.
 
 def replay_mlp_targets(layers, n_blocks: int, layers_per_block: int, blob_dev, E: int, track32_dev, track_dev, n_track: int, anchors_dev, n_cycles: int,
                        input_frames: Sequence[int], bound: float, a_dev, b_dev, valid_dev, stop_dev=None, stream: int = 0):
-    """MLP targets of E device-resident folded models in one call (wtk_replay_mlp_targets): a_dev, b_dev [n_cycles, E, 2], valid_dev [n_cycles, E]."""
+    """MLP targets of E device-resident folded models in one call (wtk_replay_mlp_targets): a_dev, b_dev [n_cycles, E, 2], valid_dev [n_cycles, E].
+    `bound`: the clip bound of every cycle as a float, or a device float32 [n_cycles] tensor of per-cycle bounds (wtk_replay_mlp_targets_bounds)."""
     inf = np.ascontiguousarray(input_frames, dtype=np.int32)
+    if hasattr(bound, "data_ptr"):
+        _check(load().wtk_replay_mlp_targets_bounds(layers, len(layers), int(n_blocks), int(layers_per_block), _ptr(blob_dev), int(E), _ptr(track32_dev),
+                                                    _ptr(track_dev), int(n_track), _ptr(anchors_dev), int(n_cycles), _ptr(inf), len(inf), _ptr(bound),
+                                                    _ptr(a_dev), _ptr(b_dev), _ptr(valid_dev), _ptr(stop_dev), C.c_void_p(stream)),
+               "wtk_replay_mlp_targets_bounds")
+        return
     _check(load().wtk_replay_mlp_targets(layers, len(layers), int(n_blocks), int(layers_per_block), _ptr(blob_dev), int(E), _ptr(track32_dev), _ptr(track_dev),
                                          int(n_track), _ptr(anchors_dev), int(n_cycles), _ptr(inf), len(inf), C.c_float(bound), _ptr(a_dev), _ptr(b_dev),
                                          _ptr(valid_dev), _ptr(stop_dev), C.c_void_p(stream)), "wtk_replay_mlp_targets")

@@ -64,6 +64,13 @@ concatenation of all logs, as the reference's Plotter takes them; a percentile o
     res = rs.run_analysis(tg, spec)                                     # res.analysis.pooled.describe [E, n_cols, 5 + Q]; .track[t] = rs.replay(t)'s bits
     rs.analyze(tg, spec)                                                # the same as device tensors, no synchronisation; precise=True: precise_error
 
+Recordings taken at different scales: one TimingConfig per track, as the reference derives the camera and microscope sizes in
+pixels, the MLP's clip bound and change_unit's factors from each recording's own px_per_mm; everything above works unchanged, pair by pair with the
+bits of `Replay(track_t, timing_configs[t], experiment_configs[t])`.  The same recording entered with G microscope sizes is a field-of-view sweep:
+
+    rs = ReplaySet.from_experiments(tracks, [ec0, ec1, ec2], 200, 40, 50, camera_size_mm=(4, 4), micro_size_mm=(0.32, 0.32))   # or ReplaySet(tracks, [tc0, tc1, tc2], ecs)
+    ReplaySet([track] * 4, [tc_small, tc_mid, tc_large, tc_huge], ec).objective(tg, "bbox_error", per_track=True)              # [4, E]
+
 There is no CPU fallback: without a visible GPU the constructors raise.  Not covered: `StepMotorController`, DataAnalyzer's `remove_cycle` and
 `save` / `load`, the plots themselves, the YOLO controller's second look (YoloConfig.recheck_margin).
 """
@@ -101,6 +108,26 @@ def polyfit_classes(track: np.ndarray, cycle_frame_num: int, n_cycles: int, samp
     masks = (finite.astype(np.int64) << np.arange(len(st), dtype=np.int64)[None, :]).sum(axis=1)
     class_mask, cycle_class = np.unique(masks, return_inverse=True)
     return cycle_class.reshape(-1).astype(np.int32), class_mask.astype(np.int32)
+
+
+def check_timing_configs(timing_configs, T: int) -> list:
+    """The T TimingConfigs of a ReplaySet's tracks as a list.  The tracks of a set share ONE cycle structure (the super-track, the [n_super_cycles, E]
+    arrays and every targets call rest on one cycle length), so the three frame counts must be equal; the sizes and px_per_mm may differ.  Refused,
+    naming the track: another number of configs than tracks, frame counts that differ from track 0's, a camera smaller than the microscope."""
+    tcs = list(timing_configs)
+    if len(tcs) != T:
+        raise ValueError(f"{T} tracks: timing_config must be one TimingConfig or a sequence of {T}, got {len(tcs)}")
+    counts = lambda tc: (int(tc.imaging_frame_num), int(tc.moving_frame_num), int(tc.pred_frame_num))  # noqa: E731
+    for t, tc in enumerate(tcs):
+        if not isinstance(tc, TimingConfig):
+            raise ValueError(f"track {t}: timing_config must hold TimingConfigs, got {type(tc).__name__}")
+        if counts(tc) != counts(tcs[0]):
+            raise ValueError(f"track {t}: (imaging_frame_num, moving_frame_num, pred_frame_num) = {counts(tc)}, track 0 has {counts(tcs[0])}: the tracks of a "
+                             "set share one cycle structure (per-track frame counts are not supported)")
+        cam, mic = tuple(int(v) for v in tc.camera_size_px), tuple(int(v) for v in tc.micro_size_px)
+        if cam[0] < mic[0] or cam[1] < mic[1] or min(mic) < 0:
+            raise ValueError(f"track {t}: the camera {cam} is smaller than the microscope {mic}")
+    return tcs
 
 
 def mlp_clip_bound(timing_config: TimingConfig, max_speed: float, pred_frames) -> float:
@@ -250,7 +277,9 @@ class Analysis:
     `bounds` (x0, y0, x1, y1) of clean (trim_cycles drops cycle 0 and the largest cycle that survives the other two filters); `unit` "frame" or "sec"
     of change_unit; `columns` (names of ANALYSIS_COLUMNS) and `percentiles` (in [0, 1]) of describe and of the per-cycle and per-cycle-step
     aggregates; the thresholds of calc_anomalies (`min_size` for both sides of the worm box; inf = off), applied to the unit-changed values.
-    `anomaly_mask`: also return the per-row bit flags [E, R]."""
+    `anomaly_mask`: also return the per-row bit flags [E, R].  On a ReplaySet with one TimingConfig per track the unit factors are each track's own
+    (`factors(rs.timing_configs)`), and the thresholds are compared with the values so converted; `bounds` stays ONE rectangle in pixels for all tracks
+    (each recording's platform moves in its own frame: give bounds that fit all of them, or analyse a track alone with `rs.replay(t)`)."""
 
     period: int = 10
     trim_cycles: bool = False
@@ -274,8 +303,11 @@ class Analysis:
             raise ValueError(f"at most {hip.ANALYSIS_MAX_COLUMNS} columns and {hip.ANALYSIS_MAX_PERCENTILES} percentiles")
         return [ANALYSIS_COLUMNS.index(c) for c in self.columns]
 
-    def factors(self, timing_config: TimingConfig) -> tuple:
-        """(time, distance, speed) factors of change_unit(unit), as the reference computes them."""
+    def factors(self, timing_config) -> tuple:
+        """(time, distance, speed) factors of change_unit(unit), as the reference computes them from the log's own TimingConfig.  A sequence of
+        configs (a ReplaySet's `timing_configs`) gives the list of one triple per track: every log of a set is converted with its own."""
+        if not isinstance(timing_config, TimingConfig):
+            return [self.factors(tc) for tc in timing_config]
         if self.unit == "frame":
             return (1.0, 1.0, 1.0)
         if self.unit != "sec":
@@ -525,7 +557,7 @@ class Replay:
         import torch
 
         folded: FoldedResMLP = model if isinstance(model, FoldedResMLP) else from_torch_module(model)
-        bound = mlp_clip_bound(self.timing_config, max_speed, folded.pred_frames)
+        bound = self._mlp_bound(max_speed, folded.pred_frames)
         net = hip.HipMLP(folded.layers, folded.n_blocks, folded.layers_per_block, device=self._dev.index)
         a, b, valid, pred, ok = self._empty(1, with_b=True, pred_dtype=torch.float32)
         with torch.cuda.device(self._dev):
@@ -533,6 +565,8 @@ class Replay:
                 self._track_f32 = self.track.to(torch.float32).contiguous()
             anchors = (self._cycles * self.L + (self.I - self.P)).contiguous()
             net.predict_track(self._track_f32, self.n_track, anchors, self.n_cycles, list(folded.input_frames), pred, ok, stream=self._stream())
+            if hasattr(bound, "data_ptr"):  # a set with per-track configs: one bound per cycle
+                bound = bound[:, None]
             a[:, 0] = torch.clamp(pred, -bound, bound).to(torch.float64)
             first = (anchors.to(torch.int64) + int(list(folded.input_frames)[0])).clamp(0, self.n_track - 1)  # only read where the sample is valid
             b[:, 0] = self.track[first, :2]
@@ -568,7 +602,7 @@ class Replay:
                 raise ValueError(f"the replay takes predictors of one frame (out_dim 2), the models have out_dim {f0.out_dim}")
             layers, n_blocks, per_block = hip.mlp_structure([(w.shape[1], w.shape[0], r) for w, _, r in f0.layers]), f0.n_blocks, f0.layers_per_block
             blob = torch.from_numpy(np.stack([pack_blob(f) for f in folded])).to(self._dev)
-        bound = mlp_clip_bound(self.timing_config, max_speed, yi)
+        bound = self._mlp_bound(max_speed, yi)
         dev, C = self._dev, self.n_cycles
         tg = Targets("mlp", E, torch.empty((C, E, 2), dtype=torch.float64, device=dev), torch.empty((C, E, 2), dtype=torch.float64, device=dev),
                      torch.empty((C, E), dtype=torch.int32, device=dev), keep=blob)
@@ -580,6 +614,10 @@ class Replay:
             hip.replay_mlp_targets(layers, n_blocks, per_block, blob, E, self._track_f32, self.track, self.n_track, self._anchors, C, xi, bound, tg.a, tg.b,
                                    tg.valid, stream=self._stream())
         return tg
+
+    def _mlp_bound(self, max_speed: float, pred_frames):
+        """The clip bound of `mlp` / `mlp_population`: one float for every cycle (a ReplaySet's super-track: a device float32 [n_cycles] tensor)."""
+        return mlp_clip_bound(self.timing_config, max_speed, pred_frames)
 
     # ------------------------------------------------------------------ populations of weight vectors
     def _sample_times(self, sample_times) -> tuple:
@@ -843,6 +881,9 @@ class _SuperTrack(Replay):
     def _enqueue_objective(self, targets: Targets, kind: int, buf: dict, out, stop_dev=None):
         self._set._enqueue_objective(targets, kind, buf, out, stop_dev=stop_dev)
 
+    def _mlp_bound(self, max_speed: float, pred_frames):
+        return self._set._mlp_bounds(max_speed, pred_frames)
+
 
 class ReplaySet:
     """The closed loop of a population of controller configurations on SEVERAL tracks at once, with an objective pooled over them (DESIGN.md section
@@ -855,7 +896,10 @@ class ReplaySet:
         rs.optimize_polyfit(1, offsets, start=[...], seed=0)    # Replay.optimize_polyfit's search over the pooled objective
         trainer.fit(..., closed_loop=rs)
 
-    `tracks`: what `Replay` takes, one per track.  All tracks share `timing_config`; `experiment_configs` is one ExperimentConfig or one per track
+    `tracks`: what `Replay` takes, one per track.  `timing_config` is one TimingConfig for all tracks or a sequence of one per track (DESIGN.md
+    section 29; `from_experiments` builds them from the ExperimentConfigs): camera size, microscope size, the MLP's clip bound and the analysis' unit
+    factors are then each track's own, while the three frame counts must be equal (one cycle structure: a set that differs in them is refused, naming
+    the track).  `timing_configs` is the list, `timing_config` its first entry.  `experiment_configs` is one ExperimentConfig or one per track
     (num_frames, init_position and the default frame shape are each track's own), `frame_shapes` None or one (H, W) / None per track.  On the device
     the tracks lie in one float64 [N, 4] "super-track": track t from row cyc_off[t] L, NaN rows up to the end of its whole-cycle slot, then
     ceil(reach / L) all-NaN guard cycles.  The targets entry points treat a NaN row as a row outside the track, so one call over the super-track gives
@@ -869,7 +913,7 @@ class ReplaySet:
     `rs.run(tg, precise=True)`, the search and the trainer's closed loop with a precise objective.  The analysis of the set, per log and over the
     concatenation of all logs, is `rs.analyze(tg, spec)` / `rs.run_analysis(tg, spec)`.  Logs stay with `rs.replay(t)`."""
 
-    def __init__(self, tracks, timing_config: TimingConfig, experiment_configs, frame_shapes=None, reach: Optional[int] = None, device: int = 0):
+    def __init__(self, tracks, timing_config, experiment_configs, frame_shapes=None, reach: Optional[int] = None, device: int = 0):
         if hip.device_count() < 1:
             raise hip.WtkError("ReplaySet needs a GPU: no HIP device visible (there is no CPU fallback)")
         import dataclasses
@@ -884,9 +928,20 @@ class ReplaySet:
         shapes = [None] * T if frame_shapes is None else list(frame_shapes)
         if len(ecs) != T or len(shapes) != T:
             raise ValueError(f"{T} tracks: experiment_configs must be one config or {T}, frame_shapes None or {T}")
-        self.timing_config, self.experiment_configs, self.T = timing_config, ecs, T
+        # one TimingConfig for all tracks, or one per track: then every kernel reads the track's sizes from a geometry table
+        self._per_track = not isinstance(timing_config, TimingConfig)
+        tcs = check_timing_configs(timing_config, T) if self._per_track else [timing_config] * T
+        self.timing_configs, self.timing_config, self.experiment_configs, self.T = tcs, tcs[0], ecs, T
         self._dev = torch.device("cuda", device)
-        self._replays = [Replay(tr, timing_config, ec, fs, device) for tr, ec, fs in zip(tracks, ecs, shapes)]
+        self._replays = []
+        for t, (tr, tc, ec, fs) in enumerate(zip(tracks, tcs, ecs, shapes)):
+            try:
+                self._replays.append(Replay(tr, tc, ec, fs, device))
+            except ValueError as err:
+                if not self._per_track:
+                    raise
+                raise ValueError(f"track {t}: {err}") from None
+        self._geom_tables = {}  # unit -> hip.ReplaySetGeometry (per-track configs only)
         g0 = self._replays[0].geometry
         self.L, self.I, self.M, self.P = L, I, _, P = g0.L, g0.I, g0.M, g0.P
         self.n_cycles, self.n_log, self.n_rows = ([getattr(rp, k) for rp in self._replays] for k in ("n_cycles", "n_log", "n_rows"))
@@ -908,8 +963,44 @@ class ReplaySet:
             self._table = hip.ReplaySetTable(rows, L, guard, off * L, device=self._dev)
         # the super-track as a Replay whose scanned cycles are all n_super_cycles: the targets builders and the swarm run on it
         ec = dataclasses.replace(ecs[0], num_frames=(off - 1) * L + I + 1)
-        self._super = _SuperTrack(self, track, timing_config, ec, device)
+        self._super = _SuperTrack(self, track, tcs[0], ec, device)
         self._frames_table = None
+
+    @classmethod
+    def from_experiments(cls, tracks, experiment_configs, imaging_time_ms: float, pred_time_ms: float, moving_time_ms: float, camera_size_mm, micro_size_mm,
+                         **kwargs) -> "ReplaySet":
+        """The set of T recordings with one TimingConfig per recording, each built from that recording's ExperimentConfig and ONE set of times (ms) and
+        view sizes (mm), as the reference's notebooks build a TimingConfig per experiment: recordings at 88, 90 and 92 px/mm get cameras of 352, 360
+        and 368 px for the same 4 mm.  `kwargs`: frame_shapes, reach, device."""
+        ecs = list(experiment_configs)
+        tcs = [TimingConfig(ec, imaging_time_ms, pred_time_ms, moving_time_ms, camera_size_mm, micro_size_mm) for ec in ecs]
+        return cls(tracks, tcs, ecs, **kwargs)
+
+    def _geom(self, unit: str = "frame"):
+        """The geometry table the set's entry points take: None for a set built from one TimingConfig (every track the config's sizes: the entry
+        points without a table), else every track's camera and microscope with its change_unit factors of `unit` (built once per unit)."""
+        if not self._per_track:
+            return None
+        if unit not in self._geom_tables:
+            import torch
+
+            factors = Analysis(unit=unit).factors(self.timing_configs)
+            entries = [dict(cam=rp.geometry.cam, mic=rp.geometry.mic, factors=f) for rp, f in zip(self._replays, factors)]
+            with torch.cuda.device(self._dev):
+                self._geom_tables[unit] = hip.ReplaySetGeometry(entries, device=self._dev)
+        return self._geom_tables[unit]
+
+    def _mlp_bounds(self, max_speed: float, pred_frames):
+        """`mlp_clip_bound` of the super-track's cycles: one float for a set built from one TimingConfig, else a device float32 [n_super_cycles] tensor,
+        track t's bound on the cycles of its slot and guard."""
+        if not self._per_track:
+            return mlp_clip_bound(self.timing_config, max_speed, pred_frames)
+        import torch
+
+        ends = self.cyc_off[1:] + [self.n_super_cycles]
+        host = np.concatenate([np.full(e - o, mlp_clip_bound(tc, max_speed, pred_frames), dtype=np.float32)
+                               for o, e, tc in zip(self.cyc_off, ends, self.timing_configs)])
+        return torch.from_numpy(host).to(self._dev)
 
     def replay(self, t: int) -> Replay:
         """The plain `Replay` of track t: logs and per-row log output stay there (and the analysis and the precise error of one track alone)."""
@@ -1026,11 +1117,11 @@ class ReplaySet:
         if "precise" in buf:
             hip.replay_set_precise_objective(sp._cfg, self._table, self._frames_table, KINDS[targets.kind], int(targets.E), sp.track, targets.a, targets.b,
                                              targets.valid, sp._share, buf["pos"], buf["move"], 0, buf["track_summary"], buf["summary"], buf["scratch"],
-                                             buf["scratch"].numel(), kind, out, track_out, stop_dev, stream=sp._stream())
+                                             buf["scratch"].numel(), kind, out, track_out, stop_dev, stream=sp._stream(), geom=self._geom())
             return
         hip.replay_set_objective(sp._cfg, self._table, KINDS[targets.kind], int(targets.E), sp.track, targets.a, targets.b, targets.valid, sp._share, buf["pos"],
                                  buf["move"], buf["track_summary"], buf["summary"], buf["scratch"], buf["scratch"].numel(), kind, out, track_out, stop_dev,
-                                 stream=sp._stream())
+                                 stream=sp._stream(), geom=self._geom())
 
     def _check_targets(self, targets: Targets) -> int:
         return self._super._check_targets(targets)
@@ -1090,7 +1181,7 @@ class ReplaySet:
                    err=torch.empty((E, rows), dtype=torch.float64, device=dev) if per_row else None,
                    counts=torch.empty((E, rows, 2), dtype=torch.int32, device=dev) if counts else None)
         hip.replay_set_precise(sp._cfg, self._table, self._frames_table, E, sp.track, sp._share, buf["pos"], buf["move"], int(max_crop_px), out["err"],
-                               out["counts"], out["track"], out["pooled"], out["scratch"], out["scratch"].numel(), stream=stream)
+                               out["counts"], out["track"], out["pooled"], out["scratch"], out["scratch"].numel(), stream=stream, geom=self._geom())
         return out
 
     def _enqueue_analysis(self, spec: Analysis, E: int, pos, move, precise_rows, stream: int, max_lds_rows: int) -> SetAnalysisResult:
@@ -1110,7 +1201,7 @@ class ReplaySet:
         scratch = new((max(1, hip.replay_set_analysis_scratch_doubles(self._table, E, n, Q)),), f64)
         sp = self._super
         hip.replay_set_analyze(sp._cfg, spec.config(self.timing_config), self._table, E, sp.track, sp._share, pos, move, precise_rows, cols, q,
-                               int(max_lds_rows), per, pooled, scratch, scratch.numel(), stream=stream)
+                               int(max_lds_rows), per, pooled, scratch, scratch.numel(), stream=stream, geom=self._geom(spec.unit))
         row0, log0 = np.concatenate([[0], np.cumsum(self.n_rows)]), np.concatenate([[0], np.cumsum(self.n_log)])
         names = list(spec.columns)
         track = [AnalysisResult(names, q, self.n_rows[t], per[0][t], per[1][:, log0[t]:log0[t + 1]], per[2][:, log0[t]:log0[t + 1]], per[3][t], per[4][t],
@@ -1131,7 +1222,7 @@ class ReplaySet:
         with torch.cuda.device(self._dev):
             stream, buf = sp._stream(), self._objective_buffers(E)
             hip.replay_set_scan(sp._cfg, self._table, KINDS[targets.kind], E, sp.track, targets.a, targets.b, targets.valid, sp._share, buf["pos"], buf["move"],
-                                stream=stream)
+                                stream=stream, geom=self._geom())
             pr = self._enqueue_precise(E, buf, True, False, 0, stream) if precise else None
             return self._enqueue_analysis(spec, E, buf["pos"], buf["move"], pr["err"] if precise else None, stream, _max_lds_rows)
 
@@ -1146,9 +1237,9 @@ class ReplaySet:
         with torch.cuda.device(self._dev):
             stream, buf = sp._stream(), self._objective_buffers(E)
             hip.replay_set_scan(sp._cfg, self._table, KINDS[targets.kind], E, sp.track, targets.a, targets.b, targets.valid, sp._share, buf["pos"], buf["move"],
-                                stream=stream)
+                                stream=stream, geom=self._geom())
             hip.replay_set_rows(sp._cfg, self._table, E, sp.track, sp._share, buf["pos"], buf["move"], buf["track_summary"], buf["summary"], buf["scratch"],
-                                buf["scratch"].numel(), stream=stream)
+                                buf["scratch"].numel(), stream=stream, geom=self._geom())
             if precise:
                 pr = self._enqueue_precise(E, buf, per_row_errors or (spec is not None and "precise_error" in spec.columns), per_row_errors, _max_crop_px, stream)
                 ptrack, ppooled, perr, pcounts = pr["track"], pr["pooled"], pr["err"], pr["counts"]
